@@ -19,6 +19,10 @@ as `steady_state_it_per_s`.
 
 With N > 1 ranks the source cloud is sharded N ways (strong scaling of the same 100k ->
 100k job); the 30-double all-reduce per iteration runs over RCCL inside the library.
+
+`--dump-outputs DIR` writes what the last timed call returned (pose, error history, final
+error, iteration count, convergence flag) as DIR/<name>.npy in float64.  The inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -34,6 +38,27 @@ import numpy as np  # noqa: E402
 PEAK_FP32_TFLOPS = 157.3   # MI355X_MICROARCH.md: FP32 vector = FP32 MFMA (v_mfma_f32_16x16x4_f32)
 PEAK_BF16_TFLOPS = 2500.0  # MI355X_MICROARCH.md: dense bf16 MFMA (the pipe k_nn_coarse runs on)
 FLOP_PER_PAIR = 8.0        # 3 sub + 1 mul + 2 fma
+# the CPU leg runs at ~10 iterations/s on C3: it follows --steps only up to here, so that a long timed run does not
+# wait minutes on the host (--cpu-steps sets it explicitly)
+CPU_STEPS_MAX = 30
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(out_dir, res, hist):
+    """The arrays a caller of icpmi_align_device receives, as out_dir/<name>.npy (float64).  An error history of more
+    than DUMP_BYTES_MAX is cut to a fixed, seeded sample of its entries (kept in order)."""
+    hist = np.asarray(hist, dtype=np.float64)
+    if hist.nbytes > DUMP_BYTES_MAX - 4096:
+        keep = (DUMP_BYTES_MAX - 4096) // 8
+        hist = hist[np.sort(np.random.default_rng(0).choice(hist.size, keep, replace=False))]
+    arrays = {"transformation": np.array(res.transformation[:], dtype=np.float64).reshape(4, 4),
+              "error_history": hist,
+              "final_error": np.array([res.final_error], dtype=np.float64),
+              "num_iterations": np.array([res.num_iterations], dtype=np.float64),
+              "converged": np.array([res.converged], dtype=np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 _CPU_CHILD = r"""
@@ -191,7 +216,8 @@ def self_launch(n):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--steps", type=int, default=30,
+                    help="ICP iterations (steps) in each timed call; ms_per_step = the median call time / steps")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--points", type=int, default=100_000)
     ap.add_argument("--search", type=int, default=2,
@@ -207,13 +233,18 @@ def main():
     ap.add_argument("--force-dist", action="store_true",
                     help="rehearsal on one GPU: take the multi-rank code path (process group, RCCL communicator "
                          "inside the library, sharded kernels) with a world of 1")
-    ap.add_argument("--cpu-steps", type=int, default=None)
+    ap.add_argument("--cpu-steps", type=int, default=None,
+                    help="iterations of the CPU baseline's calls (default: --steps, at most %d)" % CPU_STEPS_MAX)
     ap.add_argument("--force-fallback-exchange", action="store_true",
                     help="rehearsal: pretend the library's RCCL communicator failed and exchange through torch.distributed")
     ap.add_argument("--rehearse-gloo", action="store_true",
                     help="rehearsal of the N-rank run where RCCL cannot form a communicator (several ranks sharing "
                          "one GPU): process group over gloo, the library's two exchanges through host callbacks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed call returned as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N ranks ourselves, one process
@@ -367,6 +398,8 @@ def main():
     res, hist, call_times, prof = series(value_search)
     elapsed = float(np.median(call_times))
     assert res.loop_iterations == args.steps, (res.loop_iterations, args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res, hist)
     comm = comm_block(prof)
     # per-stage breakdown from a second, untimed call with every stage bracketed by events.
     # Single-GPU runs only: the multi-rank line carries nothing that needs a second communicator.
@@ -485,7 +518,7 @@ def main():
             "roofline": roofline,
         }
         if not args.no_cpu_baseline and dist is None:
-            cb = cpu_baseline(src, tgt, args.cpu_steps or args.steps)
+            cb = cpu_baseline(src, tgt, args.cpu_steps or min(args.steps, CPU_STEPS_MAX))
             r = cb.pop("result")
             T = np.array(res.transformation[:]).reshape(4, 4)
             if r.loop_iterations == args.steps:

@@ -193,6 +193,31 @@ def test_bench_force_dist_proves_its_communicator():
     assert "error" not in de and de["comm"]["kind"] == "rccl" and de["history_max_abs_diff"] < 1e-9, de
 
 
+def test_bench_dump_outputs(tmp_path, oracle):
+    """`bench.py --dump-outputs DIR`: the last timed call's results, which are the oracle's on the same seeded input."""
+    import json
+    import subprocess
+    from lidar_slam_from_scratch_amd import synth
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "1",
+                          "--points", "20000", "--no-cpu-baseline", "--no-traffic", "--no-default-engine", "--repeats", "2",
+                          "--dump-outputs", str(tmp_path)], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
+                         timeout=600)
+    assert out.returncode == 0, out.stderr[-3000:]
+    d = json.loads(out.stdout.strip().splitlines()[-1])
+    assert d["steps"] == 5 and d["ms_per_step"] > 0
+    got = {n: np.load(str(tmp_path / (n + ".npy"))) for n in
+           ("transformation", "error_history", "final_error", "num_iterations", "converged")}
+    assert all(a.dtype == np.float64 for a in got.values())
+    src, tgt, _ = synth.c3_uniform(20000)
+    ref = oracle.icp_point_to_plane(src, tgt, max_iterations=5, tolerance=0.0, min_error=0.0)
+    dt, dr = synth.pose_delta(got["transformation"], ref.transformation)
+    assert dt <= 1e-9 and dr <= 1e-9, (dt, dr)
+    assert got["num_iterations"][0] == ref.num_iterations and bool(got["converged"][0]) == bool(ref.converged)
+    np.testing.assert_allclose(got["error_history"], ref.error_history, rtol=0, atol=1e-9)
+    assert got["final_error"][0] == d["final_error"] == got["error_history"][-1]
+
+
 def test_c4_eight_ranks_rehearsal(oracle):
     """BASELINE.json configs[3] as a whole: synthetic 1M -> 1M, the source cut into 8 shards of 125k rows,
     the normals of the 1M target computed in 8 row slices and all-gathered, 30 doubles all-reduced per

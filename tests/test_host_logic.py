@@ -75,3 +75,33 @@ def test_cpu_baseline_is_pinned_and_a_median_of_three():
     assert out["value"] == sorted(out["samples_it_per_s"])[1]
     assert out["pinned_cpu"] in os.sched_getaffinity(0) and out["affinity_seen_by_child"] == [out["pinned_cpu"]]
     assert out["loops"] == 2
+
+
+def test_bench_dump_outputs_writes_what_the_call_returned(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the last timed call's pose, error history, final error, iteration count and flag as
+    float64 .npy files; a history over the size budget is cut to the same seeded, ordered sample every time."""
+    import importlib.util
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+
+    class _Result:
+        transformation = list(np.arange(16.0))
+        converged, num_iterations, final_error = 1, 7, 0.25
+
+    hist = np.linspace(1.0, 0.25, 8)
+    bench.dump_outputs(str(tmp_path / "a"), _Result(), hist)
+    got = {f[:-4]: np.load(str(tmp_path / "a" / f)) for f in os.listdir(str(tmp_path / "a"))}
+    assert sorted(got) == ["converged", "error_history", "final_error", "num_iterations", "transformation"]
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert (got["transformation"] == np.arange(16.0).reshape(4, 4)).all() and (got["error_history"] == hist).all()
+    assert got["final_error"].tolist() == [0.25] and got["num_iterations"].tolist() == [7.0] and got["converged"].tolist() == [1.0]
+
+    monkeypatch.setattr(bench, "DUMP_BYTES_MAX", 4096 + 8 * 100)
+    long_hist = np.arange(1000.0)
+    bench.dump_outputs(str(tmp_path / "b"), _Result(), long_hist)
+    bench.dump_outputs(str(tmp_path / "c"), _Result(), long_hist)
+    b, c = (np.load(str(tmp_path / d / "error_history.npy")) for d in ("b", "c"))
+    assert b.size == 100 and (b == c).all() and (np.diff(b) > 0).all()
