@@ -115,6 +115,11 @@ typedef struct {
     int64_t coarse_minima_bytes;                     /* bytes this context holds for (row, split) coarse minima (6 B each): only the
                                                         stand-alone nearest-neighbour search and ICPMI_NN_BOUNDED=0 reserve any -- no
                                                         registration does (a state, not a counter: icpmi_reset_profile leaves it) */
+    int64_t nn_rows_listed;                          /* all-pairs engine with list reuse (ICPMI_NN_REUSE, default on): rows its bounded
+                                                        passes listed again -- the others kept their lists -- and ... */
+    int64_t nn_coarse_skipped;                       /* ... those passes whose coarse launch had no row to list, every workgroup left at
+                                                        once.  With list reuse nn_pairs counts the pairs of the blocks of rows that ran;
+                                                        both are counted on the device with profiling on only */
 } icpmi_profile;
 
 void icpmi_options_default(icpmi_options *opt);     /* device 0, normal_k 20 (icp.hpp:170), search AUTO or the

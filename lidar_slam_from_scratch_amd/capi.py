@@ -62,7 +62,8 @@ class Profile(C.Structure):
                 ("bounded_launches", C.c_int64),
                 ("nn_group_pairs", C.c_int64),
                 ("nn_group_pairs_run", C.c_int64),
-                ("exchange_ms", C.c_double), ("exchange_launches", C.c_int64), ("coarse_minima_bytes", C.c_int64)]
+                ("exchange_ms", C.c_double), ("exchange_launches", C.c_int64), ("coarse_minima_bytes", C.c_int64),
+                ("nn_rows_listed", C.c_int64), ("nn_coarse_skipped", C.c_int64)]
 
 
 MAX_RANKS_INFO = 64
@@ -584,3 +585,13 @@ class Context:
         p = Profile()
         self._check(self._lib.icpmi_get_profile(self._h, C.byref(p)))
         return {f[0]: getattr(p, f[0]) for f in Profile._fields_}
+
+    def nn_reuse_passes(self, cap=1024):
+        """Per bounded pass of the last registration (profiling on, all-pairs engine with list reuse): the rows its coarse
+        pass listed and the blocks of rows it ran, as two lists; empty without list reuse or profiling."""
+        fn = self._lib.icpmi_debug_nn_reuse
+        fn.restype = C.c_int64
+        fn.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_int64]
+        rows, blocks = (C.c_uint32 * cap)(), (C.c_uint32 * cap)()
+        n = min(int(fn(self._h, rows, blocks, cap)), cap)
+        return list(rows[:n]), list(blocks[:n])

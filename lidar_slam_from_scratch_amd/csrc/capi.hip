@@ -201,6 +201,8 @@ struct icpmi_ctx {
     int64_t grid_n = 0;                             // cells in grid_set
     unsigned *h_grid = nullptr;                     // pinned: the set's size on its way back
     unsigned long long *h_cnt = nullptr;            // pinned: the resolve's counters on their way back (profiling)
+    unsigned nn_epoch = 0;                          // list reuse: epoch of the last bounded pass queued (RowBounds, kernels.h)
+    std::vector<unsigned> reuse_rows, reuse_blocks; // profiling: per pass of the last registration, rows listed and coarse blocks run
     FilePrefetch *prefetch = nullptr;               // worker reading the next frame file (icpmi_stream_prefetch_file)
     // the target whose search structure and normals the context's buffers currently hold (prepare_target):
     // icpmi_stream_push prepares the NEXT frame's target while the caller is still busy with this frame's result
@@ -638,14 +640,48 @@ bool nn_bounded_enabled()
     return !(e && e[0] == '0');
 }
 
-// The per-row arrays of the bounded pass inside ctx->nn_lists (n rows)
+// ICPMI_NN_REUSE=0: every bounded pass of the all-pairs engine lists every row again (the form before list reuse; read at
+// every call like ICPMI_NN_BOUNDED).  ICPMI_NN_SKIN=<fraction of a row's sqrt(ub)>: the skin (tuning runs; RowBounds)
+bool nn_reuse_enabled()
+{
+    const char *e = getenv("ICPMI_NN_REUSE");
+    return !(e && e[0] == '0');
+}
+constexpr double kNnSkinDefault = 0.5, kNnLooseDefault = 8.0; // (the sweep: DESIGN.md, "List reuse")
+double nn_reuse_loose() // ICPMI_NN_LOOSE (tuning runs; RowBounds)
+{
+    if (const char *e = getenv("ICPMI_NN_LOOSE")) {
+        const double f = strtod(e, nullptr);
+        if (f == 0.0 || (f >= 1.0 && f <= 1e6)) return f;
+    }
+    return kNnLooseDefault;
+}
+double nn_reuse_skin()
+{
+    if (const char *e = getenv("ICPMI_NN_SKIN")) {
+        const double f = strtod(e, nullptr);
+        if (f >= 0.0 && f <= 1.0) return f;
+    }
+    return kNnSkinDefault;
+}
+
+// The per-row arrays of the bounded pass inside ctx->nn_lists (n rows), then list reuse's per-block epoch words and its
+// per-pass statistics
 struct NnListRows {
     double *ub;
     unsigned *ent;
     float *ubf, *sqf;
     int *cnt;
+    RowList *xb;
+    unsigned *epoch_w;
+    unsigned *stat_rows, *stat_blocks; // [kReuseStatPasses] each (profiling)
 };
-constexpr size_t kNnListRowBytes = sizeof(double) + 2 * sizeof(float) + sizeof(int) + sizeof(unsigned) * kNnEntCap;
+constexpr size_t kNnListRowBytes = sizeof(double) + 2 * sizeof(float) + sizeof(int) + sizeof(unsigned) * kNnEntCap + sizeof(RowList);
+constexpr int kReuseStatPasses = 1024; // (passes beyond are added to the last entry)
+size_t nn_list_bytes(int n)
+{
+    return kNnListRowBytes * (size_t)n + 64 + sizeof(unsigned) * ((size_t)n / kReuseRows + 2 + 2 * kReuseStatPasses);
+}
 NnListRows nn_list_rows(const icpmi_ctx *ctx, int n)
 {
     NnListRows r;
@@ -654,6 +690,10 @@ NnListRows nn_list_rows(const icpmi_ctx *ctx, int n)
     r.ubf = (float *)(r.ent + (size_t)kNnEntCap * n);
     r.sqf = r.ubf + n;
     r.cnt = (int *)(r.sqf + n);
+    r.xb = (RowList *)(((uintptr_t)(r.cnt + n) + 63) & ~(uintptr_t)63);
+    r.epoch_w = (unsigned *)(r.xb + n);
+    r.stat_rows = r.epoch_w + (size_t)n / kReuseRows + 2;
+    r.stat_blocks = r.stat_rows + kReuseStatPasses;
     return r;
 }
 
@@ -728,7 +768,8 @@ unsigned long long *groups_clock_buffer(icpmi_ctx *ctx)
 // in ctx->nn_lists (RowBounds, kernels.h; nn_bounded.h)
 int launch_nn_mfma(icpmi_ctx *ctx, const double *d_qry, int n, int m, int *d_idx, double *d_d2,
                    const IcpState *st, const double *d_tgt = nullptr, const double *d_nrm = nullptr,
-                   double *d_partials = nullptr, int pruned_pass = -1, bool bounded = false)
+                   double *d_partials = nullptr, int pruned_pass = -1, bool bounded = false, unsigned reuse_epoch = 0,
+                   int stat_pass = 0)
 {
     const int splits = ctx->nn_splits;
     int rc;
@@ -763,13 +804,19 @@ int launch_nn_mfma(icpmi_ctx *ctx, const double *d_qry, int n, int m, int *d_idx
                     hipLaunchKernelGGL((k_nn_coarse_groups<false, 8>), dim3(coarse_groups_grid(ctx, 8)), dim3(512), coarse_groups_lds(splits), ctx->stream,
                                        ICPMI_GROUPS_ARGS);
 #undef ICPMI_GROUPS_ARGS
-            } else if (coarse_half_units(ctx, n, splits)) {
-                constexpr int per = kCoarseQueries / kCoarseQT; // queries per workgroup with one tile per wave
-                hipLaunchKernelGGL((k_nn_coarse_bounded<1, kCoarseWaves>), dim3((n + per - 1) / per, splits), dim3(kCoarseThreads), 0,
-                                   ctx->stream, d_qry, n, (const uint4 *)ctx->bpack.p, frames, kl, st);
-            } else
-                hipLaunchKernelGGL((k_nn_coarse_bounded<kCoarseQT, kCoarseWaves>), dim3((n + kCoarseQueries - 1) / kCoarseQueries, splits),
-                                   dim3(kCoarseThreads), 0, ctx->stream, d_qry, n, (const uint4 *)ctx->bpack.p, frames, kl, st);
+            } else {
+                // list reuse (reuse_epoch != 0): only the blocks of rows that one of their rows marked for this pass do any work
+                const unsigned *epoch_w = reuse_epoch ? lr.epoch_w : nullptr;
+                unsigned *blocks_run = reuse_epoch && ctx->opt.profile ? lr.stat_blocks + std::min(stat_pass, kReuseStatPasses - 1) : nullptr;
+                if (coarse_half_units(ctx, n, splits)) {
+                    constexpr int per = kCoarseQueries / kCoarseQT; // queries per workgroup with one tile per wave
+                    hipLaunchKernelGGL((k_nn_coarse_bounded<1, kCoarseWaves>), dim3((n + per - 1) / per, splits), dim3(kCoarseThreads), 0,
+                                       ctx->stream, d_qry, n, (const uint4 *)ctx->bpack.p, frames, kl, st, epoch_w, reuse_epoch, blocks_run);
+                } else
+                    hipLaunchKernelGGL((k_nn_coarse_bounded<kCoarseQT, kCoarseWaves>), dim3((n + kCoarseQueries - 1) / kCoarseQueries, splits),
+                                       dim3(kCoarseThreads), 0, ctx->stream, d_qry, n, (const uint4 *)ctx->bpack.p, frames, kl, st, epoch_w,
+                                       reuse_epoch, blocks_run);
+            }
             ctx->prof.nn_coarse_blocks += (int64_t)((n + kCoarseQueries - 1) / kCoarseQueries) * splits;
         }
         // (the statistics: with one row in a hundred listing a second slot, most waves of a pass have something to add to the
@@ -785,7 +832,8 @@ int launch_nn_mfma(icpmi_ctx *ctx, const double *d_qry, int n, int m, int *d_idx
         default: hipLaunchKernelGGL(k_nn_resolve4_bounded<16>, dim3(resolve_blocks(n)), dim3(1024), 0, ctx->stream, ICPMI_BOUNDED_ARGS); break;
         }
 #undef ICPMI_BOUNDED_ARGS
-        ctx->prof.nn_pairs += (double)n * (double)m;
+        if (!reuse_epoch) ctx->prof.nn_pairs += (double)n * (double)m; // (a pass with list reuse: its blocks that ran, counted
+                                                                        // on the device -- profiling only -- and added after the call)
         ctx->prof.bounded_launches += 1;
         HIP_TRY(ctx, hipGetLastError());
         return ICPMI_OK;
@@ -1344,12 +1392,33 @@ int align_device(icpmi_ctx *ctx, const double *d_src, int64_t n_src64, const dou
     // all-pairs engine, the A/B and fuzz reference; the culled engine has no other form).
     const bool bounded_loop = fused && !small && n > 0 && resolve_waves(n) != -32 && (pruned || nn_bounded_enabled());
     if (pruned && !bounded_loop) return fail(ctx, ICPMI_ERR_ARG, "internal: the culled engine needs the bounded resolve kernels");
-    RowBounds rb{nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr};
+    // List reuse (RowBounds, kernels.h), all-pairs engine: a row keeps its list of slots from pass to pass while its bound and
+    // its drift from where the list was built show that a new list could hold nothing the kept one lacks, and the coarse
+    // pass runs only over the blocks of rows that were listed again.  A call's first pass lists every row (k_nn_prebound1
+    // marks its lists as not to be kept).  The culled engine keeps its own form.
+    const bool reuse = bounded_loop && !pruned && nn_reuse_enabled();
+    unsigned pass_epoch = 0; // the epoch the coming bounded pass runs under (0: every block runs)
+    RowBounds rb{};
+    NnListRows lr{};
     if (bounded_loop) {
-        if ((rc = reserve(ctx, ctx->nn_lists, kNnListRowBytes * (size_t)n + 64))) return rc;
-        const NnListRows lr = nn_list_rows(ctx, n);
+        if ((rc = reserve(ctx, ctx->nn_lists, nn_list_bytes(n)))) return rc;
+        lr = nn_list_rows(ctx, n);
         rb = RowBounds{d_tgt, idx, m, lr.ub, lr.ubf, lr.sqf, lr.cnt};
+        if (reuse) {
+            rb.xb = lr.xb;
+            rb.epoch_w = lr.epoch_w;
+            rb.skin = nn_reuse_skin();
+            rb.loose = nn_reuse_loose();
+            if (ctx->opt.profile) HIP_TRY(ctx, hipMemsetAsync(lr.stat_rows, 0, sizeof(unsigned) * 2 * kReuseStatPasses, s));
+        }
     }
+    // before each kernel that moves the rows for pass `next`: the epoch it marks the blocks of rows with
+    auto next_epoch = [&](int next) {
+        if (!reuse) return;
+        if (++ctx->nn_epoch == 0) ++ctx->nn_epoch; // (0 stands for "no reuse")
+        rb.epoch = ctx->nn_epoch;
+        rb.rebuilt = ctx->opt.profile ? lr.stat_rows + std::min(next, kReuseStatPasses - 1) : nullptr;
+    };
 
     // current_source = source * R0^T + t0^T (icp.hpp:174-176)
     if (n > 0 && !small) { // (an empty shard of a sharded run launches nothing over its rows; the small-cloud kernel moves them itself)
@@ -1398,8 +1467,11 @@ int align_device(icpmi_ctx *ctx, const double *d_src, int64_t n_src64, const dou
         const bool fuse_finish = !sharded && n > 0 && !final_pass && fuse_finish_enabled();
         if (n > 0 && fused) {
             if ((r2 = launch_nn_mfma(ctx, cur, n, m, idx, nullptr, st, d_tgt, nrm, partials,
-                                     pruned ? pass_no : -1, bounded_loop /* incumbents in idx, bounds in place: from k_nn_prebound1 or the kernel that moved the rows */))) return r2;
+                                     pruned ? pass_no : -1, bounded_loop /* incumbents in idx, bounds in place: from k_nn_prebound1 or the kernel that moved the rows */,
+                                     pass_epoch, pass_no))) return r2;
             ++pass_no;
+            if (!final_pass) next_epoch(pass_no);
+            pass_epoch = reuse && !final_pass ? rb.epoch : 0;
         } else if (n > 0) {
             if ((r2 = launch_nn(ctx, cur, n, d_tgt, m, idx, nullptr, st))) return r2;
         }
@@ -1557,6 +1629,25 @@ int align_device(icpmi_ctx *ctx, const double *d_src, int64_t n_src64, const dou
         ctx->prof.nn_group_pairs += (int64_t)ctx->h_cnt[4];
         // (the older pair of fields, in 512-row units like the all-pairs engine's)
         ctx->prof.nn_pruned_blocks += (int64_t)(ctx->h_cnt[4] - ctx->h_cnt[3]) / (kCoarseQueries / kGroupRows); // (16 tiles to a 512-row block)
+    }
+    ctx->reuse_rows.clear();
+    ctx->reuse_blocks.clear();
+    if (reuse && ctx->opt.profile && pass_no > 0) {
+        // list reuse, per pass: the rows listed (the first pass lists all) and the coarse blocks of rows that ran; the pairs
+        // of the blocks that ran are the pairs searched, and a pass none of whose blocks ran is a skipped coarse launch
+        const int np = std::min(pass_no, kReuseStatPasses);
+        ctx->reuse_rows.resize(np);
+        ctx->reuse_blocks.resize(np);
+        HIP_TRY(ctx, hipMemcpy(ctx->reuse_rows.data(), lr.stat_rows, sizeof(unsigned) * np, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(ctx->reuse_blocks.data(), lr.stat_blocks, sizeof(unsigned) * np, hipMemcpyDeviceToHost));
+        const int per = coarse_half_units(ctx, n, ctx->nn_splits) ? kCoarseQueries / kCoarseQT : kCoarseQueries;
+        ctx->reuse_rows[0] = (unsigned)n;
+        ctx->reuse_blocks[0] = (unsigned)((n + per - 1) / per);
+        for (int p = 0; p < np; ++p) {
+            ctx->prof.nn_rows_listed += ctx->reuse_rows[p];
+            if (p > 0) ctx->prof.nn_pairs += std::min((double)n, (double)ctx->reuse_blocks[p] * per) * (double)m;
+            if (p > 0 && ctx->reuse_blocks[p] == 0) ctx->prof.nn_coarse_skipped += 1;
+        }
     }
     if (ctx->ev_used > 4096) harvest_profile(ctx); // (otherwise when the profile is asked for)
     if (hs->error)
@@ -3141,11 +3232,10 @@ int icpmi_get_profile(icpmi_ctx *ctx, icpmi_profile *out)
 }
 
 #ifdef ICPMI_DEBUG_LOOP
-// diagnostic build only (scripts/loop_rows.py): the rows of the last registration as the loop left them -- matches,
-// moved coordinates, and the order the rows were taken in (0..n-1 when they were not sorted)
+// diagnostic build only (scripts/loop_rows.py): the lists of the last registration's bounded pass
 extern "C" int icpmi_debug_loop_lists(icpmi_ctx *ctx, double *ub_out, int32_t *cnt_out, uint32_t *ent_out, int64_t n)
 {
-    if (!ctx || !ctx->nn_lists.p || kNnListRowBytes * (size_t)n > ctx->nn_lists.cap) return ICPMI_ERR_ARG;
+    if (!ctx || !ctx->nn_lists.p || nn_list_bytes((int)n) > ctx->nn_lists.cap) return ICPMI_ERR_ARG;
     if (hipDeviceSynchronize() != hipSuccess) return ICPMI_ERR_HIP;
     const NnListRows lr = nn_list_rows(ctx, (int)n);
     if (hipMemcpy(ub_out, lr.ub, (size_t)n * 8, hipMemcpyDeviceToHost) != hipSuccess) return ICPMI_ERR_HIP;
@@ -3153,6 +3243,10 @@ extern "C" int icpmi_debug_loop_lists(icpmi_ctx *ctx, double *ub_out, int32_t *c
     if (hipMemcpy(ent_out, lr.ent, (size_t)n * 4 * kNnEntCap, hipMemcpyDeviceToHost) != hipSuccess) return ICPMI_ERR_HIP;
     return ICPMI_OK;
 }
+#endif
+
+// the rows of the last registration as the loop left them -- matches, moved coordinates, and the order the rows were taken
+// in (0..n-1 when they were not sorted): scripts/loop_rows.py, tests/test_gpu_nn_reuse.py
 extern "C" int icpmi_debug_loop_rows(icpmi_ctx *ctx, int32_t *idx_out, double *cur_out, uint32_t *perm_out, int64_t n)
 {
     if (!ctx || (size_t)n * sizeof(int) > ctx->idx.cap || (size_t)n * 24 > ctx->cur.cap) return ICPMI_ERR_ARG;
@@ -3166,7 +3260,20 @@ extern "C" int icpmi_debug_loop_rows(icpmi_ctx *ctx, int32_t *idx_out, double *c
     }
     return ICPMI_OK;
 }
-#endif
+
+// List reuse of the last registration with profiling on (RowBounds, kernels.h): per bounded pass, the rows listed by its
+// coarse pass and the blocks of rows that pass ran.  Returns the number of passes (at most `cap` are written), 0 without
+// list reuse or profiling.
+extern "C" int64_t icpmi_debug_nn_reuse(const icpmi_ctx *ctx, uint32_t *rows_out, uint32_t *blocks_out, int64_t cap)
+{
+    if (!ctx) return 0;
+    const int64_t np = (int64_t)ctx->reuse_rows.size();
+    for (int64_t p = 0; p < np && p < cap; ++p) {
+        if (rows_out) rows_out[p] = ctx->reuse_rows[p];
+        if (blocks_out) blocks_out[p] = ctx->reuse_blocks[p];
+    }
+    return np;
+}
 
 #if defined(ICPMI_COARSE_CLOCKS) || defined(ICPMI_SMALL_CLOCKS) || defined(ICPMI_GROUPS_CLOCKS)
 // diagnostic build only: the stamps of the last all-pairs 1-NN pass (4 words per workgroup:

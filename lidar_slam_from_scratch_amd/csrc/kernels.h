@@ -20,6 +20,7 @@
 #include <type_traits>
 
 #include "device_math.h"
+#include "list_reuse.h"
 
 namespace icpmi {
 
@@ -458,13 +459,35 @@ __global__ __launch_bounds__(64) void k_step(IcpState *st, double *history, int 
 // ---- moving the rows (icp.hpp:174-176, 225-226), with the next pass's bounds ---------------------------------------
 // What the bounded correspondence search (nn_bounded.h) wants to know about a moved row before it starts: the exact squared
 // distance to the target the row was matched with one pass ago, and its fp32 images rounded up.  tgt == nullptr: nothing.
+//
+// List reuse (xb != nullptr; nn_bounded.h, "Keeping a row's list"): a row's list of slots is built at a position x_b for a
+// listing radius R_b -- every slot that may hold a target within R_b of x_b is listed.  At a later pass the row sits at y,
+// d = |y - x_b|, and every target that can still be its nearest neighbour is within sqrt(ub) of y, hence within
+// sqrt(ub) + d of x_b: while sqrt(ub) + d <= R_b (with a margin for the fp64 roundings of both sides) the kept list is a
+// superset of what a new one would list, and the exact resolve returns the same bits from it.  Such a row keeps its
+// list (cnt / ent untouched) and gives the coarse pass a NaN threshold, under which nothing is listed; any other row is
+// listed again for R_b = sqrt(ub) + 2 skin and marks its coarse block with the coming pass's epoch, and a coarse block
+// that no row marked leaves at once (k_nn_coarse_bounded).
+constexpr int kNnEntCap = 8;   // list words per row of the bounded 1-NN pass (nn_mfma.h, nn_bounded.h)
+constexpr int kReuseRows = 256; // rows per epoch word: the rows of one workgroup of k_nn_coarse_bounded's half-unit form
+struct RowList {
+    double x, y, z; // where the row's list was built
+    double r;       // its listing radius R_b (NaN: the list is not to be kept, e.g. a call's first pass)
+};
 struct RowBounds {
     const double *tgt; // the target, caller's order
     const int *idx;    // the rows' matches of the pass just finished
     int m;
     double *ub;        // [n] |moved row - tgt[idx]|^2, +Inf without a match
-    float *ubf, *sqf;  // [n] (float)ub and its square root, rounded up; NaN / 0 for a row with a non-finite coordinate
-    int *cnt;          // [n] the row's list length, cleared here for the coming coarse pass
+    float *ubf, *sqf;  // [n] the coarse pass's radius^2 in fp32 and its square root, rounded up; NaN / 0 for a row with a
+                       // non-finite coordinate or one that keeps its list
+    int *cnt;          // [n] the row's list length, cleared here for a row listed again by the coming coarse pass
+    RowList *xb;       // [n] list reuse (null: every row is listed again, the form before list reuse)
+    unsigned *epoch_w; // [n / kReuseRows + 1] per block of rows: the epoch of the last pass any of its rows was listed for
+    unsigned epoch;    // the coming pass's epoch (never 0)
+    double skin;       // the skin as a fraction of the row's sqrt(ub)
+    double loose;      // a list built for more than `loose` x the radius it would be built for now is not kept (0: no limit)
+    unsigned *rebuilt; // profiling (or null): the coming pass's count of rows listed again
 };
 // B rows of one thread (i0, i0 + stride, ...): every load that does not depend on the pose -- the rows, their previous
 // matches' indices, then those targets -- is requested by load(), which the fused kernels call BEFORE their serial step, so
@@ -474,6 +497,8 @@ struct RowBatch {
     double x[B], y[B], z[B], tx[B], ty[B], tz[B];
     bool have[B];
     int j[B];
+    RowList lb[B]; // list reuse: where the row's list was built, and for which radius
+    int c[B];      // ... and its length
     // the rows and their previous matches' indices ...
     __device__ __forceinline__ void load_rows(const double *in, const RowBounds &rb, int i0, int stride, int n,
                                               const unsigned *__restrict__ perm = nullptr)
@@ -483,10 +508,13 @@ struct RowBatch {
             const int i = i0 + b * stride;
             x[b] = y[b] = z[b] = 0.0;
             j[b] = -1;
+            c[b] = 0;
+            lb[b] = RowList{0.0, 0.0, 0.0, __builtin_nan("")};
             if (i < n) {
                 const size_t ii = perm ? perm[i] : (unsigned)i;
                 x[b] = in[3 * ii], y[b] = in[3 * ii + 1], z[b] = in[3 * ii + 2];
                 if (rb.tgt) j[b] = rb.idx[i];
+                if (rb.xb) lb[b] = rb.xb[i], c[b] = rb.cnt[i];
             }
         }
     }
@@ -513,6 +541,7 @@ struct RowBatch {
         const double r00 = T[0], r01 = T[1], r02 = T[2], t0 = T[3];
         const double r10 = T[4], r11 = T[5], r12 = T[6], t1 = T[7];
         const double r20 = T[8], r21 = T[9], r22 = T[10], t2 = T[11];
+        unsigned listed = 0; // profiling: rows of this wave listed again (counted by the wave's first active lane)
 #pragma unroll
         for (int b = 0; b < B; ++b) {
             const int i = i0 + b * stride;
@@ -528,19 +557,42 @@ struct RowBatch {
                 // lists nothing.  No previous match (every target non-finite ...): +Inf, everything is listed.
                 double ub = __builtin_inf();
                 float ubf = __builtin_nanf(""), sqf = 0.f;
+                bool keep = false;
                 if (__builtin_isfinite(px) && __builtin_isfinite(py) && __builtin_isfinite(pz)) {
                     if (have[b]) ub = sqdist(tx[b], ty[b], tz[b], px, py, pz);
-                    ubf = (float)ub;
-                    ubf = (double)ubf < ub ? __uint_as_float(__float_as_uint(ubf) + 1u) : ubf; // (ub >= 0; Inf stays Inf)
-                    sqf = __builtin_amdgcn_sqrtf(ubf);
-                    sqf = sqf < 3.0e38f ? __uint_as_float(__float_as_uint(sqf) + 2u) : sqf;   // (1 ulp of v_sqrt_f32 and one more)
+                    double r2 = ub; // the radius^2 the coarse pass lists for
+                    if (rb.xb) {
+                        // the certificate (see RowBounds; list_reuse.h).  A list is not kept if it overflowed (cnt > kNnEntCap: the resolve's exhaustive path) or is empty (cnt == 0: a row beyond fp32's
+                        // range), nor if R_b is more than `loose` times the radius it would be built for now (a loose list:
+                        // slots the resolve would scan for nothing).  R_b NaN (first pass) fails every comparison.
+                        const double sq = __builtin_sqrt(ub);
+                        const double ex = px - lb[b].x, ey = py - lb[b].y, ez = pz - lb[b].z;
+                        const double d = __builtin_sqrt((ex * ex + ey * ey) + ez * ez);
+                        const double mx = px - x[b], my = py - y[b], mz = pz - z[b];
+                        const double rn = list_radius(sq, __builtin_sqrt((mx * mx + my * my) + mz * mz), rb.skin);
+                        keep = c[b] > 0 && c[b] <= kNnEntCap && list_certified(sq, d, lb[b].r) &&
+                               (rb.loose <= 0.0 || lb[b].r <= rb.loose * rn);
+                        if (!keep) {
+                            r2 = rn * rn;
+                            rb.xb[i] = RowList{px, py, pz, rn};
+                            rb.epoch_w[i / kReuseRows] = rb.epoch; // (equal values from every row of the block: plain stores)
+                        }
+                    }
+                    if (!keep) {
+                        ubf = (float)r2;
+                        ubf = (double)ubf < r2 ? __uint_as_float(__float_as_uint(ubf) + 1u) : ubf; // (r2 >= 0; Inf stays Inf)
+                        sqf = __builtin_amdgcn_sqrtf(ubf);
+                        sqf = sqf < 3.0e38f ? __uint_as_float(__float_as_uint(sqf) + 2u) : sqf;   // (1 ulp of v_sqrt_f32 and one more)
+                    }
                 }
                 rb.ub[i] = ub;
                 rb.ubf[i] = ubf;
                 rb.sqf[i] = sqf;
-                rb.cnt[i] = 0;
+                if (!keep) rb.cnt[i] = 0;
+                if (rb.rebuilt) listed += (unsigned)__popcll(__ballot(!keep && ubf == ubf));
             }
         }
+        if (rb.rebuilt && listed && (int)(threadIdx.x & 63) == __ffsll((long long)__ballot(1)) - 1) atomicAdd(rb.rebuilt, listed);
     }
 };
 constexpr int kRowBatch = 4;
@@ -638,7 +690,7 @@ __global__ __launch_bounds__(kFinishThreads) void k_finish_solve(const double *_
 __global__ __launch_bounds__(256) void k_transform(const double *in, double *out, int n,
                                                    const IcpState *__restrict__ st, int which,
                                                    int honour_done, const unsigned *__restrict__ perm = nullptr,
-                                                   const RowBounds rb = RowBounds{nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr})
+                                                   const RowBounds rb = RowBounds{})
 {
     if (honour_done && st->done) return;
     const double *T = which ? st->total : st->delta;

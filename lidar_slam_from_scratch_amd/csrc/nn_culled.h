@@ -261,6 +261,7 @@ __global__ __launch_bounds__(kPreThreads) void k_nn_prebound1(const double *__re
     const int bjc = have ? bj : 0;
     row_bound_store(rb, i, valid, px, py, pz, have, ICPMI_SX(sorted, ms, bjc), ICPMI_SY(sorted, ms, bjc), ICPMI_SZ(sorted, ms, bjc), lo, hi,
                     ubg);
+    if (rb.xb && valid) rb.xb[i].r = __builtin_nan(""); // (list reuse: a first pass's list is never kept -- RowBounds, kernels.h)
     if (gl.cnt) block_cull(cl, (i - lane) / kGroupRows, lo, hi, ubg, frames, nsplits, gl, lane);
 }
 

@@ -522,7 +522,6 @@ struct KnnLists {
     unsigned *ent;    // [rows][cap]
     int cap;          // words per row: kKnnEntCap (normal estimation), kNnEntCap (the ICP loop's bounded 1-NN pass)
 };
-constexpr int kNnEntCap = 8;
 
 // A operands.  Each lane builds the 16-slot bf16 row of ONE query (lane-per-query: coalesced fp64
 // loads, pieces computed once), rows go through `rows` (64 rows x 32 B of LDS private to the
@@ -877,13 +876,29 @@ __global__ __launch_bounds__(64 * WAVES) void k_nn_coarse_rows(
     coarse_unit<2, QT, WAVES, true>(lds, blockIdx.x, blockIdx.y, gridDim.y, rows, n, qstride, Bpack, frames, nullptr, nullptr, kl);
 }
 
-// all pairs, the moved source rows of an ICP pass that come with a bound (nn_bounded.h), MODE 2
+// all pairs, the moved source rows of an ICP pass that come with a bound (nn_bounded.h), MODE 2.
+// `epoch_w` (list reuse, RowBounds in kernels.h; null: every block runs): a workgroup whose rows' epoch words do not hold
+// this pass's `epoch` has no row to list -- every one of them keeps its list -- and leaves at once.  `blocks_run`
+// (profiling, or null): the blocks of rows that did run, counted by their split-0 workgroup.
 template <int QT, int WAVES>
 __global__ __launch_bounds__(64 * WAVES) void k_nn_coarse_bounded(
     const double *__restrict__ qry, int n, const uint4 *__restrict__ Bpack,
-    const SplitFrame *__restrict__ frames, KnnLists kl, const IcpState *__restrict__ st)
+    const SplitFrame *__restrict__ frames, KnnLists kl, const IcpState *__restrict__ st,
+    const unsigned *__restrict__ epoch_w = nullptr, unsigned epoch = 0, unsigned *__restrict__ blocks_run = nullptr)
 {
     if (st && st->done) return;
+    if (epoch_w) {
+        constexpr int kWords = kTile * QT * WAVES / kReuseRows;
+        static_assert(kWords * kReuseRows == kTile * QT * WAVES, "an epoch word covers whole workgroups' rows");
+        bool any = false;
+#pragma unroll
+        for (int w = 0; w < kWords; ++w) {
+            const int e = blockIdx.x * kWords + w;
+            any |= e * kReuseRows < n && epoch_w[e] == epoch;
+        }
+        if (!any) return;
+    }
+    if (blocks_run && blockIdx.y == 0 && threadIdx.x == 0) atomicAdd(blocks_run, 1u);
     __shared__ uint4 lds[CoarseLds<WAVES>::SCRATCH16];
     coarse_unit<2, QT, WAVES>(lds, blockIdx.x, blockIdx.y, gridDim.y, qry, n, 0, Bpack, frames, nullptr, nullptr, kl);
 }
