@@ -380,34 +380,18 @@ void harvest_profile(icpmi_ctx *ctx)
 
 // ---- kernel launch wrappers ------------------------------------------------------------
 
-// Smallest target for which AUTO takes the MFMA engine (and its k-NN path).  The environment
-// variable ICPMI_MFMA_MIN_TARGETS overrides it (tuning runs); both engines return the same answers.
-// Round 1 had 8192 here, chosen on the 1-NN pass alone; the exact k-NN kernel (one thread per row,
-// serial over the targets) costs 2.3 us per target point, so a 7.4k-point frame spent 17.6 ms in
-// normal estimation where the MFMA path takes 0.2 ms (scripts/threshold_sweep.py: 1.5k points
-// 4.15 -> 0.39 ms per registration, 8k points 17.7 -> 0.44 ms).
+// Smallest target for which AUTO takes the MFMA engine (and its k-NN path); both engines return the
+// same answers.  Round 1 had 8192 here, chosen on the 1-NN pass alone; the exact k-NN kernel (one
+// thread per row, serial over the targets) costs 2.3 us per target point, so a 7.4k-point frame spent
+// 17.6 ms in normal estimation where the MFMA path takes 0.2 ms (1.5k points 4.15 -> 0.39 ms per
+// registration, 8k points 17.7 -> 0.44 ms).
 // The MFMA engine still wins at 300 points (1.5 vs 2.6 ms for 50 iterations, 0.2 vs 0.8 ms of
 // normals); below 256 targets a split is mostly padding and the exact kernels are kept.
-#ifndef ICPMI_MFMA_MIN_TARGETS
-#define ICPMI_MFMA_MIN_TARGETS 256
-#endif
+constexpr int kMfmaMinTargets = 256;
 constexpr int kMfmaMinQueries = 64;
-int mfma_min_targets()
-{
-    static const int v = [] {
-        if (const char *e = getenv("ICPMI_MFMA_MIN_TARGETS")) {
-            char *end = nullptr;
-            const long x = strtol(e, &end, 10);
-            if (end != e && *end == '\0' && x >= 64 && x <= 100000000) return (int)x;
-        }
-        return (int)(ICPMI_MFMA_MIN_TARGETS);
-    }();
-    return v;
-}
 
 // Single-GPU loop: final sum, step and pose update in one launch (k_finish_step_transform).
-// ICPMI_FUSE_FINISH=0 keeps the two separate kernels (the A/B knob of scripts/ab_fuse_finish.sh);
-// ICPMI_FUSE_BLOCKS sets the number of workgroups (each repeats the final sum).
+// ICPMI_FUSE_FINISH=0 keeps the two separate kernels (the A/B knob of scripts/ab_fuse_finish.sh).
 bool fuse_finish_enabled()
 {
     static const bool v = [] {
@@ -416,25 +400,20 @@ bool fuse_finish_enabled()
     }();
     return v;
 }
+// Workgroups of the fused kernel, each of which repeats the final sum.  (Round 3: 128.  With the rows' bounds formed here
+// too (RowBounds) the row part is worth spreading over more CUs than the repeated sums cost: 32 / 64 / 128 / 256
+// workgroups 22.1 / 18.2 / 16.5 / 16.5 us at 100k rows.)
+constexpr int kFinishBlocksMax = 128;
 int finish_transform_blocks(int n)
 {
-    static const int cap = [] {
-        if (const char *e = getenv("ICPMI_FUSE_BLOCKS")) {
-            const long x = strtol(e, nullptr, 10);
-            if (x >= 1 && x <= 2048) return (int)x;
-        }
-        // (round 3: 128.  With the rows' bounds formed here too (RowBounds) the row part is worth spreading over more
-        // CUs than the repeated sums cost: 32 / 64 / 128 / 256 workgroups 22.1 / 18.2 / 16.5 / 16.5 us at 100k rows)
-        return 128;
-    }();
-    return std::max(1, std::min(cap, (n + kFinishThreads - 1) / kFinishThreads));
+    return std::max(1, std::min(kFinishBlocksMax, (n + kFinishThreads - 1) / kFinishThreads));
 }
 
 // Small clouds (the reference's real callers: filtered scans of 5-20k points): search, residuals and
 // pose update of the rows in ONE kernel per iteration (icp_small.h) when the target is at most
-// kSmallMaxSplits splits and the source at most this many rows (beyond, the general path's 512-query
+// kSmallMaxSplits splits and the source at most kSmallMaxQueries rows (beyond, the general path's 512-query
 // units amortise the operand reads better).  ICPMI_SMALL=0 switches the path off (A/B runs, parity
-// test); ICPMI_SMALL_MAX_QUERIES moves the row limit.
+// test).
 bool small_enabled()
 {
     static const bool v = [] {
@@ -443,17 +422,7 @@ bool small_enabled()
     }();
     return v;
 }
-int small_max_queries()
-{
-    static const int v = [] {
-        if (const char *e = getenv("ICPMI_SMALL_MAX_QUERIES")) {
-            const long x = strtol(e, nullptr, 10);
-            if (x >= 0 && x <= 100000000) return (int)x;
-        }
-        return 32768;
-    }();
-    return v;
-}
+constexpr int kSmallMaxQueries = 32768;
 // The small-cloud kernel's workgroup takes 32 rows through ALL splits, so its time grows with rows x splits where the
 // general path's grows with the units on the chip: measured (scripts/engine_threshold.py, profiles/r4_final/
 // engine_threshold.json: registrations of n -> n points by the three paths) it wins or ties up to 7 splits (14k points:
@@ -482,37 +451,18 @@ bool small_target(const icpmi_ctx *ctx)
 // pair count makes its fixed costs (Morton sort, operand packing, resolve) worthwhile.
 // AUTO: the exact fp64 kernels for tiny clouds; the MFMA engine from 256 targets -- over all pairs while the target is
 // a dozen splits or fewer (the small-cloud kernel of icp_small.h up to 8, the general kernels to 12), culled
-// (nn_culled.h) beyond: the same correspondences bit for bit, 90-98 % of the (row tile, split) pairs never evaluated (round 4; ICPMI_AUTO_CULLED=0 keeps AUTO on the
-// all-pairs engine everywhere, the A/B knob).
-bool auto_culled_enabled()
-{
-    static const bool v = [] {
-        const char *e = getenv("ICPMI_AUTO_CULLED");
-        return !(e && e[0] == '0' && e[1] == '\0');
-    }();
-    return v;
-}
-// (targets of more than this many splits; ICPMI_AUTO_CULLED_FROM moves it.  scripts/engine_threshold.py: at 10 splits the
-// culled engine's own fixed costs -- the rows' Morton sort, the lists -- still lose to the all-pairs kernels by 5-7 %, at 14
-// it wins by 7-13 %, at 49 by 2.3-3.1x)
-int auto_culled_from_splits()
-{
-    static const int v = [] {
-        if (const char *e = getenv("ICPMI_AUTO_CULLED_FROM")) {
-            const long x = strtol(e, nullptr, 10);
-            if (x >= 0 && x <= 1000000) return (int)x;
-        }
-        return 12;
-    }();
-    return v;
-}
+// (nn_culled.h) beyond: the same correspondences bit for bit, 90-98 % of the (row tile, split) pairs never evaluated (round 4).
+// (targets of more than kAutoCulledFrom splits.  scripts/engine_threshold.py: at 10 splits the culled engine's own fixed
+// costs -- the rows' Morton sort, the lists -- still lose to the all-pairs kernels by 5-7 %, at 14 it wins by 7-13 %, at 49
+// by 2.3-3.1x)
+constexpr int kAutoCulledFrom = 12;
 int engine_for(const icpmi_ctx *ctx, int m, int n_hint)
 {
     int engine = ctx->opt.search;
     const int splits = (m + kSplitTargets - 1) / kSplitTargets;
     if (engine == ICPMI_SEARCH_AUTO) {
-        engine = (m >= mfma_min_targets() && n_hint >= kMfmaMinQueries) ? ICPMI_SEARCH_MFMA_BF16 : ICPMI_SEARCH_EXACT_F64;
-        if (engine == ICPMI_SEARCH_MFMA_BF16 && splits > auto_culled_from_splits() && auto_culled_enabled()) engine = ICPMI_SEARCH_MFMA_PRUNED;
+        engine = (m >= kMfmaMinTargets && n_hint >= kMfmaMinQueries) ? ICPMI_SEARCH_MFMA_BF16 : ICPMI_SEARCH_EXACT_F64;
+        if (engine == ICPMI_SEARCH_MFMA_BF16 && splits > kAutoCulledFrom) engine = ICPMI_SEARCH_MFMA_PRUNED;
     }
     // (the culled coarse kernel keeps running sums over the splits in LDS: beyond kCullMaxSplits -- 6.3M targets -- all pairs)
     // (and the length of a split's list in 20 bits: fewer than 2^20 tiles of 32 rows)
@@ -576,60 +526,29 @@ int prepare_nn(icpmi_ctx *ctx, const double *d_tgt, int m, int n_hint)
 
 // when d_nrm/d_partials are given the resolve kernel also does k_reduce's work (one partial
 // row per resolve workgroup: resolve_blocks(n) rows)
-// Build-time overrides for A/B runs of the resolve kernels (see resolve_waves).
-#ifndef ICPMI_RESOLVE_WAVES
-#define ICPMI_RESOLVE_WAVES -1
-#endif
-#ifndef ICPMI_RESOLVE_Q32_FROM
-#define ICPMI_RESOLVE_Q32_FROM 2000000000 /* queries; above: k_nn_resolve<32>.  Off: at C3 (set to 81920) it
-                                             measured 55.7 us against 48.7 us (k_finish_step 11.7 against 13.3) */
-#endif
-// Which resolve kernel: 0 = k_nn_resolve<16> (16 queries per wave, 64 per workgroup); -32 = k_nn_resolve<32>
-// (32 per wave, 128 per workgroup); W > 0 = k_nn_resolve4<W> (4 queries per wave, 4 W per workgroup).
+// Which resolve kernel: 0 = k_nn_resolve<16> (16 queries per wave, 64 per workgroup); 8 = k_nn_resolve4<8> (4 queries
+// per wave, 32 per workgroup).  Measured (resolve + finish_step per pass, 100k targets): 8.8k / 12.5k / 25k queries
+// 34 -> 25 / 37 -> 27 / 41 -> 36 us with the quarter-wave kernel, 50k / 100k queries 46 -> 52 / 63 -> 80 us (its 2-4x
+// more partial rows and waves cost more than the shorter chains save).  32 queries per wave (k_nn_resolve<32>: all the
+// waves of a C3 pass on the chip at once) lost too: 55.7 us against 48.7 at C3, the longer chain per wave costs more.
 int resolve_waves(int n)
 {
-    if (ICPMI_RESOLVE_WAVES >= 0) return ICPMI_RESOLVE_WAVES;
-    // measured (scripts/sweep_resolve*.sh, resolve + finish_step per pass, 100k targets): 8.8k / 12.5k /
-    // 25k queries 34 -> 25 / 37 -> 27 / 41 -> 36 us with the quarter-wave kernel, 50k / 100k queries
-    // 46 -> 52 / 63 -> 80 us (its 2-4x more partial rows and waves cost more than the shorter chains save)
-    if (n <= 32768) return 8;
-    // 32 queries per wave would put all the waves of a C3 pass on the chip at once (3,125; the 6,250 of 16
-    // per wave need a second round at 5 per SIMD) -- and lost: the longer chain per wave costs more
-    return n <= ICPMI_RESOLVE_Q32_FROM ? 0 : -32;
+    return n <= 32768 ? 8 : 0;
 }
 // All-pairs coarse pass on few units (filtered scans: 14 query blocks x 4 splits): 256-query units -- one
-// 32-query tile per wave instead of two -- when even those fit the chip in one round.  The units' time is
-// their waves' time there, so half the work per wave is a shorter pass; once the chip is full the 512-query
-// unit amortises its staging and operand build over twice the results.  ICPMI_COARSE_HALF_UNITS=<units> moves
-// the switch (0: never).
+// 32-query tile per wave instead of two -- when even those fit the chip in one round (at most one unit per CU).
+// The units' time is their waves' time there, so half the work per wave is a shorter pass; once the chip is full
+// the 512-query unit amortises its staging and operand build over twice the results.
 bool coarse_half_units(const icpmi_ctx *ctx, int n, int splits)
 {
-    static const long limit = [] {
-        const char *e = getenv("ICPMI_COARSE_HALF_UNITS");
-        return e ? atol(e) : -1l;
-    }();
     const long units = (long)((n + kCoarseQueries - 1) / kCoarseQueries) * splits;
-    return units <= (limit >= 0 ? limit : (long)ctx->cu_count);
+    return units <= (long)ctx->cu_count;
 }
 int resolve_blocks(int n)
 {
     const int w = resolve_waves(n);
-    const int per = w > 0 ? 4 * w : (w == -32 ? kResolveWW * 32 : kResolveWW * kResolveQ);
+    const int per = w > 0 ? 4 * w : kResolveWW * kResolveQ;
     return (n + per - 1) / per;
-}
-
-// Diagnostic build (-DICPMI_COARSE_CLOCKS, scripts/coarse_clock.py): the all-pairs 1-NN pass stamps its clocks
-// into the (idle) slot-minimum buffer; icpmi_debug_coarse_clocks copies them out.  Null in the product build.
-float *coarse_clock_buffer(icpmi_ctx *ctx, int n, int splits)
-{
-#ifdef ICPMI_COARSE_CLOCKS
-    const size_t need = sizeof(unsigned long long) * 4 * (size_t)((n + kCoarseQueries - 1) / kCoarseQueries) * (size_t)splits;
-    if (reserve(ctx, ctx->slotmin, need) != ICPMI_OK) return nullptr;
-    return (float *)ctx->slotmin.p;
-#else
-    (void)ctx, (void)n, (void)splits;
-    return nullptr;
-#endif
 }
 
 // ICPMI_NN_BOUNDED=0: every pass of the ICP loop keeps its coarse minima and certifies afterwards (round 2's form)
@@ -641,29 +560,13 @@ bool nn_bounded_enabled()
 }
 
 // ICPMI_NN_REUSE=0: every bounded pass of the all-pairs engine lists every row again (the form before list reuse; read at
-// every call like ICPMI_NN_BOUNDED).  ICPMI_NN_SKIN=<fraction of a row's sqrt(ub)>: the skin (tuning runs; RowBounds)
+// every call like ICPMI_NN_BOUNDED).  The skin (a fraction of a row's sqrt(ub)) and the looseness limit: RowBounds.
 bool nn_reuse_enabled()
 {
     const char *e = getenv("ICPMI_NN_REUSE");
     return !(e && e[0] == '0');
 }
-constexpr double kNnSkinDefault = 0.5, kNnLooseDefault = 8.0; // (the sweep: DESIGN.md, "List reuse")
-double nn_reuse_loose() // ICPMI_NN_LOOSE (tuning runs; RowBounds)
-{
-    if (const char *e = getenv("ICPMI_NN_LOOSE")) {
-        const double f = strtod(e, nullptr);
-        if (f == 0.0 || (f >= 1.0 && f <= 1e6)) return f;
-    }
-    return kNnLooseDefault;
-}
-double nn_reuse_skin()
-{
-    if (const char *e = getenv("ICPMI_NN_SKIN")) {
-        const double f = strtod(e, nullptr);
-        if (f >= 0.0 && f <= 1.0) return f;
-    }
-    return kNnSkinDefault;
-}
+constexpr double kNnSkin = 0.5, kNnLoose = 8.0; // (the sweep: DESIGN.md, "List reuse")
 
 // The per-row arrays of the bounded pass inside ctx->nn_lists (n rows), then list reuse's per-block epoch words and its
 // per-pass statistics
@@ -728,41 +631,10 @@ size_t group_cnt_bytes(const icpmi_ctx *ctx)
     const size_t per = ((size_t)ctx->nn_splits + kGrpCntPad - 1) / kGrpCntPad * kGrpCntPad;
     return sizeof(unsigned) * 2 * per + 2 * sizeof(unsigned long long) + 4 * sizeof(unsigned);
 }
-// workgroups of k_nn_coarse_groups: the chip's resident set (two 8-wave workgroups per CU at 4 waves per SIMD); a
-// workgroup walks over the chunks blockIdx, blockIdx + grid, ...  ICPMI_GROUPS_GRID=<per CU> for tuning runs.
-// ICPMI_GROUPS_WAVES=4|8: pairs per workgroup (8: two workgroups per CU; 4: four, half the operand reuse, finer rounds)
-int coarse_groups_waves()
-{
-    static const int w = [] {
-        const char *e = getenv("ICPMI_GROUPS_WAVES");
-        return e && e[0] == '4' ? 4 : 8;
-    }();
-    return w;
-}
-int coarse_groups_grid(const icpmi_ctx *ctx, int waves)
-{
-    static const int per_cu = [] {
-        if (const char *e = getenv("ICPMI_GROUPS_GRID")) {
-            const long x = strtol(e, nullptr, 10);
-            if (x >= 1 && x <= 64) return (int)x;
-        }
-        return 0;
-    }();
-    return (per_cu ? per_cu : 16 / waves) * ctx->cu_count;
-}
+// workgroups of k_nn_coarse_groups (kCoarseWaves pairs each): the chip's resident set, two per CU at 4 waves per SIMD; a
+// workgroup starts on chunk blockIdx and takes its next ones from a counter (nn_culled.h)
+int coarse_groups_grid(const icpmi_ctx *ctx) { return 2 * ctx->cu_count; }
 size_t coarse_groups_lds(int splits) { return sizeof(unsigned) * (2 * (size_t)splits + 1); }
-// Diagnostic build (-DICPMI_GROUPS_CLOCKS, scripts/groups_clock.py): the culled coarse pass of the ICP loop stamps its
-// workgroups' phases into the (idle) slot-minimum buffer; icpmi_debug_coarse_clocks copies them out.  Null in the product build.
-unsigned long long *groups_clock_buffer(icpmi_ctx *ctx)
-{
-#ifdef ICPMI_GROUPS_CLOCKS
-    if (reserve(ctx, ctx->slotmin, sizeof(unsigned long long) * kGroupStamps * 64 * (size_t)ctx->cu_count) != ICPMI_OK) return nullptr;
-    return (unsigned long long *)ctx->slotmin.p;
-#else
-    (void)ctx;
-    return nullptr;
-#endif
-}
 
 // `bounded`: d_idx holds the rows' matches of the previous pass and the kernel that moved the rows has left their bounds
 // in ctx->nn_lists (RowBounds, kernels.h; nn_bounded.h)
@@ -793,17 +665,11 @@ int launch_nn_mfma(icpmi_ctx *ctx, const double *d_qry, int n, int m, int *d_idx
                 // group's bound is the largest of its rows'); pass p reads the lists counted in set p & 1 and clears the other
                 const GroupLists cur = group_lists(ctx, pruned_pass & 1), nxt = group_lists(ctx, (pruned_pass + 1) & 1);
                 const long groups = (n + kGroupRows - 1) / kGroupRows;
-#define ICPMI_GROUPS_ARGS                                                                                                              \
-    d_qry, n, (size_t)0, (const uint4 *)ctx->bpack.p, frames, splits, (const unsigned *)cur.items, cur.cap, (const unsigned *)cur.cnt, \
-        nxt.cnt, ctx->opt.profile ? group_stats(ctx) : (unsigned long long *)nullptr, (unsigned long long)(groups * splits), st, kl, \
-        group_work(ctx, pruned_pass & 1), group_work(ctx, (pruned_pass + 1) & 1), groups_clock_buffer(ctx)
-                if (coarse_groups_waves() == 4)
-                    hipLaunchKernelGGL((k_nn_coarse_groups<false, 4>), dim3(coarse_groups_grid(ctx, 4)), dim3(256), coarse_groups_lds(splits), ctx->stream,
-                                       ICPMI_GROUPS_ARGS);
-                else
-                    hipLaunchKernelGGL((k_nn_coarse_groups<false, 8>), dim3(coarse_groups_grid(ctx, 8)), dim3(512), coarse_groups_lds(splits), ctx->stream,
-                                       ICPMI_GROUPS_ARGS);
-#undef ICPMI_GROUPS_ARGS
+                hipLaunchKernelGGL((k_nn_coarse_groups<false, kCoarseWaves>), dim3(coarse_groups_grid(ctx)), dim3(kCoarseThreads),
+                                   coarse_groups_lds(splits), ctx->stream, d_qry, n, (size_t)0, (const uint4 *)ctx->bpack.p, frames, splits,
+                                   (const unsigned *)cur.items, cur.cap, (const unsigned *)cur.cnt, nxt.cnt,
+                                   ctx->opt.profile ? group_stats(ctx) : (unsigned long long *)nullptr, (unsigned long long)(groups * splits),
+                                   st, kl, group_work(ctx, pruned_pass & 1), group_work(ctx, (pruned_pass + 1) & 1));
             } else {
                 // list reuse (reuse_epoch != 0): only the blocks of rows that one of their rows marked for this pass do any work
                 const unsigned *epoch_w = reuse_epoch ? lr.epoch_w : nullptr;
@@ -825,12 +691,10 @@ int launch_nn_mfma(icpmi_ctx *ctx, const double *d_qry, int n, int m, int *d_idx
 #define ICPMI_BOUNDED_ARGS                                                                                                        \
     d_qry, n, (const double *)ctx->tgt_sorted.p, perm, m, ctx->nn_ms, splits, frames, (const double *)ub_row, (const int *)cnt_row, \
         (const unsigned *)ent_row, d_idx, ctx->opt.profile >= 2 ? counters : (unsigned long long *)nullptr, d_tgt, d_nrm, d_partials, st
-        switch (resolve_waves(n)) {
-        case 0: hipLaunchKernelGGL(k_nn_resolve_bounded, dim3(resolve_blocks(n)), dim3(64 * kResolveWW), 0, ctx->stream, ICPMI_BOUNDED_ARGS); break;
-        case 4: hipLaunchKernelGGL(k_nn_resolve4_bounded<4>, dim3(resolve_blocks(n)), dim3(256), 0, ctx->stream, ICPMI_BOUNDED_ARGS); break;
-        case 8: hipLaunchKernelGGL(k_nn_resolve4_bounded<8>, dim3(resolve_blocks(n)), dim3(512), 0, ctx->stream, ICPMI_BOUNDED_ARGS); break;
-        default: hipLaunchKernelGGL(k_nn_resolve4_bounded<16>, dim3(resolve_blocks(n)), dim3(1024), 0, ctx->stream, ICPMI_BOUNDED_ARGS); break;
-        }
+        if (resolve_waves(n) == 8)
+            hipLaunchKernelGGL(k_nn_resolve4_bounded<8>, dim3(resolve_blocks(n)), dim3(512), 0, ctx->stream, ICPMI_BOUNDED_ARGS);
+        else
+            hipLaunchKernelGGL(k_nn_resolve_bounded, dim3(resolve_blocks(n)), dim3(64 * kResolveWW), 0, ctx->stream, ICPMI_BOUNDED_ARGS);
 #undef ICPMI_BOUNDED_ARGS
         if (!reuse_epoch) ctx->prof.nn_pairs += (double)n * (double)m; // (a pass with list reuse: its blocks that ran, counted
                                                                         // on the device -- profiling only -- and added after the call)
@@ -850,7 +714,7 @@ int launch_nn_mfma(icpmi_ctx *ctx, const double *d_qry, int n, int m, int *d_idx
         } else {
             hipLaunchKernelGGL((k_nn_coarse<0, kCoarseQT, kCoarseWaves>), dim3((n + kCoarseQueries - 1) / kCoarseQueries, splits),
                                dim3(kCoarseThreads), 0, ctx->stream, d_qry, n, (const uint4 *)ctx->bpack.p, frames,
-                               (float2 *)ctx->coarse.p, coarse_clock_buffer(ctx, n, splits), st);
+                               (float2 *)ctx->coarse.p, (float *)nullptr, st);
         }
         ctx->prof.nn_coarse_blocks += (int64_t)((n + kCoarseQueries - 1) / kCoarseQueries) * splits;
     }
@@ -858,13 +722,10 @@ int launch_nn_mfma(icpmi_ctx *ctx, const double *d_qry, int n, int m, int *d_idx
 #define ICPMI_RESOLVE_ARGS                                                                                            \
     d_qry, n, (const double *)ctx->tgt_sorted.p, perm, m, ctx->nn_ms, (const float2 *)ctx->coarse.p, splits, frames,  \
         (const NnFrame *)ctx->nn_misc.p, d_idx, d_d2, counters, d_tgt, d_nrm, d_partials, blk_cnt, blk_list, st
-    switch (resolve_waves(n)) {
-    case 0: hipLaunchKernelGGL(k_nn_resolve<16>, dim3(resolve_blocks(n)), dim3(64 * kResolveWW), 0, ctx->stream, ICPMI_RESOLVE_ARGS); break;
-    case -32: hipLaunchKernelGGL(k_nn_resolve<32>, dim3(resolve_blocks(n)), dim3(64 * kResolveWW), 0, ctx->stream, ICPMI_RESOLVE_ARGS); break;
-    case 4: hipLaunchKernelGGL(k_nn_resolve4<4>, dim3(resolve_blocks(n)), dim3(256), 0, ctx->stream, ICPMI_RESOLVE_ARGS); break;
-    case 8: hipLaunchKernelGGL(k_nn_resolve4<8>, dim3(resolve_blocks(n)), dim3(512), 0, ctx->stream, ICPMI_RESOLVE_ARGS); break;
-    default: hipLaunchKernelGGL(k_nn_resolve4<16>, dim3(resolve_blocks(n)), dim3(1024), 0, ctx->stream, ICPMI_RESOLVE_ARGS); break;
-    }
+    if (resolve_waves(n) == 8)
+        hipLaunchKernelGGL(k_nn_resolve4<8>, dim3(resolve_blocks(n)), dim3(512), 0, ctx->stream, ICPMI_RESOLVE_ARGS);
+    else
+        hipLaunchKernelGGL(k_nn_resolve<16>, dim3(resolve_blocks(n)), dim3(64 * kResolveWW), 0, ctx->stream, ICPMI_RESOLVE_ARGS);
 #undef ICPMI_RESOLVE_ARGS
     ctx->prof.nn_pairs += (double)n * (double)m;
     HIP_TRY(ctx, hipGetLastError());
@@ -916,12 +777,9 @@ bool knn_lists_enabled()
 }
 bool sorted_normal_rows(const icpmi_ctx *ctx, int k, int m)
 {
-    return ctx->nn_engine == ICPMI_SEARCH_MFMA_BF16 && (ctx->nn_pruned || knn_lists_enabled()) && k <= 32 && m >= mfma_min_targets();
+    return ctx->nn_engine == ICPMI_SEARCH_MFMA_BF16 && (ctx->nn_pruned || knn_lists_enabled()) && k <= 32 && m >= kMfmaMinTargets;
 }
 
-#ifndef ICPMI_KNN_CHUNK_DEFAULT_MB
-#define ICPMI_KNN_CHUNK_DEFAULT_MB 1024
-#endif
 // k-NN lists of rows [row0,row1) of d_qry among the m points d_pts (kdtree.hpp:65-78): MFMA
 // coarse pass + exact resolve, or the exact fp64 kernel.  List of row i -> ctx->knn_idx[i * k ..],
 // closest first.  prepare_nn() must have run for d_pts.  d_qry == d_pts for normal estimation.
@@ -938,25 +796,13 @@ int launch_knn(icpmi_ctx *ctx, const double *d_qry, int nq_total, const double *
     hipStream_t s = ctx->stream;
     constexpr int BLOCK = 128;
     const size_t smem = (size_t)k * BLOCK * (sizeof(double) + sizeof(int));
-    const bool mfma = ctx->nn_engine == ICPMI_SEARCH_MFMA_BF16 && k <= 32 && m >= mfma_min_targets();
+    const bool mfma = ctx->nn_engine == ICPMI_SEARCH_MFMA_BF16 && k <= 32 && m >= kMfmaMinTargets;
     const unsigned *perm = mfma ? (const unsigned *)ctx->sort_keys.p + 3 * (size_t)m : nullptr;
     const double *qsep = d_qry == d_pts ? nullptr : d_qry; // the exact kernels read rows from d_pts unless told otherwise
     if (by_sorted_row && (!mfma || qsep)) return fail(ctx, ICPMI_ERR_ARG, "sorted-row lists need the MFMA engine's sorted target");
     if (mfma) {
         const int splits = ctx->nn_splits, nslots = splits * kCols;
-        // bound the slot-minimum buffer (2 B x nslots per row) by chunking the rows: ~1 GiB, or
-        // ~4 GiB when culling leaves most of it untouched (the pruned engine writes only the
-        // listed splits of a row, the layout stays dense)
-        // (ICPMI_KNN_CHUNK_MB: the all-pairs budget in MiB, for tuning runs.  The buffer is written by the MODE-1 coarse
-        // pass and read once by k_knn_resolve: a chunk that fits the 256 MB Infinity Cache beside the target never
-        // goes to HBM between the two)
-        static const long knn_budget = [] {
-            if (const char *e = getenv("ICPMI_KNN_CHUNK_MB")) {
-                const long x = strtol(e, nullptr, 10);
-                if (x >= 1 && x <= 16384) return x << 20;
-            }
-            return (long)ICPMI_KNN_CHUNK_DEFAULT_MB << 20;
-        }();
+        // bound the per-row buffer (the lists, or 2 B x nslots of slot minima) by chunking the rows: ~1 GiB
         // all-pairs engine, rows in the target's Morton order: bound first, lists instead of minima (knn_lists.h)
         // (pruned engine: the same lists on the units that survive the box test against the block's largest row bound)
         const bool lists = by_sorted_row; // (round 3's block lists over slot minima for the culled engine are gone)
@@ -965,7 +811,7 @@ int launch_knn(icpmi_ctx *ctx, const double *d_qry, int nq_total, const double *
         // icpmi_estimate_normals_rows) get their place in the sorted order from their Morton key (k_knn_prebound_q)
         const bool lists_q = !by_sorted_row && knn_lists_enabled();
         constexpr long kListRowBytes = sizeof(double) + 2 * sizeof(float) + sizeof(int) + sizeof(unsigned) * kKnnEntCap;
-        const long budget = (lists || lists_q) ? (1l << 30) : by_sorted_row ? (4l << 30) : knn_budget;
+        constexpr long budget = 1l << 30;
         long chunk = (budget / ((lists || lists_q) ? kListRowBytes : (long)nslots * 2)) / kCoarseQueries * kCoarseQueries; // 2 bytes per slot minimum (bf16)
         chunk = std::max<long>(kCoarseQueries, std::min<long>(chunk, ((long)rows + kCoarseQueries - 1) / kCoarseQueries * kCoarseQueries));
         if ((rc = reserve(ctx, ctx->slotmin, (lists || lists_q) ? (size_t)kListRowBytes * chunk : sizeof(unsigned short) * (size_t)chunk * nslots))) return rc;
@@ -993,17 +839,11 @@ int launch_knn(icpmi_ctx *ctx, const double *d_qry, int nq_total, const double *
                     HIP_TRY(ctx, hipMemsetAsync(ctx->grp_cnt.p, 0, group_cnt_bytes(ctx), s));
                     hipLaunchKernelGGL(k_knn_group_cull, dim3((waves + 15) / 16), dim3(1024), 0, s, sorted, m, ctx->nn_ms, (int)c0, nq,
                                        (const double *)t_row, frames, splits, gl);
-#define ICPMI_GROUPS_ARGS                                                                                                                   \
-    sorted + c0, nq, (size_t)ctx->nn_ms, (const uint4 *)ctx->bpack.p, frames, splits, (const unsigned *)gl.items, gl.cap,                  \
-        (const unsigned *)gl.cnt, (unsigned *)nullptr, (unsigned long long *)nullptr, 0ull, (const IcpState *)nullptr, kl,               \
-        group_work(ctx, 0), (unsigned *)nullptr
-                    if (coarse_groups_waves() == 4)
-                        hipLaunchKernelGGL((k_nn_coarse_groups<true, 4>), dim3(coarse_groups_grid(ctx, 4)), dim3(256), coarse_groups_lds(splits), s,
-                                           ICPMI_GROUPS_ARGS);
-                    else
-                        hipLaunchKernelGGL((k_nn_coarse_groups<true, 8>), dim3(coarse_groups_grid(ctx, 8)), dim3(512), coarse_groups_lds(splits), s,
-                                           ICPMI_GROUPS_ARGS);
-#undef ICPMI_GROUPS_ARGS
+                    hipLaunchKernelGGL((k_nn_coarse_groups<true, kCoarseWaves>), dim3(coarse_groups_grid(ctx)), dim3(kCoarseThreads),
+                                       coarse_groups_lds(splits), s, sorted + c0, nq, (size_t)ctx->nn_ms, (const uint4 *)ctx->bpack.p, frames,
+                                       splits, (const unsigned *)gl.items, gl.cap, (const unsigned *)gl.cnt, (unsigned *)nullptr,
+                                       (unsigned long long *)nullptr, 0ull, (const IcpState *)nullptr, kl, group_work(ctx, 0),
+                                       (unsigned *)nullptr);
                 } else if (coarse_half_units(ctx, nq, splits)) {
                     constexpr int per = kCoarseQueries / kCoarseQT;
                     hipLaunchKernelGGL((k_nn_coarse_rows<1, kCoarseWaves>), dim3((nq + per - 1) / per, splits), dim3(kCoarseThreads), 0,
@@ -1078,7 +918,7 @@ int launch_normals(icpmi_ctx *ctx, const double *d_pts, int m, int k, int row0, 
     Range range("icpmi:normals");
     StageTimer t(ctx, ST_NORMALS);
     if ((rc = launch_knn(ctx, d_pts, m, d_pts, m, k, row0, row1, by_sorted_row))) return rc;
-    const bool mfma = ctx->nn_engine == ICPMI_SEARCH_MFMA_BF16 && k <= 32 && m >= mfma_min_targets();
+    const bool mfma = ctx->nn_engine == ICPMI_SEARCH_MFMA_BF16 && k <= 32 && m >= kMfmaMinTargets;
     const unsigned *perm = mfma ? (const unsigned *)ctx->sort_keys.p + 3 * (size_t)m : nullptr;
     hipLaunchKernelGGL(k_normals_from_knn, dim3((rows + 255) / 256), dim3(256), 0, ctx->stream, d_pts, m, k, row0, row1,
                        (const int *)ctx->knn_idx.p, d_normals, by_sorted_row ? perm : (const unsigned *)nullptr,
@@ -1282,18 +1122,11 @@ int align_device(icpmi_ctx *ctx, const double *d_src, int64_t n_src64, const dou
     // with the MFMA engine the resolve kernel also forms the normal-equation partial sums
     const bool fused = ctx->nn_engine == ICPMI_SEARCH_MFMA_BF16;
     // small clouds: one kernel per iteration for the rows' work (icp_small.h), then k_finish_step
-    const bool small = !sharded_run && n > 0 && n <= small_max_queries() && small_target(ctx);
+    const bool small = !sharded_run && n > 0 && n <= kSmallMaxQueries && small_target(ctx);
     const int rblocks = small ? (n + kSmallQ - 1) / kSmallQ : (fused ? resolve_blocks(n) : reduce_blocks(ctx, n));
     // very many partial rows (a resolve workgroup leaves one per 64 queries) are first added in groups of kSumGroup by a
     // kernel of their own (k_sum_groups, kernels.h): the step kernels then sum rblocks2 rows
-    static const int sum_tree_from = [] {
-        if (const char *e = getenv("ICPMI_SUM_TREE_FROM")) {
-            const long x = strtol(e, nullptr, 10);
-            if (x >= 1) return (int)std::min<long>(x, 2000000000l);
-        }
-        return kSumTreeFrom;
-    }();
-    const bool sum_tree = rblocks >= sum_tree_from;
+    const bool sum_tree = rblocks >= kSumTreeFrom;
     const int rblocks2 = sum_tree ? (rblocks + kSumGroup - 1) / kSumGroup : 0;
     if ((rc = reserve(ctx, ctx->partials, sizeof(double) * kSumsStride * ((size_t)rblocks + (size_t)rblocks2)))) return rc;
     double *partials = (double *)ctx->partials.p;
@@ -1344,12 +1177,11 @@ int align_device(icpmi_ctx *ctx, const double *d_src, int64_t n_src64, const dou
     // (from 4,096 rows: below, the Morton sort of the rows costs a call more than its passes gain)
     // (not where ICPMI_SMALL=0 puts the general kernels in the small-cloud kernel's place: there they keep its order of rows,
     // hence its bits)
-    const bool small_regime = !sharded_run && n <= small_max_queries() && ctx->nn_splits <= small_max_splits();
+    const bool small_regime = !sharded_run && n <= kSmallMaxQueries && ctx->nn_splits <= small_max_splits();
     // (and only against targets of more than a dozen splits: at 10 splits -- 18k x 20k points, six iterations -- the rows' sort is
     // 55 us of a 0.45 ms registration whose coarse pass is 5 us; profiles/r4_final/c2_20k/timeline.txt)
     constexpr int kSortRowsFromSplits = 12;
-    const bool sorted_rows_loop = fused && !pruned && !small && !small_regime && n >= 4096 && ctx->nn_splits > kSortRowsFromSplits &&
-                                  resolve_waves(n) != -32;
+    const bool sorted_rows_loop = fused && !pruned && !small && !small_regime && n >= 4096 && ctx->nn_splits > kSortRowsFromSplits;
     size_t sort_bytes = 0;
     if (pruned || sorted_rows_loop) {
         HIP_TRY(ctx, sort_pairs_u32(nullptr, &sort_bytes, nullptr, nullptr, nullptr, nullptr, (unsigned)n, s));
@@ -1390,7 +1222,7 @@ int align_device(icpmi_ctx *ctx, const double *d_src, int64_t n_src64, const dou
     // the (row, split) buffer (6 B each: 2.9 GB at 1M x 1M) is not reserved by this function at all.  Every general-path
     // loop of the MFMA engines is bounded now, whatever its row order (ICPMI_NN_BOUNDED=0: round 2's form for the
     // all-pairs engine, the A/B and fuzz reference; the culled engine has no other form).
-    const bool bounded_loop = fused && !small && n > 0 && resolve_waves(n) != -32 && (pruned || nn_bounded_enabled());
+    const bool bounded_loop = fused && !small && n > 0 && (pruned || nn_bounded_enabled());
     if (pruned && !bounded_loop) return fail(ctx, ICPMI_ERR_ARG, "internal: the culled engine needs the bounded resolve kernels");
     // List reuse (RowBounds, kernels.h), all-pairs engine: a row keeps its list of slots from pass to pass while its bound and
     // its drift from where the list was built show that a new list could hold nothing the kept one lacks, and the coarse
@@ -1407,8 +1239,8 @@ int align_device(icpmi_ctx *ctx, const double *d_src, int64_t n_src64, const dou
         if (reuse) {
             rb.xb = lr.xb;
             rb.epoch_w = lr.epoch_w;
-            rb.skin = nn_reuse_skin();
-            rb.loose = nn_reuse_loose();
+            rb.skin = kNnSkin;
+            rb.loose = kNnLoose;
             if (ctx->opt.profile) HIP_TRY(ctx, hipMemsetAsync(lr.stat_rows, 0, sizeof(unsigned) * 2 * kReuseStatPasses, s));
         }
     }
@@ -1431,13 +1263,6 @@ int align_device(icpmi_ctx *ctx, const double *d_src, int64_t n_src64, const dou
                                frames, splits, pruned ? group_lists(ctx, 0) : GroupLists{nullptr, nullptr, 0});
     }
 
-    unsigned long long *small_clocks = nullptr;
-#ifdef ICPMI_SMALL_CLOCKS /* diagnostic build: the stamps of the last pass land in the (idle) slot-minimum buffer */
-    if (small) {
-        if ((rc = reserve(ctx, ctx->slotmin, sizeof(unsigned long long) * 2 * kSmallStamps * (size_t)rblocks))) return rc;
-        small_clocks = (unsigned long long *)ctx->slotmin.p;
-    }
-#endif
     bool small_first = true; // the small-cloud kernel's first pass applies the initial transform to the caller's rows
     auto iteration = [&](int final_pass, int *progress, int ticket) -> int {
         int r2;
@@ -1449,7 +1274,7 @@ int align_device(icpmi_ctx *ctx, const double *d_src, int64_t n_src64, const dou
     small_first ? d_src : (const double *)cur, cur, n, (const IcpState *)st, small_first ? 1 : 0, (const uint4 *)ctx->bpack.p,    \
         frames, splits, (const double *)ctx->tgt_sorted.p, (const double *)ctx->nrm_sorted.p,                                       \
         (const unsigned *)ctx->sort_keys.p + 3 * (size_t)m, m, ctx->nn_ms, d_tgt, (const double *)nrm, partials,                    \
-        (unsigned long long *)((char *)ctx->nn_misc.p + 128), small_clocks
+        (unsigned long long *)((char *)ctx->nn_misc.p + 128)
                 hipLaunchKernelGGL(k_icp_small, dim3(rblocks), dim3(kSmallThreads), 0, s, ICPMI_SMALL_ARGS);
 #undef ICPMI_SMALL_ARGS
                 small_first = false;
@@ -3231,20 +3056,6 @@ int icpmi_get_profile(icpmi_ctx *ctx, icpmi_profile *out)
     return ICPMI_OK;
 }
 
-#ifdef ICPMI_DEBUG_LOOP
-// diagnostic build only (scripts/loop_rows.py): the lists of the last registration's bounded pass
-extern "C" int icpmi_debug_loop_lists(icpmi_ctx *ctx, double *ub_out, int32_t *cnt_out, uint32_t *ent_out, int64_t n)
-{
-    if (!ctx || !ctx->nn_lists.p || nn_list_bytes((int)n) > ctx->nn_lists.cap) return ICPMI_ERR_ARG;
-    if (hipDeviceSynchronize() != hipSuccess) return ICPMI_ERR_HIP;
-    const NnListRows lr = nn_list_rows(ctx, (int)n);
-    if (hipMemcpy(ub_out, lr.ub, (size_t)n * 8, hipMemcpyDeviceToHost) != hipSuccess) return ICPMI_ERR_HIP;
-    if (hipMemcpy(cnt_out, lr.cnt, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess) return ICPMI_ERR_HIP;
-    if (hipMemcpy(ent_out, lr.ent, (size_t)n * 4 * kNnEntCap, hipMemcpyDeviceToHost) != hipSuccess) return ICPMI_ERR_HIP;
-    return ICPMI_OK;
-}
-#endif
-
 // the rows of the last registration as the loop left them -- matches, moved coordinates, and the order the rows were taken
 // in (0..n-1 when they were not sorted): scripts/loop_rows.py, tests/test_gpu_nn_reuse.py
 extern "C" int icpmi_debug_loop_rows(icpmi_ctx *ctx, int32_t *idx_out, double *cur_out, uint32_t *perm_out, int64_t n)
@@ -3274,16 +3085,5 @@ extern "C" int64_t icpmi_debug_nn_reuse(const icpmi_ctx *ctx, uint32_t *rows_out
     }
     return np;
 }
-
-#if defined(ICPMI_COARSE_CLOCKS) || defined(ICPMI_SMALL_CLOCKS) || defined(ICPMI_GROUPS_CLOCKS)
-// diagnostic build only: the stamps of the last all-pairs 1-NN pass (4 words per workgroup:
-// s_memtime, s_memrealtime at its start and at its end)
-int icpmi_debug_coarse_clocks(icpmi_ctx *ctx, unsigned long long *out, int64_t words)
-{
-    if (!ctx || !out || (size_t)words * 8 > ctx->slotmin.cap) return ICPMI_ERR_ARG;
-    if (hipMemcpy(out, ctx->slotmin.p, (size_t)words * 8, hipMemcpyDeviceToHost) != hipSuccess) return ICPMI_ERR_HIP;
-    return ICPMI_OK;
-}
-#endif
 
 } // extern "C"

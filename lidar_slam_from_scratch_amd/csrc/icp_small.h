@@ -6,7 +6,7 @@
 // (reads them back, exact scans, normal-equation terms) and the pose update of the points -- is
 // three dependent launches of a few microseconds each for ~2 us of matrix work, and the
 // intermediate is written and read again for nothing.  k_icp_small does an iteration's row work
-// in one launch and keeps the intermediate in LDS.  (Measured and dropped, scripts/small_clock.py:
+// in one launch and keeps the intermediate in LDS.  (Measured with in-kernel clocks and dropped:
 // four waves per workgroup with whole splits per wave -- fewer instructions in all, but one wave per
 // SIMD leaves every MFMA -> minimum dependency and every load exposed: 30k cycles against 21k; slot
 // scans by the whole wave with DPP reductions instead of quarter-waves: 6.4k cycles against 4.4k; the step of
@@ -65,31 +65,13 @@ __device__ __forceinline__ void small_merge(float &v1, float &v2, const float w1
     v2 = n2;
 }
 
-// Diagnostic build only (-DICPMI_SMALL_CLOCKS, scripts/small_clock.py): s_memtime stamps of the first and the last
-// wave of every workgroup at the kernel's phases, everything outstanding drained first (which perturbs what it measures).
-#ifdef ICPMI_SMALL_CLOCKS
-#define ICPMI_SMALL_STAMP(k)                                                   \
-    do {                                                                       \
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");            \
-        stamp[k] = __builtin_amdgcn_s_memtime();                               \
-    } while (0)
-#else
-#define ICPMI_SMALL_STAMP(k) do { } while (0)
-#endif
-constexpr int kSmallStamps = 12;
-
 __global__ __launch_bounds__(kSmallThreads) void k_icp_small(
     const double *in, double *cur, int n, const IcpState *__restrict__ st, int which,
     const uint4 *__restrict__ Bpack, const SplitFrame *__restrict__ frames, int splits,
     const double *__restrict__ sorted, const double *__restrict__ nrm_sorted, const unsigned *__restrict__ perm,
     int m, int ms, const double *__restrict__ tgt_orig, const double *__restrict__ nrm,
-    double *__restrict__ partials, unsigned long long *__restrict__ counters, unsigned long long *__restrict__ clocks)
+    double *__restrict__ partials, unsigned long long *__restrict__ counters)
 {
-#ifdef ICPMI_SMALL_CLOCKS
-    unsigned long long stamp[kSmallStamps];
-    for (int k = 0; k < kSmallStamps; ++k) stamp[k] = 0;
-    stamp[0] = __builtin_amdgcn_s_memtime();
-#endif
     __shared__ uint4 scratch[kSmallWaves][32 * 36 / 4]; // per wave: A rows, then the epilogue's transpose
     __shared__ float2 rec[kSmallMaxSplits * kSmallUnitsPerSplit][kSmallQ];
     __shared__ double jrow[kSmallQ][29];
@@ -151,7 +133,6 @@ __global__ __launch_bounds__(kSmallThreads) void k_icp_small(
             const uint4 u1 = make_uint4(zh | (zh << 16), zm | (zm << 16), one | (one << 16), one | (pnh << 16));
             afrag = __builtin_bit_cast(bf16x8, lane < 32 ? u0 : u1);
         }
-        ICPMI_SMALL_STAMP(1); // state, rows and the unit's operands here, A built
         f32x16 mn;
 #pragma unroll
         for (int r = 0; r < 16; ++r) mn[r] = kBig;
@@ -200,9 +181,7 @@ __global__ __launch_bounds__(kSmallThreads) void k_icp_small(
             for (int tt = 0; tt < kSmallUnitTiles; ++tt) b[tt] = tiles[tt * 64];
         }
     }
-    ICPMI_SMALL_STAMP(2); // this wave's records written
     __syncthreads(); // records complete; every wave has read the old rows of `in`
-    ICPMI_SMALL_STAMP(3);
     if (wave == 0 && lane < 32 && q0 + lane < n) {
         cur[3 * (q0 + lane)] = px;
         cur[3 * (q0 + lane) + 1] = py;
@@ -276,7 +255,6 @@ __global__ __launch_bounds__(kSmallThreads) void k_icp_small(
     double bd = ld;
     int bj = lj;
     row16_argmin(bd, bj);
-    ICPMI_SMALL_STAMP(4); // slots scanned
 
     // certificate: every split's record against its bound (resolve_certify without the first filter:
     // there are at most 16 splits, one per lane of the quarter)
@@ -310,7 +288,6 @@ __global__ __launch_bounds__(kSmallThreads) void k_icp_small(
             if (counters && lane == L) atomicAdd(&counters[w ? 1 : 0], 1ull);
         }
     }
-    ICPMI_SMALL_STAMP(5); // certificate done
 
     // 4. J row and b (icp.hpp:99-117) by the lane that holds the winner's point and normal; if the certificate
     // moved the winner out of the scanned slot (a few rows in a thousand) or the row has no neighbour
@@ -348,7 +325,6 @@ __global__ __launch_bounds__(kSmallThreads) void k_icp_small(
             for (int e = 0; e < 28; ++e) jrow[qi][e] = 0.0;
         }
     }
-    ICPMI_SMALL_STAMP(6); // rows of terms in LDS
     __builtin_amdgcn_wave_barrier();
     // k_nn_resolve4<8>'s order: a wave's four rows, then the waves in order
     if (lane < 28)
@@ -361,14 +337,6 @@ __global__ __launch_bounds__(kSmallThreads) void k_icp_small(
         for (int w = 1; w < kSmallWaves; ++w) v += red[w][e];
         partials[(size_t)blockIdx.x * kSumsStride + e] = v;
     }
-#ifdef ICPMI_SMALL_CLOCKS
-    ICPMI_SMALL_STAMP(7);
-    if (clocks && lane == 0 && (wave == 0 || wave == kSmallWaves - 1)) {
-        unsigned long long *o = clocks + ((size_t)blockIdx.x * 2 + (wave ? 1 : 0)) * kSmallStamps;
-        for (int k = 0; k < kSmallStamps; ++k) o[k] = stamp[k];
-        o[11] = __builtin_amdgcn_s_memrealtime();
-    }
-#endif
 }
 
 } // namespace icpmi

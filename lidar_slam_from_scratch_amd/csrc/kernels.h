@@ -255,8 +255,8 @@ __device__ inline void finish_sums(const double *__restrict__ partials, int nblo
 // writes the XCD's L2 back, an acquire drops the CU's L1, once per workgroup and seven workgroups to a CU), and the
 // fence-free sc1 form is measured for one workgroup per CU only (MI355X_MICROARCH.md).  A launch boundary costs ~3 us and
 // the step kernel's sum of C3's 1,563 rows 6.7: measured at C3, default engine, 30 iterations, same box: 9,614 -> 9,810
-// iterations/s with the threshold at 1,024 rows (ICPMI_SUM_TREE_FROM moves it; the sums' order of additions differs on
-// either side of it, inside every tolerance of the tests).
+// iterations/s with the threshold at 1,024 rows (the sums' order of additions differs on either side of it, inside every
+// tolerance of the tests).
 constexpr int kSumGroup = 16;
 constexpr int kSumTreeFrom = 1024;
 __global__ __launch_bounds__(256) void k_sum_groups(const double *__restrict__ rows, int nblocks, double *__restrict__ rows2,

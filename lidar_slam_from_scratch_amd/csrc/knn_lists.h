@@ -24,10 +24,9 @@
 
 namespace icpmi {
 
-#ifndef ICPMI_KNN_LIST_CAP
-#define ICPMI_KNN_LIST_CAP 128 /* 256 -> 128: 12 KB of LDS per workgroup instead of 23.5, eight waves per SIMD instead of six: 114.7 -> 108.2 us per 100k rows; a row with more candidates within its bound tightens the bound from those it holds and goes round again */
-#endif
-constexpr int kKnnListCap = ICPMI_KNN_LIST_CAP; // candidates per row held in LDS by k_knn_resolve_lists (more: the bound is tightened and the row redone)
+// candidates per row held in LDS by k_knn_resolve_lists (more: the bound is tightened and the row redone).  256 -> 128: 12 KB
+// of LDS per workgroup instead of 23.5, eight waves per SIMD instead of six: 114.7 -> 108.2 us per 100k rows
+constexpr int kKnnListCap = 128;
 constexpr int kKnnSlotCap = 192; // listed slots scanned per row
 constexpr int kKnnWindow = 256;  // sorted positions around a row that bound its k-th neighbour
 

@@ -36,10 +36,14 @@ namespace icpmi {
 constexpr int kNnSlotCap = 16; // listed slots scanned per row
 
 // Q = 16 queries per wave, the lane layout, workgroup shape and sums of k_nn_resolve<16>.
-#ifndef ICPMI_BOUNDED_OCC
-#define ICPMI_BOUNDED_OCC 5 /* waves per SIMD the register allocation must allow.  With a slot's loads requested as a batch (SlotBatch, nn_mfma.h) and all four rounds' state live the kernel wanted ~107 registers: at 5 (96, nothing spilled) 19.8 us per C3 pass, at 6 (40 dwords spilled) 24.2, at 7 (72, more spilled) 30.4; before the batch -- every candidate's loads next to their use, sixteen dependent trips per wave -- 7 was the best (22.1).  Round by round (one round's query, distances and indices live: 75 registers) it fits 7 without spills, and measures 19.3 at 5 or 6, 19.9 at 7, 22.0 at 8: 5 stays (scripts/ab_kernels.sh, same box) */
-#endif
-__global__ __launch_bounds__(64 * kResolveWW) __attribute__((amdgpu_waves_per_eu(ICPMI_BOUNDED_OCC, 8))) void k_nn_resolve_bounded(
+// Waves per SIMD the register allocation must allow: 5.  With a slot's loads requested as a batch (SlotBatch, nn_mfma.h) and
+// all four rounds' state live the kernel wanted ~107 registers: at 5 (96, nothing spilled) 19.8 us per C3 pass, at 6 (40
+// dwords spilled) 24.2, at 7 (72, more spilled) 30.4; before the batch -- every candidate's loads next to their use, sixteen
+// dependent trips per wave -- 7 was the best (22.1).  Round by round (one round's query, distances and indices live: 75
+// registers) it fits 7 without spills, and measures 19.3 at 5 or 6, 19.9 at 7, 22.0 at 8: 5 stays (scripts/ab_kernels.sh,
+// same box).
+constexpr int kBoundedOcc = 5;
+__global__ __launch_bounds__(64 * kResolveWW) __attribute__((amdgpu_waves_per_eu(kBoundedOcc, 8))) void k_nn_resolve_bounded(
     const double *__restrict__ qry, int n, const double *__restrict__ sorted, const unsigned *__restrict__ perm, int m, int ms,
     int splits, const SplitFrame *__restrict__ frames, const double *__restrict__ ub_row, const int *__restrict__ cnt_row,
     const unsigned *__restrict__ ent_row, int *__restrict__ idx /* in: previous match, out: this pass's */,
@@ -87,9 +91,6 @@ __global__ __launch_bounds__(64 * kResolveWW) __attribute__((amdgpu_waves_per_eu
     // lists nothing -- found by scripts/fuzz_bounded.py, seed 7368).
     const bool over = look && (cnt <= 0 || cnt > kNnEntCap || nsl > kNnSlotCap);
     const int nsl_eff = over ? 0 : nsl;
-#if defined(ICPMI_NNB_STOP) && ICPMI_NNB_STOP == 1 /* timing experiments only (WRONG results): where the kernel's time goes */
-    if (nsl_eff >= 0) { if (valid && sub == 0) idx[i] = first_slot + (int)bd; return; }
-#endif
 
     // exact evaluation of the listed slots, one query per quarter-wave and round (lane takes l16, l16+16, ...: coalesced),
     // the original indices beside the coordinates.  Round by round -- query, first slot, further slots, the quarter's
@@ -138,9 +139,6 @@ __global__ __launch_bounds__(64 * kResolveWW) __attribute__((amdgpu_waves_per_eu
         bj = take ? jo : bj;
     }
 
-#if defined(ICPMI_NNB_STOP) && ICPMI_NNB_STOP == 3
-    if (nsl_eff >= 0) { if (valid && own) idx[i] = bj + (int)bd; return; }
-#endif
     // rows whose list did not fit: every split whose bounding box is within the incumbent's distance, its slots culled
     // by their boxes (scan_split), nearest-first is not needed for correctness -- the radius only shrinks
     unsigned extra_splits = 0;
@@ -169,8 +167,8 @@ __global__ __launch_bounds__(64 * kResolveWW) __attribute__((amdgpu_waves_per_eu
             while (smask) {
                 const int sL = s0 + __ffsll((long long)smask) - 1;
                 smask &= smask - 1;
-                scan_split<ICPMI_RESOLVE_SCANBATCH>(sorted, perm, m, ms, reinterpret_cast<const double *>(frames + splits), sL, qx, qy,
-                                                    qz, qd, lane, qd, qj);
+                scan_split<kResolveScanBatch>(sorted, perm, m, ms, reinterpret_cast<const double *>(frames + splits), sL, qx, qy,
+                                              qz, qd, lane, qd, qj);
             }
         }
         if ((lane & (Q - 1)) == (L & (Q - 1))) {
@@ -180,9 +178,6 @@ __global__ __launch_bounds__(64 * kResolveWW) __attribute__((amdgpu_waves_per_eu
         if (lane == L) ++extra_splits;
     }
 
-#if defined(ICPMI_NNB_STOP) && ICPMI_NNB_STOP == 4
-    if (nsl_eff >= 0) { if (valid && own) idx[i] = bj + (int)bd; return; }
-#endif
     const unsigned extra_slots = (own && look && !over && nsl > 1) ? (unsigned)(nsl - 1) : 0u;
     resolve_finish<Q>(lane, wave, ql, own, i, valid, bd, bj, px, py, pz, m, idx, nullptr, counters, extra_slots, extra_splits,
                       tgt_orig, nrm, partials, -1, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0);
@@ -295,8 +290,8 @@ __global__ __launch_bounds__(64 * WAVES) void k_nn_resolve4_bounded(
             while (smask) {
                 const int sL = s0 + __ffsll((long long)smask) - 1;
                 smask &= smask - 1;
-                scan_split<ICPMI_RESOLVE4_SCANBATCH>(sorted, perm, m, ms, reinterpret_cast<const double *>(frames + splits), sL, qx, qy,
-                                                     qz, qd, lane, qd, qj);
+                scan_split<kResolve4ScanBatch>(sorted, perm, m, ms, reinterpret_cast<const double *>(frames + splits), sL, qx, qy,
+                                               qz, qd, lane, qd, qj);
             }
         }
         if ((lane >> 4) == (L >> 4)) {

@@ -30,7 +30,6 @@
 namespace icpmi {
 
 constexpr int kGroupRows = 32;          // rows per group: one 32-row MFMA tile (a wave of the coarse pass takes two, any two of a split's list)
-constexpr int kGroupStamps = 12;        // diagnostic build (-DICPMI_GROUPS_CLOCKS): words per workgroup of k_nn_coarse_groups
 constexpr int kCullMaxSplits = 3072;    // splits whose running sums fit the coarse kernel's LDS beside its 36 KiB of staging (2 x 3072 + 1 words of the 64 KiB a workgroup may have): 6.3M targets; beyond: all pairs
 static_assert(kGroupRows == kTile && kCoarseQT == 2, "a group is one tile; a wave of the coarse unit takes two");
 static_assert(sizeof(uint4) * CoarseLds<kCoarseWaves>::SCRATCH16 + sizeof(unsigned) * (2 * kCullMaxSplits + 1) + 64 <= 65536,
@@ -469,7 +468,7 @@ __global__ __launch_bounds__(1024) void k_knn_group_cull(const double *__restric
 // this kernel runs, so they are cleared here.
 // The chunks are handed out DYNAMICALLY: a workgroup starts on chunk blockIdx and takes its next one from a counter
 // (`work`: this pass's; `work_next`: the next pass's, cleared here).  With a static stride the two workgroups of a CU do not
-// share it evenly -- the SIMDs' arbiter serves the older workgroup's waves first (in-kernel stamps, scripts/groups_clock.py:
+// share it evenly -- the SIMDs' arbiter serves the older workgroup's waves first (in-kernel stamps:
 // first chunk 14.8 us in the workgroup that arrived first, 26 us in the other) -- so the 84 late workgroups that also
 // had a second chunk were a tail of 12 us behind everybody else: 42 us where 30 do.
 // Dynamic LDS: (2 nsplits + 1) words.
@@ -478,15 +477,8 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(4, 4
     const double *__restrict__ qry, int n, size_t qstride, const uint4 *__restrict__ Bpack, const SplitFrame *__restrict__ frames,
     int nsplits, const unsigned *__restrict__ items, int cap, const unsigned *__restrict__ cnt, unsigned *__restrict__ cnt_next,
     unsigned long long *__restrict__ stats /* [0] += pairs run, [1] += pairs of the pass (may be null) */, unsigned long long pairs_total,
-    const IcpState *__restrict__ st, const KnnLists kl, unsigned *__restrict__ work, unsigned *__restrict__ work_next,
-    unsigned long long *__restrict__ clocks = nullptr /* diagnostic build only */)
+    const IcpState *__restrict__ st, const KnnLists kl, unsigned *__restrict__ work, unsigned *__restrict__ work_next)
 {
-#ifdef ICPMI_GROUPS_CLOCKS /* scripts/groups_clock.py: 100 MHz stamps per workgroup -- entry, lists known, each chunk's ends, exit */
-    unsigned long long stamp[kGroupStamps];
-    for (int k = 0; k < kGroupStamps; ++k) stamp[k] = 0;
-    stamp[0] = __builtin_amdgcn_s_memrealtime();
-    int nchunk = 0;
-#endif
     __shared__ uint4 lds[CoarseLds<WAVES>::SCRATCH16];
     extern __shared__ unsigned dyn_lds[];
     // pre[s]: FULL chunks (2 WAVES entries) of the splits before s; word2[s]: bits 0-19 the length of split s's list, bits
@@ -543,9 +535,6 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(4, 4
     if (blockIdx.x == 0 && threadIdx.x == 0 && work_next) *work_next = 0u;
     __shared__ unsigned next_chunk;
     __syncthreads();
-#ifdef ICPMI_GROUPS_CLOCKS
-    stamp[1] = __builtin_amdgcn_s_memrealtime();
-#endif
     const unsigned nfull = s_full, total = s_total;
     // chunk c -> its split, and this wave's two list entries (requested, not waited for)
     auto lookup = [&](const unsigned c, int &s, bool &active, bool &active_b, uint2 &gv) {
@@ -579,32 +568,15 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(4, 4
         const int g = __builtin_amdgcn_readfirstlane((int)gv.x);
         // (a wave with one tile only -- the odd last entry of a list: the second tile's rows lie past the end, nothing of it is listed)
         const int gb = active_b ? __builtin_amdgcn_readfirstlane((int)gv.y) * kGroupRows : n;
-#ifdef ICPMI_GROUPS_CLOCKS
-        if (nchunk < 3) stamp[2 + 2 * nchunk] = __builtin_amdgcn_s_memrealtime();
-        if (nchunk == 0) stamp[8] = (unsigned long long)s | ((unsigned long long)__popcll(__ballot(active)) << 32);
-#endif
         coarse_unit_rows<2, kCoarseQT, WAVES, QSOA>(lds, g * kGroupRows, active, s, nsplits, qry, n, qstride, Bpack, frames, nullptr, nullptr,
-                                                    kl, 0, gb, false /* operands behind the A build: measured, nn_mfma.h */);
+                                                    kl, gb, false /* operands behind the A build: measured, nn_mfma.h */);
         __syncthreads(); // the epilogue's LDS is the next chunk's operand buffer; everybody has read next_chunk
-#ifdef ICPMI_GROUPS_CLOCKS
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        if (nchunk < 3) stamp[3 + 2 * nchunk] = __builtin_amdgcn_s_memrealtime();
-        ++nchunk;
-#endif
         // the next chunk is claimed only now, when this one is done: a workgroup that claimed ahead would sit on a chunk
         // while its faster neighbours have run out (the other workgroup of the CU fills the claim's round trip)
         if (threadIdx.x == 0) next_chunk = gridDim.x + atomicAdd(work, 1u);
         __syncthreads();
         c = next_chunk;
     }
-#ifdef ICPMI_GROUPS_CLOCKS
-    if (clocks && threadIdx.x == 0) {
-        stamp[10] = __builtin_amdgcn_s_memrealtime();
-        stamp[11] = (unsigned long long)nchunk;
-        stamp[9] = (unsigned long long)__builtin_amdgcn_s_getreg(63492) | ((unsigned long long)__builtin_amdgcn_s_getreg(63508) << 32); // HW_ID | XCC_ID
-        for (int k = 0; k < kGroupStamps; ++k) clocks[(size_t)blockIdx.x * kGroupStamps + k] = stamp[k];
-    }
-#endif
 }
 
 } // namespace icpmi

@@ -71,11 +71,7 @@ namespace icpmi {
 
 constexpr int kTile = 32;                         // queries / targets per MFMA tile
 constexpr int kCols = 32;                         // columns (slots) per split
-#ifndef ICPMI_SPLIT_TILES
-#define ICPMI_SPLIT_TILES 64
-#endif
-constexpr int kSplitTiles = ICPMI_SPLIT_TILES;    // target tiles per split (build-time tunable)
-static_assert(kSplitTiles % 64 == 0, "slots (kSplitTiles targets) are scanned in runs of 64; 32 was tried: slower and not supported");
+constexpr int kSplitTiles = 64;                   // target tiles per split
 constexpr int kSplitTargets = kSplitTiles * kTile;// targets per split
 constexpr int kSlotTargets = kSplitTiles;         // targets per (split, column) slot
 constexpr int kChunkTiles = 32;                   // tiles staged in LDS at a time (32 KiB)
@@ -84,10 +80,7 @@ constexpr int kCoarseWaves = 8;                   // waves per workgroup
 constexpr int kCoarseThreads = 64 * kCoarseWaves;
 constexpr int kCoarseQueries = kTile * kCoarseQT * kCoarseWaves; // queries per workgroup
 constexpr float kBig = 3.0e38f;
-#ifndef ICPMI_ARITH_BOUND
-#define ICPMI_ARITH_BOUND 52.0
-#endif
-constexpr double kArithBound = ICPMI_ARITH_BOUND; // x u a^2, see above (build-time override: A/B timing only)
+constexpr double kArithBound = 52.0;              // x u a^2, see above
 constexpr double kReprEps = 1.52587890625e-05 + 5.9604644775390625e-08; // 2^-16 + 2^-24
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -656,11 +649,7 @@ __device__ __forceinline__ void coarse_epilogue(float *sc, const int lane, const
                     unsigned mask = 0u;
 #pragma unroll
                     for (int c = 0; c < 16; ++c) mask |= min_raw(v[c] + pnq, kBig) <= thr_q ? (1u << c) : 0u;
-#if defined(ICPMI_TIMING_NO_ATOMIC) /* timing experiment only (WRONG results): what the returning atomic costs */
-                    const int pos = 0;
-#else
                     const int pos = atomicAdd(kl.cnt + iq, 1);
-#endif
                     if (pos < kl.cap) kl.ent[(size_t)iq * kl.cap + pos] = ((unsigned)s << 17) | ((unsigned)half << 16) | mask;
                 }
             }
@@ -723,22 +712,13 @@ __device__ __forceinline__ void coarse_unit_rows(uint4 *lds, const int q0, const
                                                  const uint4 *__restrict__ Bpack,
                                                  const SplitFrame *__restrict__ frames,
                                                  float2 *__restrict__ coarse, float *__restrict__ slotmin,
-                                                 const KnnLists kl = KnnLists{nullptr, nullptr, nullptr, nullptr, 0}, const int bx = 0,
+                                                 const KnnLists kl = KnnLists{nullptr, nullptr, nullptr, nullptr, 0},
                                                  const int q0b = -1 /* >= 0: the wave's second tile starts there (coarse_build_a) */,
                                                  const bool early_stage = true /* the first chunk of operands requested before the rows */)
 {
     constexpr int THREADS = 64 * WAVES;
     constexpr int CHUNK16 = kChunkTiles * 64;  // uint4 per staged chunk (32 KiB)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#ifdef ICPMI_COARSE_CLOCKS /* diagnostic build only (scripts/coarse_clock.py): the clock the chip holds inside this
-                              kernel = d(s_memtime) / d(s_memrealtime) x 100 MHz; the 1-NN pass gets a stamp buffer
-                              through the otherwise unused `slotmin` argument */
-    unsigned long long ck0 = 0, rk0 = 0;
-    if (MODE == 0 && slotmin && threadIdx.x == 0) {
-        ck0 = __builtin_amdgcn_s_memtime();
-        rk0 = __builtin_amdgcn_s_memrealtime();
-    }
-#endif
     // B operands: 2 chunks of 32 tiles through one 32 KiB LDS buffer, by LDS DMA (global_load_lds_dwordx4: a wave's 64
     // 16-byte pieces land at consecutive LDS slots, no register in between).  With `early_stage` the FIRST chunk is requested
     // here, before the rows are even loaded -- it depends on the split alone, and since the A operands no longer pass through
@@ -747,26 +727,13 @@ __device__ __forceinline__ void coarse_unit_rows(uint4 *lds, const int q0, const
     // the grid kernels (one unit per workgroup) 299.3 -> 291.7 us with it, 296-299 with the DMA behind the A operands, 299.7
     // with the permlane A build alone; the culled kernel (a workgroup walks over several chunks) 37.1 -> 38.4 with it and
     // 37.2 with the DMA behind the A operands: k_nn_coarse_groups passes false.
-#if defined(ICPMI_TIMING_B0) /* timing experiment only (WRONG results): every unit reads split 0's operands -- what L2 misses on them cost */
-    const uint4 *src = Bpack;
-#else
     const uint4 *src = Bpack + (size_t)s * (kSplitTiles * 64);
-#endif
-#ifndef ICPMI_COARSE_DMA
-#define ICPMI_COARSE_DMA 1 /* 1: LDS DMA; 0: through registers (A/B) */
-#endif
-#ifndef ICPMI_COARSE_DMA_EARLY
-#define ICPMI_COARSE_DMA_EARLY 1 /* 1: the first chunk requested before the rows; 0: behind the A operands as before (A/B) */
-#endif
     auto stage = [&](const int chunk) {
 #pragma unroll
-        for (int e = 0; e < CHUNK16 / THREADS; ++e) {
-            if (ICPMI_COARSE_DMA)
-                __builtin_amdgcn_global_load_lds(src + (size_t)chunk * CHUNK16 + threadIdx.x + e * THREADS, lds + e * THREADS + wave * 64, 16, 0, 0);
-            else lds[threadIdx.x + e * THREADS] = src[(size_t)chunk * CHUNK16 + threadIdx.x + e * THREADS];
-        }
+        for (int e = 0; e < CHUNK16 / THREADS; ++e)
+            __builtin_amdgcn_global_load_lds(src + (size_t)chunk * CHUNK16 + threadIdx.x + e * THREADS, lds + e * THREADS + wave * 64, 16, 0, 0);
     };
-    if (ICPMI_COARSE_DMA_EARLY && early_stage) stage(0);
+    if (early_stage) stage(0);
     const double c0 = frames[s].c[0], c1 = frames[s].c[1], c2 = frames[s].c[2];
 
     bf16x8 afrag[QT];
@@ -798,14 +765,9 @@ __device__ __forceinline__ void coarse_unit_rows(uint4 *lds, const int q0, const
 #pragma unroll
     for (int r = 0; r < 16; ++r) zero[r] = 0.f;
 
-#if defined(ICPMI_COARSE_PRIO) && ICPMI_COARSE_PRIO == 1 /* A/B: static priority for the younger half (MI355X_MICROARCH.md, two waves per SIMD, item 4) */
-    if (wave >= WAVES / 2) __builtin_amdgcn_s_setprio(1);
-#elif defined(ICPMI_COARSE_PRIO) && ICPMI_COARSE_PRIO == 2
-    if (wave & 1) __builtin_amdgcn_s_setprio(1);
-#endif
 #pragma unroll 1
     for (int chunk = 0; chunk < kSplitTiles / kChunkTiles; ++chunk) {
-        if (chunk > 0 || !(ICPMI_COARSE_DMA_EARLY && early_stage)) {
+        if (chunk > 0 || !early_stage) {
             if (chunk > 0) __syncthreads(); // the previous chunk is no longer needed
             stage(chunk);
         }
@@ -815,22 +777,9 @@ __device__ __forceinline__ void coarse_unit_rows(uint4 *lds, const int q0, const
     }
 
     __syncthreads(); // every wave is done with the B operands
-#if defined(ICPMI_TIMING_SKIP_EPILOGUE) /* timing experiment only (WRONG results) */
-    if (active && lane == 99)
-#else
     if (active)
-#endif
         coarse_epilogue<MODE, QT>(reinterpret_cast<float *>(lds) + wave * (32 * 36), lane, q0, s, nsplits, n, m, pn, coarse,
                                   slotmin, kl, thr, q0b);
-#ifdef ICPMI_COARSE_CLOCKS
-    if (MODE == 0 && slotmin && threadIdx.x == 0) {
-        unsigned long long *o = reinterpret_cast<unsigned long long *>(slotmin) + 4 * ((size_t)bx * nsplits + s);
-        o[0] = ck0;
-        o[1] = rk0;
-        o[2] = __builtin_amdgcn_s_memtime();
-        o[3] = __builtin_amdgcn_s_memrealtime();
-    }
-#endif
 }
 
 // One (query block, split) unit: wave w of block bx takes rows (bx * WAVES + w) * 32 QT ...
@@ -843,7 +792,7 @@ __device__ __forceinline__ void coarse_unit(uint4 *lds, const int bx, const int 
                                             const KnnLists kl = KnnLists{nullptr, nullptr, nullptr, nullptr, 0})
 {
     coarse_unit_rows<MODE, QT, WAVES, QSOA>(lds, (bx * WAVES + (int)(threadIdx.x >> 6)) * (kTile * QT), true, s, nsplits, qry, n, qstride,
-                                            Bpack, frames, coarse, slotmin, kl, bx);
+                                            Bpack, frames, coarse, slotmin, kl);
 }
 
 template <int WAVES>
@@ -1084,7 +1033,7 @@ __device__ __forceinline__ void scan_split(const double *__restrict__ sorted, co
 // of 49 on the 100k cloud -- get the per-split bound (frame loads + ~40 fp64 operations), and
 // the slots or splits under it are scanned exactly by the whole wave.
 template <int GROUP, int Q, int KEEP, int SCANBATCH>
-__device__ __forceinline__ void resolve_certify(const float (&pv)[KEEP > 0 ? KEEP : 1], // phase 1's first KEEP values per lane
+__device__ __forceinline__ void resolve_certify(const float (&pv)[KEEP], // phase 1's first KEEP values per lane
                                                 const int lane, const int sub, const bool valid, const int ic, const int n,
                                                 const double px, const double py, const double pz,
                                                 const float2 *__restrict__ coarse, const int nsplits,
@@ -1096,11 +1045,7 @@ __device__ __forceinline__ void resolve_certify(const float (&pv)[KEEP > 0 ? KEE
                                                 unsigned &extra_slots, unsigned &extra_splits)
 {
     const double sq = sqrt(bd);
-#ifdef ICPMI_NO_FIRST_FILTER /* A/B timing only */
-    const float tmax = 3.4028235e38f;
-#else
     const float tmax = all_splits_tau(px, py, pz, *gframe, bd, sq);
-#endif
     // a query with a NaN or infinite coordinate has no neighbour whatever is scanned (kdtree.hpp:125
     // never holds): it takes no part
     const bool look = valid && finite3(px, py, pz);
@@ -1109,7 +1054,7 @@ __device__ __forceinline__ void resolve_certify(const float (&pv)[KEEP > 0 ? KEE
         const int left = nact - base;
         const int kmax = left >= 32 * GROUP ? 32 : (left + GROUP - 1) / GROUP; // wave-uniform
         int k0 = 0;
-        if (KEEP > 0 && base == 0) { // the values phase 1 already loaded: no second trip to memory for them
+        if (base == 0) { // the values phase 1 already loaded: no second trip to memory for them
 #pragma unroll
             for (int k = 0; k < KEEP; ++k) {
                 const int e = k * GROUP + sub;
@@ -1139,11 +1084,6 @@ __device__ __forceinline__ void resolve_certify(const float (&pv)[KEEP > 0 ? KEE
                 whole = v.y <= tauf;                       // a second column is inside the bound
                 slot = !whole && s != bs && v.x <= tauf;
             }
-#if defined(ICPMI_TIMING_SKIP_SCANS) /* timing experiment only (WRONG results): 1 = no whole-split scans, 2 = nothing of the
-                                        certificate survives (its results are unused) */
-            if (ICPMI_TIMING_SKIP_SCANS >= 1) whole = false;
-            if (ICPMI_TIMING_SKIP_SCANS >= 2) slot = false;
-#endif
             unsigned long long pend = __ballot(whole || slot);
             while (pend) {                                 // rare; wave-uniform loop
                 const int L = __ffsll((long long)pend) - 1;
@@ -1174,10 +1114,7 @@ __device__ __forceinline__ void resolve_certify(const float (&pv)[KEEP > 0 ? KEE
     }
 }
 
-#ifndef ICPMI_RESOLVE_WW
-#define ICPMI_RESOLVE_WW 4 /* waves per workgroup = Q * WW queries per partial row of normal-equation terms */
-#endif
-constexpr int kResolveWW = ICPMI_RESOLVE_WW;
+constexpr int kResolveWW = 4; // waves per workgroup = Q * WW queries per partial row of normal-equation terms
 // The end of the Q-queries-per-wave resolve kernels (k_nn_resolve, k_nn_resolve_bounded): results out, counters, and the
 // fused residual + normal-equation terms.  (jspec, q*, n*): the matched target and normal gathered ahead for target
 // `jspec` (< 0: nothing was gathered).
@@ -1321,42 +1258,27 @@ __device__ __forceinline__ void resolve_finish(const int lane, const int wave, c
     }
 }
 
-// One wave resolves 16 (or 32) queries.  Lane = (query ql, sub-lane): the sub-lanes share the
+// One wave resolves 16 queries.  Lane = (query ql, sub-lane): the sub-lanes share the
 // bookkeeping of a query (each looks at its share of the splits) and each quarter-wave scans one
 // winning slot at a time (lane l16 takes sorted positions l16, l16+16, ... of the slot: three
 // coalesced streams), so 4 slots are in flight per wave.
 constexpr int kResolveQ = 16;
-// Waves per SIMD the register allocation must allow (A/B knob).  The kernel waits on memory three
+// Waves per SIMD the register allocation must allow: 5.  The kernel waits on memory three
 // quarters of the time (SQ_WAIT_ANY / SQ_WAVE_CYCLES = 0.77) and, at 64 queries per workgroup, C3
 // has 1,563 workgroups: at 5 per CU (82 VGPRs) 283 of them form a second round.  Forcing 6 / 7
-// waves per SIMD (80 / 72 VGPRs, 11 spilled at 7) measured 52 / 54 us against 48 us at 5: kept at 5.
-#ifndef ICPMI_RESOLVE_OCC
-#define ICPMI_RESOLVE_OCC 5
-#endif
-#ifndef ICPMI_RESOLVE_KEEP
-#define ICPMI_RESOLVE_KEEP 16 /* phase-1 values per lane kept for the certificate (64 splits at 16 queries per wave) */
-#endif
+// waves per SIMD (80 / 72 VGPRs, 11 spilled at 7) measured 52 / 54 us against 48 us at 5.
+constexpr int kResolveOcc = 5;
+constexpr int kResolveKeep = 16; // phase-1 values per lane kept for the certificate (64 splits at 16 queries per wave)
 // slots of a whole-split scan whose loads are in flight together (scan_split): what each kernel's
 // register budget allows
-#ifndef ICPMI_RESOLVE_SCANBATCH
-#define ICPMI_RESOLVE_SCANBATCH 1
-#endif
-#ifndef ICPMI_RESOLVE4_SCANBATCH
-#define ICPMI_RESOLVE4_SCANBATCH 2
-#endif
-#ifndef ICPMI_RESOLVE_UNROLL
-#define ICPMI_RESOLVE_UNROLL 4
-#endif
-#ifndef ICPMI_RESOLVE_RUNROLL
-#define ICPMI_RESOLVE_RUNROLL 4
-#endif
+constexpr int kResolveScanBatch = 1;
+constexpr int kResolve4ScanBatch = 2;
 
-// Q = queries per wave, 16 or 32: lane = (query ql = lane % Q, sub = lane / Q); the 64 / Q sub-lanes
-// of a query share its bookkeeping.  Q = 32 halves the waves of a pass (C3: 3,125, all resident
-// at once, where the 6,250 of Q = 16 need a second round at 5 waves per SIMD) at the price of a
-// longer chain per wave (8 scan rounds instead of 4).
+// Q = queries per wave: lane = (query ql = lane % Q, sub = lane / Q); the 64 / Q sub-lanes of a query
+// share its bookkeeping.  Only Q = 16 is instantiated: 32 (half the waves of a pass, a longer chain
+// per wave) measured slower.
 template <int Q>
-__global__ __launch_bounds__(64 * kResolveWW) __attribute__((amdgpu_waves_per_eu(ICPMI_RESOLVE_OCC, 8))) void k_nn_resolve(
+__global__ __launch_bounds__(64 * kResolveWW) __attribute__((amdgpu_waves_per_eu(kResolveOcc, 8))) void k_nn_resolve(
     const double *__restrict__ qry, int n,
                                                     const double *__restrict__ sorted,
                                                     const unsigned *__restrict__ perm, int m, int ms,
@@ -1392,14 +1314,14 @@ __global__ __launch_bounds__(64 * kResolveWW) __attribute__((amdgpu_waves_per_eu
 
     // phase 1: smallest coarse value over the splits (each sub-lane takes every SUBS-th split); the
     // first KEEP values of a lane stay in registers for the certificate's first filter
-    constexpr int KEEP = ICPMI_RESOLVE_KEEP;
+    constexpr int KEEP = kResolveKeep;
     static_assert(KEEP <= 32, "one bit of the certificate's candidate mask per kept value");
-    float pv[KEEP > 0 ? KEEP : 1];
+    float pv[KEEP];
     float best = kBig;
     int bs = 0;
     // (the loads unconditional -- a clamped split, the value dropped by a select -- so that they are all in flight together:
     // with a guard per load the compiler makes each a load-wait-compare of its own, KEEP dependent round trips)
-    int ps[KEEP > 0 ? KEEP : 1];
+    int ps[KEEP];
 #pragma unroll
     for (int k = 0; k < KEEP; ++k) {
         const int e = sub + SUBS * k, ec = e < nact ? e : 0;
@@ -1437,7 +1359,7 @@ __global__ __launch_bounds__(64 * kResolveWW) __attribute__((amdgpu_waves_per_eu
     // phase 2: exact evaluation of the winning slots, one query per quarter-wave and round
     double bd = 1.7976931348623157e308;
     int bj = 0x7fffffff;
-#pragma unroll ICPMI_RESOLVE_RUNROLL
+#pragma unroll 4
     for (int r = 0; r < ROUNDS; ++r) {
         const int src = quarter * ROUNDS + r; // the query this quarter scans now (a lane with sub == 0)
         const double qx = __shfl(px, src, 64), qy = __shfl(py, src, 64), qz = __shfl(pz, src, 64);
@@ -1473,7 +1395,7 @@ __global__ __launch_bounds__(64 * kResolveWW) __attribute__((amdgpu_waves_per_eu
 
     // phase 3: certificate (resolve_certify)
     unsigned extra_slots = 0, extra_splits = 0;
-    resolve_certify<SUBS, Q, KEEP, ICPMI_RESOLVE_SCANBATCH>(pv, lane, sub, valid, ic, n, px, py, pz, coarse, splits, slist, nact, frames, gframe, bs, sorted, perm, m, ms,
+    resolve_certify<SUBS, Q, KEEP, kResolveScanBatch>(pv, lane, sub, valid, ic, n, px, py, pz, coarse, splits, slist, nact, frames, gframe, bs, sorted, perm, m, ms,
                              bd, bj, extra_slots, extra_splits);
     resolve_finish<Q>(lane, wave, ql, sub == 0, i, valid, bd, bj, px, py, pz, m, idx, d2out, counters, extra_slots, extra_splits,
                       tgt_orig, nrm, partials, jspec, q0, q1, q2, n0, n1, n2);
@@ -1608,11 +1530,11 @@ __global__ __launch_bounds__(64 * WAVES) void k_nn_resolve4(const double *__rest
 
     // phase 1: smallest coarse value over the splits; ties to the lowest split.  The first KEEP4
     // values of a lane (64 splits) stay in registers for the certificate's first filter.
-    constexpr int KEEP4 = ICPMI_RESOLVE_KEEP > 0 ? 4 : 0;
-    float pv[KEEP4 > 0 ? KEEP4 : 1];
+    constexpr int KEEP4 = 4;
+    float pv[KEEP4];
     float best = kBig;
     int bs = 0;
-    int ps[KEEP4 > 0 ? KEEP4 : 1]; // (unconditional loads, all in flight together: see k_nn_resolve)
+    int ps[KEEP4]; // (unconditional loads, all in flight together: see k_nn_resolve)
 #pragma unroll
     for (int k = 0; k < KEEP4; ++k) {
         const int e = ql + 16 * k, ec = e < nact ? e : 0;
@@ -1685,7 +1607,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_nn_resolve4(const double *__rest
 
     // phase 3: certificate (resolve_certify)
     unsigned extra_slots = 0, extra_splits = 0;
-    resolve_certify<16, 4, KEEP4, ICPMI_RESOLVE4_SCANBATCH>(pv, lane, ql, valid, ic, n, px, py, pz, coarse, splits, slist, nact, frames, gframe, bs, sorted, perm, m, ms,
+    resolve_certify<16, 4, KEEP4, kResolve4ScanBatch>(pv, lane, ql, valid, ic, n, px, py, pz, coarse, splits, slist, nact, frames, gframe, bs, sorted, perm, m, ms,
                         bd, bj, extra_slots, extra_splits);
     resolve4_finish<WAVES>(lane, wave, ql, quarter, i, valid, bd, bj, px, py, pz, m, idx, d2out, counters, extra_slots, extra_splits,
                            tgt_orig, nrm, partials, jspec, q0, q1, q2, n0, n1, n2);
@@ -1706,17 +1628,13 @@ __global__ __launch_bounds__(64 * WAVES) void k_nn_resolve4(const double *__rest
 // with exact distance <= T is collected; the k smallest by (distance, original index) are
 // written closest first -- the order kdtree.hpp:72-76 returns and icp.hpp:41-51 sums in.
 constexpr int kKnnCap = 256;        // candidates per row held in LDS (more: the bound is tightened and the row redone)
-#ifndef ICPMI_KNN_BATCH
-#define ICPMI_KNN_BATCH 2 /* 1 / 2 / 4: 431 / 435 / 432 us (the kernel is issue bound, not latency bound) */
-#endif
-constexpr int kKnnBatch = ICPMI_KNN_BATCH; // flagged slots scanned per round (their loads overlap)
+constexpr int kKnnBatch = 2;        // flagged slots scanned per round (their loads overlap).  1 / 2 / 4: 431 / 435 / 432 us
+                                    // (the kernel is issue bound, not latency bound)
 constexpr int kKnnFlagCap = 192;    // slots listed for scanning per row and attempt (a sane bound flags ~10)
 constexpr int kKnnMaxSplits = 256;  // per-split bounds cached in LDS (512k targets); beyond: recomputed
-#ifndef ICPMI_KNN_REGSLOTS
-#define ICPMI_KNN_REGSLOTS 26 /* as fp32: 26 -> 119 VGPRs = 4 waves per SIMD, 32 -> 129 = 3 waves (430 vs 529 us on C3);
-                                 as bf16 pairs 107 / 115 VGPRs, 382 / 395 us: 26 kept */
-#endif
-constexpr int kKnnRegSlots = ICPMI_KNN_REGSLOTS;    // slot minima per lane kept in registers, two per dword (1664 slots = 106k targets)
+// slot minima per lane kept in registers, two per dword (1664 slots = 106k targets).  As fp32: 26 -> 119 VGPRs = 4 waves
+// per SIMD, 32 -> 129 = 3 waves (430 vs 529 us on C3); as bf16 pairs 107 / 115 VGPRs, 382 / 395 us: 26 kept
+constexpr int kKnnRegSlots = 26;
 
 // Ascending bitonic sort of one value per lane (21 compare-exchange steps); lane i ends up
 // with the i-th smallest.  Used for "k-th smallest of 64": a rank-by-counting loop costs 64
@@ -1891,9 +1809,6 @@ __global__ __launch_bounds__(256) void k_knn_resolve(const double *__restrict__ 
         }
         bslot = __shfl(lslot, bl, 64);
     }
-#if defined(ICPMI_KNN_STOP) && ICPMI_KNN_STOP == 1 /* timing experiment only: stop after the slot minima */
-    if (bslot >= 0) { if (lane == 0) knn_idx[(size_t)i * k] = bslot; return; }
-#endif
     // bound (b): exact scan of the best slot (kSlotTargets / 64 targets per lane); when a slot
     // is a single 64-run the 64 sorted positions after it (the next slot) also tighten the
     // bound -- those are collected later through the normal path
@@ -1918,13 +1833,11 @@ __global__ __launch_bounds__(256) void k_knn_resolve(const double *__restrict__ 
     double lbest = dloc[0];
 #pragma unroll
     for (int c = 1; c < kBnd; ++c) lbest = dloc[c] < lbest ? dloc[c] : lbest;
-#ifndef ICPMI_KNN_MORE_RUNS
-#define ICPMI_KNN_MORE_RUNS 1 /* measured on C3: 0 -> 668 us, 1 -> 555, 2 -> 564, 4 -> 588 */
-#endif
+    constexpr int kMoreRuns = 1; // measured on C3: 0 -> 668 us, 1 -> 555, 2 -> 564, 4 -> 588
     { // further runs of 64 sorted neighbours on both sides, for the bound only
         const int gb = gslot(bslot), j0 = (gb / kCols) * kSplitTargets + (gb % kCols) * kSlotTargets;
 #pragma unroll
-        for (int c = 0; c < ICPMI_KNN_MORE_RUNS; ++c) {
+        for (int c = 0; c < kMoreRuns; ++c) {
             const int ja = j0 - 64 * (c + 1) + lane, jb = j0 + 64 * (kBnd + c) + lane;
             if (ja >= 0) {
                 const double d = sqdist(ICPMI_SX(sorted, ms, ja), ICPMI_SY(sorted, ms, ja), ICPMI_SZ(sorted, ms, ja), px, py, pz);
@@ -1967,18 +1880,12 @@ __global__ __launch_bounds__(256) void k_knn_resolve(const double *__restrict__ 
         T = T < dmax ? T : dmax; // (NaN rows: T becomes dmax)
     }
 
-#if defined(ICPMI_KNN_STOP) && ICPMI_KNN_STOP == 2 /* timing experiment only: stop after the bounds */
-    if (T >= 0.0) { if (lane == 0) knn_idx[(size_t)i * k] = (int)T; return; }
-#endif
     // candidates: the best slot's targets under T, then every other slot under its split's
     // bound.  If more than kKnnCap turn up, the k-th smallest of those already held is a
     // tighter valid bound: collect again with it (a few rows per cloud).
     const int nsplits = LISTED ? nact : (nslots + kCols - 1) / kCols; // (local) splits this row looks at
     static_assert(kSlotTargets <= kKnnCap, "the best slot's targets must fit the candidate list");
     int total = 0;
-#if defined(ICPMI_KNN_STOP) && ICPMI_KNN_STOP == 4
-    int nf_last = 0, attempts_run = 0;
-#endif
     for (int attempt = 0; attempt < 4; ++attempt) {
         const double sq = sqrt(T);
         for (int sp = lane; sp < nsplits && sp < kKnnMaxSplits; sp += 64)
@@ -2045,9 +1952,6 @@ __global__ __launch_bounds__(256) void k_knn_resolve(const double *__restrict__ 
                 if (__ballot(cand)) list_flagged(cand, e + h);
             }
         }
-#if defined(ICPMI_KNN_STOP) && ICPMI_KNN_STOP == 4
-        nf_last = nf, attempts_run = attempt + 1;
-#endif
         const bool overflow = nf > kKnnFlagCap; // (only with a bound that rules nothing out)
         const int nfl = overflow ? kKnnFlagCap : nf;
         __builtin_amdgcn_wave_barrier();
@@ -2107,15 +2011,6 @@ __global__ __launch_bounds__(256) void k_knn_resolve(const double *__restrict__ 
         if (!(tnew < T)) break; // cannot tighten (e.g. hundreds of coincident points)
         T = tnew;
     }
-#if defined(ICPMI_KNN_STOP) && ICPMI_KNN_STOP == 4 /* diagnostic only: per row, the slots listed, the candidates found and T, in place of neighbours */
-    if (total >= 0) {
-        if (lane < k) knn_idx[(size_t)i * k + lane] = lane == 0 ? nf_last : lane == 1 ? total : lane == 2 ? attempts_run : 0;
-        return;
-    }
-#endif
-#if defined(ICPMI_KNN_STOP) && ICPMI_KNN_STOP == 3 /* timing experiment only: stop after collecting candidates */
-    if (total >= 0) { if (lane == 0) knn_idx[(size_t)i * k] = total; return; }
-#endif
     if (total > kKnnCap) { // still too many targets under the bound: hand the row to the exact kernel
         if (lane == 0) fb_list[atomicAdd(fb_count, 1)] = i;
         return;

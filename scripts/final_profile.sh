@@ -48,15 +48,12 @@ timeout -k 10 600 python scripts/run_sequence.py --make-synthetic /tmp/drive200 
 timeout -k 10 300 python scripts/run_sequence.py --data_dir /tmp/drive200 --frames 0:200 --no-prefetch > "$O/sequence_200_noprefetch.json" 2> /dev/null || exit 1
 # ... and with the map side of every frame (world points + occupancy grid), the cell set compared with the oracle's
 timeout -k 10 600 python scripts/run_sequence.py --data_dir /tmp/drive200 --frames 0:200 --oracle --map > "$O/sequence_200_map.json" 2> "$O/sequence_200_map.err" || exit 1
-# same-box A/B of the fused finish + step + transform kernel, and the clock inside the coarse kernel
+# same-box A/B of the fused finish + step + transform kernel
 timeout -k 10 300 python scripts/ab_fuse_finish.py > "$O/ab_fuse_finish.json" 2> "$O/ab_fuse_finish.err" || exit 1
-timeout -k 10 300 python scripts/coarse_clock.py 100000 3 > "$O/coarse_clock.json" 2> "$O/coarse_clock.err" || exit 1
 timeout -k 10 300 python scripts/ab_r1_r2.py > "$O/ab_r1_r2.json" 2> "$O/ab_r1_r2.err" || true   # needs scripts/ab_r1_libicp.so (round 1's library, built from git archive 0fd41fd)
-timeout -k 10 300 python scripts/threshold_sweep.py > "$O/threshold_sweep.json" 2> "$O/threshold_sweep.err" || exit 1
-# round 3: the small-cloud kernel against the general path (same box, alternating child processes), its phase clocks,
+# round 3: the small-cloud kernel against the general path (same box, alternating child processes),
 # the loop-closure verifications side by side, and the iteration-count sensitivity of the oracle loop (CPU)
 timeout -k 10 400 python scripts/ab_small.py > "$O/ab_small.json" 2> "$O/ab_small.err" || exit 1
-timeout -k 10 300 python scripts/small_clock.py 8000 > "$O/small_clock.json" 2> "$O/small_clock.err" || exit 1
 timeout -k 10 300 python scripts/batch_timing.py > "$O/batch_timing.json" 2> "$O/batch_timing.err" || exit 1
 timeout -k 10 900 python scripts/iteration_sensitivity.py > "$O/iteration_sensitivity.json" 2> "$O/iteration_sensitivity.err" || exit 1
 ICPMI_STREAM_STATS=1 ICPMI_PREFETCH_STATS=1 timeout -k 10 300 python scripts/run_sequence.py --data_dir /tmp/drive200 --frames 0:200 > /dev/null 2> "$O/stream_threads.txt" || true

@@ -2,9 +2,9 @@
 # Round 4's measurement set, run on the GPU box (two gpurun calls of <= 20 min).  Output under gpurun_out/final4/; the
 # summaries are copied into profiles/r4_final/ by scripts/collect_profiles_r4.py (see profiles/README.md).
 # usage: scripts/final_profile_r4.sh a   bench lines, kernel stats of the same command, counter passes for both engines' dominant
-#                                        kernels, secondary workloads, the culled kernel's in-kernel stamps, C2 at 20k
+#                                        kernels, secondary workloads, C2 at 20k
 #        scripts/final_profile_r4.sh b   engine thresholds, offsets, frame stream, small-cloud A/B, batch
-#        scripts/final_profile_r4.sh c   the all-pairs kernel's in-kernel clock, the small-cloud regime under rocprofv3, fuzz runs
+#        scripts/final_profile_r4.sh c   the small-cloud regime under rocprofv3, fuzz runs
 #        scripts/final_profile_r4.sh d   bench lines, kernel stats, shard shapes, C2 / C3 timelines, stream, small-cloud A/B, fuzz, soak: the part that
 #                                        moves with every late change, once more (no counter passes)
 cd "$GRAFT_REPO_ROOT"
@@ -27,7 +27,6 @@ timeout -k 10 300 python scripts/engine_compare.py 1000000 5 > "$O/engines_1m.js
 timeout -k 10 300 python scripts/engine_compare.py 4000000 2 > "$O/engines_4m.json" 2>&1 || exit 1
 timeout -k 10 300 python scripts/shard_overhead.py 0 > "$O/shard_overhead_default.json" 2>&1 || exit 1
 timeout -k 10 300 python scripts/shard_overhead.py 2 > "$O/shard_overhead_all_pairs.json" 2>&1 || exit 1
-timeout -k 10 200 python scripts/groups_clock.py 100000 12 > "$O/groups_clock.json" 2> "$O/groups_clock.err" || exit 1
 bash scripts/prof_c2.sh final4/c2_20k 0 0.3 > "$O/c2_20k.log" 2>&1 || exit 1
 bash scripts/quick_prof.sh final4/c3_default 0 100000 20 3 > /dev/null 2>&1 || exit 1
 python scripts/call_timeline.py "$O/c3_default/stats" > "$O/c3_default_timeline.txt" 2>&1
@@ -68,7 +67,6 @@ echo done d
 exit 0
 fi
 # part c
-timeout -k 10 300 python scripts/coarse_clock.py 100000 3 > "$O/coarse_clock.json" 2> "$O/coarse_clock.err" || exit 1
 mkdir -p "$O/small"
 [ -d /tmp/drive200 ] || timeout -k 10 300 python scripts/run_sequence.py --make-synthetic /tmp/drive200 --frames 0:200 > /dev/null 2>&1 || exit 1
 (cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/small/stats" -- python3 "$GRAFT_REPO_ROOT/scripts/run_sequence.py" --data_dir /tmp/drive200 --frames 0:40 > "$O/small/sequence_40_under_rocprof.json" 2> "$O/small/stats.err") || exit 1

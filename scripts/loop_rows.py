@@ -1,26 +1,17 @@
 """Diagnostic: the per-row matches the ICP loop's last pass left behind, bounded form (nn_bounded.h) against unbounded
-form, for one seed of scripts/fuzz_bounded.py -- a diagnostic build of the library (-DICPMI_DEBUG_LOOP, /tmp) exports
-them.  Every row whose match differs is printed with both distances and the brute-force truth.
+form, for one seed of scripts/fuzz_bounded.py (icpmi_debug_loop_rows exports them).  Every row whose match differs is
+printed with both distances and the brute-force truth.
     python scripts/loop_rows.py <seed> [iterations]"""
 import ctypes as C
 import os
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "scripts"))
-CSRC = os.path.join(ROOT, "lidar_slam_from_scratch_amd", "csrc")
-so = "/tmp/libicp_dbg.so"
-subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
-                       "-DICPMI_DEBUG_LOOP", "-c", "-o", "/tmp/capi_dbg.o", os.path.join(CSRC, "capi.hip")])
-if not os.path.exists(os.path.join(CSRC, "sort.o")):
-    subprocess.check_call(["make", "-s", "-C", CSRC, "sort.o"])
-subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", so, "/tmp/capi_dbg.o",
-                       os.path.join(CSRC, "sort.o"), "-ldl"])
 import numpy as np
 import torch  # noqa: F401
 from lidar_slam_from_scratch_amd import capi
-L = capi.load_library(so)
+L = capi.load_library()
 L.icpmi_debug_loop_rows.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.c_int64]
 from fuzz_bounded import make_case as make
 
@@ -39,17 +30,6 @@ for knob in ("1", "0"):
     rc = L.icpmi_debug_loop_rows(ctx._h, idx.ctypes.data_as(C.POINTER(C.c_int32)), cur.ctypes.data_as(C.POINTER(C.c_double)),
                                  perm.ctypes.data_as(C.POINTER(C.c_uint32)), n)
     assert rc == 0, rc
-    if knob == "1":   # the lists the last bounded pass read
-        L.icpmi_debug_loop_lists.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.c_int64]
-        ub = np.empty(n); cnt = np.empty(n, np.int32); ent = np.empty((n, 8), np.uint32)
-        if L.icpmi_debug_loop_lists(ctx._h, ub.ctypes.data_as(C.POINTER(C.c_double)), cnt.ctypes.data_as(C.POINTER(C.c_int32)),
-                                    ent.ctypes.data_as(C.POINTER(C.c_uint32)), n) == 0:
-            fin = np.isfinite(cur).all(1)
-            print("  lists: rows", n, "finite", int(fin.sum()), "cnt==0 among finite", int(((cnt == 0) & fin).sum()), "cnt>8", int((cnt > 8).sum()),
-                  "max |coordinate|", float(np.abs(cur[fin]).max()) if fin.any() else None, "ub range", float(np.nanmin(ub)), float(np.nanmax(ub)))
-            z = np.nonzero((cnt == 0) & fin)[0][:5]
-            for r in z:
-                print("   empty list: row", r, "p", cur[r], "ub", ub[r], "prev/now match", idx[r])
     out[knob] = (idx, cur, perm, hist)
     print("knob", knob, "history", [float("%.9g" % h) for h in hist])
     ctx.close()

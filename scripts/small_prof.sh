@@ -1,6 +1,6 @@
 #!/bin/bash
 # Kernel-time table of the small-cloud regime (40 frames of the synthetic drive, file -> pose), on the GPU box.
-# usage: scripts/small_prof.sh <tag>   (further environment, e.g. ICPMI_COARSE_HALF_UNITS=0, is inherited)
+# usage: scripts/small_prof.sh <tag>   (further environment is inherited)
 cd "$GRAFT_REPO_ROOT"
 O="$GRAFT_REPO_ROOT/gpurun_out/$1"
 mkdir -p "$O"

@@ -1,4 +1,4 @@
-"""Run a script (or `-m module`) of this repo against another build of the library -- A/B builds with -D knobs:
+"""Run a script (or `-m module`) of this repo against another build of the library (built from a copy of the tree):
     python scripts/with_lib.py <libicp_variant.so> scripts/run_sequence.py --data_dir ...
     python scripts/with_lib.py <libicp_variant.so> -m pytest tests -m gpu -q
 The variant is loaded in place of lidar_slam_from_scratch_amd/libicp_mi355x.so for this process only."""

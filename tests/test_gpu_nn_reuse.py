@@ -92,7 +92,6 @@ ctx.close()
 
 def _run(code, args, reuse, timeout=600):
     env = dict(os.environ, ICPMI_NN_REUSE=reuse, ICPMI_SMALL="0")
-    env.pop("ICPMI_NN_SKIN", None)
     r = subprocess.run([sys.executable, "-c", code, ROOT] + args, env=env, capture_output=True, text=True, timeout=timeout)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     return r.stdout
