@@ -14,6 +14,7 @@ OK = 0
 ERR_NULL, ERR_EMPTY_SOURCE, ERR_EMPTY_TARGET, ERR_CAPACITY = -1, -2, -3, -4
 ERR_HIP, ERR_RCCL, ERR_ARG, ERR_NO_DEVICE = -5, -6, -7, -8
 SEARCH_AUTO, SEARCH_EXACT_F64, SEARCH_MFMA_BF16, SEARCH_MFMA_PRUNED = 0, 1, 2, 3
+DEBUG_NO_IDX = 1   # icpmi_debug_loop_rows: the last pass's matches were not kept (small-cloud kernel)
 UNIQUE_ID_BYTES = 128
 
 EXPORTS = [
@@ -595,3 +596,17 @@ class Context:
         rows, blocks = (C.c_uint32 * cap)(), (C.c_uint32 * cap)()
         n = min(int(fn(self._h, rows, blocks, cap)), cap)
         return list(rows[:n]), list(blocks[:n])
+
+    def debug_loop_rows(self, n):
+        """The rows the last registration's last pass matched, as the loop left them: (idx, cur, perm, idx_valid) in the
+        loop's internal order of rows -- row r of `cur` is source row perm[r] moved by the pose of that pass, idx[r] its
+        match.  `n` must be the registration's row count.  idx_valid is False where the last pass's matches were never
+        written to memory (the small-cloud kernel's loop): idx is then all -1 and only cur, perm and the history speak."""
+        fn = self._lib.icpmi_debug_loop_rows
+        fn.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.c_int64]
+        idx, cur, perm = np.empty(n, np.int32), np.empty((n, 3)), np.empty(n, np.uint32)
+        rc = fn(self._h, idx.ctypes.data_as(C.POINTER(C.c_int32)), cur.ctypes.data_as(C.POINTER(C.c_double)),
+                perm.ctypes.data_as(C.POINTER(C.c_uint32)), n)
+        if rc not in (OK, DEBUG_NO_IDX):
+            raise IcpError(rc, "icpmi_debug_loop_rows: n is not the last registration's row count")
+        return idx, cur, perm, rc == OK

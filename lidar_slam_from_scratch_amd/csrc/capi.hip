@@ -223,6 +223,11 @@ struct icpmi_ctx {
     DevBuf sort_keys, sort_tmp, tgt_sorted, frames; // Morton pre-pass: keys/values, sorted copy, split frames
     DevBuf bpack, coarse, bbox_part, nn_misc; // MFMA engine: operands, coarse minima, frame + counters
     DevBuf src_sort;                          // Morton order of the source rows (the loop's internal order)
+    // the rows the last registration left in cur / idx (icpmi_debug_loop_rows): their count (-1: no registration has
+    // completed since), whether idx holds the last pass's matches (not after the small-cloud kernel, which keeps them in
+    // registers, nor after a nearest_batch call, which reuses the buffer), whether the rows were Morton-sorted (src_sort)
+    int64_t loop_rows = -1;
+    bool loop_idx_valid = false, loop_sorted = false;
 
     DevBuf grp_cnt, grp_items;                // culled engine: per target split the list of 64-row groups within reach (nn_culled.h)
     bool nn_pruned = false;                   // the culled engine (ICPMI_SEARCH_MFMA_PRUNED; AUTO on large targets)
@@ -1086,6 +1091,7 @@ int align_device(icpmi_ctx *ctx, const double *d_src, int64_t n_src64, const dou
     hipStream_t s = ctx->stream;
     int rc;
 
+    ctx->loop_rows = -1; // (set again once this call has completed)
     if ((rc = reserve(ctx, ctx->cur, sizeof(double) * 3 * (size_t)n))) return rc;
     if ((rc = reserve(ctx, ctx->nrm, sizeof(double) * 3 * (size_t)m))) return rc;
     if ((rc = reserve(ctx, ctx->idx, sizeof(int) * (size_t)n))) return rc;
@@ -1478,6 +1484,9 @@ int align_device(icpmi_ctx *ctx, const double *d_src, int64_t n_src64, const dou
     if (hs->error)
         return fail(ctx, ICPMI_ERR_RCCL, "the ranks of this sharded run disagreed on the end of the loop "
                                          "(different icpmi_config per rank, or an exchange that is not bit-identical on every rank)");
+    ctx->loop_rows = n;
+    ctx->loop_idx_valid = n > 0 && !small;
+    ctx->loop_sorted = pruned || sorted_rows_loop;
 
     memcpy(result->transformation, hs->total, sizeof(double) * 16); // icp.hpp:254
     result->converged = hs->converged;
@@ -1921,6 +1930,7 @@ int icpmi_nearest_batch(icpmi_ctx *ctx, const double *targets_xyz, int64_t n_tgt
     const int n = (int)n_qry, m = (int)n_tgt;
     if ((rc = reserve(ctx, ctx->stage_b, sizeof(double) * 3 * (size_t)n))) return rc;
     if ((rc = reserve(ctx, ctx->stage_c, sizeof(double) * 3 * (size_t)m))) return rc;
+    ctx->loop_idx_valid = false; // (the search below writes its indices into idx)
     if ((rc = reserve(ctx, ctx->idx, sizeof(int) * (size_t)n))) return rc;
     if ((rc = reserve(ctx, ctx->d2out, sizeof(double) * (size_t)n))) return rc;
     hipStream_t s = ctx->stream;
@@ -3057,19 +3067,27 @@ int icpmi_get_profile(icpmi_ctx *ctx, icpmi_profile *out)
 }
 
 // the rows of the last registration as the loop left them -- matches, moved coordinates, and the order the rows were taken
-// in (0..n-1 when they were not sorted): scripts/loop_rows.py, tests/test_gpu_nn_reuse.py
+// in (0..n-1 when they were not sorted): scripts/loop_rows.py, tests/test_gpu_nn_reuse.py, tests/test_gpu_loop_matches.py.
+// `n` must be the last registration's row count (ICPMI_ERR_ARG otherwise, and when none has completed).  Returns
+// ICPMI_DEBUG_NO_IDX (1) when idx does not hold the last pass's matches -- the small-cloud kernel's loop, or a nearest_batch
+// call since -- with idx_out set to -1: cur_out and perm_out are still the last pass's.
+constexpr int ICPMI_DEBUG_NO_IDX = 1;
 extern "C" int icpmi_debug_loop_rows(icpmi_ctx *ctx, int32_t *idx_out, double *cur_out, uint32_t *perm_out, int64_t n)
 {
-    if (!ctx || (size_t)n * sizeof(int) > ctx->idx.cap || (size_t)n * 24 > ctx->cur.cap) return ICPMI_ERR_ARG;
+    if (!ctx || n < 0 || n != ctx->loop_rows || (size_t)n * sizeof(int) > ctx->idx.cap || (size_t)n * 24 > ctx->cur.cap)
+        return ICPMI_ERR_ARG;
     if (hipDeviceSynchronize() != hipSuccess) return ICPMI_ERR_HIP;
-    if (hipMemcpy(idx_out, ctx->idx.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return ICPMI_ERR_HIP;
+    if (!ctx->loop_idx_valid)
+        for (int64_t i = 0; i < n; ++i) idx_out[i] = -1;
+    else if (hipMemcpy(idx_out, ctx->idx.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
+        return ICPMI_ERR_HIP;
     if (hipMemcpy(cur_out, ctx->cur.p, (size_t)n * 24, hipMemcpyDeviceToHost) != hipSuccess) return ICPMI_ERR_HIP;
-    if (ctx->src_sort.p && ctx->src_sort.cap >= (size_t)n * 16) {
+    if (ctx->loop_sorted && ctx->src_sort.p && ctx->src_sort.cap >= (size_t)n * 16) {
         if (hipMemcpy(perm_out, (const unsigned *)ctx->src_sort.p + 3 * (size_t)n, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess) return ICPMI_ERR_HIP;
     } else {
         for (int64_t i = 0; i < n; ++i) perm_out[i] = (uint32_t)i;
     }
-    return ICPMI_OK;
+    return ctx->loop_idx_valid ? ICPMI_OK : ICPMI_DEBUG_NO_IDX;
 }
 
 // List reuse of the last registration with profiling on (RowBounds, kernels.h): per bounded pass, the rows listed by its

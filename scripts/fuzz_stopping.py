@@ -80,7 +80,7 @@ def oracle_margin(ref):
 def check_case(seed, ctxs, cfg, stats):
     """One trial through every context of `ctxs` -> mismatches; `stats` (decided / under / exhausted / min_margin) is updated."""
     src, tgt, what = make_case(seed)
-    ref = orc.icp_point_to_plane(src, tgt, MAX_IT, TOL, MIN_ERR, nthreads=os.cpu_count() or 1)
+    ref = orc.icp_point_to_plane(src, tgt, MAX_IT, TOL, MIN_ERR, nthreads=min(16, os.cpu_count() or 1))
     margin = oracle_margin(ref)
     bad = 0
     if not ref.converged:
@@ -139,8 +139,8 @@ def oracle_own_spread(src, tgt):
     if key not in _own_cache:
         sys.path.insert(0, os.path.join(ROOT, "scripts"))
         import iteration_sensitivity as its
-        a = its.registration_margins(src, tgt, MAX_IT, TOL, MIN_ERR, order="index", nthreads=os.cpu_count() or 1)
-        b = its.registration_margins(src, tgt, MAX_IT, TOL, MIN_ERR, order="reversed", nthreads=os.cpu_count() or 1)
+        a = its.registration_margins(src, tgt, MAX_IT, TOL, MIN_ERR, order="index", nthreads=min(16, os.cpu_count() or 1))
+        b = its.registration_margins(src, tgt, MAX_IT, TOL, MIN_ERR, order="reversed", nthreads=min(16, os.cpu_count() or 1))
         if a["num_iterations"] != b["num_iterations"]:
             _own_cache[key] = (np.inf, np.inf, np.inf)   # the oracle's own count moves: nothing can be held
         else:

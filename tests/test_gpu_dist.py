@@ -258,7 +258,7 @@ def test_c4_eight_ranks_rehearsal(oracle):
     per = -(-(-(-tgt.shape[0] // world)) // 512) * 512
     assert per == 125_440 and group.gathered.shape[0] == 3 * per * world
     gathered = group.gathered.reshape(-1, 3)[:tgt.shape[0]]
-    nth = os.cpu_count() or 1
+    nth = min(16, os.cpu_count() or 1)
     want_nrm = oracle.estimate_normals(tgt, None, 20, nthreads=nth)
     rows_of = lambda a: a[np.lexsort((a[:, 2], a[:, 1], a[:, 0]))]
     assert (rows_of(gathered) == rows_of(want_nrm)).all()

@@ -33,3 +33,11 @@ def test_fuzz_stopping_tests_against_the_oracle_loop(oracle, monkeypatch):
     seeded trials here."""
     import fuzz_stopping
     assert fuzz_stopping.main(["fuzz_stopping.py", "40", "9000"]) == 0
+
+
+def test_fuzz_loop_rows_against_exact_nn(oracle):
+    """scripts/fuzz_loop_rows.py: registrations at random shapes around the loop's dispatch thresholds (each +-1, +31, +33),
+    geometries and engines, every pass's matches against the exact fp64 nearest target and its error against the one
+    recomputed from them: 40 seeded trials here."""
+    import fuzz_loop_rows
+    assert fuzz_loop_rows.main(["fuzz_loop_rows.py", "40", "61000"]) == 0
