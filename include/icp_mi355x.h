@@ -372,6 +372,80 @@ typedef struct {
 } icpmi_comm_info_t;
 int icpmi_comm_info(icpmi_ctx *ctx, icpmi_comm_info_t *out);
 
+/* Pose graph: replaces slam::PoseGraph (core/pose_graph.hpp:49-147, src/core/pose_graph.cpp), the GTSAM
+ * Levenberg-Marquardt back end the node feeds one odometry factor per frame (slam_node.cpp:145) and one factor per
+ * accepted loop closure (:163), and re-optimises after a pending closure (:112-115) and at the end (:106).
+ * Objective 0.5 sum ||r||^2_Sigma with GTSAM 4.x Pose3 (EXPMAP build), tangent order (omega, v); the LM policy is
+ * GTSAM's defaults (lambda 1e-5, factor 10, upper bound 1e5, minModelFidelity 1e-3, H + lambda I).  The factors and
+ * estimates live in device buffers owned by the handle; optimize() uploads what was added since the last call and
+ * reads back two doubles per lambda trial.  A handle uses its context's device and stream: one caller thread at a
+ * time, never overlapping the context's own calls.  Transforms are row-major double[16]; rotations are taken as given
+ * (Rot3(Matrix3)), not re-orthonormalised.  A non-finite entry, or from == to, is ICPMI_ERR_ARG. */
+typedef struct icpmi_pose_graph icpmi_pose_graph;
+typedef struct {                     /* slam::PoseGraphConfig, pose_graph.hpp:22-40 */
+    double odom_rotation_sigma;      /* 0.01 rad */
+    double odom_translation_sigma;   /* 0.05 m */
+    double prior_rotation_sigma;     /* 0.001 */
+    double prior_translation_sigma;  /* 0.001 */
+    double loop_rotation_sigma;      /* 0.005 */
+    double loop_translation_sigma;   /* 0.025 */
+    int32_t max_iterations;          /* 100 */
+    int32_t reserved;
+    double relative_error_tol;       /* 1e-5 */
+    double absolute_error_tol;       /* 1e-5 */
+} icpmi_pose_graph_config;
+
+#define ICPMI_PG_STOP_NONE 0
+#define ICPMI_PG_STOP_ZERO_ERROR 1        /* error <= errorTol (0) */
+#define ICPMI_PG_STOP_MAX_ITERATIONS 2
+#define ICPMI_PG_STOP_RELATIVE 3          /* checkConvergence: relative decrease <= relative_error_tol */
+#define ICPMI_PG_STOP_ABSOLUTE 4          /* checkConvergence: absolute decrease <= absolute_error_tol */
+#define ICPMI_PG_STOP_LAMBDA_BOUND 5      /* tryLambda: lambda reached 1e5 without a successful step */
+#define ICPMI_PG_STOP_SMALL_COST_CHANGE 6 /* tryLambda: |cost change| < relative_error_tol * error, no step taken */
+#define ICPMI_PG_STOP_NOT_FINITE 7
+
+typedef struct {
+    int32_t optimized;         /* 1: optimize() returned true (optimized_ set) */
+    int32_t iterations;        /* LevenbergMarquardtOptimizer::iterations(): successful steps */
+    int32_t inner_iterations;  /* lambda trials (tryLambda calls) */
+    int32_t stop_reason;       /* ICPMI_PG_STOP_* */
+    double initial_error;
+    double final_error;        /* optimizer.error() (pose_graph.cpp:159) */
+    double final_lambda;
+    int32_t history_len;       /* initial error + one entry per outer iteration */
+    int32_t reserved;
+} icpmi_pose_graph_info;
+
+void icpmi_pose_graph_config_default(icpmi_pose_graph_config *cfg);   /* pose_graph.hpp:25-39 */
+/* PoseGraph::PoseGraph (pose_graph.cpp:10-16); cfg NULL: defaults */
+int icpmi_pose_graph_create(icpmi_ctx *ctx, const icpmi_pose_graph_config *cfg, icpmi_pose_graph **out);
+void icpmi_pose_graph_destroy(icpmi_pose_graph *graph);
+/* addPrior (pose_graph.cpp:58-79): prior with sigmas (rotation, translation); inserts pose as the estimate of index
+ * if it has none.  Does not clear the optimised state (the reference's quirk). */
+int icpmi_pose_graph_add_prior(icpmi_pose_graph *graph, int64_t index, const double pose[16]);
+/* addOdometryFactor (:81-116): sigmas scaled by 1 + 10 fitness; `to` gets X_from * rel if it has no estimate.  Where
+ * the reference throws (no estimate for `from` either), ICPMI_ERR_ARG and the graph is unchanged. */
+int icpmi_pose_graph_add_odometry(icpmi_pose_graph *graph, int64_t from, int64_t to, const double rel[16],
+                                  double fitness);
+/* addLoopClosure (:118-141): loop sigmas, counted, no estimate added */
+int icpmi_pose_graph_add_loop_closure(icpmi_pose_graph *graph, int64_t from, int64_t to, const double rel[16]);
+/* optimize (:147-171), always from the initial estimates.  Empty graph: ICPMI_OK with info->optimized 0 (the
+ * reference returns false).  A factor on a pose with no estimate: ICPMI_ERR_ARG (the reference's catch returns
+ * false), nothing changes.  info may be NULL; history (may be NULL) receives info->history_len errors and needs
+ * max_iterations + 1 entries (else ICPMI_ERR_CAPACITY). */
+int icpmi_pose_graph_optimize(icpmi_pose_graph *graph, icpmi_pose_graph_info *info, double *history,
+                              int32_t history_cap);
+/* getPose (:177-186): optimised values while optimized_ holds, initial estimates otherwise; a missing index is
+ * ICPMI_ERR_ARG. */
+int icpmi_pose_graph_pose(icpmi_pose_graph *graph, int64_t index, double pose[16]);
+/* getAllPoses (:188-200): indices 0 .. size()-1 with an estimate, in order.  *n_out receives their number; poses
+ * (count x 16) and indices (count; the pose index of each) may be NULL; fewer than *n_out of capacity is
+ * ICPMI_ERR_CAPACITY. */
+int icpmi_pose_graph_poses(icpmi_pose_graph *graph, double *poses, int64_t cap, int64_t *n_out, int64_t *indices);
+/* size() / loopClosureCount() / getFinalError() + getIterations() (pose_graph.hpp:117-128); any may be NULL */
+int icpmi_pose_graph_size(const icpmi_pose_graph *graph, int64_t *num_poses, int64_t *num_loop_closures,
+                          icpmi_pose_graph_info *last);
+
 /* profiling */
 int icpmi_reset_profile(icpmi_ctx *ctx);
 int icpmi_get_profile(icpmi_ctx *ctx, icpmi_profile *out);

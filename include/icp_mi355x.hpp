@@ -21,6 +21,8 @@
 //   OccupancyGridConfig / GridCell / update_occupancy_grid / cells_to_occupancy_grid_msg
 //     (slam_viz/include/slam_viz/ros/slam_node.hpp:35-58, slam_node.cpp:211-221,279-297)
 //                                                        OccupancyGridConfig, GridCell, OccupancyGrid
+//   slam::PoseGraphConfig / slam::PoseGraph
+//                               pose_graph.hpp:22-147        PoseGraphConfig, PoseGraph (device Levenberg-Marquardt)
 //
 // A caller that already has Eigen and the reference's own types uses
 // slam_icp_adapter.hpp instead, which keeps slam::icp_point_to_plane's exact signature.
@@ -662,6 +664,127 @@ public:
 
 private:
     ICPConfig config_;
+};
+
+// slam::PoseGraphConfig (pose_graph.hpp:22-40)
+struct PoseGraphConfig {
+    double odom_rotation_sigma = 0.01;
+    double odom_translation_sigma = 0.05;
+    double prior_rotation_sigma = 0.001;
+    double prior_translation_sigma = 0.001;
+    double loop_rotation_sigma = 0.005;
+    double loop_translation_sigma = 0.025;
+    int max_iterations = 100;
+    double relative_error_tol = 1e-5;
+    double absolute_error_tol = 1e-5;
+};
+
+// slam::PoseGraph (pose_graph.hpp:49-147) on icpmi_pose_graph: the factors and estimates live on the device of the
+// context it was made with, and optimize() runs Levenberg-Marquardt there.  Non-copyable, movable.  Where the
+// reference throws (addOdometryFactor from a pose with no estimate, getPose of a missing index) this throws IcpError;
+// optimize() returns false where the reference's catch does.
+class PoseGraph {
+public:
+    explicit PoseGraph(const PoseGraphConfig &config = PoseGraphConfig(), Context *ctx = nullptr)
+        : ctx_(ctx ? ctx : &default_context())
+    {
+        icpmi_pose_graph_config c;
+        icpmi_pose_graph_config_default(&c);
+        c.odom_rotation_sigma = config.odom_rotation_sigma;
+        c.odom_translation_sigma = config.odom_translation_sigma;
+        c.prior_rotation_sigma = config.prior_rotation_sigma;
+        c.prior_translation_sigma = config.prior_translation_sigma;
+        c.loop_rotation_sigma = config.loop_rotation_sigma;
+        c.loop_translation_sigma = config.loop_translation_sigma;
+        c.max_iterations = config.max_iterations;
+        c.relative_error_tol = config.relative_error_tol;
+        c.absolute_error_tol = config.absolute_error_tol;
+        check(icpmi_pose_graph_create(ctx_->get(), &c, &g_));
+    }
+    ~PoseGraph() { icpmi_pose_graph_destroy(g_); }
+    PoseGraph(const PoseGraph &) = delete;
+    PoseGraph &operator=(const PoseGraph &) = delete;
+    PoseGraph(PoseGraph &&o) noexcept : ctx_(o.ctx_), g_(o.g_) { o.g_ = nullptr; }
+    PoseGraph &operator=(PoseGraph &&o) noexcept
+    {
+        if (this != &o) {
+            icpmi_pose_graph_destroy(g_);
+            ctx_ = o.ctx_;
+            g_ = o.g_;
+            o.g_ = nullptr;
+        }
+        return *this;
+    }
+
+    void addPrior(std::size_t index, const Transformation &pose) // pose_graph.cpp:58-79
+    {
+        check(icpmi_pose_graph_add_prior(g_, static_cast<int64_t>(index), pose.matrix().data()));
+    }
+    void addOdometryFactor(std::size_t from_idx, std::size_t to_idx, const Transformation &relative_transform,
+                           double fitness_score = 0.0) // :81-116
+    {
+        check(icpmi_pose_graph_add_odometry(g_, static_cast<int64_t>(from_idx), static_cast<int64_t>(to_idx),
+                                            relative_transform.matrix().data(), fitness_score));
+    }
+    void addLoopClosure(std::size_t from_idx, std::size_t to_idx, const Transformation &relative_transform) // :118-141
+    {
+        check(icpmi_pose_graph_add_loop_closure(g_, static_cast<int64_t>(from_idx), static_cast<int64_t>(to_idx),
+                                                relative_transform.matrix().data()));
+    }
+    bool optimize() // :147-171
+    {
+        icpmi_pose_graph_info info;
+        const int rc = icpmi_pose_graph_optimize(g_, &info, nullptr, 0);
+        if (rc == ICPMI_ERR_ARG) return false;   // a factor on a pose with no estimate: the reference's catch
+        check(rc);
+        return info.optimized != 0;
+    }
+    Transformation getPose(std::size_t index) const // :177-186
+    {
+        std::array<double, 16> m;
+        check(icpmi_pose_graph_pose(g_, static_cast<int64_t>(index), m.data()));
+        return Transformation(m);
+    }
+    std::vector<Transformation> getAllPoses() const // :188-200
+    {
+        int64_t n = 0;
+        check(icpmi_pose_graph_poses(g_, nullptr, 0, &n, nullptr));
+        std::vector<double> buf(16 * static_cast<std::size_t>(n));
+        if (n) check(icpmi_pose_graph_poses(g_, buf.data(), n, &n, nullptr));
+        std::vector<Transformation> out;
+        out.reserve(static_cast<std::size_t>(n));
+        for (int64_t i = 0; i < n; ++i) {
+            std::array<double, 16> m;
+            std::copy(buf.begin() + 16 * i, buf.begin() + 16 * (i + 1), m.begin());
+            out.emplace_back(m);
+        }
+        return out;
+    }
+    std::size_t size() const { return static_cast<std::size_t>(counts().first); }
+    std::size_t loopClosureCount() const { return static_cast<std::size_t>(counts().second); }
+    double getFinalError() const { return last().final_error; }
+    int getIterations() const { return last().iterations; }
+    icpmi_pose_graph *get() const { return g_; }
+
+private:
+    void check(int rc) const
+    {
+        if (rc != ICPMI_OK) throw IcpError(rc, icpmi_last_error(ctx_->get()));
+    }
+    std::pair<int64_t, int64_t> counts() const
+    {
+        int64_t n = 0, l = 0;
+        check(icpmi_pose_graph_size(g_, &n, &l, nullptr));
+        return {n, l};
+    }
+    icpmi_pose_graph_info last() const
+    {
+        icpmi_pose_graph_info info;
+        check(icpmi_pose_graph_size(g_, nullptr, nullptr, &info));
+        return info;
+    }
+    Context *ctx_;
+    icpmi_pose_graph *g_ = nullptr;
 };
 
 } // namespace icp_mi355x

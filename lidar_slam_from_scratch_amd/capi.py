@@ -29,6 +29,9 @@ EXPORTS = [
     "icpmi_grid_config_default", "icpmi_occupancy_update", "icpmi_occupancy_update_device", "icpmi_occupancy_cells",
     "icpmi_occupancy_clear", "icpmi_stream_map_update", "icpmi_stream_current_scan",
     "icpmi_reset_profile", "icpmi_get_profile",
+    "icpmi_pose_graph_config_default", "icpmi_pose_graph_create", "icpmi_pose_graph_destroy",
+    "icpmi_pose_graph_add_prior", "icpmi_pose_graph_add_odometry", "icpmi_pose_graph_add_loop_closure",
+    "icpmi_pose_graph_optimize", "icpmi_pose_graph_pose", "icpmi_pose_graph_poses", "icpmi_pose_graph_size",
 ]
 
 
@@ -86,6 +89,25 @@ STREAM_REGISTERED, STREAM_FIRST_FRAME, STREAM_TOO_FEW_POINTS = 0, 1, 2
 class GridConfig(C.Structure):
     """OccupancyGridConfig (slam_node.hpp:35-40)"""
     _fields_ = [("resolution", C.c_double), ("height_min", C.c_double), ("height_max", C.c_double), ("max_range", C.c_double)]
+
+
+class PoseGraphConfig(C.Structure):
+    """slam::PoseGraphConfig (pose_graph.hpp:22-40)"""
+    _fields_ = [("odom_rotation_sigma", C.c_double), ("odom_translation_sigma", C.c_double),
+                ("prior_rotation_sigma", C.c_double), ("prior_translation_sigma", C.c_double),
+                ("loop_rotation_sigma", C.c_double), ("loop_translation_sigma", C.c_double),
+                ("max_iterations", C.c_int32), ("reserved", C.c_int32),
+                ("relative_error_tol", C.c_double), ("absolute_error_tol", C.c_double)]
+
+
+class PoseGraphInfo(C.Structure):
+    _fields_ = [("optimized", C.c_int32), ("iterations", C.c_int32), ("inner_iterations", C.c_int32),
+                ("stop_reason", C.c_int32), ("initial_error", C.c_double), ("final_error", C.c_double),
+                ("final_lambda", C.c_double), ("history_len", C.c_int32), ("reserved", C.c_int32)]
+
+
+PG_STOP_NONE, PG_STOP_ZERO_ERROR, PG_STOP_MAX_ITERATIONS, PG_STOP_RELATIVE, PG_STOP_ABSOLUTE, PG_STOP_LAMBDA_BOUND, \
+    PG_STOP_SMALL_COST_CHANGE, PG_STOP_NOT_FINITE = range(8)
 
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int32)
@@ -207,6 +229,19 @@ def load_library(path=None):
     L.icpmi_comm_info.argtypes = [vp, C.POINTER(CommInfo)]
     L.icpmi_reset_profile.argtypes = [vp]
     L.icpmi_get_profile.argtypes = [vp, C.POINTER(Profile)]
+    pg = C.c_void_p
+    L.icpmi_pose_graph_config_default.argtypes = [C.POINTER(PoseGraphConfig)]
+    L.icpmi_pose_graph_config_default.restype = None
+    L.icpmi_pose_graph_create.argtypes = [vp, C.POINTER(PoseGraphConfig), C.POINTER(pg)]
+    L.icpmi_pose_graph_destroy.argtypes = [pg]
+    L.icpmi_pose_graph_destroy.restype = None
+    L.icpmi_pose_graph_add_prior.argtypes = [pg, C.c_int64, dp]
+    L.icpmi_pose_graph_add_odometry.argtypes = [pg, C.c_int64, C.c_int64, dp, C.c_double]
+    L.icpmi_pose_graph_add_loop_closure.argtypes = [pg, C.c_int64, C.c_int64, dp]
+    L.icpmi_pose_graph_optimize.argtypes = [pg, C.POINTER(PoseGraphInfo), dp, C.c_int32]
+    L.icpmi_pose_graph_pose.argtypes = [pg, C.c_int64, dp]
+    L.icpmi_pose_graph_poses.argtypes = [pg, dp, C.c_int64, i64p, i64p]
+    L.icpmi_pose_graph_size.argtypes = [pg, i64p, i64p, C.POINTER(PoseGraphInfo)]
     for name in EXPORTS:
         getattr(L, name)  # raises AttributeError if a declared symbol is not exported
     _LIB = L
@@ -273,6 +308,8 @@ class Context:
 
     def close(self):
         if getattr(self, "_h", None):
+            for g in list(getattr(self, "_pose_graphs", ())):   # icpmi_pose_graph handles go before their context
+                g.close()
             self._lib.icpmi_destroy(self._h)
             self._h = None
 

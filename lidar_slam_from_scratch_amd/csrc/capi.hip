@@ -21,6 +21,8 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
+#include <limits>
 #include <condition_variable>
 #include <functional>
 #include <mutex>
@@ -38,6 +40,7 @@
 #include "voxel.h"
 #include "scan_context.h"
 #include "occupancy.h"
+#include "pose_graph.h"
 
 using namespace icpmi;
 
@@ -3102,6 +3105,627 @@ extern "C" int64_t icpmi_debug_nn_reuse(const icpmi_ctx *ctx, uint32_t *rows_out
         if (blocks_out) blocks_out[p] = ctx->reuse_blocks[p];
     }
     return np;
+}
+
+} // extern "C"
+
+// ======================================================================================================================
+// Pose graph (core/pose_graph.cpp): factors and estimates on the host, the LM iteration on the device (pose_graph.h).
+// The LM policy below restates LevenbergMarquardtOptimizer::tryLambda / iterate and NonlinearOptimizer::defaultOptimize
+// exactly as scripts/pose_graph_ref.py levenberg_marquardt does, rule for rule.
+
+struct icpmi_pose_graph {
+    icpmi_ctx *ctx = nullptr;
+    icpmi_pose_graph_config cfg;
+    std::vector<PgFactor> factors;
+    std::vector<double> init;            // 12 per pose index (valid where has_init)
+    std::vector<char> has_init;
+    std::vector<double> opt;             // optimised values, 12 per pose index (valid where has_init, while optimized)
+    int64_t num_poses = 0, num_loops = 0;
+    bool optimized = false;
+    size_t uploaded_factors = 0;         // factors already in d_fac
+    int64_t init_dirty_lo = INT64_MAX, init_dirty_hi = 0;   // pose range of estimates not yet in d_init
+    DevBuf d_fac, d_init, d_map, d_keys, d_X, d_Xc, d_A, d_rw, d_err, d_H, d_g, d_D, d_gn, d_Cn, d_L, d_U, d_Y,
+        d_schur, d_S, d_xb, d_delta, d_errc, d_errl, d_out, d_status, d_inc_ptr, d_inc, d_cn_ptr, d_cn, d_segs,
+        d_blocks, d_codes, d_sep_node, d_sep_segs, d_sep_pos, d_node_seg;
+    double *h_out = nullptr;             // pinned: the two sums and the status of a trial
+    icpmi_pose_graph_info last{};        // of the last optimize()
+};
+
+namespace {
+
+int pg_check_T(icpmi_ctx *ctx, const double *T)
+{
+    if (!T) return fail(ctx, ICPMI_ERR_NULL, "null transform");
+    for (int e = 0; e < 16; ++e)
+        if (!std::isfinite(T[e])) return fail(ctx, ICPMI_ERR_ARG, "non-finite transform entry");
+    return ICPMI_OK;
+}
+
+void pg_to12(const double *T, double *o) // row-major 4x4 -> R (9), t (3); rotations taken as given (Rot3(Matrix3))
+{
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) o[3 * r + c] = T[4 * r + c];
+    o[9] = T[3]; o[10] = T[7]; o[11] = T[11];
+}
+void pg_to16(const double *o, double *T)
+{
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) T[4 * r + c] = o[3 * r + c];
+        T[4 * r + 3] = o[9 + r];
+    }
+    T[12] = T[13] = T[14] = 0.0;
+    T[15] = 1.0;
+}
+
+void pg_grow(icpmi_pose_graph *g, int64_t idx)
+{
+    if ((int64_t)g->has_init.size() <= idx) {
+        g->has_init.resize(idx + 1, 0);
+        g->init.resize(12 * (size_t)(idx + 1), 0.0);
+    }
+}
+void pg_set_init(icpmi_pose_graph *g, int64_t idx, const double *p12)
+{
+    pg_grow(g, idx);
+    std::copy(p12, p12 + 12, g->init.begin() + 12 * idx);
+    g->has_init[idx] = 1;
+    g->init_dirty_lo = std::min(g->init_dirty_lo, idx);
+    g->init_dirty_hi = std::max(g->init_dirty_hi, idx + 1);
+    g->num_poses = std::max(g->num_poses, idx + 1);
+}
+bool pg_has(const icpmi_pose_graph *g, int64_t idx)
+{
+    return idx >= 0 && idx < (int64_t)g->has_init.size() && g->has_init[idx];
+}
+
+void pg_factor(PgFactor &f, int kind, int64_t i, int64_t j, const double *T, double rs, double ts)
+{
+    f.kind = kind;
+    f.i = (int32_t)i;
+    f.j = (int32_t)j;
+    f.reserved = 0;
+    pg_to12(T, f.Z);
+    for (int a = 0; a < 3; ++a) {
+        f.inv_sigma[a] = 1.0 / rs;        // noiseModel::Diagonal::Sigmas keeps 1/sigma and whitens by multiplying
+        f.inv_sigma[3 + a] = 1.0 / ts;
+    }
+}
+
+template <class T> int pg_upload(icpmi_ctx *ctx, DevBuf &b, const std::vector<T> &v)
+{
+    int rc;
+    if ((rc = reserve(ctx, b, sizeof(T) * std::max<size_t>(v.size(), 1)))) return rc;
+    if (!v.empty()) HIP_TRY(ctx, hipMemcpyAsync(b.p, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice, ctx->stream));
+    return ICPMI_OK;
+}
+
+unsigned pg_grid(size_t n, unsigned b) { return (unsigned)((n + b - 1) / b); }
+
+// The graph's structure for the device solve (rebuilt by every optimize(): O(poses + factors) on the host).
+struct PgPlan {
+    int n = 0, F = 0, nb = 0, nseg = 0, nblocks = 0;
+    std::vector<int32_t> keys, map;
+};
+
+int pg_plan(icpmi_pose_graph *g, PgPlan &P)
+{
+    icpmi_ctx *ctx = g->ctx;
+    const int64_t np = g->num_poses;
+    P.map.assign(np, -1);
+    for (int64_t k = 0; k < np; ++k)
+        if (g->has_init[k]) {
+            P.map[k] = (int32_t)P.keys.size();
+            P.keys.push_back((int32_t)k);
+        }
+    const int n = (int)P.keys.size(), F = (int)g->factors.size();
+    P.n = n;
+    P.F = F;
+    std::vector<char> sep(n, 0);
+    std::vector<int32_t> inc_cnt(n + 1, 0), cn_cnt(n + 1, 0);
+    for (int k = 0; k < n; ++k)
+        if (P.keys[k] % kPgChainK == kPgChainK - 1) sep[k] = 1;        // caps a chain run at K - 1 nodes
+    for (int f = 0; f < F; ++f) {
+        const PgFactor &fa = g->factors[f];
+        inc_cnt[P.map[fa.i] + 1]++;
+        if (fa.kind == 1) {
+            inc_cnt[P.map[fa.j] + 1]++;
+            if (fa.j == fa.i + 1) cn_cnt[P.map[fa.i] + 1]++;          // chain factor (k, k+1)
+            else sep[P.map[fa.i]] = sep[P.map[fa.j]] = 1;             // any other between factor: two separators
+        }
+    }
+    for (int k = 0; k < n; ++k) {
+        inc_cnt[k + 1] += inc_cnt[k];
+        cn_cnt[k + 1] += cn_cnt[k];
+    }
+    std::vector<int32_t> inc(inc_cnt[n]), cn(cn_cnt[n]), ip(inc_cnt.begin(), inc_cnt.end() - 1),
+        cp(cn_cnt.begin(), cn_cnt.end() - 1);
+    for (int f = 0; f < F; ++f) {   // ascending f within every node
+        const PgFactor &fa = g->factors[f];
+        inc[ip[P.map[fa.i]]++] = 2 * f;
+        if (fa.kind == 1) {
+            inc[ip[P.map[fa.j]]++] = 2 * f + 1;
+            if (fa.j == fa.i + 1) cn[cp[P.map[fa.i]]++] = f;
+        }
+    }
+    // separators in compact order; segments = maximal runs of the rest
+    std::vector<int32_t> sep_pos(n, -1), sep_node, node_seg(n), sep_segs;
+    std::vector<PgSeg> segs;
+    for (int k = 0; k < n; ++k)
+        if (sep[k]) {
+            sep_pos[k] = (int32_t)sep_node.size();
+            sep_node.push_back(k);
+        }
+    const int nb = (int)sep_node.size();
+    sep_segs.assign(2 * (size_t)nb, -1);
+    for (int k = 0; k < n;) {
+        if (sep[k]) {
+            node_seg[k] = -1 - sep_pos[k];
+            ++k;
+            continue;
+        }
+        PgSeg s;
+        s.start = k;
+        while (k < n && !sep[k]) node_seg[k++] = (int32_t)segs.size();
+        s.len = k - s.start;
+        s.left = s.start > 0 ? s.start - 1 : -1;
+        s.right = k < n ? k : -1;
+        if (s.left >= 0) sep_segs[2 * sep_pos[s.left] + 1] = (int32_t)segs.size();
+        if (s.right >= 0) sep_segs[2 * sep_pos[s.right]] = (int32_t)segs.size();
+        segs.push_back(s);
+    }
+    // the reduced system's lower blocks and what each sums, in a fixed order
+    std::vector<std::vector<int32_t>> per;                 // contributions per block
+    std::vector<PgBlock> blocks;
+    std::vector<std::pair<int64_t, int32_t>> index;        // (row * nb + col) -> block, sorted later
+    auto block = [&](int row, int col) -> std::vector<int32_t> & {
+        const int64_t key = (int64_t)row * nb + col;
+        for (auto it = index.rbegin(); it != index.rend() && it - index.rbegin() < 4; ++it)
+            if (it->first == key) return per[it->second];
+        index.push_back({key, (int32_t)blocks.size()});
+        PgBlock b{row, col, 0, 0};
+        blocks.push_back(b);
+        per.emplace_back();
+        return per.back();
+    };
+    for (int a = 0; a < nb; ++a) {
+        auto &c = block(a, a);
+        const int v = sep_node[a];
+        c.push_back(v);                                            // D_v + lam I
+        if (sep_segs[2 * a] >= 0) c.push_back((4 << 28) | (4 * sep_segs[2 * a] + 3));          // RR of the left segment
+        if (sep_segs[2 * a + 1] >= 0) c.push_back((4 << 28) | (4 * sep_segs[2 * a + 1] + 0));  // LL of the right one
+        if (v + 1 < n && sep[v + 1] && cn_cnt[v + 1] > cn_cnt[v]) block(a + 1, a).push_back((1 << 28) | v);
+    }
+    for (size_t s = 0; s < segs.size(); ++s)
+        if (segs[s].left >= 0 && segs[s].right >= 0)
+            block(sep_pos[segs[s].right], sep_pos[segs[s].left]).push_back((4 << 28) | (4 * (int)s + 1));
+    // non-chain between factors: O(1) amortised lookup of the (row, col) block through a sorted index
+    {
+        std::vector<std::pair<int64_t, int32_t>> sorted(index);
+        std::sort(sorted.begin(), sorted.end());
+        std::vector<std::pair<int64_t, int32_t>> extra;
+        for (int f = 0; f < F; ++f) {
+            const PgFactor &fa = g->factors[f];
+            if (fa.kind != 1 || fa.j == fa.i + 1) continue;
+            const int pi = sep_pos[P.map[fa.i]], pj = sep_pos[P.map[fa.j]];
+            const int row = std::max(pi, pj), col = std::min(pi, pj);
+            const int64_t key = (int64_t)row * nb + col;
+            auto it = std::lower_bound(sorted.begin(), sorted.end(), std::make_pair(key, (int32_t)-1));
+            int32_t bidx;
+            if (it != sorted.end() && it->first == key) bidx = it->second;
+            else {
+                bidx = (int32_t)blocks.size();
+                blocks.push_back(PgBlock{row, col, 0, 0});
+                per.emplace_back();
+                sorted.insert(it, {key, bidx});
+            }
+            per[bidx].push_back(((pi > pj ? 3 : 2) << 28) | f);
+        }
+    }
+    std::vector<int32_t> codes;
+    for (size_t b = 0; b < blocks.size(); ++b) {
+        blocks[b].begin = (int32_t)codes.size();
+        codes.insert(codes.end(), per[b].begin(), per[b].end());
+        blocks[b].end = (int32_t)codes.size();
+    }
+    if (F >= (1 << 28) || n >= (1 << 26)) return fail(ctx, ICPMI_ERR_ARG, "pose graph too large for the block codes");
+    P.nb = nb;
+    P.nseg = (int)segs.size();
+    P.nblocks = (int)blocks.size();
+    int rc;
+    if ((rc = pg_upload(ctx, g->d_map, P.map)) || (rc = pg_upload(ctx, g->d_keys, P.keys)) ||
+        (rc = pg_upload(ctx, g->d_inc_ptr, inc_cnt)) || (rc = pg_upload(ctx, g->d_inc, inc)) ||
+        (rc = pg_upload(ctx, g->d_cn_ptr, cn_cnt)) || (rc = pg_upload(ctx, g->d_cn, cn)) ||
+        (rc = pg_upload(ctx, g->d_segs, segs)) || (rc = pg_upload(ctx, g->d_blocks, blocks)) ||
+        (rc = pg_upload(ctx, g->d_codes, codes)) || (rc = pg_upload(ctx, g->d_sep_node, sep_node)) ||
+        (rc = pg_upload(ctx, g->d_sep_segs, sep_segs)) || (rc = pg_upload(ctx, g->d_sep_pos, sep_pos)) ||
+        (rc = pg_upload(ctx, g->d_node_seg, node_seg)))
+        return rc;
+    const size_t F1 = std::max(F, 1), n1 = std::max(n, 1), nr = 6 * (size_t)std::max(nb, 1);
+    struct { DevBuf *b; size_t bytes; } need[] = {
+        {&g->d_X, 96 * n1}, {&g->d_Xc, 96 * n1}, {&g->d_A, 576 * F1}, {&g->d_rw, 48 * F1}, {&g->d_err, 8 * F1},
+        {&g->d_H, 864 * F1}, {&g->d_g, 96 * F1}, {&g->d_D, 288 * n1}, {&g->d_gn, 48 * n1}, {&g->d_Cn, 288 * n1},
+        {&g->d_L, 288 * n1}, {&g->d_U, 288 * n1}, {&g->d_Y, 624 * n1}, {&g->d_schur, 1248 * (size_t)std::max(P.nseg, 1)},
+        {&g->d_S, 8 * nr * nr}, {&g->d_xb, 8 * nr}, {&g->d_delta, 48 * n1}, {&g->d_errc, 8 * F1}, {&g->d_errl, 8 * F1},
+        {&g->d_out, 64}, {&g->d_status, 64}};
+    for (auto &q : need)
+        if ((rc = reserve(ctx, *q.b, q.bytes))) return rc;
+    return ICPMI_OK;
+}
+
+// one readback: {sum a, sum b, status}
+int pg_sums(icpmi_pose_graph *g, const double *a, const double *b, int F, double out[3])
+{
+    icpmi_ctx *ctx = g->ctx;
+    hipStream_t s = ctx->stream;
+    hipLaunchKernelGGL(k_pg_reduce, dim3(1), dim3(1024), 0, s, a, b, F, (double *)g->d_out.p);
+    HIP_TRY(ctx, hipMemcpyAsync(g->h_out, g->d_out.p, 16, hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipMemcpyAsync(g->h_out + 2, g->d_status.p, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    HIP_TRY(ctx, hipGetLastError());
+    out[0] = g->h_out[0];
+    out[1] = g->h_out[1];
+    int st;
+    memcpy(&st, g->h_out + 2, sizeof(int));
+    out[2] = st;
+    return ICPMI_OK;
+}
+
+// (H + lam I) delta = -g on the device; then the candidate and its two errors
+int pg_trial(icpmi_pose_graph *g, const PgPlan &P, const PgLin &lin, double lam, double out[3])
+{
+    icpmi_ctx *ctx = g->ctx;
+    hipStream_t s = ctx->stream;
+    const int n = P.n, F = P.F, nb = P.nb, nr = 6 * nb;
+    HIP_TRY(ctx, hipMemsetAsync(g->d_status.p, 0, sizeof(int), s));
+    int *status = (int *)g->d_status.p;
+    if (P.nseg > 0)
+        hipLaunchKernelGGL(k_pg_segment, dim3(P.nseg), dim3(kPgSegThreads), 0, s, (const PgSeg *)g->d_segs.p, lam,
+                           (const double *)g->d_D.p, (const double *)g->d_gn.p, (const double *)g->d_Cn.p,
+                           (double *)g->d_L.p, (double *)g->d_U.p, (double *)g->d_Y.p, (double *)g->d_schur.p, status);
+    if (nb > 0) {
+        double *S = (double *)g->d_S.p;
+        HIP_TRY(ctx, hipMemsetAsync(S, 0, sizeof(double) * (size_t)nr * nr, s));   // blocks with no coupling are zero
+        hipLaunchKernelGGL(k_pg_reduced, dim3(P.nblocks), dim3(64), 0, s, (const PgBlock *)g->d_blocks.p,
+                           (const int32_t *)g->d_codes.p, nr, lam, (const double *)g->d_D.p, (const double *)g->d_Cn.p,
+                           (const double *)lin.H, (const double *)g->d_schur.p, S);
+        hipLaunchKernelGGL(k_pg_reduced_rhs, dim3(pg_grid(nr, 256)), dim3(256), 0, s, (const int32_t *)g->d_sep_node.p,
+                           (const int32_t *)g->d_sep_segs.p, nb, (const double *)g->d_gn.p, (const double *)g->d_schur.p,
+                           (double *)g->d_xb.p);
+        for (int k0 = 0; k0 < nr; k0 += kCholNb) {
+            hipLaunchKernelGGL(k_chol_diag, dim3(1), dim3(256), 0, s, S, nr, k0, status);
+            const int rest = nr - k0 - kCholNb;
+            if (rest <= 0) break;
+            hipLaunchKernelGGL(k_chol_panel, dim3(pg_grid(rest, 64)), dim3(64), 0, s, S, nr, k0);
+            const unsigned T = pg_grid(rest, 32);
+            hipLaunchKernelGGL(k_chol_update, dim3(T, T), dim3(256), 0, s, S, nr, k0);
+        }
+        hipLaunchKernelGGL(k_trsv_pair, dim3(1), dim3(256), 0, s, (const double *)S, nr, (double *)g->d_xb.p);
+    }
+    hipLaunchKernelGGL(k_pg_backsub, dim3(pg_grid(6 * (size_t)n, 256)), dim3(256), 0, s, (const int32_t *)g->d_node_seg.p,
+                       (const PgSeg *)g->d_segs.p, (const int32_t *)g->d_sep_pos.p, (const double *)g->d_Y.p,
+                       (const double *)g->d_xb.p, n, (double *)g->d_delta.p);
+    hipLaunchKernelGGL(k_pg_retract, dim3(pg_grid(n, 128)), dim3(128), 0, s, (const double *)g->d_X.p,
+                       (const double *)g->d_delta.p, n, (double *)g->d_Xc.p);
+    hipLaunchKernelGGL(k_pg_trial, dim3(pg_grid(F, 128)), dim3(128), 0, s, (const PgFactor *)g->d_fac.p,
+                       (const int32_t *)g->d_map.p, F, (const double *)g->d_Xc.p, lin, (const double *)g->d_delta.p,
+                       (double *)g->d_errc.p, (double *)g->d_errl.p);
+    return pg_sums(g, (const double *)g->d_errc.p, (const double *)g->d_errl.p, F, out);
+}
+
+int pg_linearize(icpmi_pose_graph *g, const PgPlan &P, const PgLin &lin, double *error)
+{
+    icpmi_ctx *ctx = g->ctx;
+    hipStream_t s = ctx->stream;
+    hipLaunchKernelGGL(k_pg_linearize, dim3(pg_grid(P.F, 128)), dim3(128), 0, s, (const PgFactor *)g->d_fac.p,
+                       (const int32_t *)g->d_map.p, P.F, (const double *)g->d_X.p, lin);
+    hipLaunchKernelGGL(k_pg_assemble, dim3(pg_grid(78 * (size_t)P.n, 256)), dim3(256), 0, s, lin,
+                       (const int32_t *)g->d_inc_ptr.p, (const int32_t *)g->d_inc.p, (const int32_t *)g->d_cn_ptr.p,
+                       (const int32_t *)g->d_cn.p, P.n, (double *)g->d_D.p, (double *)g->d_gn.p, (double *)g->d_Cn.p);
+    if (!error) return ICPMI_OK;
+    double out[3];
+    int rc = pg_sums(g, lin.err, nullptr, P.F, out);
+    *error = out[0];
+    return rc;
+}
+
+} // namespace
+
+extern "C" {
+
+void icpmi_pose_graph_config_default(icpmi_pose_graph_config *c)
+{
+    if (!c) return;
+    c->odom_rotation_sigma = 0.01;       // pose_graph.hpp:25-39
+    c->odom_translation_sigma = 0.05;
+    c->prior_rotation_sigma = 0.001;
+    c->prior_translation_sigma = 0.001;
+    c->loop_rotation_sigma = 0.005;
+    c->loop_translation_sigma = 0.025;
+    c->max_iterations = 100;
+    c->reserved = 0;
+    c->relative_error_tol = 1e-5;
+    c->absolute_error_tol = 1e-5;
+}
+
+int icpmi_pose_graph_create(icpmi_ctx *ctx, const icpmi_pose_graph_config *cfg, icpmi_pose_graph **out)
+{
+    int rc;
+    if (!out) return fail(ctx, ICPMI_ERR_NULL, "out is NULL");
+    *out = nullptr;
+    if ((rc = check_common(ctx))) return rc;
+    icpmi_pose_graph_config c;
+    if (cfg) c = *cfg;
+    else icpmi_pose_graph_config_default(&c);
+    const double sig[6] = {c.odom_rotation_sigma, c.odom_translation_sigma, c.prior_rotation_sigma,
+                           c.prior_translation_sigma, c.loop_rotation_sigma, c.loop_translation_sigma};
+    for (double v : sig)
+        if (!(v > 0.0) || !std::isfinite(v)) return fail(ctx, ICPMI_ERR_ARG, "sigmas must be finite and positive");
+    if (c.max_iterations < 0 || !(c.relative_error_tol >= 0.0) || !(c.absolute_error_tol >= 0.0))
+        return fail(ctx, ICPMI_ERR_ARG, "bad optimizer settings");
+    icpmi_pose_graph *g = new icpmi_pose_graph;
+    g->ctx = ctx;
+    g->cfg = c;
+    if (hipHostMalloc((void **)&g->h_out, 64) != hipSuccess) {
+        delete g;
+        return fail(ctx, ICPMI_ERR_HIP, "hipHostMalloc failed");
+    }
+    *out = g;
+    return ICPMI_OK;
+}
+
+void icpmi_pose_graph_destroy(icpmi_pose_graph *g)
+{
+    if (!g) return;
+    (void)hipSetDevice(g->ctx->opt.device);
+    (void)hipStreamSynchronize(g->ctx->stream);
+    DevBuf *bufs[] = {&g->d_fac, &g->d_init, &g->d_map, &g->d_keys, &g->d_X, &g->d_Xc, &g->d_A, &g->d_rw, &g->d_err,
+                      &g->d_H, &g->d_g, &g->d_D, &g->d_gn, &g->d_Cn, &g->d_L, &g->d_U, &g->d_Y, &g->d_schur, &g->d_S,
+                      &g->d_xb, &g->d_delta, &g->d_errc, &g->d_errl, &g->d_out, &g->d_status, &g->d_inc_ptr, &g->d_inc,
+                      &g->d_cn_ptr, &g->d_cn, &g->d_segs, &g->d_blocks, &g->d_codes, &g->d_sep_node, &g->d_sep_segs,
+                      &g->d_sep_pos, &g->d_node_seg};
+    for (DevBuf *b : bufs) release(*b);
+    if (g->h_out) (void)hipHostFree(g->h_out);
+    delete g;
+}
+
+int icpmi_pose_graph_add_prior(icpmi_pose_graph *g, int64_t index, const double pose[16])
+{
+    if (!g) return ICPMI_ERR_NULL;
+    int rc;
+    if ((rc = pg_check_T(g->ctx, pose))) return rc;
+    if (index < 0 || index >= INT32_MAX - 1) return fail(g->ctx, ICPMI_ERR_ARG, "pose index out of range");
+    const double c = g->cfg.prior_rotation_sigma, t = g->cfg.prior_translation_sigma;
+    PgFactor f;
+    pg_factor(f, 0, index, -1, pose, c, t);
+    g->factors.push_back(f);                       // graph_->addPrior (pose_graph.cpp:72)
+    if (!pg_has(g, index)) pg_set_init(g, index, f.Z);   // :75-78; optimized_ is left as it is
+    return ICPMI_OK;
+}
+
+int icpmi_pose_graph_add_odometry(icpmi_pose_graph *g, int64_t from, int64_t to, const double rel[16], double fitness)
+{
+    if (!g) return ICPMI_ERR_NULL;
+    int rc;
+    if ((rc = pg_check_T(g->ctx, rel))) return rc;
+    if (from < 0 || to < 0 || from >= INT32_MAX - 1 || to >= INT32_MAX - 1 || from == to || !std::isfinite(fitness))
+        return fail(g->ctx, ICPMI_ERR_ARG, "bad odometry factor");
+    const bool need = !pg_has(g, to);
+    if (need && !pg_has(g, from))                  // Values::at throws in the reference (pose_graph.cpp:104)
+        return fail(g->ctx, ICPMI_ERR_ARG, "pose %lld has no estimate", (long long)from);
+    const double scale = 1.0 + fitness * 10.0;     // :88
+    PgFactor f;
+    pg_factor(f, 1, from, to, rel, g->cfg.odom_rotation_sigma * scale, g->cfg.odom_translation_sigma * scale);
+    g->factors.push_back(f);                       // :99-101
+    if (need) {                                    // :103-110: X_to = X_from * Z (Pose3::compose)
+        const double *a = g->init.data() + 12 * from, *b = f.Z;
+        double o[12];
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) o[3 * i + j] = a[3 * i] * b[j] + a[3 * i + 1] * b[3 + j] + a[3 * i + 2] * b[6 + j];
+        for (int i = 0; i < 3; ++i) o[9 + i] = (a[3 * i] * b[9] + a[3 * i + 1] * b[10] + a[3 * i + 2] * b[11]) + a[9 + i];
+        pg_set_init(g, to, o);
+    }
+    g->optimized = false;                          // :112
+    return ICPMI_OK;
+}
+
+int icpmi_pose_graph_add_loop_closure(icpmi_pose_graph *g, int64_t from, int64_t to, const double rel[16])
+{
+    if (!g) return ICPMI_ERR_NULL;
+    int rc;
+    if ((rc = pg_check_T(g->ctx, rel))) return rc;
+    if (from < 0 || to < 0 || from >= INT32_MAX - 1 || to >= INT32_MAX - 1 || from == to)
+        return fail(g->ctx, ICPMI_ERR_ARG, "bad loop closure");
+    PgFactor f;
+    pg_factor(f, 1, from, to, rel, g->cfg.loop_rotation_sigma, g->cfg.loop_translation_sigma);
+    g->factors.push_back(f);                       // pose_graph.cpp:132-134
+    g->num_loops++;                                // :136
+    g->optimized = false;                          // :137
+    return ICPMI_OK;
+}
+
+// grow keeping the first `used` bytes (the incremental uploads)
+static int pg_reserve_keep(icpmi_ctx *ctx, DevBuf &b, size_t used, size_t bytes)
+{
+    if (bytes <= b.cap) return ICPMI_OK;
+    DevBuf nb;
+    HIP_TRY(ctx, reserve_raw(nb, std::max(bytes, 2 * b.cap)));
+    if (used) HIP_TRY(ctx, hipMemcpyAsync(nb.p, b.p, used, hipMemcpyDeviceToDevice, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    release(b);
+    b = nb;
+    return ICPMI_OK;
+}
+
+int icpmi_pose_graph_optimize(icpmi_pose_graph *g, icpmi_pose_graph_info *info, double *history, int32_t history_cap)
+{
+    if (!g) return ICPMI_ERR_NULL;
+    icpmi_ctx *ctx = g->ctx;
+    int rc;
+    if ((rc = check_common(ctx))) return rc;
+    const icpmi_pose_graph_config &c = g->cfg;
+    if (history && history_cap < c.max_iterations + 1)
+        return fail(ctx, ICPMI_ERR_CAPACITY, "history needs max_iterations + 1 entries");
+    icpmi_pose_graph_info st;
+    memset(&st, 0, sizeof(st));
+    if (info) *info = st;
+    if (g->num_poses == 0) return ICPMI_OK;                 // pose_graph.cpp:148-150: false, nothing changes
+    for (const PgFactor &f : g->factors)
+        if (!pg_has(g, f.i) || (f.kind == 1 && !pg_has(g, f.j)))
+            return fail(ctx, ICPMI_ERR_ARG, "a factor names pose %lld, which has no estimate",
+                        (long long)(pg_has(g, f.i) ? f.j : f.i));   // the reference's catch (:166-169)
+    hipStream_t s = ctx->stream;
+    // only what was added since the last call goes up: the new factors and the new estimates
+    const size_t F = g->factors.size();
+    if ((rc = pg_reserve_keep(ctx, g->d_fac, sizeof(PgFactor) * g->uploaded_factors, sizeof(PgFactor) * F))) return rc;
+    if (F > g->uploaded_factors)
+        HIP_TRY(ctx, hipMemcpyAsync((PgFactor *)g->d_fac.p + g->uploaded_factors, g->factors.data() + g->uploaded_factors,
+                                    sizeof(PgFactor) * (F - g->uploaded_factors), hipMemcpyHostToDevice, s));
+    g->uploaded_factors = F;
+    const size_t init_used = g->d_init.cap / 96 * 96;
+    if ((rc = pg_reserve_keep(ctx, g->d_init, init_used, 96 * (size_t)g->num_poses))) return rc;
+    if (g->init_dirty_hi > g->init_dirty_lo) {
+        const int64_t lo = g->init_dirty_lo, hi = g->init_dirty_hi;
+        HIP_TRY(ctx, hipMemcpyAsync((double *)g->d_init.p + 12 * lo, g->init.data() + 12 * lo, 96 * (size_t)(hi - lo),
+                                    hipMemcpyHostToDevice, s));
+        g->init_dirty_lo = INT64_MAX;
+        g->init_dirty_hi = 0;
+    }
+    PgPlan P;
+    if ((rc = pg_plan(g, P))) return rc;
+    PgLin lin{(double *)g->d_A.p, (double *)g->d_rw.p, (double *)g->d_err.p, (double *)g->d_H.p, (double *)g->d_g.p};
+    // optimize() always starts from the initial estimates (pose_graph.cpp:153: the optimizer gets *initial_estimates_)
+    hipLaunchKernelGGL(k_pg_gather, dim3(pg_grid(12 * (size_t)P.n, 256)), dim3(256), 0, s, (const double *)g->d_init.p,
+                       (const int32_t *)g->d_keys.p, P.n, (double *)g->d_X.p);
+
+    // ---- LevenbergMarquardtParams defaults; the caller's maxIterations / relativeErrorTol / absoluteErrorTol
+    double lam = 1e-5;                                    // lambdaInitial
+    const double lam_factor = 10.0, lam_lower = 0.0, lam_upper = 1e5, min_fidelity = 1e-3;
+    const double rel_tol = c.relative_error_tol, abs_tol = c.absolute_error_tol, err_tol = 0.0;   // errorTol 0
+    double error;
+    if ((rc = pg_linearize(g, P, lin, &error))) return rc;
+    st.initial_error = error;
+    int nh = 0;
+    if (history) history[nh] = error;
+    ++nh;
+    bool linearized = true;                               // lin holds the linearisation at X
+    // NonlinearOptimizer::defaultOptimize: nothing to do when the error is already <= errorTol or no iteration allowed
+    if (error <= err_tol) st.stop_reason = ICPMI_PG_STOP_ZERO_ERROR;
+    else if (c.max_iterations <= 0) st.stop_reason = ICPMI_PG_STOP_MAX_ITERATIONS;
+    while (st.stop_reason == ICPMI_PG_STOP_NONE) {
+        const double current = error;
+        // LevenbergMarquardtOptimizer::iterate: linearise once, then tryLambda until it returns true
+        if (!linearized && (rc = pg_linearize(g, P, lin, nullptr))) return rc;
+        const double old_lin = current;                   // linear.error(VectorValues::Zero) = 0.5 sum ||rw||^2
+        bool stepped = false;
+        int inner_stop = ICPMI_PG_STOP_NONE;
+        double new_err = 0.0;
+        for (;;) {
+            st.inner_iterations++;
+            // tryLambda: buildDampedSystem adds lambda I (diagonalDamping off); solve; a Cholesky that meets a
+            // non-positive pivot is an unsolved system (IndeterminantLinearSystemException)
+            double out[3];
+            if ((rc = pg_trial(g, P, lin, lam, out))) return rc;
+            const bool solved = out[2] == 0.0 && std::isfinite(out[1]);
+            bool step_ok = false, stop_search = false;
+            if (solved) {
+                const double lin_change = old_lin - out[1];
+                if (lin_change >= 0.0) {                  // tryLambda: the step is valid
+                    new_err = out[0];
+                    const double cost_change = current - new_err;
+                    if (lin_change > std::numeric_limits<double>::epsilon() * old_lin)
+                        step_ok = cost_change / lin_change > min_fidelity;   // tryLambda: modelFidelity
+                    else
+                        step_ok = true;                   // linearised change ~ 0
+                    // tryLambda: stop searching lambda once |costChange| < relativeErrorTol * error
+                    stop_search = std::fabs(cost_change) < rel_tol * current;
+                }
+            }
+            if (step_ok) {
+                lam = std::max(lam_lower, lam / lam_factor);   // State::decreaseLambda (useFixedLambdaFactor)
+                std::swap(g->d_X, g->d_Xc);
+                error = new_err;
+                st.iterations++;
+                stepped = true;
+                break;
+            }
+            if (stop_search) {
+                inner_stop = ICPMI_PG_STOP_SMALL_COST_CHANGE;
+                break;
+            }
+            lam *= lam_factor;                            // State::increaseLambda
+            if (lam >= lam_upper) {                       // tryLambda: lambda too big, give up
+                inner_stop = ICPMI_PG_STOP_LAMBDA_BOUND;
+                break;
+            }
+        }
+        linearized = !stepped;
+        if (history) history[nh] = error;
+        ++nh;
+        // defaultOptimize's loop condition: iterations < maxIterations && !checkConvergence(...) && isfinite(error)
+        if (!stepped) st.stop_reason = inner_stop;        // the error did not move: checkConvergence holds
+        else if (st.iterations >= c.max_iterations) st.stop_reason = ICPMI_PG_STOP_MAX_ITERATIONS;
+        else if (!std::isfinite(current)) st.stop_reason = ICPMI_PG_STOP_NOT_FINITE;
+        else {
+            const double abs_dec = current - error, rel_dec = abs_dec / current;   // checkConvergence
+            if (error <= err_tol) st.stop_reason = ICPMI_PG_STOP_ZERO_ERROR;
+            else if (rel_tol != 0.0 && rel_dec <= rel_tol) st.stop_reason = ICPMI_PG_STOP_RELATIVE;
+            else if (abs_dec <= abs_tol) st.stop_reason = ICPMI_PG_STOP_ABSOLUTE;
+        }
+    }
+    // the optimised values back to the host, by pose index
+    std::vector<double> X(12 * (size_t)P.n);
+    HIP_TRY(ctx, hipMemcpyAsync(X.data(), g->d_X.p, sizeof(double) * X.size(), hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    HIP_TRY(ctx, hipGetLastError());
+    g->opt.assign(12 * (size_t)g->num_poses, 0.0);
+    for (int k = 0; k < P.n; ++k) std::copy(X.begin() + 12 * k, X.begin() + 12 * (k + 1), g->opt.begin() + 12 * (size_t)P.keys[k]);
+    g->optimized = true;                                  // pose_graph.cpp:160-162
+    st.optimized = 1;
+    st.final_error = error;
+    st.final_lambda = lam;
+    st.history_len = nh;
+    g->last = st;
+    if (info) *info = st;
+    return ICPMI_OK;
+}
+
+int icpmi_pose_graph_pose(icpmi_pose_graph *g, int64_t index, double pose[16])
+{
+    if (!g) return ICPMI_ERR_NULL;
+    if (!pose) return fail(g->ctx, ICPMI_ERR_NULL, "pose is NULL");
+    if (!pg_has(g, index)) return fail(g->ctx, ICPMI_ERR_ARG, "Pose index %lld not found", (long long)index);   // :181-183
+    pg_to16((g->optimized ? g->opt.data() : g->init.data()) + 12 * index, pose);   // :180
+    return ICPMI_OK;
+}
+
+int icpmi_pose_graph_poses(icpmi_pose_graph *g, double *poses, int64_t cap, int64_t *n_out, int64_t *indices)
+{
+    if (!g) return ICPMI_ERR_NULL;
+    int64_t cnt = 0;
+    for (int64_t k = 0; k < g->num_poses; ++k) cnt += pg_has(g, k);
+    if (n_out) *n_out = cnt;
+    if (!poses && !indices) return ICPMI_OK;
+    if (cap < cnt) return fail(g->ctx, ICPMI_ERR_CAPACITY, "%lld poses need room", (long long)cnt);
+    const double *src = g->optimized ? g->opt.data() : g->init.data();
+    int64_t o = 0;
+    for (int64_t k = 0; k < g->num_poses; ++k)      // pose_graph.cpp:194-198: 0 .. num_poses_-1, gaps skipped
+        if (pg_has(g, k)) {
+            if (poses) pg_to16(src + 12 * k, poses + 16 * o);
+            if (indices) indices[o] = k;
+            ++o;
+        }
+    return ICPMI_OK;
+}
+
+int icpmi_pose_graph_size(const icpmi_pose_graph *g, int64_t *num_poses, int64_t *num_loop_closures,
+                          icpmi_pose_graph_info *last)
+{
+    if (!g) return ICPMI_ERR_NULL;
+    if (num_poses) *num_poses = g->num_poses;                 // pose_graph.hpp:117
+    if (num_loop_closures) *num_loop_closures = g->num_loops; // :122
+    if (last) *last = g->last;                                // :127-128 (final error, iterations)
+    return ICPMI_OK;
 }
 
 } // extern "C"

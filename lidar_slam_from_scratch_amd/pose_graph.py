@@ -1,0 +1,132 @@
+"""slam::PoseGraph (core/pose_graph.hpp:49-147, src/core/pose_graph.cpp) through the C ABI: the factors and estimates
+live on the device (icpmi_pose_graph), Levenberg-Marquardt runs there (csrc/pose_graph.h).  Method names follow the
+reference's, in Python spelling.  `stats` holds the last optimize()'s icpmi_pose_graph_info and error history."""
+import ctypes as C
+import weakref
+
+import numpy as np
+
+from . import capi
+
+
+class PoseGraphConfig:
+    """pose_graph.hpp:22-40"""
+
+    def __init__(self, **kw):
+        c = capi.PoseGraphConfig()
+        capi.load_library().icpmi_pose_graph_config_default(C.byref(c))
+        for name, _t in capi.PoseGraphConfig._fields_:
+            if name != "reserved":
+                setattr(self, name, getattr(c, name))
+        for k, v in kw.items():
+            if not hasattr(self, k):
+                raise TypeError(k)
+            setattr(self, k, v)
+
+    def to_c(self):
+        c = capi.PoseGraphConfig()
+        for name, _t in capi.PoseGraphConfig._fields_:
+            if name != "reserved":
+                setattr(c, name, getattr(self, name))
+        return c
+
+
+class PoseGraphStats:
+    def __init__(self, info, history):
+        self.optimized = bool(info.optimized)
+        self.iterations = info.iterations
+        self.inner_trials = info.inner_iterations
+        self.stop_reason = info.stop_reason
+        self.initial_error = info.initial_error
+        self.final_error = info.final_error
+        self.final_lambda = info.final_lambda
+        self.history = list(history[:info.history_len])
+
+
+def _T(pose):
+    T = np.ascontiguousarray(pose, dtype=np.float64)
+    if T.shape != (4, 4):
+        raise ValueError("expected a 4 x 4 transform")
+    return T
+
+
+class PoseGraph:
+    def __init__(self, ctx, config=None):
+        self._lib = capi.load_library()
+        self.ctx = ctx
+        self.config = config or PoseGraphConfig()
+        h = C.c_void_p()
+        cfg = self.config.to_c()
+        ctx._check(self._lib.icpmi_pose_graph_create(ctx._h, C.byref(cfg), C.byref(h)))
+        self._h = h
+        self.stats = None
+        if not hasattr(ctx, "_pose_graphs"):
+            ctx._pose_graphs = weakref.WeakSet()
+        ctx._pose_graphs.add(self)     # Context.close() destroys the graph first
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.icpmi_pose_graph_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def add_prior(self, index, pose):
+        """pose_graph.cpp:58-79"""
+        T = _T(pose)
+        self.ctx._check(self._lib.icpmi_pose_graph_add_prior(self._h, int(index), capi._dp(T)))
+
+    def add_odometry_factor(self, from_idx, to_idx, relative_transform, fitness_score=0.0):
+        """pose_graph.cpp:81-116"""
+        T = _T(relative_transform)
+        self.ctx._check(self._lib.icpmi_pose_graph_add_odometry(self._h, int(from_idx), int(to_idx), capi._dp(T),
+                                                                float(fitness_score)))
+
+    def add_loop_closure(self, from_idx, to_idx, relative_transform):
+        """pose_graph.cpp:118-141"""
+        T = _T(relative_transform)
+        self.ctx._check(self._lib.icpmi_pose_graph_add_loop_closure(self._h, int(from_idx), int(to_idx), capi._dp(T)))
+
+    def optimize(self):
+        """pose_graph.cpp:147-171: False on an empty graph or where a factor names a pose with no estimate"""
+        info = capi.PoseGraphInfo()
+        hist = np.zeros(self.config.max_iterations + 1)
+        rc = self._lib.icpmi_pose_graph_optimize(self._h, C.byref(info), capi._dp(hist), hist.shape[0])
+        if rc == capi.ERR_ARG:
+            self.stats = None
+            return False
+        self.ctx._check(rc)
+        self.stats = PoseGraphStats(info, hist)
+        return bool(info.optimized)
+
+    def get_pose(self, index):
+        """pose_graph.cpp:177-186"""
+        out = np.zeros((4, 4))
+        self.ctx._check(self._lib.icpmi_pose_graph_pose(self._h, int(index), capi._dp(out)))
+        return out
+
+    def get_all_poses(self):
+        """pose_graph.cpp:188-200"""
+        n = C.c_int64(0)
+        self.ctx._check(self._lib.icpmi_pose_graph_poses(self._h, None, 0, C.byref(n), None))
+        out = np.zeros((n.value, 4, 4))
+        if n.value:
+            self.ctx._check(self._lib.icpmi_pose_graph_poses(self._h, capi._dp(out), n.value, C.byref(n), None))
+        return list(out)
+
+    def _size(self):
+        n, lc, info = C.c_int64(0), C.c_int64(0), capi.PoseGraphInfo()
+        self.ctx._check(self._lib.icpmi_pose_graph_size(self._h, C.byref(n), C.byref(lc), C.byref(info)))
+        return n.value, lc.value, info
+
+    def size(self):
+        return self._size()[0]
+
+    def loop_closure_count(self):
+        return self._size()[1]
+
+    def get_final_error(self):
+        return self._size()[2].final_error
+
+    def get_iterations(self):
+        return self._size()[2].iterations

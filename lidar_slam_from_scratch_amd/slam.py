@@ -1,0 +1,90 @@
+"""The reference node's whole loop without ROS: SlamNode's timer (slam_viz/src/ros/slam_node.cpp:63-185) over
+already-downsampled frames, with registration, loop closure and the pose-graph back end behind it.
+
+    pose_graph_.addPrior(0, identity)                                   :66
+    per frame k >= 1 (process_frame, :118-175):
+        too few points: repeat the last pose, no factor, no addFrame    :125-130
+        ICP against the previous frame, identity if not converged or final_error > 1   :132-142
+        addOdometryFactor(k-1, k, delta, final_error)                   :145
+        loop_detector_.addFrame(curr, k)                                :159
+        every 10 frames after 50: detect(), addLoopClosure(match, query, T) per closure   :160-167
+    optimize after a frame that found closures (:112-115) and at the end (:106); on success the track's poses become
+    getAllPoses() (:177-185).
+
+The detector uses the node's LoopClosureConfig (:77-81).  By default everything runs through the library on `ctx`;
+`align`, `loop_backend` and `pose_graph` replace the three parts (the tests put the CPU oracle and
+scripts/pose_graph_ref.py there).  As in the reference, the frame after a too-few-points frame names a pose with no
+estimate: its addOdometryFactor raises (ICPMI_ERR_ARG), where the reference throws."""
+import numpy as np
+
+from . import loop_closure as lc
+
+
+class SlamRun:
+    def __init__(self):
+        self.poses = [np.eye(4)]      # slam_node.cpp:64
+        self.factors = []             # ("prior", i, T) / ("odom", i, j, T, fitness) / ("loop", i, j, T), in call order
+        self.closures = []            # LoopClosureResult, in the order found
+        self.optimizations = []       # (frame index or "end", ok, stats) per optimize()
+
+
+def node_loop_config():
+    """slam_node.cpp:77-80"""
+    return lc.LoopClosureConfig(frame_gap=50, sc_distance_threshold=0.2, icp_fitness_threshold=0.3)
+
+
+def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, pose_graph_config=None,
+             align=None, loop_backend=None, pose_graph=None):
+    """frames: sequence of N x 3 fp64 clouds (already downsampled).  Returns a SlamRun."""
+    if align is None:
+        from .odometry import gpu_align
+        align = gpu_align(ctx)
+    if loop_backend is None:
+        loop_backend = lc.GpuBackend(ctx)
+    if pose_graph is None:
+        from .pose_graph import PoseGraph
+        pose_graph = PoseGraph(ctx, pose_graph_config)
+    run = SlamRun()
+    detector = lc.LoopClosureDetector(loop_backend, node_loop_config())
+
+    def add(kind, *args):
+        run.factors.append((kind,) + args)
+        if kind == "prior":
+            pose_graph.add_prior(*args)
+        elif kind == "odom":
+            pose_graph.add_odometry_factor(*args)
+        else:
+            pose_graph.add_loop_closure(*args)
+
+    def optimize(tag):                                               # run_pose_graph_optimization, :177-185
+        ok = pose_graph.optimize()
+        run.optimizations.append((tag, ok, pose_graph.stats))
+        if ok:
+            run.poses = [np.asarray(p) for p in pose_graph.get_all_poses()]
+
+    add("prior", 0, np.eye(4))                                       # :66
+    frames = list(frames)
+    prev = np.ascontiguousarray(frames[0], dtype=np.float64)         # :69-72
+    for k in range(1, len(frames)):
+        curr = np.ascontiguousarray(frames[k], dtype=np.float64)
+        pending = False
+        if curr.shape[0] < min_points:                               # :125-130
+            run.poses.append(run.poses[-1].copy())
+            prev = curr
+            continue
+        r = align(curr, prev, max_iterations, tolerance)             # :132-138
+        bad = (not r.converged) or r.final_error > 1.0               # :139-140
+        delta = np.eye(4) if bad else np.asarray(r.transformation, dtype=np.float64)
+        run.poses.append(run.poses[-1] @ delta)                      # :142-143
+        add("odom", len(run.poses) - 2, len(run.poses) - 1, delta, float(r.final_error))   # :145
+        prev = curr                                                  # :151
+        detector.add_frame(curr, k)                                  # :159
+        if k % 10 == 0 and k > 50:                                   # :160
+            for c in detector.detect():                              # :161-166
+                add("loop", c.match_frame, c.query_frame, np.asarray(c.transform, dtype=np.float64))
+                run.closures.append(c)
+                pending = True
+        if pending:                                                  # :112-115
+            optimize(k)
+    optimize("end")                                                  # :103-106
+    return run

@@ -1,0 +1,283 @@
+"""The device pose-graph optimiser (icpmi_pose_graph_*, csrc/pose_graph.h) against the CPU restatement of the
+reference's GTSAM back end (scripts/pose_graph_ref.py) on the same factors.
+
+Tolerance per pose: 10x the restatement's own spread (COLAMD against NATURAL ordering in splu), at least
+1e-12 (1 + |t|).  Iterations, lambda trials and the error history must match.  A case whose nearest LM decision has a
+relative margin below 1e-6 in the restatement is sensitive: its seed is changed, never excused (asserted below).
+Cases sit at the solver's dispatch edges: chain lengths around K (every K-th pose index is a separator), loops sharing
+an endpoint, a loop between adjacent indices (a chain factor), duplicates, out-of-order factors, a skipped index,
+rejected steps, the relative test switched off and a KITTI-00-sized graph."""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "scripts"))
+
+import pose_graph_ref as R  # noqa: E402
+from lidar_slam_from_scratch_amd import synth  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+K = 64   # kPgChainK (csrc/pose_graph.h)
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    """Fails loudly (no skip, no fallback) when the HIP library or the device is missing."""
+    from lidar_slam_from_scratch_amd import build, capi
+    build.build_library()
+    c = capi.Context(device=0)
+    yield c
+    c.close()
+
+
+def _noise(rng, rs=0.004, ts=0.03):
+    return R.se3_exp(np.r_[rng.normal(0, rs, 3), rng.normal(0, ts, 3)])
+
+
+def _rel(a, b):
+    return np.linalg.inv(a) @ b
+
+
+def _drive(n, seed, step=1.5, turn=0.02):
+    rng = np.random.default_rng(seed)
+    T = [np.eye(4)]
+    for _ in range(n - 1):
+        T.append(T[-1] @ synth.make_transform([0, 0, turn + rng.normal(0, 0.01)], [step, rng.normal(0, 0.05), 0]))
+    return T
+
+
+def chain_ops(n, seed):
+    rng = np.random.default_rng(seed)
+    gt = _drive(n, seed)
+    ops = [("prior", 0, gt[0])]
+    ops += [("odom", k, k + 1, _rel(gt[k], gt[k + 1]) @ _noise(rng), 0.05 * rng.uniform()) for k in range(n - 1)]
+    ops.append(("prior", n - 1, gt[n - 1] @ _noise(rng, 0.01, 0.2)))   # something to pull against
+    return ops
+
+
+def ring_ops(n, seed, loops, drift=0.0):
+    rng = np.random.default_rng(seed)
+    gt = [synth.make_transform([0, 0, 2 * np.pi * k / n], [30 * np.cos(2 * np.pi * k / n), 30 * np.sin(2 * np.pi * k / n),
+                                                           0.3 * np.sin(6 * np.pi * k / n)]) for k in range(n)]
+    ops = [("prior", 0, gt[0])]
+    for k in range(n - 1):
+        d = synth.make_transform([0, 0, drift], [0, 0, 0])
+        ops.append(("odom", k, k + 1, _rel(gt[k], gt[k + 1]) @ d @ _noise(rng), 0.0))
+    ops += [("loop", i, j, _rel(gt[i], gt[j]) @ _noise(rng, 0.001, 0.01)) for i, j in loops]
+    return ops
+
+
+def kitti_ops(seed=7, n=4541, lap=900, every=30):
+    """4,541 poses, 4,540 odometry factors, three closures per query (as detect() yields) on later laps."""
+    rng = np.random.default_rng(seed)
+    gt = []
+    for k in range(n):
+        a = 2 * np.pi * (k % lap) / lap
+        gt.append(synth.make_transform([0, 0, a], [200 * np.cos(a), 120 * np.sin(a), 2 * np.sin(3 * a)]))
+    ops = [("prior", 0, gt[0])]
+    ops += [("odom", k, k + 1, _rel(gt[k], gt[k + 1]) @ _noise(rng, 0.002, 0.02), 0.02 * rng.uniform())
+            for k in range(n - 1)]
+    for q in range(lap + 60, n, every):
+        for m in (q - lap - 1, q - lap, q - lap + 2):
+            ops.append(("loop", m, q, _rel(gt[m], gt[q]) @ _noise(rng, 0.001, 0.01)))
+    return ops
+
+
+def apply(g, ops):
+    for op in ops:
+        if op[0] == "prior":
+            g.add_prior(op[1], op[2])
+        elif op[0] == "odom":
+            g.add_odometry_factor(op[1], op[2], op[3], op[4])
+        else:
+            g.add_loop_closure(op[1], op[2], op[3])
+
+
+def run_case(ctx, ops, max_iterations=100, rel_tol=1e-5):
+    from lidar_slam_from_scratch_amd import pose_graph as pg
+    ref = R.PoseGraph(R.PoseGraphConfig(max_iterations=max_iterations, relative_error_tol=rel_tol))
+    apply(ref, ops)
+    assert ref.optimize("COLAMD")
+    a, sa = np.stack(ref.get_all_poses()), ref.stats
+    assert ref.optimize("NATURAL")
+    b, sb = np.stack(ref.get_all_poses()), ref.stats
+    assert (sa.iterations, sa.inner_trials) == (sb.iterations, sb.inner_trials)
+    assert sa.min_margin > 1e-6, "sensitive case: change its seed (margin %.3g)" % sa.min_margin
+    dev = pg.PoseGraph(ctx, pg.PoseGraphConfig(max_iterations=max_iterations, relative_error_tol=rel_tol))
+    apply(dev, ops)
+    assert dev.optimize()
+    got = np.stack(dev.get_all_poses())
+    st = dev.stats
+    assert got.shape == a.shape
+    assert (st.iterations, st.inner_trials, st.stop_reason) == (sa.iterations, sa.inner_trials, sa.stop_reason), \
+        ((st.iterations, st.inner_trials, st.stop_reason), (sa.iterations, sa.inner_trials, sa.stop_reason))
+    spread = np.abs(a - b).reshape(len(a), -1).max(axis=1)
+    floor = 1e-12 * (1.0 + np.linalg.norm(a[:, :3, 3], axis=1))
+    tol = np.maximum(10 * spread, floor)
+    err = np.abs(got - a).reshape(len(a), -1).max(axis=1)
+    assert (err <= tol).all(), (int(np.argmax(err / tol)), float(np.max(err / tol)))
+    hs = np.abs(np.array(sa.history) - np.array(sb.history))
+    htol = np.maximum(10 * hs, 1e-12 * (1 + np.abs(sa.history)))
+    assert len(st.history) == len(sa.history)
+    assert (np.abs(np.array(st.history) - sa.history) <= htol).all(), (st.history, sa.history)
+    return dev, st
+
+
+@pytest.mark.parametrize("n", [K - 1, K, K + 1, 3 * K - 1, 3 * K + 1])
+def test_pure_chain(ctx, n):
+    _, st = run_case(ctx, chain_ops(n, seed=n))
+    print("chain", n, st.iterations, st.inner_trials)
+
+
+def test_loops_sharing_one_endpoint(ctx):
+    loops = [(m, q) for q in (150, 170, 190) for m in (q - 140, q - 139, q - 137)]
+    _, st = run_case(ctx, ring_ops(200, 3, loops))
+    print("shared", st.iterations, st.inner_trials)
+
+
+def test_loop_between_adjacent_indices_is_chain(ctx):
+    _, st = run_case(ctx, ring_ops(100, 4, [(40, 41), (0, 99), (62, 63), (63, 64)]))
+    print("adjacent", st.iterations, st.inner_trials)
+
+
+def test_duplicate_factors(ctx):
+    ops = ring_ops(90, 5, [(0, 80), (0, 80), (10, 85)])
+    ops += [op for op in ops if op[0] == "odom" and op[1] in (20, 63)]
+    _, st = run_case(ctx, ops)
+    print("duplicates", st.iterations, st.inner_trials)
+
+
+def test_factors_out_of_index_order(ctx):
+    ops = ring_ops(120, 6, [(5, 110), (30, 100)])
+    rng = np.random.default_rng(6)
+    head, tail = ops[:1], ops[1:]
+    odo = [op for op in tail if op[0] == "odom"]
+    rest = [op for op in tail if op[0] != "odom"]
+    # chain order is needed for the estimates; the loops and a second prior go first, odometry in pieces
+    order = rest + odo
+    perm = list(rng.permutation(len(rest)))
+    _, st = run_case(ctx, head + [rest[i] for i in perm] + [o for o in order if o[0] == "odom"])
+    print("out_of_order", st.iterations, st.inner_trials)
+
+
+def test_odometry_skipping_an_index(ctx):
+    ops = ring_ops(80, 8, [(0, 75)])
+    ops = [op for op in ops if not (op[0] == "odom" and op[1] in (30, 31))]
+    z30, z31 = [op[3] for op in ring_ops(80, 8, []) if op[0] == "odom" and op[1] in (30, 31)]
+    ops.insert(31, ("odom", 30, 32, z30 @ z31, 0.0))
+    dev, st = run_case(ctx, ops)
+    assert dev.size() == 80 and len(dev.get_all_poses()) == 79
+    print("skip", st.iterations, st.inner_trials)
+
+
+def test_rejected_steps(ctx):
+    g = [("prior", 0, np.eye(4))]
+    n, drift = 60, 0.1
+    a = 2 * np.pi / n
+    Z = synth.make_transform([0, 0, a + drift], [2.0, 0, 0])
+    g += [("odom", k, k + 1, Z, 0.0) for k in range(n - 1)]
+    g += [("loop", 0, n - 1, synth.make_transform([0, 0, -a], [-2.0, 0, 0])),
+          ("loop", 0, n // 2, synth.make_transform([0, 0, np.pi], [0, 2 * n / np.pi, 0]))]
+    _, st = run_case(ctx, g)
+    assert st.inner_trials > st.iterations + 1
+    print("rejected", st.iterations, st.inner_trials)
+
+
+def test_relative_test_off(ctx):
+    """relative_error_tol 0: checkConvergence's relative clause is skipped and the absolute one stops the loop."""
+    from lidar_slam_from_scratch_amd import capi
+    _, st = run_case(ctx, chain_ops(20, seed=9), rel_tol=0.0)
+    assert st.stop_reason == capi.PG_STOP_ABSOLUTE
+    print("relative_off", st.iterations, st.inner_trials)
+
+
+def test_kitti_shaped_graph(ctx):
+    ops = kitti_ops()
+    assert sum(op[0] == "odom" for op in ops) == 4540
+    dev, st = run_case(ctx, ops)
+    assert dev.size() == 4541 and dev.loop_closure_count() > 200
+    print("kitti", st.iterations, st.inner_trials, dev.loop_closure_count())
+
+
+def test_repeated_optimize_is_bit_identical(ctx):
+    from lidar_slam_from_scratch_amd import pose_graph as pg
+    dev = pg.PoseGraph(ctx)
+    apply(dev, ring_ops(300, 10, [(0, 290), (10, 280), (100, 250)]))
+    assert dev.optimize()
+    a = np.stack(dev.get_all_poses())
+    assert dev.optimize()
+    assert (np.stack(dev.get_all_poses()) == a).all()
+
+
+def test_error_paths(ctx):
+    from lidar_slam_from_scratch_amd import capi
+    from lidar_slam_from_scratch_amd import pose_graph as pg
+    g = pg.PoseGraph(ctx)
+    assert not g.optimize()                                   # empty graph
+    g.add_prior(0, np.eye(4))
+    with pytest.raises(capi.IcpError) as e:
+        g.add_odometry_factor(3, 4, np.eye(4))                # no estimate for `from`
+    assert e.value.code == capi.ERR_ARG and g.size() == 1
+    with pytest.raises(capi.IcpError):
+        g.add_loop_closure(0, 0, np.eye(4))                   # from == to
+    bad = np.eye(4)
+    bad[1, 3] = np.nan
+    with pytest.raises(capi.IcpError):
+        g.add_odometry_factor(0, 1, bad)
+    g.add_odometry_factor(0, 1, synth.make_transform([0, 0, 0.1], [1, 0, 0]))
+    g.add_odometry_factor(1, 3, synth.make_transform([0, 0, 0.1], [1, 0, 0]))
+    with pytest.raises(capi.IcpError) as e:
+        g.get_pose(2)                                         # a gap
+    assert e.value.code == capi.ERR_ARG
+    assert len(g.get_all_poses()) == 3
+    assert g.optimize()
+    g.add_loop_closure(0, 7, np.eye(4))                       # onto a pose with no estimate
+    assert not g.optimize()
+    assert len(g.get_all_poses()) == 3
+
+
+def test_run_slam_out_and_back(ctx):
+    """The node's loop (lidar_slam_from_scratch_amd.slam.run_slam) on the synthetic street driven 60 frames out and
+    back: queries from frame 90 on revisit frames at least 50 back.  The factor list must be the node's, and the final
+    poses the restatement's optimum of that list."""
+    from lidar_slam_from_scratch_amd import slam
+    order = list(range(60)) + list(range(59, -1, -1))
+    cache = {}
+    for f in set(order):
+        cache[f] = synth.lidar_frame(f, beams=32, azimuths=900, **synth.DRIVE_200)
+    run = slam.run_slam([cache[f] for f in order], ctx)
+    assert run.closures, "no loop closure found"
+    assert any(c.query_frame >= 90 and c.query_frame - c.match_frame >= 50 for c in run.closures)
+    # the node's rules: prior at 0, then odometry k-1 -> k for every frame, closures (match, query) after frames
+    # k % 10 == 0, k > 50, in the detector's order
+    n = len(order)
+    kinds = [f[0] for f in run.factors]
+    assert run.factors[0][:2] == ("prior", 0) and (run.factors[0][2] == np.eye(4)).all()
+    odo = [f for f in run.factors if f[0] == "odom"]
+    assert [(f[1], f[2]) for f in odo] == [(k - 1, k) for k in range(1, n)]
+    loops = [f for f in run.factors if f[0] == "loop"]
+    assert [(f[1], f[2]) for f in loops] == [(c.match_frame, c.query_frame) for c in run.closures]
+    for f in loops:
+        pos = run.factors.index(f)
+        q = f[2]
+        assert q % 10 == 0 and q > 50 and kinds[pos - 1] in ("odom", "loop")
+        assert max(i for i, g in enumerate(run.factors) if g[0] == "odom" and g[2] == q) < pos
+    assert [o[0] for o in run.optimizations] == sorted({c.query_frame for c in run.closures}) + ["end"]
+    assert all(o[1] for o in run.optimizations)
+    # the final poses: the restatement on the same factor list, two orderings for the spread
+    ref = R.PoseGraph()
+    apply(ref, run.factors)
+    assert ref.optimize("COLAMD")
+    a = np.stack(ref.get_all_poses())
+    assert ref.optimize("NATURAL")
+    b = np.stack(ref.get_all_poses())
+    got = np.stack(run.poses)
+    tol = np.maximum(10 * np.abs(a - b).reshape(n, -1).max(axis=1), 1e-12 * (1 + np.linalg.norm(a[:, :3, 3], axis=1)))
+    assert (np.abs(got - a).reshape(n, -1).max(axis=1) <= tol).all()
+    st = run.optimizations[-1][2]
+    assert (st.iterations, st.inner_trials) == (ref.stats.iterations, ref.stats.inner_trials)
+    print("run_slam closures", len(run.closures), "optimizations", [(o[0], o[2].iterations) for o in run.optimizations])

@@ -1,0 +1,11 @@
+"""The pose-graph part of the C++ mirror header (include/icp_mi355x.hpp): tests/cpp/pose_graph_demo.cpp, the node's
+use of slam::PoseGraph with the mirror behind it, must compile cleanly.  Runs on the CPU (no device needed)."""
+import os
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_pose_graph_demo_compiles():
+    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-fsyntax-only",
+                           "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "pose_graph_demo.cpp")])
