@@ -446,6 +446,49 @@ int icpmi_pose_graph_poses(icpmi_pose_graph *graph, double *poses, int64_t cap, 
 int icpmi_pose_graph_size(const icpmi_pose_graph *graph, int64_t *num_poses, int64_t *num_loop_closures,
                           icpmi_pose_graph_info *last);
 
+/* Global map: the node's kept filtered scans and what it builds from them with the optimised poses
+ * (slam_viz/src/ros/slam_node.cpp):
+ *     downsampled_clouds_.push_back(curr)                      :71, :123      icpmi_map_add_frame*
+ *     rebuild_recent_clouds (after each successful optimize)   :177-194       icpmi_map_world, first = max(0, frames - 20)
+ *     build_final_global_map                                   :196-209       icpmi_map_world, first = 0
+ *     rebuild_occupancy_grid: clear, then each frame with its own :223-229    icpmi_map_finish (grid)
+ *         pose's translation as the sensor position
+ *     publish_global_map once complete: voxel_downsample(       :235-238      icpmi_map_finish (voxel_size)
+ *         global_map_points_, 2 * voxel_size)
+ * The rows live in one device arena owned by the handle, frame after frame; frame k is the k-th add.  Frames of 0
+ * rows are legal.  A call uses frames i < min(frames, n_poses) (the reference's i < downsampled_clouds_.size() &&
+ * i < poses_.size()); poses are n_poses row-major 4 x 4 (extra ones are ignored), a NULL array with n_poses > 0 is
+ * ICPMI_ERR_NULL and a non-finite entry among the used ones ICPMI_ERR_ARG.  World points are
+ * ((x R_a0 + y R_a1) + z R_a2) + t_a, bit for bit those of icpmi_stream_map_update and icpmi_transform_points.
+ * The store holds at most 700,000,000 rows: an add past that is ICPMI_ERR_ARG and changes nothing.  The handle uses
+ * its context's device and stream, with the same lifetime rules as icpmi_pose_graph: destroy it before its context.
+ * Each call waits for the device once (icpmi_map_finish: once for the counts, once more for the published map). */
+typedef struct icpmi_map icpmi_map;
+int icpmi_map_create(icpmi_ctx *ctx, icpmi_map **out);
+void icpmi_map_destroy(icpmi_map *map);
+int icpmi_map_add_frame(icpmi_map *map, const double *xyz, int64_t n);           /* n x 3 rows in host memory */
+int icpmi_map_add_frame_device(icpmi_map *map, const double *d_xyz, int64_t n);  /* ... in device memory */
+/* the filtered scan the last icpmi_stream_push* left resident (too-few-points scans included), device to device;
+ * ICPMI_ERR_ARG if there is none */
+int icpmi_map_add_stream_frame(icpmi_map *map);
+int icpmi_map_size(const icpmi_map *map, int64_t *frames, int64_t *points);      /* either may be NULL */
+/* World points of frames [first, min(frames, n_poses)), frame then row order, into out_xyz (host, cap rows; fewer
+ * than *n_out is ICPMI_ERR_CAPACITY).  out_xyz may be NULL: only *n_out is set, no device work.
+ * rebuild_recent_clouds is first = max(0, frames - 20); build_final_global_map is first = 0. */
+int icpmi_map_world(icpmi_map *map, const double *poses, int64_t n_poses, int64_t first, double *out_xyz, int64_t cap,
+                    int64_t *n_out);
+/* build_final_global_map's tail in one world pass; the global map itself never leaves the device.
+ *   grid (may be NULL: the set is untouched): rebuild_occupancy_grid into the context's cell set, which
+ *     icpmi_occupancy_cells then reads and later updates merge into.  The rebuilt set replaces the old one only if
+ *     the whole call succeeds.  Frames the per-frame path never inserts (the first, too-few-points ones) are in it,
+ *     as in the reference.
+ *   voxel_size > 0 and map_out not NULL (else skipped): voxel_downsample(global map, voxel_size) into map_out
+ *     (map_cap rows; too few is ICPMI_ERR_CAPACITY), *n_map its rows.  The rules of icpmi_voxel_downsample hold: more
+ *     than 2^21 voxels on an axis is ICPMI_ERR_ARG.
+ * n_map and n_cells may be NULL. */
+int icpmi_map_finish(icpmi_map *map, const double *poses, int64_t n_poses, const icpmi_grid_config *grid,
+                     double voxel_size, double *map_out, int64_t map_cap, int64_t *n_map, int64_t *n_cells);
+
 /* profiling */
 int icpmi_reset_profile(icpmi_ctx *ctx);
 int icpmi_get_profile(icpmi_ctx *ctx, icpmi_profile *out);

@@ -23,6 +23,8 @@
 //                                                        OccupancyGridConfig, GridCell, OccupancyGrid
 //   slam::PoseGraphConfig / slam::PoseGraph
 //                               pose_graph.hpp:22-147        PoseGraphConfig, PoseGraph (device Levenberg-Marquardt)
+//   downsampled_clouds_ / rebuild_recent_clouds / build_final_global_map / rebuild_occupancy_grid / publish_global_map
+//     (slam_node.cpp:71,123,187-209,223-229,235-238)       GlobalMap (kept scans in device memory)
 //
 // A caller that already has Eigen and the reference's own types uses
 // slam_icp_adapter.hpp instead, which keeps slam::icp_point_to_plane's exact signature.
@@ -785,6 +787,110 @@ private:
     }
     Context *ctx_;
     icpmi_pose_graph *g_ = nullptr;
+};
+
+// The node's kept scans (downsampled_clouds_, slam_node.cpp:71,123) in device memory, and what it builds from them
+// with the optimised poses: rebuild_recent_clouds (:187-194), build_final_global_map (:196-209) with
+// rebuild_occupancy_grid (:223-229), and the map publish_global_map sends once complete (:235-238).  finish() rebuilds
+// the cell set of the context, which OccupancyGrid::cells() on the same context reads.
+class GlobalMap {
+public:
+    static constexpr std::size_t kMaxRecentClouds = 20; // slam_node.hpp:169
+
+    explicit GlobalMap(Context *ctx = nullptr) : ctx_(ctx ? ctx : &default_context()) { check(icpmi_map_create(ctx_->get(), &m_)); }
+    ~GlobalMap() { icpmi_map_destroy(m_); }
+    GlobalMap(const GlobalMap &) = delete;
+    GlobalMap &operator=(const GlobalMap &) = delete;
+    GlobalMap(GlobalMap &&o) noexcept : ctx_(o.ctx_), m_(o.m_), rows_(std::move(o.rows_)) { o.m_ = nullptr; }
+    GlobalMap &operator=(GlobalMap &&o) noexcept
+    {
+        if (this != &o) {
+            icpmi_map_destroy(m_);
+            ctx_ = o.ctx_;
+            m_ = o.m_;
+            rows_ = std::move(o.rows_);
+            o.m_ = nullptr;
+        }
+        return *this;
+    }
+
+    // downsampled_clouds_.push_back(curr) (:71, :123)
+    void add_frame(const PointCloud &cloud)
+    {
+        check(icpmi_map_add_frame(m_, cloud.data(), static_cast<int64_t>(cloud.size())));
+        rows_.push_back(cloud.size());
+    }
+    // the same for the scan an OdometryStream on this context pushed last, without a trip through the host
+    void add_stream_frame()
+    {
+        const int64_t before = points();
+        check(icpmi_map_add_stream_frame(m_));
+        rows_.push_back(static_cast<std::size_t>(points() - before));
+    }
+    std::size_t frames() const { return rows_.size(); }
+
+    // rebuild_recent_clouds (:187-194): one world cloud per frame of the last kMaxRecentClouds
+    std::vector<PointCloud> recent_clouds(const std::vector<Transformation> &poses) const
+    {
+        const std::size_t first = rows_.size() > kMaxRecentClouds ? rows_.size() - kMaxRecentClouds : 0;
+        const std::vector<double> w = world(poses, first);
+        std::vector<PointCloud> out;
+        std::size_t at = 0;
+        for (std::size_t i = first; i < rows_.size() && i < poses.size(); ++i) {
+            out.emplace_back(w.data() + 3 * at, rows_[i]);
+            at += rows_[i];
+        }
+        return out;
+    }
+    // build_final_global_map (:196-209): global_map_points_
+    PointCloud global_map(const std::vector<Transformation> &poses) const { return PointCloud(world(poses, 0)); }
+    // rebuild_occupancy_grid (:223-229) into the context's cell set, and voxel_downsample(global map, voxel_size)
+    // (:235-238) of a global map that never leaves the device
+    PointCloud finish(const std::vector<Transformation> &poses, const OccupancyGridConfig &grid, double voxel_size)
+    {
+        const std::vector<double> P = flatten(poses);
+        const icpmi_grid_config g = detail::to_c(grid);
+        std::size_t rows = 0;
+        for (std::size_t i = 0; i < rows_.size() && i < poses.size(); ++i) rows += rows_[i];
+        std::vector<double> out(3 * std::max<std::size_t>(rows, 1));
+        int64_t n = 0;
+        check(icpmi_map_finish(m_, P.data(), static_cast<int64_t>(poses.size()), &g, voxel_size, out.data(),
+                               static_cast<int64_t>(rows), &n, nullptr));
+        out.resize(3 * static_cast<std::size_t>(n));
+        return PointCloud(std::move(out));
+    }
+    icpmi_map *get() const { return m_; }
+
+private:
+    void check(int rc) const
+    {
+        if (rc != ICPMI_OK) throw IcpError(rc, icpmi_last_error(ctx_->get()));
+    }
+    int64_t points() const
+    {
+        int64_t n = 0;
+        check(icpmi_map_size(m_, nullptr, &n));
+        return n;
+    }
+    static std::vector<double> flatten(const std::vector<Transformation> &poses)
+    {
+        std::vector<double> P;
+        P.reserve(16 * poses.size());
+        for (const Transformation &T : poses) P.insert(P.end(), T.matrix().begin(), T.matrix().end());
+        return P;
+    }
+    std::vector<double> world(const std::vector<Transformation> &poses, std::size_t first) const
+    {
+        const std::vector<double> P = flatten(poses);
+        int64_t n = 0;
+        check(icpmi_map_world(m_, P.data(), static_cast<int64_t>(poses.size()), static_cast<int64_t>(first), nullptr, 0, &n));
+        std::vector<double> out(3 * static_cast<std::size_t>(n));
+        if (n) check(icpmi_map_world(m_, P.data(), static_cast<int64_t>(poses.size()), static_cast<int64_t>(first), out.data(), n, &n));
+        return out;
+    }
+    Context *ctx_;
+    icpmi_map *m_ = nullptr;
+    std::vector<std::size_t> rows_; // rows per frame
 };
 
 } // namespace icp_mi355x

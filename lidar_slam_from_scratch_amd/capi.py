@@ -32,6 +32,8 @@ EXPORTS = [
     "icpmi_pose_graph_config_default", "icpmi_pose_graph_create", "icpmi_pose_graph_destroy",
     "icpmi_pose_graph_add_prior", "icpmi_pose_graph_add_odometry", "icpmi_pose_graph_add_loop_closure",
     "icpmi_pose_graph_optimize", "icpmi_pose_graph_pose", "icpmi_pose_graph_poses", "icpmi_pose_graph_size",
+    "icpmi_map_create", "icpmi_map_destroy", "icpmi_map_add_frame", "icpmi_map_add_frame_device",
+    "icpmi_map_add_stream_frame", "icpmi_map_size", "icpmi_map_world", "icpmi_map_finish",
 ]
 
 
@@ -242,6 +244,15 @@ def load_library(path=None):
     L.icpmi_pose_graph_pose.argtypes = [pg, C.c_int64, dp]
     L.icpmi_pose_graph_poses.argtypes = [pg, dp, C.c_int64, i64p, i64p]
     L.icpmi_pose_graph_size.argtypes = [pg, i64p, i64p, C.POINTER(PoseGraphInfo)]
+    L.icpmi_map_create.argtypes = [vp, C.POINTER(vp)]
+    L.icpmi_map_destroy.argtypes = [vp]
+    L.icpmi_map_destroy.restype = None
+    L.icpmi_map_add_frame.argtypes = [vp, dp, C.c_int64]
+    L.icpmi_map_add_frame_device.argtypes = [vp, vp, C.c_int64]
+    L.icpmi_map_add_stream_frame.argtypes = [vp]
+    L.icpmi_map_size.argtypes = [vp, i64p, i64p]
+    L.icpmi_map_world.argtypes = [vp, dp, C.c_int64, C.c_int64, dp, C.c_int64, i64p]
+    L.icpmi_map_finish.argtypes = [vp, dp, C.c_int64, C.POINTER(GridConfig), C.c_double, dp, C.c_int64, i64p, i64p]
     for name in EXPORTS:
         getattr(L, name)  # raises AttributeError if a declared symbol is not exported
     _LIB = L
@@ -310,6 +321,8 @@ class Context:
         if getattr(self, "_h", None):
             for g in list(getattr(self, "_pose_graphs", ())):   # icpmi_pose_graph handles go before their context
                 g.close()
+            for m in list(getattr(self, "_maps", ())):          # ... and so do icpmi_map handles
+                m.close()
             self._lib.icpmi_destroy(self._h)
             self._h = None
 

@@ -40,6 +40,7 @@
 #include "voxel.h"
 #include "scan_context.h"
 #include "occupancy.h"
+#include "global_map.h"
 #include "pose_graph.h"
 
 using namespace icpmi;
@@ -1606,6 +1607,38 @@ int voxel_downsample_device(icpmi_ctx *ctx, const double *d_pts, int n, double v
     return rc == ICPMI_OK ? rc : fail(ctx, rc, "%s", msg);
 }
 
+// n cell keys (kGridNone: none) -> sorted, made unique, padded: `uniq` then holds the distinct cells in ascending
+// order followed by kGridNone up to n entries, and counts[n + 1] = set_n + their number (k_grid_pad).  counts holds
+// n + 16 words (run lengths, then the run count and that size).  The occupancy update and the global map's rebuild
+// (icpmi_map_finish) share it.
+struct GridKeySort {
+    unsigned long long *keys, *sorted, *uniq;
+    unsigned *counts;
+    int n;
+};
+// the sort's scratch (ctx->sort_tmp), with room for `extra` bytes of the caller's own use of it
+int grid_sort_reserve(icpmi_ctx *ctx, const GridKeySort &k, size_t extra)
+{
+    hipStream_t s = ctx->stream;
+    size_t b1 = 0, b2 = 0;
+    HIP_TRY(ctx, sort_keys_u64(nullptr, &b1, k.keys, k.sorted, (unsigned)k.n, s));
+    HIP_TRY(ctx, run_lengths_u64(nullptr, &b2, k.sorted, (unsigned)k.n, k.uniq, k.counts, k.counts + k.n, s));
+    return reserve(ctx, ctx->sort_tmp, std::max(b1, std::max(b2, extra)));
+}
+int grid_sort_queue(icpmi_ctx *ctx, const GridKeySort &k, unsigned set_n)
+{
+    hipStream_t s = ctx->stream;
+    const int n = k.n;
+    unsigned *runs_d = k.counts + n, *count_d = runs_d + 1;
+    size_t b1 = 0, b2 = 0;
+    HIP_TRY(ctx, sort_keys_u64(nullptr, &b1, k.keys, k.sorted, (unsigned)n, s));
+    HIP_TRY(ctx, run_lengths_u64(nullptr, &b2, k.sorted, (unsigned)n, k.uniq, k.counts, runs_d, s));
+    HIP_TRY(ctx, sort_keys_u64(ctx->sort_tmp.p, &b1, k.keys, k.sorted, (unsigned)n, s));
+    HIP_TRY(ctx, run_lengths_u64(ctx->sort_tmp.p, &b2, k.sorted, (unsigned)n, k.uniq, k.counts, runs_d, s));
+    hipLaunchKernelGGL(k_grid_pad, dim3((n + 255) / 256), dim3(256), 0, s, k.uniq, n, (const unsigned *)runs_d, set_n, count_d);
+    return ICPMI_OK;
+}
+
 // update_occupancy_grid (slam_node.cpp:211-221) on device memory: the frame's keys, less those the set already
 // holds, sorted, made unique and merged into the set (occupancy.h); the set's new size is queued for the host
 // (ctx->h_grid[0]) and picked up by grid_finish after the caller's wait.
@@ -1626,21 +1659,19 @@ int grid_update_queue(icpmi_ctx *ctx, const double *d_world, int n, const double
     if ((rc = reserve(ctx, ctx->grid_cnt, sizeof(unsigned) * (un + 16)))) return rc;
     if ((rc = reserve(ctx, ctx->grid_out, sizeof(unsigned long long) * total))) return rc;
     unsigned long long *keys = (unsigned long long *)ctx->grid_in.p, *sorted = keys + un, *uniq = keys + 2 * un;
-    unsigned *counts = (unsigned *)ctx->grid_cnt.p, *runs_d = counts + un, *count_d = runs_d + 1;
-    size_t b1 = 0, b2 = 0, b3 = 0;
-    HIP_TRY(ctx, sort_keys_u64(nullptr, &b1, keys, sorted, (unsigned)n, s));
-    HIP_TRY(ctx, run_lengths_u64(nullptr, &b2, sorted, (unsigned)n, uniq, counts, runs_d, s));
+    unsigned *counts = (unsigned *)ctx->grid_cnt.p;
+    size_t b3 = 0;
     HIP_TRY(ctx, merge_keys_u64(nullptr, &b3, (const unsigned long long *)ctx->grid_set.p, uniq, (unsigned long long *)ctx->grid_out.p,
                                 (unsigned)set_n, (unsigned)n, s));
-    if ((rc = reserve(ctx, ctx->sort_tmp, std::max(b1, std::max(b2, b3))))) return rc;
+    GridKeySort ks{keys, sorted, uniq, counts, n};
+    if ((rc = grid_sort_reserve(ctx, ks, b3))) return rc;
     GridParams g{sensor[0], sensor[1], grid->resolution, grid->height_min, grid->height_max, grid->max_range};
     hipLaunchKernelGGL(k_grid_keys, dim3((n + 255) / 256), dim3(256), 0, s, d_world, n, g, keys);
     if (set_n > 0)
         hipLaunchKernelGGL(k_grid_drop_known, dim3((n + 255) / 256), dim3(256), 0, s, keys, n,
                            (const unsigned long long *)ctx->grid_set.p, (int)set_n);
-    HIP_TRY(ctx, sort_keys_u64(ctx->sort_tmp.p, &b1, keys, sorted, (unsigned)n, s));
-    HIP_TRY(ctx, run_lengths_u64(ctx->sort_tmp.p, &b2, sorted, (unsigned)n, uniq, counts, runs_d, s));
-    hipLaunchKernelGGL(k_grid_pad, dim3((n + 255) / 256), dim3(256), 0, s, uniq, n, (const unsigned *)runs_d, (unsigned)set_n, count_d);
+    if ((rc = grid_sort_queue(ctx, ks, (unsigned)set_n))) return rc;
+    unsigned *count_d = ks.counts + un + 1;
     HIP_TRY(ctx, merge_keys_u64(ctx->sort_tmp.p, &b3, set_n > 0 ? (const unsigned long long *)ctx->grid_set.p : uniq, uniq,
                                 (unsigned long long *)ctx->grid_out.p, (unsigned)set_n, (unsigned)n, s));
     std::swap(ctx->grid_set, ctx->grid_out); // the merged array (cells, then n - new entries of kGridNone) is the set now
@@ -3725,6 +3756,264 @@ int icpmi_pose_graph_size(const icpmi_pose_graph *g, int64_t *num_poses, int64_t
     if (num_poses) *num_poses = g->num_poses;                 // pose_graph.hpp:117
     if (num_loop_closures) *num_loop_closures = g->num_loops; // :122
     if (last) *last = g->last;                                // :127-128 (final error, iterations)
+    return ICPMI_OK;
+}
+
+} // extern "C"
+
+// ======================================================================================================================
+// Global map (slam_node.cpp:187-238): the node's kept scans (downsampled_clouds_) in one device arena, and the world
+// points, cell set and published map of any prefix of them from one launch of k_map_world (global_map.h).
+
+struct icpmi_map {
+    icpmi_ctx *ctx = nullptr;
+    DevBuf d_rows;                       // the store: every frame's rows, frame after frame (N x 3 fp64)
+    DevBuf d_tiles;                      // the tile table (MapTile), uploaded as it grows
+    DevBuf d_poses, d_world;             // a call's poses (16 doubles per frame), its world points
+    std::vector<int64_t> row0{0};        // per frame its first row in the store; row0[frames] = rows
+    std::vector<int64_t> tile0{0};       // per frame its first tile; tile0[frames] = tiles
+    std::vector<MapTile> tiles;
+    size_t uploaded_tiles = 0;           // tiles already in d_tiles
+};
+
+namespace {
+
+constexpr int64_t kMapMaxRows = 700000000; // the library's per-call limit
+
+int64_t map_frames(const icpmi_map *m) { return (int64_t)m->row0.size() - 1; }
+
+// downsampled_clouds_.push_back (slam_node.cpp:71,123): n rows from `src` (host or device memory, `kind`) behind the
+// store's rows.  The arena grows geometrically by a device copy; the old one is freed after the call's one wait.  On
+// any error the store is as it was.
+int map_append(icpmi_map *m, const void *src, int64_t n, hipMemcpyKind kind)
+{
+    icpmi_ctx *ctx = m->ctx;
+    const int64_t have = m->row0.back();
+    if (n < 0 || n > kMapMaxRows - have)
+        return fail(ctx, ICPMI_ERR_ARG, "the store holds %lld rows; %lld more would pass the limit of %lld", (long long)have,
+                    (long long)n, (long long)kMapMaxRows);
+    if (map_frames(m) >= INT32_MAX) return fail(ctx, ICPMI_ERR_ARG, "too many frames");
+    hipStream_t s = ctx->stream;
+    const size_t used = sizeof(double) * 3 * (size_t)have, need = sizeof(double) * 3 * (size_t)(have + n);
+    DevBuf grown; // the new arena, if the store has to grow
+    auto drop = [&](hipError_t e) {
+        release(grown);
+        return fail(ctx, ICPMI_ERR_HIP, "global map store: %s", hipGetErrorString(e));
+    };
+    hipError_t e = hipSuccess;
+    DevBuf &dst = need > m->d_rows.cap ? grown : m->d_rows;
+    if (&dst == &grown) {
+        if ((e = reserve_raw(grown, std::max(need, 2 * m->d_rows.cap))) != hipSuccess) return drop(e);
+        if (used && (e = hipMemcpyAsync(grown.p, m->d_rows.p, used, hipMemcpyDeviceToDevice, s)) != hipSuccess) return drop(e);
+    }
+    if (n && (e = hipMemcpyAsync((char *)dst.p + used, src, need - used, kind, s)) != hipSuccess) return drop(e);
+    if ((e = hipStreamSynchronize(s)) != hipSuccess) return drop(e); // the call's one wait
+    if (&dst == &grown) {
+        release(m->d_rows);
+        m->d_rows = grown;
+    }
+    const int32_t f = (int32_t)map_frames(m);
+    for (int64_t r = 0; r < n; r += kMapTileRows)
+        m->tiles.push_back(MapTile{have + r, f, (int32_t)std::min<int64_t>(kMapTileRows, n - r)});
+    m->row0.push_back(have + n);
+    m->tile0.push_back((int64_t)m->tiles.size());
+    return ICPMI_OK;
+}
+
+// The frames a call uses: [0, min(frames, n_poses)) (slam_node.cpp:190,201,225: i < downsampled_clouds_.size() &&
+// i < poses_.size()).  The poses they use must be finite.
+int map_check_poses(icpmi_map *m, const double *poses, int64_t n_poses, int64_t *last)
+{
+    icpmi_ctx *ctx = m->ctx;
+    if (n_poses < 0) return fail(ctx, ICPMI_ERR_ARG, "n_poses < 0");
+    if (!poses && n_poses > 0) return fail(ctx, ICPMI_ERR_NULL, "poses is NULL");
+    *last = std::min(map_frames(m), n_poses);
+    for (int64_t i = 0; i < 16 * *last; ++i)
+        if (!std::isfinite(poses[i])) return fail(ctx, ICPMI_ERR_ARG, "pose %lld has a non-finite entry", (long long)(i / 16));
+    return ICPMI_OK;
+}
+
+// Queue, for frames [first, last) (first < last): the tile table's new entries, the frames' poses, and k_map_world
+// into world (rows x 3) and / or keys (rows), row 0 being frame first's first row.
+int map_queue_world(icpmi_map *m, const double *poses, int64_t first, int64_t last, double *world, unsigned long long *keys,
+                    const icpmi_grid_config *grid)
+{
+    icpmi_ctx *ctx = m->ctx;
+    hipStream_t s = ctx->stream;
+    int rc;
+    const size_t T = m->tiles.size();
+    if (sizeof(MapTile) * T > m->d_tiles.cap) { // grows geometrically: the whole table goes up again
+        release(m->d_tiles);
+        m->uploaded_tiles = 0;
+        if ((rc = reserve(ctx, m->d_tiles, sizeof(MapTile) * 2 * T))) return rc;
+    }
+    if (T > m->uploaded_tiles)
+        HIP_TRY(ctx, hipMemcpyAsync((MapTile *)m->d_tiles.p + m->uploaded_tiles, m->tiles.data() + m->uploaded_tiles,
+                                    sizeof(MapTile) * (T - m->uploaded_tiles), hipMemcpyHostToDevice, s));
+    m->uploaded_tiles = T;
+    const size_t pose_bytes = sizeof(double) * 16 * (size_t)(last - first);
+    if ((rc = reserve(ctx, m->d_poses, pose_bytes))) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(m->d_poses.p, poses + 16 * first, pose_bytes, hipMemcpyHostToDevice, s));
+    const int64_t t0 = m->tile0[first], nt = m->tile0[last] - t0;
+    GridParams g{0.0, 0.0, 1.0, 0.0, 0.0, 0.0};
+    if (grid) g = GridParams{0.0, 0.0, grid->resolution, grid->height_min, grid->height_max, grid->max_range};
+    if (nt > 0)
+        hipLaunchKernelGGL(k_map_world, dim3((unsigned)nt), dim3(256), 0, s, (const double *)m->d_rows.p,
+                           (const MapTile *)m->d_tiles.p + t0, (const double *)m->d_poses.p, (int32_t)first, m->row0[first],
+                           world, keys, g);
+    HIP_TRY(ctx, hipGetLastError());
+    return ICPMI_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int icpmi_map_create(icpmi_ctx *ctx, icpmi_map **out)
+{
+    int rc;
+    if (!out) return fail(ctx, ICPMI_ERR_NULL, "out is NULL");
+    *out = nullptr;
+    if ((rc = check_common(ctx))) return rc;
+    icpmi_map *m = new icpmi_map;
+    m->ctx = ctx;
+    *out = m;
+    return ICPMI_OK;
+}
+
+void icpmi_map_destroy(icpmi_map *m)
+{
+    if (!m) return;
+    (void)hipSetDevice(m->ctx->opt.device);
+    (void)hipStreamSynchronize(m->ctx->stream);
+    for (DevBuf *b : {&m->d_rows, &m->d_tiles, &m->d_poses, &m->d_world}) release(*b);
+    delete m;
+}
+
+int icpmi_map_add_frame(icpmi_map *m, const double *xyz, int64_t n)
+{
+    if (!m) return ICPMI_ERR_NULL;
+    int rc;
+    if ((rc = check_common(m->ctx))) return rc;
+    if (!xyz && n != 0) return fail(m->ctx, ICPMI_ERR_NULL, "null argument");
+    return map_append(m, xyz, n, hipMemcpyHostToDevice);
+}
+
+int icpmi_map_add_frame_device(icpmi_map *m, const double *d_xyz, int64_t n)
+{
+    if (!m) return ICPMI_ERR_NULL;
+    int rc;
+    if ((rc = check_common(m->ctx))) return rc;
+    if (!d_xyz && n != 0) return fail(m->ctx, ICPMI_ERR_NULL, "null argument");
+    return map_append(m, d_xyz, n, hipMemcpyDeviceToDevice);
+}
+
+int icpmi_map_add_stream_frame(icpmi_map *m)
+{
+    if (!m) return ICPMI_ERR_NULL;
+    icpmi_ctx *ctx = m->ctx;
+    int rc;
+    if ((rc = check_common(ctx))) return rc;
+    if (ctx->stream_prev_n < 0) return fail(ctx, ICPMI_ERR_ARG, "no resident frame: call icpmi_stream_push first");
+    return map_append(m, ctx->stream_prev.p, ctx->stream_prev_n, hipMemcpyDeviceToDevice);
+}
+
+int icpmi_map_size(const icpmi_map *m, int64_t *frames, int64_t *points)
+{
+    if (!m) return ICPMI_ERR_NULL;
+    if (frames) *frames = map_frames(m);
+    if (points) *points = m->row0.back();
+    return ICPMI_OK;
+}
+
+int icpmi_map_world(icpmi_map *m, const double *poses, int64_t n_poses, int64_t first, double *out_xyz, int64_t cap,
+                    int64_t *n_out)
+{
+    if (!m) return ICPMI_ERR_NULL;
+    icpmi_ctx *ctx = m->ctx;
+    int rc;
+    if ((rc = check_common(ctx))) return rc;
+    if (!n_out) return fail(ctx, ICPMI_ERR_NULL, "null argument");
+    if (first < 0) return fail(ctx, ICPMI_ERR_ARG, "first < 0");
+    int64_t last = 0;
+    if ((rc = map_check_poses(m, poses, n_poses, &last))) return rc;
+    first = std::min(first, last);
+    const int64_t rows = m->row0[last] - m->row0[first];
+    *n_out = rows;
+    if (!out_xyz || rows == 0) return ICPMI_OK;
+    if (cap < rows) return fail(ctx, ICPMI_ERR_CAPACITY, "output holds %lld rows, needs %lld", (long long)cap, (long long)rows);
+    Range range("icpmi:map_world");
+    const size_t bytes = sizeof(double) * 3 * (size_t)rows;
+    if ((rc = reserve(ctx, m->d_world, bytes))) return rc;
+    if ((rc = map_queue_world(m, poses, first, last, (double *)m->d_world.p, nullptr, nullptr))) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(out_xyz, m->d_world.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); // the call's one wait
+    HIP_TRY(ctx, hipGetLastError());
+    return ICPMI_OK;
+}
+
+int icpmi_map_finish(icpmi_map *m, const double *poses, int64_t n_poses, const icpmi_grid_config *grid, double voxel_size,
+                     double *map_out, int64_t map_cap, int64_t *n_map, int64_t *n_cells)
+{
+    if (!m) return ICPMI_ERR_NULL;
+    icpmi_ctx *ctx = m->ctx;
+    int rc;
+    if ((rc = check_common(ctx))) return rc;
+    if (grid && !(grid->resolution > 0.0)) return fail(ctx, ICPMI_ERR_ARG, "grid resolution must be positive");
+    int64_t last = 0;
+    if ((rc = map_check_poses(m, poses, n_poses, &last))) return rc;
+    const bool want_map = map_out && voxel_size > 0.0;
+    if (n_map) *n_map = 0;
+    const int64_t n64 = m->row0[last];
+    if (n64 == 0 || (!grid && !want_map)) {
+        if (grid) ctx->grid_n = 0; // occupied_cells_.clear() and nothing inserted
+        if (n_cells) *n_cells = ctx->grid_n;
+        return ICPMI_OK;
+    }
+    Range range("icpmi:map_finish");
+    hipStream_t s = ctx->stream;
+    const int n = (int)n64;
+    const size_t un = (size_t)n;
+    double *world = nullptr;
+    if (want_map) {
+        if ((rc = reserve(ctx, m->d_world, sizeof(double) * 3 * un))) return rc;
+        world = (double *)m->d_world.p;
+    }
+    // rebuild_occupancy_grid (slam_node.cpp:223-229): the keys of every row -> sorted, unique -> the new set, built in
+    // grid_out and swapped in only once the whole call has succeeded
+    GridKeySort ks{nullptr, nullptr, nullptr, nullptr, n};
+    if (grid) {
+        if ((rc = reserve(ctx, ctx->grid_in, sizeof(unsigned long long) * 2 * un))) return rc;
+        if ((rc = reserve(ctx, ctx->grid_out, sizeof(unsigned long long) * un))) return rc;
+        if ((rc = reserve(ctx, ctx->grid_cnt, sizeof(unsigned) * (un + 16)))) return rc;
+        ks = GridKeySort{(unsigned long long *)ctx->grid_in.p, (unsigned long long *)ctx->grid_in.p + un,
+                         (unsigned long long *)ctx->grid_out.p, (unsigned *)ctx->grid_cnt.p, n};
+        if ((rc = grid_sort_reserve(ctx, ks, 0))) return rc;
+    }
+    if ((rc = map_queue_world(m, poses, 0, last, world, ks.keys, grid))) return rc;
+    if (grid) {
+        if ((rc = grid_sort_queue(ctx, ks, 0))) return rc;
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->h_grid, ks.counts + un + 1, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    }
+    int64_t rows = 0;
+    if (want_map) {
+        // publish_global_map (slam_node.cpp:235-238): voxel_downsample(global_map_points_, voxel) on the world rows, in
+        // frame then row order.  The filter waits for its voxel count (and with it the set's size) before it queues the
+        // centroids.
+        const int64_t cap = std::max<int64_t>(0, std::min<int64_t>(n64, map_cap));
+        if ((rc = reserve(ctx, ctx->vox_out, sizeof(double) * 3 * (size_t)std::max<int64_t>(cap, 1)))) return rc;
+        if ((rc = voxel_downsample_device(ctx, world, n, voxel_size, (double *)ctx->vox_out.p, cap, &rows, false))) return rc;
+        if (rows > 0)
+            HIP_TRY(ctx, hipMemcpyAsync(map_out, ctx->vox_out.p, sizeof(double) * 3 * (size_t)rows, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    HIP_TRY(ctx, hipGetLastError());
+    if (grid) {
+        std::swap(ctx->grid_set, ctx->grid_out);
+        ctx->grid_n = (int64_t)ctx->h_grid[0];
+    }
+    if (n_map) *n_map = rows;
+    if (n_cells) *n_cells = ctx->grid_n;
     return ICPMI_OK;
 }
 

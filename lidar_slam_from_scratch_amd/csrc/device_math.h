@@ -17,6 +17,23 @@
 
 namespace icpmi {
 
+// A rigid transform's upper 3 x 4 (row-major 4 x 4 in memory), read once into registers.  apply() is the world point
+// of a row, ((x R_a0 + y R_a1) + z R_a2) + t_a (cloud * R^T + t^T, types.hpp:110-115): the one formula the ICP loop
+// (RowBatch::finish, k_transform) and the global map (k_map_world) share, so that their points agree bit for bit.
+struct Rigid34 {
+    double r00, r01, r02, t0, r10, r11, r12, t1, r20, r21, r22, t2;
+    __device__ __forceinline__ static Rigid34 load(const double *T)
+    {
+        return Rigid34{T[0], T[1], T[2], T[3], T[4], T[5], T[6], T[7], T[8], T[9], T[10], T[11]};
+    }
+    __device__ __forceinline__ void apply(double x, double y, double z, double &px, double &py, double &pz) const
+    {
+        px = ((x * r00 + y * r01) + z * r02) + t0;
+        py = ((x * r10 + y * r11) + z * r12) + t1;
+        pz = ((x * r20 + y * r21) + z * r22) + t2;
+    }
+};
+
 __device__ __forceinline__ double sqdist(double ax, double ay, double az, double bx, double by,
                                          double bz)
 {

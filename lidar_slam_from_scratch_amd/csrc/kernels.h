@@ -538,17 +538,14 @@ struct RowBatch {
     }
     __device__ __forceinline__ void finish(double *out, const RowBounds &rb, int i0, int stride, int n, const double *T) const
     {
-        const double r00 = T[0], r01 = T[1], r02 = T[2], t0 = T[3];
-        const double r10 = T[4], r11 = T[5], r12 = T[6], t1 = T[7];
-        const double r20 = T[8], r21 = T[9], r22 = T[10], t2 = T[11];
+        const Rigid34 P = Rigid34::load(T);
         unsigned listed = 0; // profiling: rows of this wave listed again (counted by the wave's first active lane)
 #pragma unroll
         for (int b = 0; b < B; ++b) {
             const int i = i0 + b * stride;
             if (i >= n) continue;
-            const double px = ((x[b] * r00 + y[b] * r01) + z[b] * r02) + t0;
-            const double py = ((x[b] * r10 + y[b] * r11) + z[b] * r12) + t1;
-            const double pz = ((x[b] * r20 + y[b] * r21) + z[b] * r22) + t2;
+            double px, py, pz;
+            P.apply(x[b], y[b], z[b], px, py, pz);
             out[3 * i] = px;
             out[3 * i + 1] = py;
             out[3 * i + 2] = pz;

@@ -30,25 +30,33 @@ __device__ __forceinline__ unsigned long long grid_key(int x, int y)
     return ((unsigned long long)((unsigned)x ^ 0x80000000u) << 32) | (unsigned long long)((unsigned)y ^ 0x80000000u);
 }
 
-// keys[i] = the cell point i marks, kGridNone where the reference `continue`s.  A quotient that is
-// not finite or does not fit an int is undefined in the reference's static_cast: it marks nothing
-// here (|cell| <= 2^31 - 2, so kGridNone = (INT_MAX, INT_MAX) is never a cell).
-__global__ __launch_bounds__(256) void k_grid_keys(const double *__restrict__ pts, int n, GridParams g,
-                                                   unsigned long long *__restrict__ keys)
+// The cell a world point marks with the sensor at (sx, sy), kGridNone where the reference `continue`s.  A
+// quotient that is not finite or does not fit an int is undefined in the reference's static_cast: it marks
+// nothing here (|cell| <= 2^31 - 2, so kGridNone = (INT_MAX, INT_MAX) is never a cell).  k_grid_keys and
+// k_map_world (global_map.h) share it.
+__device__ __forceinline__ unsigned long long grid_cell_key(double x, double y, double z, const GridParams &g, double sx,
+                                                            double sy)
 {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const double x = pts[3 * i], y = pts[3 * i + 1], z = pts[3 * i + 2];
     unsigned long long key = kGridNone;
     if (!(z < g.height_min || z > g.height_max)) {
-        const double dx = x - g.sx, dy = y - g.sy;
+        const double dx = x - sx, dy = y - sy;
         const double r = __dsqrt_rn(dx * dx + dy * dy);
         if (!(r > g.max_range || r < 0.5)) {
             const double cx = floor(x / g.resolution), cy = floor(y / g.resolution);
             if (fabs(cx) <= 2147483646.0 && fabs(cy) <= 2147483646.0) key = grid_key((int)cx, (int)cy);
         }
     }
-    keys[i] = key;
+    return key;
+}
+
+// keys[i] = the cell point i marks (grid_cell_key with the sensor of g)
+__global__ __launch_bounds__(256) void k_grid_keys(const double *__restrict__ pts, int n, GridParams g,
+                                                   unsigned long long *__restrict__ keys)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const double x = pts[3 * i], y = pts[3 * i + 1], z = pts[3 * i + 2];
+    keys[i] = grid_cell_key(x, y, z, g, g.sx, g.sy);
 }
 
 // keys already in the (sorted, unique) set become kGridNone

@@ -1,0 +1,93 @@
+"""The node's global map through the C ABI (icpmi_map): SlamNode keeps every filtered scan (downsampled_clouds_,
+slam_viz/src/ros/slam_node.cpp:71,123) and, with the optimised poses, rebuilds the recent clouds after each successful
+optimize (rebuild_recent_clouds, :187-194), and at the end the global map, the occupancy set (build_final_global_map,
+rebuild_occupancy_grid, :196-209, :223-229) and the map it publishes (publish_global_map, :235-238).  Here the scans
+stay in device memory (csrc/global_map.h); scripts/map_ref.py restates the same interface on the CPU."""
+import ctypes as C
+import weakref
+
+import numpy as np
+
+from . import capi
+
+MAX_RECENT_CLOUDS = 20   # slam_node.hpp:169
+
+
+def _poses(poses):
+    P = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4))
+    return P, (capi._dp(P) if P.shape[0] else None)
+
+
+class GlobalMap:
+    def __init__(self, ctx):
+        self._lib = capi.load_library()
+        self.ctx = ctx
+        h = C.c_void_p()
+        ctx._check(self._lib.icpmi_map_create(ctx._h, C.byref(h)))
+        self._h = h
+        self._rows = []                # rows per frame, in order
+        if not hasattr(ctx, "_maps"):
+            ctx._maps = weakref.WeakSet()
+        ctx._maps.add(self)            # Context.close() destroys the map first
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.icpmi_map_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def add_frame(self, cloud):
+        """downsampled_clouds_.push_back(curr) (slam_node.cpp:71,123) with the rows in host memory"""
+        pts = capi._f64(cloud) if len(cloud) else np.zeros((0, 3))
+        self.ctx._check(self._lib.icpmi_map_add_frame(self._h, capi._dp(pts), pts.shape[0]))
+        self._rows.append(pts.shape[0])
+
+    def add_frame_device(self, ptr, n_rows):
+        self.ctx._check(self._lib.icpmi_map_add_frame_device(self._h, C.c_void_p(ptr), int(n_rows)))
+        self._rows.append(int(n_rows))
+
+    def add_stream_frame(self):
+        """the filtered scan the context's last stream_push* left resident, device to device"""
+        before = self.size()[1]
+        self.ctx._check(self._lib.icpmi_map_add_stream_frame(self._h))
+        self._rows.append(self.size()[1] - before)
+
+    def size(self):
+        """(frames, rows)"""
+        f, n = C.c_int64(0), C.c_int64(0)
+        self.ctx._check(self._lib.icpmi_map_size(self._h, C.byref(f), C.byref(n)))
+        return f.value, n.value
+
+    def world(self, poses, first=0):
+        """world points of frames [first, min(frames, len(poses))), frame then row order: N x 3"""
+        P, pp = _poses(poses)
+        n = C.c_int64(0)
+        self.ctx._check(self._lib.icpmi_map_world(self._h, pp, P.shape[0], int(first), None, 0, C.byref(n)))
+        out = np.empty((n.value, 3))
+        if n.value:
+            self.ctx._check(self._lib.icpmi_map_world(self._h, pp, P.shape[0], int(first), capi._dp(out), n.value,
+                                                      C.byref(n)))
+        return out
+
+    def recent_clouds(self, poses, max_recent=MAX_RECENT_CLOUDS):
+        """rebuild_recent_clouds (slam_node.cpp:187-194): one world cloud per frame, for the last max_recent frames"""
+        frames = len(self._rows)
+        first = frames - max_recent if frames > max_recent else 0
+        last = min(frames, len(poses))
+        w = self.world(poses, first)
+        bounds = np.cumsum([0] + self._rows[first:last])
+        return [w[bounds[i]:bounds[i + 1]] for i in range(max(0, last - first))]
+
+    def finish(self, poses, grid=None, voxel=1.0):
+        """build_final_global_map -> rebuild_occupancy_grid (slam_node.cpp:196-209, :223-229) into the context's cell
+        set, and voxel_downsample(global map, voxel) (:235-238).  grid None: the default OccupancyGridConfig.
+        Returns (cells: (n, 2) int32 sorted by x then y, published map: M x 3)."""
+        P, pp = _poses(poses)
+        g = grid if grid is not None else self.ctx.make_grid_config()
+        rows = int(sum(self._rows[:min(len(self._rows), P.shape[0])]))
+        out = np.empty((max(rows, 1), 3))
+        nm, nc = C.c_int64(0), C.c_int64(0)
+        self.ctx._check(self._lib.icpmi_map_finish(self._h, pp, P.shape[0], C.byref(g), float(voxel), capi._dp(out),
+                                                   rows, C.byref(nm), C.byref(nc)))
+        return self.ctx.occupancy_cells(), out[:nm.value].copy()

@@ -13,7 +13,9 @@ already-downsampled frames, with registration, loop closure and the pose-graph b
 
 The detector uses the node's LoopClosureConfig (:77-81).  By default everything runs through the library on `ctx`;
 `align`, `loop_backend` and `pose_graph` replace the three parts (the tests put the CPU oracle and
-scripts/pose_graph_ref.py there).  As in the reference, the frame after a too-few-points frame names a pose with no
+scripts/pose_graph_ref.py there).  Given a `global_map` (global_map.GlobalMap, or scripts/map_ref.py's restatement),
+the run also keeps every frame in it (:71,123), rebuilds the recent clouds after each successful optimize (:187-194)
+and at the end the cell set and the published map (build_final_global_map, :196-209, :223-229, :235-238).  As in the reference, the frame after a too-few-points frame names a pose with no
 estimate: its addOdometryFactor raises (ICPMI_ERR_ARG), where the reference throws."""
 import numpy as np
 
@@ -26,6 +28,9 @@ class SlamRun:
         self.factors = []             # ("prior", i, T) / ("odom", i, j, T, fitness) / ("loop", i, j, T), in call order
         self.closures = []            # LoopClosureResult, in the order found
         self.optimizations = []       # (frame index or "end", ok, stats) per optimize()
+        self.recent_world = []        # with a global map: recent_clouds_world_ after each successful optimize
+        self.cells = None             # ... and at the end the rebuilt cell set ((n, 2) int32, sorted)
+        self.published_map = None     # ... and voxel_downsample(global map, map_voxel)
 
 
 def node_loop_config():
@@ -34,8 +39,9 @@ def node_loop_config():
 
 
 def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, pose_graph_config=None,
-             align=None, loop_backend=None, pose_graph=None):
-    """frames: sequence of N x 3 fp64 clouds (already downsampled).  Returns a SlamRun."""
+             align=None, loop_backend=None, pose_graph=None, global_map=None, grid=None, map_voxel=1.0):
+    """frames: sequence of N x 3 fp64 clouds (already downsampled).  Returns a SlamRun.  global_map: an object with
+    add_frame, recent_clouds and finish (None: no map is built); grid: its occupancy grid config (None: defaults)."""
     if align is None:
         from .odometry import gpu_align
         align = gpu_align(ctx)
@@ -61,13 +67,19 @@ def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, po
         run.optimizations.append((tag, ok, pose_graph.stats))
         if ok:
             run.poses = [np.asarray(p) for p in pose_graph.get_all_poses()]
+            if global_map is not None:                               # rebuild_recent_clouds, :182,187-194
+                run.recent_world.append(global_map.recent_clouds(run.poses))
 
     add("prior", 0, np.eye(4))                                       # :66
     frames = list(frames)
     prev = np.ascontiguousarray(frames[0], dtype=np.float64)         # :69-72
+    if global_map is not None:
+        global_map.add_frame(prev)                                   # :71
     for k in range(1, len(frames)):
         curr = np.ascontiguousarray(frames[k], dtype=np.float64)
         pending = False
+        if global_map is not None:
+            global_map.add_frame(curr)                               # :123
         if curr.shape[0] < min_points:                               # :125-130
             run.poses.append(run.poses[-1].copy())
             prev = curr
@@ -87,4 +99,6 @@ def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, po
         if pending:                                                  # :112-115
             optimize(k)
     optimize("end")                                                  # :103-106
+    if global_map is not None:                                       # build_final_global_map, :107,196-209
+        run.cells, run.published_map = global_map.finish(run.poses, grid, map_voxel)
     return run
