@@ -489,6 +489,50 @@ int icpmi_map_world(icpmi_map *map, const double *poses, int64_t n_poses, int64_
 int icpmi_map_finish(icpmi_map *map, const double *poses, int64_t n_poses, const icpmi_grid_config *grid,
                      double voxel_size, double *map_out, int64_t map_cap, int64_t *n_map, int64_t *n_cells);
 
+/* Loop-closure detection over a global map's kept scans (slam::LoopClosureDetector, core/loop_closure.hpp:41-148),
+ * with its database on the device: an entry is a store frame with a label (the node's frame_idx).  Each entry's
+ * Scan Context descriptor lives in device memory; its rows stay in the store and are never copied to the host.
+ *   icpmi_loop_add_frame      addFrame (:53-60): entry = store frame, labelled frame_idx.  No device work: the
+ *                             descriptors of the entries added since the last detect are formed at its start, in one
+ *                             launch, bit for bit those of icpmi_scan_context on the same rows.
+ *   icpmi_loop_detect         detect (:66-126) for the newest entry q: every older entry i with
+ *                             label[q] - label[i] >= frame_gap and a distance (bit for bit icpmi_scan_context_distances)
+ *                             below sc_distance_threshold is a candidate; the candidates, by distance then entry, are
+ *                             verified with icp_point_to_plane(query rows, candidate rows) (30 iterations, tolerance
+ *                             1e-6, min_error 1e-9, identity start) until max_candidates are accepted (converged and
+ *                             final_error < icp_fitness_threshold).  Up to min(max_candidates - accepted,
+ *                             ICPMI_MAX_BATCH) of them run side by side, as in icpmi_align_batch.  The results are those
+ *                             of the host detector over the same clouds.  One wait for the candidates, then the
+ *                             verifications' own.  Fewer than two entries: *n_out = 0.  A cap of max_candidates always
+ *                             suffices; fewer than the results is ICPMI_ERR_CAPACITY.  A context with a communicator
+ *                             is refused (ICPMI_ERR_ARG); a verification's error is returned as icpmi_align_batch
+ *                             returns it.
+ *   icpmi_loop_descriptor     entry's 20 x 60 descriptor (row-major) into desc_out; forms any pending ones first.
+ *   icpmi_loop_clear          drops every entry; the store is untouched.
+ * A store frame or an entry out of range is ICPMI_ERR_ARG and changes nothing.  The handle uses its map's context and
+ * stream: destroy it before its map, and the map before the context. */
+typedef struct icpmi_loop icpmi_loop;
+typedef struct {
+    int32_t frame_gap;             /* loop_closure.hpp:15 */
+    int32_t max_candidates;        /* :18 */
+    double sc_distance_threshold;  /* :16 */
+    double icp_fitness_threshold;  /* :17 */
+} icpmi_loop_config;
+typedef struct {                   /* LoopClosureResult, :25-31 */
+    int32_t query_frame, match_frame;
+    double transform[16];          /* row-major, maps the query's rows onto the match's */
+    double scan_context_distance;
+    double icp_fitness;
+} icpmi_loop_result;
+void icpmi_loop_config_default(icpmi_loop_config *cfg); /* :14-19: 50, 3, 0.25, 0.3 */
+int icpmi_loop_create(icpmi_map *map, const icpmi_loop_config *cfg, icpmi_loop **out);
+void icpmi_loop_destroy(icpmi_loop *loop);
+int icpmi_loop_add_frame(icpmi_loop *loop, int64_t store_frame, int32_t frame_idx);
+int icpmi_loop_detect(icpmi_loop *loop, icpmi_loop_result *out, int64_t cap, int64_t *n_out);
+int icpmi_loop_descriptor(icpmi_loop *loop, int64_t entry, double *desc_out /* 1200 */);
+int icpmi_loop_size(const icpmi_loop *loop, int64_t *entries);
+int icpmi_loop_clear(icpmi_loop *loop);
+
 /* profiling */
 int icpmi_reset_profile(icpmi_ctx *ctx);
 int icpmi_get_profile(icpmi_ctx *ctx, icpmi_profile *out);

@@ -860,6 +860,7 @@ public:
         return PointCloud(std::move(out));
     }
     icpmi_map *get() const { return m_; }
+    Context *context() const { return ctx_; }
 
 private:
     void check(int rc) const
@@ -891,6 +892,90 @@ private:
     Context *ctx_;
     icpmi_map *m_ = nullptr;
     std::vector<std::size_t> rows_; // rows per frame
+};
+
+// LoopClosureDetector with its database on the device, as an index over a GlobalMap's frames (icpmi_loop_*): an
+// entry is a store frame with the node's frame_idx as its label, so the node calls
+//     map.add_stream_frame(); loop.addFrame(map.frames() - 1, frame_idx);
+// and the scan never visits the host.  Holds no clouds and no descriptors; detect() returns what LoopClosureDetector
+// returns over the same clouds.  Non-copyable, movable; destroy it before its map.
+class StoreLoopClosureDetector {
+public:
+    explicit StoreLoopClosureDetector(GlobalMap &map, LoopClosureConfig config = LoopClosureConfig())
+        : ctx_(map.context()), config_(config)
+    {
+        icpmi_loop_config c;
+        icpmi_loop_config_default(&c);
+        c.frame_gap = config.frame_gap;
+        c.max_candidates = config.max_candidates;
+        c.sc_distance_threshold = config.sc_distance_threshold;
+        c.icp_fitness_threshold = config.icp_fitness_threshold;
+        check(icpmi_loop_create(map.get(), &c, &l_));
+    }
+    ~StoreLoopClosureDetector() { icpmi_loop_destroy(l_); }
+    StoreLoopClosureDetector(const StoreLoopClosureDetector &) = delete;
+    StoreLoopClosureDetector &operator=(const StoreLoopClosureDetector &) = delete;
+    StoreLoopClosureDetector(StoreLoopClosureDetector &&o) noexcept : ctx_(o.ctx_), config_(o.config_), l_(o.l_) { o.l_ = nullptr; }
+    StoreLoopClosureDetector &operator=(StoreLoopClosureDetector &&o) noexcept
+    {
+        if (this != &o) {
+            icpmi_loop_destroy(l_);
+            ctx_ = o.ctx_;
+            config_ = o.config_;
+            l_ = o.l_;
+            o.l_ = nullptr;
+        }
+        return *this;
+    }
+
+    void addFrame(std::size_t store_frame, int frame_idx) // loop_closure.hpp:53-60 for the store's frame
+    {
+        check(icpmi_loop_add_frame(l_, static_cast<int64_t>(store_frame), frame_idx));
+    }
+    std::vector<LoopClosureResult> detect() // loop_closure.hpp:66-126
+    {
+        std::vector<icpmi_loop_result> buf(static_cast<std::size_t>(std::max(config_.max_candidates, 1)));
+        int64_t n = 0;
+        check(icpmi_loop_detect(l_, buf.data(), static_cast<int64_t>(std::max(config_.max_candidates, 0)), &n));
+        std::vector<LoopClosureResult> out;
+        for (int64_t i = 0; i < n; ++i) {
+            const icpmi_loop_result &r = buf[static_cast<std::size_t>(i)];
+            LoopClosureResult o;
+            o.query_frame = r.query_frame;
+            o.match_frame = r.match_frame;
+            std::array<double, 16> m;
+            std::copy(r.transform, r.transform + 16, m.begin());
+            o.transform = Transformation(m);
+            o.scan_context_distance = r.scan_context_distance;
+            o.icp_fitness = r.icp_fitness;
+            out.push_back(o);
+        }
+        return out;
+    }
+    std::size_t size() const
+    {
+        int64_t n = 0;
+        check(icpmi_loop_size(l_, &n));
+        return static_cast<std::size_t>(n);
+    }
+    void clear() { check(icpmi_loop_clear(l_)); } // the store is untouched
+    std::vector<double> descriptor(std::size_t entry) const // 20 x 60, row-major
+    {
+        std::vector<double> d(static_cast<std::size_t>(ICPMI_SC_RINGS) * ICPMI_SC_SECTORS);
+        check(icpmi_loop_descriptor(l_, static_cast<int64_t>(entry), d.data()));
+        return d;
+    }
+    const LoopClosureConfig &config() const { return config_; }
+    icpmi_loop *get() const { return l_; }
+
+private:
+    void check(int rc) const
+    {
+        if (rc != ICPMI_OK) throw IcpError(rc, icpmi_last_error(ctx_->get()));
+    }
+    Context *ctx_;
+    LoopClosureConfig config_;
+    icpmi_loop *l_ = nullptr;
 };
 
 } // namespace icp_mi355x

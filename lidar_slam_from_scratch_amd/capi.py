@@ -34,6 +34,8 @@ EXPORTS = [
     "icpmi_pose_graph_optimize", "icpmi_pose_graph_pose", "icpmi_pose_graph_poses", "icpmi_pose_graph_size",
     "icpmi_map_create", "icpmi_map_destroy", "icpmi_map_add_frame", "icpmi_map_add_frame_device",
     "icpmi_map_add_stream_frame", "icpmi_map_size", "icpmi_map_world", "icpmi_map_finish",
+    "icpmi_loop_config_default", "icpmi_loop_create", "icpmi_loop_destroy", "icpmi_loop_add_frame", "icpmi_loop_detect",
+    "icpmi_loop_descriptor", "icpmi_loop_size", "icpmi_loop_clear",
 ]
 
 
@@ -52,6 +54,16 @@ class Result(C.Structure):
     _fields_ = [("transformation", C.c_double * 16), ("converged", C.c_int32),
                 ("num_iterations", C.c_int32), ("final_error", C.c_double),
                 ("history_len", C.c_int32), ("loop_iterations", C.c_int32)]
+
+
+class LoopConfig(C.Structure):
+    _fields_ = [("frame_gap", C.c_int32), ("max_candidates", C.c_int32),
+                ("sc_distance_threshold", C.c_double), ("icp_fitness_threshold", C.c_double)]
+
+
+class LoopResult(C.Structure):
+    _fields_ = [("query_frame", C.c_int32), ("match_frame", C.c_int32), ("transform", C.c_double * 16),
+                ("scan_context_distance", C.c_double), ("icp_fitness", C.c_double)]
 
 
 class Profile(C.Structure):
@@ -253,6 +265,16 @@ def load_library(path=None):
     L.icpmi_map_size.argtypes = [vp, i64p, i64p]
     L.icpmi_map_world.argtypes = [vp, dp, C.c_int64, C.c_int64, dp, C.c_int64, i64p]
     L.icpmi_map_finish.argtypes = [vp, dp, C.c_int64, C.POINTER(GridConfig), C.c_double, dp, C.c_int64, i64p, i64p]
+    L.icpmi_loop_config_default.argtypes = [C.POINTER(LoopConfig)]
+    L.icpmi_loop_config_default.restype = None
+    L.icpmi_loop_create.argtypes = [vp, C.POINTER(LoopConfig), C.POINTER(vp)]
+    L.icpmi_loop_destroy.argtypes = [vp]
+    L.icpmi_loop_destroy.restype = None
+    L.icpmi_loop_add_frame.argtypes = [vp, C.c_int64, C.c_int32]
+    L.icpmi_loop_detect.argtypes = [vp, C.POINTER(LoopResult), C.c_int64, i64p]
+    L.icpmi_loop_descriptor.argtypes = [vp, C.c_int64, dp]
+    L.icpmi_loop_size.argtypes = [vp, i64p]
+    L.icpmi_loop_clear.argtypes = [vp]
     for name in EXPORTS:
         getattr(L, name)  # raises AttributeError if a declared symbol is not exported
     _LIB = L
@@ -321,6 +343,8 @@ class Context:
         if getattr(self, "_h", None):
             for g in list(getattr(self, "_pose_graphs", ())):   # icpmi_pose_graph handles go before their context
                 g.close()
+            for d in list(getattr(self, "_loops", ())):         # icpmi_loop handles go before their maps
+                d.close()
             for m in list(getattr(self, "_maps", ())):          # ... and so do icpmi_map handles
                 m.close()
             self._lib.icpmi_destroy(self._h)

@@ -41,6 +41,7 @@
 #include "scan_context.h"
 #include "occupancy.h"
 #include "global_map.h"
+#include "loop_store.h"
 #include "pose_graph.h"
 
 using namespace icpmi;
@@ -1872,34 +1873,29 @@ int icpmi_align_device(icpmi_ctx *ctx, const double *d_source_xyz, int64_t n_src
                         history_cap);
 }
 
-int icpmi_align(icpmi_ctx *ctx, const double *source_xyz, int64_t n_src, const double *target_xyz,
-                int64_t n_tgt, const icpmi_config *cfg, icpmi_result *result,
-                double *error_history, int32_t history_cap)
+namespace {
+
+// icpmi_align after its checks: the rows (host or device memory, `kind`) go into the context's own buffers first, so
+// every registration reads its clouds from the same place whoever supplied them (icpmi_align, the loop store's
+// verifications).
+int align_staged(icpmi_ctx *ctx, const double *source_xyz, int64_t n_src, const double *target_xyz, int64_t n_tgt,
+                 hipMemcpyKind kind, const icpmi_config *cfg, icpmi_result *result, double *error_history,
+                 int32_t history_cap)
 {
-    int rc = validate_align(ctx, source_xyz, n_src, target_xyz, n_tgt, cfg, result, error_history,
-                            history_cap);
-    if (rc) return rc;
-    if ((rc = check_common(ctx))) return rc;
+    int rc;
     if ((rc = reserve(ctx, ctx->stage_b, sizeof(double) * 3 * (size_t)n_src))) return rc;
     if ((rc = reserve(ctx, ctx->stage_c, sizeof(double) * 3 * (size_t)n_tgt))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->stage_b.p, source_xyz, sizeof(double) * 3 * (size_t)n_src,
-                                hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->stage_c.p, target_xyz, sizeof(double) * 3 * (size_t)n_tgt,
-                                hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->stage_b.p, source_xyz, sizeof(double) * 3 * (size_t)n_src, kind, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->stage_c.p, target_xyz, sizeof(double) * 3 * (size_t)n_tgt, kind, ctx->stream));
     return align_device(ctx, (const double *)ctx->stage_b.p, n_src, (const double *)ctx->stage_c.p,
                         n_tgt, cfg, result, error_history, history_cap);
 }
 
-int icpmi_align_batch(icpmi_ctx *ctx, int32_t count, const double *const *sources_xyz, const int64_t *n_src,
-                      const double *const *targets_xyz, const int64_t *n_tgt, const icpmi_config *cfgs,
-                      icpmi_result *results, double *error_history, int32_t history_stride, int32_t *status)
+// Runs job(c, k) for k in [0, count) side by side: k = 0 on ctx itself, k >= 1 on helper k - 1's context and host
+// thread.  status[k] receives each job's return; the first failing one is returned, with its text in ctx.
+int batch_run(icpmi_ctx *ctx, int32_t count, const std::function<int(icpmi_ctx *, int)> &job, int32_t *status)
 {
     int rc;
-    if ((rc = check_common(ctx))) return rc;
-    if (!sources_xyz || !n_src || !targets_xyz || !n_tgt || !cfgs || !results || !error_history || !status)
-        return fail(ctx, ICPMI_ERR_NULL, "null argument");
-    if (count < 1 || count > ICPMI_MAX_BATCH) return fail(ctx, ICPMI_ERR_ARG, "count %d outside [1,%d]", count, ICPMI_MAX_BATCH);
-    if (ctx->comm || ctx->cb_allreduce) return fail(ctx, ICPMI_ERR_ARG, "a context with a communicator registers one (sharded) problem at a time");
     while ((int)ctx->helpers.size() < count - 1) { // grown once, kept: their workspaces are grow-only like ctx's own
         icpmi_options o = ctx->opt;
         o.profile = 0;
@@ -1922,11 +1918,7 @@ int icpmi_align_batch(icpmi_ctx *ctx, int32_t count, const double *const *source
         });
         ctx->helpers.push_back(w);
     }
-    auto run = [&](int k) {
-        icpmi_ctx *c = k == 0 ? ctx : ctx->helpers[(size_t)k - 1]->helper;
-        status[k] = icpmi_align(c, sources_xyz[k], n_src[k], targets_xyz[k], n_tgt[k], &cfgs[k], &results[k],
-                                error_history + (size_t)k * (size_t)history_stride, history_stride);
-    };
+    auto run = [&](int k) { status[k] = job(k == 0 ? ctx : ctx->helpers[(size_t)k - 1]->helper, k); };
     for (int k = 1; k < count; ++k) {
         BatchWorker *w = ctx->helpers[(size_t)k - 1];
         {
@@ -1949,6 +1941,36 @@ int icpmi_align_batch(icpmi_ctx *ctx, int32_t count, const double *const *source
             return status[k];
         }
     return ICPMI_OK;
+}
+
+} // namespace
+
+int icpmi_align(icpmi_ctx *ctx, const double *source_xyz, int64_t n_src, const double *target_xyz,
+                int64_t n_tgt, const icpmi_config *cfg, icpmi_result *result,
+                double *error_history, int32_t history_cap)
+{
+    int rc = validate_align(ctx, source_xyz, n_src, target_xyz, n_tgt, cfg, result, error_history,
+                            history_cap);
+    if (rc) return rc;
+    if ((rc = check_common(ctx))) return rc;
+    return align_staged(ctx, source_xyz, n_src, target_xyz, n_tgt, hipMemcpyHostToDevice, cfg, result, error_history,
+                        history_cap);
+}
+
+int icpmi_align_batch(icpmi_ctx *ctx, int32_t count, const double *const *sources_xyz, const int64_t *n_src,
+                      const double *const *targets_xyz, const int64_t *n_tgt, const icpmi_config *cfgs,
+                      icpmi_result *results, double *error_history, int32_t history_stride, int32_t *status)
+{
+    int rc;
+    if ((rc = check_common(ctx))) return rc;
+    if (!sources_xyz || !n_src || !targets_xyz || !n_tgt || !cfgs || !results || !error_history || !status)
+        return fail(ctx, ICPMI_ERR_NULL, "null argument");
+    if (count < 1 || count > ICPMI_MAX_BATCH) return fail(ctx, ICPMI_ERR_ARG, "count %d outside [1,%d]", count, ICPMI_MAX_BATCH);
+    if (ctx->comm || ctx->cb_allreduce) return fail(ctx, ICPMI_ERR_ARG, "a context with a communicator registers one (sharded) problem at a time");
+    return batch_run(ctx, count, [&](icpmi_ctx *c, int k) {
+        return icpmi_align(c, sources_xyz[k], n_src[k], targets_xyz[k], n_tgt[k], &cfgs[k], &results[k],
+                           error_history + (size_t)k * (size_t)history_stride, history_stride);
+    }, status);
 }
 
 int icpmi_nearest_batch(icpmi_ctx *ctx, const double *targets_xyz, int64_t n_tgt,
@@ -4014,6 +4036,301 @@ int icpmi_map_finish(icpmi_map *m, const double *poses, int64_t n_poses, const i
     }
     if (n_map) *n_map = rows;
     if (n_cells) *n_cells = ctx->grid_n;
+    return ICPMI_OK;
+}
+
+} // extern "C"
+
+// ======================================================================================================================
+// Loop-closure detection over the store (core/loop_closure.hpp:41-148; loop_store.h): the entries' descriptors and
+// labels in device memory, the rows in the map's arena.  Per detect: one upload of the pending entries' (row0, rows,
+// label), k_loop_describe for them, k_loop_candidates, one wait; then the candidates' verifications.
+
+struct icpmi_loop {
+    icpmi_map *map = nullptr;
+    icpmi_loop_config cfg{};
+    DevBuf d_desc;                       // kScCells doubles per entry, entry-major
+    DevBuf d_labels;                     // int32 per entry
+    DevBuf d_jobs;                       // the pending entries' LoopJob
+    DevBuf d_counters;                   // k_loop_candidates' two counters (0 between launches)
+    LoopCandidate *h_cand = nullptr;     // pinned, host-mapped: the candidate list (h_cap records) and its length
+    int64_t *h_count = nullptr;
+    size_t h_cap = 0;
+    std::vector<int64_t> frames;         // per entry its store frame
+    std::vector<int32_t> labels;         // per entry its label
+    int64_t described = 0;               // entries [0, described) have their descriptor on the device
+    std::vector<LoopJob> jobs;
+};
+
+namespace {
+
+void loop_free_host(icpmi_loop *L)
+{
+    if (L->h_cand) (void)hipHostFree(L->h_cand);
+    L->h_cand = nullptr;
+    L->h_count = nullptr;
+    L->h_cap = 0;
+}
+
+// Grow b to hold `bytes`, keeping its first `used` bytes (queued on the stream); the old buffer goes to `old`, to be
+// released after the caller's wait.
+int loop_grow(icpmi_ctx *ctx, DevBuf &b, size_t used, size_t bytes, std::vector<DevBuf> &old)
+{
+    if (bytes <= b.cap) return ICPMI_OK;
+    DevBuf nb;
+    HIP_TRY(ctx, reserve_raw(nb, std::max(bytes, 2 * b.cap)));
+    if (used) {
+        const hipError_t e = hipMemcpyAsync(nb.p, b.p, used, hipMemcpyDeviceToDevice, ctx->stream);
+        if (e != hipSuccess) {
+            release(nb);
+            return fail(ctx, ICPMI_ERR_HIP, "loop store: %s", hipGetErrorString(e));
+        }
+    }
+    old.push_back(b);
+    b = nb;
+    return ICPMI_OK;
+}
+
+// Queue the descriptors of entries [described, entries): their rows are looked up in the store now (the arena moves
+// when it grows, so no device pointer is kept).  The store's own calls end in a wait, so its rows are complete.
+int loop_queue_describe(icpmi_loop *L, std::vector<DevBuf> &old)
+{
+    icpmi_ctx *ctx = L->map->ctx;
+    hipStream_t s = ctx->stream;
+    const int64_t E = (int64_t)L->frames.size(), e0 = L->described;
+    if (e0 >= E) return ICPMI_OK;
+    int rc;
+    if ((rc = loop_grow(ctx, L->d_desc, sizeof(double) * kScCells * (size_t)e0, sizeof(double) * kScCells * (size_t)E, old)))
+        return rc;
+    if ((rc = loop_grow(ctx, L->d_labels, sizeof(int32_t) * (size_t)e0, sizeof(int32_t) * (size_t)E, old))) return rc;
+    L->jobs.clear();
+    for (int64_t e = e0; e < E; ++e) {
+        const int64_t f = L->frames[(size_t)e];
+        L->jobs.push_back(LoopJob{L->map->row0[(size_t)f], (int32_t)(L->map->row0[(size_t)f + 1] - L->map->row0[(size_t)f]),
+                                  L->labels[(size_t)e]});
+    }
+    if ((rc = reserve(ctx, L->d_jobs, sizeof(LoopJob) * L->jobs.size()))) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(L->d_jobs.p, L->jobs.data(), sizeof(LoopJob) * L->jobs.size(), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_loop_describe, dim3((unsigned)(E - e0)), dim3(1024), 0, s, (const double *)L->map->d_rows.p,
+                       (const LoopJob *)L->d_jobs.p, (int32_t)e0, (double *)L->d_desc.p, (int32_t *)L->d_labels.p);
+    HIP_TRY(ctx, hipGetLastError());
+    return ICPMI_OK;
+}
+
+// After the wait that ends a call which queued loop_queue_describe: the old buffers go, the entries count as described.
+int loop_settle(icpmi_loop *L, std::vector<DevBuf> &old, int rc)
+{
+    icpmi_ctx *ctx = L->map->ctx;
+    if (rc == ICPMI_OK) {
+        const hipError_t e = hipStreamSynchronize(ctx->stream);
+        if (e == hipSuccess) L->described = (int64_t)L->frames.size();
+        else rc = fail(ctx, ICPMI_ERR_HIP, "loop store: %s", hipGetErrorString(e));
+    } else {
+        (void)hipStreamSynchronize(ctx->stream); // nothing queued may still read a buffer released below
+    }
+    for (DevBuf &b : old) release(b);
+    old.clear();
+    return rc;
+}
+
+} // namespace
+
+extern "C" {
+
+void icpmi_loop_config_default(icpmi_loop_config *cfg)
+{
+    if (!cfg) return;
+    cfg->frame_gap = 50;                // loop_closure.hpp:15
+    cfg->max_candidates = 3;            // :18
+    cfg->sc_distance_threshold = 0.25;  // :16
+    cfg->icp_fitness_threshold = 0.3;   // :17
+}
+
+int icpmi_loop_create(icpmi_map *map, const icpmi_loop_config *cfg, icpmi_loop **out)
+{
+    if (!map) return ICPMI_ERR_NULL;
+    icpmi_ctx *ctx = map->ctx;
+    int rc;
+    if (!out) return fail(ctx, ICPMI_ERR_NULL, "out is NULL");
+    *out = nullptr;
+    if ((rc = check_common(ctx))) return rc;
+    icpmi_loop *L = new icpmi_loop;
+    L->map = map;
+    if (cfg) L->cfg = *cfg;
+    else icpmi_loop_config_default(&L->cfg);
+    hipError_t e = reserve_raw(L->d_counters, 2 * sizeof(unsigned));
+    if (e == hipSuccess) e = hipMemsetAsync(L->d_counters.p, 0, 2 * sizeof(unsigned), ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) {
+        release(L->d_counters);
+        delete L;
+        return fail(ctx, ICPMI_ERR_HIP, "loop store: %s", hipGetErrorString(e));
+    }
+    *out = L;
+    return ICPMI_OK;
+}
+
+void icpmi_loop_destroy(icpmi_loop *L)
+{
+    if (!L) return;
+    (void)hipSetDevice(L->map->ctx->opt.device);
+    (void)hipStreamSynchronize(L->map->ctx->stream);
+    for (DevBuf *b : {&L->d_desc, &L->d_labels, &L->d_jobs, &L->d_counters}) release(*b);
+    loop_free_host(L);
+    delete L;
+}
+
+int icpmi_loop_add_frame(icpmi_loop *L, int64_t store_frame, int32_t frame_idx)
+{
+    if (!L) return ICPMI_ERR_NULL;
+    icpmi_ctx *ctx = L->map->ctx;
+    if (store_frame < 0 || store_frame >= map_frames(L->map))
+        return fail(ctx, ICPMI_ERR_ARG, "store frame %lld outside [0, %lld)", (long long)store_frame,
+                    (long long)map_frames(L->map));
+    if ((int64_t)L->frames.size() >= INT32_MAX) return fail(ctx, ICPMI_ERR_ARG, "too many entries");
+    L->frames.push_back(store_frame);
+    L->labels.push_back(frame_idx);
+    return ICPMI_OK;
+}
+
+int icpmi_loop_size(const icpmi_loop *L, int64_t *entries)
+{
+    if (!L) return ICPMI_ERR_NULL;
+    if (entries) *entries = (int64_t)L->frames.size();
+    return ICPMI_OK;
+}
+
+int icpmi_loop_clear(icpmi_loop *L)
+{
+    if (!L) return ICPMI_ERR_NULL;
+    L->frames.clear();
+    L->labels.clear();
+    L->described = 0;
+    return ICPMI_OK;
+}
+
+int icpmi_loop_descriptor(icpmi_loop *L, int64_t entry, double *desc_out)
+{
+    if (!L) return ICPMI_ERR_NULL;
+    icpmi_ctx *ctx = L->map->ctx;
+    int rc;
+    if ((rc = check_common(ctx))) return rc;
+    if (!desc_out) return fail(ctx, ICPMI_ERR_NULL, "null argument");
+    if (entry < 0 || entry >= (int64_t)L->frames.size())
+        return fail(ctx, ICPMI_ERR_ARG, "entry %lld outside [0, %lld)", (long long)entry, (long long)L->frames.size());
+    Range range("icpmi:loop_descriptor");
+    std::vector<DevBuf> old;
+    rc = loop_queue_describe(L, old);
+    if (rc == ICPMI_OK) {
+        const hipError_t e = hipMemcpyAsync(desc_out, (const double *)L->d_desc.p + (size_t)entry * kScCells,
+                                            sizeof(double) * kScCells, hipMemcpyDeviceToHost, ctx->stream);
+        if (e != hipSuccess) rc = fail(ctx, ICPMI_ERR_HIP, "loop store: %s", hipGetErrorString(e));
+    }
+    return loop_settle(L, old, rc); // the call's one wait
+}
+
+int icpmi_loop_detect(icpmi_loop *L, icpmi_loop_result *out, int64_t cap, int64_t *n_out)
+{
+    if (!L) return ICPMI_ERR_NULL;
+    icpmi_ctx *ctx = L->map->ctx;
+    int rc;
+    if ((rc = check_common(ctx))) return rc;
+    if (!n_out || (!out && cap > 0)) return fail(ctx, ICPMI_ERR_NULL, "null argument");
+    if (ctx->comm || ctx->cb_allreduce) return fail(ctx, ICPMI_ERR_ARG, "a context with a communicator registers one (sharded) problem at a time");
+    *n_out = 0;
+    const int64_t E = (int64_t)L->frames.size();
+    if (E < 2) return ICPMI_OK; // :69
+    Range range("icpmi:loop_detect");
+    hipStream_t s = ctx->stream;
+    const int64_t q = E - 1;
+    std::vector<DevBuf> old;
+    rc = loop_queue_describe(L, old);
+    if (rc == ICPMI_OK && (size_t)q > L->h_cap) { // the list holds every older entry, at worst
+        loop_free_host(L);
+        const size_t cap_rec = std::max<size_t>(2 * (size_t)q, 1024);
+        void *h = nullptr;
+        const hipError_t e = hipHostMalloc(&h, sizeof(LoopCandidate) * cap_rec + 64, hipHostMallocMapped);
+        if (e != hipSuccess) rc = fail(ctx, ICPMI_ERR_HIP, "loop store: hipHostMalloc: %s", hipGetErrorString(e));
+        else {
+            L->h_cand = (LoopCandidate *)h;
+            L->h_count = (int64_t *)((char *)h + sizeof(LoopCandidate) * cap_rec);
+            L->h_cap = cap_rec;
+        }
+    }
+    LoopCandidate *d_cand = nullptr;
+    int64_t *d_count = nullptr;
+    if (rc == ICPMI_OK) {
+        hipError_t e = hipHostGetDevicePointer((void **)&d_cand, L->h_cand, 0);
+        if (e == hipSuccess) e = hipHostGetDevicePointer((void **)&d_count, L->h_count, 0);
+        if (e != hipSuccess) rc = fail(ctx, ICPMI_ERR_HIP, "loop store: hipHostGetDevicePointer: %s", hipGetErrorString(e));
+    }
+    if (rc == ICPMI_OK) {
+        *L->h_count = -1;
+        hipLaunchKernelGGL(k_loop_candidates, dim3((unsigned)q), dim3(64), 0, s, (const double *)L->d_desc.p,
+                           (const int32_t *)L->d_labels.p, (int32_t)q, L->cfg.frame_gap, L->cfg.sc_distance_threshold,
+                           (unsigned *)L->d_counters.p, d_cand, d_count);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) rc = fail(ctx, ICPMI_ERR_HIP, "k_loop_candidates: %s", hipGetErrorString(e));
+    }
+    if ((rc = loop_settle(L, old, rc))) return rc; // the call's one wait before the verifications
+    const int64_t nc = *(volatile int64_t *)L->h_count;
+    if (nc < 0 || nc > q) return fail(ctx, ICPMI_ERR_HIP, "k_loop_candidates returned %lld candidates of %lld", (long long)nc, (long long)q);
+    std::vector<std::pair<double, int>> candidates;
+    candidates.reserve((size_t)nc);
+    for (int64_t i = 0; i < nc; ++i) candidates.emplace_back(L->h_cand[i].dist, (int)L->h_cand[i].entry);
+    std::sort(candidates.begin(), candidates.end()); // :93
+
+    // :96-123: verify in order until max_candidates are accepted; the next min(max_candidates - accepted,
+    // ICPMI_MAX_BATCH) run side by side on the batch's helper contexts, straight from the store
+    icpmi_config icp;
+    icpmi_config_default(&icp);
+    icp.max_iterations = 30; // :102-105
+    icp.tolerance = 1e-6;
+    const int32_t hcap = icp.max_iterations + 1;
+    std::vector<icpmi_loop_result> results;
+    const double *rows = (const double *)L->map->d_rows.p;
+    const int64_t fq = L->frames[(size_t)q];
+    const int64_t q0 = L->map->row0[(size_t)fq], nq = L->map->row0[(size_t)fq + 1] - q0;
+    int verified = 0;
+    size_t pos = 0;
+    while (pos < candidates.size() && verified < L->cfg.max_candidates) { // :97
+        const int32_t take = (int32_t)std::min<size_t>(candidates.size() - pos,
+                                                       std::min<size_t>((size_t)(L->cfg.max_candidates - verified), ICPMI_MAX_BATCH));
+        icpmi_result res[ICPMI_MAX_BATCH];
+        int32_t status[ICPMI_MAX_BATCH];
+        std::vector<double> hist((size_t)take * (size_t)hcap);
+        rc = batch_run(ctx, take, [&](icpmi_ctx *c, int k) {
+            const int64_t f = L->frames[(size_t)candidates[pos + (size_t)k].second];
+            const int64_t t0 = L->map->row0[(size_t)f], nt = L->map->row0[(size_t)f + 1] - t0;
+            // (only the sizes are checked: the rows are the store's, non-null even for a frame of 0 rows)
+            int r = validate_align(c, &icp, nq, &icp, nt, &icp, &res[k], hist.data() + (size_t)k * hcap, hcap);
+            if (r == ICPMI_OK) r = check_common(c);
+            if (r == ICPMI_OK)
+                r = align_staged(c, rows + 3 * (size_t)q0, nq, rows + 3 * (size_t)t0, nt, hipMemcpyDeviceToDevice, &icp,
+                                 &res[k], hist.data() + (size_t)k * hcap, hcap);
+            return r;
+        }, status);
+        if (rc) return rc;
+        for (int32_t k = 0; k < take; ++k) {
+            const icpmi_result &r = res[k];
+            const auto &cand = candidates[pos + (size_t)k];
+            if (r.converged && r.final_error < L->cfg.icp_fitness_threshold) { // :112
+                icpmi_loop_result o;
+                o.query_frame = L->labels[(size_t)q];
+                o.match_frame = L->labels[(size_t)cand.second];
+                memcpy(o.transform, r.transformation, sizeof(o.transform));
+                o.scan_context_distance = cand.first;
+                o.icp_fitness = r.final_error;
+                results.push_back(o);
+                ++verified;
+            }
+        }
+        pos += (size_t)take;
+    }
+    *n_out = (int64_t)results.size();
+    if ((int64_t)results.size() > cap)
+        return fail(ctx, ICPMI_ERR_CAPACITY, "output holds %lld results, needs %lld", (long long)cap, (long long)results.size());
+    if (!results.empty()) memcpy(out, results.data(), sizeof(icpmi_loop_result) * results.size());
     return ICPMI_OK;
 }
 

@@ -8,7 +8,8 @@
 // The max per bin is order independent, so an LDS 64-bit atomic max on an order-preserving
 // integer image of the double gives the reference's result bit for bit (up to atan2's last
 // ulp at a sector boundary).  The distance sums run in the reference's (ring, sector) order
-// with unfused multiply-adds, one thread per (descriptor, shift).
+// with unfused multiply-adds, one thread per (descriptor, shift).  Both bodies are device functions
+// (sc_describe, sc_distance) that the loop-closure store's kernels (loop_store.h) run as well.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -28,8 +29,10 @@ __device__ __forceinline__ double sc_decode(unsigned long long k)
     return __longlong_as_double((long long)b);
 }
 
-__global__ __launch_bounds__(1024) void k_scan_context(const double *__restrict__ cloud, int n,
-                                                       double *__restrict__ desc)
+// The body of k_scan_context, shared with k_loop_describe (loop_store.h): the descriptor of rows
+// cloud[0 .. n) into desc, by the 1024 threads of one workgroup.  (The LDS is declared here, not passed in: so the
+// kernels' code is what it was before the body moved.)
+__device__ __forceinline__ void sc_describe(const double *__restrict__ cloud, int n, double *__restrict__ desc)
 {
     __shared__ unsigned long long bins[kScCells];
     const double kMaxRange = 80.0;                         // scan_context.hpp:29
@@ -56,17 +59,21 @@ __global__ __launch_bounds__(1024) void k_scan_context(const double *__restrict_
     }
 }
 
-// grid = history size, 64 threads: thread `shift` evaluates column_shifted_distance
-__global__ __launch_bounds__(64) void k_sc_distances(const double *__restrict__ query,
-                                                     const double *__restrict__ hist, int count,
-                                                     double *__restrict__ out)
+__global__ __launch_bounds__(1024) void k_scan_context(const double *__restrict__ cloud, int n,
+                                                       double *__restrict__ desc)
+{
+    sc_describe(cloud, n, desc);
+}
+
+// The body of k_sc_distances, shared with k_loop_candidates (loop_store.h): column_shifted_distance of
+// descriptor `other` to `query` by the 64 threads of one workgroup (thread `shift` evaluates one shift).  Every
+// lane returns the min over the shifts.
+__device__ __forceinline__ double sc_distance(const double *__restrict__ query, const double *__restrict__ other)
 {
     __shared__ double a[kScCells], b[kScCells];
-    const int d = blockIdx.x;
-    if (d >= count) return;
     for (int e = threadIdx.x; e < kScCells; e += 64) {
         a[e] = query[e];
-        b[e] = hist[(size_t)d * kScCells + e];
+        b[e] = other[e];
     }
     __syncthreads();
     const int shift = threadIdx.x;
@@ -90,6 +97,17 @@ __global__ __launch_bounds__(64) void k_sc_distances(const double *__restrict__ 
         const double o = __shfl_xor(dist, off, 64);
         dist = o < dist ? o : dist;
     }
+    return dist;
+}
+
+// grid = history size, 64 threads
+__global__ __launch_bounds__(64) void k_sc_distances(const double *__restrict__ query,
+                                                     const double *__restrict__ hist, int count,
+                                                     double *__restrict__ out)
+{
+    const int d = blockIdx.x;
+    if (d >= count) return;
+    const double dist = sc_distance(query, hist + (size_t)d * kScCells);
     if (threadIdx.x == 0) out[d] = dist;
 }
 

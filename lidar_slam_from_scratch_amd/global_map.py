@@ -32,6 +32,8 @@ class GlobalMap:
 
     def close(self):
         if getattr(self, "_h", None):
+            for d in list(getattr(self, "_loops", ())):   # loop_closure.StoreLoopClosureDetector handles go first
+                d.close()
             self._lib.icpmi_map_destroy(self._h)
             self._h = None
 

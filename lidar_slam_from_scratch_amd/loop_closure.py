@@ -8,6 +8,9 @@ with the arithmetic behind a small backend object:
     backend.align(source, target, max_iterations, tolerance)      icp.hpp:157-258
 `GpuBackend` goes through the C ABI; the parity tests plug the oracle in instead.
 """
+import ctypes as C
+import weakref
+
 import numpy as np
 
 MAX_BATCH = 8   # ICPMI_MAX_BATCH (include/icp_mi355x.h): registrations one icpmi_align_batch call takes
@@ -123,3 +126,64 @@ class LoopClosureDetector:
                                                      np.asarray(r.transformation), sc_dist, r.final_error))
                     verified += 1
         return results
+
+
+class StoreLoopClosureDetector:
+    """The same detector with its database on the device (icpmi_loop, csrc/loop_store.h): an index over the frames of a
+    global_map.GlobalMap.  add_frame(store_frame, frame_idx) names a frame the store already holds; the detector keeps
+    no clouds and no descriptors on the host, and detect() returns what LoopClosureDetector(GpuBackend(ctx)) returns
+    over the same clouds, bit for bit."""
+
+    def __init__(self, ctx, store, config=None):
+        from . import capi
+        self._lib = capi.load_library()
+        self.ctx, self.store = ctx, store
+        self.config = config or LoopClosureConfig()
+        c = capi.LoopConfig()
+        c.frame_gap, c.max_candidates = int(self.config.frame_gap), int(self.config.max_candidates)
+        c.sc_distance_threshold = float(self.config.sc_distance_threshold)
+        c.icp_fitness_threshold = float(self.config.icp_fitness_threshold)
+        h = C.c_void_p()
+        ctx._check(self._lib.icpmi_loop_create(store._h, C.byref(c), C.byref(h)))
+        self._h = h
+        for owner in (ctx, store):     # Context.close() and store.close() destroy it before the map
+            if not hasattr(owner, "_loops"):
+                owner._loops = weakref.WeakSet()
+            owner._loops.add(self)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.icpmi_loop_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def add_frame(self, store_frame, frame_idx):
+        """loop_closure.hpp:54-60 for the cloud the store holds as frame `store_frame`"""
+        self.ctx._check(self._lib.icpmi_loop_add_frame(self._h, int(store_frame), int(frame_idx)))
+
+    def size(self):
+        n = C.c_int64(0)
+        self.ctx._check(self._lib.icpmi_loop_size(self._h, C.byref(n)))
+        return n.value
+
+    def clear(self):
+        """drops every entry; the store is untouched"""
+        self.ctx._check(self._lib.icpmi_loop_clear(self._h))
+
+    def descriptor(self, entry):
+        """entry's (20, 60) descriptor (icpmi_scan_context of its rows, bit for bit)"""
+        from . import capi
+        out = np.empty((20, 60))
+        self.ctx._check(self._lib.icpmi_loop_descriptor(self._h, int(entry), capi._dp(out)))
+        return out
+
+    def detect(self):
+        """loop_closure.hpp:66-126: closures for the most recently added entry"""
+        from . import capi
+        cap = max(int(self.config.max_candidates), 0)
+        buf = (capi.LoopResult * max(cap, 1))()
+        n = C.c_int64(0)
+        self.ctx._check(self._lib.icpmi_loop_detect(self._h, buf, cap, C.byref(n)))
+        return [LoopClosureResult(r.query_frame, r.match_frame, np.array(r.transform[:]).reshape(4, 4),
+                                  r.scan_context_distance, r.icp_fitness) for r in buf[:n.value]]

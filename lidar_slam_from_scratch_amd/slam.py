@@ -15,7 +15,9 @@ The detector uses the node's LoopClosureConfig (:77-81).  By default everything 
 `align`, `loop_backend` and `pose_graph` replace the three parts (the tests put the CPU oracle and
 scripts/pose_graph_ref.py there).  Given a `global_map` (global_map.GlobalMap, or scripts/map_ref.py's restatement),
 the run also keeps every frame in it (:71,123), rebuilds the recent clouds after each successful optimize (:187-194)
-and at the end the cell set and the published map (build_final_global_map, :196-209, :223-229, :235-238).  As in the reference, the frame after a too-few-points frame names a pose with no
+and at the end the cell set and the published map (build_final_global_map, :196-209, :223-229, :235-238).  With
+loop_on_device the detector's database lives on the device as an index over the kept scans (icpmi_loop): the global
+map's, or a private store's.  As in the reference, the frame after a too-few-points frame names a pose with no
 estimate: its addOdometryFactor raises (ICPMI_ERR_ARG), where the reference throws."""
 import numpy as np
 
@@ -39,19 +41,38 @@ def node_loop_config():
 
 
 def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, pose_graph_config=None,
-             align=None, loop_backend=None, pose_graph=None, global_map=None, grid=None, map_voxel=1.0):
+             align=None, loop_backend=None, pose_graph=None, global_map=None, grid=None, map_voxel=1.0,
+             loop_on_device=False):
     """frames: sequence of N x 3 fp64 clouds (already downsampled).  Returns a SlamRun.  global_map: an object with
-    add_frame, recent_clouds and finish (None: no map is built); grid: its occupancy grid config (None: defaults)."""
+    add_frame, recent_clouds and finish (None: no map is built); grid: its occupancy grid config (None: defaults).
+    loop_on_device: the detector is loop_closure.StoreLoopClosureDetector over global_map (a global_map.GlobalMap),
+    or over a private GlobalMap that keeps every frame; it holds no clouds and gives the same closures."""
+    if loop_on_device and loop_backend is not None:
+        raise ValueError("loop_backend and loop_on_device=True both choose the detector")
     if align is None:
         from .odometry import gpu_align
         align = gpu_align(ctx)
-    if loop_backend is None:
+    if loop_backend is None and not loop_on_device:
         loop_backend = lc.GpuBackend(ctx)
     if pose_graph is None:
         from .pose_graph import PoseGraph
         pose_graph = PoseGraph(ctx, pose_graph_config)
     run = SlamRun()
-    detector = lc.LoopClosureDetector(loop_backend, node_loop_config())
+    store = None                                                     # (the store the device detector indexes)
+    if loop_on_device:
+        from .global_map import GlobalMap
+        store = global_map if global_map is not None else GlobalMap(ctx)
+        detector = lc.StoreLoopClosureDetector(ctx, store, node_loop_config())
+    else:
+        detector = lc.LoopClosureDetector(loop_backend, node_loop_config())
+
+    def keep(cloud):                                                 # downsampled_clouds_.push_back, :71,123
+        """-> the store index of the frame just kept (None without a store)"""
+        if global_map is not None:
+            global_map.add_frame(cloud)
+        elif store is not None:
+            store.add_frame(cloud)
+        return store.size()[0] - 1 if store is not None else None
 
     def add(kind, *args):
         run.factors.append((kind,) + args)
@@ -73,13 +94,11 @@ def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, po
     add("prior", 0, np.eye(4))                                       # :66
     frames = list(frames)
     prev = np.ascontiguousarray(frames[0], dtype=np.float64)         # :69-72
-    if global_map is not None:
-        global_map.add_frame(prev)                                   # :71
+    keep(prev)                                                       # :71
     for k in range(1, len(frames)):
         curr = np.ascontiguousarray(frames[k], dtype=np.float64)
         pending = False
-        if global_map is not None:
-            global_map.add_frame(curr)                               # :123
+        kept = keep(curr)                                            # :123
         if curr.shape[0] < min_points:                               # :125-130
             run.poses.append(run.poses[-1].copy())
             prev = curr
@@ -90,7 +109,7 @@ def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, po
         run.poses.append(run.poses[-1] @ delta)                      # :142-143
         add("odom", len(run.poses) - 2, len(run.poses) - 1, delta, float(r.final_error))   # :145
         prev = curr                                                  # :151
-        detector.add_frame(curr, k)                                  # :159
+        detector.add_frame(kept if loop_on_device else curr, k)      # :159
         if k % 10 == 0 and k > 50:                                   # :160
             for c in detector.detect():                              # :161-166
                 add("loop", c.match_frame, c.query_frame, np.asarray(c.transform, dtype=np.float64))
@@ -101,4 +120,8 @@ def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, po
     optimize("end")                                                  # :103-106
     if global_map is not None:                                       # build_final_global_map, :107,196-209
         run.cells, run.published_map = global_map.finish(run.poses, grid, map_voxel)
+    if loop_on_device:                                               # the detector (and a private store) go now
+        detector.close()
+        if global_map is None:
+            store.close()
     return run
