@@ -118,7 +118,7 @@ typedef struct {
     int64_t nn_rows_listed;                          /* all-pairs engine with list reuse (ICPMI_NN_REUSE, default on): rows its bounded
                                                         passes listed again -- the others kept their lists -- and ... */
     int64_t nn_coarse_skipped;                       /* ... those passes whose coarse launch had no row to list, every workgroup left at
-                                                        once.  With list reuse nn_pairs counts the pairs of the blocks of rows that ran;
+                                                        once.  With list reuse nn_pairs counts the pairs of the listed rows' workgroups;
                                                         both are counted on the device with profiling on only */
 } icpmi_profile;
 

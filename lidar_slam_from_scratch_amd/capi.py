@@ -663,7 +663,7 @@ class Context:
 
     def nn_reuse_passes(self, cap=1024):
         """Per bounded pass of the last registration (profiling on, all-pairs engine with list reuse): the rows its coarse
-        pass listed and the blocks of rows it ran, as two lists; empty without list reuse or profiling."""
+        pass listed and the workgroup columns it ran (ceil(rows / rows per workgroup)), as two lists; empty without list reuse or profiling."""
         fn = self._lib.icpmi_debug_nn_reuse
         fn.restype = C.c_int64
         fn.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_int64]

@@ -206,8 +206,7 @@ struct icpmi_ctx {
     int64_t grid_n = 0;                             // cells in grid_set
     unsigned *h_grid = nullptr;                     // pinned: the set's size on its way back
     unsigned long long *h_cnt = nullptr;            // pinned: the resolve's counters on their way back (profiling)
-    unsigned nn_epoch = 0;                          // list reuse: epoch of the last bounded pass queued (RowBounds, kernels.h)
-    std::vector<unsigned> reuse_rows, reuse_blocks; // profiling: per pass of the last registration, rows listed and coarse blocks run
+    std::vector<unsigned> reuse_rows, reuse_blocks; // profiling: per pass of the last registration, rows listed and workgroup columns run
     FilePrefetch *prefetch = nullptr;               // worker reading the next frame file (icpmi_stream_prefetch_file)
     // the target whose search structure and normals the context's buffers currently hold (prepare_target):
     // icpmi_stream_push prepares the NEXT frame's target while the caller is still busy with this frame's result
@@ -578,22 +577,24 @@ bool nn_reuse_enabled()
 }
 constexpr double kNnSkin = 0.5, kNnLoose = 8.0; // (the sweep: DESIGN.md, "List reuse")
 
-// The per-row arrays of the bounded pass inside ctx->nn_lists (n rows), then list reuse's per-block epoch words and its
-// per-pass statistics
+// The per-row arrays of the bounded pass inside ctx->nn_lists (n rows), then list reuse's word per 64 rows, its packed
+// list of rows (kRowListHead words in front) and its per-pass statistics
 struct NnListRows {
     double *ub;
     unsigned *ent;
     float *ubf, *sqf;
     int *cnt;
     RowList *xb;
-    unsigned *epoch_w;
+    unsigned long long *mask;
+    int *list;
     unsigned *stat_rows, *stat_blocks; // [kReuseStatPasses] each (profiling)
 };
 constexpr size_t kNnListRowBytes = sizeof(double) + 2 * sizeof(float) + sizeof(int) + sizeof(unsigned) * kNnEntCap + sizeof(RowList);
 constexpr int kReuseStatPasses = 1024; // (passes beyond are added to the last entry)
 size_t nn_list_bytes(int n)
 {
-    return kNnListRowBytes * (size_t)n + 64 + sizeof(unsigned) * ((size_t)n / kReuseRows + 2 + 2 * kReuseStatPasses);
+    return kNnListRowBytes * (size_t)n + 64 + sizeof(unsigned long long) * (((size_t)n + 63) / 64) +
+           sizeof(int) * ((size_t)n + kRowListHead) + sizeof(unsigned) * 2 * kReuseStatPasses;
 }
 NnListRows nn_list_rows(const icpmi_ctx *ctx, int n)
 {
@@ -604,8 +605,9 @@ NnListRows nn_list_rows(const icpmi_ctx *ctx, int n)
     r.sqf = r.ubf + n;
     r.cnt = (int *)(r.sqf + n);
     r.xb = (RowList *)(((uintptr_t)(r.cnt + n) + 63) & ~(uintptr_t)63);
-    r.epoch_w = (unsigned *)(r.xb + n);
-    r.stat_rows = r.epoch_w + (size_t)n / kReuseRows + 2;
+    r.mask = (unsigned long long *)(r.xb + n); // (RowList is 32 bytes: 8-byte aligned)
+    r.list = (int *)(r.mask + ((size_t)n + 63) / 64);
+    r.stat_rows = (unsigned *)(r.list + (size_t)n + kRowListHead);
     r.stat_blocks = r.stat_rows + kReuseStatPasses;
     return r;
 }
@@ -650,7 +652,7 @@ size_t coarse_groups_lds(int splits) { return sizeof(unsigned) * (2 * (size_t)sp
 // in ctx->nn_lists (RowBounds, kernels.h; nn_bounded.h)
 int launch_nn_mfma(icpmi_ctx *ctx, const double *d_qry, int n, int m, int *d_idx, double *d_d2,
                    const IcpState *st, const double *d_tgt = nullptr, const double *d_nrm = nullptr,
-                   double *d_partials = nullptr, int pruned_pass = -1, bool bounded = false, unsigned reuse_epoch = 0,
+                   double *d_partials = nullptr, int pruned_pass = -1, bool bounded = false, bool reuse_list = false,
                    int stat_pass = 0)
 {
     const int splits = ctx->nn_splits;
@@ -681,17 +683,17 @@ int launch_nn_mfma(icpmi_ctx *ctx, const double *d_qry, int n, int m, int *d_idx
                                    ctx->opt.profile ? group_stats(ctx) : (unsigned long long *)nullptr, (unsigned long long)(groups * splits),
                                    st, kl, group_work(ctx, pruned_pass & 1), group_work(ctx, (pruned_pass + 1) & 1));
             } else {
-                // list reuse (reuse_epoch != 0): only the blocks of rows that one of their rows marked for this pass do any work
-                const unsigned *epoch_w = reuse_epoch ? lr.epoch_w : nullptr;
-                unsigned *blocks_run = reuse_epoch && ctx->opt.profile ? lr.stat_blocks + std::min(stat_pass, kReuseStatPasses - 1) : nullptr;
+                // list reuse (`reuse_list`): the pass runs over the packed list of the rows listed again (k_row_list) and no others
+                const int *list = reuse_list ? lr.list : nullptr;
+                unsigned *blocks_run = reuse_list && ctx->opt.profile ? lr.stat_blocks + std::min(stat_pass, kReuseStatPasses - 1) : nullptr;
                 if (coarse_half_units(ctx, n, splits)) {
                     constexpr int per = kCoarseQueries / kCoarseQT; // queries per workgroup with one tile per wave
                     hipLaunchKernelGGL((k_nn_coarse_bounded<1, kCoarseWaves>), dim3((n + per - 1) / per, splits), dim3(kCoarseThreads), 0,
-                                       ctx->stream, d_qry, n, (const uint4 *)ctx->bpack.p, frames, kl, st, epoch_w, reuse_epoch, blocks_run);
+                                       ctx->stream, d_qry, n, (const uint4 *)ctx->bpack.p, frames, kl, st, list, blocks_run);
                 } else
                     hipLaunchKernelGGL((k_nn_coarse_bounded<kCoarseQT, kCoarseWaves>), dim3((n + kCoarseQueries - 1) / kCoarseQueries, splits),
-                                       dim3(kCoarseThreads), 0, ctx->stream, d_qry, n, (const uint4 *)ctx->bpack.p, frames, kl, st, epoch_w,
-                                       reuse_epoch, blocks_run);
+                                       dim3(kCoarseThreads), 0, ctx->stream, d_qry, n, (const uint4 *)ctx->bpack.p, frames, kl, st, list,
+                                       blocks_run);
             }
             ctx->prof.nn_coarse_blocks += (int64_t)((n + kCoarseQueries - 1) / kCoarseQueries) * splits;
         }
@@ -706,8 +708,8 @@ int launch_nn_mfma(icpmi_ctx *ctx, const double *d_qry, int n, int m, int *d_idx
         else
             hipLaunchKernelGGL(k_nn_resolve_bounded, dim3(resolve_blocks(n)), dim3(64 * kResolveWW), 0, ctx->stream, ICPMI_BOUNDED_ARGS);
 #undef ICPMI_BOUNDED_ARGS
-        if (!reuse_epoch) ctx->prof.nn_pairs += (double)n * (double)m; // (a pass with list reuse: its blocks that ran, counted
-                                                                        // on the device -- profiling only -- and added after the call)
+        if (!reuse_list) ctx->prof.nn_pairs += (double)n * (double)m; // (a pass with list reuse: its workgroup columns that ran,
+                                                                      // counted on the device -- profiling only -- and added after the call)
         ctx->prof.bounded_launches += 1;
         HIP_TRY(ctx, hipGetLastError());
         return ICPMI_OK;
@@ -1237,10 +1239,11 @@ int align_device(icpmi_ctx *ctx, const double *d_src, int64_t n_src64, const dou
     if (pruned && !bounded_loop) return fail(ctx, ICPMI_ERR_ARG, "internal: the culled engine needs the bounded resolve kernels");
     // List reuse (RowBounds, kernels.h), all-pairs engine: a row keeps its list of slots from pass to pass while its bound and
     // its drift from where the list was built show that a new list could hold nothing the kept one lacks, and the coarse
-    // pass runs only over the blocks of rows that were listed again.  A call's first pass lists every row (k_nn_prebound1
-    // marks its lists as not to be kept).  The culled engine keeps its own form.
+    // pass runs over the packed list of the rows that were listed again (k_row_list, queued behind the kernel that moves
+    // the rows).  A call's first pass lists every row (k_nn_prebound1 marks its lists as not to be kept).  The culled engine
+    // keeps its own form.
     const bool reuse = bounded_loop && !pruned && nn_reuse_enabled();
-    unsigned pass_epoch = 0; // the epoch the coming bounded pass runs under (0: every block runs)
+    bool pass_list = false; // the coming bounded pass runs over the packed list (false: over every row -- a call's first pass)
     RowBounds rb{};
     NnListRows lr{};
     if (bounded_loop) {
@@ -1249,18 +1252,15 @@ int align_device(icpmi_ctx *ctx, const double *d_src, int64_t n_src64, const dou
         rb = RowBounds{d_tgt, idx, m, lr.ub, lr.ubf, lr.sqf, lr.cnt};
         if (reuse) {
             rb.xb = lr.xb;
-            rb.epoch_w = lr.epoch_w;
+            rb.mask = lr.mask;
             rb.skin = kNnSkin;
             rb.loose = kNnLoose;
             if (ctx->opt.profile) HIP_TRY(ctx, hipMemsetAsync(lr.stat_rows, 0, sizeof(unsigned) * 2 * kReuseStatPasses, s));
         }
     }
-    // before each kernel that moves the rows for pass `next`: the epoch it marks the blocks of rows with
-    auto next_epoch = [&](int next) {
-        if (!reuse) return;
-        if (++ctx->nn_epoch == 0) ++ctx->nn_epoch; // (0 stands for "no reuse")
-        rb.epoch = ctx->nn_epoch;
-        rb.rebuilt = ctx->opt.profile ? lr.stat_rows + std::min(next, kReuseStatPasses - 1) : nullptr;
+    // before each kernel that moves the rows for pass `next`: where it counts the rows listed again (profiling)
+    auto next_pass_stats = [&](int next) {
+        if (reuse) rb.rebuilt = ctx->opt.profile ? lr.stat_rows + std::min(next, kReuseStatPasses - 1) : nullptr;
     };
 
     // current_source = source * R0^T + t0^T (icp.hpp:174-176)
@@ -1304,10 +1304,10 @@ int align_device(icpmi_ctx *ctx, const double *d_src, int64_t n_src64, const dou
         if (n > 0 && fused) {
             if ((r2 = launch_nn_mfma(ctx, cur, n, m, idx, nullptr, st, d_tgt, nrm, partials,
                                      pruned ? pass_no : -1, bounded_loop /* incumbents in idx, bounds in place: from k_nn_prebound1 or the kernel that moved the rows */,
-                                     pass_epoch, pass_no))) return r2;
+                                     pass_list, pass_no))) return r2;
             ++pass_no;
-            if (!final_pass) next_epoch(pass_no);
-            pass_epoch = reuse && !final_pass ? rb.epoch : 0;
+            if (!final_pass) next_pass_stats(pass_no);
+            pass_list = reuse && !final_pass;
         } else if (n > 0) {
             if ((r2 = launch_nn(ctx, cur, n, d_tgt, m, idx, nullptr, st))) return r2;
         }
@@ -1368,6 +1368,9 @@ int align_device(icpmi_ctx *ctx, const double *d_src, int64_t n_src64, const dou
                 hipLaunchKernelGGL(k_transform, dim3(std::min(2048, (n + 255) / 256)), dim3(256), 0, s,
                                    cur, cur, n, st, 0, 1, (const unsigned *)nullptr, rb);
         }
+        if (pass_list) // the rows just moved left their "listed again" words: the coming pass's list of rows
+            hipLaunchKernelGGL(k_row_list, dim3(((n + 63) / 64 + kRowListThreads - 1) / kRowListThreads), dim3(kRowListThreads), 0, s,
+                               (const unsigned long long *)lr.mask, n, lr.list, (const IcpState *)st);
         return ICPMI_OK;
     };
 
@@ -1469,8 +1472,9 @@ int align_device(icpmi_ctx *ctx, const double *d_src, int64_t n_src64, const dou
     ctx->reuse_rows.clear();
     ctx->reuse_blocks.clear();
     if (reuse && ctx->opt.profile && pass_no > 0) {
-        // list reuse, per pass: the rows listed (the first pass lists all) and the coarse blocks of rows that ran; the pairs
-        // of the blocks that ran are the pairs searched, and a pass none of whose blocks ran is a skipped coarse launch
+        // list reuse, per pass: the rows listed (the first pass lists all) and the workgroup columns of the coarse pass that
+        // ran, ceil(rows / rows per workgroup); their pairs are the pairs searched, and a pass none of which ran is a skipped
+        // coarse launch
         const int np = std::min(pass_no, kReuseStatPasses);
         ctx->reuse_rows.resize(np);
         ctx->reuse_blocks.resize(np);
@@ -3147,7 +3151,7 @@ extern "C" int icpmi_debug_loop_rows(icpmi_ctx *ctx, int32_t *idx_out, double *c
 }
 
 // List reuse of the last registration with profiling on (RowBounds, kernels.h): per bounded pass, the rows listed by its
-// coarse pass and the blocks of rows that pass ran.  Returns the number of passes (at most `cap` are written), 0 without
+// coarse pass and the workgroup columns that pass ran.  Returns the number of passes (at most `cap` are written), 0 without
 // list reuse or profiling.
 extern "C" int64_t icpmi_debug_nn_reuse(const icpmi_ctx *ctx, uint32_t *rows_out, uint32_t *blocks_out, int64_t cap)
 {

@@ -465,11 +465,13 @@ __global__ __launch_bounds__(64) void k_step(IcpState *st, double *history, int 
 // d = |y - x_b|, and every target that can still be its nearest neighbour is within sqrt(ub) of y, hence within
 // sqrt(ub) + d of x_b: while sqrt(ub) + d <= R_b (with a margin for the fp64 roundings of both sides) the kept list is a
 // superset of what a new one would list, and the exact resolve returns the same bits from it.  Such a row keeps its
-// list (cnt / ent untouched) and gives the coarse pass a NaN threshold, under which nothing is listed; any other row is
-// listed again for R_b = sqrt(ub) + 2 skin and marks its coarse block with the coming pass's epoch, and a coarse block
-// that no row marked leaves at once (k_nn_coarse_bounded).
+// list (cnt / ent untouched); any other row is listed again for R_b = sqrt(ub) + 2 skin.  The coarse pass runs over the
+// rows listed again and over no other: a wave of the kernel that moves the rows holds 64 consecutive rows, and one lane
+// stores the wave's ballot of "listed again" as the word of that group of rows (`mask`: every group's word in every pass,
+// zeros too, so nothing is ever cleared); k_row_list below packs the set bits' rows, in ascending order, into the list
+// k_nn_coarse_bounded takes its rows from (nn_mfma.h, RowsListed).  A row that keeps its list is not in it, and costs the
+// coarse pass nothing.
 constexpr int kNnEntCap = 8;   // list words per row of the bounded 1-NN pass (nn_mfma.h, nn_bounded.h)
-constexpr int kReuseRows = 256; // rows per epoch word: the rows of one workgroup of k_nn_coarse_bounded's half-unit form
 struct RowList {
     double x, y, z; // where the row's list was built
     double r;       // its listing radius R_b (NaN: the list is not to be kept, e.g. a call's first pass)
@@ -480,11 +482,11 @@ struct RowBounds {
     int m;
     double *ub;        // [n] |moved row - tgt[idx]|^2, +Inf without a match
     float *ubf, *sqf;  // [n] the coarse pass's radius^2 in fp32 and its square root, rounded up; NaN / 0 for a row with a
-                       // non-finite coordinate or one that keeps its list
+                       // non-finite coordinate, and for one that keeps its list (which the coarse pass never reads: such a
+                       // row is not in the packed list)
     int *cnt;          // [n] the row's list length, cleared here for a row listed again by the coming coarse pass
     RowList *xb;       // [n] list reuse (null: every row is listed again, the form before list reuse)
-    unsigned *epoch_w; // [n / kReuseRows + 1] per block of rows: the epoch of the last pass any of its rows was listed for
-    unsigned epoch;    // the coming pass's epoch (never 0)
+    unsigned long long *mask; // [(n + 63) / 64] list reuse: bit b of word g = row 64 g + b is listed again by the coming pass
     double skin;       // the skin as a fraction of the row's sqrt(ub)
     double loose;      // a list built for more than `loose` x the radius it would be built for now is not kept (0: no limit)
     unsigned *rebuilt; // profiling (or null): the coming pass's count of rows listed again
@@ -572,7 +574,6 @@ struct RowBatch {
                         if (!keep) {
                             r2 = rn * rn;
                             rb.xb[i] = RowList{px, py, pz, rn};
-                            rb.epoch_w[i / kReuseRows] = rb.epoch; // (equal values from every row of the block: plain stores)
                         }
                     }
                     if (!keep) {
@@ -586,13 +587,58 @@ struct RowBatch {
                 rb.ubf[i] = ubf;
                 rb.sqf[i] = sqf;
                 if (!keep) rb.cnt[i] = 0;
-                if (rb.rebuilt) listed += (unsigned)__popcll(__ballot(!keep && ubf == ubf));
+                if (rb.mask) {
+                    // the wave's rows are 64 consecutive ones from a multiple of 64 (rows past n are not here and leave their
+                    // bits clear): lane 0 holds the first of them and stores the group's word
+                    const unsigned long long again = __ballot(!keep && ubf == ubf);
+                    if ((i & 63) == 0) rb.mask[i >> 6] = again;
+                    if (rb.rebuilt) listed += (unsigned)__popcll(again);
+                }
             }
         }
         if (rb.rebuilt && listed && (int)(threadIdx.x & 63) == __ffsll((long long)__ballot(1)) - 1) atomicAdd(rb.rebuilt, listed);
     }
 };
 constexpr int kRowBatch = 4;
+
+// The packed list of the rows listed again, from the words the kernel that moved the rows left (RowBounds::mask):
+// list[0] = their number, list[1] = 1 where that is every row (the coarse pass then indexes its rows directly and reads no
+// list: none is written), list[kRowListHead ...] = the rows in ascending order -- neighbours in the list are neighbours in
+// the rows' Morton order, which the coarse epilogue's short path lives on.  One word per thread.  A workgroup waits for no
+// other one: each counts the words below its own itself (12 KB of words per 100k rows, out of the L2), and the rest for the
+// total, then scans its own 256 counts and expands its words (list_reuse.h).  No atomics.  Every workgroup thus reads all
+// ceil(n / 64) words, quadratic in n / 16,384: 7 workgroups x 12 KB at 100k rows, 62 x 125 KB at 1M rows (not measured there;
+// a pass is 29 ms at that size).
+// Measured and dropped: the same work at the end of the kernel that moves the rows, by its last workgroup behind a fence and
+// a ticket per workgroup -- one launch fewer per iteration, but the fences cost the moving kernel more than the launch:
+// C3 at 30 steps 1.11x the parent's rate against 1.43x in this form, and 0.82x against 1.22x at 100 steps (same box,
+// alternating; profiles/row_list/).
+constexpr int kRowListThreads = 256;
+constexpr int kRowListHead = 16; // (the rows start on a 64-byte line)
+__global__ __launch_bounds__(kRowListThreads) void k_row_list(const unsigned long long *__restrict__ mask, int n, int *__restrict__ list,
+                                                              const IcpState *__restrict__ st)
+{
+    if (st->done) return; // (the rows were not moved and the coarse pass will not run)
+    __shared__ int part[3][kRowListThreads / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nw = (n + 63) / 64, g0 = blockIdx.x * kRowListThreads, g = g0 + tid;
+    const unsigned long long w = g < nw ? mask[g] : 0ull;
+    const int mine = row_list_popcount(w);
+    const unsigned below = wave_scan_incl((unsigned)row_list_count(mask, tid, g0, kRowListThreads));
+    const unsigned above = wave_scan_incl((unsigned)row_list_count(mask, g0 + kRowListThreads + tid, nw, kRowListThreads));
+    const unsigned incl = wave_scan_incl((unsigned)mine);
+    if (lane == 63) part[0][wave] = (int)below, part[1][wave] = (int)above, part[2][wave] = (int)incl;
+    __syncthreads();
+    int at = 0, total = 0;
+#pragma unroll
+    for (int v = 0; v < kRowListThreads / 64; ++v) {
+        at += part[0][v] + (v < wave ? part[2][v] : 0);
+        total += part[0][v] + part[1][v] + part[2][v];
+    }
+    if (blockIdx.x == 0 && tid == 0) list[0] = total, list[1] = total == n;
+    if (total == n) return;
+    row_list_expand(w, g, list + kRowListHead, at + (int)incl - mine);
+}
 
 
 // multi GPU, one launch fewer per iteration: k_step and k_transform in one kernel.  Every workgroup
@@ -607,7 +653,7 @@ __global__ __launch_bounds__(256) void k_step_transform(const double *in, double
                                                         int n_ranks, const RowBounds rb)
 {
     __shared__ IcpState ls;
-    const int i0 = blockIdx.x * 256 + threadIdx.x, stride = gridDim.x * 256;
+    const int i0 = blockIdx.x * 256 + threadIdx.x, stride = gridDim.x * 256; // (a wave: 64 rows from a multiple of 64, RowBounds::mask)
     RowBatch<kRowBatch> rows;
     rows.load(in, rb, i0, stride, n);
     state_copy(&ls, sin);
@@ -646,6 +692,7 @@ __global__ __launch_bounds__(kFinishThreads) void k_finish_step_transform(
     // The kernel is a chain of memory round trips, so everything that does not depend on the state
     // is requested first: this thread's first rows (with their previous matches), and the partial rows (summed whether
     // or not the loop has ended; the sums are taken over only if it has not, like k_finish_step).
+    static_assert(kFinishThreads % 64 == 0, "a wave's rows start at a multiple of 64 (RowBounds::mask)");
     const int i0 = blockIdx.x * kFinishThreads + threadIdx.x, stride = gridDim.x * kFinishThreads;
     RowBatch<kRowBatch> rows;
     rows.load_rows(in, rb, i0, stride, n);

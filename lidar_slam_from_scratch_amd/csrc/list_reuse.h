@@ -24,4 +24,50 @@ ICPMI_HD inline double list_radius(const double sq, const double disp, const dou
 // value: the factor 1 + 1e-12 on the left covers them.  NaN r_b (a list not to be kept) fails the comparison.
 ICPMI_HD inline bool list_certified(const double sq, const double d, const double r_b) { return (sq + d) * (1.0 + 1e-12) <= r_b; }
 
+// ---- the packed list of the rows listed again (RowBounds::mask, k_row_list in kernels.h) -------------------------------
+// The kernel that moves the rows leaves one 64-bit word per group of 64 consecutive rows, bit b of word g set where row
+// 64 g + b is listed again.  The packed list is the set bits' rows in ascending order: row_list_count gives a word's place
+// in it, row_list_expand writes a word's rows there.  tests/cpp/row_list_check.cpp runs the three on the host.
+ICPMI_HD inline int row_list_popcount(unsigned long long w)
+{
+    w = w - ((w >> 1) & 0x5555555555555555ull);
+    w = (w & 0x3333333333333333ull) + ((w >> 2) & 0x3333333333333333ull);
+    w = (w + (w >> 4)) & 0x0f0f0f0f0f0f0f0full;
+    return (int)((w * 0x0101010101010101ull) >> 56);
+}
+
+// set bits of words[lo], words[lo + step], ... below `hi` (the device: one thread's share of a prefix; the host: step 1)
+ICPMI_HD inline int row_list_count(const unsigned long long *words, const int lo, const int hi, const int step)
+{
+    int c = 0;
+    for (int g = lo; g < hi; g += step) c += row_list_popcount(words[g]);
+    return c;
+}
+
+// position of the k-th set bit of w, k = 0 for the lowest (k < popcount(w)): by halves, on the counts below each half
+ICPMI_HD inline int row_list_kth_bit(unsigned long long w, int k)
+{
+    int pos = 0;
+    for (int width = 32; width > 0; width >>= 1) {
+        const unsigned long long low = w & ((1ull << width) - 1ull);
+        const int c = row_list_popcount(low);
+        if (k >= c) {
+            k -= c;
+            w >>= width;
+            pos += width;
+        } else {
+            w = low;
+        }
+    }
+    return pos;
+}
+
+// rows[at ...] = the rows of group `g` whose bit is set in `w`, ascending; returns how many
+ICPMI_HD inline int row_list_expand(const unsigned long long w, const int g, int *rows, const int at)
+{
+    const int c = row_list_popcount(w);
+    for (int k = 0; k < c; ++k) rows[at + k] = 64 * g + row_list_kth_bit(w, k);
+    return c;
+}
+
 } // namespace icpmi

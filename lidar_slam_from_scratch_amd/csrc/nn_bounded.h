@@ -25,9 +25,9 @@
 // The normal-equation terms are formed and summed exactly as in k_nn_resolve<16> (resolve_finish), so the partial rows,
 // hence history and pose, are bit-identical to the unbounded pass's.
 // Keeping a row's list (all-pairs engine, ICPMI_NN_REUSE, default on; RowBounds in kernels.h, list_reuse.h): a row whose
-// list, built at x_b for radius R_b, still covers every target within sqrt(ub) of the row's new place keeps it, and a
-// coarse block none of whose rows was listed again is skipped.  The resolve below reads such a row's kept cnt / ent like
-// a new list; it never looks at the NaN threshold a kept row leaves for the coarse pass (`look` is from the coordinates).
+// list, built at x_b for radius R_b, still covers every target within sqrt(ub) of the row's new place keeps it, and the
+// coarse pass runs over the packed list of the other rows alone (k_row_list).  The resolve below reads such a row's kept
+// cnt / ent like a new list; it never looks at the NaN threshold a kept row is left with (`look` is from the coordinates).
 #pragma once
 #include "nn_mfma.h"
 

@@ -516,6 +516,30 @@ struct KnnLists {
     int cap;          // words per row: kKnnEntCap (normal estimation), kNnEntCap (the ICP loop's bounded 1-NN pass)
 };
 
+// Which row a unit's position stands for (`ROWS`, threaded through the three parts below like QSOA and q0b).
+// RowsDirect: the position is the row -- every kernel but the one below.  RowsListed (k_nn_coarse_bounded with list reuse):
+// position p < count is row rows[p] of the packed list of the rows listed again (k_row_list, kernels.h), and positions from
+// `count` on are nobody's: they load the list's last row, get a NaN threshold and list nothing.  rows == nullptr: every
+// row is listed (count = n), the position is the row again, and no list is read -- a wave-uniform choice.
+struct RowsDirect {
+    __device__ __forceinline__ bool has(const int p, const int n) const { return p < n; }
+    __device__ __forceinline__ int load_row(const int p, const int n) const { return p < n ? p : n - 1; } // (a row to load for any p)
+    __device__ __forceinline__ int row(const int p) const { return p; }                                  // (has(p) holds)
+    __device__ __forceinline__ float thr(const int, const float t) const { return t; }
+};
+struct RowsListed {
+    const int *__restrict__ rows;
+    int count; // >= 1
+    __device__ __forceinline__ bool has(const int p, const int) const { return p < count; }
+    __device__ __forceinline__ int load_row(const int p, const int) const
+    {
+        const int pc = p < count ? p : count - 1;
+        return rows ? rows[pc] : pc;
+    }
+    __device__ __forceinline__ int row(const int p) const { return rows ? rows[p] : p; }
+    __device__ __forceinline__ float thr(const int p, const float t) const { return p < count ? t : __builtin_nanf(""); }
+};
+
 // A operands.  Each lane builds the 16-slot bf16 row of ONE query (lane-per-query: coalesced fp64
 // loads, pieces computed once), rows go through `rows` (64 rows x 32 B of LDS private to the
 // wave), and every lane picks up its fragment: row l&31 of the tile, slots 8*(l>>5) .. +7.
@@ -523,8 +547,8 @@ struct KnnLists {
 // the sorted target) instead of the rows of an N x 3 array.
 // `q0b` >= 0 (QT == 2): the wave's second 32-row tile starts at row q0b instead of q0 + 32 (the culled engine hands a
 // wave any two tiles of a split's list, nn_culled.h).
-template <int QT, bool QSOA>
-__device__ __forceinline__ void coarse_build_a(uint4 *rows, const int lane, const int q0,
+template <int QT, bool QSOA, typename ROWS>
+__device__ __forceinline__ void coarse_build_a(const ROWS &map, uint4 *rows, const int lane, const int q0,
                                                const double *__restrict__ qry, const int n, const size_t qstride,
                                                const double c0, const double c1, const double c2,
                                                bf16x8 (&afrag)[QT], float (&pn)[(QT + 1) / 2], float (&p2)[(QT + 1) / 2],
@@ -535,7 +559,7 @@ __device__ __forceinline__ void coarse_build_a(uint4 *rows, const int lane, cons
     for (int gq = 0; gq < (QT + 1) / 2; ++gq) {
         const int ql = QT == 1 ? (lane & 31) : lane; // QT = 1: lanes 32.. repeat the rows of lanes 0..31
         const int ir = (QT == 2 && q0b >= 0 && lane >= 32) ? q0b + (lane - 32) : q0 + gq * 64 + ql;
-        const int iq = ir < n ? ir : n - 1;
+        const int iq = map.load_row(ir, n);
         const float px = (float)((QSOA ? qry[iq] : qry[3 * iq]) - c0),
                     py = (float)((QSOA ? qry[qstride + iq] : qry[3 * iq + 1]) - c1),
                     pz = (float)((QSOA ? qry[2 * qstride + iq] : qry[3 * iq + 2]) - c2);
@@ -600,8 +624,8 @@ __device__ __forceinline__ void coarse_tiles(const uint4 *tiles, const int lane,
 // Epilogue.  Transpose through `sc` (32 x 36 floats of LDS private to the wave; row stride 36:
 // conflict-free ds_read_b128), one 32-query tile at a time: lane l then owns query l&31 and
 // columns 16*(l>>5).. +15; + |P|^2, per-lane top-2, the two halves merge with one cross-lane step.
-template <int MODE, int QT>
-__device__ __forceinline__ void coarse_epilogue(float *sc, const int lane, const int q0, const int s, const int nsplits,
+template <int MODE, int QT, typename ROWS>
+__device__ __forceinline__ void coarse_epilogue(const ROWS &map, float *sc, const int lane, const int q0, const int s, const int nsplits,
                                                 const int n, const f32x16 (&m)[QT], const float (&pn)[(QT + 1) / 2],
                                                 float2 *__restrict__ coarse, float *__restrict__ slotmin,
                                                 const KnnLists &kl, const float (&thr)[(QT + 1) / 2], const int q0b = -1)
@@ -634,7 +658,8 @@ __device__ __forceinline__ void coarse_epilogue(float *sc, const int lane, const
             }
         }
         __builtin_amdgcn_wave_barrier();
-        const int iq = (QT == 2 && q0b >= 0 && t == 1) ? q0b + ql : q0 + t * 32 + ql;
+        const int ip = (QT == 2 && q0b >= 0 && t == 1) ? q0b + ql : q0 + t * 32 + ql; // the position; its row: map.row(ip)
+        static_assert(MODE == 2 || std::is_same<ROWS, RowsDirect>::value, "only the list epilogue maps positions to rows");
         if (MODE == 2) {
             // Nearly every (row, split) pair has nothing under the row's bound: one minimum over the lane's 16
             // columns, one compare, one ballot.  (+Inf / NaN of a far-away or NaN row become kBig like in MODE 1;
@@ -643,9 +668,10 @@ __device__ __forceinline__ void coarse_epilogue(float *sc, const int lane, const
 #pragma unroll
             for (int c = 3; c < 15; c += 2) mn = min3f(mn, v[c], v[c + 1]);
             mn = min_raw(mn, v[15]);
-            const bool pass = iq < n && min_raw(mn + pnq, kBig) <= thr_q;
+            const bool pass = map.has(ip, n) && min_raw(mn + pnq, kBig) <= thr_q;
             if (__ballot(pass) != 0ull) {
                 if (pass) {
+                    const int iq = map.row(ip);
                     unsigned mask = 0u;
 #pragma unroll
                     for (int c = 0; c < 16; ++c) mask |= min_raw(v[c] + pnq, kBig) <= thr_q ? (1u << c) : 0u;
@@ -654,6 +680,7 @@ __device__ __forceinline__ void coarse_epilogue(float *sc, const int lane, const
                 }
             }
         } else if (MODE == 1) {
+            const int iq = ip;
             if (iq < n) {
                 // stored as bf16 ROUNDED DOWN (the upper half of the fp32 word of a non-negative value):
                 // half the bytes of the one buffer that grows with rows x slots; a stored minimum never
@@ -692,6 +719,7 @@ __device__ __forceinline__ void coarse_epilogue(float *sc, const int lane, const
             const float hi = __builtin_fmaxf(v1, o1);
             v1 = __builtin_fminf(v1, o1);
             v2 = min3f(hi, v2, o2);
+            const int iq = ip;
             if (half == 0 && iq < n) {
                 float *plane = reinterpret_cast<float *>(coarse);
                 plane[(size_t)s * n + iq] = v1;
@@ -706,7 +734,7 @@ __device__ __forceinline__ void coarse_epilogue(float *sc, const int lane, const
 // staged through one 32 KiB LDS buffer in two chunks.
 // `q0`: the wave's first row; `active` (wave-uniform): a wave without rows of its own (the culled engine's last chunk
 // of a split's list, nn_culled.h) still stages operands and meets the barriers, and does nothing else.
-template <int MODE, int QT, int WAVES, bool QSOA = false>
+template <int MODE, int QT, int WAVES, bool QSOA = false, typename ROWS = RowsDirect>
 __device__ __forceinline__ void coarse_unit_rows(uint4 *lds, const int q0, const bool active, const int s, const int nsplits,
                                                  const double *__restrict__ qry, const int n, const size_t qstride,
                                                  const uint4 *__restrict__ Bpack,
@@ -714,7 +742,8 @@ __device__ __forceinline__ void coarse_unit_rows(uint4 *lds, const int q0, const
                                                  float2 *__restrict__ coarse, float *__restrict__ slotmin,
                                                  const KnnLists kl = KnnLists{nullptr, nullptr, nullptr, nullptr, 0},
                                                  const int q0b = -1 /* >= 0: the wave's second tile starts there (coarse_build_a) */,
-                                                 const bool early_stage = true /* the first chunk of operands requested before the rows */)
+                                                 const bool early_stage = true /* the first chunk of operands requested before the rows */,
+                                                 const ROWS map = ROWS{})
 {
     constexpr int THREADS = 64 * WAVES;
     constexpr int CHUNK16 = kChunkTiles * 64;  // uint4 per staged chunk (32 KiB)
@@ -738,7 +767,7 @@ __device__ __forceinline__ void coarse_unit_rows(uint4 *lds, const int q0, const
 
     bf16x8 afrag[QT];
     float pn[(QT + 1) / 2] = {}, p2[(QT + 1) / 2] = {}, thr[(QT + 1) / 2];
-    if (active) coarse_build_a<QT, QSOA>(lds + wave * (64 * 2), lane, q0, qry, n, qstride, c0, c1, c2, afrag, pn, p2, q0b);
+    if (active) coarse_build_a<QT, QSOA>(map, lds + wave * (64 * 2), lane, q0, qry, n, qstride, c0, c1, c2, afrag, pn, p2, q0b);
 #pragma unroll
     for (int gq = 0; gq < (QT + 1) / 2; ++gq) {
         thr[gq] = 0.f;
@@ -749,11 +778,11 @@ __device__ __forceinline__ void coarse_unit_rows(uint4 *lds, const int q0, const
             // gives a NaN threshold, under which nothing is; an infinite one (no previous match) lists everything.
             const int ql = QT == 1 ? (lane & 31) : lane;
             const int ir = (QT == 2 && q0b >= 0 && lane >= 32) ? q0b + (lane - 32) : q0 + gq * 64 + ql;
-            const int iq = ir < n ? ir : n - 1;
+            const int iq = map.load_row(ir, n);
             const float ubf = kl.thr[iq], sqf = kl.sq[iq];
             const float a = (__builtin_amdgcn_sqrtf(p2[gq]) + (float)frames[s].rho) * 1.0001f;
             const float eps = 1.5260e-05f * a;
-            thr[gq] = ((ubf + eps * (2.f * sqf + eps)) + (float)(kArithBound * 5.9604644775390625e-08) * (a * a)) * 1.00002f;
+            thr[gq] = map.thr(ir, ((ubf + eps * (2.f * sqf + eps)) + (float)(kArithBound * 5.9604644775390625e-08) * (a * a)) * 1.00002f);
         }
     }
     f32x16 m[QT];
@@ -778,21 +807,22 @@ __device__ __forceinline__ void coarse_unit_rows(uint4 *lds, const int q0, const
 
     __syncthreads(); // every wave is done with the B operands
     if (active)
-        coarse_epilogue<MODE, QT>(reinterpret_cast<float *>(lds) + wave * (32 * 36), lane, q0, s, nsplits, n, m, pn, coarse,
+        coarse_epilogue<MODE, QT>(map, reinterpret_cast<float *>(lds) + wave * (32 * 36), lane, q0, s, nsplits, n, m, pn, coarse,
                                   slotmin, kl, thr, q0b);
 }
 
 // One (query block, split) unit: wave w of block bx takes rows (bx * WAVES + w) * 32 QT ...
-template <int MODE, int QT, int WAVES, bool QSOA = false>
+template <int MODE, int QT, int WAVES, bool QSOA = false, typename ROWS = RowsDirect>
 __device__ __forceinline__ void coarse_unit(uint4 *lds, const int bx, const int s, const int nsplits,
                                             const double *__restrict__ qry, const int n, const size_t qstride,
                                             const uint4 *__restrict__ Bpack,
                                             const SplitFrame *__restrict__ frames,
                                             float2 *__restrict__ coarse, float *__restrict__ slotmin,
-                                            const KnnLists kl = KnnLists{nullptr, nullptr, nullptr, nullptr, 0})
+                                            const KnnLists kl = KnnLists{nullptr, nullptr, nullptr, nullptr, 0},
+                                            const ROWS map = ROWS{})
 {
-    coarse_unit_rows<MODE, QT, WAVES, QSOA>(lds, (bx * WAVES + (int)(threadIdx.x >> 6)) * (kTile * QT), true, s, nsplits, qry, n, qstride,
-                                            Bpack, frames, coarse, slotmin, kl);
+    coarse_unit_rows<MODE, QT, WAVES, QSOA, ROWS>(lds, (bx * WAVES + (int)(threadIdx.x >> 6)) * (kTile * QT), true, s, nsplits, qry, n,
+                                                  qstride, Bpack, frames, coarse, slotmin, kl, -1, true, map);
 }
 
 template <int WAVES>
@@ -826,30 +856,24 @@ __global__ __launch_bounds__(64 * WAVES) void k_nn_coarse_rows(
 }
 
 // all pairs, the moved source rows of an ICP pass that come with a bound (nn_bounded.h), MODE 2.
-// `epoch_w` (list reuse, RowBounds in kernels.h; null: every block runs): a workgroup whose rows' epoch words do not hold
-// this pass's `epoch` has no row to list -- every one of them keeps its list -- and leaves at once.  `blocks_run`
-// (profiling, or null): the blocks of rows that did run, counted by their split-0 workgroup.
+// `list` (list reuse, RowBounds in kernels.h; null: every row of the launch is listed -- a call's first pass, nearest_batch,
+// normal estimation): the packed list of the rows listed again, as k_row_list left it.  The grid is sized for n rows, since
+// the host never learns the count: workgroup bx takes the list's positions from bx x (its rows) on and leaves at once
+// where the list ends before them.  Where the list says that it holds every row, the rows are indexed directly, as
+// without one.  `blocks_run` (profiling, or null): the workgroup columns that did run, counted by their split-0 workgroup.
 template <int QT, int WAVES>
 __global__ __launch_bounds__(64 * WAVES) void k_nn_coarse_bounded(
     const double *__restrict__ qry, int n, const uint4 *__restrict__ Bpack,
     const SplitFrame *__restrict__ frames, KnnLists kl, const IcpState *__restrict__ st,
-    const unsigned *__restrict__ epoch_w = nullptr, unsigned epoch = 0, unsigned *__restrict__ blocks_run = nullptr)
+    const int *__restrict__ list = nullptr, unsigned *__restrict__ blocks_run = nullptr)
 {
     if (st && st->done) return;
-    if (epoch_w) {
-        constexpr int kWords = kTile * QT * WAVES / kReuseRows;
-        static_assert(kWords * kReuseRows == kTile * QT * WAVES, "an epoch word covers whole workgroups' rows");
-        bool any = false;
-#pragma unroll
-        for (int w = 0; w < kWords; ++w) {
-            const int e = blockIdx.x * kWords + w;
-            any |= e * kReuseRows < n && epoch_w[e] == epoch;
-        }
-        if (!any) return;
-    }
+    RowsListed map{nullptr, n};
+    if (list && !list[1]) map = RowsListed{list + kRowListHead, list[0]};
+    if (blockIdx.x * (kTile * QT * WAVES) >= map.count) return;
     if (blocks_run && blockIdx.y == 0 && threadIdx.x == 0) atomicAdd(blocks_run, 1u);
     __shared__ uint4 lds[CoarseLds<WAVES>::SCRATCH16];
-    coarse_unit<2, QT, WAVES>(lds, blockIdx.x, blockIdx.y, gridDim.y, qry, n, 0, Bpack, frames, nullptr, nullptr, kl);
+    coarse_unit<2, QT, WAVES, false, RowsListed>(lds, blockIdx.x, blockIdx.y, gridDim.y, qry, n, 0, Bpack, frames, nullptr, nullptr, kl, map);
 }
 
 // (Measured and not kept, scripts/micro/README.md: a RESIDENT form -- one 16-wave workgroup per CU stages a
