@@ -489,6 +489,47 @@ int icpmi_map_world(icpmi_map *map, const double *poses, int64_t n_poses, int64_
 int icpmi_map_finish(icpmi_map *map, const double *poses, int64_t n_poses, const icpmi_grid_config *grid,
                      double voxel_size, double *map_out, int64_t map_cap, int64_t *n_map, int64_t *n_cells);
 
+/* The kept scans ray-cast into a free / occupied / unknown raster a planner can use.  The reference's
+ * cells_to_occupancy_grid_msg (slam_node.cpp:279-297) writes 100 for a hit cell and 0 everywhere else, so it
+ * publishes space the LiDAR never saw as free; here that space is unknown.  With the frames, poses and grid of
+ * icpmi_map_finish (frames i < min(frames, n_poses), the first and too-few-points ones included):
+ *   hits      a row of frame i marks the cell icpmi_map_finish(grid) inserts for it, under the same tests (height
+ *             band, 0.5 <= r <= max_range from the frame's translation, a representable quotient).  A row that marks
+ *             nothing casts no ray.  The occupied cells are exactly icpmi_map_finish's cell set.
+ *   rays      from the frame's sensor cell (floor(t.x / resolution), floor(t.y / resolution)) to each hit cell, the
+ *             all-integer Bresenham line in that direction (dx = |x1 - x0|, dy = |y1 - y0|, err = dx - dy; while not at
+ *             the hit: carve, e2 = 2 err, if e2 > -dy: err -= dy, x += sx; if e2 < dx: err += dx, y += sy).  The sensor
+ *             cell is carved, the hit cell is not; a hit in the sensor's own cell carves nothing.
+ *   state     100 a cell in the occupied set, whatever passes through it; 0 a cell carved by any ray of any frame and
+ *             not occupied; -1 every other cell.  Unions of sets: no dependence on the order of frames or rows.
+ *   raster    nav_msgs/OccupancyGrid's layout: min_x, min_y are the least x and y over the occupied and free cells
+ *             less 5 cells, width and height reach 5 cells past the greatest, and cell (x, y) is
+ *             data[(y - min_y) * width + (x - min_x)].  No occupied and no free cell: 0 x 0.
+ * Limits, each refused with ICPMI_ERR_ARG before any device work, nothing changed: resolution not finite or not
+ * positive; R = ceil(max_range / resolution) > ICPMI_RAYCAST_MAX_R (a max_range that is not finite included); a used
+ * pose with a non-finite entry; a used frame whose sensor cell is more than 2^31 - 2 - R - 6 in magnitude on an axis;
+ * width * height > 2^31 - 1, judged before the rays are cast by the raster's bound (W + 10) * (H + 10), W and H being
+ * the spans of the sensor cells of the used frames that hold rows, widened by R + 1 cells on every side (every hit
+ * lies within R + 1 cells of its sensor cell).  NULL poses with n_poses > 0, or a NULL grid, is ICPMI_ERR_NULL.
+ * Rays are walked in a per-frame window in on-chip memory up to R = ICPMI_RAYCAST_LDS_MAX_R and straight in device
+ * memory beyond; the results are the same.
+ *   icpmi_map_raycast   builds the raster and keeps it on the device, in a buffer the handle owns; info may be NULL.
+ *                       A failed call leaves the previous raster in place.  The context's cell set is not touched.
+ *                       Waits for the device twice (the raster's size, the raster); once when no cell is marked.
+ *   icpmi_map_raster    sets *info (may be NULL) to the last successful raycast's, all zeros before the first, and, if
+ *                       data is not NULL, copies its width * height bytes out (cap bytes; fewer is
+ *                       ICPMI_ERR_CAPACITY).  One wait. */
+#define ICPMI_RAYCAST_MAX_R 4096
+#define ICPMI_RAYCAST_LDS_MAX_R 559
+typedef struct {
+    int32_t min_x, min_y, width, height;
+    double resolution;
+    int64_t n_occupied, n_free;
+} icpmi_raster_info;
+int icpmi_map_raycast(icpmi_map *map, const double *poses, int64_t n_poses, const icpmi_grid_config *grid,
+                      icpmi_raster_info *info);
+int icpmi_map_raster(icpmi_map *map, int8_t *data, int64_t cap, icpmi_raster_info *info);
+
 /* Loop-closure detection over a global map's kept scans (slam::LoopClosureDetector, core/loop_closure.hpp:41-148),
  * with its database on the device: an entry is a store frame with a label (the node's frame_idx).  Each entry's
  * Scan Context descriptor lives in device memory; its rows stay in the store and are never copied to the host.

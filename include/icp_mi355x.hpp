@@ -789,6 +789,14 @@ private:
     icpmi_pose_graph *g_ = nullptr;
 };
 
+// What GlobalMap::raycast returns (icpmi_map_raster): nav_msgs/OccupancyGrid's layout, cell (x, y) at
+// data[(y - min_y) * width + (x - min_x)]: 100 occupied, 0 free, -1 unknown.
+struct OccupancyRaster {
+    int32_t min_x = 0, min_y = 0, width = 0, height = 0;
+    double resolution = 0.0;
+    std::vector<int8_t> data;
+};
+
 // The node's kept scans (downsampled_clouds_, slam_node.cpp:71,123) in device memory, and what it builds from them
 // with the optimised poses: rebuild_recent_clouds (:187-194), build_final_global_map (:196-209) with
 // rebuild_occupancy_grid (:223-229), and the map publish_global_map sends once complete (:235-238).  finish() rebuilds
@@ -858,6 +866,22 @@ public:
                                static_cast<int64_t>(rows), &n, nullptr));
         out.resize(3 * static_cast<std::size_t>(n));
         return PointCloud(std::move(out));
+    }
+    // The kept scans ray-cast into a free / occupied / unknown raster (icpmi_map_raycast), where the reference's
+    // cells_to_occupancy_grid_msg (:279-297) publishes everything but the hit cells as free.  The context's cell set
+    // is not touched.
+    OccupancyRaster raycast(const std::vector<Transformation> &poses, const OccupancyGridConfig &grid)
+    {
+        const std::vector<double> P = flatten(poses);
+        const icpmi_grid_config g = detail::to_c(grid);
+        icpmi_raster_info info;
+        check(icpmi_map_raycast(m_, P.data(), static_cast<int64_t>(poses.size()), &g, &info));
+        OccupancyRaster out;
+        out.min_x = info.min_x, out.min_y = info.min_y, out.width = info.width, out.height = info.height;
+        out.resolution = info.resolution;
+        out.data.resize(static_cast<std::size_t>(info.width) * static_cast<std::size_t>(info.height));
+        if (!out.data.empty()) check(icpmi_map_raster(m_, out.data.data(), static_cast<int64_t>(out.data.size()), nullptr));
+        return out;
     }
     icpmi_map *get() const { return m_; }
     Context *context() const { return ctx_; }

@@ -34,6 +34,7 @@ EXPORTS = [
     "icpmi_pose_graph_optimize", "icpmi_pose_graph_pose", "icpmi_pose_graph_poses", "icpmi_pose_graph_size",
     "icpmi_map_create", "icpmi_map_destroy", "icpmi_map_add_frame", "icpmi_map_add_frame_device",
     "icpmi_map_add_stream_frame", "icpmi_map_size", "icpmi_map_world", "icpmi_map_finish",
+    "icpmi_map_raycast", "icpmi_map_raster",
     "icpmi_loop_config_default", "icpmi_loop_create", "icpmi_loop_destroy", "icpmi_loop_add_frame", "icpmi_loop_detect",
     "icpmi_loop_descriptor", "icpmi_loop_size", "icpmi_loop_clear",
 ]
@@ -103,6 +104,15 @@ STREAM_REGISTERED, STREAM_FIRST_FRAME, STREAM_TOO_FEW_POINTS = 0, 1, 2
 class GridConfig(C.Structure):
     """OccupancyGridConfig (slam_node.hpp:35-40)"""
     _fields_ = [("resolution", C.c_double), ("height_min", C.c_double), ("height_max", C.c_double), ("max_range", C.c_double)]
+
+
+RAYCAST_MAX_R, RAYCAST_LDS_MAX_R = 4096, 559   # ICPMI_RAYCAST_MAX_R, ICPMI_RAYCAST_LDS_MAX_R
+
+
+class RasterInfo(C.Structure):
+    """icpmi_raster_info"""
+    _fields_ = [("min_x", C.c_int32), ("min_y", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("resolution", C.c_double), ("n_occupied", C.c_int64), ("n_free", C.c_int64)]
 
 
 class PoseGraphConfig(C.Structure):
@@ -265,6 +275,8 @@ def load_library(path=None):
     L.icpmi_map_size.argtypes = [vp, i64p, i64p]
     L.icpmi_map_world.argtypes = [vp, dp, C.c_int64, C.c_int64, dp, C.c_int64, i64p]
     L.icpmi_map_finish.argtypes = [vp, dp, C.c_int64, C.POINTER(GridConfig), C.c_double, dp, C.c_int64, i64p, i64p]
+    L.icpmi_map_raycast.argtypes = [vp, dp, C.c_int64, C.POINTER(GridConfig), C.POINTER(RasterInfo)]
+    L.icpmi_map_raster.argtypes = [vp, C.POINTER(C.c_int8), C.c_int64, C.POINTER(RasterInfo)]
     L.icpmi_loop_config_default.argtypes = [C.POINTER(LoopConfig)]
     L.icpmi_loop_config_default.restype = None
     L.icpmi_loop_create.argtypes = [vp, C.POINTER(LoopConfig), C.POINTER(vp)]

@@ -41,6 +41,7 @@
 #include "scan_context.h"
 #include "occupancy.h"
 #include "global_map.h"
+#include "raycast.h"
 #include "loop_store.h"
 #include "pose_graph.h"
 
@@ -3800,6 +3801,9 @@ struct icpmi_map {
     std::vector<int64_t> tile0{0};       // per frame its first tile; tile0[frames] = tiles
     std::vector<MapTile> tiles;
     size_t uploaded_tiles = 0;           // tiles already in d_tiles
+    DevBuf d_ray_frames, d_ray_planes;   // icpmi_map_raycast: the frame table; the carved and occupied planes, RayBounds
+    DevBuf d_raster, d_raster_next;      // the last successful raster; the one a call is building
+    icpmi_raster_info raster{};          // the last successful raster's (all zeros before the first)
 };
 
 namespace {
@@ -3912,7 +3916,9 @@ void icpmi_map_destroy(icpmi_map *m)
     if (!m) return;
     (void)hipSetDevice(m->ctx->opt.device);
     (void)hipStreamSynchronize(m->ctx->stream);
-    for (DevBuf *b : {&m->d_rows, &m->d_tiles, &m->d_poses, &m->d_world}) release(*b);
+    for (DevBuf *b : {&m->d_rows, &m->d_tiles, &m->d_poses, &m->d_world, &m->d_ray_frames, &m->d_ray_planes, &m->d_raster,
+                      &m->d_raster_next})
+        release(*b);
     delete m;
 }
 
@@ -4040,6 +4046,115 @@ int icpmi_map_finish(icpmi_map *m, const double *poses, int64_t n_poses, const i
     }
     if (n_map) *n_map = rows;
     if (n_cells) *n_cells = ctx->grid_n;
+    return ICPMI_OK;
+}
+
+static_assert(kRayMaxR == ICPMI_RAYCAST_MAX_R && kRayLdsMaxR == ICPMI_RAYCAST_LDS_MAX_R, "the header states these limits");
+
+int icpmi_map_raycast(icpmi_map *m, const double *poses, int64_t n_poses, const icpmi_grid_config *grid, icpmi_raster_info *info)
+{
+    if (!m) return ICPMI_ERR_NULL;
+    icpmi_ctx *ctx = m->ctx;
+    int rc;
+    if ((rc = check_common(ctx))) return rc;
+    if (!grid) return fail(ctx, ICPMI_ERR_NULL, "grid is NULL");
+    const double res = grid->resolution;
+    if (!(std::isfinite(res) && res > 0.0)) return fail(ctx, ICPMI_ERR_ARG, "grid resolution must be finite and positive");
+    const double Rd = std::ceil(grid->max_range / res);
+    if (!(Rd <= (double)kRayMaxR))
+        return fail(ctx, ICPMI_ERR_ARG, "max_range / resolution must be at most %d cells", kRayMaxR);
+    const int R = Rd > 0.0 ? (int)Rd : 0;
+    int64_t last = 0;
+    if ((rc = map_check_poses(m, poses, n_poses, &last))) return rc;
+    // the sensor cells, and with them the plane: every carved or occupied cell lies within R + 1 cells of one
+    const double cell_max = 2147483646.0 - R - 6;
+    std::vector<RayFrame> frames((size_t)last);
+    int64_t lo_x = INT64_MAX, lo_y = INT64_MAX, hi_x = INT64_MIN, hi_y = INT64_MIN;
+    for (int64_t i = 0; i < last; ++i) {
+        const double cx = std::floor(poses[16 * i + 3] / res), cy = std::floor(poses[16 * i + 7] / res);
+        if (!(std::fabs(cx) <= cell_max && std::fabs(cy) <= cell_max))
+            return fail(ctx, ICPMI_ERR_ARG, "frame %lld's sensor cell is out of range", (long long)i);
+        const int64_t rows = m->row0[i + 1] - m->row0[i];
+        frames[(size_t)i] = RayFrame{m->row0[i], (int32_t)rows, (int32_t)cx, (int32_t)cy, 0};
+        if (rows == 0) continue;
+        lo_x = std::min<int64_t>(lo_x, (int64_t)cx), hi_x = std::max<int64_t>(hi_x, (int64_t)cx);
+        lo_y = std::min<int64_t>(lo_y, (int64_t)cy), hi_y = std::max<int64_t>(hi_y, (int64_t)cy);
+    }
+    icpmi_raster_info out{0, 0, 0, 0, res, 0, 0};
+    const int64_t n64 = m->row0[last];
+    if (n64 > 0) {
+        const int64_t W = hi_x - lo_x + 2 * R + 3, H = hi_y - lo_y + 2 * R + 3;
+        if ((W + 10) > (int64_t)INT32_MAX / (H + 10)) // the raster is the tight box widened by 5: never more than this
+            return fail(ctx, ICPMI_ERR_ARG, "the used frames span %lld x %lld cells: more than 2^31 - 1", (long long)(W + 10),
+                        (long long)(H + 10));
+        Range range("icpmi:map_raycast");
+        hipStream_t s = ctx->stream;
+        const RayPlane pl{(int32_t)(lo_x - R - 1), (int32_t)(lo_y - R - 1), (int32_t)W, (int32_t)H, (int32_t)((W + 31) / 32)};
+        const size_t words = (size_t)pl.wpr * (size_t)H;
+        if ((rc = reserve(ctx, ctx->grid_in, sizeof(unsigned long long) * (size_t)n64))) return rc;
+        if ((rc = reserve(ctx, m->d_ray_frames, sizeof(RayFrame) * (size_t)last))) return rc;
+        if ((rc = reserve(ctx, m->d_ray_planes, sizeof(unsigned) * 2 * words + sizeof(RayBounds)))) return rc;
+        unsigned long long *keys = (unsigned long long *)ctx->grid_in.p;
+        unsigned *carved = (unsigned *)m->d_ray_planes.p, *occupied = carved + words;
+        RayBounds *bounds_d = (RayBounds *)(occupied + words); // (2 * words * 4 bytes: a multiple of 8)
+        const RayFrame *frames_d = (const RayFrame *)m->d_ray_frames.p;
+        static const RayBounds kNone{INT32_MAX, INT32_MAX, -1, -1, 0, 0};
+        HIP_TRY(ctx, hipMemsetAsync(carved, 0, sizeof(unsigned) * 2 * words, s));
+        HIP_TRY(ctx, hipMemcpyAsync(bounds_d, &kNone, sizeof(RayBounds), hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipMemcpyAsync(m->d_ray_frames.p, frames.data(), sizeof(RayFrame) * (size_t)last, hipMemcpyHostToDevice, s));
+        if ((rc = map_queue_world(m, poses, 0, last, nullptr, keys, grid))) return rc;
+        if (R <= kRayLdsMaxR) {
+            const size_t window = sizeof(unsigned) * (size_t)ray_window_words(R);
+            if (window > 64 * 1024) // (R > 351) dynamic LDS past 64 KiB has to be allowed first
+                HIP_TRY(ctx, hipFuncSetAttribute((const void *)k_ray_carve_lds, hipFuncAttributeMaxDynamicSharedMemorySize, kRayLdsBytes));
+            hipLaunchKernelGGL(k_ray_carve_lds, dim3((unsigned)last), dim3(kRayThreads), window, s,
+                               (const unsigned long long *)keys, frames_d, R, pl, carved, occupied);
+        } else
+            hipLaunchKernelGGL(k_ray_carve_global, dim3((unsigned)m->tile0[last]), dim3(256), 0, s, (const unsigned long long *)keys,
+                               (const MapTile *)m->d_tiles.p, frames_d, R, pl, carved, occupied);
+        HIP_TRY(ctx, hipGetLastError());
+        const unsigned blocks = (unsigned)std::min<size_t>((words + 255) / 256, 1024);
+        hipLaunchKernelGGL(k_ray_bounds, dim3(blocks), dim3(256), 0, s, (const unsigned *)carved, (const unsigned *)occupied, pl,
+                           bounds_d);
+        HIP_TRY(ctx, hipGetLastError());
+        RayBounds b{};
+        HIP_TRY(ctx, hipMemcpyAsync(&b, bounds_d, sizeof(RayBounds), hipMemcpyDeviceToHost, s));
+        HIP_TRY(ctx, hipStreamSynchronize(s)); // the first wait: the raster's size
+        if (b.max_x >= 0) {
+            out.min_x = pl.x0 + b.min_x - 5;
+            out.min_y = pl.y0 + b.min_y - 5;
+            out.width = b.max_x - b.min_x + 11;
+            out.height = b.max_y - b.min_y + 11;
+            out.n_occupied = (int64_t)b.n_occupied;
+            out.n_free = (int64_t)b.n_free;
+            const size_t cells = (size_t)out.width * (size_t)out.height;
+            if ((rc = reserve(ctx, m->d_raster_next, cells))) return rc;
+            hipLaunchKernelGGL(k_ray_raster, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, (const unsigned *)carved,
+                               (const unsigned *)occupied, pl, b.min_x - 5, b.min_y - 5, out.width, out.height,
+                               (int8_t *)m->d_raster_next.p);
+            HIP_TRY(ctx, hipGetLastError());
+            HIP_TRY(ctx, hipStreamSynchronize(s)); // the second: the raster is complete before it replaces the last one
+            std::swap(m->d_raster, m->d_raster_next);
+        }
+    }
+    m->raster = out;
+    if (info) *info = out;
+    return ICPMI_OK;
+}
+
+int icpmi_map_raster(icpmi_map *m, int8_t *data, int64_t cap, icpmi_raster_info *info)
+{
+    if (!m) return ICPMI_ERR_NULL;
+    icpmi_ctx *ctx = m->ctx;
+    int rc;
+    if ((rc = check_common(ctx))) return rc;
+    if (info) *info = m->raster;
+    if (!data) return ICPMI_OK;
+    const int64_t cells = (int64_t)m->raster.width * (int64_t)m->raster.height;
+    if (cap < cells) return fail(ctx, ICPMI_ERR_CAPACITY, "data holds %lld cells, needs %lld", (long long)cap, (long long)cells);
+    if (cells == 0) return ICPMI_OK;
+    HIP_TRY(ctx, hipMemcpyAsync(data, m->d_raster.p, (size_t)cells, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); // the call's one wait
     return ICPMI_OK;
 }
 

@@ -18,6 +18,16 @@ def _poses(poses):
     return P, (capi._dp(P) if P.shape[0] else None)
 
 
+class OccupancyRaster:
+    """icpmi_map_raster's result: the info fields, and data[y - min_y, x - min_x] as (height, width) int8:
+    100 occupied, 0 free, -1 unknown"""
+
+    def __init__(self, info, data):
+        self.min_x, self.min_y, self.width, self.height = info.min_x, info.min_y, info.width, info.height
+        self.resolution, self.n_occupied, self.n_free = info.resolution, info.n_occupied, info.n_free
+        self.data = data
+
+
 class GlobalMap:
     def __init__(self, ctx):
         self._lib = capi.load_library()
@@ -93,3 +103,22 @@ class GlobalMap:
         self.ctx._check(self._lib.icpmi_map_finish(self._h, pp, P.shape[0], C.byref(g), float(voxel), capi._dp(out),
                                                    rows, C.byref(nm), C.byref(nc)))
         return self.ctx.occupancy_cells(), out[:nm.value].copy()
+
+    def raster(self):
+        """the last successful raycast's raster (0 x 0 before the first)"""
+        info = capi.RasterInfo()
+        self.ctx._check(self._lib.icpmi_map_raster(self._h, None, 0, C.byref(info)))
+        data = np.empty((info.height, info.width), dtype=np.int8)
+        if data.size:
+            self.ctx._check(self._lib.icpmi_map_raster(self._h, data.ctypes.data_as(C.POINTER(C.c_int8)), data.size,
+                                                       C.byref(info)))
+        return OccupancyRaster(info, data)
+
+    def raycast(self, poses, grid=None):
+        """The kept scans ray-cast into a free / occupied / unknown raster (icpmi_map_raycast): every hit marks its cell
+        occupied and carves the Bresenham line from its frame's sensor cell to it.  grid None: the default
+        OccupancyGridConfig.  The context's cell set is not touched.  Returns an OccupancyRaster."""
+        P, pp = _poses(poses)
+        g = grid if grid is not None else self.ctx.make_grid_config()
+        self.ctx._check(self._lib.icpmi_map_raycast(self._h, pp, P.shape[0], C.byref(g), None))
+        return self.raster()

@@ -11,7 +11,11 @@ that tests/test_gpu_map.py holds the device (icpmi_map, lidar_slam_from_scratch_
 Only frames i < min(F, len(poses)) are used (the reference's i < downsampled_clouds_.size() && i < poses_.size()).
 World points are ((x R_a0 + y R_a1) + z R_a2) + t_a, elementwise in numpy (no fused multiply-add), so they are the
 device's bit for bit.  The cell set is the oracle's occupancy_update per frame, the published map its voxel_downsample.
-The interface is GlobalMap's, so an instance can be handed to slam.run_slam as its global_map."""
+The interface is GlobalMap's, so an instance can be handed to slam.run_slam as its global_map.
+
+MapRef.raycast is the normative text of icpmi_map_raycast (include/icp_mi355x.h, csrc/raycast.h): the kept scans
+ray-cast into a free / occupied / unknown raster.  bresenham() restates the device's ray_walk line for line;
+bresenham_lockstep() is the same walk for many rays at once, one step per numpy operation."""
 import os
 import sys
 
@@ -51,6 +55,87 @@ def cells_array(cell_set):
     return np.array(sorted(cell_set), dtype=np.int32).reshape(-1, 2)
 
 
+RAYCAST_MAX_R = 4096        # ICPMI_RAYCAST_MAX_R
+UNKNOWN, FREE, OCCUPIED = -1, 0, 100
+
+
+class Raster:
+    """what icpmi_map_raster returns: the info fields, and data[y - min_y, x - min_x] as (height, width) int8"""
+
+    def __init__(self, min_x, min_y, width, height, resolution, n_occupied, n_free, data):
+        self.min_x, self.min_y, self.width, self.height = int(min_x), int(min_y), int(width), int(height)
+        self.resolution, self.n_occupied, self.n_free = float(resolution), int(n_occupied), int(n_free)
+        self.data = data
+
+    def cells(self, value):
+        """the (x, y) cells holding `value`, as a set"""
+        y, x = np.nonzero(self.data == value)
+        return set(zip((x + self.min_x).tolist(), (y + self.min_y).tolist()))
+
+
+def bresenham(x0, y0, x1, y1):
+    """ray_walk (csrc/raycast.h): the cells carved on the way from (x0, y0) to (x1, y1): the first, not the last"""
+    out = []
+    dx, dy = abs(x1 - x0), abs(y1 - y0)
+    sx = 1 if x1 > x0 else (-1 if x1 < x0 else 0)
+    sy = 1 if y1 > y0 else (-1 if y1 < y0 else 0)
+    err, x, y = dx - dy, x0, y0
+    while x != x1 or y != y1:
+        out.append((x, y))
+        e2 = 2 * err
+        if e2 > -dy:
+            err -= dy
+            x += sx
+        if e2 < dx:
+            err += dx
+            y += sy
+    return out
+
+
+def bresenham_lockstep(x0, y0, x1, y1):
+    """bresenham() for arrays of rays, all advanced one step per pass: the carved cells of all of them, (n, 2) int64
+    (a cell once per ray that carves it, in no particular order).  Every pass moves a ray one cell along its longer
+    axis, so a ray takes max(dx, dy) passes: with the rays sorted longest first, the live ones are a prefix."""
+    x0, y0, x1, y1 = (np.asarray(a, dtype=np.int64).ravel() for a in np.broadcast_arrays(x0, y0, x1, y1))
+    order = np.argsort(-np.maximum(np.abs(x1 - x0), np.abs(y1 - y0)), kind="stable")
+    x0, y0, x1, y1 = x0[order], y0[order], x1[order], y1[order]
+    dx, dy = np.abs(x1 - x0), np.abs(y1 - y0)
+    sx, sy = np.sign(x1 - x0), np.sign(y1 - y0)
+    err, x, y = dx - dy, x0.copy(), y0.copy()
+    out = []
+    n = int(np.count_nonzero((x != x1) | (y != y1)))
+    while n:
+        out.append(np.stack([x[:n], y[:n]], axis=1))
+        e2 = 2 * err[:n]
+        mx, my = e2 > -dy[:n], e2 < dx[:n]
+        err[:n] += my * dx[:n] - mx * dy[:n]
+        x[:n] += mx * sx[:n]
+        y[:n] += my * sy[:n]
+        n = int(np.count_nonzero((x[:n] != x1[:n]) | (y[:n] != y1[:n])))
+        assert not n or ((x[:n] != x1[:n]) | (y[:n] != y1[:n])).all()      # the live rays are a prefix
+    return np.concatenate(out) if out else np.zeros((0, 2), dtype=np.int64)
+
+
+def hit_cells(world, sensor_xy, resolution, height_min, height_max, max_range):
+    """grid_cell_key (csrc/occupancy.h) on every world row with the sensor at sensor_xy: the (x, y) cells of the
+    rows that mark one, (n, 2) int64 in row order.  The same IEEE operations, elementwise."""
+    w = np.asarray(world, dtype=np.float64).reshape(-1, 3)
+    x, y, z = w[:, 0], w[:, 1], w[:, 2]
+    with np.errstate(all="ignore"):
+        dx, dy = x - sensor_xy[0], y - sensor_xy[1]
+        r = np.sqrt(dx * dx + dy * dy)
+        cx, cy = np.floor(x / resolution), np.floor(y / resolution)
+        ok = ~((z < height_min) | (z > height_max)) & ~((r > max_range) | (r < 0.5))
+        ok &= (np.abs(cx) <= 2147483646.0) & (np.abs(cy) <= 2147483646.0)
+    return np.stack([cx[ok], cy[ok]], axis=1).astype(np.int64)
+
+
+def _unique_cells(cells):
+    """(n, 2) int64 cells (|x|, |y| < 2^31) -> the distinct ones, sorted by x then y"""
+    k = np.unique(cells[:, 0] * 2**32 + (cells[:, 1] + 2**31))     # one word per cell: a 1-D unique is much faster
+    return np.stack([k >> 32, (k & (2**32 - 1)) - 2**31], axis=1)
+
+
 class MapRef:
     def __init__(self):
         self.clouds = []
@@ -88,3 +173,48 @@ class MapRef:
         g = self.world(poses)
         published = orc.voxel_downsample(g, voxel) if voxel > 0 and g.shape[0] else np.zeros((0, 3))
         return cells, published
+
+    def raycast(self, poses, grid=None):
+        """icpmi_map_raycast: every used frame's hits mark their cells occupied and carve the Bresenham line from the
+        frame's sensor cell; 100 occupied, 0 carved and not occupied, -1 neither; bounds widened by 5 cells.  The limits
+        the library refuses with ICPMI_ERR_ARG raise ValueError here."""
+        g = grid_kwargs(grid)
+        res = g["resolution"]
+        if not (np.isfinite(res) and res > 0.0):
+            raise ValueError("grid resolution must be finite and positive")
+        with np.errstate(all="ignore"):
+            Rd = np.ceil(np.float64(g["max_range"]) / res)
+        if not Rd <= RAYCAST_MAX_R:
+            raise ValueError("max_range / resolution must be at most %d cells" % RAYCAST_MAX_R)
+        R = int(Rd) if Rd > 0 else 0
+        last = min(len(self.clouds), len(poses))
+        P = [np.asarray(poses[i], dtype=np.float64).reshape(4, 4) for i in range(last)]
+        if not all(np.isfinite(T).all() for T in P):
+            raise ValueError("a used pose has a non-finite entry")
+        sensors = [(np.floor(T[0, 3] / res), np.floor(T[1, 3] / res)) for T in P]
+        if any(abs(c) > 2147483646.0 - R - 6 for s in sensors for c in s):
+            raise ValueError("a used frame's sensor cell is out of range")
+        held = np.array([s for i, s in enumerate(sensors) if self.clouds[i].shape[0]], dtype=np.int64).reshape(-1, 2)
+        if len(held):
+            W, H = (int(v) + 2 * R + 3 for v in held.max(axis=0) - held.min(axis=0))
+            if (W + 10) * (H + 10) > 2**31 - 1:
+                raise ValueError("the used frames span more than 2^31 - 1 cells")
+        occupied, carved = [], []
+        for i in range(last):
+            with np.errstate(all="ignore"):                             # non-finite rows mark nothing
+                world = world_points(self.clouds[i], P[i])
+            hits = _unique_cells(hit_cells(world, P[i][:2, 3], res, g["height_min"], g["height_max"], g["max_range"]))
+            occupied.append(hits)
+            s = sensors[i]
+            carved.append(_unique_cells(bresenham_lockstep(int(s[0]), int(s[1]), hits[:, 0], hits[:, 1])))
+        occupied = _unique_cells(np.concatenate(occupied)) if occupied else np.zeros((0, 2), dtype=np.int64)
+        carved = _unique_cells(np.concatenate(carved)) if carved else np.zeros((0, 2), dtype=np.int64)
+        both = np.concatenate([occupied, carved])
+        if not len(both):
+            return Raster(0, 0, 0, 0, res, 0, 0, np.zeros((0, 0), dtype=np.int8))
+        lo, hi = both.min(axis=0) - 5, both.max(axis=0) + 5
+        width, height = (int(v) for v in hi - lo + 1)
+        data = np.full((height, width), UNKNOWN, dtype=np.int8)
+        data[carved[:, 1] - lo[1], carved[:, 0] - lo[0]] = FREE
+        data[occupied[:, 1] - lo[1], occupied[:, 0] - lo[0]] = OCCUPIED      # occupied wins
+        return Raster(lo[0], lo[1], width, height, res, len(occupied), int(np.count_nonzero(data == FREE)), data)
