@@ -530,6 +530,50 @@ int icpmi_map_raycast(icpmi_map *map, const double *poses, int64_t n_poses, cons
                       icpmi_raster_info *info);
 int icpmi_map_raster(icpmi_map *map, int8_t *data, int64_t cap, icpmi_raster_info *info);
 
+/* The same rays counted per cell: how many used frames saw a cell occupied and how many saw through it, and the
+ * occupancy probability a planner reads from the two.  In icpmi_map_raycast's raster one return of one frame blocks a
+ * cell for good; here a parked car that drove off is outvoted by the later frames that look through it.  The frames
+ * (i < min(frames, n_poses)), poses, grid, hit cells, sensor cells and ray walk are exactly icpmi_map_raycast's.  For
+ * a used frame i:
+ *   H_i       the set of its distinct hit cells
+ *   C_i       the set of cells carved by any of its rays, minus H_i: within one scan occupied wins
+ * and for a cell c:
+ *   hits[c]   = #{i : c in H_i}
+ *   misses[c] = #{i : c in C_i}
+ * so a frame adds at most 1 to each of a cell's two counts, however many of its rows or rays touch the cell.
+ *   probability[c]  -1 if hits + misses == 0; else, with n = hits + misses, (200 hits + n) / (2 n) in integer
+ *             division: 100 hits / n rounded half up, the counting model, with no floating point.
+ *   bounds    tight over the cells with hits + misses > 0, widened by 5 cells: icpmi_map_raycast's box, since the
+ *             observed cells are its occupied and free ones.  Nothing observed: 0 x 0.  The layout of each array is
+ *             icpmi_map_raster's: cell (x, y) at [(y - min_y) * width + (x - min_x)].
+ * Hence hits > 0 exactly where the raster holds 100; hits == 0 and misses > 0 exactly where it holds 0; both -1
+ * elsewhere.  All integer sums: no dependence on the order of frames or rows.
+ * Every ICPMI_ERR_ARG and ICPMI_ERR_NULL case of icpmi_map_raycast applies unchanged; in addition more than
+ * ICPMI_RAYCOUNT_MAX_FRAMES used frames is ICPMI_ERR_ARG (a count is 16 bits wide).  All are decided before any device
+ * work.  Up to R = ICPMI_RAYCOUNT_LDS_MAX_R a frame's two bit windows (carved, hit) live in on-chip memory, beyond in
+ * device scratch; the results are the same.
+ *   icpmi_map_raycast_counts  builds the three arrays and keeps them on the device, in a buffer the handle owns; info
+ *                       may be NULL.  A failed call leaves the previous counts in place.  The context's cell set is
+ *                       not touched, and neither is icpmi_map_raster's raster: the two products are independent.
+ *                       Waits for the device twice (the arrays' size, the arrays); once when nothing is observed.
+ *   icpmi_map_counts    sets *info (may be NULL) to the last successful raycast_counts', all zeros before the first,
+ *                       and copies out the arrays that are not NULL (cap cells each; fewer than width * height with
+ *                       any array given is ICPMI_ERR_CAPACITY).  One wait.
+ * info: n_observed cells have hits + misses > 0; n_hit_cells have hits > 0 (icpmi_map_raycast's n_occupied); max_hits
+ * and max_misses are the greatest counts; frames_used is min(frames, n_poses). */
+#define ICPMI_RAYCOUNT_MAX_FRAMES 65535      /* counts are uint16: a frame adds at most 1 */
+#define ICPMI_RAYCOUNT_LDS_MAX_R 392         /* two bit windows in 160 KiB */
+typedef struct {
+    int32_t min_x, min_y, width, height;
+    double resolution;
+    int64_t n_observed, n_hit_cells;
+    int32_t max_hits, max_misses, frames_used, pad;
+} icpmi_counts_info;
+int icpmi_map_raycast_counts(icpmi_map *map, const double *poses, int64_t n_poses, const icpmi_grid_config *grid,
+                             icpmi_counts_info *info);
+int icpmi_map_counts(icpmi_map *map, uint16_t *hits, uint16_t *misses, int8_t *probability, int64_t cap,
+                     icpmi_counts_info *info);
+
 /* Loop-closure detection over a global map's kept scans (slam::LoopClosureDetector, core/loop_closure.hpp:41-148),
  * with its database on the device: an entry is a store frame with a label (the node's frame_idx).  Each entry's
  * Scan Context descriptor lives in device memory; its rows stay in the store and are never copied to the host.

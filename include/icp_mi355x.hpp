@@ -797,6 +797,18 @@ struct OccupancyRaster {
     std::vector<int8_t> data;
 };
 
+// What GlobalMap::raycast_counts returns (icpmi_map_counts): three arrays in OccupancyRaster's layout.  hits and
+// misses count the used frames that saw the cell occupied and that saw through it; probability is -1 for a cell no
+// frame observed and else 100 hits / (hits + misses) rounded half up, what nav_msgs/OccupancyGrid's data carries.
+struct OccupancyCounts {
+    int32_t min_x = 0, min_y = 0, width = 0, height = 0;
+    double resolution = 0.0;
+    int64_t n_observed = 0, n_hit_cells = 0;
+    int32_t max_hits = 0, max_misses = 0, frames_used = 0;
+    std::vector<uint16_t> hits, misses;
+    std::vector<int8_t> probability;
+};
+
 // The node's kept scans (downsampled_clouds_, slam_node.cpp:71,123) in device memory, and what it builds from them
 // with the optimised poses: rebuild_recent_clouds (:187-194), build_final_global_map (:196-209) with
 // rebuild_occupancy_grid (:223-229), and the map publish_global_map sends once complete (:235-238).  finish() rebuilds
@@ -881,6 +893,27 @@ public:
         out.resolution = info.resolution;
         out.data.resize(static_cast<std::size_t>(info.width) * static_cast<std::size_t>(info.height));
         if (!out.data.empty()) check(icpmi_map_raster(m_, out.data.data(), static_cast<int64_t>(out.data.size()), nullptr));
+        return out;
+    }
+    // The same rays counted per cell (icpmi_map_raycast_counts): a used frame adds 1 to the hits of each of its
+    // distinct hit cells and 1 to the misses of every other cell its rays carve.  Neither the context's cell set nor
+    // the last raycast's raster is touched.
+    OccupancyCounts raycast_counts(const std::vector<Transformation> &poses, const OccupancyGridConfig &grid)
+    {
+        const std::vector<double> P = flatten(poses);
+        const icpmi_grid_config g = detail::to_c(grid);
+        icpmi_counts_info info;
+        check(icpmi_map_raycast_counts(m_, P.data(), static_cast<int64_t>(poses.size()), &g, &info));
+        OccupancyCounts out;
+        out.min_x = info.min_x, out.min_y = info.min_y, out.width = info.width, out.height = info.height;
+        out.resolution = info.resolution;
+        out.n_observed = info.n_observed, out.n_hit_cells = info.n_hit_cells;
+        out.max_hits = info.max_hits, out.max_misses = info.max_misses, out.frames_used = info.frames_used;
+        const std::size_t cells = static_cast<std::size_t>(info.width) * static_cast<std::size_t>(info.height);
+        out.hits.resize(cells), out.misses.resize(cells), out.probability.resize(cells);
+        if (cells)
+            check(icpmi_map_counts(m_, out.hits.data(), out.misses.data(), out.probability.data(), static_cast<int64_t>(cells),
+                                   nullptr));
         return out;
     }
     icpmi_map *get() const { return m_; }

@@ -34,7 +34,7 @@ EXPORTS = [
     "icpmi_pose_graph_optimize", "icpmi_pose_graph_pose", "icpmi_pose_graph_poses", "icpmi_pose_graph_size",
     "icpmi_map_create", "icpmi_map_destroy", "icpmi_map_add_frame", "icpmi_map_add_frame_device",
     "icpmi_map_add_stream_frame", "icpmi_map_size", "icpmi_map_world", "icpmi_map_finish",
-    "icpmi_map_raycast", "icpmi_map_raster",
+    "icpmi_map_raycast", "icpmi_map_raster", "icpmi_map_raycast_counts", "icpmi_map_counts",
     "icpmi_loop_config_default", "icpmi_loop_create", "icpmi_loop_destroy", "icpmi_loop_add_frame", "icpmi_loop_detect",
     "icpmi_loop_descriptor", "icpmi_loop_size", "icpmi_loop_clear",
 ]
@@ -113,6 +113,16 @@ class RasterInfo(C.Structure):
     """icpmi_raster_info"""
     _fields_ = [("min_x", C.c_int32), ("min_y", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
                 ("resolution", C.c_double), ("n_occupied", C.c_int64), ("n_free", C.c_int64)]
+
+
+RAYCOUNT_MAX_FRAMES, RAYCOUNT_LDS_MAX_R = 65535, 392   # ICPMI_RAYCOUNT_MAX_FRAMES, ICPMI_RAYCOUNT_LDS_MAX_R
+
+
+class CountsInfo(C.Structure):
+    """icpmi_counts_info"""
+    _fields_ = [("min_x", C.c_int32), ("min_y", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("resolution", C.c_double), ("n_observed", C.c_int64), ("n_hit_cells", C.c_int64),
+                ("max_hits", C.c_int32), ("max_misses", C.c_int32), ("frames_used", C.c_int32), ("pad", C.c_int32)]
 
 
 class PoseGraphConfig(C.Structure):
@@ -277,6 +287,9 @@ def load_library(path=None):
     L.icpmi_map_finish.argtypes = [vp, dp, C.c_int64, C.POINTER(GridConfig), C.c_double, dp, C.c_int64, i64p, i64p]
     L.icpmi_map_raycast.argtypes = [vp, dp, C.c_int64, C.POINTER(GridConfig), C.POINTER(RasterInfo)]
     L.icpmi_map_raster.argtypes = [vp, C.POINTER(C.c_int8), C.c_int64, C.POINTER(RasterInfo)]
+    L.icpmi_map_raycast_counts.argtypes = [vp, dp, C.c_int64, C.POINTER(GridConfig), C.POINTER(CountsInfo)]
+    L.icpmi_map_counts.argtypes = [vp, C.POINTER(C.c_uint16), C.POINTER(C.c_uint16), C.POINTER(C.c_int8), C.c_int64,
+                                   C.POINTER(CountsInfo)]
     L.icpmi_loop_config_default.argtypes = [C.POINTER(LoopConfig)]
     L.icpmi_loop_config_default.restype = None
     L.icpmi_loop_create.argtypes = [vp, C.POINTER(LoopConfig), C.POINTER(vp)]

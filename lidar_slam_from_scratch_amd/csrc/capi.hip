@@ -42,6 +42,7 @@
 #include "occupancy.h"
 #include "global_map.h"
 #include "raycast.h"
+#include "raycount.h"
 #include "loop_store.h"
 #include "pose_graph.h"
 
@@ -3804,6 +3805,9 @@ struct icpmi_map {
     DevBuf d_ray_frames, d_ray_planes;   // icpmi_map_raycast: the frame table; the carved and occupied planes, RayBounds
     DevBuf d_raster, d_raster_next;      // the last successful raster; the one a call is building
     icpmi_raster_info raster{};          // the last successful raster's (all zeros before the first)
+    DevBuf d_count_plane, d_count_scratch; // icpmi_map_raycast_counts: the count plane and CountBounds; the windows past LDS
+    DevBuf d_counts, d_counts_next;      // the last successful counts (hits, misses, probability); those a call is building
+    icpmi_counts_info counts{};          // the last successful counts' (all zeros before the first)
 };
 
 namespace {
@@ -3895,6 +3899,56 @@ int map_queue_world(icpmi_map *m, const double *poses, int64_t first, int64_t la
     return ICPMI_OK;
 }
 
+// What icpmi_map_raycast and icpmi_map_raycast_counts decide on the host before any device work: R, the used frames'
+// table with their sensor cells, and the plane that holds every used frame's window.
+struct RayPlan {
+    int R = 0;
+    int64_t last = 0, rows = 0;      // the used frames [0, last) and the rows they hold
+    std::vector<RayFrame> frames;
+    RayPlane pl{0, 0, 0, 0, 0};      // set when rows > 0
+};
+
+int ray_plan(icpmi_map *m, const double *poses, int64_t n_poses, const icpmi_grid_config *grid, int64_t max_frames, RayPlan *out)
+{
+    icpmi_ctx *ctx = m->ctx;
+    int rc;
+    if (!grid) return fail(ctx, ICPMI_ERR_NULL, "grid is NULL");
+    const double res = grid->resolution;
+    if (!(std::isfinite(res) && res > 0.0)) return fail(ctx, ICPMI_ERR_ARG, "grid resolution must be finite and positive");
+    const double Rd = std::ceil(grid->max_range / res);
+    if (!(Rd <= (double)kRayMaxR))
+        return fail(ctx, ICPMI_ERR_ARG, "max_range / resolution must be at most %d cells", kRayMaxR);
+    const int R = Rd > 0.0 ? (int)Rd : 0;
+    int64_t last = 0;
+    if ((rc = map_check_poses(m, poses, n_poses, &last))) return rc;
+    if (last > max_frames)
+        return fail(ctx, ICPMI_ERR_ARG, "%lld frames would be used: at most %lld", (long long)last, (long long)max_frames);
+    // the sensor cells, and with them the plane: every carved or occupied cell lies within R + 1 cells of one
+    const double cell_max = 2147483646.0 - R - 6;
+    std::vector<RayFrame> frames((size_t)last);
+    int64_t lo_x = INT64_MAX, lo_y = INT64_MAX, hi_x = INT64_MIN, hi_y = INT64_MIN;
+    for (int64_t i = 0; i < last; ++i) {
+        const double cx = std::floor(poses[16 * i + 3] / res), cy = std::floor(poses[16 * i + 7] / res);
+        if (!(std::fabs(cx) <= cell_max && std::fabs(cy) <= cell_max))
+            return fail(ctx, ICPMI_ERR_ARG, "frame %lld's sensor cell is out of range", (long long)i);
+        const int64_t rows = m->row0[i + 1] - m->row0[i];
+        frames[(size_t)i] = RayFrame{m->row0[i], (int32_t)rows, (int32_t)cx, (int32_t)cy, 0};
+        if (rows == 0) continue;
+        lo_x = std::min<int64_t>(lo_x, (int64_t)cx), hi_x = std::max<int64_t>(hi_x, (int64_t)cx);
+        lo_y = std::min<int64_t>(lo_y, (int64_t)cy), hi_y = std::max<int64_t>(hi_y, (int64_t)cy);
+    }
+    out->R = R, out->last = last, out->rows = m->row0[last];
+    if (out->rows > 0) {
+        const int64_t W = hi_x - lo_x + 2 * R + 3, H = hi_y - lo_y + 2 * R + 3;
+        if ((W + 10) > (int64_t)INT32_MAX / (H + 10)) // the raster is the tight box widened by 5: never more than this
+            return fail(ctx, ICPMI_ERR_ARG, "the used frames span %lld x %lld cells: more than 2^31 - 1", (long long)(W + 10),
+                        (long long)(H + 10));
+        out->pl = RayPlane{(int32_t)(lo_x - R - 1), (int32_t)(lo_y - R - 1), (int32_t)W, (int32_t)H, (int32_t)((W + 31) / 32)};
+    }
+    out->frames = std::move(frames);
+    return ICPMI_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -3917,7 +3971,7 @@ void icpmi_map_destroy(icpmi_map *m)
     (void)hipSetDevice(m->ctx->opt.device);
     (void)hipStreamSynchronize(m->ctx->stream);
     for (DevBuf *b : {&m->d_rows, &m->d_tiles, &m->d_poses, &m->d_world, &m->d_ray_frames, &m->d_ray_planes, &m->d_raster,
-                      &m->d_raster_next})
+                      &m->d_raster_next, &m->d_count_plane, &m->d_count_scratch, &m->d_counts, &m->d_counts_next})
         release(*b);
     delete m;
 }
@@ -4057,40 +4111,17 @@ int icpmi_map_raycast(icpmi_map *m, const double *poses, int64_t n_poses, const 
     icpmi_ctx *ctx = m->ctx;
     int rc;
     if ((rc = check_common(ctx))) return rc;
-    if (!grid) return fail(ctx, ICPMI_ERR_NULL, "grid is NULL");
-    const double res = grid->resolution;
-    if (!(std::isfinite(res) && res > 0.0)) return fail(ctx, ICPMI_ERR_ARG, "grid resolution must be finite and positive");
-    const double Rd = std::ceil(grid->max_range / res);
-    if (!(Rd <= (double)kRayMaxR))
-        return fail(ctx, ICPMI_ERR_ARG, "max_range / resolution must be at most %d cells", kRayMaxR);
-    const int R = Rd > 0.0 ? (int)Rd : 0;
-    int64_t last = 0;
-    if ((rc = map_check_poses(m, poses, n_poses, &last))) return rc;
-    // the sensor cells, and with them the plane: every carved or occupied cell lies within R + 1 cells of one
-    const double cell_max = 2147483646.0 - R - 6;
-    std::vector<RayFrame> frames((size_t)last);
-    int64_t lo_x = INT64_MAX, lo_y = INT64_MAX, hi_x = INT64_MIN, hi_y = INT64_MIN;
-    for (int64_t i = 0; i < last; ++i) {
-        const double cx = std::floor(poses[16 * i + 3] / res), cy = std::floor(poses[16 * i + 7] / res);
-        if (!(std::fabs(cx) <= cell_max && std::fabs(cy) <= cell_max))
-            return fail(ctx, ICPMI_ERR_ARG, "frame %lld's sensor cell is out of range", (long long)i);
-        const int64_t rows = m->row0[i + 1] - m->row0[i];
-        frames[(size_t)i] = RayFrame{m->row0[i], (int32_t)rows, (int32_t)cx, (int32_t)cy, 0};
-        if (rows == 0) continue;
-        lo_x = std::min<int64_t>(lo_x, (int64_t)cx), hi_x = std::max<int64_t>(hi_x, (int64_t)cx);
-        lo_y = std::min<int64_t>(lo_y, (int64_t)cy), hi_y = std::max<int64_t>(hi_y, (int64_t)cy);
-    }
-    icpmi_raster_info out{0, 0, 0, 0, res, 0, 0};
-    const int64_t n64 = m->row0[last];
+    RayPlan plan;
+    if ((rc = ray_plan(m, poses, n_poses, grid, INT64_MAX, &plan))) return rc;
+    const int R = plan.R;
+    const int64_t last = plan.last, n64 = plan.rows;
+    const std::vector<RayFrame> &frames = plan.frames;
+    icpmi_raster_info out{0, 0, 0, 0, grid->resolution, 0, 0};
     if (n64 > 0) {
-        const int64_t W = hi_x - lo_x + 2 * R + 3, H = hi_y - lo_y + 2 * R + 3;
-        if ((W + 10) > (int64_t)INT32_MAX / (H + 10)) // the raster is the tight box widened by 5: never more than this
-            return fail(ctx, ICPMI_ERR_ARG, "the used frames span %lld x %lld cells: more than 2^31 - 1", (long long)(W + 10),
-                        (long long)(H + 10));
         Range range("icpmi:map_raycast");
         hipStream_t s = ctx->stream;
-        const RayPlane pl{(int32_t)(lo_x - R - 1), (int32_t)(lo_y - R - 1), (int32_t)W, (int32_t)H, (int32_t)((W + 31) / 32)};
-        const size_t words = (size_t)pl.wpr * (size_t)H;
+        const RayPlane pl = plan.pl;
+        const size_t words = (size_t)pl.wpr * (size_t)pl.h;
         if ((rc = reserve(ctx, ctx->grid_in, sizeof(unsigned long long) * (size_t)n64))) return rc;
         if ((rc = reserve(ctx, m->d_ray_frames, sizeof(RayFrame) * (size_t)last))) return rc;
         if ((rc = reserve(ctx, m->d_ray_planes, sizeof(unsigned) * 2 * words + sizeof(RayBounds)))) return rc;
@@ -4154,6 +4185,105 @@ int icpmi_map_raster(icpmi_map *m, int8_t *data, int64_t cap, icpmi_raster_info 
     if (cap < cells) return fail(ctx, ICPMI_ERR_CAPACITY, "data holds %lld cells, needs %lld", (long long)cap, (long long)cells);
     if (cells == 0) return ICPMI_OK;
     HIP_TRY(ctx, hipMemcpyAsync(data, m->d_raster.p, (size_t)cells, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); // the call's one wait
+    return ICPMI_OK;
+}
+
+static_assert(kCountMaxFrames == ICPMI_RAYCOUNT_MAX_FRAMES && kCountLdsMaxR == ICPMI_RAYCOUNT_LDS_MAX_R, "the header states these limits");
+
+// hits (uint16), misses (uint16), probability (int8) of `cells` cells, in that order in one buffer
+static size_t counts_bytes(size_t cells) { return 5 * cells; }
+
+int icpmi_map_raycast_counts(icpmi_map *m, const double *poses, int64_t n_poses, const icpmi_grid_config *grid,
+                             icpmi_counts_info *info)
+{
+    if (!m) return ICPMI_ERR_NULL;
+    icpmi_ctx *ctx = m->ctx;
+    int rc;
+    if ((rc = check_common(ctx))) return rc;
+    RayPlan plan;
+    if ((rc = ray_plan(m, poses, n_poses, grid, kCountMaxFrames, &plan))) return rc;
+    const int R = plan.R;
+    const int64_t last = plan.last, n64 = plan.rows;
+    icpmi_counts_info out{0, 0, 0, 0, grid->resolution, 0, 0, 0, 0, (int32_t)last, 0};
+    if (n64 > 0) {
+        Range range("icpmi:map_raycast_counts");
+        hipStream_t s = ctx->stream;
+        const RayPlane pl = plan.pl;
+        const size_t plane_cells = (size_t)pl.w * (size_t)pl.h;
+        const size_t pair = sizeof(unsigned) * 2 * (size_t)ray_window_words(R);
+        const bool lds = R <= kCountLdsMaxR;
+        const int groups = lds ? (int)last : count_scratch_groups(R, last);
+        if ((rc = reserve(ctx, ctx->grid_in, sizeof(unsigned long long) * (size_t)n64))) return rc;
+        if ((rc = reserve(ctx, m->d_ray_frames, sizeof(RayFrame) * (size_t)last))) return rc;
+        if ((rc = reserve(ctx, m->d_count_plane, sizeof(unsigned) * plane_cells + 8 + sizeof(CountBounds)))) return rc;
+        if (!lds && (rc = reserve(ctx, m->d_count_scratch, pair * (size_t)groups))) return rc;
+        unsigned long long *keys = (unsigned long long *)ctx->grid_in.p;
+        unsigned *plane = (unsigned *)m->d_count_plane.p;
+        CountBounds *bounds_d = (CountBounds *)((char *)plane + (sizeof(unsigned) * plane_cells + 7) / 8 * 8);
+        const RayFrame *frames_d = (const RayFrame *)m->d_ray_frames.p;
+        static const CountBounds kNone{INT32_MAX, INT32_MAX, -1, -1, 0, 0, 0, 0};
+        HIP_TRY(ctx, hipMemsetAsync(plane, 0, sizeof(unsigned) * plane_cells, s));
+        HIP_TRY(ctx, hipMemcpyAsync(bounds_d, &kNone, sizeof(CountBounds), hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipMemcpyAsync(m->d_ray_frames.p, plan.frames.data(), sizeof(RayFrame) * (size_t)last, hipMemcpyHostToDevice, s));
+        if ((rc = map_queue_world(m, poses, 0, last, nullptr, keys, grid))) return rc;
+        if (lds) {
+            if (R > kCountLdsPlainMaxR) // dynamic LDS past 64 KiB has to be allowed first
+                HIP_TRY(ctx, hipFuncSetAttribute((const void *)k_ray_count<true>, hipFuncAttributeMaxDynamicSharedMemorySize, kRayLdsBytes));
+            hipLaunchKernelGGL(k_ray_count<true>, dim3((unsigned)groups), dim3(kRayThreads), pair, s, (const unsigned long long *)keys,
+                               frames_d, (int)last, R, pl, (unsigned *)nullptr, plane);
+        } else {
+            HIP_TRY(ctx, hipMemsetAsync(m->d_count_scratch.p, 0, pair * (size_t)groups, s));
+            hipLaunchKernelGGL(k_ray_count<false>, dim3((unsigned)groups), dim3(kRayThreads), 0, s, (const unsigned long long *)keys,
+                               frames_d, (int)last, R, pl, (unsigned *)m->d_count_scratch.p, plane);
+        }
+        HIP_TRY(ctx, hipGetLastError());
+        hipLaunchKernelGGL(k_count_bounds, dim3((unsigned)std::min<int32_t>(pl.h, 1024)), dim3(256), 0, s, (const unsigned *)plane, pl,
+                           bounds_d);
+        HIP_TRY(ctx, hipGetLastError());
+        CountBounds b{};
+        HIP_TRY(ctx, hipMemcpyAsync(&b, bounds_d, sizeof(CountBounds), hipMemcpyDeviceToHost, s));
+        HIP_TRY(ctx, hipStreamSynchronize(s)); // the first wait: the arrays' size
+        if (b.max_x >= 0) {
+            out.min_x = pl.x0 + b.min_x - 5;
+            out.min_y = pl.y0 + b.min_y - 5;
+            out.width = b.max_x - b.min_x + 11;
+            out.height = b.max_y - b.min_y + 11;
+            out.n_observed = (int64_t)b.n_observed;
+            out.n_hit_cells = (int64_t)b.n_hit_cells;
+            out.max_hits = b.max_hits;
+            out.max_misses = b.max_misses;
+            const size_t cells = (size_t)out.width * (size_t)out.height;
+            if ((rc = reserve(ctx, m->d_counts_next, counts_bytes(cells)))) return rc;
+            uint16_t *hits = (uint16_t *)m->d_counts_next.p;
+            hipLaunchKernelGGL(k_count_raster, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, (const unsigned *)plane, pl,
+                               b.min_x - 5, b.min_y - 5, out.width, out.height, hits, hits + cells, (int8_t *)(hits + 2 * cells));
+            HIP_TRY(ctx, hipGetLastError());
+            HIP_TRY(ctx, hipStreamSynchronize(s)); // the second: the arrays are complete before they replace the last ones
+            std::swap(m->d_counts, m->d_counts_next);
+        }
+    }
+    m->counts = out;
+    if (info) *info = out;
+    return ICPMI_OK;
+}
+
+int icpmi_map_counts(icpmi_map *m, uint16_t *hits, uint16_t *misses, int8_t *probability, int64_t cap, icpmi_counts_info *info)
+{
+    if (!m) return ICPMI_ERR_NULL;
+    icpmi_ctx *ctx = m->ctx;
+    int rc;
+    if ((rc = check_common(ctx))) return rc;
+    if (info) *info = m->counts;
+    if (!hits && !misses && !probability) return ICPMI_OK;
+    const int64_t cells = (int64_t)m->counts.width * (int64_t)m->counts.height;
+    if (cap < cells) return fail(ctx, ICPMI_ERR_CAPACITY, "the arrays hold %lld cells, need %lld", (long long)cap, (long long)cells);
+    if (cells == 0) return ICPMI_OK;
+    const char *src = (const char *)m->d_counts.p;
+    const size_t n = (size_t)cells;
+    if (hits) HIP_TRY(ctx, hipMemcpyAsync(hits, src, 2 * n, hipMemcpyDeviceToHost, ctx->stream));
+    if (misses) HIP_TRY(ctx, hipMemcpyAsync(misses, src + 2 * n, 2 * n, hipMemcpyDeviceToHost, ctx->stream));
+    if (probability) HIP_TRY(ctx, hipMemcpyAsync(probability, src + 4 * n, n, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); // the call's one wait
     return ICPMI_OK;
 }

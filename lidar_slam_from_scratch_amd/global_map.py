@@ -28,6 +28,17 @@ class OccupancyRaster:
         self.data = data
 
 
+class OccupancyCounts:
+    """icpmi_map_counts' result: the info fields, and hits, misses (uint16) and probability (int8: -1 unobserved, else
+    100 hits / (hits + misses) rounded half up), each [y - min_y, x - min_x] as (height, width)"""
+
+    def __init__(self, info, hits, misses, probability):
+        self.min_x, self.min_y, self.width, self.height = info.min_x, info.min_y, info.width, info.height
+        self.resolution, self.n_observed, self.n_hit_cells = info.resolution, info.n_observed, info.n_hit_cells
+        self.max_hits, self.max_misses, self.frames_used = info.max_hits, info.max_misses, info.frames_used
+        self.hits, self.misses, self.probability = hits, misses, probability
+
+
 class GlobalMap:
     def __init__(self, ctx):
         self._lib = capi.load_library()
@@ -122,3 +133,27 @@ class GlobalMap:
         g = grid if grid is not None else self.ctx.make_grid_config()
         self.ctx._check(self._lib.icpmi_map_raycast(self._h, pp, P.shape[0], C.byref(g), None))
         return self.raster()
+
+    def counts(self):
+        """the last successful raycast_counts' arrays (0 x 0 before the first)"""
+        info = capi.CountsInfo()
+        self.ctx._check(self._lib.icpmi_map_counts(self._h, None, None, None, 0, C.byref(info)))
+        shape = (info.height, info.width)
+        hits, misses = np.empty(shape, dtype=np.uint16), np.empty(shape, dtype=np.uint16)
+        probability = np.empty(shape, dtype=np.int8)
+        if hits.size:
+            u16 = C.POINTER(C.c_uint16)
+            self.ctx._check(self._lib.icpmi_map_counts(self._h, hits.ctypes.data_as(u16), misses.ctypes.data_as(u16),
+                                                       probability.ctypes.data_as(C.POINTER(C.c_int8)), hits.size,
+                                                       C.byref(info)))
+        return OccupancyCounts(info, hits, misses, probability)
+
+    def raycast_counts(self, poses, grid=None):
+        """The kept scans ray-cast into per-cell hit and miss counts (icpmi_map_raycast_counts): a used frame adds 1 to
+        the hits of each of its distinct hit cells and 1 to the misses of every other cell its rays carve.  grid None:
+        the default OccupancyGridConfig.  Neither the context's cell set nor raster() is touched.  Returns an
+        OccupancyCounts."""
+        P, pp = _poses(poses)
+        g = grid if grid is not None else self.ctx.make_grid_config()
+        self.ctx._check(self._lib.icpmi_map_raycast_counts(self._h, pp, P.shape[0], C.byref(g), None))
+        return self.counts()

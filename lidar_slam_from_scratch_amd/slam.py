@@ -34,6 +34,7 @@ class SlamRun:
         self.cells = None             # ... and at the end the rebuilt cell set ((n, 2) int32, sorted)
         self.published_map = None     # ... and voxel_downsample(global map, map_voxel)
         self.raster = None            # ... and, with raycast=True, the free / occupied / unknown raster
+        self.counts = None            # ... and, with counts=True, the per-cell hit and miss counts
 
 
 def node_loop_config():
@@ -43,12 +44,13 @@ def node_loop_config():
 
 def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, pose_graph_config=None,
              align=None, loop_backend=None, pose_graph=None, global_map=None, grid=None, map_voxel=1.0,
-             loop_on_device=False, raycast=False):
+             loop_on_device=False, raycast=False, counts=False):
     """frames: sequence of N x 3 fp64 clouds (already downsampled).  Returns a SlamRun.  global_map: an object with
     add_frame, recent_clouds and finish (None: no map is built); grid: its occupancy grid config (None: defaults).
     loop_on_device: the detector is loop_closure.StoreLoopClosureDetector over global_map (a global_map.GlobalMap),
     or over a private GlobalMap that keeps every frame; it holds no clouds and gives the same closures.
-    raycast: with a global_map, SlamRun.raster = global_map.raycast(poses, grid) after its finish."""
+    raycast: with a global_map, SlamRun.raster = global_map.raycast(poses, grid) after its finish.
+    counts: with a global_map, SlamRun.counts = global_map.raycast_counts(poses, grid) after its finish."""
     if loop_on_device and loop_backend is not None:
         raise ValueError("loop_backend and loop_on_device=True both choose the detector")
     if align is None:
@@ -124,6 +126,8 @@ def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, po
         run.cells, run.published_map = global_map.finish(run.poses, grid, map_voxel)
         if raycast:
             run.raster = global_map.raycast(run.poses, grid)
+        if counts:
+            run.counts = global_map.raycast_counts(run.poses, grid)
     if loop_on_device:                                               # the detector (and a private store) go now
         detector.close()
         if global_map is None:

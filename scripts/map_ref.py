@@ -73,6 +73,27 @@ class Raster:
         return set(zip((x + self.min_x).tolist(), (y + self.min_y).tolist()))
 
 
+class Counts:
+    """what icpmi_map_counts returns: the info fields, and hits, misses (uint16) and probability (int8), each
+    [y - min_y, x - min_x] as (height, width)"""
+    MAX_FRAMES = 65535      # ICPMI_RAYCOUNT_MAX_FRAMES: a count is 16 bits wide and a frame adds at most 1
+
+    def __init__(self, min_x, min_y, width, height, resolution, n_observed, n_hit_cells, max_hits, max_misses,
+                 frames_used, hits, misses, probability):
+        self.min_x, self.min_y, self.width, self.height = int(min_x), int(min_y), int(width), int(height)
+        self.resolution, self.n_observed, self.n_hit_cells = float(resolution), int(n_observed), int(n_hit_cells)
+        self.max_hits, self.max_misses, self.frames_used = int(max_hits), int(max_misses), int(frames_used)
+        self.hits, self.misses, self.probability = hits, misses, probability
+
+    @staticmethod
+    def probability_of(hits, misses):
+        """-1 where hits + misses == 0; else (200 hits + n) // (2 n), n = hits + misses: 100 hits / n rounded half
+        up, in integers"""
+        h, m = np.asarray(hits, dtype=np.int64), np.asarray(misses, dtype=np.int64)
+        n = h + m
+        return np.where(n == 0, -1, (200 * h + n) // np.maximum(2 * n, 1)).astype(np.int8)
+
+
 def bresenham(x0, y0, x1, y1):
     """ray_walk (csrc/raycast.h): the cells carved on the way from (x0, y0) to (x1, y1): the first, not the last"""
     out = []
@@ -218,3 +239,63 @@ class MapRef:
         data[carved[:, 1] - lo[1], carved[:, 0] - lo[0]] = FREE
         data[occupied[:, 1] - lo[1], occupied[:, 0] - lo[0]] = OCCUPIED      # occupied wins
         return Raster(lo[0], lo[1], width, height, res, len(occupied), int(np.count_nonzero(data == FREE)), data)
+
+    def raycast_counts(self, poses, grid=None):
+        """icpmi_map_raycast_counts, normatively.  The frames (i < min(frames, len(poses))), poses, grid, hit cells,
+        sensor cells and ray walk are raycast's.  For a used frame i, H_i is the set of its distinct hit cells and C_i
+        the set of cells carved by any of its rays, minus H_i (within one scan occupied wins).  For a cell c,
+        hits[c] = #{i : c in H_i} and misses[c] = #{i : c in C_i}: a frame adds at most 1 to each.  probability is -1
+        where hits + misses == 0, else (200 hits + n) // (2 n) with n = hits + misses.  Bounds: tight over the cells
+        with hits + misses > 0, widened by 5; nothing observed gives 0 x 0.  The limits the library refuses with
+        ICPMI_ERR_ARG raise ValueError here: raycast's, and more than Counts.MAX_FRAMES used frames."""
+        g = grid_kwargs(grid)
+        res = g["resolution"]
+        if not (np.isfinite(res) and res > 0.0):
+            raise ValueError("grid resolution must be finite and positive")
+        with np.errstate(all="ignore"):
+            Rd = np.ceil(np.float64(g["max_range"]) / res)
+        if not Rd <= RAYCAST_MAX_R:
+            raise ValueError("max_range / resolution must be at most %d cells" % RAYCAST_MAX_R)
+        R = int(Rd) if Rd > 0 else 0
+        last = min(len(self.clouds), len(poses))
+        if last > Counts.MAX_FRAMES:
+            raise ValueError("more than %d frames would be used" % Counts.MAX_FRAMES)
+        P = [np.asarray(poses[i], dtype=np.float64).reshape(4, 4) for i in range(last)]
+        if not all(np.isfinite(T).all() for T in P):
+            raise ValueError("a used pose has a non-finite entry")
+        sensors = [(np.floor(T[0, 3] / res), np.floor(T[1, 3] / res)) for T in P]
+        if any(abs(c) > 2147483646.0 - R - 6 for s in sensors for c in s):
+            raise ValueError("a used frame's sensor cell is out of range")
+        held = np.array([s for i, s in enumerate(sensors) if self.clouds[i].shape[0]], dtype=np.int64).reshape(-1, 2)
+        if len(held):
+            W, H = (int(v) + 2 * R + 3 for v in held.max(axis=0) - held.min(axis=0))
+            if (W + 10) * (H + 10) > 2**31 - 1:
+                raise ValueError("the used frames span more than 2^31 - 1 cells")
+        key = lambda cells: cells[:, 0] * 2**32 + (cells[:, 1] + 2**31)     # noqa: E731  (_unique_cells' word per cell)
+        hit_keys, miss_keys = [], []
+        for i in range(last):
+            with np.errstate(all="ignore"):                             # non-finite rows mark nothing
+                world = world_points(self.clouds[i], P[i])
+            H_i = _unique_cells(hit_cells(world, P[i][:2, 3], res, g["height_min"], g["height_max"], g["max_range"]))
+            s = sensors[i]
+            carved = _unique_cells(bresenham_lockstep(int(s[0]), int(s[1]), H_i[:, 0], H_i[:, 1]))
+            hit_keys.append(key(H_i))
+            miss_keys.append(np.setdiff1d(key(carved), key(H_i), assume_unique=True))   # C_i
+        empty = np.zeros((0,), dtype=np.int64)
+        hk, hn = np.unique(np.concatenate(hit_keys + [empty]), return_counts=True)      # a frame lists a cell once
+        mk, mn = np.unique(np.concatenate(miss_keys + [empty]), return_counts=True)
+        both = np.concatenate([hk, mk])
+        if not len(both):
+            z16 = np.zeros((0, 0), dtype=np.uint16)
+            return Counts(0, 0, 0, 0, res, 0, 0, 0, 0, last, z16, z16.copy(), np.zeros((0, 0), dtype=np.int8))
+        xy = lambda k: (k >> 32, (k & (2**32 - 1)) - 2**31)                 # noqa: E731
+        bx, by = xy(both)
+        lo = np.array([bx.min(), by.min()]) - 5
+        width, height = int(bx.max()) + 5 - int(lo[0]) + 1, int(by.max()) + 5 - int(lo[1]) + 1
+        hits, misses = np.zeros((height, width), dtype=np.uint16), np.zeros((height, width), dtype=np.uint16)
+        x, y = xy(hk)
+        hits[y - lo[1], x - lo[0]] = hn
+        x, y = xy(mk)
+        misses[y - lo[1], x - lo[0]] = mn
+        return Counts(lo[0], lo[1], width, height, res, int(np.count_nonzero(hits | misses)), len(hk),
+                      hits.max(), misses.max(), last, hits, misses, Counts.probability_of(hits, misses))
