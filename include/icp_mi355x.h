@@ -574,6 +574,50 @@ int icpmi_map_raycast_counts(icpmi_map *map, const double *poses, int64_t n_pose
 int icpmi_map_counts(icpmi_map *map, uint16_t *hits, uint16_t *misses, int8_t *probability, int64_t cap,
                      icpmi_counts_info *info);
 
+/* The same counts kept while the node drives: a count plane that persists in the handle and moves with the map, so
+ * that a call casts only the frames that are new.  The contract is one sentence: icpmi_map_live_update(map, poses,
+ * n_poses, grid, info) leaves the handle's live counts byte for byte what icpmi_map_raycast_counts(map, poses, n_poses,
+ * grid, ...) would build from the same store; only the cost differs.  The handle remembers the grid, the number of
+ * frames it has cast (n_cast) and the 16 doubles of the pose each was cast with.  With used = min(frames, n_poses):
+ *   incremental  the grid is bitwise the remembered one, used >= n_cast and the first n_cast poses are bitwise the
+ *             remembered ones: frames [n_cast, used) are cast and added to the plane; nothing else is touched.
+ *   rebuild   every other case (poses moved by an optimize, fewer poses, another grid, the first call, the first call
+ *             after icpmi_map_live_clear or after a call that failed on the device): the plane is zeroed and frames
+ *             [0, used) are cast, by icpmi_map_raycast_counts' kernels.
+ *   nothing new  used == n_cast and nothing changed: no device work, and the same bytes.
+ * The counts are integer sums over sets, so the order frames are added in does not show.
+ * The plane is a dense box of 32-bit words, one per cell.  A frame whose (2R + 3)^2 window around its sensor cell
+ * leaves the box makes the plane grow: a new zeroed allocation and one device copy, with at least half the box's extent
+ * of slack on each side that was crossed, so that over a drive the cells copied are at most 4 x the final plane's; the
+ * old buffer is freed after the call's wait.  The slack is memory: the plane may hold up to 3/2 of the used frames' own
+ * extent on an axis driven one way, and is not held to the 2^31 - 1 cells the used frames' own box is held to.
+ * Every ICPMI_ERR_NULL and ICPMI_ERR_ARG case of icpmi_map_raycast_counts applies, the ICPMI_RAYCOUNT_MAX_FRAMES cap
+ * included, decided by the same host code before any device work; such a call leaves *info unwritten and the live
+ * state as it was, and the next good call is still incremental.  An ICPMI_ERR_HIP in the middle of a call marks the
+ * state invalid: the next call rebuilds.
+ *   icpmi_map_live_update  info may be NULL.  One wait for the device (none when nothing was cast).
+ *   icpmi_map_live_counts  sets *info (may be NULL) to the last successful update's, all zeros before the first and
+ *                       after a clear, and copies out the arrays that are not NULL: layout, cap and NULL rules of
+ *                       icpmi_map_counts, info->counts.width * height cells each.  One wait.
+ *   icpmi_map_live_clear   forgets the cast frames: the next update casts every used frame again.
+ * Neither call touches icpmi_map_counts' arrays, icpmi_map_raster's raster or the context's cell set, and neither
+ * icpmi_map_raycast_counts nor icpmi_map_raycast touches the live counts.
+ * info: counts is exactly what icpmi_map_raycast_counts would report; frames_cast the frames this call cast (0 when
+ * nothing was new); rebuilt 1 when remembered frames were discarded and cast again; moved 1 when the plane was
+ * reallocated and its words copied in this call; plane_* the plane's box in cells (0 x 0: no plane). */
+typedef struct {
+    icpmi_counts_info counts;
+    int64_t frames_cast;
+    int32_t rebuilt;
+    int32_t moved;
+    int32_t plane_x0, plane_y0, plane_w, plane_h;
+} icpmi_live_info;
+int icpmi_map_live_update(icpmi_map *map, const double *poses, int64_t n_poses, const icpmi_grid_config *grid,
+                          icpmi_live_info *info);
+int icpmi_map_live_counts(icpmi_map *map, uint16_t *hits, uint16_t *misses, int8_t *probability, int64_t cap,
+                          icpmi_live_info *info);
+int icpmi_map_live_clear(icpmi_map *map);
+
 /* Loop-closure detection over a global map's kept scans (slam::LoopClosureDetector, core/loop_closure.hpp:41-148),
  * with its database on the device: an entry is a store frame with a label (the node's frame_idx).  Each entry's
  * Scan Context descriptor lives in device memory; its rows stay in the store and are never copied to the host.

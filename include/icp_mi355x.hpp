@@ -809,6 +809,15 @@ struct OccupancyCounts {
     std::vector<int8_t> probability;
 };
 
+// What GlobalMap::live_update returns (icpmi_live_info, less the counts' info, which live_counts carries): the frames
+// the call cast, whether remembered frames were discarded and cast again, whether the plane was reallocated and
+// copied, and the plane's box in cells.
+struct LiveUpdate {
+    int64_t frames_cast = 0;
+    bool rebuilt = false, moved = false;
+    int32_t plane_x0 = 0, plane_y0 = 0, plane_w = 0, plane_h = 0;
+};
+
 // The node's kept scans (downsampled_clouds_, slam_node.cpp:71,123) in device memory, and what it builds from them
 // with the optimised poses: rebuild_recent_clouds (:187-194), build_final_global_map (:196-209) with
 // rebuild_occupancy_grid (:223-229), and the map publish_global_map sends once complete (:235-238).  finish() rebuilds
@@ -916,6 +925,42 @@ public:
                                    nullptr));
         return out;
     }
+    // The counts kept while the node drives (icpmi_map_live_update): afterwards live_counts() is byte for byte what
+    // raycast_counts(poses, grid) would return, but only the frames not cast yet are cast, unless a pose already cast
+    // or the grid has changed.  Where update_occupancy_grid stands in process_frame (:152), and after
+    // run_pose_graph_optimization has replaced the poses (:177-185).  counts(), raster and cell set are not touched.
+    LiveUpdate live_update(const std::vector<Transformation> &poses, const OccupancyGridConfig &grid)
+    {
+        const std::vector<double> P = flatten(poses);
+        const icpmi_grid_config g = detail::to_c(grid);
+        icpmi_live_info info;
+        check(icpmi_map_live_update(m_, P.data(), static_cast<int64_t>(poses.size()), &g, &info));
+        LiveUpdate out;
+        out.frames_cast = info.frames_cast;
+        out.rebuilt = info.rebuilt != 0, out.moved = info.moved != 0;
+        out.plane_x0 = info.plane_x0, out.plane_y0 = info.plane_y0, out.plane_w = info.plane_w, out.plane_h = info.plane_h;
+        return out;
+    }
+    // the live counts of the last successful live_update (icpmi_map_live_counts): 0 x 0 before the first
+    OccupancyCounts live_counts()
+    {
+        icpmi_live_info live;
+        check(icpmi_map_live_counts(m_, nullptr, nullptr, nullptr, 0, &live));
+        const icpmi_counts_info &info = live.counts;
+        OccupancyCounts out;
+        out.min_x = info.min_x, out.min_y = info.min_y, out.width = info.width, out.height = info.height;
+        out.resolution = info.resolution;
+        out.n_observed = info.n_observed, out.n_hit_cells = info.n_hit_cells;
+        out.max_hits = info.max_hits, out.max_misses = info.max_misses, out.frames_used = info.frames_used;
+        const std::size_t cells = static_cast<std::size_t>(info.width) * static_cast<std::size_t>(info.height);
+        out.hits.resize(cells), out.misses.resize(cells), out.probability.resize(cells);
+        if (cells)
+            check(icpmi_map_live_counts(m_, out.hits.data(), out.misses.data(), out.probability.data(),
+                                        static_cast<int64_t>(cells), nullptr));
+        return out;
+    }
+    // forget the frames cast so far: the next live_update casts every used frame again
+    void live_clear() { check(icpmi_map_live_clear(m_)); }
     icpmi_map *get() const { return m_; }
     Context *context() const { return ctx_; }
 

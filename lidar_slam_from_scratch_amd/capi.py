@@ -35,6 +35,7 @@ EXPORTS = [
     "icpmi_map_create", "icpmi_map_destroy", "icpmi_map_add_frame", "icpmi_map_add_frame_device",
     "icpmi_map_add_stream_frame", "icpmi_map_size", "icpmi_map_world", "icpmi_map_finish",
     "icpmi_map_raycast", "icpmi_map_raster", "icpmi_map_raycast_counts", "icpmi_map_counts",
+    "icpmi_map_live_update", "icpmi_map_live_counts", "icpmi_map_live_clear",
     "icpmi_loop_config_default", "icpmi_loop_create", "icpmi_loop_destroy", "icpmi_loop_add_frame", "icpmi_loop_detect",
     "icpmi_loop_descriptor", "icpmi_loop_size", "icpmi_loop_clear",
 ]
@@ -123,6 +124,16 @@ class CountsInfo(C.Structure):
     _fields_ = [("min_x", C.c_int32), ("min_y", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
                 ("resolution", C.c_double), ("n_observed", C.c_int64), ("n_hit_cells", C.c_int64),
                 ("max_hits", C.c_int32), ("max_misses", C.c_int32), ("frames_used", C.c_int32), ("pad", C.c_int32)]
+
+
+LIVE_CARVE_GROUPS, LIVE_CARVE_ROWS = 16, 1024   # csrc/live_counts.h's kLiveGroups and kLiveGroupRows: a new frame's rows
+#                                                 are shared among min(16, ceil(rows / 1024)) workgroups
+
+
+class LiveInfo(C.Structure):
+    """icpmi_live_info"""
+    _fields_ = [("counts", CountsInfo), ("frames_cast", C.c_int64), ("rebuilt", C.c_int32), ("moved", C.c_int32),
+                ("plane_x0", C.c_int32), ("plane_y0", C.c_int32), ("plane_w", C.c_int32), ("plane_h", C.c_int32)]
 
 
 class PoseGraphConfig(C.Structure):
@@ -290,6 +301,10 @@ def load_library(path=None):
     L.icpmi_map_raycast_counts.argtypes = [vp, dp, C.c_int64, C.POINTER(GridConfig), C.POINTER(CountsInfo)]
     L.icpmi_map_counts.argtypes = [vp, C.POINTER(C.c_uint16), C.POINTER(C.c_uint16), C.POINTER(C.c_int8), C.c_int64,
                                    C.POINTER(CountsInfo)]
+    L.icpmi_map_live_update.argtypes = [vp, dp, C.c_int64, C.POINTER(GridConfig), C.POINTER(LiveInfo)]
+    L.icpmi_map_live_counts.argtypes = [vp, C.POINTER(C.c_uint16), C.POINTER(C.c_uint16), C.POINTER(C.c_int8), C.c_int64,
+                                        C.POINTER(LiveInfo)]
+    L.icpmi_map_live_clear.argtypes = [vp]
     L.icpmi_loop_config_default.argtypes = [C.POINTER(LoopConfig)]
     L.icpmi_loop_config_default.restype = None
     L.icpmi_loop_create.argtypes = [vp, C.POINTER(LoopConfig), C.POINTER(vp)]

@@ -43,6 +43,8 @@
 #include "global_map.h"
 #include "raycast.h"
 #include "raycount.h"
+#include "live_plane.h"
+#include "live_counts.h"
 #include "loop_store.h"
 #include "pose_graph.h"
 
@@ -3793,6 +3795,23 @@ int icpmi_pose_graph_size(const icpmi_pose_graph *g, int64_t *num_poses, int64_t
 // Global map (slam_node.cpp:187-238): the node's kept scans (downsampled_clouds_) in one device arena, and the world
 // points, cell set and published map of any prefix of them from one launch of k_map_world (global_map.h).
 
+// What a map handle remembers between icpmi_map_live_update calls: the plane and its box, the running bounds, and the
+// grid and poses the frames [0, n_cast) were cast with.
+struct LiveCounts {
+    bool valid = false;                  // false: the next update rebuilds (nothing cast yet, cleared, or a HIP failure)
+    bool windows_clean = false;          // d_windows is all zeros
+    icpmi_grid_config grid{};
+    int R = 0;
+    int64_t n_cast = 0;
+    std::vector<double> poses;           // 16 doubles per cast frame
+    int64_t span[4] = {INT64_MAX, INT64_MAX, INT64_MIN, INT64_MIN};   // the sensor cells of the cast frames that hold rows
+    LiveBox box;                         // the plane's cells (w == 0: no plane)
+    CountBounds bounds{INT32_MAX, INT32_MAX, -1, -1, 0, 0, 0, 0};     // the host's copy after the last update
+    DevBuf d_plane, d_bounds, d_windows; // one word per cell; CountBounds; k_live_carve's pair of windows
+    DevBuf d_out;                        // icpmi_map_live_counts: hits, misses, probability
+    icpmi_live_info info{};              // the last successful update's (all zeros before the first)
+};
+
 struct icpmi_map {
     icpmi_ctx *ctx = nullptr;
     DevBuf d_rows;                       // the store: every frame's rows, frame after frame (N x 3 fp64)
@@ -3808,6 +3827,7 @@ struct icpmi_map {
     DevBuf d_count_plane, d_count_scratch; // icpmi_map_raycast_counts: the count plane and CountBounds; the windows past LDS
     DevBuf d_counts, d_counts_next;      // the last successful counts (hits, misses, probability); those a call is building
     icpmi_counts_info counts{};          // the last successful counts' (all zeros before the first)
+    LiveCounts live;                     // icpmi_map_live_update: the counts that persist (live_counts.h)
 };
 
 namespace {
@@ -3855,16 +3875,28 @@ int map_append(icpmi_map *m, const void *src, int64_t n, hipMemcpyKind kind)
 }
 
 // The frames a call uses: [0, min(frames, n_poses)) (slam_node.cpp:190,201,225: i < downsampled_clouds_.size() &&
-// i < poses_.size()).  The poses they use must be finite.
-int map_check_poses(icpmi_map *m, const double *poses, int64_t n_poses, int64_t *last)
+// i < poses_.size()).  The poses they use must be finite; map_check_poses is the two steps over every used frame.
+int map_check_count(icpmi_map *m, const double *poses, int64_t n_poses, int64_t *last)
 {
     icpmi_ctx *ctx = m->ctx;
     if (n_poses < 0) return fail(ctx, ICPMI_ERR_ARG, "n_poses < 0");
     if (!poses && n_poses > 0) return fail(ctx, ICPMI_ERR_NULL, "poses is NULL");
     *last = std::min(map_frames(m), n_poses);
-    for (int64_t i = 0; i < 16 * *last; ++i)
-        if (!std::isfinite(poses[i])) return fail(ctx, ICPMI_ERR_ARG, "pose %lld has a non-finite entry", (long long)(i / 16));
     return ICPMI_OK;
+}
+
+int map_check_finite(icpmi_map *m, const double *poses, int64_t first, int64_t last)
+{
+    for (int64_t i = 16 * first; i < 16 * last; ++i)
+        if (!std::isfinite(poses[i])) return fail(m->ctx, ICPMI_ERR_ARG, "pose %lld has a non-finite entry", (long long)(i / 16));
+    return ICPMI_OK;
+}
+
+int map_check_poses(icpmi_map *m, const double *poses, int64_t n_poses, int64_t *last)
+{
+    int rc;
+    if ((rc = map_check_count(m, poses, n_poses, last))) return rc;
+    return map_check_finite(m, poses, 0, *last);
 }
 
 // Queue, for frames [first, last) (first < last): the tile table's new entries, the frames' poses, and k_map_world
@@ -3899,8 +3931,9 @@ int map_queue_world(icpmi_map *m, const double *poses, int64_t first, int64_t la
     return ICPMI_OK;
 }
 
-// What icpmi_map_raycast and icpmi_map_raycast_counts decide on the host before any device work: R, the used frames'
-// table with their sensor cells, and the plane that holds every used frame's window.
+// What icpmi_map_raycast, icpmi_map_raycast_counts and icpmi_map_live_update decide on the host before any device
+// work: R, the used frames' table with their sensor cells, and the plane that holds every used frame's window.
+// ray_plan is the four steps below over every used frame; icpmi_map_live_update runs them over its new frames only.
 struct RayPlan {
     int R = 0;
     int64_t last = 0, rows = 0;      // the used frames [0, last) and the rows they hold
@@ -3908,43 +3941,68 @@ struct RayPlan {
     RayPlane pl{0, 0, 0, 0, 0};      // set when rows > 0
 };
 
-int ray_plan(icpmi_map *m, const double *poses, int64_t n_poses, const icpmi_grid_config *grid, int64_t max_frames, RayPlan *out)
+struct RaySpan {                     // of the sensor cells of the frames that hold rows
+    int64_t lo_x = INT64_MAX, lo_y = INT64_MAX, hi_x = INT64_MIN, hi_y = INT64_MIN;
+};
+
+int ray_plan_grid(icpmi_ctx *ctx, const icpmi_grid_config *grid, int *R)
 {
-    icpmi_ctx *ctx = m->ctx;
-    int rc;
     if (!grid) return fail(ctx, ICPMI_ERR_NULL, "grid is NULL");
     const double res = grid->resolution;
     if (!(std::isfinite(res) && res > 0.0)) return fail(ctx, ICPMI_ERR_ARG, "grid resolution must be finite and positive");
     const double Rd = std::ceil(grid->max_range / res);
     if (!(Rd <= (double)kRayMaxR))
         return fail(ctx, ICPMI_ERR_ARG, "max_range / resolution must be at most %d cells", kRayMaxR);
-    const int R = Rd > 0.0 ? (int)Rd : 0;
+    *R = Rd > 0.0 ? (int)Rd : 0;
+    return ICPMI_OK;
+}
+
+// Frames [first, last): their sensor cells (each within range), their table entries behind *frames with row0 counted
+// from frame `first`'s first row (k_map_world's keys for those frames), and *span widened by those that hold rows.
+int ray_plan_frames(icpmi_map *m, const double *poses, double res, int R, int64_t first, int64_t last, RaySpan *span,
+                    std::vector<RayFrame> *frames)
+{
+    // every carved or occupied cell lies within R + 1 cells of a sensor cell
+    const double cell_max = 2147483646.0 - R - 6;
+    frames->reserve(frames->size() + (size_t)(last - first));
+    for (int64_t i = first; i < last; ++i) {
+        const double cx = std::floor(poses[16 * i + 3] / res), cy = std::floor(poses[16 * i + 7] / res);
+        if (!(std::fabs(cx) <= cell_max && std::fabs(cy) <= cell_max))
+            return fail(m->ctx, ICPMI_ERR_ARG, "frame %lld's sensor cell is out of range", (long long)i);
+        const int64_t rows = m->row0[i + 1] - m->row0[i];
+        frames->push_back(RayFrame{m->row0[i] - m->row0[first], (int32_t)rows, (int32_t)cx, (int32_t)cy, 0});
+        if (rows == 0) continue;
+        span->lo_x = std::min<int64_t>(span->lo_x, (int64_t)cx), span->hi_x = std::max<int64_t>(span->hi_x, (int64_t)cx);
+        span->lo_y = std::min<int64_t>(span->lo_y, (int64_t)cy), span->hi_y = std::max<int64_t>(span->hi_y, (int64_t)cy);
+    }
+    return ICPMI_OK;
+}
+
+// The plane of a span (of at least one frame): every window, and no more than 2^31 - 1 cells with the raster's margin.
+int ray_plan_plane(icpmi_ctx *ctx, const RaySpan &sp, int R, RayPlane *pl)
+{
+    const int64_t W = sp.hi_x - sp.lo_x + 2 * R + 3, H = sp.hi_y - sp.lo_y + 2 * R + 3;
+    if ((W + 10) > (int64_t)INT32_MAX / (H + 10)) // the raster is the tight box widened by 5: never more than this
+        return fail(ctx, ICPMI_ERR_ARG, "the used frames span %lld x %lld cells: more than 2^31 - 1", (long long)(W + 10),
+                    (long long)(H + 10));
+    *pl = RayPlane{(int32_t)(sp.lo_x - R - 1), (int32_t)(sp.lo_y - R - 1), (int32_t)W, (int32_t)H, (int32_t)((W + 31) / 32)};
+    return ICPMI_OK;
+}
+
+int ray_plan(icpmi_map *m, const double *poses, int64_t n_poses, const icpmi_grid_config *grid, int64_t max_frames, RayPlan *out)
+{
+    icpmi_ctx *ctx = m->ctx;
+    int rc, R = 0;
+    if ((rc = ray_plan_grid(ctx, grid, &R))) return rc;
     int64_t last = 0;
     if ((rc = map_check_poses(m, poses, n_poses, &last))) return rc;
     if (last > max_frames)
         return fail(ctx, ICPMI_ERR_ARG, "%lld frames would be used: at most %lld", (long long)last, (long long)max_frames);
-    // the sensor cells, and with them the plane: every carved or occupied cell lies within R + 1 cells of one
-    const double cell_max = 2147483646.0 - R - 6;
-    std::vector<RayFrame> frames((size_t)last);
-    int64_t lo_x = INT64_MAX, lo_y = INT64_MAX, hi_x = INT64_MIN, hi_y = INT64_MIN;
-    for (int64_t i = 0; i < last; ++i) {
-        const double cx = std::floor(poses[16 * i + 3] / res), cy = std::floor(poses[16 * i + 7] / res);
-        if (!(std::fabs(cx) <= cell_max && std::fabs(cy) <= cell_max))
-            return fail(ctx, ICPMI_ERR_ARG, "frame %lld's sensor cell is out of range", (long long)i);
-        const int64_t rows = m->row0[i + 1] - m->row0[i];
-        frames[(size_t)i] = RayFrame{m->row0[i], (int32_t)rows, (int32_t)cx, (int32_t)cy, 0};
-        if (rows == 0) continue;
-        lo_x = std::min<int64_t>(lo_x, (int64_t)cx), hi_x = std::max<int64_t>(hi_x, (int64_t)cx);
-        lo_y = std::min<int64_t>(lo_y, (int64_t)cy), hi_y = std::max<int64_t>(hi_y, (int64_t)cy);
-    }
+    std::vector<RayFrame> frames;
+    RaySpan span;
+    if ((rc = ray_plan_frames(m, poses, grid->resolution, R, 0, last, &span, &frames))) return rc;
     out->R = R, out->last = last, out->rows = m->row0[last];
-    if (out->rows > 0) {
-        const int64_t W = hi_x - lo_x + 2 * R + 3, H = hi_y - lo_y + 2 * R + 3;
-        if ((W + 10) > (int64_t)INT32_MAX / (H + 10)) // the raster is the tight box widened by 5: never more than this
-            return fail(ctx, ICPMI_ERR_ARG, "the used frames span %lld x %lld cells: more than 2^31 - 1", (long long)(W + 10),
-                        (long long)(H + 10));
-        out->pl = RayPlane{(int32_t)(lo_x - R - 1), (int32_t)(lo_y - R - 1), (int32_t)W, (int32_t)H, (int32_t)((W + 31) / 32)};
-    }
+    if (out->rows > 0 && (rc = ray_plan_plane(ctx, span, R, &out->pl))) return rc;
     out->frames = std::move(frames);
     return ICPMI_OK;
 }
@@ -3971,7 +4029,8 @@ void icpmi_map_destroy(icpmi_map *m)
     (void)hipSetDevice(m->ctx->opt.device);
     (void)hipStreamSynchronize(m->ctx->stream);
     for (DevBuf *b : {&m->d_rows, &m->d_tiles, &m->d_poses, &m->d_world, &m->d_ray_frames, &m->d_ray_planes, &m->d_raster,
-                      &m->d_raster_next, &m->d_count_plane, &m->d_count_scratch, &m->d_counts, &m->d_counts_next})
+                      &m->d_raster_next, &m->d_count_plane, &m->d_count_scratch, &m->d_counts, &m->d_counts_next, &m->live.d_plane,
+                      &m->live.d_bounds, &m->live.d_windows, &m->live.d_out})
         release(*b);
     delete m;
 }
@@ -4286,6 +4345,243 @@ int icpmi_map_counts(icpmi_map *m, uint16_t *hits, uint16_t *misses, int8_t *pro
     if (probability) HIP_TRY(ctx, hipMemcpyAsync(probability, src + 4 * n, n, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); // the call's one wait
     return ICPMI_OK;
+}
+
+} // extern "C"
+
+// ---- the counts kept while the node drives (live_counts.h, live_plane.h) ----
+
+namespace {
+
+const CountBounds kCountNone{INT32_MAX, INT32_MAX, -1, -1, 0, 0, 0, 0};
+
+RayPlane live_ray_plane(const LiveBox &b)
+{
+    return RayPlane{(int32_t)b.x0, (int32_t)b.y0, (int32_t)b.w, (int32_t)b.h, (int32_t)((b.w + 31) / 32)};
+}
+
+// What an update reports: icpmi_map_raycast_counts' info from the running bounds, and the plane's box.
+void live_fill_info(const LiveCounts &L, int64_t used, icpmi_live_info *out)
+{
+    icpmi_counts_info c{0, 0, 0, 0, L.grid.resolution, 0, 0, 0, 0, (int32_t)used, 0};
+    const CountBounds &b = L.bounds;
+    if (L.box.w > 0 && b.max_x >= 0) {
+        c.min_x = (int32_t)L.box.x0 + b.min_x - 5;
+        c.min_y = (int32_t)L.box.y0 + b.min_y - 5;
+        c.width = b.max_x - b.min_x + 11;
+        c.height = b.max_y - b.min_y + 11;
+        c.n_observed = (int64_t)b.n_observed;
+        c.n_hit_cells = (int64_t)b.n_hit_cells;
+        c.max_hits = b.max_hits;
+        c.max_misses = b.max_misses;
+    }
+    out->counts = c;
+    out->plane_x0 = (int32_t)L.box.x0, out->plane_y0 = (int32_t)L.box.y0;
+    out->plane_w = (int32_t)L.box.w, out->plane_h = (int32_t)L.box.h;
+}
+
+// An update's device work and its one wait: frames [first, used) (`frames`: their table, rows counted from frame
+// first's; they hold rows) are cast into the plane, which becomes `box`.  rebuild: the plane is zeroed first.  `old`
+// takes the buffers to release after the wait; *b the bounds after it.
+int live_cast(icpmi_map *m, const double *poses, const icpmi_grid_config *grid, int R, bool rebuild, int64_t first, int64_t used,
+              const std::vector<RayFrame> &frames, const LiveBox &box, bool *moved, std::vector<DevBuf> &old, CountBounds *b)
+{
+    icpmi_ctx *ctx = m->ctx;
+    LiveCounts &L = m->live;
+    hipStream_t s = ctx->stream;
+    int rc;
+    Range range("icpmi:map_live_update");
+    const int64_t rows = m->row0[used] - m->row0[first];
+    const size_t plane_bytes = sizeof(unsigned) * (size_t)box.w * (size_t)box.h;
+    if ((rc = reserve(ctx, ctx->grid_in, sizeof(unsigned long long) * (size_t)rows))) return rc;
+    if ((rc = reserve(ctx, L.d_bounds, sizeof(CountBounds)))) return rc;
+    CountBounds *bounds_d = (CountBounds *)L.d_bounds.p;
+    if (rebuild || L.box.w == 0) {  // a fresh plane
+        if ((rc = reserve(ctx, L.d_plane, plane_bytes))) return rc;
+        HIP_TRY(ctx, hipMemsetAsync(L.d_plane.p, 0, plane_bytes, s));
+        HIP_TRY(ctx, hipMemcpyAsync(bounds_d, &kCountNone, sizeof(CountBounds), hipMemcpyHostToDevice, s));
+    } else if (box.x0 != L.box.x0 || box.y0 != L.box.y0 || box.w != L.box.w || box.h != L.box.h) {
+        DevBuf grown;               // the plane grows: its words move into a larger zeroed one
+        HIP_TRY(ctx, reserve_raw(grown, plane_bytes));
+        old.push_back(L.d_plane);
+        L.d_plane = grown;
+        HIP_TRY(ctx, hipMemsetAsync(grown.p, 0, plane_bytes, s));
+        hipLaunchKernelGGL(k_plane_move, dim3((unsigned)std::min<int64_t>(L.box.h, 2048)), dim3(256), 0, s,
+                           (const unsigned *)old.back().p, (int)L.box.w, (int)L.box.h, (unsigned *)grown.p, (int)box.w,
+                           (int)(L.box.x0 - box.x0), (int)(L.box.y0 - box.y0), bounds_d);
+        HIP_TRY(ctx, hipGetLastError());
+        *moved = true;
+    }
+    L.box = box;
+    const RayPlane pl = live_ray_plane(box);
+    unsigned *plane = (unsigned *)L.d_plane.p;
+    unsigned long long *keys = (unsigned long long *)ctx->grid_in.p;
+    if ((rc = map_queue_world(m, poses, first, used, nullptr, keys, grid))) return rc;
+    const int64_t nf = used - first;
+    int64_t held = 0;
+    for (const RayFrame &f : frames) held += f.rows > 0;
+    const size_t pair = sizeof(unsigned) * 2 * (size_t)ray_window_words(R);
+    const bool lds = R <= kCountLdsMaxR;
+    if (rebuild || !lds || held > kLiveBatchFrames) {
+        // icpmi_map_raycast_counts' kernels, aimed at the live plane: their adds are atomic, so they may fall on counts
+        // already there; the bounds are then counted again over the whole plane
+        const int groups = lds ? (int)nf : count_scratch_groups(R, nf);
+        if ((rc = reserve(ctx, m->d_ray_frames, sizeof(RayFrame) * (size_t)nf))) return rc;
+        if (!lds && (rc = reserve(ctx, m->d_count_scratch, pair * (size_t)groups))) return rc;
+        const RayFrame *frames_d = (const RayFrame *)m->d_ray_frames.p;
+        HIP_TRY(ctx, hipMemcpyAsync(m->d_ray_frames.p, frames.data(), sizeof(RayFrame) * (size_t)nf, hipMemcpyHostToDevice, s));
+        if (lds) {
+            if (R > kCountLdsPlainMaxR)
+                HIP_TRY(ctx, hipFuncSetAttribute((const void *)k_ray_count<true>, hipFuncAttributeMaxDynamicSharedMemorySize, kRayLdsBytes));
+            hipLaunchKernelGGL(k_ray_count<true>, dim3((unsigned)groups), dim3(kRayThreads), pair, s, (const unsigned long long *)keys,
+                               frames_d, (int)nf, R, pl, (unsigned *)nullptr, plane);
+        } else {
+            HIP_TRY(ctx, hipMemsetAsync(m->d_count_scratch.p, 0, pair * (size_t)groups, s));
+            hipLaunchKernelGGL(k_ray_count<false>, dim3((unsigned)groups), dim3(kRayThreads), 0, s, (const unsigned long long *)keys,
+                               frames_d, (int)nf, R, pl, (unsigned *)m->d_count_scratch.p, plane);
+        }
+        HIP_TRY(ctx, hipGetLastError());
+        if (!rebuild) HIP_TRY(ctx, hipMemcpyAsync(bounds_d, &kCountNone, sizeof(CountBounds), hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_count_bounds, dim3((unsigned)std::min<int32_t>(pl.h, 1024)), dim3(256), 0, s, (const unsigned *)plane, pl,
+                           bounds_d);
+        HIP_TRY(ctx, hipGetLastError());
+    } else {
+        if (pair > L.d_windows.cap) L.windows_clean = false;
+        if ((rc = reserve(ctx, L.d_windows, pair))) return rc;
+        if (!L.windows_clean) HIP_TRY(ctx, hipMemsetAsync(L.d_windows.p, 0, L.d_windows.cap, s));
+        L.windows_clean = false;    // until the call's wait has shown that every k_live_apply ran
+        if (R > kCountLdsPlainMaxR) // dynamic LDS past 64 KiB has to be allowed first
+            HIP_TRY(ctx, hipFuncSetAttribute((const void *)k_live_carve, hipFuncAttributeMaxDynamicSharedMemorySize, kRayLdsBytes));
+        unsigned *win = (unsigned *)L.d_windows.p;
+        const int tasks = (ray_window_words(R) + 1) / 2, per = kLiveApplyThreads / 64;
+        const unsigned apply_groups = (unsigned)std::min(kLiveApplyGroups, (tasks + per - 1) / per);
+        for (const RayFrame &f : frames) {
+            if (f.rows == 0) continue;
+            const int wx0 = (int)((int64_t)f.sx - (R + 1) - box.x0), wy0 = (int)((int64_t)f.sy - (R + 1) - box.y0);
+            hipLaunchKernelGGL(k_live_carve, dim3((unsigned)live_carve_groups(f.rows)), dim3(kRayThreads), pair, s,
+                               (const unsigned long long *)keys, f, R, wx0 & 31, live_carve_share(f.rows), win);
+            hipLaunchKernelGGL(k_live_apply, dim3(apply_groups), dim3(kLiveApplyThreads), 0, s, win, R, wx0, wy0, pl, plane, bounds_d);
+        }
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(b, bounds_d, sizeof(CountBounds), hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s)); // the call's one wait
+    HIP_TRY(ctx, hipGetLastError());
+    return ICPMI_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int icpmi_map_live_update(icpmi_map *m, const double *poses, int64_t n_poses, const icpmi_grid_config *grid, icpmi_live_info *info)
+{
+    if (!m) return ICPMI_ERR_NULL;
+    icpmi_ctx *ctx = m->ctx;
+    LiveCounts &L = m->live;
+    int rc, R = 0;
+    if ((rc = check_common(ctx))) return rc;
+    // ray_plan's steps, over the frames this call would cast
+    if ((rc = ray_plan_grid(ctx, grid, &R))) return rc;
+    int64_t used = 0;
+    if ((rc = map_check_count(m, poses, n_poses, &used))) return rc;
+    const bool inc = L.valid && memcmp(&L.grid, grid, sizeof(*grid)) == 0 && used >= L.n_cast &&
+                     (L.n_cast == 0 || memcmp(poses, L.poses.data(), sizeof(double) * 16 * (size_t)L.n_cast) == 0);
+    const int64_t first = inc ? L.n_cast : 0;
+    if ((rc = map_check_finite(m, poses, first, used))) return rc;
+    if (used > kCountMaxFrames)
+        return fail(ctx, ICPMI_ERR_ARG, "%lld frames would be used: at most %lld", (long long)used, (long long)kCountMaxFrames);
+    RaySpan span;
+    if (inc) span = RaySpan{L.span[0], L.span[1], L.span[2], L.span[3]};
+    std::vector<RayFrame> frames;
+    if ((rc = ray_plan_frames(m, poses, grid->resolution, R, first, used, &span, &frames))) return rc;
+    RayPlane exact{0, 0, 0, 0, 0};
+    if (m->row0[used] > 0 && (rc = ray_plan_plane(ctx, span, R, &exact))) return rc;
+    icpmi_live_info out{};
+    if (inc && used == L.n_cast) {  // nothing new
+        out = L.info;
+        out.frames_cast = 0, out.rebuilt = 0, out.moved = 0;
+        L.info = out;
+        if (info) *info = out;
+        return ICPMI_OK;
+    }
+    LiveBox box = inc ? L.box : LiveBox{exact.x0, exact.y0, exact.w, exact.h};
+    if (inc)
+        for (const RayFrame &f : frames)
+            if (f.rows > 0) box = live_plane_grow(box, live_window(f.sx, f.sy, R));
+    if (box.w > INT32_MAX || box.h > INT32_MAX) return fail(ctx, ICPMI_ERR_ARG, "the live plane would be too wide");
+    out.frames_cast = used - first;
+    out.rebuilt = !inc && L.n_cast > 0;
+    // from here on the remembered state stands only once the call has succeeded
+    L.valid = false;
+    L.info = icpmi_live_info{};
+    CountBounds b = L.bounds;
+    bool moved = false;
+    if (m->row0[used] - m->row0[first] > 0) {
+        std::vector<DevBuf> old;
+        rc = live_cast(m, poses, grid, R, !inc, first, used, frames, box, &moved, old, &b);
+        for (DevBuf &o : old) release(o);
+        if (rc) return rc;
+        L.windows_clean = true;
+    } else if (!inc) {              // no used frame holds a row: no plane
+        L.box = LiveBox{};
+        b = kCountNone;
+    }
+    L.grid = *grid, L.R = R;
+    if (!inc) L.poses.clear();
+    L.poses.insert(L.poses.end(), poses + 16 * first, poses + 16 * used);
+    L.n_cast = used;
+    L.span[0] = span.lo_x, L.span[1] = span.lo_y, L.span[2] = span.hi_x, L.span[3] = span.hi_y;
+    L.bounds = b;
+    L.valid = true;
+    out.moved = moved;
+    live_fill_info(L, used, &out);
+    L.info = out;
+    if (info) *info = out;
+    return ICPMI_OK;
+}
+
+int icpmi_map_live_counts(icpmi_map *m, uint16_t *hits, uint16_t *misses, int8_t *probability, int64_t cap, icpmi_live_info *info)
+{
+    if (!m) return ICPMI_ERR_NULL;
+    icpmi_ctx *ctx = m->ctx;
+    LiveCounts &L = m->live;
+    int rc;
+    if ((rc = check_common(ctx))) return rc;
+    if (info) *info = L.info;
+    if (!hits && !misses && !probability) return ICPMI_OK;
+    const icpmi_counts_info &c = L.info.counts;
+    const int64_t cells = (int64_t)c.width * (int64_t)c.height;
+    if (cap < cells) return fail(ctx, ICPMI_ERR_CAPACITY, "the arrays hold %lld cells, need %lld", (long long)cap, (long long)cells);
+    if (cells == 0) return ICPMI_OK;
+    Range range("icpmi:map_live_counts");
+    hipStream_t s = ctx->stream;
+    const size_t n = (size_t)cells;
+    if ((rc = reserve(ctx, L.d_out, counts_bytes(n)))) return rc;
+    uint16_t *out = (uint16_t *)L.d_out.p;
+    hipLaunchKernelGGL(k_count_raster, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const unsigned *)L.d_plane.p,
+                       live_ray_plane(L.box), L.bounds.min_x - 5, L.bounds.min_y - 5, c.width, c.height, out, out + n,
+                       (int8_t *)(out + 2 * n));
+    HIP_TRY(ctx, hipGetLastError());
+    const char *src = (const char *)L.d_out.p;
+    if (hits) HIP_TRY(ctx, hipMemcpyAsync(hits, src, 2 * n, hipMemcpyDeviceToHost, s));
+    if (misses) HIP_TRY(ctx, hipMemcpyAsync(misses, src + 2 * n, 2 * n, hipMemcpyDeviceToHost, s));
+    if (probability) HIP_TRY(ctx, hipMemcpyAsync(probability, src + 4 * n, n, hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s)); // the call's one wait
+    return ICPMI_OK;
+}
+
+int icpmi_map_live_clear(icpmi_map *m)
+{
+    if (!m) return ICPMI_ERR_NULL;
+    LiveCounts &L = m->live;
+    L.valid = false;
+    L.n_cast = 0;
+    L.poses.clear();
+    L.box = LiveBox{};
+    L.bounds = kCountNone;
+    L.info = icpmi_live_info{};
+    return ICPMI_OK;            // the buffers stay for the next plane
 }
 
 } // extern "C"

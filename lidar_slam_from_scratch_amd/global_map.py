@@ -157,3 +157,32 @@ class GlobalMap:
         g = grid if grid is not None else self.ctx.make_grid_config()
         self.ctx._check(self._lib.icpmi_map_raycast_counts(self._h, pp, P.shape[0], C.byref(g), None))
         return self.counts()
+
+    def live_update(self, poses, grid=None):
+        """The counts kept while the node drives (icpmi_map_live_update): afterwards the handle's live counts are byte
+        for byte what raycast_counts(poses, grid) would build, but only the frames not yet cast are cast, unless a pose
+        already cast or the grid has changed.  grid None: the default OccupancyGridConfig.  Neither counts(), raster()
+        nor the context's cell set is touched.  Returns the capi.LiveInfo."""
+        P, pp = _poses(poses)
+        g = grid if grid is not None else self.ctx.make_grid_config()
+        info = capi.LiveInfo()
+        self.ctx._check(self._lib.icpmi_map_live_update(self._h, pp, P.shape[0], C.byref(g), C.byref(info)))
+        return info
+
+    def live_counts(self):
+        """(OccupancyCounts, capi.LiveInfo) of the last successful live_update (0 x 0 before the first)"""
+        info = capi.LiveInfo()
+        self.ctx._check(self._lib.icpmi_map_live_counts(self._h, None, None, None, 0, C.byref(info)))
+        shape = (info.counts.height, info.counts.width)
+        hits, misses = np.empty(shape, dtype=np.uint16), np.empty(shape, dtype=np.uint16)
+        probability = np.empty(shape, dtype=np.int8)
+        if hits.size:
+            u16 = C.POINTER(C.c_uint16)
+            self.ctx._check(self._lib.icpmi_map_live_counts(self._h, hits.ctypes.data_as(u16), misses.ctypes.data_as(u16),
+                                                            probability.ctypes.data_as(C.POINTER(C.c_int8)), hits.size,
+                                                            C.byref(info)))
+        return OccupancyCounts(info.counts, hits, misses, probability), info
+
+    def live_clear(self):
+        """forget the frames cast so far: the next live_update casts every used frame again"""
+        self.ctx._check(self._lib.icpmi_map_live_clear(self._h))

@@ -35,6 +35,8 @@ class SlamRun:
         self.published_map = None     # ... and voxel_downsample(global map, map_voxel)
         self.raster = None            # ... and, with raycast=True, the free / occupied / unknown raster
         self.counts = None            # ... and, with counts=True, the per-cell hit and miss counts
+        self.live = None              # ... and, with live=True, the counts kept up to date frame by frame
+        self.live_log = []            # ... with (frames_cast, rebuilt) per live_update, in call order
 
 
 def node_loop_config():
@@ -44,13 +46,15 @@ def node_loop_config():
 
 def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, pose_graph_config=None,
              align=None, loop_backend=None, pose_graph=None, global_map=None, grid=None, map_voxel=1.0,
-             loop_on_device=False, raycast=False, counts=False):
+             loop_on_device=False, raycast=False, counts=False, live=False):
     """frames: sequence of N x 3 fp64 clouds (already downsampled).  Returns a SlamRun.  global_map: an object with
     add_frame, recent_clouds and finish (None: no map is built); grid: its occupancy grid config (None: defaults).
     loop_on_device: the detector is loop_closure.StoreLoopClosureDetector over global_map (a global_map.GlobalMap),
     or over a private GlobalMap that keeps every frame; it holds no clouds and gives the same closures.
     raycast: with a global_map, SlamRun.raster = global_map.raycast(poses, grid) after its finish.
-    counts: with a global_map, SlamRun.counts = global_map.raycast_counts(poses, grid) after its finish."""
+    counts: with a global_map, SlamRun.counts = global_map.raycast_counts(poses, grid) after its finish.
+    live: with a global_map, global_map.live_update(poses, grid) after each frame's pose is known and after each
+    optimize, (frames_cast, rebuilt) of each in SlamRun.live_log; SlamRun.live = the live counts on the final poses."""
     if loop_on_device and loop_backend is not None:
         raise ValueError("loop_backend and loop_on_device=True both choose the detector")
     if align is None:
@@ -87,6 +91,11 @@ def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, po
         else:
             pose_graph.add_loop_closure(*args)
 
+    def live_update():                                               # update_occupancy_grid's place, :152
+        if live and global_map is not None:
+            info = global_map.live_update(run.poses, grid)
+            run.live_log.append((info.frames_cast, info.rebuilt))
+
     def optimize(tag):                                               # run_pose_graph_optimization, :177-185
         ok = pose_graph.optimize()
         run.optimizations.append((tag, ok, pose_graph.stats))
@@ -94,11 +103,13 @@ def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, po
             run.poses = [np.asarray(p) for p in pose_graph.get_all_poses()]
             if global_map is not None:                               # rebuild_recent_clouds, :182,187-194
                 run.recent_world.append(global_map.recent_clouds(run.poses))
+        live_update()
 
     add("prior", 0, np.eye(4))                                       # :66
     frames = list(frames)
     prev = np.ascontiguousarray(frames[0], dtype=np.float64)         # :69-72
     keep(prev)                                                       # :71
+    live_update()
     for k in range(1, len(frames)):
         curr = np.ascontiguousarray(frames[k], dtype=np.float64)
         pending = False
@@ -106,6 +117,7 @@ def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, po
         if curr.shape[0] < min_points:                               # :125-130
             run.poses.append(run.poses[-1].copy())
             prev = curr
+            live_update()
             continue
         r = align(curr, prev, max_iterations, tolerance)             # :132-138
         bad = (not r.converged) or r.final_error > 1.0               # :139-140
@@ -113,6 +125,7 @@ def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, po
         run.poses.append(run.poses[-1] @ delta)                      # :142-143
         add("odom", len(run.poses) - 2, len(run.poses) - 1, delta, float(r.final_error))   # :145
         prev = curr                                                  # :151
+        live_update()
         detector.add_frame(kept if loop_on_device else curr, k)      # :159
         if k % 10 == 0 and k > 50:                                   # :160
             for c in detector.detect():                              # :161-166
@@ -128,6 +141,9 @@ def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, po
             run.raster = global_map.raycast(run.poses, grid)
         if counts:
             run.counts = global_map.raycast_counts(run.poses, grid)
+        if live:
+            live_update()
+            run.live = global_map.live_counts()[0]
     if loop_on_device:                                               # the detector (and a private store) go now
         detector.close()
         if global_map is None:

@@ -13,6 +13,8 @@ World points are ((x R_a0 + y R_a1) + z R_a2) + t_a, elementwise in numpy (no fu
 device's bit for bit.  The cell set is the oracle's occupancy_update per frame, the published map its voxel_downsample.
 The interface is GlobalMap's, so an instance can be handed to slam.run_slam as its global_map.
 
+MapRefLive restates icpmi_map_live_update: the decision of what to cast again, and counts that persist.
+
 MapRef.raycast is the normative text of icpmi_map_raycast (include/icp_mi355x.h, csrc/raycast.h): the kept scans
 ray-cast into a free / occupied / unknown raster.  bresenham() restates the device's ray_walk line for line;
 bresenham_lockstep() is the same walk for many rays at once, one step per numpy operation."""
@@ -299,3 +301,90 @@ class MapRef:
         misses[y - lo[1], x - lo[0]] = mn
         return Counts(lo[0], lo[1], width, height, res, int(np.count_nonzero(hits | misses)), len(hk),
                       hits.max(), misses.max(), last, hits, misses, Counts.probability_of(hits, misses))
+
+
+class MapRefLive(MapRef):
+    """icpmi_map_live_update, normatively: the counts kept while frames arrive.  The host's decision is restated as it
+    stands in the library: with used = min(frames, len(poses)), the update is incremental when the grid is bitwise
+    the remembered one, used >= n_cast and the first n_cast poses are bitwise the remembered ones, and then only frames
+    [n_cast, used) are cast; in every other case everything remembered is dropped and frames [0, used) are cast.  A
+    frame's H_i and C_i (raycast_counts' definition) are added into two dictionaries, cell -> count, that persist; since
+    the counts are sums over sets, live_counts() must equal raycast_counts(poses, grid) after every update, which
+    tests/test_live_reference.py asserts.  An input raycast_counts refuses raises ValueError and changes nothing."""
+
+    def __init__(self):
+        super().__init__()
+        self.live_clear()
+
+    def live_clear(self):
+        self._grid, self._cast, self._res = None, [], 0.0       # the grid's and each cast pose's bytes
+        self._hits, self._misses = {}, {}                       # _unique_cells' word per cell -> count
+
+    @staticmethod
+    def _grid_bytes(g):
+        return np.array([g["resolution"], g["height_min"], g["height_max"], g["max_range"]], dtype=np.float64).tobytes()
+
+    def live_update(self, poses, grid=None):
+        """-> (frames_cast, rebuilt), icpmi_live_info's"""
+        g = grid_kwargs(grid)
+        res = g["resolution"]
+        if not (np.isfinite(res) and res > 0.0):
+            raise ValueError("grid resolution must be finite and positive")
+        with np.errstate(all="ignore"):
+            Rd = np.ceil(np.float64(g["max_range"]) / res)
+        if not Rd <= RAYCAST_MAX_R:
+            raise ValueError("max_range / resolution must be at most %d cells" % RAYCAST_MAX_R)
+        R = int(Rd) if Rd > 0 else 0
+        used = min(len(self.clouds), len(poses))
+        P = [np.ascontiguousarray(np.asarray(poses[i], dtype=np.float64).reshape(4, 4)) for i in range(used)]
+        if not all(np.isfinite(T).all() for T in P):
+            raise ValueError("a used pose has a non-finite entry")
+        if used > Counts.MAX_FRAMES:
+            raise ValueError("more than %d frames would be used" % Counts.MAX_FRAMES)
+        sensors = [(np.floor(T[0, 3] / res), np.floor(T[1, 3] / res)) for T in P]
+        if any(abs(c) > 2147483646.0 - R - 6 for s in sensors for c in s):
+            raise ValueError("a used frame's sensor cell is out of range")
+        held = np.array([s for i, s in enumerate(sensors) if self.clouds[i].shape[0]], dtype=np.int64).reshape(-1, 2)
+        if len(held):
+            W, H = (int(v) + 2 * R + 3 for v in held.max(axis=0) - held.min(axis=0))
+            if (W + 10) * (H + 10) > 2**31 - 1:
+                raise ValueError("the used frames span more than 2^31 - 1 cells")
+        # the decision
+        n_cast = len(self._cast)
+        incremental = (self._grid == self._grid_bytes(g) and used >= n_cast
+                       and all(P[i].tobytes() == self._cast[i] for i in range(n_cast)))
+        rebuilt = int(not incremental and n_cast > 0)
+        if not incremental:
+            self.live_clear()
+            n_cast = 0
+        self._grid, self._res = self._grid_bytes(g), res
+        for i in range(n_cast, used):
+            with np.errstate(all="ignore"):
+                world = world_points(self.clouds[i], P[i])
+            H_i = _unique_cells(hit_cells(world, P[i][:2, 3], res, g["height_min"], g["height_max"], g["max_range"]))
+            s = sensors[i]
+            carved = _unique_cells(bresenham_lockstep(int(s[0]), int(s[1]), H_i[:, 0], H_i[:, 1]))
+            hk = H_i[:, 0] * 2**32 + (H_i[:, 1] + 2**31)
+            ck = carved[:, 0] * 2**32 + (carved[:, 1] + 2**31)
+            for k in hk.tolist():
+                self._hits[k] = self._hits.get(k, 0) + 1
+            for k in np.setdiff1d(ck, hk, assume_unique=True).tolist():     # C_i
+                self._misses[k] = self._misses.get(k, 0) + 1
+            self._cast.append(P[i].tobytes())
+        return used - n_cast, rebuilt
+
+    def live_counts(self):
+        """the Counts of the frames cast so far"""
+        last = len(self._cast)
+        keys = np.array(sorted(set(self._hits) | set(self._misses)), dtype=np.int64)
+        if not len(keys):
+            z16 = np.zeros((0, 0), dtype=np.uint16)
+            return Counts(0, 0, 0, 0, self._res, 0, 0, 0, 0, last, z16, z16.copy(), np.zeros((0, 0), dtype=np.int8))
+        x, y = keys >> 32, (keys & (2**32 - 1)) - 2**31
+        lo = np.array([x.min(), y.min()]) - 5
+        width, height = int(x.max()) + 5 - int(lo[0]) + 1, int(y.max()) + 5 - int(lo[1]) + 1
+        hits, misses = np.zeros((height, width), dtype=np.uint16), np.zeros((height, width), dtype=np.uint16)
+        hits[y - lo[1], x - lo[0]] = [self._hits.get(k, 0) for k in keys.tolist()]
+        misses[y - lo[1], x - lo[0]] = [self._misses.get(k, 0) for k in keys.tolist()]
+        return Counts(lo[0], lo[1], width, height, self._res, len(keys), len(self._hits), hits.max(), misses.max(), last,
+                      hits, misses, Counts.probability_of(hits, misses))
