@@ -332,6 +332,17 @@ int icpmi_scan_context(icpmi_ctx *ctx, const double *cloud_xyz, int64_t n, doubl
  * column shifts of 1 - cosine(query, hist_descs + 1200 * i). */
 int icpmi_scan_context_distances(icpmi_ctx *ctx, const double *query_desc, const double *hist_descs,
                                  int64_t count, double *dist_out);
+/* The same call with the argmin kept (not in the reference, which drops it at scan_context.hpp:94-99): dist_out is
+ * icpmi_scan_context_distances' bit for bit, shift_out[i] in 0..59 the SMALLEST column shift that attains dist_out[i]
+ * (the reference's loop runs upward with a strict <).  query[ring][j] was compared with hist[ring][(j + shift) % 60],
+ * so the shift is the yaw between the two scans to within half a sector.  Where a per-shift distance is NaN the shift
+ * is some value in 0..59. */
+int icpmi_scan_context_distances_shift(icpmi_ctx *ctx, const double *query_desc, const double *hist_descs,
+                                       int64_t count, double *dist_out, int32_t *shift_out);
+/* The initial transform a loop-closure verification takes from that shift, query = source, candidate = target:
+ * row-major Rz(shift * (2.0 * M_PI / 60)) by the C library's cos and sin; shift 0 is the exact identity.  A shift
+ * outside 0..59 is ICPMI_ERR_ARG.  Host only: no context, no device.  The one definition of the guess. */
+int icpmi_sc_shift_transform(int32_t shift, double T[16]);
 
 /* Multi-GPU (new; the reference has no distributed path).  One process per GPU.  Rank 0
  * obtains an id, the host distributes it (e.g. torch.distributed broadcast), every rank
@@ -638,6 +649,16 @@ int icpmi_map_live_clear(icpmi_map *map);
  *                             returns it.
  *   icpmi_loop_descriptor     entry's 20 x 60 descriptor (row-major) into desc_out; forms any pending ones first.
  *   icpmi_loop_clear          drops every entry; the store is untouched.
+ *   icpmi_loop_set_yaw_guess  on != 0 (off at creation; not in the reference): detect keeps the column shift that
+ *                             attained each candidate's distance (icpmi_scan_context_distances_shift) and starts its
+ *                             verification from icpmi_sc_shift_transform(shift) instead of from the identity, so a
+ *                             place revisited with another heading verifies.  Candidates, their order (distance, then
+ *                             entry; the shift never enters it) and the distances are unchanged; the result's
+ *                             transform is the registration's, which includes the start.  Entries and descriptors
+ *                             are untouched; takes effect at the next detect.
+ *   icpmi_loop_last_shifts    the shifts the last detect's results started from, in result order: *n_out = the number
+ *                             of results (shifts may be NULL with cap 0; a cap below it is ICPMI_ERR_CAPACITY); each is
+ *                             -1 when that detect ran with the guess off.
  * A store frame or an entry out of range is ICPMI_ERR_ARG and changes nothing.  The handle uses its map's context and
  * stream: destroy it before its map, and the map before the context. */
 typedef struct icpmi_loop icpmi_loop;
@@ -661,6 +682,8 @@ int icpmi_loop_detect(icpmi_loop *loop, icpmi_loop_result *out, int64_t cap, int
 int icpmi_loop_descriptor(icpmi_loop *loop, int64_t entry, double *desc_out /* 1200 */);
 int icpmi_loop_size(const icpmi_loop *loop, int64_t *entries);
 int icpmi_loop_clear(icpmi_loop *loop);
+int icpmi_loop_set_yaw_guess(icpmi_loop *loop, int32_t on);
+int icpmi_loop_last_shifts(const icpmi_loop *loop, int32_t *shifts, int64_t cap, int64_t *n_out);
 
 /* profiling */
 int icpmi_reset_profile(icpmi_ctx *ctx);

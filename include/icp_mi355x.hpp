@@ -228,12 +228,16 @@ inline ICPResult icp_point_to_plane(Context &ctx, const double *source_xyz, std:
 
 // Several independent registrations of one source at once (icpmi_align_batch): what the verifications of one
 // LoopClosureDetector::detect() are (loop_closure.hpp:94-123).  Each result is that of icp_point_to_plane alone.
+// initial_transforms: empty (config's for every target), or one per target (each verification its own start).
 inline std::vector<ICPResult> icp_point_to_plane_batch(Context &ctx, const PointCloud &source,
-                                                       const std::vector<const PointCloud *> &targets, const ICPConfig &config)
+                                                       const std::vector<const PointCloud *> &targets, const ICPConfig &config,
+                                                       const std::vector<Transformation> &initial_transforms = {})
 {
     const std::size_t k = targets.size();
     std::vector<ICPResult> out(k);
     if (k == 0) return out;
+    if (!initial_transforms.empty() && initial_transforms.size() != k)
+        throw IcpError(ICPMI_ERR_ARG, "as many initial transforms as targets, or none");
     std::vector<const double *> sp(k, source.data()), tp(k);
     std::vector<int64_t> ns(k, static_cast<int64_t>(source.size())), nt(k);
     for (std::size_t i = 0; i < k; ++i) {
@@ -241,6 +245,8 @@ inline std::vector<ICPResult> icp_point_to_plane_batch(Context &ctx, const Point
         nt[i] = static_cast<int64_t>(targets[i]->size());
     }
     std::vector<icpmi_config> cfgs(k, detail::to_c(config));
+    for (std::size_t i = 0; i < initial_transforms.size(); ++i)
+        for (int e = 0; e < 16; ++e) cfgs[i].initial_transform[e] = initial_transforms[i].matrix()[static_cast<std::size_t>(e)];
     const std::size_t stride = static_cast<std::size_t>(config.max_iterations > 0 ? config.max_iterations : 0) + 1;
     std::vector<double> hist(k * stride);
     std::vector<icpmi_result> res(k);
@@ -565,12 +571,26 @@ struct LoopClosureConfig { // loop_closure.hpp:14-19
     double sc_distance_threshold = 0.25;
     double icp_fitness_threshold = 0.3;
     int max_candidates = 3;
+    // Not in the reference: keep the column shift that attained each candidate's distance and start its verification
+    // from Rz(shift * 6 deg) (icpmi_sc_shift_transform) instead of from the identity, so that a place revisited with
+    // another heading closes too.  Off: the reference's behaviour.
+    bool yaw_guess = false;
 };
 struct LoopClosureResult { // loop_closure.hpp:25-31
     int query_frame = 0, match_frame = 0;
     Transformation transform;
     double scan_context_distance = 0.0, icp_fitness = 0.0;
+    int sector_shift = -1; // the shift the verification started from (-1: yaw_guess off)
 };
+
+// icpmi_sc_shift_transform: the start of a verification whose candidate matched at column shift `shift` (0..59).
+inline Transformation sc_shift_transform(int shift)
+{
+    std::array<double, 16> m;
+    const int rc = icpmi_sc_shift_transform(shift, m.data());
+    if (rc != ICPMI_OK) throw IcpError(rc, "shift outside 0..59");
+    return Transformation(m);
+}
 
 // slam::LoopClosureDetector (loop_closure.hpp:41-148): keeps every frame's cloud and descriptor, and
 // detect() looks for closures of the most recently added frame -- the distances of its descriptor to the
@@ -603,8 +623,12 @@ public:
         constexpr std::size_t kDesc = static_cast<std::size_t>(ScanContext::kRings) * ScanContext::kSectors;
         const std::size_t q = frame_indices_.size() - 1;
         std::vector<double> dist(q);
-        const int rc = icpmi_scan_context_distances(ctx_->get(), descriptors_.data() + q * kDesc, descriptors_.data(),
-                                                    static_cast<int64_t>(q), dist.data()); // :84 for every i
+        std::vector<int32_t> shift(config_.yaw_guess ? q : 0);
+        const int rc = config_.yaw_guess
+                           ? icpmi_scan_context_distances_shift(ctx_->get(), descriptors_.data() + q * kDesc, descriptors_.data(),
+                                                                static_cast<int64_t>(q), dist.data(), shift.data())
+                           : icpmi_scan_context_distances(ctx_->get(), descriptors_.data() + q * kDesc, descriptors_.data(),
+                                                          static_cast<int64_t>(q), dist.data()); // :84 for every i
         if (rc != ICPMI_OK) throw IcpError(rc, icpmi_last_error(ctx_->get()));
         std::vector<std::pair<double, int>> candidates;
         for (std::size_t i = 0; i < q; ++i) {
@@ -624,8 +648,13 @@ public:
             const std::size_t take = std::min<std::size_t>(candidates.size() - pos,
                                                            std::min<std::size_t>(static_cast<std::size_t>(config_.max_candidates - verified), ICPMI_MAX_BATCH));
             std::vector<const PointCloud *> tg;
-            for (std::size_t i = 0; i < take; ++i) tg.push_back(&clouds_[static_cast<std::size_t>(candidates[pos + i].second)]);
-            const std::vector<ICPResult> rs = icp_point_to_plane_batch(*ctx_, clouds_[q], tg, icp); // :109
+            std::vector<Transformation> starts; // (the shift rides along: it never entered the order)
+            for (std::size_t i = 0; i < take; ++i) {
+                const std::size_t c = static_cast<std::size_t>(candidates[pos + i].second);
+                tg.push_back(&clouds_[c]);
+                if (config_.yaw_guess) starts.push_back(sc_shift_transform(shift[c]));
+            }
+            const std::vector<ICPResult> rs = icp_point_to_plane_batch(*ctx_, clouds_[q], tg, icp, starts); // :109
             for (std::size_t i = 0; i < take; ++i) {
                 const ICPResult &r = rs[i];
                 const auto &cand = candidates[pos + i];
@@ -636,6 +665,7 @@ public:
                     out.transform = r.transformation;
                     out.scan_context_distance = cand.first;
                     out.icp_fitness = r.final_error;
+                    if (config_.yaw_guess) out.sector_shift = shift[static_cast<std::size_t>(cand.second)];
                     results.push_back(out);
                     ++verified;
                 }
@@ -1013,6 +1043,7 @@ public:
         c.sc_distance_threshold = config.sc_distance_threshold;
         c.icp_fitness_threshold = config.icp_fitness_threshold;
         check(icpmi_loop_create(map.get(), &c, &l_));
+        if (config.yaw_guess) check(icpmi_loop_set_yaw_guess(l_, 1));
     }
     ~StoreLoopClosureDetector() { icpmi_loop_destroy(l_); }
     StoreLoopClosureDetector(const StoreLoopClosureDetector &) = delete;
@@ -1039,10 +1070,14 @@ public:
         std::vector<icpmi_loop_result> buf(static_cast<std::size_t>(std::max(config_.max_candidates, 1)));
         int64_t n = 0;
         check(icpmi_loop_detect(l_, buf.data(), static_cast<int64_t>(std::max(config_.max_candidates, 0)), &n));
+        std::vector<int32_t> shifts(static_cast<std::size_t>(std::max<int64_t>(n, 1)), -1);
+        int64_t ns = 0;
+        check(icpmi_loop_last_shifts(l_, shifts.data(), n, &ns)); // -1 each with the guess off
         std::vector<LoopClosureResult> out;
         for (int64_t i = 0; i < n; ++i) {
             const icpmi_loop_result &r = buf[static_cast<std::size_t>(i)];
             LoopClosureResult o;
+            o.sector_shift = shifts[static_cast<std::size_t>(i)];
             o.query_frame = r.query_frame;
             o.match_frame = r.match_frame;
             std::array<double, 16> m;

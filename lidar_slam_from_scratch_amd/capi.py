@@ -38,6 +38,7 @@ EXPORTS = [
     "icpmi_map_live_update", "icpmi_map_live_counts", "icpmi_map_live_clear",
     "icpmi_loop_config_default", "icpmi_loop_create", "icpmi_loop_destroy", "icpmi_loop_add_frame", "icpmi_loop_detect",
     "icpmi_loop_descriptor", "icpmi_loop_size", "icpmi_loop_clear",
+    "icpmi_scan_context_distances_shift", "icpmi_sc_shift_transform", "icpmi_loop_set_yaw_guess", "icpmi_loop_last_shifts",
 ]
 
 
@@ -267,6 +268,8 @@ def load_library(path=None):
     L.icpmi_stream_current_scan.argtypes = [vp, dp, C.c_int64, i64p]
     L.icpmi_scan_context.argtypes = [vp, dp, C.c_int64, dp]
     L.icpmi_scan_context_distances.argtypes = [vp, dp, dp, C.c_int64, dp]
+    L.icpmi_scan_context_distances_shift.argtypes = [vp, dp, dp, C.c_int64, dp, C.POINTER(C.c_int32)]
+    L.icpmi_sc_shift_transform.argtypes = [C.c_int32, dp]
     L.icpmi_comm_unique_id.argtypes = [vp, vp]
     L.icpmi_comm_init.argtypes = [vp, C.c_int32, C.c_int32, vp]
     L.icpmi_comm_finalize.argtypes = [vp]
@@ -315,6 +318,8 @@ def load_library(path=None):
     L.icpmi_loop_descriptor.argtypes = [vp, C.c_int64, dp]
     L.icpmi_loop_size.argtypes = [vp, i64p]
     L.icpmi_loop_clear.argtypes = [vp]
+    L.icpmi_loop_set_yaw_guess.argtypes = [vp, C.c_int32]
+    L.icpmi_loop_last_shifts.argtypes = [vp, C.POINTER(C.c_int32), C.c_int64, i64p]
     for name in EXPORTS:
         getattr(L, name)  # raises AttributeError if a declared symbol is not exported
     _LIB = L
@@ -643,6 +648,15 @@ class Context:
         out = np.empty(h.shape[0])
         self._check(self._lib.icpmi_scan_context_distances(self._h, _dp(q), _dp(h), h.shape[0], _dp(out)))
         return out
+
+    def scan_context_distances_shift(self, query_desc, hist_descs):
+        """scan_context_distances and, per descriptor, the smallest column shift that attains its distance (int32)"""
+        q = np.ascontiguousarray(query_desc, dtype=np.float64).reshape(1200)
+        h = np.ascontiguousarray(hist_descs, dtype=np.float64).reshape(-1, 1200)
+        out, shift = np.empty(h.shape[0]), np.empty(h.shape[0], dtype=np.int32)
+        self._check(self._lib.icpmi_scan_context_distances_shift(self._h, _dp(q), _dp(h), h.shape[0], _dp(out),
+                                                                 shift.ctypes.data_as(C.POINTER(C.c_int32))))
+        return out, shift
 
     # multi-GPU
     def comm_unique_id(self):

@@ -2991,6 +2991,46 @@ int icpmi_scan_context_distances(icpmi_ctx *ctx, const double *query_desc, const
     return ICPMI_OK;
 }
 
+int icpmi_scan_context_distances_shift(icpmi_ctx *ctx, const double *query_desc, const double *hist_descs,
+                                       int64_t count, double *dist_out, int32_t *shift_out)
+{
+    int rc;
+    if ((rc = check_common(ctx))) return rc;
+    if (!query_desc || (count > 0 && (!hist_descs || !dist_out || !shift_out))) return fail(ctx, ICPMI_ERR_NULL, "null argument");
+    if (count < 0 || count > 100000000) return fail(ctx, ICPMI_ERR_ARG, "count out of range");
+    if (count == 0) return ICPMI_OK;
+    const size_t hb = sizeof(double) * kScCells * (size_t)count;
+    if ((rc = reserve(ctx, ctx->stage_a, hb))) return rc;
+    if ((rc = reserve(ctx, ctx->stage_b, sizeof(double) * kScCells))) return rc;
+    if ((rc = reserve(ctx, ctx->vox_out, (sizeof(double) + sizeof(int32_t)) * (size_t)count))) return rc;
+    double *d_dist = (double *)ctx->vox_out.p;
+    int32_t *d_shift = (int32_t *)(d_dist + count);
+    hipStream_t s = ctx->stream;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->stage_a.p, hist_descs, hb, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->stage_b.p, query_desc, sizeof(double) * kScCells, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_sc_distances_shift, dim3((unsigned)count), dim3(64), 0, s, (const double *)ctx->stage_b.p,
+                       (const double *)ctx->stage_a.p, (int)count, d_dist, d_shift);
+    HIP_TRY(ctx, hipMemcpyAsync(dist_out, d_dist, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipMemcpyAsync(shift_out, d_shift, sizeof(int32_t) * (size_t)count, hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    HIP_TRY(ctx, hipGetLastError());
+    return ICPMI_OK;
+}
+
+int icpmi_sc_shift_transform(int32_t shift, double T[16])
+{
+    if (!T) return ICPMI_ERR_NULL;
+    if (shift < 0 || shift >= kScSectors) return ICPMI_ERR_ARG;
+    const double angle = shift * (2.0 * M_PI / 60);
+    const double c = cos(angle), s = sin(angle);
+    for (int i = 0; i < 16; ++i) T[i] = (i % 5 == 0) ? 1.0 : 0.0;
+    T[0] = c;
+    T[1] = 0.0 - s; // (+0 at shift 0: the exact identity)
+    T[4] = s;
+    T[5] = c;
+    return ICPMI_OK;
+}
+
 int icpmi_comm_unique_id(icpmi_ctx *ctx, void *id_out)
 {
     int rc;
@@ -4589,7 +4629,9 @@ int icpmi_map_live_clear(icpmi_map *m)
 // ======================================================================================================================
 // Loop-closure detection over the store (core/loop_closure.hpp:41-148; loop_store.h): the entries' descriptors and
 // labels in device memory, the rows in the map's arena.  Per detect: one upload of the pending entries' (row0, rows,
-// label), k_loop_describe for them, k_loop_candidates, one wait; then the candidates' verifications.
+// label), k_loop_describe for them, k_loop_candidates, one wait; then the candidates' verifications.  With the yaw
+// guess on (icpmi_loop_set_yaw_guess) the candidate pass is k_loop_candidates_shift and each verification starts from
+// its candidate's icpmi_sc_shift_transform.
 
 struct icpmi_loop {
     icpmi_map *map = nullptr;
@@ -4605,6 +4647,8 @@ struct icpmi_loop {
     std::vector<int32_t> labels;         // per entry its label
     int64_t described = 0;               // entries [0, described) have their descriptor on the device
     std::vector<LoopJob> jobs;
+    bool yaw_guess = false;              // icpmi_loop_set_yaw_guess
+    std::vector<int32_t> last_shifts;    // per result of the last detect its shift (-1: the guess was off)
 };
 
 namespace {
@@ -4783,6 +4827,8 @@ int icpmi_loop_detect(icpmi_loop *L, icpmi_loop_result *out, int64_t cap, int64_
     if (!n_out || (!out && cap > 0)) return fail(ctx, ICPMI_ERR_NULL, "null argument");
     if (ctx->comm || ctx->cb_allreduce) return fail(ctx, ICPMI_ERR_ARG, "a context with a communicator registers one (sharded) problem at a time");
     *n_out = 0;
+    L->last_shifts.clear();
+    const bool guess = L->yaw_guess;
     const int64_t E = (int64_t)L->frames.size();
     if (E < 2) return ICPMI_OK; // :69
     Range range("icpmi:loop_detect");
@@ -4811,9 +4857,14 @@ int icpmi_loop_detect(icpmi_loop *L, icpmi_loop_result *out, int64_t cap, int64_
     }
     if (rc == ICPMI_OK) {
         *L->h_count = -1;
-        hipLaunchKernelGGL(k_loop_candidates, dim3((unsigned)q), dim3(64), 0, s, (const double *)L->d_desc.p,
-                           (const int32_t *)L->d_labels.p, (int32_t)q, L->cfg.frame_gap, L->cfg.sc_distance_threshold,
-                           (unsigned *)L->d_counters.p, d_cand, d_count);
+        if (guess)
+            hipLaunchKernelGGL(k_loop_candidates_shift, dim3((unsigned)q), dim3(64), 0, s, (const double *)L->d_desc.p,
+                               (const int32_t *)L->d_labels.p, (int32_t)q, L->cfg.frame_gap, L->cfg.sc_distance_threshold,
+                               (unsigned *)L->d_counters.p, (LoopCandidateShift *)d_cand, d_count);
+        else
+            hipLaunchKernelGGL(k_loop_candidates, dim3((unsigned)q), dim3(64), 0, s, (const double *)L->d_desc.p,
+                               (const int32_t *)L->d_labels.p, (int32_t)q, L->cfg.frame_gap, L->cfg.sc_distance_threshold,
+                               (unsigned *)L->d_counters.p, d_cand, d_count);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) rc = fail(ctx, ICPMI_ERR_HIP, "k_loop_candidates: %s", hipGetErrorString(e));
     }
@@ -4822,7 +4873,19 @@ int icpmi_loop_detect(icpmi_loop *L, icpmi_loop_result *out, int64_t cap, int64_
     if (nc < 0 || nc > q) return fail(ctx, ICPMI_ERR_HIP, "k_loop_candidates returned %lld candidates of %lld", (long long)nc, (long long)q);
     std::vector<std::pair<double, int>> candidates;
     candidates.reserve((size_t)nc);
-    for (int64_t i = 0; i < nc; ++i) candidates.emplace_back(L->h_cand[i].dist, (int)L->h_cand[i].entry);
+    std::vector<int32_t> shift_of; // per entry its shift (guess only): it rides along and never enters the order
+    if (guess) {
+        shift_of.assign((size_t)q, 0);
+        const LoopCandidateShift *h = (const LoopCandidateShift *)L->h_cand;
+        for (int64_t i = 0; i < nc; ++i) {
+            if (h[i].entry < 0 || h[i].entry >= q || h[i].shift < 0 || h[i].shift >= kScSectors)
+                return fail(ctx, ICPMI_ERR_HIP, "k_loop_candidates_shift returned entry %d, shift %d", h[i].entry, h[i].shift);
+            candidates.emplace_back(h[i].dist, (int)h[i].entry);
+            shift_of[(size_t)h[i].entry] = h[i].shift;
+        }
+    } else {
+        for (int64_t i = 0; i < nc; ++i) candidates.emplace_back(L->h_cand[i].dist, (int)L->h_cand[i].entry);
+    }
     std::sort(candidates.begin(), candidates.end()); // :93
 
     // :96-123: verify in order until max_candidates are accepted; the next min(max_candidates - accepted,
@@ -4844,14 +4907,20 @@ int icpmi_loop_detect(icpmi_loop *L, icpmi_loop_result *out, int64_t cap, int64_
         icpmi_result res[ICPMI_MAX_BATCH];
         int32_t status[ICPMI_MAX_BATCH];
         std::vector<double> hist((size_t)take * (size_t)hcap);
+        icpmi_config icps[ICPMI_MAX_BATCH]; // every problem its own start
+        for (int32_t k = 0; k < take; ++k) {
+            icps[k] = icp;
+            if (guess && (rc = icpmi_sc_shift_transform(shift_of[(size_t)candidates[pos + (size_t)k].second], icps[k].initial_transform)))
+                return fail(ctx, rc, "internal: shift out of range");
+        }
         rc = batch_run(ctx, take, [&](icpmi_ctx *c, int k) {
             const int64_t f = L->frames[(size_t)candidates[pos + (size_t)k].second];
             const int64_t t0 = L->map->row0[(size_t)f], nt = L->map->row0[(size_t)f + 1] - t0;
             // (only the sizes are checked: the rows are the store's, non-null even for a frame of 0 rows)
-            int r = validate_align(c, &icp, nq, &icp, nt, &icp, &res[k], hist.data() + (size_t)k * hcap, hcap);
+            int r = validate_align(c, &icp, nq, &icp, nt, &icps[k], &res[k], hist.data() + (size_t)k * hcap, hcap);
             if (r == ICPMI_OK) r = check_common(c);
             if (r == ICPMI_OK)
-                r = align_staged(c, rows + 3 * (size_t)q0, nq, rows + 3 * (size_t)t0, nt, hipMemcpyDeviceToDevice, &icp,
+                r = align_staged(c, rows + 3 * (size_t)q0, nq, rows + 3 * (size_t)t0, nt, hipMemcpyDeviceToDevice, &icps[k],
                                  &res[k], hist.data() + (size_t)k * hcap, hcap);
             return r;
         }, status);
@@ -4867,6 +4936,7 @@ int icpmi_loop_detect(icpmi_loop *L, icpmi_loop_result *out, int64_t cap, int64_
                 o.scan_context_distance = cand.first;
                 o.icp_fitness = r.final_error;
                 results.push_back(o);
+                L->last_shifts.push_back(guess ? shift_of[(size_t)cand.second] : -1);
                 ++verified;
             }
         }
@@ -4876,6 +4946,25 @@ int icpmi_loop_detect(icpmi_loop *L, icpmi_loop_result *out, int64_t cap, int64_
     if ((int64_t)results.size() > cap)
         return fail(ctx, ICPMI_ERR_CAPACITY, "output holds %lld results, needs %lld", (long long)cap, (long long)results.size());
     if (!results.empty()) memcpy(out, results.data(), sizeof(icpmi_loop_result) * results.size());
+    return ICPMI_OK;
+}
+
+int icpmi_loop_set_yaw_guess(icpmi_loop *L, int32_t on)
+{
+    if (!L) return ICPMI_ERR_NULL;
+    L->yaw_guess = on != 0;
+    return ICPMI_OK;
+}
+
+int icpmi_loop_last_shifts(const icpmi_loop *L, int32_t *shifts, int64_t cap, int64_t *n_out)
+{
+    if (!L) return ICPMI_ERR_NULL;
+    icpmi_ctx *ctx = L->map->ctx;
+    if (!n_out || (!shifts && cap > 0)) return fail(ctx, ICPMI_ERR_NULL, "null argument");
+    const int64_t n = (int64_t)L->last_shifts.size();
+    *n_out = n;
+    if (n > cap) return fail(ctx, ICPMI_ERR_CAPACITY, "output holds %lld shifts, needs %lld", (long long)cap, (long long)n);
+    if (n) memcpy(shifts, L->last_shifts.data(), sizeof(int32_t) * (size_t)n);
     return ICPMI_OK;
 }
 

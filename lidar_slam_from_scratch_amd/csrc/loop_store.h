@@ -10,6 +10,8 @@
 //                      append (distance, entry) to a host-mapped list; the last workgroup to finish writes the
 //                      list's length there too and rearms the counters, so the host waits once and reads only the
 //                      candidates.
+//   k_loop_candidates_shift  the same pass with sc_distance_shift: each record also carries the smallest column shift
+//                      that attains its distance, from which the candidate's verification starts (yaw guess, capi.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -30,6 +32,14 @@ struct LoopCandidate {
     int64_t entry;
 };
 static_assert(sizeof(LoopCandidate) == 16, "the host reads the list as it is");
+
+// k_loop_candidates_shift's record: as wide as LoopCandidate (one host list serves both), the shift beside the entry
+struct LoopCandidateShift {
+    double dist;
+    int32_t entry;
+    int32_t shift; // 0..59
+};
+static_assert(sizeof(LoopCandidateShift) == sizeof(LoopCandidate), "the host list holds either record");
 
 // grid = pending entries, entry0 + blockIdx.x being the entry each describes
 __global__ __launch_bounds__(1024) void k_loop_describe(const double *__restrict__ store, const LoopJob *__restrict__ jobs,
@@ -55,6 +65,33 @@ __global__ __launch_bounds__(64) void k_loop_candidates(const double *__restrict
         if (threadIdx.x == 0 && dist < threshold) { // strict; NaN never passes
             const unsigned slot = atomicAdd(&counters[0], 1u);
             out[slot] = LoopCandidate{dist, (int64_t)d};
+        }
+    }
+    if (threadIdx.x == 0) {
+        __threadfence();
+        if (atomicAdd(&counters[1], 1u) == gridDim.x - 1) { // the last workgroup: every append is in
+            __threadfence();
+            *out_n = (int64_t)atomicAdd(&counters[0], 0u);
+            counters[0] = 0;
+            counters[1] = 0;
+        }
+    }
+}
+
+// k_loop_candidates with the argmin kept: same launch, same counters, same order of events; out holds
+// LoopCandidateShift records.
+__global__ __launch_bounds__(64) void k_loop_candidates_shift(const double *__restrict__ table, const int32_t *__restrict__ labels,
+                                                              int32_t q, int32_t frame_gap, double threshold,
+                                                              unsigned *__restrict__ counters, LoopCandidateShift *out,
+                                                              int64_t *out_n)
+{
+    const int32_t d = blockIdx.x;
+    if ((int64_t)labels[q] - (int64_t)labels[d] >= (int64_t)frame_gap) {
+        int shift;
+        const double dist = sc_distance_shift(table + (size_t)q * kScCells, table + (size_t)d * kScCells, shift);
+        if (threadIdx.x == 0 && dist < threshold) { // strict; NaN never passes
+            const unsigned slot = atomicAdd(&counters[0], 1u);
+            out[slot] = LoopCandidateShift{dist, d, shift};
         }
     }
     if (threadIdx.x == 0) {

@@ -4,6 +4,9 @@
 //   k_scan_context      scan_context.hpp:44-82   20 rings x 60 sectors, max height per bin
 //   k_sc_distances      scan_context.hpp:90-142  one query against a history of descriptors,
 //                                                min over the 60 column shifts of 1 - cosine
+//   k_sc_distances_shift                         the same distance and the smallest shift that attains it (the yaw
+//                                                between the two scans to half a sector; not in the reference, which
+//                                                drops the argmin at :94-99)
 //
 // The max per bin is order independent, so an LDS 64-bit atomic max on an order-preserving
 // integer image of the double gives the reference's result bit for bit (up to atan2's last
@@ -109,6 +112,66 @@ __global__ __launch_bounds__(64) void k_sc_distances(const double *__restrict__ 
     if (d >= count) return;
     const double dist = sc_distance(query, hist + (size_t)d * kScCells);
     if (threadIdx.x == 0) out[d] = dist;
+}
+
+// sc_distance that keeps the argmin: every lane returns the same min over the shifts, bit for bit, and in `shift` the
+// SMALLEST shift that attains it (scan_context.hpp:94-99 runs upward with a strict <).  The per-lane sums restate
+// sc_distance's, in its order, and are not shared with it: k_sc_distances and k_loop_candidates keep their code.  The
+// reduction is sc_distance's butterfly with the shift riding along, one more 32-bit exchange per step; the distance's
+// own update is unchanged, so with a NaN among the per-shift distances the value is still what sc_distance returns
+// (the shift is then some lane's, 0..59).  Lanes 60-63 enter as the reference's loop starts, (DBL_MAX, no shift
+// chosen: 0): no shift's distance equals DBL_MAX, so they never win a tie against one.
+__device__ __forceinline__ double sc_distance_shift(const double *__restrict__ query, const double *__restrict__ other,
+                                                    int &shift_out)
+{
+    __shared__ double a[kScCells], b[kScCells];
+    for (int e = threadIdx.x; e < kScCells; e += 64) {
+        a[e] = query[e];
+        b[e] = other[e];
+    }
+    __syncthreads();
+    const int lane = threadIdx.x;
+    double dist = 1.7976931348623157e308; // scan_context.hpp:91
+    int shift = 0;
+    if (lane < kScSectors) {
+        shift = lane;
+        double sum_ab = 0.0, sum_aa = 0.0, sum_bb = 0.0; // :122-124
+        for (int i = 0; i < kScRings; ++i)
+            for (int j = 0; j < kScSectors; ++j) {
+                int js = j + lane;
+                js = js >= kScSectors ? js - kScSectors : js;
+                const double va = a[i * kScSectors + j], vb = b[i * kScSectors + js];
+                sum_ab += va * vb;
+                sum_aa += va * va;
+                sum_bb += vb * vb;
+            }
+        const double norm = __dsqrt_rn(sum_aa) * __dsqrt_rn(sum_bb); // :137
+        dist = norm < 1e-10 ? 1.0 : 1.0 - sum_ab / norm;            // :138-141
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const double o = __shfl_xor(dist, off, 64);
+        const int os = __shfl_xor(shift, off, 64);
+        shift = (o < dist || (o == dist && os < shift)) ? os : shift;
+        dist = o < dist ? o : dist;
+    }
+    shift_out = shift;
+    return dist;
+}
+
+// grid = history size, 64 threads
+__global__ __launch_bounds__(64) void k_sc_distances_shift(const double *__restrict__ query,
+                                                           const double *__restrict__ hist, int count,
+                                                           double *__restrict__ out, int32_t *__restrict__ shift_out)
+{
+    const int d = blockIdx.x;
+    if (d >= count) return;
+    int shift;
+    const double dist = sc_distance_shift(query, hist + (size_t)d * kScCells, shift);
+    if (threadIdx.x == 0) {
+        out[d] = dist;
+        shift_out[d] = shift;
+    }
 }
 
 } // namespace icpmi

@@ -7,6 +7,13 @@ with the arithmetic behind a small backend object:
     backend.distances(query_desc, hist_descs) -> array            scan_context.hpp:90-142
     backend.align(source, target, max_iterations, tolerance)      icp.hpp:157-258
 `GpuBackend` goes through the C ABI; the parity tests plug the oracle in instead.
+
+LoopClosureConfig(yaw_guess=True) (not in the reference) keeps the column shift that attained each
+candidate's distance and starts its verification from Rz(shift * 6 deg) (icpmi_sc_shift_transform) instead of from the
+identity, so a place revisited with another heading closes too.  The backend then also needs
+    backend.distances_shift(query_desc, hist_descs) -> (distances, shifts)
+and align / align_many that take keyword-only initial_transform / initial_transforms; with the option off neither is
+touched, so a backend with the four-argument align keeps working.
 """
 import ctypes as C
 import weakref
@@ -19,7 +26,9 @@ MAX_BATCH = 8   # ICPMI_MAX_BATCH (include/icp_mi355x.h): registrations one icpm
 class LoopClosureConfig:
     """loop_closure.hpp:14-19"""
 
-    def __init__(self, frame_gap=50, sc_distance_threshold=0.25, icp_fitness_threshold=0.3, max_candidates=3):
+    def __init__(self, frame_gap=50, sc_distance_threshold=0.25, icp_fitness_threshold=0.3, max_candidates=3,
+                 yaw_guess=False):
+        self.yaw_guess = yaw_guess
         self.frame_gap = frame_gap
         self.sc_distance_threshold = sc_distance_threshold
         self.icp_fitness_threshold = icp_fitness_threshold
@@ -27,9 +36,10 @@ class LoopClosureConfig:
 
 
 class LoopClosureResult:
-    """loop_closure.hpp:25-31"""
+    """loop_closure.hpp:25-31; sector_shift: the column shift the verification started from (None: yaw_guess off)"""
 
-    def __init__(self, query_frame, match_frame, transform, scan_context_distance, icp_fitness):
+    def __init__(self, query_frame, match_frame, transform, scan_context_distance, icp_fitness, sector_shift=None):
+        self.sector_shift = sector_shift
         self.query_frame = query_frame
         self.match_frame = match_frame
         self.transform = transform
@@ -47,19 +57,28 @@ class GpuBackend:
     def distances(self, query_desc, hist_descs):
         return self.ctx.scan_context_distances(query_desc, hist_descs)
 
-    def align(self, source, target, max_iterations, tolerance):
-        from .odometry import gpu_align
-        return gpu_align(self.ctx)(source, target, max_iterations, tolerance)
+    def distances_shift(self, query_desc, hist_descs):
+        """-> (distances, the smallest column shift attaining each), icpmi_scan_context_distances_shift"""
+        return self.ctx.scan_context_distances_shift(query_desc, hist_descs)
 
-    def align_many(self, source, targets, max_iterations, tolerance):
+    def align(self, source, target, max_iterations, tolerance, *, initial_transform=None):
+        if initial_transform is None:
+            from .odometry import gpu_align
+            return gpu_align(self.ctx)(source, target, max_iterations, tolerance)
+        return self.align_many(source, [target], max_iterations, tolerance, initial_transforms=[initial_transform])[0]
+
+    def align_many(self, source, targets, max_iterations, tolerance, *, initial_transforms=None):
         """The verifications of one detect() side by side on the GPU (icpmi_align_batch): same results as
-        align() one after the other."""
+        align() one after the other.  initial_transforms: one 4 x 4 per target (None: the identity for all)."""
         from . import capi
 
         class _R:
             pass
 
         cfg = capi.Context.make_config(max_iterations=max_iterations, tolerance=tolerance)
+        if initial_transforms is not None:
+            cfg = [capi.Context.make_config(max_iterations=max_iterations, tolerance=tolerance, initial_transform=T)
+                   for T in initial_transforms]
         out = []
         for res, _hist in self.ctx.align_batch([source] * len(targets), targets, cfg):
             r = _R()
@@ -67,6 +86,16 @@ class GpuBackend:
             r.converged, r.final_error, r.num_iterations = bool(res.converged), res.final_error, res.num_iterations
             out.append(r)
         return out
+
+
+def sc_shift_transform(shift):
+    """icpmi_sc_shift_transform (host only, no device): the 4 x 4 a verification starts from, Rz(shift * 2 pi / 60)"""
+    from . import capi
+    T = np.empty((4, 4))
+    rc = capi.load_library().icpmi_sc_shift_transform(int(shift), capi._dp(T))
+    if rc != capi.OK:
+        raise capi.IcpError(rc, "shift %d outside 0..59" % int(shift))
+    return T
 
 
 class LoopClosureDetector:
@@ -98,14 +127,18 @@ class LoopClosureDetector:
             return results
         q = len(self._descriptors) - 1
         hist = np.stack(self._descriptors[:-1])
-        dist = self.backend.distances(self._descriptors[q], hist)            # :86 for every i
+        guess = bool(getattr(self.config, "yaw_guess", False))
+        if guess:
+            dist, shift = self.backend.distances_shift(self._descriptors[q], hist)
+        else:
+            dist = self.backend.distances(self._descriptors[q], hist)        # :86 for every i
         candidates = []
         for i in range(q):
             if self._frame_indices[q] - self._frame_indices[i] < self.config.frame_gap:   # :81-82
                 continue
             if dist[i] < self.config.sc_distance_threshold:                   # :87-89
                 candidates.append((float(dist[i]), i))
-        candidates.sort()                                                     # :93
+        candidates.sort()                                                     # :93 (the shift never enters the order)
         # The reference verifies the candidates one after the other until max_candidates are ACCEPTED (:96-123).
         # The registrations are independent, so the next (max_candidates - accepted) of them -- all of which the
         # sequential loop would reach -- run side by side when the backend can (icpmi_align_batch); the
@@ -116,14 +149,20 @@ class LoopClosureDetector:
             # (at most MAX_BATCH side by side: icpmi_align_batch's limit; a larger max_candidates takes more rounds)
             chunk = candidates[pos:pos + min(self.config.max_candidates - verified, MAX_BATCH)]
             pos += len(chunk)
+            starts = [sc_shift_transform(int(shift[c])) for _, c in chunk] if guess else None
             if many is not None and len(chunk) > 1:
-                outs = many(self._clouds[q], [self._clouds[c] for _, c in chunk], 30, 1e-6)
+                kw = {"initial_transforms": starts} if guess else {}
+                outs = many(self._clouds[q], [self._clouds[c] for _, c in chunk], 30, 1e-6, **kw)
+            elif guess:
+                outs = [self.backend.align(self._clouds[q], self._clouds[c], 30, 1e-6, initial_transform=T)
+                        for (_, c), T in zip(chunk, starts)]
             else:
                 outs = [self.backend.align(self._clouds[q], self._clouds[c], 30, 1e-6) for _, c in chunk]   # :102-109
             for (sc_dist, cand), r in zip(chunk, outs):
                 if r.converged and r.final_error < self.config.icp_fitness_threshold:   # :112
                     results.append(LoopClosureResult(self._frame_indices[q], self._frame_indices[cand],
-                                                     np.asarray(r.transformation), sc_dist, r.final_error))
+                                                     np.asarray(r.transformation), sc_dist, r.final_error,
+                                                     int(shift[cand]) if guess else None))
                     verified += 1
         return results
 
@@ -146,6 +185,8 @@ class StoreLoopClosureDetector:
         h = C.c_void_p()
         ctx._check(self._lib.icpmi_loop_create(store._h, C.byref(c), C.byref(h)))
         self._h = h
+        if getattr(self.config, "yaw_guess", False):
+            ctx._check(self._lib.icpmi_loop_set_yaw_guess(h, 1))
         for owner in (ctx, store):     # Context.close() and store.close() destroy it before the map
             if not hasattr(owner, "_loops"):
                 owner._loops = weakref.WeakSet()
@@ -185,5 +226,11 @@ class StoreLoopClosureDetector:
         buf = (capi.LoopResult * max(cap, 1))()
         n = C.c_int64(0)
         self.ctx._check(self._lib.icpmi_loop_detect(self._h, buf, cap, C.byref(n)))
+        shifts = [None] * n.value
+        if getattr(self.config, "yaw_guess", False):
+            sh = (C.c_int32 * max(n.value, 1))()
+            m = C.c_int64(0)
+            self.ctx._check(self._lib.icpmi_loop_last_shifts(self._h, sh, n.value, C.byref(m)))
+            shifts = [int(v) for v in sh[:m.value]]
         return [LoopClosureResult(r.query_frame, r.match_frame, np.array(r.transform[:]).reshape(4, 4),
-                                  r.scan_context_distance, r.icp_fitness) for r in buf[:n.value]]
+                                  r.scan_context_distance, r.icp_fitness, s) for r, s in zip(buf[:n.value], shifts)]

@@ -192,6 +192,18 @@ def lidar_frame(frame, voxel=0.5, seed=3, beams=64, azimuths=1800, range_noise=0
     return voxel_centroids(pts, voxel) if voxel else pts
 
 
+def lidar_frame_at(T, noise_seed, voxel=0.5, seed=3, beams=64, azimuths=1800, range_noise=0.01):
+    """lidar_frame's scan from an arbitrary sensor pose T (4 x 4, sensor -> world): any heading at any place, which
+    lidar_pose's drive never gives.  noise_seed seeds the range noise (lidar_frame uses 1000 + frame)."""
+    scene = _scene(seed)
+    T = np.asarray(T, dtype=np.float64).reshape(4, 4)
+    pts = _raycast(T[:3, 3], T[:3, :3], scene, beams=beams, azimuths=azimuths)
+    rng = np.random.Generator(np.random.PCG64(noise_seed))
+    r = np.linalg.norm(pts, axis=1, keepdims=True)
+    pts = pts * (1.0 + rng.normal(0.0, range_noise, size=r.shape) / np.maximum(r, 1e-9))
+    return voxel_centroids(pts, voxel) if voxel else pts
+
+
 def c2_lidar_pair(voxel=0.5, beams=64, azimuths=1800):
     """Frames 0 and 1 of the synthetic drive: source = frame 1, target = frame 0, as
     slam_node.cpp:132-133 does (source = current, target = previous).  Ground truth

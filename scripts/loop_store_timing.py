@@ -15,7 +15,14 @@ KITTI (every copy at least frame_gap back passes the threshold).  max_candidates
 Medians of --reps runs after one warm-up, with min and max.  (c) also checks that both detectors return the same
 closures bit for bit.  --device-only runs (c) for the store detector alone (for rocprofv3).
 
-    python scripts/loop_store_timing.py --out profiles/loop_store/timing.json"""
+--yaw-guess measures the yaw guess instead, in one process:
+    (d) the candidate phase (max_candidates = 0) of one detect for the newest of N entries, k_loop_candidates and
+        k_loop_candidates_shift alternating call by call on two detectors over the same store
+    (e) the verifications of scripts/loop_yaw_ref.py's reverse drive R12 through the host detector, from the identity and
+        from the shift: how many, their iteration counts, their summed time, the closures accepted
+
+    python scripts/loop_store_timing.py --out profiles/loop_store/timing.json
+    python scripts/loop_store_timing.py --yaw-guess --out profiles/loop_store/yaw_timing.json"""
 import argparse
 import json
 import os
@@ -71,6 +78,70 @@ def node_pattern(det, frames, add):
     return out
 
 
+class TimedBackend(lc.GpuBackend):
+    """GpuBackend that records every verification's iteration count and the time spent in them"""
+
+    def __init__(self, ctx):
+        super().__init__(ctx)
+        self.iterations, self.seconds = [], 0.0
+
+    def align(self, *args, **kw):
+        t = time.perf_counter()
+        r = super().align(*args, **kw)
+        self.seconds += time.perf_counter() - t
+        self.iterations.append(int(r.num_iterations))
+        return r
+
+    def align_many(self, *args, **kw):
+        t = time.perf_counter()
+        rs = super().align_many(*args, **kw)
+        self.seconds += time.perf_counter() - t
+        self.iterations += [int(r.num_iterations) for r in rs]
+        return rs
+
+
+def yaw_guess_timing(ctx, gm, sizes, reps):
+    sys.path.insert(0, os.path.join(ROOT, "scripts"))
+    import loop_yaw_ref as ref
+    res = {"candidates": {}, "reverse_drive": {}}
+    for n in sizes:
+        dets = {}
+        for on in (False, True):
+            c = cfg(0)
+            c.yaw_guess = on
+            dets[on] = lc.StoreLoopClosureDetector(ctx, gm, c)
+            for k in range(n):
+                dets[on].add_frame(k, k)
+            dets[on].detect()                                   # the descriptors, and a warm-up
+        ts = {False: [], True: []}
+        for _ in range(reps):
+            for on in (False, True):                            # alternating, call by call
+                t = time.perf_counter()
+                dets[on].detect()
+                ts[on].append(time.perf_counter() - t)
+        res["candidates"][str(n)] = {"k_loop_candidates": stats(ts[False]), "k_loop_candidates_shift": stats(ts[True])}
+        for d in dets.values():
+            d.close()
+        print(n, json.dumps({k: v["median_ms"] for k, v in res["candidates"][str(n)].items()}), flush=True)
+    poses, labels = ref.r12_reverse_drive()
+    clouds = ref.scans(poses)
+    for on in (False, True):
+        for rep in range(2):                                    # the second pass is the one kept (the first warms up)
+            be = TimedBackend(ctx)
+            det = lc.LoopClosureDetector(be, lc.LoopClosureConfig(frame_gap=50, sc_distance_threshold=0.2,
+                                                                  icp_fitness_threshold=0.3, yaw_guess=on))
+            found = []
+            for c, label in zip(clouds, labels):
+                det.add_frame(c, label)
+                found += det.detect()
+        res["reverse_drive"]["on" if on else "off"] = {
+            "verifications": len(be.iterations), "iterations": be.iterations, "verify_ms": 1e3 * be.seconds,
+            "closures": [(r.query_frame, r.match_frame, r.sector_shift) for r in found]}
+        print("reverse drive, guess %s: %s" % ("on" if on else "off", json.dumps(res["reverse_drive"]["on" if on else "off"])),
+              flush=True)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=4541)
@@ -78,6 +149,7 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--sizes", default="100,1000,4540")
     ap.add_argument("--device-only", action="store_true")
+    ap.add_argument("--yaw-guess", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
 
@@ -91,6 +163,16 @@ def main():
     print("store: %d frames, %d rows (%.1f per frame)" % (frames, rows, rows / frames), flush=True)
     add_host = lambda d, k: d.add_frame(cloud(k), k)  # noqa: E731
     add_dev = lambda d, k: d.add_frame(k, k)  # noqa: E731
+    if a.yaw_guess:
+        res = yaw_guess_timing(ctx, gm, [int(s) for s in a.sizes.split(",")], a.reps)
+        res.update(frames=frames, rows=rows, reps=a.reps)
+        if a.out:
+            os.makedirs(os.path.dirname(a.out), exist_ok=True)
+            with open(a.out, "w") as f:
+                json.dump(res, f, indent=1)
+        gm.close()
+        ctx.close()
+        return
     if a.device_only:
         t = time.perf_counter()
         r = node_pattern(lc.StoreLoopClosureDetector(ctx, gm, cfg(3)), frames, add_dev)
