@@ -156,6 +156,41 @@ int icpmi_align_batch(icpmi_ctx *ctx, int32_t count, const double *const *source
                       const double *const *targets_xyz, const int64_t *n_tgt, const icpmi_config *cfgs,
                       icpmi_result *results, double *error_history, int32_t history_stride, int32_t *status);
 
+/* The same registrations behind a correspondence-distance gate (not in the reference, which sums every source row into
+ * the normal equations: icp.hpp:89-144).  With g2 = max_distance * max_distance a pass keeps row i, whose nearest target
+ * is j, iff  e = q_j - p_i,  (e0 * e0 + e1 * e1) + e2 * e2 <= g2  in unfused fp64; a row with a non-finite coordinate is
+ * dropped.  The sums run over the kept rows and the error is their RMS, sqrt(sum b^2 / kept); everything else -- the tests
+ * in front of the solve, total = delta * total, the post-loop entry -- is icpmi_align's.  A pass that keeps no row ends
+ * the call like a break without convergence: converged = 0, +Inf entered as that pass's error and again as the
+ * post-loop entry, final_error = +Inf, the transform what had accumulated.  A gate that keeps every row gives
+ * icpmi_align's bits.  max_distance must be finite and > 0 (ICPMI_ERR_ARG); "no gate" is icpmi_align*.  A context with
+ * a communicator is refused (ICPMI_ERR_ARG).  Targets of up to 8 splits of 2,048 points run in the small-cloud kernel
+ * as ungated ones do; beyond that every pass is a stand-alone search followed by the gated sums -- with the MFMA engines
+ * that search keeps rows x splits x 6 B of coarse minima -- and is slower than the ungated loop.  A tight gate can make
+ * the kept set alternate between passes, so that `tolerance` is never met; 2 m suits 0.5 m voxel-filtered street scans.
+ * gate must not be NULL (ICPMI_ERR_NULL: "no gate" is icpmi_align*); its reserved[] is ignored.
+ * info (may be NULL): pairs = rows kept by the pass that produced final_error, rows = n_src. */
+typedef struct {
+    double max_distance;           /* metres; finite, > 0 */
+    int32_t reserved[2];
+} icpmi_gate;
+typedef struct {
+    int64_t pairs;
+    int64_t rows;
+} icpmi_gate_info;
+int icpmi_align_gated(icpmi_ctx *ctx, const double *source_xyz, int64_t n_src, const double *target_xyz, int64_t n_tgt,
+                      const icpmi_config *cfg, const icpmi_gate *gate, icpmi_result *result, icpmi_gate_info *info,
+                      double *error_history, int32_t history_cap);
+int icpmi_align_gated_device(icpmi_ctx *ctx, const double *d_source_xyz, int64_t n_src, const double *d_target_xyz,
+                             int64_t n_tgt, const icpmi_config *cfg, const icpmi_gate *gate, icpmi_result *result,
+                             icpmi_gate_info *info, double *error_history, int32_t history_cap);
+/* icpmi_align_batch with a gate per problem (gates: `count` entries; infos: `count` entries or NULL): every result is
+ * bit-identical to the same icpmi_align_gated call made alone. */
+int icpmi_align_gated_batch(icpmi_ctx *ctx, int32_t count, const double *const *sources_xyz, const int64_t *n_src,
+                            const double *const *targets_xyz, const int64_t *n_tgt, const icpmi_config *cfgs,
+                            const icpmi_gate *gates, icpmi_result *results, icpmi_gate_info *infos, double *error_history,
+                            int32_t history_stride, int32_t *status);
+
 /* Replaces KDTree(points) + KDTree::nearest_batch (kdtree.hpp:20-26,43-59): for each
  * query the index of, and squared distance to, its nearest target.  Host pointers;
  * dist_sq may be NULL. */
@@ -659,6 +694,13 @@ int icpmi_map_live_clear(icpmi_map *map);
  *   icpmi_loop_last_shifts    the shifts the last detect's results started from, in result order: *n_out = the number
  *                             of results (shifts may be NULL with cap 0; a cap below it is ICPMI_ERR_CAPACITY); each is
  *                             -1 when that detect ran with the guess off.
+ *   icpmi_loop_set_gate       max_distance > 0 (0: off, as at creation; not in the reference): detect's verifications
+ *                             run behind that correspondence-distance gate (icpmi_align_gated), so a place revisited
+ *                             a lane aside -- scans that overlap only partly -- verifies; icp_fitness is then the RMS
+ *                             over the kept rows.  Composes with the yaw guess; candidates and their order are
+ *                             unchanged; takes effect at the next detect.  Negative or non-finite: ICPMI_ERR_ARG.
+ *   icpmi_loop_last_pairs     the rows each of the last detect's results kept in its last pass, in result order, as
+ *                             icpmi_loop_last_shifts returns the shifts; each is -1 when that detect ran ungated.
  * A store frame or an entry out of range is ICPMI_ERR_ARG and changes nothing.  The handle uses its map's context and
  * stream: destroy it before its map, and the map before the context. */
 typedef struct icpmi_loop icpmi_loop;
@@ -684,6 +726,8 @@ int icpmi_loop_size(const icpmi_loop *loop, int64_t *entries);
 int icpmi_loop_clear(icpmi_loop *loop);
 int icpmi_loop_set_yaw_guess(icpmi_loop *loop, int32_t on);
 int icpmi_loop_last_shifts(const icpmi_loop *loop, int32_t *shifts, int64_t cap, int64_t *n_out);
+int icpmi_loop_set_gate(icpmi_loop *loop, double max_distance);
+int icpmi_loop_last_pairs(const icpmi_loop *loop, int64_t *pairs, int64_t cap, int64_t *n_out);
 
 /* profiling */
 int icpmi_reset_profile(icpmi_ctx *ctx);

@@ -267,6 +267,93 @@ inline std::vector<ICPResult> icp_point_to_plane_batch(Context &ctx, const Point
     return out;
 }
 
+// ---- the correspondence-distance gate (icpmi_align_gated*; not in the reference) -----------------
+// A pass sums only the rows whose nearest target is within max_distance (metres; finite, > 0), and the error is the
+// RMS over those.  pairs: the rows kept by the pass that produced final_error, of `rows`.  A pass that keeps none ends
+// the call unconverged with final_error = +Inf.  A gate that keeps every row gives icp_point_to_plane's bits.
+struct GatedICPResult : ICPResult {
+    long long pairs = 0;
+    long long rows = 0;
+};
+
+namespace detail {
+inline void fill(ICPResult &out, const icpmi_result &r, const double *hist)
+{
+    std::array<double, 16> m;
+    for (int e = 0; e < 16; ++e) m[static_cast<std::size_t>(e)] = r.transformation[e];
+    out.transformation = Transformation(m);
+    out.converged = r.converged != 0;
+    out.num_iterations = r.num_iterations;
+    out.final_error = r.final_error;
+    out.error_history.assign(hist, hist + r.history_len);
+}
+} // namespace detail
+
+inline GatedICPResult align_gated(Context &ctx, const double *source_xyz, std::size_t n_src, const double *target_xyz,
+                                  std::size_t n_tgt, double max_distance, const ICPConfig &config = ICPConfig())
+{
+    icpmi_config k = detail::to_c(config);
+    icpmi_gate g{};
+    g.max_distance = max_distance;
+    icpmi_gate_info info{};
+    std::vector<double> hist(static_cast<std::size_t>(config.max_iterations > 0 ? config.max_iterations : 0) + 1);
+    icpmi_result r;
+    const int rc = icpmi_align_gated(ctx.get(), source_xyz, static_cast<int64_t>(n_src), target_xyz, static_cast<int64_t>(n_tgt),
+                                     &k, &g, &r, &info, hist.data(), static_cast<int32_t>(hist.size()));
+    if (rc != ICPMI_OK) throw IcpError(rc, icpmi_last_error(ctx.get()));
+    GatedICPResult out;
+    detail::fill(out, r, hist.data());
+    out.pairs = info.pairs;
+    out.rows = info.rows;
+    return out;
+}
+inline GatedICPResult align_gated(const PointCloud &source, const PointCloud &target, double max_distance,
+                                  const ICPConfig &config = ICPConfig())
+{
+    return align_gated(default_context(), source.data(), source.size(), target.data(), target.size(), max_distance, config);
+}
+
+// icp_point_to_plane_batch behind one gate for every problem (icpmi_align_gated_batch): each result is that of
+// align_gated alone.
+inline std::vector<GatedICPResult> align_gated_batch(Context &ctx, const PointCloud &source,
+                                                     const std::vector<const PointCloud *> &targets, double max_distance,
+                                                     const ICPConfig &config,
+                                                     const std::vector<Transformation> &initial_transforms = {})
+{
+    const std::size_t k = targets.size();
+    std::vector<GatedICPResult> out(k);
+    if (k == 0) return out;
+    if (!initial_transforms.empty() && initial_transforms.size() != k)
+        throw IcpError(ICPMI_ERR_ARG, "as many initial transforms as targets, or none");
+    std::vector<const double *> sp(k, source.data()), tp(k);
+    std::vector<int64_t> ns(k, static_cast<int64_t>(source.size())), nt(k);
+    for (std::size_t i = 0; i < k; ++i) {
+        tp[i] = targets[i]->data();
+        nt[i] = static_cast<int64_t>(targets[i]->size());
+    }
+    std::vector<icpmi_config> cfgs(k, detail::to_c(config));
+    for (std::size_t i = 0; i < initial_transforms.size(); ++i)
+        for (int e = 0; e < 16; ++e) cfgs[i].initial_transform[e] = initial_transforms[i].matrix()[static_cast<std::size_t>(e)];
+    icpmi_gate g{};
+    g.max_distance = max_distance;
+    std::vector<icpmi_gate> gates(k, g);
+    std::vector<icpmi_gate_info> infos(k);
+    const std::size_t stride = static_cast<std::size_t>(config.max_iterations > 0 ? config.max_iterations : 0) + 1;
+    std::vector<double> hist(k * stride);
+    std::vector<icpmi_result> res(k);
+    std::vector<int32_t> status(k);
+    const int rc = icpmi_align_gated_batch(ctx.get(), static_cast<int32_t>(k), sp.data(), ns.data(), tp.data(), nt.data(),
+                                           cfgs.data(), gates.data(), res.data(), infos.data(), hist.data(),
+                                           static_cast<int32_t>(stride), status.data());
+    if (rc != ICPMI_OK) throw IcpError(rc, icpmi_last_error(ctx.get()));
+    for (std::size_t i = 0; i < k; ++i) {
+        detail::fill(out[i], res[i], hist.data() + i * stride);
+        out[i].pairs = infos[i].pairs;
+        out[i].rows = infos[i].rows;
+    }
+    return out;
+}
+
 // Same call shape as slam::icp_point_to_plane (icp.hpp:157-161).
 inline ICPResult icp_point_to_plane(const PointCloud &source, const PointCloud &target,
                                     const ICPConfig &config = ICPConfig())
@@ -575,12 +662,18 @@ struct LoopClosureConfig { // loop_closure.hpp:14-19
     // from Rz(shift * 6 deg) (icpmi_sc_shift_transform) instead of from the identity, so that a place revisited with
     // another heading closes too.  Off: the reference's behaviour.
     bool yaw_guess = false;
+    // Not in the reference: > 0 runs the verifications behind that correspondence-distance gate (align_gated; metres),
+    // so that a place revisited a lane aside, whose scans overlap only partly, closes too; icp_fitness is then the RMS
+    // over the kept rows.  2 m suits 0.5 m voxel-filtered street scans; a tight gate (1 m) can make the kept set
+    // alternate between passes until the iterations run out.  0: the reference's behaviour.
+    double max_correspondence_distance = 0.0;
 };
 struct LoopClosureResult { // loop_closure.hpp:25-31
     int query_frame = 0, match_frame = 0;
     Transformation transform;
     double scan_context_distance = 0.0, icp_fitness = 0.0;
     int sector_shift = -1; // the shift the verification started from (-1: yaw_guess off)
+    long long pairs = -1;  // the rows the verification's last pass kept (-1: no correspondence-distance gate)
 };
 
 // icpmi_sc_shift_transform: the start of a verification whose candidate matched at column shift `shift` (0..59).
@@ -654,7 +747,18 @@ public:
                 tg.push_back(&clouds_[c]);
                 if (config_.yaw_guess) starts.push_back(sc_shift_transform(shift[c]));
             }
-            const std::vector<ICPResult> rs = icp_point_to_plane_batch(*ctx_, clouds_[q], tg, icp, starts); // :109
+            const bool gated = config_.max_correspondence_distance > 0.0;
+            std::vector<ICPResult> rs; // :109
+            std::vector<long long> kept(take, -1);
+            if (gated) {
+                const std::vector<GatedICPResult> gs = align_gated_batch(*ctx_, clouds_[q], tg, config_.max_correspondence_distance, icp, starts);
+                for (std::size_t i = 0; i < take; ++i) {
+                    rs.push_back(gs[i]);
+                    kept[i] = gs[i].pairs;
+                }
+            } else {
+                rs = icp_point_to_plane_batch(*ctx_, clouds_[q], tg, icp, starts);
+            }
             for (std::size_t i = 0; i < take; ++i) {
                 const ICPResult &r = rs[i];
                 const auto &cand = candidates[pos + i];
@@ -666,6 +770,7 @@ public:
                     out.scan_context_distance = cand.first;
                     out.icp_fitness = r.final_error;
                     if (config_.yaw_guess) out.sector_shift = shift[static_cast<std::size_t>(cand.second)];
+                    out.pairs = kept[i];
                     results.push_back(out);
                     ++verified;
                 }
@@ -1044,6 +1149,7 @@ public:
         c.icp_fitness_threshold = config.icp_fitness_threshold;
         check(icpmi_loop_create(map.get(), &c, &l_));
         if (config.yaw_guess) check(icpmi_loop_set_yaw_guess(l_, 1));
+        if (config.max_correspondence_distance > 0.0) check(icpmi_loop_set_gate(l_, config.max_correspondence_distance));
     }
     ~StoreLoopClosureDetector() { icpmi_loop_destroy(l_); }
     StoreLoopClosureDetector(const StoreLoopClosureDetector &) = delete;
@@ -1073,11 +1179,14 @@ public:
         std::vector<int32_t> shifts(static_cast<std::size_t>(std::max<int64_t>(n, 1)), -1);
         int64_t ns = 0;
         check(icpmi_loop_last_shifts(l_, shifts.data(), n, &ns)); // -1 each with the guess off
+        std::vector<int64_t> kept(static_cast<std::size_t>(std::max<int64_t>(n, 1)), -1);
+        check(icpmi_loop_last_pairs(l_, kept.data(), n, &ns)); // -1 each with the gate off
         std::vector<LoopClosureResult> out;
         for (int64_t i = 0; i < n; ++i) {
             const icpmi_loop_result &r = buf[static_cast<std::size_t>(i)];
             LoopClosureResult o;
             o.sector_shift = shifts[static_cast<std::size_t>(i)];
+            o.pairs = kept[static_cast<std::size_t>(i)];
             o.query_frame = r.query_frame;
             o.match_frame = r.match_frame;
             std::array<double, 16> m;

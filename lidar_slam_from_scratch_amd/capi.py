@@ -39,6 +39,7 @@ EXPORTS = [
     "icpmi_loop_config_default", "icpmi_loop_create", "icpmi_loop_destroy", "icpmi_loop_add_frame", "icpmi_loop_detect",
     "icpmi_loop_descriptor", "icpmi_loop_size", "icpmi_loop_clear",
     "icpmi_scan_context_distances_shift", "icpmi_sc_shift_transform", "icpmi_loop_set_yaw_guess", "icpmi_loop_last_shifts",
+    "icpmi_align_gated", "icpmi_align_gated_device", "icpmi_align_gated_batch", "icpmi_loop_set_gate", "icpmi_loop_last_pairs",
 ]
 
 
@@ -57,6 +58,16 @@ class Result(C.Structure):
     _fields_ = [("transformation", C.c_double * 16), ("converged", C.c_int32),
                 ("num_iterations", C.c_int32), ("final_error", C.c_double),
                 ("history_len", C.c_int32), ("loop_iterations", C.c_int32)]
+
+
+class Gate(C.Structure):
+    """icpmi_gate: the correspondence-distance gate of align_gated*"""
+    _fields_ = [("max_distance", C.c_double), ("reserved", C.c_int32 * 2)]
+
+
+class GateInfo(C.Structure):
+    """icpmi_gate_info: rows kept by the pass that produced final_error, of `rows`"""
+    _fields_ = [("pairs", C.c_int64), ("rows", C.c_int64)]
 
 
 class LoopConfig(C.Structure):
@@ -237,6 +248,13 @@ def load_library(path=None):
                                      C.POINTER(Result), dp, C.c_int32]
     L.icpmi_align_batch.argtypes = [vp, C.c_int32, C.POINTER(dp), C.POINTER(C.c_int64), C.POINTER(dp), C.POINTER(C.c_int64),
                                     C.POINTER(Config), C.POINTER(Result), dp, C.c_int32, C.POINTER(C.c_int32)]
+    L.icpmi_align_gated.argtypes = [vp, dp, C.c_int64, dp, C.c_int64, C.POINTER(Config), C.POINTER(Gate),
+                                    C.POINTER(Result), C.POINTER(GateInfo), dp, C.c_int32]
+    L.icpmi_align_gated_device.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, C.POINTER(Config), C.POINTER(Gate),
+                                           C.POINTER(Result), C.POINTER(GateInfo), dp, C.c_int32]
+    L.icpmi_align_gated_batch.argtypes = [vp, C.c_int32, C.POINTER(dp), C.POINTER(C.c_int64), C.POINTER(dp), C.POINTER(C.c_int64),
+                                          C.POINTER(Config), C.POINTER(Gate), C.POINTER(Result), C.POINTER(GateInfo), dp,
+                                          C.c_int32, C.POINTER(C.c_int32)]
     L.icpmi_nearest_batch.argtypes = [vp, dp, C.c_int64, dp, C.c_int64, C.POINTER(C.c_int32), dp]
     L.icpmi_k_nearest.argtypes = [vp, dp, C.c_int64, dp, C.c_int64, C.c_int32, C.POINTER(C.c_int32), dp]
     L.icpmi_estimate_normals.argtypes = [vp, dp, C.c_int64, C.c_int32, dp]
@@ -320,6 +338,8 @@ def load_library(path=None):
     L.icpmi_loop_clear.argtypes = [vp]
     L.icpmi_loop_set_yaw_guess.argtypes = [vp, C.c_int32]
     L.icpmi_loop_last_shifts.argtypes = [vp, C.POINTER(C.c_int32), C.c_int64, i64p]
+    L.icpmi_loop_set_gate.argtypes = [vp, C.c_double]
+    L.icpmi_loop_last_pairs.argtypes = [vp, i64p, C.c_int64, i64p]
     for name in EXPORTS:
         getattr(L, name)  # raises AttributeError if a declared symbol is not exported
     _LIB = L
@@ -455,6 +475,62 @@ class Context:
                                                  C.c_void_p(tgt_ptr), n_tgt, C.byref(cfg),
                                                  C.byref(res), _dp(hist), cap))
         return res, hist[:res.history_len].copy()
+
+    @staticmethod
+    def _gate(max_distance):
+        g = Gate()
+        g.max_distance = float(max_distance)
+        return g
+
+    def align_gated(self, source, target, cfg, max_distance):
+        """align() behind a correspondence-distance gate (icpmi_align_gated): a pass sums only the rows whose nearest
+        target is within max_distance -> (Result, error history, rows kept by the pass that produced final_error)"""
+        src, tgt = _f64(source), _f64(target)
+        cap = cfg.max_iterations + 1
+        hist = np.zeros(max(cap, 1))
+        res, info, gate = Result(), GateInfo(), self._gate(max_distance)
+        self._check(self._lib.icpmi_align_gated(self._h, _dp(src), src.shape[0], _dp(tgt), tgt.shape[0], C.byref(cfg),
+                                                C.byref(gate), C.byref(res), C.byref(info), _dp(hist), cap))
+        return res, hist[:res.history_len].copy(), int(info.pairs)
+
+    def align_gated_device(self, src_ptr, n_src, tgt_ptr, n_tgt, cfg, max_distance):
+        """align_gated with both clouds in device memory (addresses of row-major N x 3 fp64)"""
+        cap = cfg.max_iterations + 1
+        hist = np.zeros(max(cap, 1))
+        res, info, gate = Result(), GateInfo(), self._gate(max_distance)
+        self._check(self._lib.icpmi_align_gated_device(self._h, C.c_void_p(src_ptr), n_src, C.c_void_p(tgt_ptr), n_tgt,
+                                                       C.byref(cfg), C.byref(gate), C.byref(res), C.byref(info),
+                                                       _dp(hist), cap))
+        return res, hist[:res.history_len].copy(), int(info.pairs)
+
+    def align_gated_batch(self, sources, targets, cfgs, max_distances):
+        """align_batch behind a gate (icpmi_align_gated_batch) -> [(Result, error history, pairs), ...], each
+        bit-identical to align_gated() of the same pair.  max_distances: one for all, or one per pair."""
+        srcs, tgts = [_f64(a) for a in sources], [_f64(a) for a in targets]
+        k = len(srcs)
+        if k != len(tgts) or k < 1:
+            raise ValueError("as many targets as sources, at least one")
+        cfg_list = list(cfgs) if isinstance(cfgs, (list, tuple)) else [cfgs] * k
+        gate_list = list(max_distances) if isinstance(max_distances, (list, tuple)) else [max_distances] * k
+        cfg_arr = (Config * k)(*cfg_list)
+        gates = (Gate * k)(*[self._gate(g) for g in gate_list])
+        stride = max(c.max_iterations for c in cfg_list) + 1
+        hist = np.zeros((k, stride))
+        res, infos = (Result * k)(), (GateInfo * k)()
+        status = (C.c_int32 * k)()
+        dpp = C.POINTER(C.c_double)
+        sp = (dpp * k)(*[_dp(a) for a in srcs])
+        tp = (dpp * k)(*[_dp(a) for a in tgts])
+        ns = (C.c_int64 * k)(*[a.shape[0] for a in srcs])
+        nt = (C.c_int64 * k)(*[a.shape[0] for a in tgts])
+        self._check(self._lib.icpmi_align_gated_batch(self._h, k, sp, ns, tp, nt, cfg_arr, gates, res, infos, _dp(hist),
+                                                      stride, status))
+        out = []
+        for i in range(k):
+            r = Result()
+            C.memmove(C.byref(r), C.byref(res[i]), C.sizeof(Result))
+            out.append((r, hist[i, :r.history_len].copy(), int(infos[i].pairs)))
+        return out
 
     def nearest_batch(self, targets, queries, want_dist=True):
         tgt, qry = _f64(targets), _f64(queries)

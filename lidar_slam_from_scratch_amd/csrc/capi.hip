@@ -34,6 +34,7 @@
 #include "kernels.h"
 #include "nn_mfma.h"
 #include "icp_small.h"
+#include "icp_gated.h"
 #include "knn_lists.h"
 #include "nn_bounded.h"
 #include "nn_culled.h"
@@ -1088,13 +1089,23 @@ int prepare_target(icpmi_ctx *ctx, const double *d_tgt, int m, int n_hint)
     return ICPMI_OK;
 }
 
+// The correspondence-distance gate of a registration (icp_gated.h): null means none, and every branch below is then
+// what it was before the gate existed.
+struct GateRun {
+    double g2;     // max_distance * max_distance
+    int64_t pairs; // out: the rows kept by the pass that produced final_error (the state's sums[28], which comes back anyway)
+};
+
+// `gate` (may be null): see GateRun.  A gated registration runs the small-cloud kernel's gated form in the small regime
+// and otherwise the unfused general path -- search (launch_nn), k_reduce_gated, k_finish_step_gated, k_transform -- on
+// whichever engine prepare_nn chose: no fused resolve, no culling, no bounds, no list reuse, no sorted rows.
 // `before_wait` (may be null): called once everything of the registration, the copies of its results
 // included, is queued and an event behind them recorded -- what it queues runs while the host waits
 // for that event only (icpmi_stream_push prepares the next frame's target there).
 int align_device(icpmi_ctx *ctx, const double *d_src, int64_t n_src64, const double *d_tgt,
                  int64_t n_tgt64, const icpmi_config *cfg, icpmi_result *result,
                  double *error_history, int32_t history_cap, int (*before_wait)(icpmi_ctx *) = nullptr,
-                 int (*after_first)(icpmi_ctx *) = nullptr)
+                 int (*after_first)(icpmi_ctx *) = nullptr, GateRun *gate = nullptr)
 {
     const int n = (int)n_src64, m = (int)n_tgt64;
     const int max_it = cfg->max_iterations;
@@ -1131,13 +1142,15 @@ int align_device(icpmi_ctx *ctx, const double *d_src, int64_t n_src64, const dou
     HIP_TRY(ctx, hipMemcpyAsync(st, hs, sizeof(IcpState), hipMemcpyHostToDevice, s));
 
     const bool sharded_run = ctx->comm != nullptr || ctx->cb_allreduce != nullptr;
+    if (gate && sharded_run) return fail(ctx, ICPMI_ERR_ARG, "a context with a communicator does not run gated registrations");
     const bool prepared = !sharded_run && ctx->prep_valid && ctx->prep_tgt == d_tgt && ctx->prep_m == m &&
                           ctx->prep_engine == engine_for(ctx, m, n);
     // (the ranks of a sharded run must agree on the engine -- it decides the order of the normal rows they gather -- so
     // there AUTO looks at the target alone, whatever this rank's share of the source)
     if (!prepared && (rc = prepare_nn(ctx, d_tgt, m, sharded_run ? std::max(n, kMfmaMinQueries) : n))) return rc;
     // with the MFMA engine the resolve kernel also forms the normal-equation partial sums
-    const bool fused = ctx->nn_engine == ICPMI_SEARCH_MFMA_BF16;
+    // (not under a gate: its general path searches first and tests the rows in k_reduce_gated)
+    const bool fused = ctx->nn_engine == ICPMI_SEARCH_MFMA_BF16 && !gate;
     // small clouds: one kernel per iteration for the rows' work (icp_small.h), then k_finish_step
     const bool small = !sharded_run && n > 0 && n <= kSmallMaxQueries && small_target(ctx);
     const int rblocks = small ? (n + kSmallQ - 1) / kSmallQ : (fused ? resolve_blocks(n) : reduce_blocks(ctx, n));
@@ -1290,7 +1303,8 @@ int align_device(icpmi_ctx *ctx, const double *d_src, int64_t n_src64, const dou
         frames, splits, (const double *)ctx->tgt_sorted.p, (const double *)ctx->nrm_sorted.p,                                       \
         (const unsigned *)ctx->sort_keys.p + 3 * (size_t)m, m, ctx->nn_ms, d_tgt, (const double *)nrm, partials,                    \
         (unsigned long long *)((char *)ctx->nn_misc.p + 128)
-                hipLaunchKernelGGL(k_icp_small, dim3(rblocks), dim3(kSmallThreads), 0, s, ICPMI_SMALL_ARGS);
+                if (gate) hipLaunchKernelGGL(k_icp_small_gated, dim3(rblocks), dim3(kSmallThreads), 0, s, ICPMI_SMALL_ARGS, gate->g2);
+                else hipLaunchKernelGGL(k_icp_small, dim3(rblocks), dim3(kSmallThreads), 0, s, ICPMI_SMALL_ARGS);
 #undef ICPMI_SMALL_ARGS
                 small_first = false;
                 ctx->prof.nn_pairs += (double)n * (double)m;
@@ -1299,12 +1313,13 @@ int align_device(icpmi_ctx *ctx, const double *d_src, int64_t n_src64, const dou
             }
             Range range("icpmi:reduce_solve");
             StageTimer t(ctx, ST_REDUCE);
-            hipLaunchKernelGGL(k_finish_step, dim3(1), dim3(kFinishThreads), 0, s, partials, rblocks, n, st, hist, final_pass, progress, ticket);
+            if (gate) hipLaunchKernelGGL(k_finish_step_gated, dim3(1), dim3(kFinishThreads), 0, s, partials, rblocks, st, hist, final_pass, progress, ticket);
+            else hipLaunchKernelGGL(k_finish_step, dim3(1), dim3(kFinishThreads), 0, s, partials, rblocks, n, st, hist, final_pass, progress, ticket);
             HIP_TRY(ctx, hipGetLastError());
             return ICPMI_OK;
         }
         const bool fuse_step = sharded && n > 0 && !final_pass;
-        const bool fuse_finish = !sharded && n > 0 && !final_pass && fuse_finish_enabled();
+        const bool fuse_finish = !sharded && n > 0 && !final_pass && !gate && fuse_finish_enabled();
         if (n > 0 && fused) {
             if ((r2 = launch_nn_mfma(ctx, cur, n, m, idx, nullptr, st, d_tgt, nrm, partials,
                                      pruned ? pass_no : -1, bounded_loop /* incumbents in idx, bounds in place: from k_nn_prebound1 or the kernel that moved the rows */,
@@ -1318,7 +1333,10 @@ int align_device(icpmi_ctx *ctx, const double *d_src, int64_t n_src64, const dou
         {
             Range range("icpmi:reduce_solve");
             StageTimer t(ctx, ST_REDUCE);
-            if (!fused)
+            if (gate)
+                hipLaunchKernelGGL(k_reduce_gated, dim3(rblocks), dim3(256), 0, s, cur, n, d_tgt, m, nrm, idx, partials,
+                                   st, gate->g2);
+            else if (!fused)
                 hipLaunchKernelGGL(k_reduce, dim3(rblocks), dim3(256), 0, s, cur, n, d_tgt, m, nrm, idx, partials,
                                    st);
             if (sum_tree)
@@ -1357,6 +1375,9 @@ int align_device(icpmi_ctx *ctx, const double *d_src, int64_t n_src64, const dou
                                        fin_rows, fin_blocks, n, (const double *)cur, cur, n,
                                        (const IcpState *)st, other, hist, progress, ticket, rb);
                 st = other;
+            } else if (gate) {
+                hipLaunchKernelGGL(k_finish_step_gated, dim3(1), dim3(kFinishThreads), 0, s, fin_rows, fin_blocks,
+                                   st, hist, final_pass, progress, ticket);
             } else {
                 hipLaunchKernelGGL(k_finish_step, dim3(1), dim3(kFinishThreads), 0, s, fin_rows, fin_blocks, n,
                                    st, hist, final_pass, progress, ticket);
@@ -1500,6 +1521,13 @@ int align_device(icpmi_ctx *ctx, const double *d_src, int64_t n_src64, const dou
     ctx->loop_rows = n;
     ctx->loop_idx_valid = n > 0 && !small;
     ctx->loop_sorted = pruned || sorted_rows_loop;
+    if (gate) {
+        // A gated loop's idx holds matches of rows the gate dropped as well: loop_rows stays -1 ("no registration's rows
+        // are held"), so icpmi_debug_loop_rows refuses every row count and nothing reads them as an ungated loop's.
+        ctx->loop_rows = -1;
+        ctx->loop_idx_valid = false;
+        gate->pairs = (int64_t)hs->sums[28];
+    }
 
     memcpy(result->transformation, hs->total, sizeof(double) * 16); // icp.hpp:254
     result->converged = hs->converged;
@@ -1883,12 +1911,24 @@ int icpmi_align_device(icpmi_ctx *ctx, const double *d_source_xyz, int64_t n_src
 
 namespace {
 
+// the gate of the gated entry points: finite and > 0, and not on a context with a communicator (out of scope)
+int validate_gate(icpmi_ctx *ctx, const icpmi_gate *gate, GateRun *run)
+{
+    if (!gate) return fail(ctx, ICPMI_ERR_NULL, "gate is NULL (ungated: icpmi_align*)");
+    if (!(gate->max_distance > 0.0) || !std::isfinite(gate->max_distance))
+        return fail(ctx, ICPMI_ERR_ARG, "max_distance must be finite and > 0");
+    if (ctx->comm || ctx->cb_allreduce) return fail(ctx, ICPMI_ERR_ARG, "a context with a communicator does not run gated registrations");
+    run->g2 = gate->max_distance * gate->max_distance;
+    run->pairs = 0;
+    return ICPMI_OK;
+}
+
 // icpmi_align after its checks: the rows (host or device memory, `kind`) go into the context's own buffers first, so
 // every registration reads its clouds from the same place whoever supplied them (icpmi_align, the loop store's
 // verifications).
 int align_staged(icpmi_ctx *ctx, const double *source_xyz, int64_t n_src, const double *target_xyz, int64_t n_tgt,
                  hipMemcpyKind kind, const icpmi_config *cfg, icpmi_result *result, double *error_history,
-                 int32_t history_cap)
+                 int32_t history_cap, GateRun *gate = nullptr)
 {
     int rc;
     if ((rc = reserve(ctx, ctx->stage_b, sizeof(double) * 3 * (size_t)n_src))) return rc;
@@ -1896,7 +1936,7 @@ int align_staged(icpmi_ctx *ctx, const double *source_xyz, int64_t n_src, const 
     HIP_TRY(ctx, hipMemcpyAsync(ctx->stage_b.p, source_xyz, sizeof(double) * 3 * (size_t)n_src, kind, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(ctx->stage_c.p, target_xyz, sizeof(double) * 3 * (size_t)n_tgt, kind, ctx->stream));
     return align_device(ctx, (const double *)ctx->stage_b.p, n_src, (const double *)ctx->stage_c.p,
-                        n_tgt, cfg, result, error_history, history_cap);
+                        n_tgt, cfg, result, error_history, history_cap, nullptr, nullptr, gate);
 }
 
 // Runs job(c, k) for k in [0, count) side by side: k = 0 on ctx itself, k >= 1 on helper k - 1's context and host
@@ -1978,6 +2018,55 @@ int icpmi_align_batch(icpmi_ctx *ctx, int32_t count, const double *const *source
     return batch_run(ctx, count, [&](icpmi_ctx *c, int k) {
         return icpmi_align(c, sources_xyz[k], n_src[k], targets_xyz[k], n_tgt[k], &cfgs[k], &results[k],
                            error_history + (size_t)k * (size_t)history_stride, history_stride);
+    }, status);
+}
+
+int icpmi_align_gated_device(icpmi_ctx *ctx, const double *d_source_xyz, int64_t n_src, const double *d_target_xyz,
+                             int64_t n_tgt, const icpmi_config *cfg, const icpmi_gate *gate, icpmi_result *result,
+                             icpmi_gate_info *info, double *error_history, int32_t history_cap)
+{
+    int rc = validate_align(ctx, d_source_xyz, n_src, d_target_xyz, n_tgt, cfg, result, error_history, history_cap);
+    if (rc) return rc;
+    if ((rc = check_common(ctx))) return rc;
+    GateRun run;
+    if ((rc = validate_gate(ctx, gate, &run))) return rc;
+    if ((rc = align_device(ctx, d_source_xyz, n_src, d_target_xyz, n_tgt, cfg, result, error_history, history_cap, nullptr,
+                           nullptr, &run)))
+        return rc;
+    if (info) info->pairs = run.pairs, info->rows = n_src;
+    return ICPMI_OK;
+}
+
+int icpmi_align_gated(icpmi_ctx *ctx, const double *source_xyz, int64_t n_src, const double *target_xyz, int64_t n_tgt,
+                      const icpmi_config *cfg, const icpmi_gate *gate, icpmi_result *result, icpmi_gate_info *info,
+                      double *error_history, int32_t history_cap)
+{
+    int rc = validate_align(ctx, source_xyz, n_src, target_xyz, n_tgt, cfg, result, error_history, history_cap);
+    if (rc) return rc;
+    if ((rc = check_common(ctx))) return rc;
+    GateRun run;
+    if ((rc = validate_gate(ctx, gate, &run))) return rc;
+    if ((rc = align_staged(ctx, source_xyz, n_src, target_xyz, n_tgt, hipMemcpyHostToDevice, cfg, result, error_history,
+                           history_cap, &run)))
+        return rc;
+    if (info) info->pairs = run.pairs, info->rows = n_src;
+    return ICPMI_OK;
+}
+
+int icpmi_align_gated_batch(icpmi_ctx *ctx, int32_t count, const double *const *sources_xyz, const int64_t *n_src,
+                            const double *const *targets_xyz, const int64_t *n_tgt, const icpmi_config *cfgs,
+                            const icpmi_gate *gates, icpmi_result *results, icpmi_gate_info *infos, double *error_history,
+                            int32_t history_stride, int32_t *status)
+{
+    int rc;
+    if ((rc = check_common(ctx))) return rc;
+    if (!sources_xyz || !n_src || !targets_xyz || !n_tgt || !cfgs || !gates || !results || !error_history || !status)
+        return fail(ctx, ICPMI_ERR_NULL, "null argument");
+    if (count < 1 || count > ICPMI_MAX_BATCH) return fail(ctx, ICPMI_ERR_ARG, "count %d outside [1,%d]", count, ICPMI_MAX_BATCH);
+    if (ctx->comm || ctx->cb_allreduce) return fail(ctx, ICPMI_ERR_ARG, "a context with a communicator registers one (sharded) problem at a time");
+    return batch_run(ctx, count, [&](icpmi_ctx *c, int k) {
+        return icpmi_align_gated(c, sources_xyz[k], n_src[k], targets_xyz[k], n_tgt[k], &cfgs[k], &gates[k], &results[k],
+                                 infos ? &infos[k] : nullptr, error_history + (size_t)k * (size_t)history_stride, history_stride);
     }, status);
 }
 
@@ -4649,6 +4738,8 @@ struct icpmi_loop {
     std::vector<LoopJob> jobs;
     bool yaw_guess = false;              // icpmi_loop_set_yaw_guess
     std::vector<int32_t> last_shifts;    // per result of the last detect its shift (-1: the guess was off)
+    double gate = 0.0;                   // icpmi_loop_set_gate (0: off)
+    std::vector<int64_t> last_pairs;     // per result of the last detect its kept rows (-1: the gate was off)
 };
 
 namespace {
@@ -4828,7 +4919,9 @@ int icpmi_loop_detect(icpmi_loop *L, icpmi_loop_result *out, int64_t cap, int64_
     if (ctx->comm || ctx->cb_allreduce) return fail(ctx, ICPMI_ERR_ARG, "a context with a communicator registers one (sharded) problem at a time");
     *n_out = 0;
     L->last_shifts.clear();
+    L->last_pairs.clear();
     const bool guess = L->yaw_guess;
+    const bool gated = L->gate > 0.0;
     const int64_t E = (int64_t)L->frames.size();
     if (E < 2) return ICPMI_OK; // :69
     Range range("icpmi:loop_detect");
@@ -4908,6 +5001,7 @@ int icpmi_loop_detect(icpmi_loop *L, icpmi_loop_result *out, int64_t cap, int64_
         int32_t status[ICPMI_MAX_BATCH];
         std::vector<double> hist((size_t)take * (size_t)hcap);
         icpmi_config icps[ICPMI_MAX_BATCH]; // every problem its own start
+        GateRun gates[ICPMI_MAX_BATCH];
         for (int32_t k = 0; k < take; ++k) {
             icps[k] = icp;
             if (guess && (rc = icpmi_sc_shift_transform(shift_of[(size_t)candidates[pos + (size_t)k].second], icps[k].initial_transform)))
@@ -4919,9 +5013,10 @@ int icpmi_loop_detect(icpmi_loop *L, icpmi_loop_result *out, int64_t cap, int64_
             // (only the sizes are checked: the rows are the store's, non-null even for a frame of 0 rows)
             int r = validate_align(c, &icp, nq, &icp, nt, &icps[k], &res[k], hist.data() + (size_t)k * hcap, hcap);
             if (r == ICPMI_OK) r = check_common(c);
+            gates[k] = GateRun{L->gate * L->gate, 0};
             if (r == ICPMI_OK)
                 r = align_staged(c, rows + 3 * (size_t)q0, nq, rows + 3 * (size_t)t0, nt, hipMemcpyDeviceToDevice, &icps[k],
-                                 &res[k], hist.data() + (size_t)k * hcap, hcap);
+                                 &res[k], hist.data() + (size_t)k * hcap, hcap, gated ? &gates[k] : nullptr);
             return r;
         }, status);
         if (rc) return rc;
@@ -4937,6 +5032,7 @@ int icpmi_loop_detect(icpmi_loop *L, icpmi_loop_result *out, int64_t cap, int64_
                 o.icp_fitness = r.final_error;
                 results.push_back(o);
                 L->last_shifts.push_back(guess ? shift_of[(size_t)cand.second] : -1);
+                L->last_pairs.push_back(gated ? gates[k].pairs : -1);
                 ++verified;
             }
         }
@@ -4953,6 +5049,27 @@ int icpmi_loop_set_yaw_guess(icpmi_loop *L, int32_t on)
 {
     if (!L) return ICPMI_ERR_NULL;
     L->yaw_guess = on != 0;
+    return ICPMI_OK;
+}
+
+int icpmi_loop_set_gate(icpmi_loop *L, double max_distance)
+{
+    if (!L) return ICPMI_ERR_NULL;
+    if (max_distance != 0.0 && (!(max_distance > 0.0) || !std::isfinite(max_distance)))
+        return fail(L->map->ctx, ICPMI_ERR_ARG, "max_distance must be 0 (off) or finite and > 0");
+    L->gate = max_distance;
+    return ICPMI_OK;
+}
+
+int icpmi_loop_last_pairs(const icpmi_loop *L, int64_t *pairs, int64_t cap, int64_t *n_out)
+{
+    if (!L) return ICPMI_ERR_NULL;
+    icpmi_ctx *ctx = L->map->ctx;
+    if (!n_out || (!pairs && cap > 0)) return fail(ctx, ICPMI_ERR_NULL, "null argument");
+    const int64_t n = (int64_t)L->last_pairs.size();
+    *n_out = n;
+    if (n > cap) return fail(ctx, ICPMI_ERR_CAPACITY, "output holds %lld counts, needs %lld", (long long)cap, (long long)n);
+    if (n) memcpy(pairs, L->last_pairs.data(), sizeof(int64_t) * (size_t)n);
     return ICPMI_OK;
 }
 

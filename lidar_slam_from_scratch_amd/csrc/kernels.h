@@ -198,6 +198,9 @@ __global__ __launch_bounds__(256) void k_reduce(const double *__restrict__ cur, 
 constexpr int kFinishThreads = 1024;
 constexpr int kFinishGroups = kFinishThreads / 32;
 
+// Counted (icp_gated.h): column 28 of the partial rows holds each block's number of kept rows; their fixed-order sum
+// is the count, and n_local is not looked at.
+template <bool Counted = false>
 __device__ inline void finish_sums(const double *__restrict__ partials, int nblocks, int n_local,
                                    IcpState *st)
 {
@@ -239,12 +242,12 @@ __device__ inline void finish_sums(const double *__restrict__ partials, int nblo
         for (int u = 0; u < w; ++u) acc[u] += acc[u + w];
     fs[g][e] = acc[0];
     __syncthreads();
-    if (threadIdx.x < 28) {
+    if (threadIdx.x < (Counted ? 29 : 28)) {
         double s = fs[0][e];
         for (int k = 1; k < G; ++k) s += fs[k][e];
         st->sums[e] = s;
     }
-    if (threadIdx.x == 0) st->sums[28] = (double)n_local;
+    if (!Counted && threadIdx.x == 0) st->sums[28] = (double)n_local;
 }
 
 // A second level for the sums of very many partial rows (round 4): a resolve workgroup leaves one row per 64 queries --

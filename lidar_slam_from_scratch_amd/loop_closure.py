@@ -14,6 +14,13 @@ identity, so a place revisited with another heading closes too.  The backend the
     backend.distances_shift(query_desc, hist_descs) -> (distances, shifts)
 and align / align_many that take keyword-only initial_transform / initial_transforms; with the option off neither is
 touched, so a backend with the four-argument align keeps working.
+
+LoopClosureConfig(max_correspondence_distance=d) with d > 0 (not in the reference) runs the verifications
+behind a correspondence-distance gate (icpmi_align_gated): a pass sums only the rows whose nearest target is within d, so
+a place revisited a lane aside -- scans that overlap only partly -- verifies, and icp_fitness is the RMS over the kept
+rows.  align / align_many are then passed keyword-only max_distance, and their results carry `pairs`, the rows the last
+pass kept.  0 (the default) passes nothing.  2 m suits 0.5 m voxel-filtered street scans; a tight gate (1 m) can make
+the kept set alternate between passes, so that a verification runs out of iterations.
 """
 import ctypes as C
 import weakref
@@ -27,8 +34,9 @@ class LoopClosureConfig:
     """loop_closure.hpp:14-19"""
 
     def __init__(self, frame_gap=50, sc_distance_threshold=0.25, icp_fitness_threshold=0.3, max_candidates=3,
-                 yaw_guess=False):
+                 yaw_guess=False, max_correspondence_distance=0.0):
         self.yaw_guess = yaw_guess
+        self.max_correspondence_distance = max_correspondence_distance
         self.frame_gap = frame_gap
         self.sc_distance_threshold = sc_distance_threshold
         self.icp_fitness_threshold = icp_fitness_threshold
@@ -36,10 +44,13 @@ class LoopClosureConfig:
 
 
 class LoopClosureResult:
-    """loop_closure.hpp:25-31; sector_shift: the column shift the verification started from (None: yaw_guess off)"""
+    """loop_closure.hpp:25-31; sector_shift: the column shift the verification started from (None: yaw_guess off);
+    pairs: the rows the verification's last pass kept (None: no correspondence-distance gate)"""
 
-    def __init__(self, query_frame, match_frame, transform, scan_context_distance, icp_fitness, sector_shift=None):
+    def __init__(self, query_frame, match_frame, transform, scan_context_distance, icp_fitness, sector_shift=None,
+                 pairs=None):
         self.sector_shift = sector_shift
+        self.pairs = pairs
         self.query_frame = query_frame
         self.match_frame = match_frame
         self.transform = transform
@@ -61,15 +72,19 @@ class GpuBackend:
         """-> (distances, the smallest column shift attaining each), icpmi_scan_context_distances_shift"""
         return self.ctx.scan_context_distances_shift(query_desc, hist_descs)
 
-    def align(self, source, target, max_iterations, tolerance, *, initial_transform=None):
-        if initial_transform is None:
+    def align(self, source, target, max_iterations, tolerance, *, initial_transform=None, max_distance=None):
+        if initial_transform is None and max_distance is None:
             from .odometry import gpu_align
             return gpu_align(self.ctx)(source, target, max_iterations, tolerance)
-        return self.align_many(source, [target], max_iterations, tolerance, initial_transforms=[initial_transform])[0]
+        return self.align_many(source, [target], max_iterations, tolerance,
+                               initial_transforms=None if initial_transform is None else [initial_transform],
+                               max_distance=max_distance)[0]
 
-    def align_many(self, source, targets, max_iterations, tolerance, *, initial_transforms=None):
+    def align_many(self, source, targets, max_iterations, tolerance, *, initial_transforms=None, max_distance=None):
         """The verifications of one detect() side by side on the GPU (icpmi_align_batch): same results as
-        align() one after the other.  initial_transforms: one 4 x 4 per target (None: the identity for all)."""
+        align() one after the other.  initial_transforms: one 4 x 4 per target (None: the identity for all).
+        max_distance: the correspondence-distance gate (icpmi_align_gated_batch; None: none); the results then carry
+        `pairs`."""
         from . import capi
 
         class _R:
@@ -80,10 +95,16 @@ class GpuBackend:
             cfg = [capi.Context.make_config(max_iterations=max_iterations, tolerance=tolerance, initial_transform=T)
                    for T in initial_transforms]
         out = []
-        for res, _hist in self.ctx.align_batch([source] * len(targets), targets, cfg):
+        if max_distance is None:
+            runs = [(res, None) for res, _hist in self.ctx.align_batch([source] * len(targets), targets, cfg)]
+        else:
+            runs = [(res, pairs) for res, _hist, pairs in
+                    self.ctx.align_gated_batch([source] * len(targets), targets, cfg, float(max_distance))]
+        for res, pairs in runs:
             r = _R()
             r.transformation = np.array(res.transformation[:]).reshape(4, 4)
             r.converged, r.final_error, r.num_iterations = bool(res.converged), res.final_error, res.num_iterations
+            r.pairs = pairs
             out.append(r)
         return out
 
@@ -128,6 +149,8 @@ class LoopClosureDetector:
         q = len(self._descriptors) - 1
         hist = np.stack(self._descriptors[:-1])
         guess = bool(getattr(self.config, "yaw_guess", False))
+        gate = float(getattr(self.config, "max_correspondence_distance", 0.0) or 0.0)
+        gkw = {"max_distance": gate} if gate > 0.0 else {}   # (passed only when set, as the starts are)
         if guess:
             dist, shift = self.backend.distances_shift(self._descriptors[q], hist)
         else:
@@ -152,17 +175,18 @@ class LoopClosureDetector:
             starts = [sc_shift_transform(int(shift[c])) for _, c in chunk] if guess else None
             if many is not None and len(chunk) > 1:
                 kw = {"initial_transforms": starts} if guess else {}
-                outs = many(self._clouds[q], [self._clouds[c] for _, c in chunk], 30, 1e-6, **kw)
+                outs = many(self._clouds[q], [self._clouds[c] for _, c in chunk], 30, 1e-6, **kw, **gkw)
             elif guess:
-                outs = [self.backend.align(self._clouds[q], self._clouds[c], 30, 1e-6, initial_transform=T)
+                outs = [self.backend.align(self._clouds[q], self._clouds[c], 30, 1e-6, initial_transform=T, **gkw)
                         for (_, c), T in zip(chunk, starts)]
             else:
-                outs = [self.backend.align(self._clouds[q], self._clouds[c], 30, 1e-6) for _, c in chunk]   # :102-109
+                outs = [self.backend.align(self._clouds[q], self._clouds[c], 30, 1e-6, **gkw) for _, c in chunk]   # :102-109
             for (sc_dist, cand), r in zip(chunk, outs):
                 if r.converged and r.final_error < self.config.icp_fitness_threshold:   # :112
                     results.append(LoopClosureResult(self._frame_indices[q], self._frame_indices[cand],
                                                      np.asarray(r.transformation), sc_dist, r.final_error,
-                                                     int(shift[cand]) if guess else None))
+                                                     int(shift[cand]) if guess else None,
+                                                     getattr(r, "pairs", None) if gkw else None))
                     verified += 1
         return results
 
@@ -187,6 +211,9 @@ class StoreLoopClosureDetector:
         self._h = h
         if getattr(self.config, "yaw_guess", False):
             ctx._check(self._lib.icpmi_loop_set_yaw_guess(h, 1))
+        self._gated = float(getattr(self.config, "max_correspondence_distance", 0.0) or 0.0) > 0.0
+        if self._gated:
+            ctx._check(self._lib.icpmi_loop_set_gate(h, float(self.config.max_correspondence_distance)))
         for owner in (ctx, store):     # Context.close() and store.close() destroy it before the map
             if not hasattr(owner, "_loops"):
                 owner._loops = weakref.WeakSet()
@@ -198,6 +225,11 @@ class StoreLoopClosureDetector:
             self._h = None
 
     __del__ = close
+
+    def set_gate(self, max_distance):
+        """icpmi_loop_set_gate: the verifications' correspondence-distance gate from the next detect on (0: off)"""
+        self.ctx._check(self._lib.icpmi_loop_set_gate(self._h, float(max_distance)))
+        self._gated = float(max_distance) > 0.0   # (the caller's config object, which it may share, is left alone)
 
     def add_frame(self, store_frame, frame_idx):
         """loop_closure.hpp:54-60 for the cloud the store holds as frame `store_frame`"""
@@ -232,5 +264,12 @@ class StoreLoopClosureDetector:
             m = C.c_int64(0)
             self.ctx._check(self._lib.icpmi_loop_last_shifts(self._h, sh, n.value, C.byref(m)))
             shifts = [int(v) for v in sh[:m.value]]
+        pairs = [None] * n.value
+        if self._gated:
+            pr = (C.c_int64 * max(n.value, 1))()
+            m = C.c_int64(0)
+            self.ctx._check(self._lib.icpmi_loop_last_pairs(self._h, pr, n.value, C.byref(m)))
+            pairs = [int(v) for v in pr[:m.value]]
         return [LoopClosureResult(r.query_frame, r.match_frame, np.array(r.transform[:]).reshape(4, 4),
-                                  r.scan_context_distance, r.icp_fitness, s) for r, s in zip(buf[:n.value], shifts)]
+                                  r.scan_context_distance, r.icp_fitness, s, p)
+                for r, s, p in zip(buf[:n.value], shifts, pairs)]

@@ -46,7 +46,7 @@ def node_loop_config():
 
 def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, pose_graph_config=None,
              align=None, loop_backend=None, pose_graph=None, global_map=None, grid=None, map_voxel=1.0,
-             loop_on_device=False, raycast=False, counts=False, live=False, loop_yaw_guess=False):
+             loop_on_device=False, raycast=False, counts=False, live=False, loop_yaw_guess=False, loop_gate=None):
     """frames: sequence of N x 3 fp64 clouds (already downsampled).  Returns a SlamRun.  global_map: an object with
     add_frame, recent_clouds and finish (None: no map is built); grid: its occupancy grid config (None: defaults).
     loop_on_device: the detector is loop_closure.StoreLoopClosureDetector over global_map (a global_map.GlobalMap),
@@ -56,7 +56,9 @@ def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, po
     live: with a global_map, global_map.live_update(poses, grid) after each frame's pose is known and after each
     optimize, (frames_cast, rebuilt) of each in SlamRun.live_log; SlamRun.live = the live counts on the final poses.
     loop_yaw_guess: the detector (whichever is built) starts each verification from Scan Context's column shift
-    (LoopClosureConfig.yaw_guess; not in the reference node), so a street driven back the other way closes too."""
+    (LoopClosureConfig.yaw_guess; not in the reference node), so a street driven back the other way closes too.
+    loop_gate: metres (None: none); the detector's verifications run behind that correspondence-distance gate
+    (LoopClosureConfig.max_correspondence_distance; not in the reference node), so a return leg a lane aside closes."""
     if loop_on_device and loop_backend is not None:
         raise ValueError("loop_backend and loop_on_device=True both choose the detector")
     if align is None:
@@ -71,6 +73,8 @@ def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, po
     store = None                                                     # (the store the device detector indexes)
     loop_config = node_loop_config()
     loop_config.yaw_guess = bool(loop_yaw_guess)
+    if loop_gate is not None:
+        loop_config.max_correspondence_distance = float(loop_gate)
     if loop_on_device:
         from .global_map import GlobalMap
         store = global_map if global_map is not None else GlobalMap(ctx)
