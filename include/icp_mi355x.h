@@ -664,6 +664,67 @@ int icpmi_map_live_counts(icpmi_map *map, uint16_t *hits, uint16_t *misses, int8
                           icpmi_live_info *info);
 int icpmi_map_live_clear(icpmi_map *map);
 
+/* Ground segmentation of a scan in its SENSOR frame (not in the reference, which names it as future work,
+ * README.md:304), and the occupancy products built from a scan's obstacle rows instead of a band on world z.
+ * A polar grid of n_rings x n_sectors bins covers [min_range, max_range].  fp64, unfused, in the order written
+ * (scripts/ground_ref.py restates it byte for byte):
+ *   bin      range = sqrt(x*x + y*y), angle = atan2(y, x) + pi; ring = (int)((range - min_range) / ring_size) and
+ *            sector = (int)(angle / sector_size), each clamped to its last index, with ring_size = (max_range -
+ *            min_range) / n_rings and sector_size = 2 pi / n_sectors.  A row with a non-finite coordinate, or with
+ *            range < min_range or range > max_range, enters no bin and is ICPMI_GROUND_IGNORED.
+ *   pass 1   zmin[bin] = the least z of the bin's rows (independent of the row order).
+ *   walk     per sector, outward: gz = -sensor_height, gr = 0; at ring r with centre rc = min_range + (r + 0.5) *
+ *            ring_size, a bin that holds rows is accepted if fabs(zmin - gz) <= step_tol + max_slope * (rc - gr), and
+ *            then gz = zmin, gr = rc; in every case ground_z[bin] = gz.
+ *   pass 2   h = z - ground_z[bin]: ICPMI_GROUND_GROUND if h <= height_tol, else ICPMI_GROUND_OBSTACLE if clear_min <= h
+ *            <= clear_max, else ICPMI_GROUND_IGNORED.
+ * icpmi_ground_segment labels n rows in host memory, icpmi_ground_segment_device n rows in device memory; the outputs
+ * are host memory in both: labels (n bytes), height (n doubles: h, NaN for a row that entered no bin; may be NULL),
+ * ground_z (n_rings * n_sectors doubles, ring-major; may be NULL), info (may be NULL; bins_accepted counts the bins
+ * whose own minimum was taken as ground).  n == 0 is legal (xyz and labels may then be NULL).  One wait.
+ * ICPMI_ERR_ARG, before any device work and with nothing written: a config field that is not finite; n_rings < 1 or
+ * n_sectors < 1; n_rings * n_sectors > ICPMI_GROUND_MAX_BINS (the bins live in one compute unit's LDS); min_range < 0
+ * or max_range <= min_range; a negative max_slope, step_tol or height_tol; clear_max < clear_min. */
+#define ICPMI_GROUND_OBSTACLE 0
+#define ICPMI_GROUND_GROUND 1
+#define ICPMI_GROUND_IGNORED 2
+#define ICPMI_GROUND_MAX_BINS 20400
+typedef struct {
+    int32_t n_rings, n_sectors;
+    double min_range, max_range;
+    double sensor_height;            /* the prior: the ground lies this far below the sensor */
+    double max_slope, step_tol;
+    double height_tol;
+    double clear_min, clear_max;     /* the clearance band of an obstacle, over the ground */
+} icpmi_ground_config;
+typedef struct {
+    int64_t n_ground, n_obstacle, n_ignored, bins_accepted;
+} icpmi_ground_info;
+void icpmi_ground_config_default(icpmi_ground_config *cfg); /* 80, 180, 0.5, 80.5, 1.73, 0.15, 0.1, 0.2, 0.3, 2.0 */
+int icpmi_ground_segment(icpmi_ctx *ctx, const double *xyz, int64_t n, const icpmi_ground_config *cfg, uint8_t *labels,
+                         double *height, double *ground_z, icpmi_ground_info *info);
+int icpmi_ground_segment_device(icpmi_ctx *ctx, const double *d_xyz, int64_t n, const icpmi_ground_config *cfg,
+                                uint8_t *labels, double *height, double *ground_z, icpmi_ground_info *info);
+
+/* icpmi_map_set_ground(map, cfg): while a config is set (NULL turns it off; off after icpmi_map_create),
+ * icpmi_map_finish's cell set, icpmi_map_raycast, icpmi_map_raycast_counts and icpmi_map_live_update take as a frame's
+ * hits exactly its ICPMI_GROUND_OBSTACLE rows.  The grid's world-z band is not applied; every other test stays (0.5 <=
+ * r <= max_range from the frame's translation, a representable cell).  A row with another label marks nothing and
+ * casts no ray, as a row outside the band does without ground.  Stated as an equivalence: each product, its info
+ * included, is byte for byte that of a second store holding, frame by frame and in order, only the OBSTACLE rows, run
+ * without ground and with height_min = -DBL_MAX, height_max = DBL_MAX.  icpmi_map_world, the published voxel map of
+ * icpmi_map_finish and the loop-closure store are not affected.  The labels are a property of a frame's rows alone, so
+ * they survive an optimize: they are formed at the start of the first of those calls that needs them, for every frame
+ * not yet labelled, in one launch and one wait of its own (it tells the host which frames hold an OBSTACLE row), and
+ * kept until icpmi_map_set_ground is called again.  Every call to it, with the same config or another, also invalidates
+ * the live counts: the next icpmi_map_live_update rebuilds.  A bad config is ICPMI_ERR_ARG and changes nothing.
+ * With ground off every call is bit for bit what it is without this function.
+ * icpmi_map_ground_labels: *n_out = the frame's rows; labels (may be NULL with cap 0: the size alone) receives its
+ * cached bytes, formed first if need be; a cap below the rows is ICPMI_ERR_CAPACITY; without a ground config, or with a
+ * frame out of range, ICPMI_ERR_ARG. */
+int icpmi_map_set_ground(icpmi_map *map, const icpmi_ground_config *cfg);
+int icpmi_map_ground_labels(icpmi_map *map, int64_t frame, uint8_t *labels, int64_t cap, int64_t *n_out);
+
 /* Loop-closure detection over a global map's kept scans (slam::LoopClosureDetector, core/loop_closure.hpp:41-148),
  * with its database on the device: an entry is a store frame with a label (the node's frame_idx).  Each entry's
  * Scan Context descriptor lives in device memory; its rows stay in the store and are never copied to the host.

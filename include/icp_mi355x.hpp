@@ -953,6 +953,59 @@ struct LiveUpdate {
     int32_t plane_x0 = 0, plane_y0 = 0, plane_w = 0, plane_h = 0;
 };
 
+// Ground segmentation of a scan in its sensor frame (icpmi_ground_segment; not in the reference, which names it as
+// future work, README.md:304).  The defaults are icpmi_ground_config_default's.
+struct GroundConfig {
+    int n_rings = 80, n_sectors = 180;
+    double min_range = 0.5, max_range = 80.5;
+    double sensor_height = 1.73; // the prior: the ground lies this far below the sensor
+    double max_slope = 0.15, step_tol = 0.1;
+    double height_tol = 0.2;
+    double clear_min = 0.3, clear_max = 2.0; // the clearance band of an obstacle, over the ground
+};
+
+enum class GroundLabel : uint8_t { Obstacle = ICPMI_GROUND_OBSTACLE, Ground = ICPMI_GROUND_GROUND, Ignored = ICPMI_GROUND_IGNORED };
+
+// What ground_segment returns: a label per row, the row's height over its bin's ground (NaN for a row that entered no
+// bin), the ground height per bin (n_rings x n_sectors, ring-major) and the counts.
+struct GroundSegmentation {
+    std::vector<uint8_t> labels;
+    std::vector<double> height, ground_z;
+    int64_t n_ground = 0, n_obstacle = 0, n_ignored = 0, bins_accepted = 0;
+};
+
+namespace detail {
+inline icpmi_ground_config to_c(const GroundConfig &c)
+{
+    icpmi_ground_config k;
+    k.n_rings = c.n_rings, k.n_sectors = c.n_sectors;
+    k.min_range = c.min_range, k.max_range = c.max_range, k.sensor_height = c.sensor_height;
+    k.max_slope = c.max_slope, k.step_tol = c.step_tol, k.height_tol = c.height_tol;
+    k.clear_min = c.clear_min, k.clear_max = c.clear_max;
+    return k;
+}
+} // namespace detail
+
+inline GroundSegmentation ground_segment(Context &ctx, const PointCloud &scan, const GroundConfig &config = GroundConfig())
+{
+    const icpmi_ground_config k = detail::to_c(config);
+    GroundSegmentation out;
+    out.labels.resize(scan.size());
+    out.height.resize(scan.size());
+    out.ground_z.resize(static_cast<std::size_t>(std::max(k.n_rings, 0)) * static_cast<std::size_t>(std::max(k.n_sectors, 0)));
+    icpmi_ground_info info{};
+    const int rc = icpmi_ground_segment(ctx.get(), scan.data(), static_cast<int64_t>(scan.size()), &k, out.labels.data(),
+                                        out.height.data(), out.ground_z.data(), &info);
+    if (rc != ICPMI_OK) throw IcpError(rc, icpmi_last_error(ctx.get()));
+    out.n_ground = info.n_ground, out.n_obstacle = info.n_obstacle, out.n_ignored = info.n_ignored;
+    out.bins_accepted = info.bins_accepted;
+    return out;
+}
+inline GroundSegmentation ground_segment(const PointCloud &scan, const GroundConfig &config = GroundConfig())
+{
+    return ground_segment(default_context(), scan, config);
+}
+
 // The node's kept scans (downsampled_clouds_, slam_node.cpp:71,123) in device memory, and what it builds from them
 // with the optimised poses: rebuild_recent_clouds (:187-194), build_final_global_map (:196-209) with
 // rebuild_occupancy_grid (:223-229), and the map publish_global_map sends once complete (:235-238).  finish() rebuilds
@@ -1096,6 +1149,24 @@ public:
     }
     // forget the frames cast so far: the next live_update casts every used frame again
     void live_clear() { check(icpmi_map_live_clear(m_)); }
+    // icpmi_map_set_ground: from here on finish's cell set, raycast, raycast_counts and live_update take as a frame's
+    // hits its OBSTACLE rows instead of the grid's band on world z; clear_ground turns that off again.  Either way the
+    // next live_update rebuilds.
+    void set_ground(const GroundConfig &config)
+    {
+        const icpmi_ground_config k = detail::to_c(config);
+        check(icpmi_map_set_ground(m_, &k));
+    }
+    void clear_ground() { check(icpmi_map_set_ground(m_, nullptr)); }
+    // one frame's cached labels (GroundLabel's values), formed first if need be; needs a ground config
+    std::vector<uint8_t> ground_labels(std::size_t frame)
+    {
+        int64_t n = 0;
+        check(icpmi_map_ground_labels(m_, static_cast<int64_t>(frame), nullptr, 0, &n));
+        std::vector<uint8_t> out(static_cast<std::size_t>(n));
+        if (n) check(icpmi_map_ground_labels(m_, static_cast<int64_t>(frame), out.data(), n, &n));
+        return out;
+    }
     icpmi_map *get() const { return m_; }
     Context *context() const { return ctx_; }
 

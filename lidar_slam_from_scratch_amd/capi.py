@@ -40,6 +40,8 @@ EXPORTS = [
     "icpmi_loop_descriptor", "icpmi_loop_size", "icpmi_loop_clear",
     "icpmi_scan_context_distances_shift", "icpmi_sc_shift_transform", "icpmi_loop_set_yaw_guess", "icpmi_loop_last_shifts",
     "icpmi_align_gated", "icpmi_align_gated_device", "icpmi_align_gated_batch", "icpmi_loop_set_gate", "icpmi_loop_last_pairs",
+    "icpmi_ground_config_default", "icpmi_ground_segment", "icpmi_ground_segment_device", "icpmi_map_set_ground",
+    "icpmi_map_ground_labels",
 ]
 
 
@@ -146,6 +148,23 @@ class LiveInfo(C.Structure):
     """icpmi_live_info"""
     _fields_ = [("counts", CountsInfo), ("frames_cast", C.c_int64), ("rebuilt", C.c_int32), ("moved", C.c_int32),
                 ("plane_x0", C.c_int32), ("plane_y0", C.c_int32), ("plane_w", C.c_int32), ("plane_h", C.c_int32)]
+
+
+GROUND_OBSTACLE, GROUND_GROUND, GROUND_IGNORED = 0, 1, 2   # ICPMI_GROUND_*
+GROUND_MAX_BINS = 20400                                    # ICPMI_GROUND_MAX_BINS
+
+
+class GroundConfig(C.Structure):
+    """icpmi_ground_config"""
+    _fields_ = [("n_rings", C.c_int32), ("n_sectors", C.c_int32), ("min_range", C.c_double), ("max_range", C.c_double),
+                ("sensor_height", C.c_double), ("max_slope", C.c_double), ("step_tol", C.c_double),
+                ("height_tol", C.c_double), ("clear_min", C.c_double), ("clear_max", C.c_double)]
+
+
+class GroundInfo(C.Structure):
+    """icpmi_ground_info"""
+    _fields_ = [("n_ground", C.c_int64), ("n_obstacle", C.c_int64), ("n_ignored", C.c_int64),
+                ("bins_accepted", C.c_int64)]
 
 
 class PoseGraphConfig(C.Structure):
@@ -326,6 +345,13 @@ def load_library(path=None):
     L.icpmi_map_live_counts.argtypes = [vp, C.POINTER(C.c_uint16), C.POINTER(C.c_uint16), C.POINTER(C.c_int8), C.c_int64,
                                         C.POINTER(LiveInfo)]
     L.icpmi_map_live_clear.argtypes = [vp]
+    u8p = C.POINTER(C.c_uint8)
+    L.icpmi_ground_config_default.argtypes = [C.POINTER(GroundConfig)]
+    L.icpmi_ground_config_default.restype = None
+    L.icpmi_ground_segment.argtypes = [vp, dp, C.c_int64, C.POINTER(GroundConfig), u8p, dp, dp, C.POINTER(GroundInfo)]
+    L.icpmi_ground_segment_device.argtypes = [vp, vp, C.c_int64, C.POINTER(GroundConfig), u8p, dp, dp, C.POINTER(GroundInfo)]
+    L.icpmi_map_set_ground.argtypes = [vp, C.POINTER(GroundConfig)]
+    L.icpmi_map_ground_labels.argtypes = [vp, C.c_int64, u8p, C.c_int64, i64p]
     L.icpmi_loop_config_default.argtypes = [C.POINTER(LoopConfig)]
     L.icpmi_loop_config_default.restype = None
     L.icpmi_loop_create.argtypes = [vp, C.POINTER(LoopConfig), C.POINTER(vp)]

@@ -46,6 +46,7 @@
 #include "raycount.h"
 #include "live_plane.h"
 #include "live_counts.h"
+#include "ground.h"
 #include "loop_store.h"
 #include "pose_graph.h"
 
@@ -3921,6 +3922,108 @@ int icpmi_pose_graph_size(const icpmi_pose_graph *g, int64_t *num_poses, int64_t
 } // extern "C"
 
 // ======================================================================================================================
+// Ground segmentation of a scan in its sensor frame (ground.h).
+
+static_assert(kGroundMaxBins == ICPMI_GROUND_MAX_BINS && kGroundObstacle == ICPMI_GROUND_OBSTACLE &&
+                  kGroundGround == ICPMI_GROUND_GROUND && kGroundIgnored == ICPMI_GROUND_IGNORED,
+              "the header states these");
+
+namespace {
+
+int ground_check(icpmi_ctx *ctx, const icpmi_ground_config *c)
+{
+    if (!c) return fail(ctx, ICPMI_ERR_NULL, "the ground config is NULL");
+    for (double v : {c->min_range, c->max_range, c->sensor_height, c->max_slope, c->step_tol, c->height_tol, c->clear_min, c->clear_max})
+        if (!std::isfinite(v)) return fail(ctx, ICPMI_ERR_ARG, "a ground config field is not finite");
+    if (c->n_rings < 1 || c->n_sectors < 1) return fail(ctx, ICPMI_ERR_ARG, "n_rings and n_sectors must be at least 1");
+    if ((int64_t)c->n_rings * (int64_t)c->n_sectors > kGroundMaxBins)
+        return fail(ctx, ICPMI_ERR_ARG, "n_rings * n_sectors must be at most %d", kGroundMaxBins);
+    if (c->min_range < 0.0 || !(c->max_range > c->min_range)) return fail(ctx, ICPMI_ERR_ARG, "0 <= min_range < max_range is required");
+    if (c->max_slope < 0.0 || c->step_tol < 0.0 || c->height_tol < 0.0)
+        return fail(ctx, ICPMI_ERR_ARG, "max_slope, step_tol and height_tol must not be negative");
+    if (c->clear_max < c->clear_min) return fail(ctx, ICPMI_ERR_ARG, "clear_max < clear_min");
+    return ICPMI_OK;
+}
+
+// Queue k_ground_label for `scans` scans of `store` (checked config).
+int ground_queue(icpmi_ctx *ctx, const icpmi_ground_config *c, const double *store, const GroundFrame *frames_d, int64_t scans,
+                 uint8_t *labels, double *height, double *ground_z, GroundCounts *counts)
+{
+    const GroundParams p{c->n_rings,  c->n_sectors,   c->min_range, c->max_range, c->sensor_height,
+                         c->max_slope, c->step_tol, c->height_tol, c->clear_min, c->clear_max};
+    const size_t lds = sizeof(unsigned long long) * (size_t)c->n_rings * (size_t)c->n_sectors;
+    if (lds > 64 * 1024) // dynamic LDS past 64 KiB has to be allowed first
+        HIP_TRY(ctx, hipFuncSetAttribute((const void *)k_ground_label, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         (int)sizeof(unsigned long long) * kGroundMaxBins));
+    hipLaunchKernelGGL(k_ground_label, dim3((unsigned)scans), dim3(kGroundThreads), lds, ctx->stream, store, frames_d, p, labels,
+                       height, ground_z, counts);
+    HIP_TRY(ctx, hipGetLastError());
+    return ICPMI_OK;
+}
+
+int ground_segment(icpmi_ctx *ctx, const double *xyz, bool on_device, int64_t n, const icpmi_ground_config *cfg, uint8_t *labels,
+                   double *height, double *ground_z, icpmi_ground_info *info)
+{
+    int rc;
+    if ((rc = check_common(ctx))) return rc;
+    if ((rc = ground_check(ctx, cfg))) return rc;
+    if (n < 0 || n > 700000000) return fail(ctx, ICPMI_ERR_ARG, "n out of range");
+    if (n > 0 && (!xyz || !labels)) return fail(ctx, ICPMI_ERR_NULL, "null argument");
+    Range range("icpmi:ground_segment");
+    hipStream_t s = ctx->stream;
+    const size_t un = (size_t)n, bins = (size_t)cfg->n_rings * (size_t)cfg->n_sectors;
+    // the launch's outputs in one buffer: the frame table, the counts, ground_z, height, labels
+    const size_t o_counts = sizeof(GroundFrame), o_gz = o_counts + sizeof(GroundCounts), o_h = o_gz + sizeof(double) * bins,
+                 o_lab = o_h + sizeof(double) * un;
+    if ((rc = reserve(ctx, ctx->stage_b, o_lab + un))) return rc;
+    char *out = (char *)ctx->stage_b.p;
+    const double *rows = xyz;
+    if (!on_device && n > 0) {
+        if ((rc = reserve(ctx, ctx->stage_a, sizeof(double) * 3 * un))) return rc;
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->stage_a.p, xyz, sizeof(double) * 3 * un, hipMemcpyHostToDevice, s));
+        rows = (const double *)ctx->stage_a.p;
+    }
+    const GroundFrame f{0, (int32_t)n, 0};
+    GroundCounts cnt{};
+    HIP_TRY(ctx, hipMemcpyAsync(out, &f, sizeof(f), hipMemcpyHostToDevice, s));
+    if ((rc = ground_queue(ctx, cfg, rows, (const GroundFrame *)out, 1, (uint8_t *)(out + o_lab), height ? (double *)(out + o_h) : nullptr,
+                           ground_z ? (double *)(out + o_gz) : nullptr, (GroundCounts *)(out + o_counts))))
+        return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(&cnt, out + o_counts, sizeof(cnt), hipMemcpyDeviceToHost, s));
+    if (ground_z) HIP_TRY(ctx, hipMemcpyAsync(ground_z, out + o_gz, sizeof(double) * bins, hipMemcpyDeviceToHost, s));
+    if (height && n > 0) HIP_TRY(ctx, hipMemcpyAsync(height, out + o_h, sizeof(double) * un, hipMemcpyDeviceToHost, s));
+    if (n > 0) HIP_TRY(ctx, hipMemcpyAsync(labels, out + o_lab, un, hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s)); // the call's one wait
+    HIP_TRY(ctx, hipGetLastError());
+    if (info) *info = icpmi_ground_info{(int64_t)cnt.n_ground, (int64_t)cnt.n_obstacle, (int64_t)cnt.n_ignored, (int64_t)cnt.bins_accepted};
+    return ICPMI_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+void icpmi_ground_config_default(icpmi_ground_config *cfg)
+{
+    if (!cfg) return;
+    *cfg = icpmi_ground_config{80, 180, 0.5, 80.5, 1.73, 0.15, 0.1, 0.2, 0.3, 2.0};
+}
+
+int icpmi_ground_segment(icpmi_ctx *ctx, const double *xyz, int64_t n, const icpmi_ground_config *cfg, uint8_t *labels,
+                         double *height, double *ground_z, icpmi_ground_info *info)
+{
+    return ground_segment(ctx, xyz, false, n, cfg, labels, height, ground_z, info);
+}
+
+int icpmi_ground_segment_device(icpmi_ctx *ctx, const double *d_xyz, int64_t n, const icpmi_ground_config *cfg, uint8_t *labels,
+                                double *height, double *ground_z, icpmi_ground_info *info)
+{
+    return ground_segment(ctx, d_xyz, true, n, cfg, labels, height, ground_z, info);
+}
+
+} // extern "C"
+
+// ======================================================================================================================
 // Global map (slam_node.cpp:187-238): the node's kept scans (downsampled_clouds_) in one device arena, and the world
 // points, cell set and published map of any prefix of them from one launch of k_map_world (global_map.h).
 
@@ -3957,6 +4060,12 @@ struct icpmi_map {
     DevBuf d_counts, d_counts_next;      // the last successful counts (hits, misses, probability); those a call is building
     icpmi_counts_info counts{};          // the last successful counts' (all zeros before the first)
     LiveCounts live;                     // icpmi_map_live_update: the counts that persist (live_counts.h)
+    // icpmi_map_set_ground (ground.h): while ground_on, a frame's hits are its OBSTACLE rows
+    bool ground_on = false;
+    icpmi_ground_config ground{};
+    int64_t ground_frames = 0;           // frames [0, ground_frames) are labelled
+    std::vector<int32_t> ground_hits;    // per labelled frame its OBSTACLE rows
+    DevBuf d_labels, d_ground_tab;       // one byte per store row; a labelling launch's frame table and counts
 };
 
 namespace {
@@ -4052,11 +4161,19 @@ int map_queue_world(icpmi_map *m, const double *poses, int64_t first, int64_t la
     const int64_t t0 = m->tile0[first], nt = m->tile0[last] - t0;
     GridParams g{0.0, 0.0, 1.0, 0.0, 0.0, 0.0};
     if (grid) g = GridParams{0.0, 0.0, grid->resolution, grid->height_min, grid->height_max, grid->max_range};
+    const bool mask = keys && grid && m->ground_on; // the band is open; the rows that are not OBSTACLE lose their keys
+    if (mask) g.height_min = -std::numeric_limits<double>::max(), g.height_max = std::numeric_limits<double>::max();
     if (nt > 0)
         hipLaunchKernelGGL(k_map_world, dim3((unsigned)nt), dim3(256), 0, s, (const double *)m->d_rows.p,
                            (const MapTile *)m->d_tiles.p + t0, (const double *)m->d_poses.p, (int32_t)first, m->row0[first],
                            world, keys, g);
     HIP_TRY(ctx, hipGetLastError());
+    const size_t rows = (size_t)(m->row0[last] - m->row0[first]);
+    if (mask && rows > 0) {
+        hipLaunchKernelGGL(k_ground_mask, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, keys,
+                           (const uint8_t *)m->d_labels.p + m->row0[first], rows);
+        HIP_TRY(ctx, hipGetLastError());
+    }
     return ICPMI_OK;
 }
 
@@ -4086,6 +4203,46 @@ int ray_plan_grid(icpmi_ctx *ctx, const icpmi_grid_config *grid, int *R)
     return ICPMI_OK;
 }
 
+// With ground set: label the frames that are not labelled yet (ground.h), in one launch, and wait for their OBSTACLE
+// counts.  The labels are indexed by store row; on any error the labelled frames are those from before.
+int map_ground_ready(icpmi_map *m)
+{
+    icpmi_ctx *ctx = m->ctx;
+    const int64_t frames = map_frames(m), first = m->ground_frames, nf = frames - first;
+    if (!m->ground_on || nf == 0) return ICPMI_OK;
+    Range range("icpmi:map_ground_labels");
+    hipStream_t s = ctx->stream;
+    int rc;
+    const size_t used = (size_t)m->row0[first], need = (size_t)m->row0[frames];
+    DevBuf grown; // the new label arena, if it has to grow: the labelled frames' bytes move
+    struct Drop {
+        DevBuf &b;
+        ~Drop() { release(b); }
+    } drop{grown};
+    if (need > m->d_labels.cap) {
+        HIP_TRY(ctx, reserve_raw(grown, std::max(need, 2 * m->d_labels.cap)));
+        if (used) HIP_TRY(ctx, hipMemcpyAsync(grown.p, m->d_labels.p, used, hipMemcpyDeviceToDevice, s));
+    }
+    uint8_t *labels = (uint8_t *)(grown.p ? grown.p : m->d_labels.p);
+    const size_t tab = sizeof(GroundFrame) * (size_t)nf;
+    if ((rc = reserve(ctx, m->d_ground_tab, tab + sizeof(GroundCounts) * (size_t)nf))) return rc;
+    std::vector<GroundFrame> table((size_t)nf);
+    for (int64_t i = 0; i < nf; ++i) table[(size_t)i] = GroundFrame{m->row0[first + i], (int32_t)(m->row0[first + i + 1] - m->row0[first + i]), 0};
+    std::vector<GroundCounts> counts((size_t)nf);
+    GroundCounts *counts_d = (GroundCounts *)((char *)m->d_ground_tab.p + tab);
+    HIP_TRY(ctx, hipMemcpyAsync(m->d_ground_tab.p, table.data(), tab, hipMemcpyHostToDevice, s));
+    if ((rc = ground_queue(ctx, &m->ground, (const double *)m->d_rows.p, (const GroundFrame *)m->d_ground_tab.p, nf, labels, nullptr,
+                           nullptr, counts_d)))
+        return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(counts.data(), counts_d, sizeof(GroundCounts) * (size_t)nf, hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s)); // the labelling's wait: which frames hold an OBSTACLE row
+    HIP_TRY(ctx, hipGetLastError());
+    if (grown.p) std::swap(m->d_labels, grown); // (the old arena goes with `drop`)
+    for (const GroundCounts &c : counts) m->ground_hits.push_back((int32_t)c.n_obstacle);
+    m->ground_frames = frames;
+    return ICPMI_OK;
+}
+
 // Frames [first, last): their sensor cells (each within range), their table entries behind *frames with row0 counted
 // from frame `first`'s first row (k_map_world's keys for those frames), and *span widened by those that hold rows.
 int ray_plan_frames(icpmi_map *m, const double *poses, double res, int R, int64_t first, int64_t last, RaySpan *span,
@@ -4098,7 +4255,8 @@ int ray_plan_frames(icpmi_map *m, const double *poses, double res, int R, int64_
         const double cx = std::floor(poses[16 * i + 3] / res), cy = std::floor(poses[16 * i + 7] / res);
         if (!(std::fabs(cx) <= cell_max && std::fabs(cy) <= cell_max))
             return fail(m->ctx, ICPMI_ERR_ARG, "frame %lld's sensor cell is out of range", (long long)i);
-        const int64_t rows = m->row0[i + 1] - m->row0[i];
+        // (with ground set a frame holds rows if it holds an OBSTACLE row: the others are cast as empty frames)
+        const int64_t rows = m->ground_on && m->ground_hits[(size_t)i] == 0 ? 0 : m->row0[i + 1] - m->row0[i];
         frames->push_back(RayFrame{m->row0[i] - m->row0[first], (int32_t)rows, (int32_t)cx, (int32_t)cy, 0});
         if (rows == 0) continue;
         span->lo_x = std::min<int64_t>(span->lo_x, (int64_t)cx), span->hi_x = std::max<int64_t>(span->hi_x, (int64_t)cx);
@@ -4127,10 +4285,12 @@ int ray_plan(icpmi_map *m, const double *poses, int64_t n_poses, const icpmi_gri
     if ((rc = map_check_poses(m, poses, n_poses, &last))) return rc;
     if (last > max_frames)
         return fail(ctx, ICPMI_ERR_ARG, "%lld frames would be used: at most %lld", (long long)last, (long long)max_frames);
+    if ((rc = map_ground_ready(m))) return rc;
     std::vector<RayFrame> frames;
     RaySpan span;
     if ((rc = ray_plan_frames(m, poses, grid->resolution, R, 0, last, &span, &frames))) return rc;
-    out->R = R, out->last = last, out->rows = m->row0[last];
+    // (a frame that holds rows widens the span; with ground set a store with rows may hold no such frame)
+    out->R = R, out->last = last, out->rows = span.lo_x <= span.hi_x ? m->row0[last] : 0;
     if (out->rows > 0 && (rc = ray_plan_plane(ctx, span, R, &out->pl))) return rc;
     out->frames = std::move(frames);
     return ICPMI_OK;
@@ -4159,7 +4319,7 @@ void icpmi_map_destroy(icpmi_map *m)
     (void)hipStreamSynchronize(m->ctx->stream);
     for (DevBuf *b : {&m->d_rows, &m->d_tiles, &m->d_poses, &m->d_world, &m->d_ray_frames, &m->d_ray_planes, &m->d_raster,
                       &m->d_raster_next, &m->d_count_plane, &m->d_count_scratch, &m->d_counts, &m->d_counts_next, &m->live.d_plane,
-                      &m->live.d_bounds, &m->live.d_windows, &m->live.d_out})
+                      &m->live.d_bounds, &m->live.d_windows, &m->live.d_out, &m->d_labels, &m->d_ground_tab})
         release(*b);
     delete m;
 }
@@ -4239,6 +4399,7 @@ int icpmi_map_finish(icpmi_map *m, const double *poses, int64_t n_poses, const i
     const bool want_map = map_out && voxel_size > 0.0;
     if (n_map) *n_map = 0;
     const int64_t n64 = m->row0[last];
+    if (grid && n64 > 0 && (rc = map_ground_ready(m))) return rc;
     if (n64 == 0 || (!grid && !want_map)) {
         if (grid) ctx->grid_n = 0; // occupied_cells_.clear() and nothing inserted
         if (n_cells) *n_cells = ctx->grid_n;
@@ -4620,12 +4781,16 @@ int icpmi_map_live_update(icpmi_map *m, const double *poses, int64_t n_poses, co
     if ((rc = map_check_finite(m, poses, first, used))) return rc;
     if (used > kCountMaxFrames)
         return fail(ctx, ICPMI_ERR_ARG, "%lld frames would be used: at most %lld", (long long)used, (long long)kCountMaxFrames);
+    if ((rc = map_ground_ready(m))) return rc;
     RaySpan span;
     if (inc) span = RaySpan{L.span[0], L.span[1], L.span[2], L.span[3]};
     std::vector<RayFrame> frames;
     if ((rc = ray_plan_frames(m, poses, grid->resolution, R, first, used, &span, &frames))) return rc;
     RayPlane exact{0, 0, 0, 0, 0};
-    if (m->row0[used] > 0 && (rc = ray_plan_plane(ctx, span, R, &exact))) return rc;
+    // (a frame that holds rows has widened the span: without ground, row0[used] > 0 says the same)
+    if (span.lo_x <= span.hi_x && (rc = ray_plan_plane(ctx, span, R, &exact))) return rc;
+    bool new_rows = false;              // does a frame to cast hold rows?
+    for (const RayFrame &f : frames) new_rows |= f.rows > 0;
     icpmi_live_info out{};
     if (inc && used == L.n_cast) {  // nothing new
         out = L.info;
@@ -4646,7 +4811,7 @@ int icpmi_map_live_update(icpmi_map *m, const double *poses, int64_t n_poses, co
     L.info = icpmi_live_info{};
     CountBounds b = L.bounds;
     bool moved = false;
-    if (m->row0[used] - m->row0[first] > 0) {
+    if (new_rows) {
         std::vector<DevBuf> old;
         rc = live_cast(m, poses, grid, R, !inc, first, used, frames, box, &moved, old, &b);
         for (DevBuf &o : old) release(o);
@@ -4711,6 +4876,39 @@ int icpmi_map_live_clear(icpmi_map *m)
     L.bounds = kCountNone;
     L.info = icpmi_live_info{};
     return ICPMI_OK;            // the buffers stay for the next plane
+}
+
+int icpmi_map_set_ground(icpmi_map *m, const icpmi_ground_config *cfg)
+{
+    if (!m) return ICPMI_ERR_NULL;
+    int rc;
+    if (cfg && (rc = ground_check(m->ctx, cfg))) return rc;
+    m->ground_on = cfg != nullptr;
+    if (cfg) m->ground = *cfg;
+    m->ground_frames = 0;       // the labels are formed again by the next call that needs them
+    m->ground_hits.clear();
+    m->live.valid = false;      // the next icpmi_map_live_update rebuilds
+    return ICPMI_OK;
+}
+
+int icpmi_map_ground_labels(icpmi_map *m, int64_t frame, uint8_t *labels, int64_t cap, int64_t *n_out)
+{
+    if (!m) return ICPMI_ERR_NULL;
+    icpmi_ctx *ctx = m->ctx;
+    int rc;
+    if ((rc = check_common(ctx))) return rc;
+    if (!n_out) return fail(ctx, ICPMI_ERR_NULL, "null argument");
+    if (!m->ground_on) return fail(ctx, ICPMI_ERR_ARG, "no ground config is set: call icpmi_map_set_ground first");
+    if (frame < 0 || frame >= map_frames(m)) return fail(ctx, ICPMI_ERR_ARG, "frame %lld is out of range", (long long)frame);
+    const int64_t rows = m->row0[frame + 1] - m->row0[frame];
+    *n_out = rows;
+    if (!labels) return ICPMI_OK;
+    if (cap < rows) return fail(ctx, ICPMI_ERR_CAPACITY, "labels holds %lld rows, needs %lld", (long long)cap, (long long)rows);
+    if ((rc = map_ground_ready(m))) return rc;
+    if (rows == 0) return ICPMI_OK;
+    HIP_TRY(ctx, hipMemcpyAsync(labels, (const uint8_t *)m->d_labels.p + m->row0[frame], (size_t)rows, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return ICPMI_OK;
 }
 
 } // extern "C"

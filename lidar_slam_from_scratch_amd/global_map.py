@@ -186,3 +186,20 @@ class GlobalMap:
     def live_clear(self):
         """forget the frames cast so far: the next live_update casts every used frame again"""
         self.ctx._check(self._lib.icpmi_map_live_clear(self._h))
+
+    def set_ground(self, ground):
+        """icpmi_map_set_ground: with a ground.GroundConfig (or capi.GroundConfig), finish's cell set, raycast,
+        raycast_counts and live_update take as a frame's hits its OBSTACLE rows instead of the grid's world-z band;
+        None turns it off.  Either way the next live_update rebuilds."""
+        g = ground.to_c() if hasattr(ground, "to_c") else ground
+        self.ctx._check(self._lib.icpmi_map_set_ground(self._h, C.byref(g) if g is not None else None))
+
+    def ground_labels(self, frame):
+        """one frame's cached labels (uint8 per row: capi.GROUND_OBSTACLE, GROUND_GROUND, GROUND_IGNORED), formed first if
+        need be; needs a ground config"""
+        n = C.c_int64(0)
+        self.ctx._check(self._lib.icpmi_map_ground_labels(self._h, int(frame), None, 0, C.byref(n)))
+        out = np.empty(n.value, dtype=np.uint8)
+        self.ctx._check(self._lib.icpmi_map_ground_labels(self._h, int(frame), out.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                          n.value, C.byref(n)))
+        return out

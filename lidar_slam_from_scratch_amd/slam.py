@@ -46,7 +46,8 @@ def node_loop_config():
 
 def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, pose_graph_config=None,
              align=None, loop_backend=None, pose_graph=None, global_map=None, grid=None, map_voxel=1.0,
-             loop_on_device=False, raycast=False, counts=False, live=False, loop_yaw_guess=False, loop_gate=None):
+             loop_on_device=False, raycast=False, counts=False, live=False, loop_yaw_guess=False, loop_gate=None,
+             ground=None):
     """frames: sequence of N x 3 fp64 clouds (already downsampled).  Returns a SlamRun.  global_map: an object with
     add_frame, recent_clouds and finish (None: no map is built); grid: its occupancy grid config (None: defaults).
     loop_on_device: the detector is loop_closure.StoreLoopClosureDetector over global_map (a global_map.GlobalMap),
@@ -58,7 +59,10 @@ def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, po
     loop_yaw_guess: the detector (whichever is built) starts each verification from Scan Context's column shift
     (LoopClosureConfig.yaw_guess; not in the reference node), so a street driven back the other way closes too.
     loop_gate: metres (None: none); the detector's verifications run behind that correspondence-distance gate
-    (LoopClosureConfig.max_correspondence_distance; not in the reference node), so a return leg a lane aside closes."""
+    (LoopClosureConfig.max_correspondence_distance; not in the reference node), so a return leg a lane aside closes.
+    ground: a ground.GroundConfig (None: none); with a global_map, global_map.set_ground(ground) before the first
+    frame, so the cell set, raster, counts and live counts take each frame's OBSTACLE rows as its hits (not in the
+    reference node).  Ignored without a global_map."""
     if loop_on_device and loop_backend is not None:
         raise ValueError("loop_backend and loop_on_device=True both choose the detector")
     if align is None:
@@ -69,6 +73,8 @@ def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, po
     if pose_graph is None:
         from .pose_graph import PoseGraph
         pose_graph = PoseGraph(ctx, pose_graph_config)
+    if ground is not None and global_map is not None:
+        global_map.set_ground(ground)
     run = SlamRun()
     store = None                                                     # (the store the device detector indexes)
     loop_config = node_loop_config()

@@ -148,6 +148,85 @@ def _raycast(origin, R, scene, beams=64, azimuths=1800, max_range=80.0):
     return (world - origin) @ R  # sensor frame
 
 
+# The street on a grade: the road is level for x <= 0 and climbs at `grade` beyond.  What ground segmentation is for
+# (csrc/ground.h): on the climb the road itself rises into a band on world z.
+
+RAMP_GRADE = 0.06
+
+
+def ramp_road_z(x, grade=RAMP_GRADE):
+    """world z of the road at world x (the level part lies at -1.73, the ground plane of _raycast)"""
+    return -1.73 + grade * np.maximum(np.asarray(x, dtype=np.float64), 0.0)
+
+
+def _ramp_scene(seed=3, grade=RAMP_GRADE, piece=5.0):
+    """_scene's boxes and walls, each lifted to the road under its centre; the long walls in pieces of `piece` metres
+    so that they follow the road.  A lifted object reaches down to the road at its low end: nothing floats."""
+    out = []
+    for lo, hi in _scene(seed):
+        n = max(1, int(np.ceil((hi[0] - lo[0]) / piece)))
+        edges = np.linspace(lo[0], hi[0], n + 1)
+        for x0, x1 in zip(edges[:-1], edges[1:]):
+            l, h = lo.copy(), hi.copy()
+            l[0], h[0] = x0, x1
+            lift = float(ramp_road_z(0.5 * (x0 + x1), grade)) + 1.73
+            h[2] += lift
+            l[2] = float(ramp_road_z(x0, grade))
+            out.append((l, h))
+    return out
+
+
+def ramp_pose(frame, n_frames=41, x0=-30.0, x1=50.0, grade=RAMP_GRADE):
+    """The sensor's true pose at `frame` of a straight drive from x0 to x1: 1.73 m above the road along its normal and
+    pitched with it."""
+    x = x0 + (x1 - x0) * frame / max(n_frames - 1, 1)
+    theta = np.arctan(grade) if x > 0.0 else 0.0
+    T = np.eye(4)
+    T[:3, :3] = rotvec_to_matrix((0.0, -theta, 0.0))            # nose up on the climb
+    T[:3, 3] = np.array([x, 0.0, float(ramp_road_z(x, grade))]) + 1.73 * T[:3, 2]
+    return T
+
+
+def _raycast_ramp(origin, R, scene, grade=RAMP_GRADE, beams=64, azimuths=1800, max_range=80.0):
+    """_raycast over the two road planes and `scene` -> (returns in the sensor frame, per return: True where it hit an
+    object, False where it hit the road)"""
+    el = np.deg2rad(np.linspace(-24.8, 2.0, beams))
+    az = np.linspace(-np.pi, np.pi, azimuths, endpoint=False) + np.pi / azimuths   # half a step off the x axis: no
+    ce, se = np.cos(el)[:, None], np.sin(el)[:, None]                              # beam on a polar sector's edge
+    d_local = np.stack([ce * np.cos(az)[None, :], ce * np.sin(az)[None, :],
+                        np.broadcast_to(se, (beams, azimuths))], axis=-1).reshape(-1, 3)
+    d = d_local @ R.T
+    t_hit = np.full(d.shape[0], np.inf)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        t_level = (-1.73 - origin[2]) / d[:, 2]                                  # z = -1.73, where x <= 0
+        t_climb = (-1.73 + grade * origin[0] - origin[2]) / (d[:, 2] - grade * d[:, 0])   # z = -1.73 + grade x, x > 0
+    for t, side in ((t_level, -1.0), (t_climb, 1.0)):
+        x = origin[0] + d[:, 0] * t
+        ok = (t > 0) & np.isfinite(t) & ((x > 0.0) if side > 0 else (x <= 0.0)) & (t < t_hit)
+        t_hit[ok] = t[ok]
+    is_object = np.zeros(d.shape[0], dtype=bool)
+    for lo, hi in scene:
+        with np.errstate(divide="ignore", invalid="ignore"):
+            t1 = (lo - origin) / d
+            t2 = (hi - origin) / d
+        tmin = np.nanmax(np.minimum(t1, t2), axis=1)
+        tmax = np.nanmin(np.maximum(t1, t2), axis=1)
+        hit = (tmax >= tmin) & (tmax > 0) & (tmin > 0) & (tmin < t_hit)
+        t_hit = np.where(hit, tmin, t_hit)
+        is_object |= hit
+    keep = np.isfinite(t_hit) & (t_hit <= max_range) & (t_hit > 0.5)
+    world = origin + d[keep] * t_hit[keep, None]
+    return (world - origin) @ R, is_object[keep]
+
+
+def ramp_frame(frame, n_frames=41, beams=64, azimuths=600, seed=3, grade=RAMP_GRADE, **drive):
+    """One scan of the ramp drive, without noise or voxel filter -> (rows in the sensor frame, per row True where it
+    hit an object and False where it hit the road, the sensor's true pose)"""
+    T = ramp_pose(frame, n_frames, grade=grade, **drive)
+    pts, is_object = _raycast_ramp(T[:3, 3], T[:3, :3], _ramp_scene(seed, grade), grade, beams=beams, azimuths=azimuths)
+    return pts, is_object, T
+
+
 def voxel_centroids(points, voxel):
     """Centroid per occupied voxel, key = floor(coord / voxel) (file_utils.cpp:148-196).
     Output is sorted by key: the reference's order is std::unordered_map iteration
