@@ -52,7 +52,12 @@ extern "C" {
 /* nearest-neighbour search engines (all return the exact fp64 nearest neighbour) */
 #define ICPMI_SEARCH_AUTO 0
 #define ICPMI_SEARCH_EXACT_F64 1     /* fp64 brute force, SGPR-broadcast targets */
-#define ICPMI_SEARCH_MFMA_BF16 2     /* bf16 MFMA coarse pass over ALL pairs + certified fp64 resolve */
+#define ICPMI_SEARCH_MFMA_BF16 2     /* bf16 MFMA coarse pass over ALL pairs + certified fp64 resolve.  "All pairs" names
+                                        the coarse pass of the ICP loop (and of the stand-alone searches): the k-NN setup
+                                        of a target -- its 20-NN among itself, for the normals -- is culled like engine
+                                        3's on targets of more than 12 splits (24,576 points) in both MFMA engines, with
+                                        the same lists and normals bit for bit; ICPMI_KNN_CULL=0 in the environment keeps
+                                        that setup on all pairs too */
 #define ICPMI_SEARCH_MFMA_PRUNED 3   /* the same, skipping (32-row tile, target split) pairs whose bounding
                                         boxes are farther apart than the tile's known neighbour distance -- the
                                         rule of kdtree.hpp:139,177 applied to groups; same exact result, not an
@@ -120,6 +125,9 @@ typedef struct {
     int64_t nn_coarse_skipped;                       /* ... those passes whose coarse launch had no row to list, every workgroup left at
                                                         once.  With list reuse nn_pairs counts the pairs of the listed rows' workgroups;
                                                         both are counted on the device with profiling on only */
+    int64_t knn_culled_launches;                     /* k-NN setup of a target (normal estimation): coarse passes run over the (32-row
+                                                        group, split) pairs that survive the box test instead of all pairs -- both MFMA
+                                                        engines on targets of more than 12 splits, engine 3 at every size */
 } icpmi_profile;
 
 void icpmi_options_default(icpmi_options *opt);     /* device 0, normal_k 20 (icp.hpp:170), search AUTO or the

@@ -97,7 +97,8 @@ class Profile(C.Structure):
                 ("nn_group_pairs", C.c_int64),
                 ("nn_group_pairs_run", C.c_int64),
                 ("exchange_ms", C.c_double), ("exchange_launches", C.c_int64), ("coarse_minima_bytes", C.c_int64),
-                ("nn_rows_listed", C.c_int64), ("nn_coarse_skipped", C.c_int64)]
+                ("nn_rows_listed", C.c_int64), ("nn_coarse_skipped", C.c_int64),
+                ("knn_culled_launches", C.c_int64)]
 
 
 MAX_RANKS_INFO = 64

@@ -793,6 +793,25 @@ bool knn_lists_enabled()
     }();
     return on;
 }
+// The target's k-NN setup on the all-pairs engine culls its coarse pass like the culled engine's does (k_knn_group_cull +
+// k_nn_coarse_groups<true>, nn_culled.h: they read the sorted target, the rows' bounds and the split boxes, which
+// prepare_nn builds for both engines) once the target has more than kKnnCullFromSplits splits -- the size from which AUTO
+// takes the culled engine (kAutoCulledFrom, profiles/r4_final/engine_threshold.json); at a dozen splits or fewer the
+// all-pairs form stays, launch for launch.  ICPMI_KNN_CULL=0: the all-pairs coarse pass at every size (the reference leg of
+// tests/test_gpu_knn_cull_allpairs.py).  The ICP loop of the engine is all pairs either way.
+constexpr int kKnnCullFromSplits = kAutoCulledFrom;
+bool knn_cull_enabled()
+{
+    static const bool on = [] {
+        const char *e = getenv("ICPMI_KNN_CULL");
+        return !(e && e[0] == '0');
+    }();
+    return on;
+}
+bool knn_culled(const icpmi_ctx *ctx)
+{
+    return ctx->nn_pruned || (knn_cull_enabled() && ctx->nn_splits > kKnnCullFromSplits && ctx->nn_splits <= kCullMaxSplits);
+}
 bool sorted_normal_rows(const icpmi_ctx *ctx, int k, int m)
 {
     return ctx->nn_engine == ICPMI_SEARCH_MFMA_BF16 && (ctx->nn_pruned || knn_lists_enabled()) && k <= 32 && m >= kMfmaMinTargets;
@@ -822,9 +841,10 @@ int launch_knn(icpmi_ctx *ctx, const double *d_qry, int nq_total, const double *
         const int splits = ctx->nn_splits, nslots = splits * kCols;
         // bound the per-row buffer (the lists, or 2 B x nslots of slot minima) by chunking the rows: ~1 GiB
         // all-pairs engine, rows in the target's Morton order: bound first, lists instead of minima (knn_lists.h)
-        // (pruned engine: the same lists on the units that survive the box test against the block's largest row bound)
+        // (culled -- the pruned engine, and the all-pairs engine on targets of more than a dozen splits, knn_culled(): the same
+        // lists on the units that survive the box test against the group's largest row bound)
         const bool lists = by_sorted_row; // (round 3's block lists over slot minima for the culled engine are gone)
-        const bool lists_culled = lists && ctx->nn_pruned;
+        const bool lists_culled = lists && knn_culled(ctx);
         // rows that are not a range of sorted positions (arbitrary queries: icpmi_k_nearest; rows by point index:
         // icpmi_estimate_normals_rows) get their place in the sorted order from their Morton key (k_knn_prebound_q)
         const bool lists_q = !by_sorted_row && knn_lists_enabled();
@@ -835,7 +855,9 @@ int launch_knn(icpmi_ctx *ctx, const double *d_qry, int nq_total, const double *
         if ((rc = reserve(ctx, ctx->slotmin, (lists || lists_q) ? (size_t)kListRowBytes * chunk : sizeof(unsigned short) * (size_t)chunk * nslots))) return rc;
         if ((rc = reserve(ctx, ctx->fb_list, sizeof(int) * ((size_t)rows + 16)))) return rc;
         int *fb_count = (int *)ctx->fb_list.p, *fb_list = fb_count + 16;
-        HIP_TRY(ctx, hipMemsetAsync(fb_count, 0, sizeof(int), s));
+        // (the list forms: a chunk's first kernel, k_knn_prebound / k_knn_prebound_q, clears fb_count before the first chunk
+        // and the group counters before every chunk -- knn_lists.h)
+        if (!lists && !lists_q) HIP_TRY(ctx, hipMemsetAsync(fb_count, 0, sizeof(int), s));
         const SplitFrame *frames = (const SplitFrame *)ctx->frames.p;
         const double *sorted = (const double *)ctx->tgt_sorted.p;
         if (lists_culled && (rc = reserve_group_lists(ctx, splits, chunk / kGroupRows))) return rc;
@@ -849,12 +871,14 @@ int launch_knn(icpmi_ctx *ctx, const double *d_qry, int nq_total, const double *
                 unsigned *ent_row = (unsigned *)(cnt_row + chunk);
                 const KnnLists kl{tf_row, sqf_row, cnt_row, ent_row, kKnnEntCap};
                 hipLaunchKernelGGL(k_knn_prebound, dim3((nq + kPreRows - 1) / kPreRows), dim3(256), 0, s, sorted, m, ctx->nn_ms, k, (int)c0, nq,
-                                   t_row, tf_row, sqf_row, cnt_row);
+                                   t_row, tf_row, sqf_row, cnt_row, c0 == row0 ? fb_count : (int *)nullptr,
+                                   lists_culled ? (unsigned *)ctx->grp_cnt.p : (unsigned *)nullptr,
+                                   lists_culled ? (int)(group_cnt_bytes(ctx) / sizeof(unsigned)) : 0);
                 if (lists_culled) {
                     // the groups are runs of 32 sorted rows, their bound the largest of their rows' (nn_culled.h); a wave takes two
                     const GroupLists gl = group_lists(ctx, 0);
                     const int waves = (nq + 63) / 64;
-                    HIP_TRY(ctx, hipMemsetAsync(ctx->grp_cnt.p, 0, group_cnt_bytes(ctx), s));
+                    ctx->prof.knn_culled_launches += 1;
                     hipLaunchKernelGGL(k_knn_group_cull, dim3((waves + 15) / 16), dim3(1024), 0, s, sorted, m, ctx->nn_ms, (int)c0, nq,
                                        (const double *)t_row, frames, splits, gl);
                     hipLaunchKernelGGL((k_nn_coarse_groups<true, kCoarseWaves>), dim3(coarse_groups_grid(ctx)), dim3(kCoarseThreads),
@@ -880,7 +904,8 @@ int launch_knn(icpmi_ctx *ctx, const double *d_qry, int nq_total, const double *
                 const KnnLists kl{tf_row, sqf_row, cnt_row, ent_row, kKnnEntCap};
                 hipLaunchKernelGGL(k_knn_prebound_q, dim3((nq + 7) / 8), dim3(256), 0, s, d_qry, (int)c0, nq, sorted,
                                    (const unsigned *)ctx->sort_keys.p + (size_t)m /* the sorted keys */, m, ctx->nn_ms, k,
-                                   (const NnFrame *)ctx->nn_misc.p, t_row, tf_row, sqf_row, cnt_row);
+                                   (const NnFrame *)ctx->nn_misc.p, t_row, tf_row, sqf_row, cnt_row,
+                                   c0 == row0 ? fb_count : (int *)nullptr);
                 if (coarse_half_units(ctx, nq, splits)) {
                     constexpr int per = kCoarseQueries / kCoarseQT;
                     hipLaunchKernelGGL((k_nn_coarse_bounded<1, kCoarseWaves>), dim3((nq + per - 1) / per, splits), dim3(kCoarseThreads), 0,

@@ -19,6 +19,10 @@
 // exact list whatever the bound was -- bit-identical to round 2's and to the oracle's.  Rows whose list
 // does not fit (kKnnEntCap words, kKnnSlotCap slots, kKnnCap candidates after tightening: hundreds of
 // coincident points, NaN coordinates) go to k_knn_exact_rows as before.
+// On targets of more than a dozen splits the coarse pass runs over the (32-row group, split) pairs that survive a box
+// test instead (k_knn_group_cull + k_nn_coarse_groups<true>, nn_culled.h; both MFMA engines -- knn_culled() in capi.hip).
+// A pair is dropped only when no target of the split lies within the largest T of the group's rows, so the argument
+// above holds for every row of the group: the split of a true k-neighbour is evaluated and its slot listed.
 #pragma once
 #include "nn_mfma.h"
 
@@ -52,13 +56,24 @@ __device__ __forceinline__ float half_sort_asc(float v, int hl)
 // (k <= 32): lane l of a half takes positions w0 + l + 32 c -- different targets in different lanes -- and the k-th
 // smallest of the 32 lane minima comes out of a 15-step sort shared by two rows; the coarse-value bounds of the 64
 // rows are formed at the end, one row per lane.
+// The kernel is the first of a chunk's, in front of everything that appends to the exact kernel's row list or to the group
+// lists of the culled coarse pass, so it also clears their counters (two fills less per chunk): `fb_clear` (may be null:
+// every chunk but a launch's first) and the `grp_words` words at `grp_clear` (may be null: the all-pairs coarse pass).
 constexpr int kPreRows = 64;
+__device__ __forceinline__ void knn_clear_counters(int *__restrict__ fb_clear, unsigned *__restrict__ grp_clear, int grp_words)
+{
+    if (fb_clear && blockIdx.x == 0 && threadIdx.x == 0) *fb_clear = 0;
+    if (grp_clear)
+        for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < grp_words; t += gridDim.x * blockDim.x) grp_clear[t] = 0u;
+}
 __global__ __launch_bounds__(256) void k_knn_prebound(const double *__restrict__ sorted, int m, int ms, int k, int row0,
                                                       int nrows, double *__restrict__ t_row, float *__restrict__ tf_row,
-                                                      float *__restrict__ sqf_row, int *__restrict__ cnt_row)
+                                                      float *__restrict__ sqf_row, int *__restrict__ cnt_row,
+                                                      int *__restrict__ fb_clear, unsigned *__restrict__ grp_clear, int grp_words)
 {
     __shared__ double wx[kPreRows + kKnnWindow], wy[kPreRows + kKnnWindow], wz[kPreRows + kKnnWindow];
     __shared__ double tl[kPreRows];
+    knn_clear_counters(fb_clear, grp_clear, grp_words);
     const int lane = threadIdx.x & 63, hl = lane & 31, wave = threadIdx.x >> 6;
     const int first = row0 + blockIdx.x * kPreRows;                 // the workgroup's first row (sorted position)
     const int last = min(first + kPreRows, row0 + nrows) - 1;       // ... and its last
@@ -121,8 +136,10 @@ __global__ __launch_bounds__(256) void k_knn_prebound_q(const double *__restrict
                                                         const double *__restrict__ sorted, const unsigned *__restrict__ keys_sorted,
                                                         int m, int ms, int k, const NnFrame *__restrict__ frame,
                                                         double *__restrict__ t_row, float *__restrict__ tf_row,
-                                                        float *__restrict__ sqf_row, int *__restrict__ cnt_row)
+                                                        float *__restrict__ sqf_row, int *__restrict__ cnt_row,
+                                                        int *__restrict__ fb_clear /* k_knn_prebound's: may be null */)
 {
+    knn_clear_counters(fb_clear, nullptr, 0);
     const int lane = threadIdx.x & 63, hl = lane & 31;
     const int local = blockIdx.x * 8 + (threadIdx.x >> 5);
     const bool active = local < nq;
@@ -197,7 +214,7 @@ __global__ __launch_bounds__(256) void k_knn_resolve_lists(const double *__restr
     const int i = row0 + local;
     const int cnt = cnt_row[local];
     double T = t_row[local];
-    const unsigned e = lane < cnt && lane < kKnnEntCap ? ent_row[(size_t)local * kKnnEntCap + lane] : 0u;
+    unsigned e = lane < cnt && lane < kKnnEntCap ? ent_row[(size_t)local * kKnnEntCap + lane] : 0u;
     const double px = QROWS ? qry[3 * (size_t)i] : ICPMI_SX(sorted, ms, i), py = QROWS ? qry[3 * (size_t)i + 1] : ICPMI_SY(sorted, ms, i),
                  pz = QROWS ? qry[3 * (size_t)i + 2] : ICPMI_SZ(sorted, ms, i);
     // The listed slots are walked word by word, bit by bit, with SCALAR instructions (a word is read out of its lane;
@@ -212,7 +229,8 @@ __global__ __launch_bounds__(256) void k_knn_resolve_lists(const double *__restr
     const int kk = k < 64 ? k : 64;
     const double kInf = 1.7976931348623157e308;
     int total = 0;
-    for (int attempt = 0; attempt < 4; ++attempt) {
+    bool canonical = false; // the row's words in ascending order (split, half) instead of the order their atomics landed in
+    for (int attempt = 0; attempt < 5; ++attempt) {
         total = 0;
         int w = 0, base = 0;
         unsigned msk = 0u;
@@ -267,7 +285,20 @@ __global__ __launch_bounds__(256) void k_knn_resolve_lists(const double *__restr
                 }
         }
         if (total <= kKnnListCap) break;
-        // more than fit: the k-th smallest of the 64 lanes' minima over the candidates held (64 groups of different
+        // More than fit (rare).  WHICH candidates are held -- hence how far the bound tightens, and whether the row ends in the
+        // exact kernel -- follows the order of the words, and that is the order in which the coarse pass's atomics landed:
+        // another one in the culled pass than in the all-pairs pass, and in the culled pass from run to run.  The answer is
+        // exact either way, but the rows counted in knn_fallback_rows were not a function of the data.  So the words are
+        // put in ascending order first and the candidates collected again under the same bound (the slots a culled pass
+        // never listed hold no candidate: the held ones are then the same in both forms).
+        if (!canonical) {
+            __builtin_amdgcn_wave_barrier();
+            const double key = wave_sort_asc(lane < cnt ? (double)e : 4294967296.0, lane);
+            e = lane < cnt ? (unsigned)key : 0u;
+            canonical = true;
+            continue;
+        }
+        // still more than fit: the k-th smallest of the 64 lanes' minima over the candidates held (64 groups of different
         // targets) is a tighter valid bound; collect again with it
         __builtin_amdgcn_wave_barrier();
         double lm = kInf;
