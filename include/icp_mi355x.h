@@ -199,6 +199,58 @@ int icpmi_align_gated_batch(icpmi_ctx *ctx, int32_t count, const double *const *
                             const icpmi_gate *gates, icpmi_result *results, icpmi_gate_info *infos, double *error_history,
                             int32_t history_stride, int32_t *status);
 
+/* The same registrations under robust row weights (not in the reference, which gives every source row the same say in
+ * the normal equations: icp.hpp:89-144), optionally behind the correspondence-distance gate above.  Per pass, for row i
+ * with nearest target j, in unfused fp64 and in this order:
+ *     e  = q_j - p_i
+ *     d2 = (e0*e0 + e1*e1) + e2*e2
+ *     b  = (e0*n0 + e1*n1) + e2*n2          (icp.hpp:116)
+ * Gate: the row is kept iff it has a neighbour and d2 <= g2, with g2 = max_distance*max_distance when a gate is given
+ * and g2 = DBL_MAX when max_distance == 0; a NaN or infinite row is then still dropped.
+ * Weight of a kept row, a = fabs(b), k = scale:
+ *     ICPMI_ROBUST_HUBER           w = a <= k ? 1.0 : k / a
+ *     ICPMI_ROBUST_GEMAN_MCCLURE   s = k*k (formed on the host, once), t = s + b*b, r = s / t, w = r*r
+ * Sums over the kept rows, wJ[r] = w*J[r]: the 21 JtJ sums add wJ[r]*J[c], the 6 Jtb sums add wJ[r]*b, the squared
+ * error adds (w*b)*b, the weight sum adds w and the pairs add 1.0; a dropped row adds nothing.  With w == 1.0 every
+ * product is the unweighted one: a Huber scale above every |b| gives icpmi_align_gated's bits, and with no gate
+ * icpmi_align's.
+ * Error: sqrt(sum w b^2 / sum w), the WEIGHTED RMS; it is final_error, the history and what both stopping tests read,
+ * and it reads lower than the plain RMS of the same pose -- a caller's thresholds on final_error (the reference node's
+ * `> 1.0`, a loop detector's fitness `< 0.3`, a pose graph's odometry noise) see that number.
+ * A pass whose weight sum is not > 0 ends the call as a gated pass that keeps no row does (icpmi_align_gated).  The step,
+ * total = delta * total, the post-loop entry and the history invariants are icpmi_align's.
+ * A redescending weight needs a start inside its basin: Geman-McClure at a scale far below the start's residuals locks
+ * onto the start (0.1 m with a start a metre off stays a metre off); Huber does not redescend.
+ * Validation: scale finite and > 0; kind one of the two; max_distance 0 or finite and > 0 -- anything else is
+ * ICPMI_ERR_ARG; a NULL rule is ICPMI_ERR_NULL; a context with a communicator is refused (ICPMI_ERR_ARG).  Paths as
+ * icpmi_align_gated's: the small-cloud kernel in the small regime, else a stand-alone search plus the weighted sums.
+ * info (may be NULL): weight_sum and pairs of the pass that produced final_error, rows = n_src. */
+#define ICPMI_ROBUST_HUBER 1
+#define ICPMI_ROBUST_GEMAN_MCCLURE 2
+typedef struct {
+    int32_t kind;                  /* ICPMI_ROBUST_* */
+    int32_t reserved;
+    double scale;                  /* k, in metres of point-to-plane residual; finite, > 0 */
+    double max_distance;           /* the gate, metres; 0: none */
+} icpmi_robust;
+typedef struct {
+    double weight_sum;
+    int64_t pairs;
+    int64_t rows;
+} icpmi_robust_info;
+int icpmi_align_robust(icpmi_ctx *ctx, const double *source_xyz, int64_t n_src, const double *target_xyz, int64_t n_tgt,
+                       const icpmi_config *cfg, const icpmi_robust *rule, icpmi_result *result, icpmi_robust_info *info,
+                       double *error_history, int32_t history_cap);
+int icpmi_align_robust_device(icpmi_ctx *ctx, const double *d_source_xyz, int64_t n_src, const double *d_target_xyz,
+                              int64_t n_tgt, const icpmi_config *cfg, const icpmi_robust *rule, icpmi_result *result,
+                              icpmi_robust_info *info, double *error_history, int32_t history_cap);
+/* icpmi_align_batch with a rule per problem (rules: `count` entries; infos: `count` entries or NULL): every result is
+ * bit-identical to the same icpmi_align_robust call made alone. */
+int icpmi_align_robust_batch(icpmi_ctx *ctx, int32_t count, const double *const *sources_xyz, const int64_t *n_src,
+                             const double *const *targets_xyz, const int64_t *n_tgt, const icpmi_config *cfgs,
+                             const icpmi_robust *rules, icpmi_result *results, icpmi_robust_info *infos,
+                             double *error_history, int32_t history_stride, int32_t *status);
+
 /* Replaces KDTree(points) + KDTree::nearest_batch (kdtree.hpp:20-26,43-59): for each
  * query the index of, and squared distance to, its nearest target.  Host pointers;
  * dist_sq may be NULL. */
@@ -324,6 +376,13 @@ int icpmi_stream_push_file(icpmi_ctx *ctx, const char *path, double voxel_size, 
  * is reported by the push.  Never needed for correctness. */
 int icpmi_stream_prefetch_file(icpmi_ctx *ctx, const char *path);
 int icpmi_stream_reset(icpmi_ctx *ctx);   /* forget the resident frame (a new sequence starts) */
+/* Robust row weights for the stream (icpmi_align_robust's rule and validation; NULL: off, as at creation): every later
+ * icpmi_stream_push* registers under the rule, bit-identical to icpmi_align_robust on the same filtered scans.  The next
+ * target's early preparation on the helper context, and its adoption, are untouched.  The rule survives
+ * icpmi_stream_reset.  icpmi_stream_last_robust: weight_sum, pairs and rows of the last push's registration; all zero
+ * when that push registered nothing or ran without a rule. */
+int icpmi_stream_set_robust(icpmi_ctx *ctx, const icpmi_robust *rule);
+int icpmi_stream_last_robust(icpmi_ctx *ctx, icpmi_robust_info *info);
 
 /* The map side of SlamNode::process_frame, once the caller has formed new_pose = poses.back() * delta
  * (slam_viz/src/ros/slam_node.cpp:142-153):
@@ -770,6 +829,14 @@ int icpmi_map_ground_labels(icpmi_map *map, int64_t frame, uint8_t *labels, int6
  *                             unchanged; takes effect at the next detect.  Negative or non-finite: ICPMI_ERR_ARG.
  *   icpmi_loop_last_pairs     the rows each of the last detect's results kept in its last pass, in result order, as
  *                             icpmi_loop_last_shifts returns the shifts; each is -1 when that detect ran ungated.
+ *   icpmi_loop_set_robust     kind ICPMI_ROBUST_* with scale finite and > 0 (kind 0: off, as at creation, scale ignored;
+ *                             not in the reference): detect's verifications run under those row weights
+ *                             (icpmi_align_robust); icp_fitness is then the weighted RMS, which reads lower than the
+ *                             plain one against icp_fitness_threshold.  Composes with icpmi_loop_set_gate and the yaw
+ *                             guess; candidates and their order are unchanged; takes effect at the next detect.
+ *                             Anything else: ICPMI_ERR_ARG.
+ *   icpmi_loop_last_weights   the weight sum of each of the last detect's results' last pass, in result order, as
+ *                             icpmi_loop_last_pairs returns the pairs; each is -1 when that detect ran without weights.
  * A store frame or an entry out of range is ICPMI_ERR_ARG and changes nothing.  The handle uses its map's context and
  * stream: destroy it before its map, and the map before the context. */
 typedef struct icpmi_loop icpmi_loop;
@@ -797,6 +864,8 @@ int icpmi_loop_set_yaw_guess(icpmi_loop *loop, int32_t on);
 int icpmi_loop_last_shifts(const icpmi_loop *loop, int32_t *shifts, int64_t cap, int64_t *n_out);
 int icpmi_loop_set_gate(icpmi_loop *loop, double max_distance);
 int icpmi_loop_last_pairs(const icpmi_loop *loop, int64_t *pairs, int64_t cap, int64_t *n_out);
+int icpmi_loop_set_robust(icpmi_loop *loop, int32_t kind, double scale);
+int icpmi_loop_last_weights(const icpmi_loop *loop, double *weights, int64_t cap, int64_t *n_out);
 
 /* profiling */
 int icpmi_reset_profile(icpmi_ctx *ctx);

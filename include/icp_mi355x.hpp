@@ -354,6 +354,98 @@ inline std::vector<GatedICPResult> align_gated_batch(Context &ctx, const PointCl
     return out;
 }
 
+// ---- robust row weights (icpmi_align_robust*; not in the reference) ------------------------------
+// A pass weights each kept row by its point-to-plane residual b (kind ICPMI_ROBUST_HUBER: w = |b| <= scale ? 1 :
+// scale / |b|; ICPMI_ROBUST_GEMAN_MCCLURE: w = (scale^2 / (scale^2 + b^2))^2), optionally behind the gate above
+// (max_distance; 0: none); icpmi_align_robust in icp_mi355x.h has the contract.  final_error and the history are the
+// WEIGHTED RMS sqrt(sum w b^2 / sum w), which reads lower than the plain one: a caller's thresholds on it see that
+// number.  weight_sum and pairs: of the pass that produced final_error, of `rows`.
+struct RobustRule {
+    int kind = ICPMI_ROBUST_HUBER;
+    double scale = 0.1;
+    double max_distance = 0.0;
+};
+struct RobustICPResult : ICPResult {
+    double weight_sum = 0.0;
+    long long pairs = 0;
+    long long rows = 0;
+};
+
+namespace detail {
+inline icpmi_robust to_c(const RobustRule &rule)
+{
+    icpmi_robust r{};
+    r.kind = rule.kind;
+    r.scale = rule.scale;
+    r.max_distance = rule.max_distance;
+    return r;
+}
+} // namespace detail
+
+inline RobustICPResult align_robust(Context &ctx, const double *source_xyz, std::size_t n_src, const double *target_xyz,
+                                    std::size_t n_tgt, const RobustRule &rule, const ICPConfig &config = ICPConfig())
+{
+    icpmi_config k = detail::to_c(config);
+    const icpmi_robust g = detail::to_c(rule);
+    icpmi_robust_info info{};
+    std::vector<double> hist(static_cast<std::size_t>(config.max_iterations > 0 ? config.max_iterations : 0) + 1);
+    icpmi_result r;
+    const int rc = icpmi_align_robust(ctx.get(), source_xyz, static_cast<int64_t>(n_src), target_xyz, static_cast<int64_t>(n_tgt),
+                                      &k, &g, &r, &info, hist.data(), static_cast<int32_t>(hist.size()));
+    if (rc != ICPMI_OK) throw IcpError(rc, icpmi_last_error(ctx.get()));
+    RobustICPResult out;
+    detail::fill(out, r, hist.data());
+    out.weight_sum = info.weight_sum;
+    out.pairs = info.pairs;
+    out.rows = info.rows;
+    return out;
+}
+inline RobustICPResult align_robust(const PointCloud &source, const PointCloud &target, const RobustRule &rule,
+                                    const ICPConfig &config = ICPConfig())
+{
+    return align_robust(default_context(), source.data(), source.size(), target.data(), target.size(), rule, config);
+}
+
+// icp_point_to_plane_batch under one rule for every problem (icpmi_align_robust_batch): each result is that of
+// align_robust alone.
+inline std::vector<RobustICPResult> align_robust_batch(Context &ctx, const PointCloud &source,
+                                                       const std::vector<const PointCloud *> &targets, const RobustRule &rule,
+                                                       const ICPConfig &config,
+                                                       const std::vector<Transformation> &initial_transforms = {})
+{
+    const std::size_t k = targets.size();
+    std::vector<RobustICPResult> out(k);
+    if (k == 0) return out;
+    if (!initial_transforms.empty() && initial_transforms.size() != k)
+        throw IcpError(ICPMI_ERR_ARG, "as many initial transforms as targets, or none");
+    std::vector<const double *> sp(k, source.data()), tp(k);
+    std::vector<int64_t> ns(k, static_cast<int64_t>(source.size())), nt(k);
+    for (std::size_t i = 0; i < k; ++i) {
+        tp[i] = targets[i]->data();
+        nt[i] = static_cast<int64_t>(targets[i]->size());
+    }
+    std::vector<icpmi_config> cfgs(k, detail::to_c(config));
+    for (std::size_t i = 0; i < initial_transforms.size(); ++i)
+        for (int e = 0; e < 16; ++e) cfgs[i].initial_transform[e] = initial_transforms[i].matrix()[static_cast<std::size_t>(e)];
+    std::vector<icpmi_robust> rules(k, detail::to_c(rule));
+    std::vector<icpmi_robust_info> infos(k);
+    const std::size_t stride = static_cast<std::size_t>(config.max_iterations > 0 ? config.max_iterations : 0) + 1;
+    std::vector<double> hist(k * stride);
+    std::vector<icpmi_result> res(k);
+    std::vector<int32_t> status(k);
+    const int rc = icpmi_align_robust_batch(ctx.get(), static_cast<int32_t>(k), sp.data(), ns.data(), tp.data(), nt.data(),
+                                            cfgs.data(), rules.data(), res.data(), infos.data(), hist.data(),
+                                            static_cast<int32_t>(stride), status.data());
+    if (rc != ICPMI_OK) throw IcpError(rc, icpmi_last_error(ctx.get()));
+    for (std::size_t i = 0; i < k; ++i) {
+        detail::fill(out[i], res[i], hist.data() + i * stride);
+        out[i].weight_sum = infos[i].weight_sum;
+        out[i].pairs = infos[i].pairs;
+        out[i].rows = infos[i].rows;
+    }
+    return out;
+}
+
 // Same call shape as slam::icp_point_to_plane (icp.hpp:157-161).
 inline ICPResult icp_point_to_plane(const PointCloud &source, const PointCloud &target,
                                     const ICPConfig &config = ICPConfig())
@@ -600,6 +692,27 @@ public:
         return PointCloud(std::move(xyz));
     }
     void reset() { icpmi_stream_reset(ctx_->get()); }
+    // Not in the reference: every later push registers under the rule's row weights (icpmi_stream_set_robust; the
+    // rule survives reset()); clear_robust() turns them off.  last_robust(): weight sum, pairs and rows of the last
+    // push's registration.  final_error is then the weighted RMS, which reads lower against the caller's `> 1.0`.
+    void set_robust(const RobustRule &rule)
+    {
+        const icpmi_robust r = detail::to_c(rule);
+        const int rc = icpmi_stream_set_robust(ctx_->get(), &r);
+        if (rc != ICPMI_OK) throw IcpError(rc, icpmi_last_error(ctx_->get()));
+    }
+    void clear_robust()
+    {
+        const int rc = icpmi_stream_set_robust(ctx_->get(), nullptr);
+        if (rc != ICPMI_OK) throw IcpError(rc, icpmi_last_error(ctx_->get()));
+    }
+    icpmi_robust_info last_robust() const
+    {
+        icpmi_robust_info info{};
+        const int rc = icpmi_stream_last_robust(ctx_->get(), &info);
+        if (rc != ICPMI_OK) throw IcpError(rc, icpmi_last_error(ctx_->get()));
+        return info;
+    }
 
 private:
     Step finish(const icpmi_result &out, const icpmi_stream_info &info, std::vector<double> hist)
@@ -667,6 +780,11 @@ struct LoopClosureConfig { // loop_closure.hpp:14-19
     // over the kept rows.  2 m suits 0.5 m voxel-filtered street scans; a tight gate (1 m) can make the kept set
     // alternate between passes until the iterations run out.  0: the reference's behaviour.
     double max_correspondence_distance = 0.0;
+    // Not in the reference: a kind (ICPMI_ROBUST_*) runs the verifications under those row weights (align_robust), behind
+    // the gate above if that is set too; icp_fitness is then the weighted RMS, which reads lower than the plain one
+    // against icp_fitness_threshold.  0: the reference's behaviour.
+    int robust_kind = 0;
+    double robust_scale = 0.0;
 };
 struct LoopClosureResult { // loop_closure.hpp:25-31
     int query_frame = 0, match_frame = 0;
@@ -674,6 +792,7 @@ struct LoopClosureResult { // loop_closure.hpp:25-31
     double scan_context_distance = 0.0, icp_fitness = 0.0;
     int sector_shift = -1; // the shift the verification started from (-1: yaw_guess off)
     long long pairs = -1;  // the rows the verification's last pass kept (-1: no correspondence-distance gate)
+    double weight_sum = -1.0; // that pass's weight sum (-1: no robust weights)
 };
 
 // icpmi_sc_shift_transform: the start of a verification whose candidate matched at column shift `shift` (0..59).
@@ -750,7 +869,19 @@ public:
             const bool gated = config_.max_correspondence_distance > 0.0;
             std::vector<ICPResult> rs; // :109
             std::vector<long long> kept(take, -1);
-            if (gated) {
+            std::vector<double> weight(take, -1.0);
+            if (config_.robust_kind != 0) {
+                RobustRule rule;
+                rule.kind = config_.robust_kind;
+                rule.scale = config_.robust_scale;
+                rule.max_distance = gated ? config_.max_correspondence_distance : 0.0;
+                const std::vector<RobustICPResult> gs = align_robust_batch(*ctx_, clouds_[q], tg, rule, icp, starts);
+                for (std::size_t i = 0; i < take; ++i) {
+                    rs.push_back(gs[i]);
+                    if (gated) kept[i] = gs[i].pairs;
+                    weight[i] = gs[i].weight_sum;
+                }
+            } else if (gated) {
                 const std::vector<GatedICPResult> gs = align_gated_batch(*ctx_, clouds_[q], tg, config_.max_correspondence_distance, icp, starts);
                 for (std::size_t i = 0; i < take; ++i) {
                     rs.push_back(gs[i]);
@@ -771,6 +902,7 @@ public:
                     out.icp_fitness = r.final_error;
                     if (config_.yaw_guess) out.sector_shift = shift[static_cast<std::size_t>(cand.second)];
                     out.pairs = kept[i];
+                    out.weight_sum = weight[i];
                     results.push_back(out);
                     ++verified;
                 }
@@ -1221,6 +1353,7 @@ public:
         check(icpmi_loop_create(map.get(), &c, &l_));
         if (config.yaw_guess) check(icpmi_loop_set_yaw_guess(l_, 1));
         if (config.max_correspondence_distance > 0.0) check(icpmi_loop_set_gate(l_, config.max_correspondence_distance));
+        if (config.robust_kind != 0) check(icpmi_loop_set_robust(l_, config.robust_kind, config.robust_scale));
     }
     ~StoreLoopClosureDetector() { icpmi_loop_destroy(l_); }
     StoreLoopClosureDetector(const StoreLoopClosureDetector &) = delete;
@@ -1252,10 +1385,13 @@ public:
         check(icpmi_loop_last_shifts(l_, shifts.data(), n, &ns)); // -1 each with the guess off
         std::vector<int64_t> kept(static_cast<std::size_t>(std::max<int64_t>(n, 1)), -1);
         check(icpmi_loop_last_pairs(l_, kept.data(), n, &ns)); // -1 each with the gate off
+        std::vector<double> weight(static_cast<std::size_t>(std::max<int64_t>(n, 1)), -1.0);
+        check(icpmi_loop_last_weights(l_, weight.data(), n, &ns)); // -1 each with the weights off
         std::vector<LoopClosureResult> out;
         for (int64_t i = 0; i < n; ++i) {
             const icpmi_loop_result &r = buf[static_cast<std::size_t>(i)];
             LoopClosureResult o;
+            o.weight_sum = weight[static_cast<std::size_t>(i)];
             o.sector_shift = shifts[static_cast<std::size_t>(i)];
             o.pairs = kept[static_cast<std::size_t>(i)];
             o.query_frame = r.query_frame;

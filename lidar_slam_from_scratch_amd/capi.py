@@ -42,6 +42,8 @@ EXPORTS = [
     "icpmi_align_gated", "icpmi_align_gated_device", "icpmi_align_gated_batch", "icpmi_loop_set_gate", "icpmi_loop_last_pairs",
     "icpmi_ground_config_default", "icpmi_ground_segment", "icpmi_ground_segment_device", "icpmi_map_set_ground",
     "icpmi_map_ground_labels",
+    "icpmi_align_robust", "icpmi_align_robust_device", "icpmi_align_robust_batch", "icpmi_loop_set_robust",
+    "icpmi_loop_last_weights", "icpmi_stream_set_robust", "icpmi_stream_last_robust",
 ]
 
 
@@ -70,6 +72,30 @@ class Gate(C.Structure):
 class GateInfo(C.Structure):
     """icpmi_gate_info: rows kept by the pass that produced final_error, of `rows`"""
     _fields_ = [("pairs", C.c_int64), ("rows", C.c_int64)]
+
+
+ROBUST_HUBER, ROBUST_GEMAN_MCCLURE = 1, 2   # ICPMI_ROBUST_*
+
+
+class Robust(C.Structure):
+    """icpmi_robust: the row weights of align_robust* (kind ROBUST_*, scale in metres of point-to-plane residual) and
+    their optional correspondence-distance gate (max_distance; 0: none)"""
+    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("scale", C.c_double), ("max_distance", C.c_double)]
+
+
+class RobustInfo(C.Structure):
+    """icpmi_robust_info: weight sum and kept rows of the pass that produced final_error, of `rows`"""
+    _fields_ = [("weight_sum", C.c_double), ("pairs", C.c_int64), ("rows", C.c_int64)]
+
+
+def as_robust(rule):
+    """a Robust, or (kind, scale) or (kind, scale, max_distance) -> Robust"""
+    if isinstance(rule, Robust):
+        return rule
+    r = Robust()
+    r.kind, r.scale = int(rule[0]), float(rule[1])
+    r.max_distance = float(rule[2]) if len(rule) > 2 else 0.0
+    return r
 
 
 class LoopConfig(C.Structure):
@@ -275,6 +301,15 @@ def load_library(path=None):
     L.icpmi_align_gated_batch.argtypes = [vp, C.c_int32, C.POINTER(dp), C.POINTER(C.c_int64), C.POINTER(dp), C.POINTER(C.c_int64),
                                           C.POINTER(Config), C.POINTER(Gate), C.POINTER(Result), C.POINTER(GateInfo), dp,
                                           C.c_int32, C.POINTER(C.c_int32)]
+    L.icpmi_align_robust.argtypes = [vp, dp, C.c_int64, dp, C.c_int64, C.POINTER(Config), C.POINTER(Robust),
+                                     C.POINTER(Result), C.POINTER(RobustInfo), dp, C.c_int32]
+    L.icpmi_align_robust_device.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, C.POINTER(Config), C.POINTER(Robust),
+                                            C.POINTER(Result), C.POINTER(RobustInfo), dp, C.c_int32]
+    L.icpmi_align_robust_batch.argtypes = [vp, C.c_int32, C.POINTER(dp), C.POINTER(C.c_int64), C.POINTER(dp), C.POINTER(C.c_int64),
+                                           C.POINTER(Config), C.POINTER(Robust), C.POINTER(Result), C.POINTER(RobustInfo), dp,
+                                           C.c_int32, C.POINTER(C.c_int32)]
+    L.icpmi_stream_set_robust.argtypes = [vp, C.POINTER(Robust)]
+    L.icpmi_stream_last_robust.argtypes = [vp, C.POINTER(RobustInfo)]
     L.icpmi_nearest_batch.argtypes = [vp, dp, C.c_int64, dp, C.c_int64, C.POINTER(C.c_int32), dp]
     L.icpmi_k_nearest.argtypes = [vp, dp, C.c_int64, dp, C.c_int64, C.c_int32, C.POINTER(C.c_int32), dp]
     L.icpmi_estimate_normals.argtypes = [vp, dp, C.c_int64, C.c_int32, dp]
@@ -367,6 +402,8 @@ def load_library(path=None):
     L.icpmi_loop_last_shifts.argtypes = [vp, C.POINTER(C.c_int32), C.c_int64, i64p]
     L.icpmi_loop_set_gate.argtypes = [vp, C.c_double]
     L.icpmi_loop_last_pairs.argtypes = [vp, i64p, C.c_int64, i64p]
+    L.icpmi_loop_set_robust.argtypes = [vp, C.c_int32, C.c_double]
+    L.icpmi_loop_last_weights.argtypes = [vp, dp, C.c_int64, i64p]
     for name in EXPORTS:
         getattr(L, name)  # raises AttributeError if a declared symbol is not exported
     _LIB = L
@@ -559,6 +596,60 @@ class Context:
             out.append((r, hist[i, :r.history_len].copy(), int(infos[i].pairs)))
         return out
 
+    def align_robust(self, source, target, cfg, rule):
+        """align() under robust row weights (icpmi_align_robust; rule: see as_robust) -> (Result, error history,
+        RobustInfo).  final_error and the history are the WEIGHTED RMS, which reads lower than the plain one."""
+        src, tgt = _f64(source), _f64(target)
+        cap = cfg.max_iterations + 1
+        hist = np.zeros(max(cap, 1))
+        res, info, r = Result(), RobustInfo(), as_robust(rule)
+        self._check(self._lib.icpmi_align_robust(self._h, _dp(src), src.shape[0], _dp(tgt), tgt.shape[0], C.byref(cfg),
+                                                 C.byref(r), C.byref(res), C.byref(info), _dp(hist), cap))
+        return res, hist[:res.history_len].copy(), info
+
+    def align_robust_device(self, src_ptr, n_src, tgt_ptr, n_tgt, cfg, rule):
+        """align_robust with both clouds in device memory (addresses of row-major N x 3 fp64)"""
+        cap = cfg.max_iterations + 1
+        hist = np.zeros(max(cap, 1))
+        res, info, r = Result(), RobustInfo(), as_robust(rule)
+        self._check(self._lib.icpmi_align_robust_device(self._h, C.c_void_p(src_ptr), n_src, C.c_void_p(tgt_ptr), n_tgt,
+                                                        C.byref(cfg), C.byref(r), C.byref(res), C.byref(info),
+                                                        _dp(hist), cap))
+        return res, hist[:res.history_len].copy(), info
+
+    def align_robust_batch(self, sources, targets, cfgs, rules):
+        """align_batch under row weights (icpmi_align_robust_batch) -> [(Result, error history, RobustInfo), ...], each
+        bit-identical to align_robust() of the same pair.  rules: one for all (a Robust or a tuple), or a list, one per
+        pair."""
+        srcs, tgts = [_f64(a) for a in sources], [_f64(a) for a in targets]
+        k = len(srcs)
+        if k != len(tgts) or k < 1:
+            raise ValueError("as many targets as sources, at least one")
+        cfg_list = list(cfgs) if isinstance(cfgs, (list, tuple)) else [cfgs] * k
+        rule_list = list(rules) if isinstance(rules, list) else [rules] * k
+        cfg_arr = (Config * k)(*cfg_list)
+        rule_arr = (Robust * k)()
+        for i, rule in enumerate(rule_list):
+            C.memmove(C.byref(rule_arr[i]), C.byref(as_robust(rule)), C.sizeof(Robust))
+        stride = max(c.max_iterations for c in cfg_list) + 1
+        hist = np.zeros((k, stride))
+        res, infos = (Result * k)(), (RobustInfo * k)()
+        status = (C.c_int32 * k)()
+        dpp = C.POINTER(C.c_double)
+        sp = (dpp * k)(*[_dp(a) for a in srcs])
+        tp = (dpp * k)(*[_dp(a) for a in tgts])
+        ns = (C.c_int64 * k)(*[a.shape[0] for a in srcs])
+        nt = (C.c_int64 * k)(*[a.shape[0] for a in tgts])
+        self._check(self._lib.icpmi_align_robust_batch(self._h, k, sp, ns, tp, nt, cfg_arr, rule_arr, res, infos, _dp(hist),
+                                                       stride, status))
+        out = []
+        for i in range(k):
+            r, inf = Result(), RobustInfo()
+            C.memmove(C.byref(r), C.byref(res[i]), C.sizeof(Result))
+            C.memmove(C.byref(inf), C.byref(infos[i]), C.sizeof(RobustInfo))
+            out.append((r, hist[i, :r.history_len].copy(), inf))
+        return out
+
     def nearest_batch(self, targets, queries, want_dist=True):
         tgt, qry = _f64(targets), _f64(queries)
         idx = np.empty(qry.shape[0], dtype=np.int32)
@@ -672,6 +763,19 @@ class Context:
 
     def stream_reset(self):
         self._check(self._lib.icpmi_stream_reset(self._h))
+
+    def stream_set_robust(self, rule):
+        """icpmi_stream_set_robust: every later stream_push* registers under the rule (see as_robust; None: off)"""
+        if rule is None:
+            self._check(self._lib.icpmi_stream_set_robust(self._h, None))
+        else:
+            self._check(self._lib.icpmi_stream_set_robust(self._h, C.byref(as_robust(rule))))
+
+    def stream_last_robust(self):
+        """icpmi_stream_last_robust -> RobustInfo of the last push's registration (zeros without one, or without a rule)"""
+        info = RobustInfo()
+        self._check(self._lib.icpmi_stream_last_robust(self._h, C.byref(info)))
+        return info
 
     @staticmethod
     def make_grid_config(resolution=None, height_min=None, height_max=None, max_range=None):

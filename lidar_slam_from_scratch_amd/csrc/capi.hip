@@ -35,6 +35,7 @@
 #include "nn_mfma.h"
 #include "icp_small.h"
 #include "icp_gated.h"
+#include "icp_robust.h"
 #include "knn_lists.h"
 #include "nn_bounded.h"
 #include "nn_culled.h"
@@ -208,6 +209,9 @@ struct icpmi_ctx {
     DevBuf stream_prev, stream_cur, f32_stage;      // odometry stream: previous / current filtered scan; float32 upload staging
     int64_t stream_prev_n = -1;                     // rows of stream_prev (-1: no frame yet)
     int64_t stream_cur_n = 0;                       // rows of stream_cur while a push is registering it
+    bool stream_robust_on = false;                  // icpmi_stream_set_robust: the pushes register under stream_robust
+    icpmi_robust stream_robust{};
+    icpmi_robust_info stream_robust_info{};         // icpmi_stream_last_robust: of the last push
     DevBuf grid_set, grid_in, grid_out, grid_cnt, world; // occupancy grid: the set (sorted unique keys), {set, new keys}, sorted, run data; world points
     int64_t grid_n = 0;                             // cells in grid_set
     unsigned *h_grid = nullptr;                     // pinned: the set's size on its way back
@@ -1117,10 +1121,17 @@ int prepare_target(icpmi_ctx *ctx, const double *d_tgt, int m, int n_hint)
 
 // The correspondence-distance gate of a registration (icp_gated.h): null means none, and every branch below is then
 // what it was before the gate existed.
+// With a kind it is a robust rule as well (icp_robust.h): the rows that pass g2 (DBL_MAX: no gate) are weighted, the
+// robust kernels run in the gated ones' places, the weight sum is the state's sums[28] and the pairs its sums[29].
+// Without a kind the gated kernels run, unchanged.
 struct GateRun {
     double g2;     // max_distance * max_distance
     int64_t pairs; // out: the rows kept by the pass that produced final_error (the state's sums[28], which comes back anyway)
+    int32_t kind = 0;        // ICPMI_ROBUST_* (0: the gate alone)
+    double ks = 0.0;         // the kernels' scale: k for Huber, k * k for Geman-McClure
+    double weight_sum = 0.0; // out: the weight sum of that same pass
 };
+static_assert(kRobustHuber == ICPMI_ROBUST_HUBER && kRobustGemanMcClure == ICPMI_ROBUST_GEMAN_MCCLURE, "the kernels' kinds are the header's");
 
 // `gate` (may be null): see GateRun.  A gated registration runs the small-cloud kernel's gated form in the small regime
 // and otherwise the unfused general path -- search (launch_nn), k_reduce_gated, k_finish_step_gated, k_transform -- on
@@ -1184,6 +1195,8 @@ int align_device(icpmi_ctx *ctx, const double *d_src, int64_t n_src64, const dou
     // kernel of their own (k_sum_groups, kernels.h): the step kernels then sum rblocks2 rows
     const bool sum_tree = rblocks >= kSumTreeFrom;
     const int rblocks2 = sum_tree ? (rblocks + kSumGroup - 1) / kSumGroup : 0;
+    // (k_sum_groups adds kNumSums columns, one short of a robust row's; a robust general pass leaves reduce_blocks() rows)
+    if (gate && gate->kind && sum_tree && !small) return fail(ctx, ICPMI_ERR_ARG, "internal: a robust pass of %d partial rows", rblocks);
     if ((rc = reserve(ctx, ctx->partials, sizeof(double) * kSumsStride * ((size_t)rblocks + (size_t)rblocks2)))) return rc;
     double *partials = (double *)ctx->partials.p;
     // what the step kernels sum
@@ -1329,7 +1342,8 @@ int align_device(icpmi_ctx *ctx, const double *d_src, int64_t n_src64, const dou
         frames, splits, (const double *)ctx->tgt_sorted.p, (const double *)ctx->nrm_sorted.p,                                       \
         (const unsigned *)ctx->sort_keys.p + 3 * (size_t)m, m, ctx->nn_ms, d_tgt, (const double *)nrm, partials,                    \
         (unsigned long long *)((char *)ctx->nn_misc.p + 128)
-                if (gate) hipLaunchKernelGGL(k_icp_small_gated, dim3(rblocks), dim3(kSmallThreads), 0, s, ICPMI_SMALL_ARGS, gate->g2);
+                if (gate && gate->kind) hipLaunchKernelGGL(k_icp_small_robust, dim3(rblocks), dim3(kSmallThreads), 0, s, ICPMI_SMALL_ARGS, gate->g2, (int)gate->kind, gate->ks);
+                else if (gate) hipLaunchKernelGGL(k_icp_small_gated, dim3(rblocks), dim3(kSmallThreads), 0, s, ICPMI_SMALL_ARGS, gate->g2);
                 else hipLaunchKernelGGL(k_icp_small, dim3(rblocks), dim3(kSmallThreads), 0, s, ICPMI_SMALL_ARGS);
 #undef ICPMI_SMALL_ARGS
                 small_first = false;
@@ -1339,7 +1353,8 @@ int align_device(icpmi_ctx *ctx, const double *d_src, int64_t n_src64, const dou
             }
             Range range("icpmi:reduce_solve");
             StageTimer t(ctx, ST_REDUCE);
-            if (gate) hipLaunchKernelGGL(k_finish_step_gated, dim3(1), dim3(kFinishThreads), 0, s, partials, rblocks, st, hist, final_pass, progress, ticket);
+            if (gate && gate->kind) hipLaunchKernelGGL(k_finish_step_robust, dim3(1), dim3(kFinishThreads), 0, s, partials, rblocks, st, hist, final_pass, progress, ticket);
+            else if (gate) hipLaunchKernelGGL(k_finish_step_gated, dim3(1), dim3(kFinishThreads), 0, s, partials, rblocks, st, hist, final_pass, progress, ticket);
             else hipLaunchKernelGGL(k_finish_step, dim3(1), dim3(kFinishThreads), 0, s, partials, rblocks, n, st, hist, final_pass, progress, ticket);
             HIP_TRY(ctx, hipGetLastError());
             return ICPMI_OK;
@@ -1359,7 +1374,10 @@ int align_device(icpmi_ctx *ctx, const double *d_src, int64_t n_src64, const dou
         {
             Range range("icpmi:reduce_solve");
             StageTimer t(ctx, ST_REDUCE);
-            if (gate)
+            if (gate && gate->kind)
+                hipLaunchKernelGGL(k_reduce_robust, dim3(rblocks), dim3(256), 0, s, cur, n, d_tgt, m, nrm, idx, partials,
+                                   st, gate->g2, (int)gate->kind, gate->ks);
+            else if (gate)
                 hipLaunchKernelGGL(k_reduce_gated, dim3(rblocks), dim3(256), 0, s, cur, n, d_tgt, m, nrm, idx, partials,
                                    st, gate->g2);
             else if (!fused)
@@ -1401,6 +1419,9 @@ int align_device(icpmi_ctx *ctx, const double *d_src, int64_t n_src64, const dou
                                        fin_rows, fin_blocks, n, (const double *)cur, cur, n,
                                        (const IcpState *)st, other, hist, progress, ticket, rb);
                 st = other;
+            } else if (gate && gate->kind) {
+                hipLaunchKernelGGL(k_finish_step_robust, dim3(1), dim3(kFinishThreads), 0, s, fin_rows, fin_blocks,
+                                   st, hist, final_pass, progress, ticket);
             } else if (gate) {
                 hipLaunchKernelGGL(k_finish_step_gated, dim3(1), dim3(kFinishThreads), 0, s, fin_rows, fin_blocks,
                                    st, hist, final_pass, progress, ticket);
@@ -1552,7 +1573,8 @@ int align_device(icpmi_ctx *ctx, const double *d_src, int64_t n_src64, const dou
         // are held"), so icpmi_debug_loop_rows refuses every row count and nothing reads them as an ungated loop's.
         ctx->loop_rows = -1;
         ctx->loop_idx_valid = false;
-        gate->pairs = (int64_t)hs->sums[28];
+        gate->pairs = (int64_t)hs->sums[gate->kind ? 29 : 28];
+        gate->weight_sum = gate->kind ? hs->sums[28] : 0.0;
     }
 
     memcpy(result->transformation, hs->total, sizeof(double) * 16); // icp.hpp:254
@@ -1949,6 +1971,24 @@ int validate_gate(icpmi_ctx *ctx, const icpmi_gate *gate, GateRun *run)
     return ICPMI_OK;
 }
 
+// the rule of the robust entry points (icp_robust.h) -> the run
+int validate_robust(icpmi_ctx *ctx, const icpmi_robust *rule, GateRun *run)
+{
+    if (!rule) return fail(ctx, ICPMI_ERR_NULL, "rule is NULL (no weights: icpmi_align*)");
+    if (rule->kind != ICPMI_ROBUST_HUBER && rule->kind != ICPMI_ROBUST_GEMAN_MCCLURE)
+        return fail(ctx, ICPMI_ERR_ARG, "kind %d is neither ICPMI_ROBUST_HUBER nor ICPMI_ROBUST_GEMAN_MCCLURE", (int)rule->kind);
+    if (!(rule->scale > 0.0) || !std::isfinite(rule->scale)) return fail(ctx, ICPMI_ERR_ARG, "scale must be finite and > 0");
+    if (rule->max_distance != 0.0 && (!(rule->max_distance > 0.0) || !std::isfinite(rule->max_distance)))
+        return fail(ctx, ICPMI_ERR_ARG, "max_distance must be 0 (no gate) or finite and > 0");
+    if (ctx->comm || ctx->cb_allreduce) return fail(ctx, ICPMI_ERR_ARG, "a context with a communicator does not run robust registrations");
+    run->g2 = rule->max_distance != 0.0 ? rule->max_distance * rule->max_distance : 1.7976931348623157e308;
+    run->pairs = 0;
+    run->kind = rule->kind;
+    run->ks = rule->kind == ICPMI_ROBUST_GEMAN_MCCLURE ? rule->scale * rule->scale : rule->scale;
+    run->weight_sum = 0.0;
+    return ICPMI_OK;
+}
+
 // icpmi_align after its checks: the rows (host or device memory, `kind`) go into the context's own buffers first, so
 // every registration reads its clouds from the same place whoever supplied them (icpmi_align, the loop store's
 // verifications).
@@ -2093,6 +2133,55 @@ int icpmi_align_gated_batch(icpmi_ctx *ctx, int32_t count, const double *const *
     return batch_run(ctx, count, [&](icpmi_ctx *c, int k) {
         return icpmi_align_gated(c, sources_xyz[k], n_src[k], targets_xyz[k], n_tgt[k], &cfgs[k], &gates[k], &results[k],
                                  infos ? &infos[k] : nullptr, error_history + (size_t)k * (size_t)history_stride, history_stride);
+    }, status);
+}
+
+int icpmi_align_robust_device(icpmi_ctx *ctx, const double *d_source_xyz, int64_t n_src, const double *d_target_xyz,
+                              int64_t n_tgt, const icpmi_config *cfg, const icpmi_robust *rule, icpmi_result *result,
+                              icpmi_robust_info *info, double *error_history, int32_t history_cap)
+{
+    int rc = validate_align(ctx, d_source_xyz, n_src, d_target_xyz, n_tgt, cfg, result, error_history, history_cap);
+    if (rc) return rc;
+    if ((rc = check_common(ctx))) return rc;
+    GateRun run;
+    if ((rc = validate_robust(ctx, rule, &run))) return rc;
+    if ((rc = align_device(ctx, d_source_xyz, n_src, d_target_xyz, n_tgt, cfg, result, error_history, history_cap, nullptr,
+                           nullptr, &run)))
+        return rc;
+    if (info) info->weight_sum = run.weight_sum, info->pairs = run.pairs, info->rows = n_src;
+    return ICPMI_OK;
+}
+
+int icpmi_align_robust(icpmi_ctx *ctx, const double *source_xyz, int64_t n_src, const double *target_xyz, int64_t n_tgt,
+                       const icpmi_config *cfg, const icpmi_robust *rule, icpmi_result *result, icpmi_robust_info *info,
+                       double *error_history, int32_t history_cap)
+{
+    int rc = validate_align(ctx, source_xyz, n_src, target_xyz, n_tgt, cfg, result, error_history, history_cap);
+    if (rc) return rc;
+    if ((rc = check_common(ctx))) return rc;
+    GateRun run;
+    if ((rc = validate_robust(ctx, rule, &run))) return rc;
+    if ((rc = align_staged(ctx, source_xyz, n_src, target_xyz, n_tgt, hipMemcpyHostToDevice, cfg, result, error_history,
+                           history_cap, &run)))
+        return rc;
+    if (info) info->weight_sum = run.weight_sum, info->pairs = run.pairs, info->rows = n_src;
+    return ICPMI_OK;
+}
+
+int icpmi_align_robust_batch(icpmi_ctx *ctx, int32_t count, const double *const *sources_xyz, const int64_t *n_src,
+                             const double *const *targets_xyz, const int64_t *n_tgt, const icpmi_config *cfgs,
+                             const icpmi_robust *rules, icpmi_result *results, icpmi_robust_info *infos,
+                             double *error_history, int32_t history_stride, int32_t *status)
+{
+    int rc;
+    if ((rc = check_common(ctx))) return rc;
+    if (!sources_xyz || !n_src || !targets_xyz || !n_tgt || !cfgs || !rules || !results || !error_history || !status)
+        return fail(ctx, ICPMI_ERR_NULL, "null argument");
+    if (count < 1 || count > ICPMI_MAX_BATCH) return fail(ctx, ICPMI_ERR_ARG, "count %d outside [1,%d]", count, ICPMI_MAX_BATCH);
+    if (ctx->comm || ctx->cb_allreduce) return fail(ctx, ICPMI_ERR_ARG, "a context with a communicator registers one (sharded) problem at a time");
+    return batch_run(ctx, count, [&](icpmi_ctx *c, int k) {
+        return icpmi_align_robust(c, sources_xyz[k], n_src[k], targets_xyz[k], n_tgt[k], &cfgs[k], &rules[k], &results[k],
+                                  infos ? &infos[k] : nullptr, error_history + (size_t)k * (size_t)history_stride, history_stride);
     }, status);
 }
 
@@ -2600,6 +2689,9 @@ int stream_register(icpmi_ctx *ctx, int64_t n_cur, int64_t min_points, const icp
     int rc;
     info->n_filtered = n_cur;
     info->n_target = ctx->stream_prev_n < 0 ? 0 : ctx->stream_prev_n;
+    ctx->stream_robust_info = icpmi_robust_info{};
+    GateRun rule{};
+    if (ctx->stream_robust_on && (rc = validate_robust(ctx, &ctx->stream_robust, &rule))) return rc; // (a communicator set since)
     ctx->stream_cur_n = n_cur;
     // The scan just filtered is the NEXT push's target (slam_node.cpp:128,152): its search structure and
     // normals (Morton sort, split frames, operand packing, 20-NN, PCA: ~135 us of small kernels) are built on a
@@ -2665,7 +2757,8 @@ int stream_register(icpmi_ctx *ctx, int64_t n_cur, int64_t min_points, const icp
         const auto ta = std::chrono::steady_clock::now();
         rc = align_device(ctx, (const double *)ctx->stream_cur.p, n_cur, (const double *)ctx->stream_prev.p,
                           ctx->stream_prev_n, cfg, result, error_history, history_cap, nullptr,
-                          helper ? +prepare_next : nullptr);
+                          helper ? +prepare_next : nullptr, ctx->stream_robust_on ? &rule : nullptr);
+        if (rc == ICPMI_OK && ctx->stream_robust_on) ctx->stream_robust_info = icpmi_robust_info{rule.weight_sum, rule.pairs, n_cur};
         ctx->t_align += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ta).count();
         if (span) {
             (void)hipEventRecord(e1, ctx->stream);
@@ -2690,6 +2783,30 @@ int stream_register(icpmi_ctx *ctx, int64_t n_cur, int64_t min_points, const icp
     return ICPMI_OK;
 }
 } // namespace
+
+int icpmi_stream_set_robust(icpmi_ctx *ctx, const icpmi_robust *rule)
+{
+    int rc;
+    if ((rc = check_common(ctx))) return rc;
+    if (!rule) {
+        ctx->stream_robust_on = false;
+        return ICPMI_OK;
+    }
+    GateRun run;
+    if ((rc = validate_robust(ctx, rule, &run))) return rc;
+    ctx->stream_robust = *rule;
+    ctx->stream_robust_on = true;
+    return ICPMI_OK;
+}
+
+int icpmi_stream_last_robust(icpmi_ctx *ctx, icpmi_robust_info *info)
+{
+    int rc;
+    if ((rc = check_common(ctx))) return rc;
+    if (!info) return fail(ctx, ICPMI_ERR_NULL, "null argument");
+    *info = ctx->stream_robust_info;
+    return ICPMI_OK;
+}
 
 namespace {
 bool is_bin(const char *path)
@@ -4963,6 +5080,9 @@ struct icpmi_loop {
     std::vector<int32_t> last_shifts;    // per result of the last detect its shift (-1: the guess was off)
     double gate = 0.0;                   // icpmi_loop_set_gate (0: off)
     std::vector<int64_t> last_pairs;     // per result of the last detect its kept rows (-1: the gate was off)
+    int32_t robust_kind = 0;             // icpmi_loop_set_robust (0: off)
+    double robust_scale = 0.0;
+    std::vector<double> last_weights;    // per result of the last detect its weight sum (-1: the weights were off)
 };
 
 namespace {
@@ -5143,8 +5263,11 @@ int icpmi_loop_detect(icpmi_loop *L, icpmi_loop_result *out, int64_t cap, int64_
     *n_out = 0;
     L->last_shifts.clear();
     L->last_pairs.clear();
+    L->last_weights.clear();
     const bool guess = L->yaw_guess;
     const bool gated = L->gate > 0.0;
+    const int32_t robust = L->robust_kind;
+    const double robust_ks = robust == ICPMI_ROBUST_GEMAN_MCCLURE ? L->robust_scale * L->robust_scale : L->robust_scale;
     const int64_t E = (int64_t)L->frames.size();
     if (E < 2) return ICPMI_OK; // :69
     Range range("icpmi:loop_detect");
@@ -5237,9 +5360,10 @@ int icpmi_loop_detect(icpmi_loop *L, icpmi_loop_result *out, int64_t cap, int64_
             int r = validate_align(c, &icp, nq, &icp, nt, &icps[k], &res[k], hist.data() + (size_t)k * hcap, hcap);
             if (r == ICPMI_OK) r = check_common(c);
             gates[k] = GateRun{L->gate * L->gate, 0};
+            if (robust) gates[k] = GateRun{gated ? L->gate * L->gate : 1.7976931348623157e308, 0, robust, robust_ks, 0.0};
             if (r == ICPMI_OK)
                 r = align_staged(c, rows + 3 * (size_t)q0, nq, rows + 3 * (size_t)t0, nt, hipMemcpyDeviceToDevice, &icps[k],
-                                 &res[k], hist.data() + (size_t)k * hcap, hcap, gated ? &gates[k] : nullptr);
+                                 &res[k], hist.data() + (size_t)k * hcap, hcap, gated || robust ? &gates[k] : nullptr);
             return r;
         }, status);
         if (rc) return rc;
@@ -5256,6 +5380,7 @@ int icpmi_loop_detect(icpmi_loop *L, icpmi_loop_result *out, int64_t cap, int64_
                 results.push_back(o);
                 L->last_shifts.push_back(guess ? shift_of[(size_t)cand.second] : -1);
                 L->last_pairs.push_back(gated ? gates[k].pairs : -1);
+                L->last_weights.push_back(robust ? gates[k].weight_sum : -1.0);
                 ++verified;
             }
         }
@@ -5281,6 +5406,34 @@ int icpmi_loop_set_gate(icpmi_loop *L, double max_distance)
     if (max_distance != 0.0 && (!(max_distance > 0.0) || !std::isfinite(max_distance)))
         return fail(L->map->ctx, ICPMI_ERR_ARG, "max_distance must be 0 (off) or finite and > 0");
     L->gate = max_distance;
+    return ICPMI_OK;
+}
+
+int icpmi_loop_set_robust(icpmi_loop *L, int32_t kind, double scale)
+{
+    if (!L) return ICPMI_ERR_NULL;
+    if (kind == 0) {
+        L->robust_kind = 0;
+        L->robust_scale = 0.0;
+        return ICPMI_OK;
+    }
+    if (kind != ICPMI_ROBUST_HUBER && kind != ICPMI_ROBUST_GEMAN_MCCLURE)
+        return fail(L->map->ctx, ICPMI_ERR_ARG, "kind %d is neither 0 (off), ICPMI_ROBUST_HUBER nor ICPMI_ROBUST_GEMAN_MCCLURE", (int)kind);
+    if (!(scale > 0.0) || !std::isfinite(scale)) return fail(L->map->ctx, ICPMI_ERR_ARG, "scale must be finite and > 0");
+    L->robust_kind = kind;
+    L->robust_scale = scale;
+    return ICPMI_OK;
+}
+
+int icpmi_loop_last_weights(const icpmi_loop *L, double *weights, int64_t cap, int64_t *n_out)
+{
+    if (!L) return ICPMI_ERR_NULL;
+    icpmi_ctx *ctx = L->map->ctx;
+    if (!n_out || (!weights && cap > 0)) return fail(ctx, ICPMI_ERR_NULL, "null argument");
+    const int64_t n = (int64_t)L->last_weights.size();
+    *n_out = n;
+    if (n > cap) return fail(ctx, ICPMI_ERR_CAPACITY, "output holds %lld weights, needs %lld", (long long)cap, (long long)n);
+    if (n) memcpy(weights, L->last_weights.data(), sizeof(double) * (size_t)n);
     return ICPMI_OK;
 }
 

@@ -69,11 +69,14 @@ __device__ __forceinline__ void small_merge(float &v1, float &v2, const float w1
 // correspondence-distance gate of icp_gated.h.  Shared as text, not as a `template <bool Gated>` body inlined into two
 // __global__ wrappers: inlined, k_icp_small keeps its resource line but not its instructions (197 lines of its ISA
 // differ: registers renamed, loads moved), and the ungated kernel must stay the kernel that was measured.
+// (A third expansion, k_icp_small_robust with ICPMI_SMALL_ROBUST 1, is icp_robust.h's.)
+#define ICPMI_SMALL_ROBUST 0
 #define ICPMI_SMALL_GATED 0
 #include "icp_small_kernel.inc"
 #undef ICPMI_SMALL_GATED
 #define ICPMI_SMALL_GATED 1
 #include "icp_small_kernel.inc"
 #undef ICPMI_SMALL_GATED
+#undef ICPMI_SMALL_ROBUST
 
 } // namespace icpmi

@@ -1,8 +1,13 @@
 // icp_small_kernel.inc -- the text of the small-cloud kernel (icp_small.h), included twice: with ICPMI_SMALL_GATED 0 it is
 // k_icp_small, token for token what it was before the correspondence-distance gate existed (so its instructions are too),
 // with ICPMI_SMALL_GATED 1 it is k_icp_small_gated (icp_gated.h): the same kernel with the gate's test on the winner that
-// step 4 already holds, and the kept count in column 28 of the partial row.
-#if ICPMI_SMALL_GATED
+// step 4 already holds, and the kept count in column 28 of the partial row.  With ICPMI_SMALL_ROBUST 1 as well (icp_robust.h)
+// it is k_icp_small_robust: the gated kernel with the row's weight on its terms, the weight in column 28 and the kept
+// count in column 29.  The first two expansions stay token for token what they were.
+#if ICPMI_SMALL_ROBUST
+#define ICPMI_SMALL_COLS 30 // the 28 weighted sums, the weight sum and the kept count
+__global__ __launch_bounds__(kSmallThreads) void k_icp_small_robust(
+#elif ICPMI_SMALL_GATED
 #define ICPMI_SMALL_COLS 29 // columns of a partial row the kernel forms: the 28 sums and the kept count
 __global__ __launch_bounds__(kSmallThreads) void k_icp_small_gated(
 #else
@@ -17,11 +22,18 @@ __global__ __launch_bounds__(kSmallThreads) void k_icp_small(
 #if ICPMI_SMALL_GATED
     , const double g2 // max_distance^2, formed once on the host (icp_gated.h)
 #endif
+#if ICPMI_SMALL_ROBUST
+    , const int kind, const double ks // the weight and its scale (icp_robust.h: k for Huber, k * k for Geman-McClure)
+#endif
     )
 {
     __shared__ uint4 scratch[kSmallWaves][32 * 36 / 4]; // per wave: A rows, then the epilogue's transpose
     __shared__ float2 rec[kSmallMaxSplits * kSmallUnitsPerSplit][kSmallQ];
+#if ICPMI_SMALL_ROBUST
+    __shared__ double jrow[kSmallQ][31]; // (an odd stride, as 29 is)
+#else
     __shared__ double jrow[kSmallQ][29];
+#endif
     __shared__ double red[kSmallWaves][ICPMI_SMALL_COLS];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int q0 = blockIdx.x * kSmallQ;
@@ -259,6 +271,30 @@ __global__ __launch_bounds__(kSmallThreads) void k_icp_small(
             const double e0 = lq0 - qx, e1 = lq1 - qy, e2 = lq2 - qz;
             const double bb = (e0 * ln0 + e1 * ln1) + e2 * ln2; // icp.hpp:116
             double *row = jrow[qi];
+#if ICPMI_SMALL_ROBUST
+            // the gate as below, then the weight of a kept row on its terms (icp_robust.h's contract): a dropped row leaves
+            // a zero row with 0 in columns 28 and 29; with w == 1.0 every product is the gated kernel's
+            const bool keep = (e0 * e0 + e1 * e1) + e2 * e2 <= g2;
+            const double w = keep ? robust_weight(kind, ks, bb) : 0.0;
+            row[28] = w;
+            row[29] = keep ? 1.0 : 0.0;
+            if (!keep) {
+#pragma unroll
+                for (int e = 0; e < 28; ++e) row[e] = 0.0;
+            } else {
+                double wJ[6];
+#pragma unroll
+                for (int r = 0; r < 6; ++r) wJ[r] = w * J[r];
+                int o = 0;
+#pragma unroll
+                for (int r = 0; r < 6; ++r)
+#pragma unroll
+                    for (int c = r; c < 6; ++c) row[o++] = wJ[r] * J[c];
+#pragma unroll
+                for (int r = 0; r < 6; ++r) row[21 + r] = wJ[r] * bb;
+                row[27] = (w * bb) * bb;
+            }
+#else
 #if ICPMI_SMALL_GATED
             // the gate: a row whose winner is farther than sqrt(g2) -- or whose distance is a NaN -- leaves a zero row with
             // count 0, a kept row count 1; the rows and the order of additions are the ungated kernel's.  (The zero row IS
@@ -281,6 +317,7 @@ __global__ __launch_bounds__(kSmallThreads) void k_icp_small(
             row[27] = bb * bb;
 #if ICPMI_SMALL_GATED
             }
+#endif
 #endif
         } else if (!valid && ql == 0) {
 #pragma unroll

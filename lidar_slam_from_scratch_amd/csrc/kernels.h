@@ -199,8 +199,9 @@ constexpr int kFinishThreads = 1024;
 constexpr int kFinishGroups = kFinishThreads / 32;
 
 // Counted (icp_gated.h): column 28 of the partial rows holds each block's number of kept rows; their fixed-order sum
-// is the count, and n_local is not looked at.
-template <bool Counted = false>
+// is the count, and n_local is not looked at.  Cols (icp_robust.h): the columns summed -- 30 there, the weight sum in
+// column 28 and the kept rows in column 29.
+template <bool Counted = false, int Cols = (Counted ? 29 : 28)>
 __device__ inline void finish_sums(const double *__restrict__ partials, int nblocks, int n_local,
                                    IcpState *st)
 {
@@ -242,7 +243,7 @@ __device__ inline void finish_sums(const double *__restrict__ partials, int nblo
         for (int u = 0; u < w; ++u) acc[u] += acc[u + w];
     fs[g][e] = acc[0];
     __syncthreads();
-    if (threadIdx.x < (Counted ? 29 : 28)) {
+    if (threadIdx.x < Cols) {
         double s = fs[0][e];
         for (int k = 1; k < G; ++k) s += fs[k][e];
         st->sums[e] = s;

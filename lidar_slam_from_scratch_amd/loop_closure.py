@@ -21,6 +21,11 @@ a place revisited a lane aside -- scans that overlap only partly -- verifies, an
 rows.  align / align_many are then passed keyword-only max_distance, and their results carry `pairs`, the rows the last
 pass kept.  0 (the default) passes nothing.  2 m suits 0.5 m voxel-filtered street scans; a tight gate (1 m) can make
 the kept set alternate between passes, so that a verification runs out of iterations.
+
+LoopClosureConfig(robust_kind=k, robust_scale=s) with k one of capi.ROBUST_* (not in the reference) runs the
+verifications under robust row weights (icpmi_align_robust), with the gate above if that is set too.  align / align_many
+are then passed keyword-only robust=(kind, scale), and their results carry `weight_sum`.  icp_fitness is then the WEIGHTED
+RMS, which reads lower than the plain one against icp_fitness_threshold.  0 (the default) passes nothing.
 """
 import ctypes as C
 import weakref
@@ -34,8 +39,10 @@ class LoopClosureConfig:
     """loop_closure.hpp:14-19"""
 
     def __init__(self, frame_gap=50, sc_distance_threshold=0.25, icp_fitness_threshold=0.3, max_candidates=3,
-                 yaw_guess=False, max_correspondence_distance=0.0):
+                 yaw_guess=False, max_correspondence_distance=0.0, robust_kind=0, robust_scale=0.0):
         self.yaw_guess = yaw_guess
+        self.robust_kind = robust_kind
+        self.robust_scale = robust_scale
         self.max_correspondence_distance = max_correspondence_distance
         self.frame_gap = frame_gap
         self.sc_distance_threshold = sc_distance_threshold
@@ -45,11 +52,13 @@ class LoopClosureConfig:
 
 class LoopClosureResult:
     """loop_closure.hpp:25-31; sector_shift: the column shift the verification started from (None: yaw_guess off);
-    pairs: the rows the verification's last pass kept (None: no correspondence-distance gate)"""
+    pairs: the rows the verification's last pass kept (None: no correspondence-distance gate); weight_sum: that pass's
+    weight sum (None: no robust weights)"""
 
     def __init__(self, query_frame, match_frame, transform, scan_context_distance, icp_fitness, sector_shift=None,
-                 pairs=None):
+                 pairs=None, weight_sum=None):
         self.sector_shift = sector_shift
+        self.weight_sum = weight_sum
         self.pairs = pairs
         self.query_frame = query_frame
         self.match_frame = match_frame
@@ -72,19 +81,21 @@ class GpuBackend:
         """-> (distances, the smallest column shift attaining each), icpmi_scan_context_distances_shift"""
         return self.ctx.scan_context_distances_shift(query_desc, hist_descs)
 
-    def align(self, source, target, max_iterations, tolerance, *, initial_transform=None, max_distance=None):
-        if initial_transform is None and max_distance is None:
+    def align(self, source, target, max_iterations, tolerance, *, initial_transform=None, max_distance=None, robust=None):
+        if initial_transform is None and max_distance is None and robust is None:
             from .odometry import gpu_align
             return gpu_align(self.ctx)(source, target, max_iterations, tolerance)
         return self.align_many(source, [target], max_iterations, tolerance,
                                initial_transforms=None if initial_transform is None else [initial_transform],
-                               max_distance=max_distance)[0]
+                               max_distance=max_distance, robust=robust)[0]
 
-    def align_many(self, source, targets, max_iterations, tolerance, *, initial_transforms=None, max_distance=None):
+    def align_many(self, source, targets, max_iterations, tolerance, *, initial_transforms=None, max_distance=None,
+                   robust=None):
         """The verifications of one detect() side by side on the GPU (icpmi_align_batch): same results as
         align() one after the other.  initial_transforms: one 4 x 4 per target (None: the identity for all).
         max_distance: the correspondence-distance gate (icpmi_align_gated_batch; None: none); the results then carry
-        `pairs`."""
+        `pairs`.  robust: (kind, scale), the row weights (icpmi_align_robust_batch, behind max_distance if that is given
+        too; None: none); the results then carry `weight_sum` as well."""
         from . import capi
 
         class _R:
@@ -95,16 +106,21 @@ class GpuBackend:
             cfg = [capi.Context.make_config(max_iterations=max_iterations, tolerance=tolerance, initial_transform=T)
                    for T in initial_transforms]
         out = []
-        if max_distance is None:
-            runs = [(res, None) for res, _hist in self.ctx.align_batch([source] * len(targets), targets, cfg)]
+        if robust is not None:
+            rule = capi.as_robust((robust[0], robust[1], 0.0 if max_distance is None else float(max_distance)))
+            runs = [(res, int(info.pairs) if max_distance is not None else None, float(info.weight_sum)) for res, _hist, info in
+                    self.ctx.align_robust_batch([source] * len(targets), targets, cfg, rule)]
+        elif max_distance is None:
+            runs = [(res, None, None) for res, _hist in self.ctx.align_batch([source] * len(targets), targets, cfg)]
         else:
-            runs = [(res, pairs) for res, _hist, pairs in
+            runs = [(res, pairs, None) for res, _hist, pairs in
                     self.ctx.align_gated_batch([source] * len(targets), targets, cfg, float(max_distance))]
-        for res, pairs in runs:
+        for res, pairs, weight_sum in runs:
             r = _R()
             r.transformation = np.array(res.transformation[:]).reshape(4, 4)
             r.converged, r.final_error, r.num_iterations = bool(res.converged), res.final_error, res.num_iterations
             r.pairs = pairs
+            r.weight_sum = weight_sum
             out.append(r)
         return out
 
@@ -151,6 +167,11 @@ class LoopClosureDetector:
         guess = bool(getattr(self.config, "yaw_guess", False))
         gate = float(getattr(self.config, "max_correspondence_distance", 0.0) or 0.0)
         gkw = {"max_distance": gate} if gate > 0.0 else {}   # (passed only when set, as the starts are)
+        kind = int(getattr(self.config, "robust_kind", 0) or 0)
+        robust = kind != 0
+        gated = gate > 0.0
+        if robust:
+            gkw["robust"] = (kind, float(self.config.robust_scale))
         if guess:
             dist, shift = self.backend.distances_shift(self._descriptors[q], hist)
         else:
@@ -186,7 +207,8 @@ class LoopClosureDetector:
                     results.append(LoopClosureResult(self._frame_indices[q], self._frame_indices[cand],
                                                      np.asarray(r.transformation), sc_dist, r.final_error,
                                                      int(shift[cand]) if guess else None,
-                                                     getattr(r, "pairs", None) if gkw else None))
+                                                     getattr(r, "pairs", None) if gated else None,
+                                                     getattr(r, "weight_sum", None) if robust else None))
                     verified += 1
         return results
 
@@ -214,6 +236,9 @@ class StoreLoopClosureDetector:
         self._gated = float(getattr(self.config, "max_correspondence_distance", 0.0) or 0.0) > 0.0
         if self._gated:
             ctx._check(self._lib.icpmi_loop_set_gate(h, float(self.config.max_correspondence_distance)))
+        self._robust = int(getattr(self.config, "robust_kind", 0) or 0) != 0
+        if self._robust:
+            ctx._check(self._lib.icpmi_loop_set_robust(h, int(self.config.robust_kind), float(self.config.robust_scale)))
         for owner in (ctx, store):     # Context.close() and store.close() destroy it before the map
             if not hasattr(owner, "_loops"):
                 owner._loops = weakref.WeakSet()
@@ -230,6 +255,11 @@ class StoreLoopClosureDetector:
         """icpmi_loop_set_gate: the verifications' correspondence-distance gate from the next detect on (0: off)"""
         self.ctx._check(self._lib.icpmi_loop_set_gate(self._h, float(max_distance)))
         self._gated = float(max_distance) > 0.0   # (the caller's config object, which it may share, is left alone)
+
+    def set_robust(self, kind, scale=0.0):
+        """icpmi_loop_set_robust: the verifications' row weights from the next detect on (kind 0: off)"""
+        self.ctx._check(self._lib.icpmi_loop_set_robust(self._h, int(kind), float(scale)))
+        self._robust = int(kind) != 0
 
     def add_frame(self, store_frame, frame_idx):
         """loop_closure.hpp:54-60 for the cloud the store holds as frame `store_frame`"""
@@ -270,6 +300,12 @@ class StoreLoopClosureDetector:
             m = C.c_int64(0)
             self.ctx._check(self._lib.icpmi_loop_last_pairs(self._h, pr, n.value, C.byref(m)))
             pairs = [int(v) for v in pr[:m.value]]
+        weights = [None] * n.value
+        if self._robust:
+            wt = (C.c_double * max(n.value, 1))()
+            m = C.c_int64(0)
+            self.ctx._check(self._lib.icpmi_loop_last_weights(self._h, wt, n.value, C.byref(m)))
+            weights = [float(v) for v in wt[:m.value]]
         return [LoopClosureResult(r.query_frame, r.match_frame, np.array(r.transform[:]).reshape(4, 4),
-                                  r.scan_context_distance, r.icp_fitness, s, p)
-                for r, s, p in zip(buf[:n.value], shifts, pairs)]
+                                  r.scan_context_distance, r.icp_fitness, s, p, w)
+                for r, s, p, w in zip(buf[:n.value], shifts, pairs, weights)]

@@ -65,8 +65,11 @@ def run_odometry(frames, align, max_iterations=50, tolerance=1e-6, min_points=10
     return track
 
 
-def gpu_align(ctx):
-    """Adapter: capi.Context -> the `align` callable above."""
+def gpu_align(ctx, *, robust=None):
+    """Adapter: capi.Context -> the `align` callable above.  robust: a capi.Robust, or (kind, scale[, max_distance]) --
+    the registrations run under those row weights (icpmi_align_robust; None: none) and their results carry `weight_sum`
+    and `pairs`.  final_error is then the WEIGHTED RMS, which reads lower than the plain one against the caller's
+    `> 1.0`."""
     from . import capi
 
     class _R:
@@ -74,8 +77,12 @@ def gpu_align(ctx):
 
     def align(source, target, max_iterations, tolerance):
         cfg = capi.Context.make_config(max_iterations=max_iterations, tolerance=tolerance)
-        res, _hist = ctx.align(source, target, cfg)
         r = _R()
+        if robust is None:
+            res, _hist = ctx.align(source, target, cfg)
+        else:
+            res, _hist, info = ctx.align_robust(source, target, cfg, robust)
+            r.weight_sum, r.pairs = float(info.weight_sum), int(info.pairs)
         r.transformation = np.array(res.transformation[:]).reshape(4, 4)
         r.converged = bool(res.converged)
         r.final_error = res.final_error
@@ -129,7 +136,7 @@ def run_odometry_device(raw_frames, ctx, voxel=0.5, max_iterations=50, tolerance
 
 
 def run_odometry_stream(paths, ctx, voxel=0.5, max_iterations=50, tolerance=1e-6, min_points=1000, grid=None,
-                        want_world=False, prefetch=True):
+                        want_world=False, prefetch=True, robust=None):
     """The same loop over frame FILES with everything but the file read on the device: one
     `icpmi_stream_push_file` per frame does slam_node.cpp:121-152 -- the scan goes from disk through
     pinned memory to HBM (`.bin`: float32 records, widened there), voxel filter, min-points guard,
@@ -139,12 +146,16 @@ def run_odometry_stream(paths, ctx, voxel=0.5, max_iterations=50, tolerance=1e-6
     world points of the resident scan (copied out only with `want_world`) and the occupancy insert;
     track.cells then holds the size of the cell set after each frame.  With `prefetch` the next
     frame's file is read by the library's worker thread while this frame runs
-    (`icpmi_stream_prefetch_file`).  No torch in here."""
+    (`icpmi_stream_prefetch_file`).  robust: a capi.Robust, or (kind, scale[, max_distance]) -- every push registers
+    under those row weights (icpmi_stream_set_robust; None: none, and a rule set earlier is cleared); track.weight_sums
+    then holds each registration's weight sum.  No torch in here."""
     from . import capi
     track = OdometryTrack()
     track.cells = []
+    track.weight_sums = []
     cfg = capi.Context.make_config(max_iterations=max_iterations, tolerance=tolerance)
     ctx.stream_reset()
+    ctx.stream_set_robust(robust)
     if grid is not None:
         ctx.occupancy_clear()
 
@@ -178,6 +189,8 @@ def run_odometry_stream(paths, ctx, voxel=0.5, max_iterations=50, tolerance=1e-6
         track.iterations.append(res.num_iterations)
         track.converged.append(bool(res.converged))
         track.gated.append(bool(bad))
+        if robust is not None:
+            track.weight_sums.append(float(ctx.stream_last_robust().weight_sum))
         map_side(info.n_filtered)
         track.frame_ms.append(1e3 * (time.perf_counter() - t0))
     return track

@@ -47,7 +47,7 @@ def node_loop_config():
 def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, pose_graph_config=None,
              align=None, loop_backend=None, pose_graph=None, global_map=None, grid=None, map_voxel=1.0,
              loop_on_device=False, raycast=False, counts=False, live=False, loop_yaw_guess=False, loop_gate=None,
-             ground=None):
+             ground=None, odom_robust=None, loop_robust=None):
     """frames: sequence of N x 3 fp64 clouds (already downsampled).  Returns a SlamRun.  global_map: an object with
     add_frame, recent_clouds and finish (None: no map is built); grid: its occupancy grid config (None: defaults).
     loop_on_device: the detector is loop_closure.StoreLoopClosureDetector over global_map (a global_map.GlobalMap),
@@ -62,12 +62,21 @@ def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, po
     (LoopClosureConfig.max_correspondence_distance; not in the reference node), so a return leg a lane aside closes.
     ground: a ground.GroundConfig (None: none); with a global_map, global_map.set_ground(ground) before the first
     frame, so the cell set, raster, counts and live counts take each frame's OBSTACLE rows as its hits (not in the
-    reference node).  Ignored without a global_map."""
+    reference node).  Ignored without a global_map.
+    odom_robust: (kind, scale) or (kind, scale, max_distance), kind one of capi.ROBUST_* (None: none); the default
+    `align` registers under those row weights (odometry.gpu_align(ctx, robust=...); not in the reference node).  With an
+    `align` of the caller's it is refused.
+    loop_robust: (kind, scale) (None: none); the detector's verifications run under those row weights
+    (LoopClosureConfig.robust_kind / robust_scale), behind loop_gate if that is given too.
+    Under weights final_error is a weighted RMS and reads lower than the plain one: the gate `> 1.0` above, the
+    detector's fitness threshold and the odometry factors' noise all read that number."""
     if loop_on_device and loop_backend is not None:
         raise ValueError("loop_backend and loop_on_device=True both choose the detector")
+    if align is not None and odom_robust is not None:
+        raise ValueError("odom_robust configures the default align; pass a robust align of your own instead")
     if align is None:
         from .odometry import gpu_align
-        align = gpu_align(ctx)
+        align = gpu_align(ctx, robust=odom_robust)
     if loop_backend is None and not loop_on_device:
         loop_backend = lc.GpuBackend(ctx)
     if pose_graph is None:
@@ -81,6 +90,8 @@ def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, po
     loop_config.yaw_guess = bool(loop_yaw_guess)
     if loop_gate is not None:
         loop_config.max_correspondence_distance = float(loop_gate)
+    if loop_robust is not None:
+        loop_config.robust_kind, loop_config.robust_scale = int(loop_robust[0]), float(loop_robust[1])
     if loop_on_device:
         from .global_map import GlobalMap
         store = global_map if global_map is not None else GlobalMap(ctx)
