@@ -867,6 +867,72 @@ int icpmi_loop_last_pairs(const icpmi_loop *loop, int64_t *pairs, int64_t cap, i
 int icpmi_loop_set_robust(icpmi_loop *loop, int32_t kind, double scale);
 int icpmi_loop_last_weights(const icpmi_loop *loop, double *weights, int64_t cap, int64_t *n_out);
 
+/* Scan-to-local-map odometry (not in the reference node, which registers each scan against the one before it,
+ * slam_node.cpp:132-138): a sliding voxel map of the recent scans in one frame, kept on the device, as the
+ * registration target.  The table holds sorted unique 63-bit voxel keys and one fp64 point per key, at most `capacity`
+ * rows (64 bytes of device memory per row of capacity: two buffers of key + point).  Its rules, which
+ * scripts/local_map_ref.py restates in numpy and reproduces byte for byte:
+ *   world point  of a scan row under `pose` (row-major 4 x 4): ((x R_a0 + y R_a1) + z R_a2) + t_a per axis a, no FMA.
+ *   key          per axis c = (long long)floor(p / voxel_size), accepted in [-2^20, 2^20);
+ *                key = (cx + 2^20) << 42 | (cy + 2^20) << 21 | (cz + 2^20): absolute, the table outlives a call.
+ *   range        d2 = (dx*dx + dy*dy) + dz*dz against the pose's translation; in range when d2 <= max_range * max_range.
+ *   dropped row  a coordinate of its world point is not finite, a cell is outside the key range, or it is out of range.
+ *   add(scan, pose):  residents out of range of this pose leave (evicted); among the rows not dropped, the lowest scan
+ *                row of each voxel is inserted if its key is not a surviving resident's (so a voxel whose resident was
+ *                evicted is taken again by this scan's row); the other rows of a held voxel are merged away; survivors
+ *                and insertions are the new table, sorted by key.  inserted + dropped + merged == n, and
+ *                rows == rows before - evicted + inserted.
+ *   capacity     an add whose result would exceed `capacity` rows returns ICPMI_ERR_CAPACITY and leaves the table as it was.
+ * max_range must cover the sensor's range: a scan whose far rows have no counterpart in the map loses the track.
+ *   icpmi_local_map_add*          n == 0 is legal and evicts only.  info may be NULL.  One wait for the device.  Behind
+ *                             it the new table is prepared as a registration target (search structure, normals) on the
+ *                             context's stream, without waiting: the next icpmi_local_map_register* finds it in place
+ *                             unless another call on the context prepared a search in between, in which case register
+ *                             prepares it again -- the results are the same bits either way.
+ *   icpmi_local_map_add_stream_frame  the scan is the filtered one the context's last icpmi_stream_push* left resident
+ *                             (ICPMI_ERR_ARG without one).
+ *   icpmi_local_map_points        *n_out = rows; out_xyz (rows x 3) and out_keys (rows), each may be NULL, are filled when
+ *                             cap >= rows (ICPMI_ERR_CAPACITY when one is given and cap is less).
+ *   icpmi_local_map_register*     icp_point_to_plane(source = scan, target = the table's points, cfg): bit for bit
+ *                             icpmi_align_device on the same two arrays, with whichever engine ICPMI_SEARCH_AUTO picks
+ *                             for the table's size.  cfg->initial_transform is the guess in the map's frame and
+ *                             result->transformation the scan's pose in it.  An empty table is ICPMI_ERR_EMPTY_TARGET.
+ *   icpmi_local_map_register_robust*  the same through icpmi_align_robust_device (rule and info as there).
+ *   icpmi_local_map_clear         empties the table; the configuration stays.
+ * ICPMI_ERR_ARG: voxel_size or max_range not finite or <= 0, capacity < 1 or > 2^27, a pose entry that is not finite,
+ * n < 0 or above 2^27.  ICPMI_ERR_NULL: any pointer above not marked optional.  The handle uses its context's stream and
+ * workspace: destroy it before the context. */
+typedef struct icpmi_local_map icpmi_local_map;
+typedef struct {
+    double voxel_size;  /* 0.5 */
+    double max_range;   /* 100.0: must cover the sensor's range */
+    int64_t capacity;   /* rows; 1 << 20 */
+} icpmi_local_map_config;
+typedef struct {
+    int64_t rows;       /* of the table after the add */
+    int64_t inserted, evicted, dropped, merged;
+} icpmi_local_map_info;
+void icpmi_local_map_config_default(icpmi_local_map_config *cfg);
+int icpmi_local_map_create(icpmi_ctx *ctx, const icpmi_local_map_config *cfg, icpmi_local_map **out);
+void icpmi_local_map_destroy(icpmi_local_map *map);
+int icpmi_local_map_clear(icpmi_local_map *map);
+int icpmi_local_map_add(icpmi_local_map *map, const double *xyz, int64_t n, const double pose[16], icpmi_local_map_info *info);
+int icpmi_local_map_add_device(icpmi_local_map *map, const double *d_xyz, int64_t n, const double pose[16],
+                               icpmi_local_map_info *info);
+int icpmi_local_map_add_stream_frame(icpmi_local_map *map, const double pose[16], icpmi_local_map_info *info);
+int icpmi_local_map_size(const icpmi_local_map *map, int64_t *rows);
+int icpmi_local_map_points(icpmi_local_map *map, double *out_xyz, uint64_t *out_keys, int64_t cap, int64_t *n_out);
+int icpmi_local_map_register(icpmi_local_map *map, const double *xyz, int64_t n, const icpmi_config *cfg, icpmi_result *result,
+                             double *error_history, int32_t history_cap);
+int icpmi_local_map_register_device(icpmi_local_map *map, const double *d_xyz, int64_t n, const icpmi_config *cfg,
+                                    icpmi_result *result, double *error_history, int32_t history_cap);
+int icpmi_local_map_register_robust(icpmi_local_map *map, const double *xyz, int64_t n, const icpmi_config *cfg,
+                                    const icpmi_robust *rule, icpmi_result *result, icpmi_robust_info *info,
+                                    double *error_history, int32_t history_cap);
+int icpmi_local_map_register_robust_device(icpmi_local_map *map, const double *d_xyz, int64_t n, const icpmi_config *cfg,
+                                           const icpmi_robust *rule, icpmi_result *result, icpmi_robust_info *info,
+                                           double *error_history, int32_t history_cap);
+
 /* profiling */
 int icpmi_reset_profile(icpmi_ctx *ctx);
 int icpmi_get_profile(icpmi_ctx *ctx, icpmi_profile *out);

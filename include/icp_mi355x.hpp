@@ -1334,6 +1334,129 @@ private:
     std::vector<std::size_t> rows_; // rows per frame
 };
 
+// The sliding voxel map of scan-to-local-map odometry (icpmi_local_map_*; not in the reference node, which registers
+// each scan against the one before it, slam_node.cpp:132-138): the recent scans in one frame, at most one point per
+// voxel, kept on the device as the registration target.  icp_mi355x.h has the table's rules.  max_range must cover
+// the sensor's range.  Non-copyable, movable; destroy it before its context.
+struct LocalMapConfig {
+    double voxel_size = 0.5;
+    double max_range = 100.0;
+    std::int64_t capacity = std::int64_t(1) << 20; // rows, 64 bytes of device memory each
+};
+struct LocalMapInfo { // of one add
+    long long rows = 0, inserted = 0, evicted = 0, dropped = 0, merged = 0;
+};
+
+class LocalMap {
+public:
+    explicit LocalMap(const LocalMapConfig &config = LocalMapConfig(), Context *ctx = nullptr)
+        : ctx_(ctx ? ctx : &default_context()), config_(config)
+    {
+        icpmi_local_map_config c;
+        icpmi_local_map_config_default(&c);
+        c.voxel_size = config.voxel_size;
+        c.max_range = config.max_range;
+        c.capacity = config.capacity;
+        check(icpmi_local_map_create(ctx_->get(), &c, &m_));
+    }
+    ~LocalMap() { icpmi_local_map_destroy(m_); }
+    LocalMap(const LocalMap &) = delete;
+    LocalMap &operator=(const LocalMap &) = delete;
+    LocalMap(LocalMap &&o) noexcept : ctx_(o.ctx_), config_(o.config_), m_(o.m_) { o.m_ = nullptr; }
+    LocalMap &operator=(LocalMap &&o) noexcept
+    {
+        if (this != &o) {
+            icpmi_local_map_destroy(m_);
+            ctx_ = o.ctx_;
+            config_ = o.config_;
+            m_ = o.m_;
+            o.m_ = nullptr;
+        }
+        return *this;
+    }
+    const LocalMapConfig &config() const { return config_; }
+
+    // evict what is out of range of `pose`, insert the scan's new voxels, merge
+    LocalMapInfo add(const PointCloud &scan, const Transformation &pose)
+    {
+        icpmi_local_map_info i{};
+        check(icpmi_local_map_add(m_, scan.data(), static_cast<int64_t>(scan.size()), pose.matrix().data(), &i));
+        return info(i);
+    }
+    // the same for the scan an OdometryStream on this context pushed last, without a trip through the host
+    LocalMapInfo add_stream_frame(const Transformation &pose)
+    {
+        icpmi_local_map_info i{};
+        check(icpmi_local_map_add_stream_frame(m_, pose.matrix().data(), &i));
+        return info(i);
+    }
+    void clear() { check(icpmi_local_map_clear(m_)); }
+    std::size_t size() const
+    {
+        int64_t n = 0;
+        check(icpmi_local_map_size(m_, &n));
+        return static_cast<std::size_t>(n);
+    }
+    // the table's points, sorted by key; keys (may be null) receives the keys
+    PointCloud points(std::vector<std::uint64_t> *keys = nullptr) const
+    {
+        const std::size_t n = size();
+        std::vector<double> xyz(3 * n);
+        if (keys) keys->resize(n);
+        int64_t got = 0;
+        check(icpmi_local_map_points(m_, xyz.data(), keys ? keys->data() : nullptr, static_cast<int64_t>(n), &got));
+        return PointCloud(std::move(xyz));
+    }
+    // icp_point_to_plane(scan, the table's points): config.initial_transform is the guess in the map's frame, the
+    // result's transformation the scan's pose in it
+    ICPResult register_scan(const PointCloud &scan, const ICPConfig &config = ICPConfig())
+    {
+        icpmi_config k = detail::to_c(config);
+        std::vector<double> hist(static_cast<std::size_t>(config.max_iterations > 0 ? config.max_iterations : 0) + 1);
+        icpmi_result r;
+        check(icpmi_local_map_register(m_, scan.data(), static_cast<int64_t>(scan.size()), &k, &r, hist.data(),
+                                       static_cast<int32_t>(hist.size())));
+        ICPResult out;
+        detail::fill(out, r, hist.data());
+        return out;
+    }
+    RobustICPResult register_scan(const PointCloud &scan, const RobustRule &rule, const ICPConfig &config = ICPConfig())
+    {
+        icpmi_config k = detail::to_c(config);
+        const icpmi_robust g = detail::to_c(rule);
+        icpmi_robust_info i{};
+        std::vector<double> hist(static_cast<std::size_t>(config.max_iterations > 0 ? config.max_iterations : 0) + 1);
+        icpmi_result r;
+        check(icpmi_local_map_register_robust(m_, scan.data(), static_cast<int64_t>(scan.size()), &k, &g, &r, &i, hist.data(),
+                                              static_cast<int32_t>(hist.size())));
+        RobustICPResult out;
+        detail::fill(out, r, hist.data());
+        out.weight_sum = i.weight_sum;
+        out.pairs = i.pairs;
+        out.rows = i.rows;
+        return out;
+    }
+
+private:
+    void check(int rc) const
+    {
+        if (rc != ICPMI_OK) throw IcpError(rc, icpmi_last_error(ctx_->get()));
+    }
+    static LocalMapInfo info(const icpmi_local_map_info &i)
+    {
+        LocalMapInfo o;
+        o.rows = i.rows;
+        o.inserted = i.inserted;
+        o.evicted = i.evicted;
+        o.dropped = i.dropped;
+        o.merged = i.merged;
+        return o;
+    }
+    Context *ctx_;
+    LocalMapConfig config_;
+    icpmi_local_map *m_ = nullptr;
+};
+
 // LoopClosureDetector with its database on the device, as an index over a GlobalMap's frames (icpmi_loop_*): an
 // entry is a store frame with the node's frame_idx as its label, so the node calls
 //     map.add_stream_frame(); loop.addFrame(map.frames() - 1, frame_idx);

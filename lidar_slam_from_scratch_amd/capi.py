@@ -44,6 +44,10 @@ EXPORTS = [
     "icpmi_map_ground_labels",
     "icpmi_align_robust", "icpmi_align_robust_device", "icpmi_align_robust_batch", "icpmi_loop_set_robust",
     "icpmi_loop_last_weights", "icpmi_stream_set_robust", "icpmi_stream_last_robust",
+    "icpmi_local_map_config_default", "icpmi_local_map_create", "icpmi_local_map_destroy", "icpmi_local_map_clear",
+    "icpmi_local_map_add", "icpmi_local_map_add_device", "icpmi_local_map_add_stream_frame", "icpmi_local_map_size",
+    "icpmi_local_map_points", "icpmi_local_map_register", "icpmi_local_map_register_device",
+    "icpmi_local_map_register_robust", "icpmi_local_map_register_robust_device",
 ]
 
 
@@ -192,6 +196,17 @@ class GroundInfo(C.Structure):
     """icpmi_ground_info"""
     _fields_ = [("n_ground", C.c_int64), ("n_obstacle", C.c_int64), ("n_ignored", C.c_int64),
                 ("bins_accepted", C.c_int64)]
+
+
+class LocalMapConfig(C.Structure):
+    """icpmi_local_map_config (defaults: local_map.LocalMapConfig)"""
+    _fields_ = [("voxel_size", C.c_double), ("max_range", C.c_double), ("capacity", C.c_int64)]
+
+
+class LocalMapInfo(C.Structure):
+    """icpmi_local_map_info: the table's rows after an add, and what the add did with the scan's rows and the residents"""
+    _fields_ = [("rows", C.c_int64), ("inserted", C.c_int64), ("evicted", C.c_int64), ("dropped", C.c_int64),
+                ("merged", C.c_int64)]
 
 
 class PoseGraphConfig(C.Structure):
@@ -404,6 +419,23 @@ def load_library(path=None):
     L.icpmi_loop_last_pairs.argtypes = [vp, i64p, C.c_int64, i64p]
     L.icpmi_loop_set_robust.argtypes = [vp, C.c_int32, C.c_double]
     L.icpmi_loop_last_weights.argtypes = [vp, dp, C.c_int64, i64p]
+    L.icpmi_local_map_config_default.argtypes = [C.POINTER(LocalMapConfig)]
+    L.icpmi_local_map_config_default.restype = None
+    L.icpmi_local_map_create.argtypes = [vp, C.POINTER(LocalMapConfig), C.POINTER(vp)]
+    L.icpmi_local_map_destroy.argtypes = [vp]
+    L.icpmi_local_map_destroy.restype = None
+    L.icpmi_local_map_clear.argtypes = [vp]
+    L.icpmi_local_map_add.argtypes = [vp, dp, C.c_int64, dp, C.POINTER(LocalMapInfo)]
+    L.icpmi_local_map_add_device.argtypes = [vp, vp, C.c_int64, dp, C.POINTER(LocalMapInfo)]
+    L.icpmi_local_map_add_stream_frame.argtypes = [vp, dp, C.POINTER(LocalMapInfo)]
+    L.icpmi_local_map_size.argtypes = [vp, i64p]
+    L.icpmi_local_map_points.argtypes = [vp, dp, C.POINTER(C.c_uint64), C.c_int64, i64p]
+    L.icpmi_local_map_register.argtypes = [vp, dp, C.c_int64, C.POINTER(Config), C.POINTER(Result), dp, C.c_int32]
+    L.icpmi_local_map_register_device.argtypes = [vp, vp, C.c_int64, C.POINTER(Config), C.POINTER(Result), dp, C.c_int32]
+    L.icpmi_local_map_register_robust.argtypes = [vp, dp, C.c_int64, C.POINTER(Config), C.POINTER(Robust), C.POINTER(Result),
+                                                  C.POINTER(RobustInfo), dp, C.c_int32]
+    L.icpmi_local_map_register_robust_device.argtypes = [vp, vp, C.c_int64, C.POINTER(Config), C.POINTER(Robust),
+                                                         C.POINTER(Result), C.POINTER(RobustInfo), dp, C.c_int32]
     for name in EXPORTS:
         getattr(L, name)  # raises AttributeError if a declared symbol is not exported
     _LIB = L
@@ -475,6 +507,8 @@ class Context:
             for d in list(getattr(self, "_loops", ())):         # icpmi_loop handles go before their maps
                 d.close()
             for m in list(getattr(self, "_maps", ())):          # ... and so do icpmi_map handles
+                m.close()
+            for m in list(getattr(self, "_local_maps", ())):    # ... and icpmi_local_map handles
                 m.close()
             self._lib.icpmi_destroy(self._h)
             self._h = None

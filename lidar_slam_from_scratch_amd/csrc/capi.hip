@@ -50,6 +50,7 @@
 #include "ground.h"
 #include "loop_store.h"
 #include "pose_graph.h"
+#include "local_map.h"
 
 using namespace icpmi;
 
@@ -59,6 +60,9 @@ hipError_t sort_pairs_u32(void *temp, size_t *temp_bytes, const unsigned *keys_i
 hipError_t sort_pairs_u64(void *temp, size_t *temp_bytes, const unsigned long long *keys_in,
                           unsigned long long *keys_out, const unsigned *vals_in, unsigned *vals_out,
                           unsigned n, hipStream_t stream);
+hipError_t sort_pairs_u64_all(void *temp, size_t *temp_bytes, const unsigned long long *keys_in,
+                              unsigned long long *keys_out, const unsigned *vals_in, unsigned *vals_out,
+                              unsigned n, hipStream_t stream);
 hipError_t run_lengths_u64(void *temp, size_t *temp_bytes, const unsigned long long *keys, unsigned n,
                            unsigned long long *unique_out, unsigned *counts_out, unsigned *runs_out,
                            hipStream_t stream);
@@ -5459,6 +5463,296 @@ int icpmi_loop_last_shifts(const icpmi_loop *L, int32_t *shifts, int64_t cap, in
     if (n > cap) return fail(ctx, ICPMI_ERR_CAPACITY, "output holds %lld shifts, needs %lld", (long long)cap, (long long)n);
     if (n) memcpy(shifts, L->last_shifts.data(), sizeof(int32_t) * (size_t)n);
     return ICPMI_OK;
+}
+
+} // extern "C"
+
+// ======================================================================================================================
+// Local map (local_map.h): the sliding voxel table scan-to-local-map odometry registers against.  Two buffers of
+// `capacity` rows each (keys, points); an add reads the current one and writes the other, and they change places once
+// the add's one wait has shown that the result fits.
+
+struct icpmi_local_map {
+    icpmi_ctx *ctx = nullptr;
+    icpmi_local_map_config cfg{};
+    DevBuf d_keys[2], d_pts[2];          // the table and the buffer the next add writes
+    int cur = 0;                         // which of the two is the table
+    int64_t rows = 0;
+    DevBuf d_scan, d_world;              // a host add's rows on the device; the scan's world points
+    DevBuf d_new_keys, d_new_vals;       // keys in | sorted ; rows in | sorted
+    DevBuf d_marks;                      // marks (rows + n + 1) | their exclusive sum ; then the words read back
+    unsigned *h_words = nullptr;         // pinned: surviving residents, rows of the new table, dropped rows
+};
+
+namespace {
+
+constexpr int64_t kLmapMaxRows = (int64_t)1 << 27;
+
+const double *lmap_points(const icpmi_local_map *m) { return (const double *)m->d_pts[m->cur].p; }
+
+// a table change: a target remembered at either buffer's address is no longer what the context's buffers describe
+void lmap_forget_target(icpmi_local_map *m)
+{
+    icpmi_ctx *ctx = m->ctx;
+    if (ctx->prep_tgt == (const double *)m->d_pts[0].p || ctx->prep_tgt == (const double *)m->d_pts[1].p) ctx->prep_valid = false;
+}
+
+// d_scan: n rows in device memory (null with n == 0)
+int lmap_add(icpmi_local_map *m, const double *d_scan, int64_t n64, const double pose[16], icpmi_local_map_info *info)
+{
+    icpmi_ctx *ctx = m->ctx;
+    hipStream_t s = ctx->stream;
+    for (int i = 0; i < 16; ++i)
+        if (!std::isfinite(pose[i])) return fail(ctx, ICPMI_ERR_ARG, "pose entry %d is not finite", i);
+    if (n64 < 0 || n64 > kLmapMaxRows) return fail(ctx, ICPMI_ERR_ARG, "n = %lld outside [0, 2^27]", (long long)n64);
+    Range range("icpmi:local_map_add");
+    const unsigned n = (unsigned)n64, R = (unsigned)m->rows;
+    const size_t un = n, elems = (size_t)R + un + 1;
+    int rc;
+    if ((rc = reserve(ctx, m->d_world, sizeof(double) * 3 * un))) return rc;
+    if ((rc = reserve(ctx, m->d_new_keys, sizeof(unsigned long long) * 2 * un))) return rc;
+    if ((rc = reserve(ctx, m->d_new_vals, sizeof(unsigned) * 2 * un))) return rc;
+    if ((rc = reserve(ctx, m->d_marks, sizeof(unsigned) * (2 * elems + 4)))) return rc;
+    unsigned long long *keys_in = (unsigned long long *)m->d_new_keys.p, *keys = keys_in + un;
+    unsigned *vals_in = (unsigned *)m->d_new_vals.p, *order = vals_in + un;
+    unsigned *marks = (unsigned *)m->d_marks.p, *offs = marks + elems, *words = marks + 2 * elems;
+    size_t b1 = 0, b2 = 0;
+    if (n) HIP_TRY(ctx, sort_pairs_u64_all(nullptr, &b1, keys_in, keys, vals_in, order, n, s));
+    HIP_TRY(ctx, exclusive_sum_u32(nullptr, &b2, marks, offs, (unsigned)elems, s));
+    if ((rc = reserve(ctx, ctx->sort_tmp, std::max(b1, b2)))) return rc;
+
+    const double r2 = m->cfg.max_range * m->cfg.max_range;
+    const unsigned long long *res_keys = (const unsigned long long *)m->d_keys[m->cur].p;
+    const double *res_pts = lmap_points(m);
+    const int nxt = m->cur ^ 1;
+    HIP_TRY(ctx, hipMemsetAsync(words, 0, 4 * sizeof(unsigned), s));
+    if (n) {
+        Rigid34 P{pose[0], pose[1], pose[2], pose[3], pose[4], pose[5], pose[6], pose[7], pose[8], pose[9], pose[10], pose[11]};
+        hipLaunchKernelGGL(k_lmap_keys, dim3(lmap_blocks(un)), dim3(256), 0, s, d_scan, n, P, m->cfg.voxel_size, r2,
+                           (double *)m->d_world.p, keys_in, vals_in, words);
+        HIP_TRY(ctx, sort_pairs_u64_all(ctx->sort_tmp.p, &b1, keys_in, keys, vals_in, order, n, s));
+    }
+    hipLaunchKernelGGL(k_lmap_marks, dim3(lmap_blocks(elems)), dim3(256), 0, s, res_keys, res_pts, R, (const unsigned long long *)keys, n,
+                       pose[3], pose[7], pose[11], r2, marks);
+    HIP_TRY(ctx, exclusive_sum_u32(ctx->sort_tmp.p, &b2, marks, offs, (unsigned)elems, s));
+    hipLaunchKernelGGL(k_lmap_merge, dim3(lmap_blocks(elems)), dim3(256), 0, s, res_keys, res_pts, R, (const unsigned long long *)keys,
+                       (const unsigned *)order, (const double *)m->d_world.p, n, (const unsigned *)marks, (const unsigned *)offs,
+                       (unsigned long long)m->cfg.capacity, (unsigned long long *)m->d_keys[nxt].p, (double *)m->d_pts[nxt].p, words);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(m->h_words, words, 4 * sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s)); // the call's one wait
+    const int64_t S = m->h_words[kLmapS], total = m->h_words[kLmapTotal], dropped = m->h_words[kLmapDroppedRows];
+    if (total > m->cfg.capacity)
+        return fail(ctx, ICPMI_ERR_CAPACITY, "the add would leave %lld rows; the local map holds %lld", (long long)total,
+                    (long long)m->cfg.capacity);
+    lmap_forget_target(m);
+    m->cur = nxt;
+    m->rows = total;
+    if (info) {
+        info->rows = total;
+        info->inserted = total - S;
+        info->evicted = (int64_t)R - S;
+        info->dropped = dropped;
+        info->merged = n64 - info->inserted - dropped;
+    }
+    // the new table as the next registration's target, queued and not waited for (a failure only means that
+    // the registration prepares it itself: it must not leave its text in the error string of an add that succeeded)
+    if (total > 0 && !ctx->comm && !ctx->cb_allreduce) {
+        const std::string keep = ctx->err;
+        if (prepare_target(ctx, lmap_points(m), (int)total, (int)n) != ICPMI_OK) {
+            ctx->err = keep;
+            ctx->prep_valid = false;
+        }
+        ctx->trailing_work = true;
+    }
+    return ICPMI_OK;
+}
+
+int lmap_check(icpmi_local_map *m, const double *pose)
+{
+    int rc;
+    if ((rc = check_common(m->ctx))) return rc;
+    if (!pose) return fail(m->ctx, ICPMI_ERR_NULL, "pose is NULL");
+    return ICPMI_OK;
+}
+
+// the scan in host memory -> the handle's staging rows
+int lmap_stage(icpmi_local_map *m, const double *xyz, int64_t n)
+{
+    icpmi_ctx *ctx = m->ctx;
+    int rc;
+    if (n < 0 || n > kLmapMaxRows) return fail(ctx, ICPMI_ERR_ARG, "n = %lld outside [0, 2^27]", (long long)n);
+    if ((rc = reserve(ctx, m->d_scan, sizeof(double) * 3 * (size_t)n))) return rc;
+    if (n) HIP_TRY(ctx, hipMemcpyAsync(m->d_scan.p, xyz, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    return ICPMI_OK;
+}
+
+// registration of n rows (device memory) against the table; rule: null for the plain one
+int lmap_register(icpmi_local_map *m, const double *d_xyz, int64_t n, const icpmi_config *cfg, const icpmi_robust *rule,
+                  icpmi_result *result, icpmi_robust_info *info, double *error_history, int32_t history_cap)
+{
+    icpmi_ctx *ctx = m->ctx;
+    if (rule)
+        return icpmi_align_robust_device(ctx, d_xyz, n, lmap_points(m), m->rows, cfg, rule, result, info, error_history, history_cap);
+    return icpmi_align_device(ctx, d_xyz, n, lmap_points(m), m->rows, cfg, result, error_history, history_cap);
+}
+
+int lmap_register_host(icpmi_local_map *m, const double *xyz, int64_t n, const icpmi_config *cfg, const icpmi_robust *rule,
+                       bool robust, icpmi_result *result, icpmi_robust_info *info, double *error_history, int32_t history_cap)
+{
+    if (!m) return ICPMI_ERR_NULL;
+    icpmi_ctx *ctx = m->ctx;
+    int rc = validate_align(ctx, xyz, n, lmap_points(m), m->rows, cfg, result, error_history, history_cap);
+    if (rc) return rc;
+    if (robust && !rule) return fail(ctx, ICPMI_ERR_NULL, "rule is NULL (no weights: icpmi_local_map_register)");
+    if ((rc = check_common(ctx))) return rc;
+    if ((rc = reserve(ctx, ctx->stage_b, sizeof(double) * 3 * (size_t)n))) return rc; // where icpmi_align puts its source
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->stage_b.p, xyz, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    return lmap_register(m, (const double *)ctx->stage_b.p, n, cfg, rule, result, info, error_history, history_cap);
+}
+
+} // namespace
+
+extern "C" {
+
+void icpmi_local_map_config_default(icpmi_local_map_config *cfg)
+{
+    if (!cfg) return;
+    cfg->voxel_size = 0.5;
+    cfg->max_range = 100.0;
+    cfg->capacity = (int64_t)1 << 20;
+}
+
+int icpmi_local_map_create(icpmi_ctx *ctx, const icpmi_local_map_config *cfg, icpmi_local_map **out)
+{
+    int rc;
+    if (!out) return fail(ctx, ICPMI_ERR_NULL, "out is NULL");
+    *out = nullptr;
+    if ((rc = check_common(ctx))) return rc;
+    if (!cfg) return fail(ctx, ICPMI_ERR_NULL, "cfg is NULL");
+    if (!(cfg->voxel_size > 0.0) || !std::isfinite(cfg->voxel_size)) return fail(ctx, ICPMI_ERR_ARG, "voxel_size must be finite and > 0");
+    if (!(cfg->max_range > 0.0) || !std::isfinite(cfg->max_range)) return fail(ctx, ICPMI_ERR_ARG, "max_range must be finite and > 0");
+    if (cfg->capacity < 1 || cfg->capacity > kLmapMaxRows) return fail(ctx, ICPMI_ERR_ARG, "capacity outside [1, 2^27]");
+    icpmi_local_map *m = new icpmi_local_map;
+    m->ctx = ctx;
+    m->cfg = *cfg;
+    hipError_t e = hipHostMalloc((void **)&m->h_words, 4 * sizeof(unsigned), hipHostMallocDefault);
+    for (int b = 0; b < 2 && e == hipSuccess; ++b) {
+        if ((e = hipMalloc(&m->d_keys[b].p, sizeof(unsigned long long) * (size_t)cfg->capacity)) == hipSuccess)
+            m->d_keys[b].cap = sizeof(unsigned long long) * (size_t)cfg->capacity;
+        if (e == hipSuccess && (e = hipMalloc(&m->d_pts[b].p, sizeof(double) * 3 * (size_t)cfg->capacity)) == hipSuccess)
+            m->d_pts[b].cap = sizeof(double) * 3 * (size_t)cfg->capacity;
+    }
+    if (e != hipSuccess) {
+        icpmi_local_map_destroy(m);
+        return fail(ctx, ICPMI_ERR_HIP, "local map of %lld rows: %s", (long long)cfg->capacity, hipGetErrorString(e));
+    }
+    *out = m;
+    return ICPMI_OK;
+}
+
+void icpmi_local_map_destroy(icpmi_local_map *m)
+{
+    if (!m) return;
+    (void)hipSetDevice(m->ctx->opt.device);
+    (void)hipStreamSynchronize(m->ctx->stream);
+    lmap_forget_target(m);
+    for (DevBuf *b : {&m->d_keys[0], &m->d_keys[1], &m->d_pts[0], &m->d_pts[1], &m->d_scan, &m->d_world, &m->d_new_keys,
+                      &m->d_new_vals, &m->d_marks})
+        release(*b);
+    if (m->h_words) (void)hipHostFree(m->h_words);
+    delete m;
+}
+
+int icpmi_local_map_clear(icpmi_local_map *m)
+{
+    if (!m) return ICPMI_ERR_NULL;
+    int rc;
+    if ((rc = check_common(m->ctx))) return rc;
+    lmap_forget_target(m);
+    m->rows = 0;
+    return ICPMI_OK;
+}
+
+int icpmi_local_map_add(icpmi_local_map *m, const double *xyz, int64_t n, const double pose[16], icpmi_local_map_info *info)
+{
+    if (!m) return ICPMI_ERR_NULL;
+    int rc;
+    if ((rc = lmap_check(m, pose))) return rc;
+    if (!xyz && n != 0) return fail(m->ctx, ICPMI_ERR_NULL, "null argument");
+    if ((rc = lmap_stage(m, xyz, n))) return rc;
+    return lmap_add(m, (const double *)m->d_scan.p, n, pose, info);
+}
+
+int icpmi_local_map_add_device(icpmi_local_map *m, const double *d_xyz, int64_t n, const double pose[16], icpmi_local_map_info *info)
+{
+    if (!m) return ICPMI_ERR_NULL;
+    int rc;
+    if ((rc = lmap_check(m, pose))) return rc;
+    if (!d_xyz && n != 0) return fail(m->ctx, ICPMI_ERR_NULL, "null argument");
+    return lmap_add(m, d_xyz, n, pose, info);
+}
+
+int icpmi_local_map_add_stream_frame(icpmi_local_map *m, const double pose[16], icpmi_local_map_info *info)
+{
+    if (!m) return ICPMI_ERR_NULL;
+    icpmi_ctx *ctx = m->ctx;
+    int rc;
+    if ((rc = lmap_check(m, pose))) return rc;
+    if (ctx->stream_prev_n < 0) return fail(ctx, ICPMI_ERR_ARG, "no resident frame: call icpmi_stream_push first");
+    return lmap_add(m, (const double *)ctx->stream_prev.p, ctx->stream_prev_n, pose, info);
+}
+
+int icpmi_local_map_size(const icpmi_local_map *m, int64_t *rows)
+{
+    if (!m) return ICPMI_ERR_NULL;
+    if (!rows) return fail(m->ctx, ICPMI_ERR_NULL, "rows is NULL");
+    *rows = m->rows;
+    return ICPMI_OK;
+}
+
+int icpmi_local_map_points(icpmi_local_map *m, double *out_xyz, uint64_t *out_keys, int64_t cap, int64_t *n_out)
+{
+    if (!m) return ICPMI_ERR_NULL;
+    icpmi_ctx *ctx = m->ctx;
+    int rc;
+    if ((rc = check_common(ctx))) return rc;
+    if (!n_out) return fail(ctx, ICPMI_ERR_NULL, "null argument");
+    *n_out = m->rows;
+    if ((!out_xyz && !out_keys) || m->rows == 0) return ICPMI_OK;
+    if (cap < m->rows) return fail(ctx, ICPMI_ERR_CAPACITY, "output holds %lld rows, needs %lld", (long long)cap, (long long)m->rows);
+    if (out_xyz) HIP_TRY(ctx, hipMemcpyAsync(out_xyz, lmap_points(m), sizeof(double) * 3 * (size_t)m->rows, hipMemcpyDeviceToHost, ctx->stream));
+    if (out_keys) HIP_TRY(ctx, hipMemcpyAsync(out_keys, m->d_keys[m->cur].p, sizeof(uint64_t) * (size_t)m->rows, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return ICPMI_OK;
+}
+
+int icpmi_local_map_register(icpmi_local_map *m, const double *xyz, int64_t n, const icpmi_config *cfg, icpmi_result *result,
+                             double *error_history, int32_t history_cap)
+{
+    return lmap_register_host(m, xyz, n, cfg, nullptr, false, result, nullptr, error_history, history_cap);
+}
+
+int icpmi_local_map_register_device(icpmi_local_map *m, const double *d_xyz, int64_t n, const icpmi_config *cfg, icpmi_result *result,
+                                    double *error_history, int32_t history_cap)
+{
+    if (!m) return ICPMI_ERR_NULL;
+    return lmap_register(m, d_xyz, n, cfg, nullptr, result, nullptr, error_history, history_cap);
+}
+
+int icpmi_local_map_register_robust(icpmi_local_map *m, const double *xyz, int64_t n, const icpmi_config *cfg, const icpmi_robust *rule,
+                                    icpmi_result *result, icpmi_robust_info *info, double *error_history, int32_t history_cap)
+{
+    return lmap_register_host(m, xyz, n, cfg, rule, true, result, info, error_history, history_cap);
+}
+
+int icpmi_local_map_register_robust_device(icpmi_local_map *m, const double *d_xyz, int64_t n, const icpmi_config *cfg,
+                                           const icpmi_robust *rule, icpmi_result *result, icpmi_robust_info *info,
+                                           double *error_history, int32_t history_cap)
+{
+    if (!m) return ICPMI_ERR_NULL;
+    if (!rule) return fail(m->ctx, ICPMI_ERR_NULL, "rule is NULL (no weights: icpmi_local_map_register_device)");
+    return lmap_register(m, d_xyz, n, cfg, rule, result, info, error_history, history_cap);
 }
 
 } // extern "C"

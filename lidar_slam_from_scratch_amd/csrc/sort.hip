@@ -31,6 +31,14 @@ hipError_t sort_pairs_u64(void *temp, size_t *temp_bytes, const unsigned long lo
     return rocprim::radix_sort_pairs(temp, *temp_bytes, keys_in, keys_out, vals_in, vals_out, n, 0u, 63u, stream);
 }
 
+// all 64 bits: the local map's (key, row) pairs, whose dropped rows carry bit 63 and sort behind every key (local_map.h)
+hipError_t sort_pairs_u64_all(void *temp, size_t *temp_bytes, const unsigned long long *keys_in,
+                              unsigned long long *keys_out, const unsigned *vals_in, unsigned *vals_out,
+                              unsigned n, hipStream_t stream)
+{
+    return rocprim::radix_sort_pairs(temp, *temp_bytes, keys_in, keys_out, vals_in, vals_out, n, 0u, 64u, stream);
+}
+
 // runs of equal keys: counts[r] and *runs_out (device) ; unique keys are written to unique_out
 hipError_t run_lengths_u64(void *temp, size_t *temp_bytes, const unsigned long long *keys, unsigned n,
                            unsigned long long *unique_out, unsigned *counts_out, unsigned *runs_out,

@@ -196,6 +196,106 @@ def run_odometry_stream(paths, ctx, voxel=0.5, max_iterations=50, tolerance=1e-6
     return track
 
 
+def _rigid_inverse(T):
+    """(R^T, -R^T t)"""
+    out = np.eye(4)
+    out[:3, :3] = T[:3, :3].T
+    out[:3, 3] = -(T[:3, :3].T @ T[:3, 3])
+    return out
+
+
+class LocalMapOdometry:
+    """Scan-to-local-map odometry, one frame at a time (not in the reference node): each scan is registered against a
+    sliding voxel map of the recent scans (local_map.LocalMap) from a constant-velocity guess, and then added to it under
+    the pose found.  The map lives in the odometry's own frame (pose 0 = identity).
+
+        frame 0                pose = I; add(frame, I)
+        too few points         the pose repeats, nothing is added, the remembered delta becomes I
+        otherwise              guess = pose_prev . delta_prev (pose_prev alone without the motion model)
+                               r = register(frame, guess); the node's gate (!converged || final_error > 1) keeps the guess
+                               delta = pose_prev^-1 . pose; add(frame, pose) ALWAYS -- a map that skips a gated frame
+                               stalls for good
+
+    push(frame) -> None for frame 0, else (delta, result, gated) with result None for a frame of too few points;
+    result has the fields of run_odometry's `align` results, .guess, .error_history, and .weight_sum / .pairs under a
+    robust rule."""
+
+    def __init__(self, ctx, config=None, max_iterations=50, tolerance=1e-6, min_points=1000, motion_model=True, robust=None):
+        from .local_map import LocalMap
+        self.ctx, self.map = ctx, LocalMap(ctx, config)
+        self.max_iterations, self.tolerance, self.min_points = max_iterations, tolerance, min_points
+        self.motion_model, self.robust = motion_model, robust
+        self.pose, self.delta, self.frames = np.eye(4), np.eye(4), 0
+
+    def close(self):
+        self.map.close()
+
+    def push(self, frame):
+        from . import capi
+
+        class _R:
+            pass
+
+        curr = np.ascontiguousarray(frame, dtype=np.float64)
+        self.frames += 1
+        if self.frames == 1:
+            self.map.add(curr, self.pose)
+            return None
+        if curr.shape[0] < self.min_points:
+            self.delta = np.eye(4)
+            return self.delta, None, True
+        guess = self.pose @ self.delta if self.motion_model else self.pose.copy()
+        cfg = capi.Context.make_config(max_iterations=self.max_iterations, tolerance=self.tolerance, initial_transform=guess)
+        r = _R()
+        if self.robust is None:
+            res, hist = self.map.register(curr, cfg)
+        else:
+            res, hist, info = self.map.register_robust(curr, cfg, self.robust)
+            r.weight_sum, r.pairs = float(info.weight_sum), int(info.pairs)
+        r.guess, r.error_history = guess, hist
+        r.transformation = np.array(res.transformation[:]).reshape(4, 4)
+        r.converged, r.final_error, r.num_iterations = bool(res.converged), res.final_error, res.num_iterations
+        bad = (not r.converged) or r.final_error > 1.0
+        pose = guess if bad else r.transformation
+        self.delta = _rigid_inverse(self.pose) @ pose
+        self.pose = pose
+        self.map.add(curr, pose)
+        return self.delta, r, bool(bad)
+
+
+def run_odometry_local_map(frames, ctx, config=None, max_iterations=50, tolerance=1e-6, min_points=1000, motion_model=True,
+                           robust=None, on_frame=None):
+    """Scan-to-local-map odometry over already-downsampled frames (LocalMapOdometry) -> OdometryTrack; track.deltas are
+    pose_{k-1}^-1 . pose_k, track.map_rows the table's size after each frame, and under a robust rule (a capi.Robust, or
+    (kind, scale[, max_distance])) track.weight_sums each registration's weight sum.  config: a local_map.LocalMapConfig;
+    its max_range must cover the sensor's range.  on_frame(k, local map, result or None): called after frame k is done."""
+    odo = LocalMapOdometry(ctx, config, max_iterations, tolerance, min_points, motion_model, robust)
+    track = OdometryTrack()
+    track.map_rows = []
+    track.weight_sums = []
+    try:
+        for k, curr in enumerate(frames):
+            t0 = time.perf_counter()
+            out = odo.push(curr)
+            track.map_rows.append(odo.map.size())
+            if out is not None:
+                delta, r, bad = out
+                track.poses.append(odo.pose.copy())
+                track.deltas.append(delta)
+                track.final_errors.append(r.final_error if r is not None else float("nan"))
+                track.iterations.append(r.num_iterations if r is not None else 0)
+                track.converged.append(bool(r.converged) if r is not None else False)
+                track.gated.append(bool(bad))
+                if robust is not None and r is not None:
+                    track.weight_sums.append(r.weight_sum)
+                track.frame_ms.append(1e3 * (time.perf_counter() - t0))
+            if on_frame:
+                on_frame(k, odo.map, out[1] if out is not None else None)
+    finally:
+        odo.close()
+    return track
+
+
 def absolute_trajectory_error(track, truth_poses):
     """RMS translation error against ground-truth poses expressed relative to frame 0."""
     t0_inv = np.linalg.inv(truth_poses[0])

@@ -47,7 +47,7 @@ def node_loop_config():
 def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, pose_graph_config=None,
              align=None, loop_backend=None, pose_graph=None, global_map=None, grid=None, map_voxel=1.0,
              loop_on_device=False, raycast=False, counts=False, live=False, loop_yaw_guess=False, loop_gate=None,
-             ground=None, odom_robust=None, loop_robust=None):
+             ground=None, odom_robust=None, loop_robust=None, odom_local_map=None):
     """frames: sequence of N x 3 fp64 clouds (already downsampled).  Returns a SlamRun.  global_map: an object with
     add_frame, recent_clouds and finish (None: no map is built); grid: its occupancy grid config (None: defaults).
     loop_on_device: the detector is loop_closure.StoreLoopClosureDetector over global_map (a global_map.GlobalMap),
@@ -68,13 +68,26 @@ def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, po
     `align` of the caller's it is refused.
     loop_robust: (kind, scale) (None: none); the detector's verifications run under those row weights
     (LoopClosureConfig.robust_kind / robust_scale), behind loop_gate if that is given too.
+    odom_local_map: a local_map.LocalMapConfig (None: frame-to-frame, as the reference node); each odometry factor's
+    delta and final_error come from scan-to-local-map odometry (odometry.LocalMapOdometry; not in the reference node).
+    The local map lives in its own odometry frame and is never touched by optimize: the factor is pose_{k-1}^-1 . pose_k
+    of that frame, and the track goes on as poses[-1] @ delta.  Combines with odom_robust; with an `align` of the
+    caller's it is refused.
     Under weights final_error is a weighted RMS and reads lower than the plain one: the gate `> 1.0` above, the
     detector's fitness threshold and the odometry factors' noise all read that number."""
     if loop_on_device and loop_backend is not None:
         raise ValueError("loop_backend and loop_on_device=True both choose the detector")
     if align is not None and odom_robust is not None:
         raise ValueError("odom_robust configures the default align; pass a robust align of your own instead")
-    if align is None:
+    run = SlamRun()
+    if align is not None and odom_local_map is not None:
+        raise ValueError("odom_local_map replaces the default align; it does not combine with an align of your own")
+    local_odo = None
+    if odom_local_map is not None:
+        from .odometry import LocalMapOdometry
+        local_odo = LocalMapOdometry(ctx, odom_local_map, max_iterations, tolerance, min_points, robust=odom_robust)
+        run.odom_weight_sums = []                                    # under odom_robust: per registration
+    elif align is None:
         from .odometry import gpu_align
         align = gpu_align(ctx, robust=odom_robust)
     if loop_backend is None and not loop_on_device:
@@ -84,7 +97,6 @@ def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, po
         pose_graph = PoseGraph(ctx, pose_graph_config)
     if ground is not None and global_map is not None:
         global_map.set_ground(ground)
-    run = SlamRun()
     store = None                                                     # (the store the device detector indexes)
     loop_config = node_loop_config()
     loop_config.yaw_guess = bool(loop_yaw_guess)
@@ -134,6 +146,8 @@ def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, po
     frames = list(frames)
     prev = np.ascontiguousarray(frames[0], dtype=np.float64)         # :69-72
     keep(prev)                                                       # :71
+    if local_odo is not None:
+        local_odo.push(prev)
     live_update()
     for k in range(1, len(frames)):
         curr = np.ascontiguousarray(frames[k], dtype=np.float64)
@@ -142,11 +156,18 @@ def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, po
         if curr.shape[0] < min_points:                               # :125-130
             run.poses.append(run.poses[-1].copy())
             prev = curr
+            if local_odo is not None:
+                local_odo.push(curr)
             live_update()
             continue
-        r = align(curr, prev, max_iterations, tolerance)             # :132-138
-        bad = (not r.converged) or r.final_error > 1.0               # :139-140
-        delta = np.eye(4) if bad else np.asarray(r.transformation, dtype=np.float64)
+        if local_odo is not None:                                    # scan-to-local-map: the gate keeps the guess
+            delta, r, bad = local_odo.push(curr)
+            if odom_robust is not None:
+                run.odom_weight_sums.append(r.weight_sum)
+        else:
+            r = align(curr, prev, max_iterations, tolerance)         # :132-138
+            bad = (not r.converged) or r.final_error > 1.0           # :139-140
+            delta = np.eye(4) if bad else np.asarray(r.transformation, dtype=np.float64)
         run.poses.append(run.poses[-1] @ delta)                      # :142-143
         add("odom", len(run.poses) - 2, len(run.poses) - 1, delta, float(r.final_error))   # :145
         prev = curr                                                  # :151
@@ -169,6 +190,8 @@ def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, po
         if live:
             live_update()
             run.live = global_map.live_counts()[0]
+    if local_odo is not None:
+        local_odo.close()
     if loop_on_device:                                               # the detector (and a private store) go now
         detector.close()
         if global_map is None:
