@@ -128,6 +128,9 @@ typedef struct {
     int64_t knn_culled_launches;                     /* k-NN setup of a target (normal estimation): coarse passes run over the (32-row
                                                         group, split) pairs that survive the box test instead of all pairs -- both MFMA
                                                         engines on targets of more than 12 splits, engine 3 at every size */
+    int64_t nn_rows_certified;                       /* all-pairs engine, match margin (ICPMI_NN_MARGIN, default on; sources of more
+                                                        than 32,768 rows): rows of its bounded passes whose kept match was certified as
+                                                        the unique nearest target -- neither listed nor scanned.  Profiling on only */
 } icpmi_profile;
 
 void icpmi_options_default(icpmi_options *opt);     /* device 0, normal_k 20 (icp.hpp:170), search AUTO or the

@@ -128,7 +128,7 @@ class Profile(C.Structure):
                 ("nn_group_pairs_run", C.c_int64),
                 ("exchange_ms", C.c_double), ("exchange_launches", C.c_int64), ("coarse_minima_bytes", C.c_int64),
                 ("nn_rows_listed", C.c_int64), ("nn_coarse_skipped", C.c_int64),
-                ("knn_culled_launches", C.c_int64)]
+                ("knn_culled_launches", C.c_int64), ("nn_rows_certified", C.c_int64)]
 
 
 MAX_RANKS_INFO = 64
@@ -965,6 +965,16 @@ class Context:
         rows, blocks = (C.c_uint32 * cap)(), (C.c_uint32 * cap)()
         n = min(int(fn(self._h, rows, blocks, cap)), cap)
         return list(rows[:n]), list(blocks[:n])
+
+    def nn_margin_passes(self, cap=1024):
+        """Per bounded pass of the last registration (profiling on, all-pairs engine with the match margin on): the rows
+        whose kept match was certified, which the pass neither listed nor scanned; empty where the margin was off."""
+        fn = self._lib.icpmi_debug_nn_margin
+        fn.restype = C.c_int64
+        fn.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_int64]
+        rows = (C.c_uint32 * cap)()
+        n = min(int(fn(self._h, rows, cap)), cap)
+        return list(rows[:n])
 
     def debug_loop_rows(self, n):
         """The rows the last registration's last pass matched, as the loop left them: (idx, cur, perm, idx_valid) in the

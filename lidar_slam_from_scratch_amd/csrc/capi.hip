@@ -221,6 +221,7 @@ struct icpmi_ctx {
     unsigned *h_grid = nullptr;                     // pinned: the set's size on its way back
     unsigned long long *h_cnt = nullptr;            // pinned: the resolve's counters on their way back (profiling)
     std::vector<unsigned> reuse_rows, reuse_blocks; // profiling: per pass of the last registration, rows listed and workgroup columns run
+    std::vector<unsigned> margin_rows;              // ... and rows certified by the match margin (empty where it was off)
     FilePrefetch *prefetch = nullptr;               // worker reading the next frame file (icpmi_stream_prefetch_file)
     // the target whose search structure and normals the context's buffers currently hold (prepare_target):
     // icpmi_stream_push prepares the NEXT frame's target while the caller is still busy with this frame's result
@@ -591,6 +592,15 @@ bool nn_reuse_enabled()
 }
 constexpr double kNnSkin = 0.5, kNnLoose = 8.0; // (the sweep: DESIGN.md, "List reuse")
 
+// ICPMI_NN_MARGIN=0: no row's match is certified by its margin (list_reuse.h, "the match margin"): the launches and bits of
+// the form before it.  Read at every call like ICPMI_NN_REUSE; on only where list reuse is and the loop's resolve is
+// k_nn_resolve_bounded (sources of more than 32,768 rows), ungated.
+bool nn_margin_enabled()
+{
+    const char *e = getenv("ICPMI_NN_MARGIN");
+    return !(e && e[0] == '0');
+}
+
 // The per-row arrays of the bounded pass inside ctx->nn_lists (n rows), then list reuse's word per 64 rows, its packed
 // list of rows (kRowListHead words in front) and its per-pass statistics
 struct NnListRows {
@@ -602,13 +612,18 @@ struct NnListRows {
     unsigned long long *mask;
     int *list;
     unsigned *stat_rows, *stat_blocks; // [kReuseStatPasses] each (profiling)
+    unsigned *stat_cert;               // [kReuseStatPasses] the match margin: rows certified per pass (profiling)
+    RowScan *scan;                     // the match margin's per-row records, covers and word per 64 rows (RowBounds)
+    double *cover;
+    unsigned long long *cert;
 };
 constexpr size_t kNnListRowBytes = sizeof(double) + 2 * sizeof(float) + sizeof(int) + sizeof(unsigned) * kNnEntCap + sizeof(RowList);
 constexpr int kReuseStatPasses = 1024; // (passes beyond are added to the last entry)
 size_t nn_list_bytes(int n)
 {
     return kNnListRowBytes * (size_t)n + 64 + sizeof(unsigned long long) * (((size_t)n + 63) / 64) +
-           sizeof(int) * ((size_t)n + kRowListHead) + sizeof(unsigned) * 2 * kReuseStatPasses;
+           sizeof(int) * ((size_t)n + kRowListHead) + sizeof(unsigned) * 3 * kReuseStatPasses + 64 +
+           (sizeof(RowScan) + sizeof(double)) * (size_t)n + sizeof(unsigned long long) * (((size_t)n + 63) / 64);
 }
 NnListRows nn_list_rows(const icpmi_ctx *ctx, int n)
 {
@@ -623,6 +638,10 @@ NnListRows nn_list_rows(const icpmi_ctx *ctx, int n)
     r.list = (int *)(r.mask + ((size_t)n + 63) / 64);
     r.stat_rows = (unsigned *)(r.list + (size_t)n + kRowListHead);
     r.stat_blocks = r.stat_rows + kReuseStatPasses;
+    r.stat_cert = r.stat_blocks + kReuseStatPasses;
+    r.scan = (RowScan *)(((uintptr_t)(r.stat_cert + kReuseStatPasses) + 63) & ~(uintptr_t)63);
+    r.cover = (double *)(r.scan + n);
+    r.cert = (unsigned long long *)(r.cover + n);
     return r;
 }
 
@@ -667,7 +686,7 @@ size_t coarse_groups_lds(int splits) { return sizeof(unsigned) * (2 * (size_t)sp
 int launch_nn_mfma(icpmi_ctx *ctx, const double *d_qry, int n, int m, int *d_idx, double *d_d2,
                    const IcpState *st, const double *d_tgt = nullptr, const double *d_nrm = nullptr,
                    double *d_partials = nullptr, int pruned_pass = -1, bool bounded = false, bool reuse_list = false,
-                   int stat_pass = 0)
+                   int stat_pass = 0, bool margin = false)
 {
     const int splits = ctx->nn_splits;
     int rc;
@@ -719,8 +738,12 @@ int launch_nn_mfma(icpmi_ctx *ctx, const double *d_qry, int n, int m, int *d_idx
         (const unsigned *)ent_row, d_idx, ctx->opt.profile >= 2 ? counters : (unsigned long long *)nullptr, d_tgt, d_nrm, d_partials, st
         if (resolve_waves(n) == 8)
             hipLaunchKernelGGL(k_nn_resolve4_bounded<8>, dim3(resolve_blocks(n)), dim3(512), 0, ctx->stream, ICPMI_BOUNDED_ARGS);
+        else if (margin) // (the match margin: certified rows are not scanned, scanned rows leave their new margin)
+            hipLaunchKernelGGL(k_nn_resolve_bounded<true>, dim3(resolve_blocks(n)), dim3(64 * kResolveWW), 0, ctx->stream, ICPMI_BOUNDED_ARGS,
+                               (const unsigned long long *)lr.cert, (const double *)lr.cover, lr.scan);
         else
-            hipLaunchKernelGGL(k_nn_resolve_bounded, dim3(resolve_blocks(n)), dim3(64 * kResolveWW), 0, ctx->stream, ICPMI_BOUNDED_ARGS);
+            hipLaunchKernelGGL(k_nn_resolve_bounded<false>, dim3(resolve_blocks(n)), dim3(64 * kResolveWW), 0, ctx->stream, ICPMI_BOUNDED_ARGS,
+                               (const unsigned long long *)nullptr, (const double *)nullptr, (RowScan *)nullptr);
 #undef ICPMI_BOUNDED_ARGS
         if (!reuse_list) ctx->prof.nn_pairs += (double)n * (double)m; // (a pass with list reuse: its workgroup columns that ran,
                                                                       // counted on the device -- profiling only -- and added after the call)
@@ -1303,6 +1326,9 @@ int align_device(icpmi_ctx *ctx, const double *d_src, int64_t n_src64, const dou
     // the rows).  A call's first pass lists every row (k_nn_prebound1 marks its lists as not to be kept).  The culled engine
     // keeps its own form.
     const bool reuse = bounded_loop && !pruned && nn_reuse_enabled();
+    // The match margin (list_reuse.h): rows whose kept match is certified as the unique nearest target are neither listed
+    // nor scanned.  k_nn_resolve_bounded's loops only; the gated and robust loops keep the form before it.
+    const bool margin = reuse && !gate && resolve_waves(n) == 0 && nn_margin_enabled();
     bool pass_list = false; // the coming bounded pass runs over the packed list (false: over every row -- a call's first pass)
     RowBounds rb{};
     NnListRows lr{};
@@ -1315,12 +1341,15 @@ int align_device(icpmi_ctx *ctx, const double *d_src, int64_t n_src64, const dou
             rb.mask = lr.mask;
             rb.skin = kNnSkin;
             rb.loose = kNnLoose;
-            if (ctx->opt.profile) HIP_TRY(ctx, hipMemsetAsync(lr.stat_rows, 0, sizeof(unsigned) * 2 * kReuseStatPasses, s));
+            if (margin) rb.scan = lr.scan, rb.cover = lr.cover, rb.cert = lr.cert;
+            if (ctx->opt.profile) HIP_TRY(ctx, hipMemsetAsync(lr.stat_rows, 0, sizeof(unsigned) * 3 * kReuseStatPasses, s));
         }
     }
     // before each kernel that moves the rows for pass `next`: where it counts the rows listed again (profiling)
+    unsigned *cert_count = nullptr; // (the match margin's: k_row_list counts the rows certified for the coming pass)
     auto next_pass_stats = [&](int next) {
         if (reuse) rb.rebuilt = ctx->opt.profile ? lr.stat_rows + std::min(next, kReuseStatPasses - 1) : nullptr;
+        if (margin) cert_count = ctx->opt.profile ? lr.stat_cert + std::min(next, kReuseStatPasses - 1) : nullptr;
     };
 
     // current_source = source * R0^T + t0^T (icp.hpp:174-176)
@@ -1368,7 +1397,7 @@ int align_device(icpmi_ctx *ctx, const double *d_src, int64_t n_src64, const dou
         if (n > 0 && fused) {
             if ((r2 = launch_nn_mfma(ctx, cur, n, m, idx, nullptr, st, d_tgt, nrm, partials,
                                      pruned ? pass_no : -1, bounded_loop /* incumbents in idx, bounds in place: from k_nn_prebound1 or the kernel that moved the rows */,
-                                     pass_list, pass_no))) return r2;
+                                     pass_list, pass_no, margin))) return r2;
             ++pass_no;
             if (!final_pass) next_pass_stats(pass_no);
             pass_list = reuse && !final_pass;
@@ -1446,7 +1475,8 @@ int align_device(icpmi_ctx *ctx, const double *d_src, int64_t n_src64, const dou
         }
         if (pass_list) // the rows just moved left their "listed again" words: the coming pass's list of rows
             hipLaunchKernelGGL(k_row_list, dim3(((n + 63) / 64 + kRowListThreads - 1) / kRowListThreads), dim3(kRowListThreads), 0, s,
-                               (const unsigned long long *)lr.mask, n, lr.list, (const IcpState *)st);
+                               (const unsigned long long *)lr.mask, n, lr.list, (const IcpState *)st,
+                               (const unsigned long long *)(margin ? lr.cert : nullptr), cert_count);
         return ICPMI_OK;
     };
 
@@ -1547,18 +1577,24 @@ int align_device(icpmi_ctx *ctx, const double *d_src, int64_t n_src64, const dou
     }
     ctx->reuse_rows.clear();
     ctx->reuse_blocks.clear();
+    ctx->margin_rows.clear();
     if (reuse && ctx->opt.profile && pass_no > 0) {
         // list reuse, per pass: the rows listed (the first pass lists all) and the workgroup columns of the coarse pass that
         // ran, ceil(rows / rows per workgroup); their pairs are the pairs searched, and a pass none of which ran is a skipped
         // coarse launch
         const int np = std::min(pass_no, kReuseStatPasses);
-        ctx->reuse_rows.resize(np);
-        ctx->reuse_blocks.resize(np);
-        HIP_TRY(ctx, hipMemcpy(ctx->reuse_rows.data(), lr.stat_rows, sizeof(unsigned) * np, hipMemcpyDeviceToHost));
-        HIP_TRY(ctx, hipMemcpy(ctx->reuse_blocks.data(), lr.stat_blocks, sizeof(unsigned) * np, hipMemcpyDeviceToHost));
+        // (the three arrays lie one behind the other: ONE blocking copy -- each costs the caller some 15 us)
+        std::vector<unsigned> stat((size_t)(margin ? 2 : 1) * kReuseStatPasses + np);
+        HIP_TRY(ctx, hipMemcpy(stat.data(), lr.stat_rows, sizeof(unsigned) * stat.size(), hipMemcpyDeviceToHost));
+        ctx->reuse_rows.assign(stat.begin(), stat.begin() + np);
+        ctx->reuse_blocks.assign(stat.begin() + kReuseStatPasses, stat.begin() + kReuseStatPasses + np);
         const int per = coarse_half_units(ctx, n, ctx->nn_splits) ? kCoarseQueries / kCoarseQT : kCoarseQueries;
         ctx->reuse_rows[0] = (unsigned)n;
         ctx->reuse_blocks[0] = (unsigned)((n + per - 1) / per);
+        if (margin) { // the match margin, per pass: the rows certified (the first pass certifies none)
+            ctx->margin_rows.assign(stat.begin() + 2 * kReuseStatPasses, stat.begin() + 2 * kReuseStatPasses + np);
+            for (int p = 0; p < np; ++p) ctx->prof.nn_rows_certified += ctx->margin_rows[p];
+        }
         for (int p = 0; p < np; ++p) {
             ctx->prof.nn_rows_listed += ctx->reuse_rows[p];
             if (p > 0) ctx->prof.nn_pairs += std::min((double)n, (double)ctx->reuse_blocks[p] * per) * (double)m;
@@ -3441,6 +3477,18 @@ extern "C" int64_t icpmi_debug_nn_reuse(const icpmi_ctx *ctx, uint32_t *rows_out
         if (rows_out) rows_out[p] = ctx->reuse_rows[p];
         if (blocks_out) blocks_out[p] = ctx->reuse_blocks[p];
     }
+    return np;
+}
+
+// The match margin of the last registration with profiling on (list_reuse.h): per bounded pass, the rows whose kept match
+// was certified and that were neither listed nor scanned.  Returns the number of passes (at most `cap` are written), 0
+// where the margin was off (ICPMI_NN_MARGIN=0, no list reuse, another resolve kernel) or without profiling.
+extern "C" int64_t icpmi_debug_nn_margin(const icpmi_ctx *ctx, uint32_t *rows_out, int64_t cap)
+{
+    if (!ctx) return 0;
+    const int64_t np = (int64_t)ctx->margin_rows.size();
+    for (int64_t p = 0; p < np && p < cap; ++p)
+        if (rows_out) rows_out[p] = ctx->margin_rows[p];
     return np;
 }
 

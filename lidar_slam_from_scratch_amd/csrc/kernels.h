@@ -480,6 +480,10 @@ struct RowList {
     double x, y, z; // where the row's list was built
     double r;       // its listing radius R_b (NaN: the list is not to be kept, e.g. a call's first pass)
 };
+struct RowScan {
+    double x, y, z; // where the resolve last scanned the row's listed slots
+    double g;       // every target but that scan's winner is at least g away from there (NaN: nothing is known)
+};
 struct RowBounds {
     const double *tgt; // the target, caller's order
     const int *idx;    // the rows' matches of the pass just finished
@@ -494,6 +498,17 @@ struct RowBounds {
     double skin;       // the skin as a fraction of the row's sqrt(ub)
     double loose;      // a list built for more than `loose` x the radius it would be built for now is not kept (0: no limit)
     unsigned *rebuilt; // profiling (or null): the coming pass's count of rows listed again
+    // The match margin (null: off; on only with list reuse -- list_reuse.h, "the match margin"): the resolve leaves, per row
+    // it scans, where it scanned it and how far every target but the winner is from there (g); a row whose kept match is
+    // nearer than g less the row's drift since needs no search at all in the coming pass.  Such a row keeps ub, is left
+    // with ubf = NaN / sqf = 0, keeps cnt, ent and xb as they are (a list is a standing geometric fact: it may certify
+    // again once the margin no longer does), is not in `mask`, and has its bit set in `cert` -- written like `mask`, every
+    // group's word in every pass.  Every other row leaves the cover of its list at its new place for the resolve.
+    RowScan *scan;            // [n] where the row was last scanned, and its g (NaN: no margin)
+    double *cover;            // [n] the coming resolve's: the radius around the row within which its list holds every target
+    unsigned long long *cert; // [(n + 63) / 64] bit b of word g = row 64 g + b needs no search in the coming pass
+                              // (profiling counts them from these words in k_row_list: once the loop has settled every
+                              // wave holds certified rows, and a count per wave here was 1,563 atomics on one word per pass)
 };
 // B rows of one thread (i0, i0 + stride, ...): every load that does not depend on the pose -- the rows, their previous
 // matches' indices, then those targets -- is requested by load(), which the fused kernels call BEFORE their serial step, so
@@ -505,6 +520,7 @@ struct RowBatch {
     int j[B];
     RowList lb[B]; // list reuse: where the row's list was built, and for which radius
     int c[B];      // ... and its length
+    RowScan sc[B]; // the match margin: where the row was last scanned, and its g
     // the rows and their previous matches' indices ...
     __device__ __forceinline__ void load_rows(const double *in, const RowBounds &rb, int i0, int stride, int n,
                                               const unsigned *__restrict__ perm = nullptr)
@@ -516,11 +532,13 @@ struct RowBatch {
             j[b] = -1;
             c[b] = 0;
             lb[b] = RowList{0.0, 0.0, 0.0, __builtin_nan("")};
+            sc[b] = RowScan{0.0, 0.0, 0.0, __builtin_nan("")};
             if (i < n) {
                 const size_t ii = perm ? perm[i] : (unsigned)i;
                 x[b] = in[3 * ii], y[b] = in[3 * ii + 1], z[b] = in[3 * ii + 2];
                 if (rb.tgt) j[b] = rb.idx[i];
                 if (rb.xb) lb[b] = rb.xb[i], c[b] = rb.cnt[i];
+                if (rb.scan) sc[b] = rb.scan[i];
             }
         }
     }
@@ -560,7 +578,7 @@ struct RowBatch {
                 // lists nothing.  No previous match (every target non-finite ...): +Inf, everything is listed.
                 double ub = __builtin_inf();
                 float ubf = __builtin_nanf(""), sqf = 0.f;
-                bool keep = false;
+                bool keep = false, cert = false;
                 if (__builtin_isfinite(px) && __builtin_isfinite(py) && __builtin_isfinite(pz)) {
                     if (have[b]) ub = sqdist(tx[b], ty[b], tz[b], px, py, pz);
                     double r2 = ub; // the radius^2 the coarse pass lists for
@@ -569,18 +587,25 @@ struct RowBatch {
                         // range), nor if R_b is more than `loose` times the radius it would be built for now (a loose list:
                         // slots the resolve would scan for nothing).  R_b NaN (first pass) fails every comparison.
                         const double sq = __builtin_sqrt(ub);
-                        const double ex = px - lb[b].x, ey = py - lb[b].y, ez = pz - lb[b].z;
-                        const double d = __builtin_sqrt((ex * ex + ey * ey) + ez * ez);
-                        const double mx = px - x[b], my = py - y[b], mz = pz - z[b];
-                        const double rn = list_radius(sq, __builtin_sqrt((mx * mx + my * my) + mz * mz), rb.skin);
-                        keep = c[b] > 0 && c[b] <= kNnEntCap && list_certified(sq, d, lb[b].r) &&
-                               (rb.loose <= 0.0 || lb[b].r <= rb.loose * rn);
-                        if (!keep) {
-                            r2 = rn * rn;
-                            rb.xb[i] = RowList{px, py, pz, rn};
+                        if (rb.scan) { // the match margin first: a certified row has nothing to do with its list
+                            const double sx = px - sc[b].x, sy = py - sc[b].y, sz = pz - sc[b].z;
+                            cert = match_certified(sq, __builtin_sqrt((sx * sx + sy * sy) + sz * sz), sc[b].g);
+                        }
+                        if (!cert) {
+                            const double ex = px - lb[b].x, ey = py - lb[b].y, ez = pz - lb[b].z;
+                            const double d = __builtin_sqrt((ex * ex + ey * ey) + ez * ez);
+                            const double mx = px - x[b], my = py - y[b], mz = pz - z[b];
+                            const double rn = list_radius(sq, __builtin_sqrt((mx * mx + my * my) + mz * mz), rb.skin);
+                            keep = c[b] > 0 && c[b] <= kNnEntCap && list_certified(sq, d, lb[b].r) &&
+                                   (rb.loose <= 0.0 || lb[b].r <= rb.loose * rn);
+                            if (!keep) {
+                                r2 = rn * rn;
+                                rb.xb[i] = RowList{px, py, pz, rn};
+                            }
+                            if (rb.cover) rb.cover[i] = keep ? list_cover(lb[b].r, d) : list_cover(rn, 0.0);
                         }
                     }
-                    if (!keep) {
+                    if (!keep && !cert) {
                         ubf = (float)r2;
                         ubf = (double)ubf < r2 ? __uint_as_float(__float_as_uint(ubf) + 1u) : ubf; // (r2 >= 0; Inf stays Inf)
                         sqf = __builtin_amdgcn_sqrtf(ubf);
@@ -590,20 +615,28 @@ struct RowBatch {
                 rb.ub[i] = ub;
                 rb.ubf[i] = ubf;
                 rb.sqf[i] = sqf;
-                if (!keep) rb.cnt[i] = 0;
+                if (!keep && !cert) rb.cnt[i] = 0;
                 if (rb.mask) {
                     // the wave's rows are 64 consecutive ones from a multiple of 64 (rows past n are not here and leave their
                     // bits clear): lane 0 holds the first of them and stores the group's word
-                    const unsigned long long again = __ballot(!keep && ubf == ubf);
+                    const unsigned long long again = __ballot(!keep && !cert && ubf == ubf);
                     if ((i & 63) == 0) rb.mask[i >> 6] = again;
                     if (rb.rebuilt) listed += (unsigned)__popcll(again);
+                    if (rb.cert) {
+                        const unsigned long long sure = __ballot(cert);
+                        if ((i & 63) == 0) rb.cert[i >> 6] = sure;
+                    }
                 }
             }
         }
         if (rb.rebuilt && listed && (int)(threadIdx.x & 63) == __ffsll((long long)__ballot(1)) - 1) atomicAdd(rb.rebuilt, listed);
     }
 };
-constexpr int kRowBatch = 4;
+// Rows per thread and batch.  The fused kernels' grids give a thread ONE row up to 131,072 rows (k_transform: 524,288), so a
+// batch only costs registers there, and with the match margin's record a batch of 4 rows no longer fit
+// k_finish_step_transform's 128 registers (1,024 threads): 216 dwords spilled, 41 before the record.  At 2: 125 registers,
+// nothing spilled (k_step_transform 114, k_transform 81; -Rpass-analysis=kernel-resource-usage).
+constexpr int kRowBatch = 2;
 
 // The packed list of the rows listed again, from the words the kernel that moved the rows left (RowBounds::mask):
 // list[0] = their number, list[1] = 1 where that is every row (the coarse pass then indexes its rows directly and reads no
@@ -619,11 +652,15 @@ constexpr int kRowBatch = 4;
 // alternating; profiles/row_list/).
 constexpr int kRowListThreads = 256;
 constexpr int kRowListHead = 16; // (the rows start on a 64-byte line)
+// Profiling of the match margin (`cert_count` non-null): the first workgroup also counts the set bits of the rows' "certified"
+// words (RowBounds::cert) and stores their number -- a plain store, no atomics.
 __global__ __launch_bounds__(kRowListThreads) void k_row_list(const unsigned long long *__restrict__ mask, int n, int *__restrict__ list,
-                                                              const IcpState *__restrict__ st)
+                                                              const IcpState *__restrict__ st,
+                                                              const unsigned long long *__restrict__ cert = nullptr,
+                                                              unsigned *__restrict__ cert_count = nullptr)
 {
     if (st->done) return; // (the rows were not moved and the coarse pass will not run)
-    __shared__ int part[3][kRowListThreads / 64];
+    __shared__ int part[4][kRowListThreads / 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int nw = (n + 63) / 64, g0 = blockIdx.x * kRowListThreads, g = g0 + tid;
     const unsigned long long w = g < nw ? mask[g] : 0ull;
@@ -632,7 +669,16 @@ __global__ __launch_bounds__(kRowListThreads) void k_row_list(const unsigned lon
     const unsigned above = wave_scan_incl((unsigned)row_list_count(mask, g0 + kRowListThreads + tid, nw, kRowListThreads));
     const unsigned incl = wave_scan_incl((unsigned)mine);
     if (lane == 63) part[0][wave] = (int)below, part[1][wave] = (int)above, part[2][wave] = (int)incl;
+    if (cert_count && blockIdx.x == 0) {
+        const unsigned sure = wave_scan_incl((unsigned)row_list_count(cert, tid, nw, kRowListThreads));
+        if (lane == 63) part[3][wave] = (int)sure;
+    }
     __syncthreads();
+    if (cert_count && blockIdx.x == 0 && tid == 0) {
+        int c = 0;
+        for (int v = 0; v < kRowListThreads / 64; ++v) c += part[3][v];
+        *cert_count = (unsigned)c;
+    }
     int at = 0, total = 0;
 #pragma unroll
     for (int v = 0; v < kRowListThreads / 64; ++v) {

@@ -24,6 +24,33 @@ ICPMI_HD inline double list_radius(const double sq, const double disp, const dou
 // value: the factor 1 + 1e-12 on the left covers them.  NaN r_b (a list not to be kept) fails the comparison.
 ICPMI_HD inline bool list_certified(const double sq, const double d, const double r_b) { return (sq + d) * (1.0 + 1e-12) <= r_b; }
 
+// ---- the match margin (RowBounds::scan, kernels.h; k_nn_resolve_bounded<true>, nn_bounded.h) ---------------------------
+// When the exact resolve scans a row at x_s it sees the exact distance of every target in the row's listed slots, and
+// the list holds every target within `cover` of x_s.  With d2 the distance of the nearest scanned target OTHER than the
+// winner, every target but the winner is at least g = min(d2, cover) away from x_s.  At a later pass the row sits at y,
+// delta = |y - x_s|, and its kept match is at sqrt(ub) exactly: every other target is at least g - delta away, so while
+// sqrt(ub) + delta < g the kept match is the unique nearest target at y and the exact resolve, which starts from it at
+// bd = ub, would return it unchanged -- no scan, no list, no coarse pass for that row.
+
+// The radius around the row's place y within which a list built at x_b for r_b holds every target: r_b - |y - x_b|
+// (d = |y - x_b|, 0 for a list built where the row is).  The factors push both terms the safe way by more than their
+// roundings (1e-15 relative, see list_certified).  NaN r_b (a call's first pass) gives NaN.
+ICPMI_HD inline double list_cover(const double r_b, const double d) { return r_b * (1.0 - 1e-12) - d * (1.0 + 1e-12); }
+
+// g from the SQUARED distance of the nearest scanned target other than the winner (`none`: no other target was scanned)
+// and the list's cover; the root is pulled down by more than its rounding.  NaN cover gives NaN, which never certifies.
+ICPMI_HD inline double match_margin(const double d2sq, const bool none, const double cover)
+{
+    if (!(cover == cover)) return cover;
+    const double d2 = __builtin_sqrt(d2sq) * (1.0 - 1e-12);
+    return (none || cover < d2) ? cover : d2;
+}
+
+// sq = sqrt(ub), delta = |y - x_s|: fp64 roots of sums of a few correctly rounded terms, each within 1e-15 of its exact
+// value, like g's ingredients; 1 + 1e-12 covers them.  Strict: a tie (a duplicated target point: d2 == the match's own
+// distance) never certifies.  NaN in g, sq or delta fails the comparison; so does sq = +Inf (a row without a match).
+ICPMI_HD inline bool match_certified(const double sq, const double delta, const double g) { return (sq + delta) * (1.0 + 1e-12) < g; }
+
 // ---- the packed list of the rows listed again (RowBounds::mask, k_row_list in kernels.h) -------------------------------
 // The kernel that moves the rows leaves one 64-bit word per group of 64 consecutive rows, bit b of word g set where row
 // 64 g + b is listed again.  The packed list is the set bits' rows in ascending order: row_list_count gives a word's place

@@ -42,13 +42,27 @@ constexpr int kNnSlotCap = 16; // listed slots scanned per row
 // dependent trips per wave -- 7 was the best (22.1).  Round by round (one round's query, distances and indices live: 75
 // registers) it fits 7 without spills, and measures 19.3 at 5 or 6, 19.9 at 7, 22.0 at 8: 5 stays (scripts/ab_kernels.sh,
 // same box).
+//
+// MARGIN (all-pairs engine with list reuse; list_reuse.h, "the match margin"; RowBounds in kernels.h): the kernel that moved
+// the rows has certified some of them -- their kept match is the unique nearest target, whatever their lists say -- and
+// left a bit per row in `cert`.  Such a row lists nothing here, is never `over`, keeps its incumbent and goes through
+// resolve_finish like any other.  The slot loads sit behind wave-uniform branches (a masked-off lane still costs the
+// address unit, this kernel's limit): a round none of whose four queries has a slot to scan issues none, and a wave whose
+// rows are all certified reads no list either.  A row that IS scanned also yields the distance of the nearest scanned
+// target other than the winner: every lane keeps its best two, the row of 16 takes the minimum of "my best unless it is
+// the scan's winner, else my second", and if the incumbent won without being the scan's winner the scan's own minimum is
+// it.  With the list's cover (`cover`, left by the mover) that is the row's new margin, stored with the row's place by
+// its owner; a row searched exhaustively (`over`) or without finite coordinates stores NaN, no margin.  MARGIN = false is
+// the kernel as it was: the culled engine's passes and ICPMI_NN_MARGIN=0 run that one.
 constexpr int kBoundedOcc = 5;
+template <bool MARGIN>
 __global__ __launch_bounds__(64 * kResolveWW) __attribute__((amdgpu_waves_per_eu(kBoundedOcc, 8))) void k_nn_resolve_bounded(
     const double *__restrict__ qry, int n, const double *__restrict__ sorted, const unsigned *__restrict__ perm, int m, int ms,
     int splits, const SplitFrame *__restrict__ frames, const double *__restrict__ ub_row, const int *__restrict__ cnt_row,
     const unsigned *__restrict__ ent_row, int *__restrict__ idx /* in: previous match, out: this pass's */,
     unsigned long long *__restrict__ counters, const double *__restrict__ tgt_orig, const double *__restrict__ nrm,
-    double *__restrict__ partials, const IcpState *__restrict__ st)
+    double *__restrict__ partials, const IcpState *__restrict__ st, const unsigned long long *__restrict__ cert = nullptr,
+    const double *__restrict__ cover_row = nullptr, RowScan *__restrict__ scan_row = nullptr)
 {
     constexpr int Q = 16, ROUNDS = Q / 4;
     static_assert(kNnEntCap == 8, "two words per sub-lane");
@@ -72,10 +86,28 @@ __global__ __launch_bounds__(64 * kResolveWW) __attribute__((amdgpu_waves_per_eu
     if (!look) bj = 0x7fffffff;
     if (bj == 0x7fffffff) bd = kMax;
 
+    // the match margin: the wave's 16 certificate bits by one wave-uniform load (rows qbase ... qbase + 15 of one word)
+    bool sure = false, scan_any = true;
+    if constexpr (MARGIN) {
+        const int qb = __builtin_amdgcn_readfirstlane(qbase < n ? qbase : n - 1);
+        const unsigned c16 = (unsigned)(cert[qb >> 6] >> (qb & 48)) & 0xFFFFu;
+        sure = valid && ((c16 >> ql) & 1u);
+        scan_any = __ballot(look && !sure) != 0ull;
+    }
+
     // the row's list: sub-lane `sub` of query ql holds words 2 sub and 2 sub + 1.  The FIRST listed slot is the lowest bit
     // of word 0 (a word is only ever appended with a bit set); all but a hundredth of the rows list nothing else.
-    const int cnt = cnt_row[ic];
-    const uint2 w = *reinterpret_cast<const uint2 *>(ent_row + (size_t)ic * kNnEntCap + 2 * sub);
+    int cnt = 0;
+    uint2 w = make_uint2(0u, 0u);
+    double cover = __builtin_nan("");
+    if (scan_any) { // (MARGIN: a wave with nothing to scan reads no list)
+        cnt = cnt_row[ic];
+        w = *reinterpret_cast<const uint2 *>(ent_row + (size_t)ic * kNnEntCap + 2 * sub);
+        if constexpr (MARGIN) cover = cover_row[ic];
+    }
+    if constexpr (MARGIN) {
+        if (sure) cnt = 0, w = make_uint2(0u, 0u);
+    }
     const unsigned w0 = (look && 2 * sub < cnt) ? w.x : 0u, w1 = (look && 2 * sub + 1 < cnt) ? w.y : 0u;
     const int mine = __popc(w0 & 0xFFFFu) + __popc(w1 & 0xFFFFu);
     // prefix over the query's four sub-lanes (one in each row of 16 lanes) and the total, by two row exchanges
@@ -89,8 +121,11 @@ __global__ __launch_bounds__(64 * kResolveWW) __attribute__((amdgpu_waves_per_eu
     // match it lists at least that match's slot and without one everything, unless a coordinate is beyond fp32's range
     // (a singular step can throw the cloud 1e47 away: fp64 still tells the targets apart, the coarse pass sees NaN and
     // lists nothing -- found by scripts/fuzz_bounded.py, seed 7368).
-    const bool over = look && (cnt <= 0 || cnt > kNnEntCap || nsl > kNnSlotCap);
+    const bool over = look && !sure && (cnt <= 0 || cnt > kNnEntCap || nsl > kNnSlotCap);
     const int nsl_eff = over ? 0 : nsl;
+    // MARGIN: the queries with a slot to scan, bit ql (from the lanes of sub-lane 0: every sub-lane knows nsl)
+    const unsigned scan16 = MARGIN ? (unsigned)__ballot(nsl_eff > 0) & 0xFFFFu : 0xFFFFu;
+    double d2o = kMax; // MARGIN, owner: squared distance of the nearest scanned target other than the winner
 
     // exact evaluation of the listed slots, one query per quarter-wave and round (lane takes l16, l16+16, ...: coalesced),
     // the original indices beside the coordinates.  Round by round -- query, first slot, further slots, the quarter's
@@ -117,26 +152,42 @@ __global__ __launch_bounds__(64 * kResolveWW) __attribute__((amdgpu_waves_per_eu
     }
 #pragma unroll
     for (int r = 0; r < ROUNDS; ++r) {
+        if (MARGIN && !(scan16 & (0x1111u << r))) continue; // (wave-uniform: none of this round's four queries has a slot)
         const int src = quarter * ROUNDS + r; // the query this quarter scans in round r (a lane with sub == 0)
         // (measured and dropped: the coordinates by a load of their own instead of six LDS crossbar trips -- twelve more
         // vector-memory instructions per lane in a kernel that waits on memory: 22.6 -> 23.8 us at C3, same box)
         const double qx = __shfl(px, src, 64), qy = __shfl(py, src, 64), qz = __shfl(pz, src, 64);
         const int nsr = __shfl(nsl_eff, src, 64);
-        double d = kMax;
+        double d = kMax, d2 = kMax; // (d2: MARGIN, this lane's second smallest)
         int jo = 0x7fffffff;
         auto scan_slot = [&](const int slot, const bool act) {
             const int j0 = (slot / kCols) * kSplitTargets + (slot % kCols) * kSlotTargets + l16;
             SlotBatch b;
             b.load(sorted, perm, m, ms, j0);
-            b.eval(m, j0, act, qx, qy, qz, d, jo);
+            if constexpr (MARGIN) b.eval2(m, j0, act, qx, qy, qz, d, jo, d2);
+            else b.eval(m, j0, act, qx, qy, qz, d, jo);
         };
         scan_slot(__shfl(first_slot, src, 64), nsr > 0);
         if (more)
             for (int t = 1; __ballot(t < nsr) != 0ull; ++t) scan_slot(t < nsr ? flist[wave][src][t] : 0, t < nsr);
+        const double dl = d;
+        const int jl = jo;
         row16_argmin(d, jo);
-        const bool take = own & ((ql % ROUNDS) == r) & look & ((d < bd) | ((d == bd) & (jo < bj)));
+        const bool mine_now = own & ((ql % ROUNDS) == r);
+        const bool take = mine_now & look & ((d < bd) | ((d == bd) & (jo < bj)));
         bd = take ? d : bd;
         bj = take ? jo : bj;
+        if constexpr (MARGIN) {
+            // the nearest scanned target other than the scan's winner jo ...
+            double o = jl == jo ? d2 : dl;
+            o = vmin_f64(o, row16_partner<0>(o));
+            o = vmin_f64(o, row16_partner<1>(o));
+            o = vmin_f64(o, row16_partner<2>(o));
+            o = vmin_f64(o, row16_partner<3>(o));
+            // ... and other than the row's winner: an incumbent that won without being jo leaves the scan's minimum itself
+            // (an incumbent that was scanned and won IS jo: same coordinates, same arithmetic, ties to the lowest index)
+            d2o = mine_now ? (bj == jo ? o : d) : d2o;
+        }
     }
 
     // rows whose list did not fit: every split whose bounding box is within the incumbent's distance, its slots culled
@@ -176,6 +227,15 @@ __global__ __launch_bounds__(64 * kResolveWW) __attribute__((amdgpu_waves_per_eu
             bj = qj;
         }
         if (lane == L) ++extra_splits;
+    }
+
+    if constexpr (MARGIN) {
+        // the scanned rows' new records (a certified row keeps the one it was certified by)
+        if (own && valid && !sure) {
+            const bool none = d2o >= kMax;
+            const double g = (look && !over && nsl_eff > 0) ? match_margin(d2o, none, cover) : __builtin_nan("");
+            scan_row[i] = RowScan{px, py, pz, g};
+        }
     }
 
     const unsigned extra_slots = (own && look && !over && nsl > 1) ? (unsigned)(nsl - 1) : 0u;

@@ -261,6 +261,15 @@ __global__ __launch_bounds__(kPreThreads) void k_nn_prebound1(const double *__re
     row_bound_store(rb, i, valid, px, py, pz, have, ICPMI_SX(sorted, ms, bjc), ICPMI_SY(sorted, ms, bjc), ICPMI_SZ(sorted, ms, bjc), lo, hi,
                     ubg);
     if (rb.xb && valid) rb.xb[i].r = __builtin_nan(""); // (list reuse: a first pass's list is never kept -- RowBounds, kernels.h)
+    if (rb.scan) {
+        // the match margin: the buffers outlive a call, so every call starts from "nothing is known" -- no row is certified
+        // for the first pass, whose lists (built for about the match's own distance) leave no margin either: NaN cover
+        if (valid) {
+            rb.scan[i] = RowScan{px, py, pz, __builtin_nan("")};
+            rb.cover[i] = __builtin_nan("");
+        }
+        if (valid && (i & 63) == 0) rb.cert[i >> 6] = 0ull;
+    }
     if (gl.cnt) block_cull(cl, (i - lane) / kGroupRows, lo, hi, ubg, frames, nsplits, gl, lane);
 }
 

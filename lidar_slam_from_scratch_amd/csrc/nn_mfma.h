@@ -1184,6 +1184,22 @@ struct SlotBatch {
             jo = take ? oj[o] : jo;
         }
     }
+    // ... and the lane's second smallest distance d2 with it (the match margin, nn_bounded.h): a candidate that takes
+    // the minimum leaves the old one as the second, any other one may lower the second
+    __device__ __forceinline__ void eval2(const int m, const int j0, const bool act, const double qx, const double qy, const double qz,
+                                          double &d, int &jo, double &d2) const
+    {
+#pragma unroll
+        for (int o = 0; o < N; ++o) {
+            const double dd = sqdist(x[o], y[o], z[o], qx, qy, qz);
+            const bool in = act & (j0 + 16 * o < m);
+            const bool take = in & ((dd < d) | ((dd == d) & (oj[o] < jo)));
+            const double rest = take ? d : dd; // (the one of the two that is not the minimum)
+            d2 = (in & (rest < d2)) ? rest : d2;
+            d = take ? dd : d;
+            jo = take ? oj[o] : jo;
+        }
+    }
 };
 
 template <int Q>
