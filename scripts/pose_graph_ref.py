@@ -14,6 +14,7 @@ Poses are 4x4 arrays; batched helpers take (n, 3, 3) rotations and (n, 3) vector
 import math
 
 import numpy as np
+import scipy.linalg as sla
 import scipy.sparse as sp
 import scipy.sparse.linalg as spla
 
@@ -246,9 +247,17 @@ EPS = np.finfo(np.float64).eps
 def _solve(H, g, lam, ordering):
     """(H + lam I) delta = -g by sparse LU without row pivoting (diag_pivot_thresh 0, symmetric mode): on an SPD
     matrix its pivots are those of the Cholesky; a non-positive or non-finite one is an unsolved system, as GTSAM's
-    IndeterminantLinearSystemException (caught in LevenbergMarquardtOptimizer::tryLambda)."""
+    IndeterminantLinearSystemException (caught in LevenbergMarquardtOptimizer::tryLambda).  ordering "DENSE": the same
+    matrix by numpy's dense Cholesky, a third rounding of the same step for the tests' spread."""
     n = H.shape[0]
     M = (H + lam * sp.identity(n, format="csc")).tocsc()
+    if ordering == "DENSE":
+        try:
+            L = np.linalg.cholesky(M.toarray())
+        except np.linalg.LinAlgError:
+            return None
+        d = sla.solve_triangular(L, sla.solve_triangular(L, -g, lower=True), lower=True, trans="T")
+        return d if np.all(np.isfinite(d)) else None
     try:
         lu = spla.splu(M, permc_spec=ordering, diag_pivot_thresh=0.0, options=dict(SymmetricMode=True))
     except RuntimeError:

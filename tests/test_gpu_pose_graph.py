@@ -6,7 +6,8 @@ Tolerance per pose: 10x the restatement's own spread (COLAMD against NATURAL ord
 relative margin below 1e-6 in the restatement is sensitive: its seed is changed, never excused (asserted below).
 Cases sit at the solver's dispatch edges: chain lengths around K (every K-th pose index is a separator), loops sharing
 an endpoint, a loop between adjacent indices (a chain factor), duplicates, out-of-order factors, a skipped index,
-rejected steps, the relative test switched off and a KITTI-00-sized graph."""
+rejected steps, the relative test switched off and a KITTI-00-sized graph.  Those all turn about z; the last part of the file
+tumbles (general axes, residuals up to 3.1 rad through every Shepperd branch) and sweeps the reduced system's size."""
 import os
 import sys
 
@@ -97,7 +98,9 @@ def apply(g, ops):
             g.add_loop_closure(op[1], op[2], op[3])
 
 
-def run_case(ctx, ops, max_iterations=100, rel_tol=1e-5):
+def run_case(ctx, ops, max_iterations=100, rel_tol=1e-5, dense=False):
+    """dense: the spread gains a third member of the reference, the same steps solved by numpy's dense Cholesky (two
+    sparse-LU orderings understate solver rounding on the stiff tumbling systems, whose initial error is ~1e7)."""
     from lidar_slam_from_scratch_amd import pose_graph as pg
     ref = R.PoseGraph(R.PoseGraphConfig(max_iterations=max_iterations, relative_error_tol=rel_tol))
     apply(ref, ops)
@@ -116,11 +119,17 @@ def run_case(ctx, ops, max_iterations=100, rel_tol=1e-5):
     assert (st.iterations, st.inner_trials, st.stop_reason) == (sa.iterations, sa.inner_trials, sa.stop_reason), \
         ((st.iterations, st.inner_trials, st.stop_reason), (sa.iterations, sa.inner_trials, sa.stop_reason))
     spread = np.abs(a - b).reshape(len(a), -1).max(axis=1)
+    hs = np.abs(np.array(sa.history) - np.array(sb.history))
+    if dense:
+        assert ref.optimize("DENSE")
+        c, sc = np.stack(ref.get_all_poses()), ref.stats
+        assert (sa.iterations, sa.inner_trials) == (sc.iterations, sc.inner_trials)
+        spread = np.maximum(spread, np.abs(a - c).reshape(len(a), -1).max(axis=1))
+        hs = np.maximum(hs, np.abs(np.array(sa.history) - np.array(sc.history)))
     floor = 1e-12 * (1.0 + np.linalg.norm(a[:, :3, 3], axis=1))
     tol = np.maximum(10 * spread, floor)
     err = np.abs(got - a).reshape(len(a), -1).max(axis=1)
     assert (err <= tol).all(), (int(np.argmax(err / tol)), float(np.max(err / tol)))
-    hs = np.abs(np.array(sa.history) - np.array(sb.history))
     htol = np.maximum(10 * hs, 1e-12 * (1 + np.abs(sa.history)))
     assert len(st.history) == len(sa.history)
     assert (np.abs(np.array(st.history) - sa.history) <= htol).all(), (st.history, sa.history)
@@ -281,3 +290,154 @@ def test_run_slam_out_and_back(ctx):
     st = run.optimizations[-1][2]
     assert (st.iterations, st.inner_trials) == (ref.stats.iterations, ref.stats.inner_trials)
     print("run_slam closures", len(run.closures), "optimizations", [(o[0], o[2].iterations) for o in run.optimizations])
+
+
+# ------------------------------------------------------------------------------------------------ off the planar path
+# The graphs above turn about z only.  These tumble: general axes in every step, residuals of up to ~3.1 rad about x, y,
+# z and (1,1,1) (the x, y and z Shepperd branches of so3_log, the closed forms of se3_coefs, the coupling block of
+# se3_jr_inv and the adjoint with W and V not aligned), and reduced systems of every size class of the dense Cholesky.
+
+NEAR_X, NEAR_Y, NEAR_Z, DIAG = (1.0, 0.05, -0.03), (-0.04, 1.0, 0.06), (0.03, -0.05, 1.0), (1.0, 1.0, 1.0)
+
+
+def _rot(axis, angle):
+    a = np.asarray(axis, dtype=np.float64)
+    return R.se3_exp(np.r_[angle * a / np.linalg.norm(a), 0.0, 0.0, 0.0])
+
+
+def _tumble(n, rng, sigma):
+    """Every step turns by N(0, sigma^2) per component about a general axis and moves by about (1, 0, 0)."""
+    T = [np.eye(4)]
+    for _ in range(n - 1):
+        T.append(T[-1] @ R.se3_exp(np.r_[rng.normal(0, sigma, 3), 1.0 + rng.normal(0, 0.1), rng.normal(0, 0.2, 2)]))
+    return T
+
+
+def tumble_ops(n, seed, axis, wrong, sigma=0.5):
+    """A tumbling chain, a prior on pose 0 and a second one on pose n - 1 turned by `wrong` radians about `axis`: the
+    whole chain must turn."""
+    rng = np.random.default_rng(seed)
+    gt = _tumble(n, rng, sigma)
+    ops = [("prior", 0, gt[0])]
+    ops += [("odom", k, k + 1, _rel(gt[k], gt[k + 1]) @ _noise(rng, 0.02, 0.05), 0.0) for k in range(n - 1)]
+    ops.append(("prior", n - 1, gt[n - 1] @ _rot(axis, wrong)))
+    return ops
+
+
+def tumble_loop_ops(seed, n=130):
+    """130 tumbling poses and five closures whose measurements are off by 2.8, 2.9 and 3.0 rad about x, y and z and by
+    0.4-0.5 rad for two more, one of them between 63 and 64 (a separator by index and its chain neighbour)."""
+    rng = np.random.default_rng(seed)
+    gt = _tumble(n, rng, 0.5)
+    ops = [("prior", 0, gt[0])]
+    ops += [("odom", k, k + 1, _rel(gt[k], gt[k + 1]) @ _noise(rng, 0.02, 0.05), 0.0) for k in range(n - 1)]
+    for i, j, axis, off in ((5, 100, NEAR_X, 2.8), (20, 90, NEAR_Y, 2.9), (40, 120, NEAR_Z, 3.0),
+                            (63, 64, (0.5, -1.0, 0.7), 0.45), (10, 127, (-0.8, 0.3, 1.0), 0.5)):
+        ops.append(("loop", i, j, _rel(gt[i], gt[j]) @ _rot(axis, off)))
+    return ops
+
+
+def sweep_ops(b, seed, n=62):
+    """62 tumbling poses (no index = 63 mod 64) and closures whose distinct endpoints number exactly b, each pair at
+    least two indices apart: the reduced system has 6 b rows."""
+    rng = np.random.default_rng(seed)
+    gt = _tumble(n, rng, 0.15)
+    ops = [("prior", 0, gt[0])]
+    ops += [("odom", k, k + 1, _rel(gt[k], gt[k + 1]) @ _noise(rng), 0.0) for k in range(n - 1)]
+    while True:
+        e = np.sort(rng.choice(n, size=b, replace=False))
+        if b > 2 or e[1] - e[0] >= 2:
+            break
+    h = max(b // 2, 1)
+    pairs = [(int(e[k]), int(e[k + h])) for k in range(b // 2)]
+    if b % 2:
+        pairs.append((int(e[0]), int(e[b - 1])))
+    assert all(j - i >= 2 for i, j in pairs) and len({x for p in pairs for x in p}) == b
+    ops += [("loop", i, j, _rel(gt[i], gt[j]) @ _noise(rng, 0.001, 0.01)) for i, j in pairs]
+    return ops
+
+
+def separators(ops):
+    """pg_plan's rule (capi.hip): index % K == K - 1, or an endpoint of a between factor with j != i + 1."""
+    idx = {op[1] for op in ops} | {op[2] for op in ops if op[0] != "prior"}
+    sep = {k for k in idx if k % K == K - 1}
+    for op in ops:
+        if op[0] != "prior" and op[2] != op[1] + 1:
+            sep |= {op[1], op[2]}
+    return sep
+
+
+class LogWatch:
+    """Wraps the restatement's so3_log (one rotation at a time) for the reference runs of a case: which Shepperd branch
+    each call took and the largest angle it returned, so that the case cannot quietly turn planar or small."""
+
+    def __init__(self, monkeypatch):
+        self.angle = {0: 0.0, 1: 0.0, 2: 0.0, 3: 0.0}       # branch (0 w, 1 x, 2 y, 3 z) -> largest angle
+        self.off_z = 0.0                                    # largest |omega_x| or |omega_y| of any residual
+        inner = R._so3_log1
+
+        def watched(Rm):
+            tr = Rm[0, 0] + Rm[1, 1] + Rm[2, 2]
+            if tr >= Rm[0, 0] and tr >= Rm[1, 1] and tr >= Rm[2, 2]:
+                br = 0
+            elif Rm[0, 0] >= Rm[1, 1] and Rm[0, 0] >= Rm[2, 2]:
+                br = 1
+            else:
+                br = 2 if Rm[1, 1] >= Rm[2, 2] else 3
+            w = inner(Rm)
+            self.angle[br] = max(self.angle[br], float(np.linalg.norm(w)))
+            self.off_z = max(self.off_z, float(abs(w[0])), float(abs(w[1])))
+            return w
+
+        monkeypatch.setattr(R, "_so3_log1", watched)
+
+    def branches(self):
+        return {b for b, a in self.angle.items() if a > 0.0}
+
+
+@pytest.mark.parametrize("n", [8, 70])
+@pytest.mark.parametrize("wrong", [2.6, 3.05])
+@pytest.mark.parametrize("axis,branch", [(NEAR_X, {1}), (NEAR_Y, {2}), (NEAR_Z, {3}), (DIAG, {1, 2, 3})],
+                         ids=["x", "y", "z", "xyz"])
+def test_tumbling_chain_turns_as_a_whole(ctx, monkeypatch, n, wrong, axis, branch):
+    watch = LogWatch(monkeypatch)
+    ops = tumble_ops(n, seed=1000 + n, axis=axis, wrong=wrong)
+    assert (K - 1 in separators(ops)) == (n > K)
+    _, st = run_case(ctx, ops, dense=True)
+    took = watch.branches() & {1, 2, 3}
+    assert took and took <= branch, (took, branch)
+    assert max(watch.angle[b] for b in took) >= wrong - 0.2 and watch.off_z >= 0.1
+    print("tumble", n, wrong, axis, st.iterations, st.inner_trials, watch.angle)
+
+
+def test_tumbling_loops(ctx, monkeypatch):
+    watch = LogWatch(monkeypatch)
+    ops = tumble_loop_ops(seed=130)
+    assert separators(ops) == {5, 100, 20, 90, 40, 120, 63, 10, 127}      # (63, 64) is a chain factor
+    _, st = run_case(ctx, ops, dense=True)
+    assert watch.branches() == {0, 1, 2, 3}
+    assert min(watch.angle[b] for b in (1, 2, 3)) >= 2.7 and watch.angle[0] >= 0.4 and watch.off_z >= 2.7
+    print("tumble loops", st.iterations, st.inner_trials, watch.angle)
+
+
+# b separators -> a reduced system of 6 b rows (panel width 32): one partial panel; 30; a panel and a tail of 4; two
+# panels and 2; exactly three; three and 6; exactly six; more than 64 rows under a panel (k_chol_panel's second
+# workgroup) from 102 on; k_trsv_pair past 256 + 32 rows at 294; every node a separator at 372 (no segment at all).
+SWEEP = [(2, 21), (5, 22), (6, 23), (11, 24), (16, 25), (17, 26), (32, 27), (33, 28), (49, 29), (62, 30)]
+
+
+@pytest.mark.parametrize("b,seed", SWEEP)
+def test_reduced_size_sweep(ctx, monkeypatch, b, seed):
+    watch = LogWatch(monkeypatch)
+    ops = sweep_ops(b, seed)
+    assert 6 * len(separators(ops)) == {2: 12, 5: 30, 6: 36, 11: 66, 16: 96, 17: 102, 32: 192, 33: 198, 49: 294,
+                                        62: 372}[b]
+    _, st = run_case(ctx, ops)
+    assert watch.off_z >= 0.005      # the residuals are of the odometry noise here, but not about z alone
+    print("sweep", b, 6 * b, st.iterations, st.inner_trials)
+
+
+def test_sweep_covers_both_kinds_of_end_segment():
+    """Pose 0 or pose 61 a separator in some cases and not in others: a segment's left / right is then -1 or not."""
+    seps = [separators(sweep_ops(b, seed)) for b, seed in SWEEP if b < 62]
+    assert {0 in s for s in seps} == {True, False} and {61 in s for s in seps} == {True, False}

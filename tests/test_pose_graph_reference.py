@@ -216,6 +216,10 @@ def test_drift_case_loop_closures_cut_ate():
     a = np.stack(g.get_all_poses())
     g.optimize("NATURAL")
     assert np.abs(np.stack(g.get_all_poses()) - a).max() < 1e-10
+    # and so does the dense Cholesky of the same matrices, step for step
+    it = (g.stats.iterations, g.stats.inner_trials)
+    g.optimize("DENSE")
+    assert np.abs(np.stack(g.get_all_poses()) - a).max() < 1e-10 and (g.stats.iterations, g.stats.inner_trials) == it
 
 
 def rotational_drift_graph(n=60, drift=0.1):
