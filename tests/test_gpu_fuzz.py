@@ -30,7 +30,9 @@ def test_fuzz_stopping_tests_against_the_oracle_loop(oracle, monkeypatch):
     """scripts/fuzz_stopping.py: registrations with the caller's settings (50, 1e-6, 1e-9) on LiDAR-like pairs and room
     corners through AUTO, the all-pairs and the culled engine: num_iterations, converged and history length equal to the
     oracle's on every trial whose stopping-test margin exceeds 1e-12 (trials under it are counted and printed): 40
-    seeded trials here."""
+    seeded trials here.  On these 40 the oracle converges in 4-9 iterations with a spread of 6e-15 m under reversed
+    summation, so none may be SENSITIVE (the cap is 40 // 100 = 0); the rule for registrations that are is held by
+    tests/test_stopping_rule.py and tests/test_gpu_stopping_pinned.py."""
     import fuzz_stopping
     assert fuzz_stopping.main(["fuzz_stopping.py", "40", "9000"]) == 0
 
