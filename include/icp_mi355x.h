@@ -131,6 +131,10 @@ typedef struct {
     int64_t nn_rows_certified;                       /* all-pairs engine, match margin (ICPMI_NN_MARGIN, default on; sources of more
                                                         than 32,768 rows): rows of its bounded passes whose kept match was certified as
                                                         the unique nearest target -- neither listed nor scanned.  Profiling on only */
+    int64_t nn_lean_passes;                          /* all-pairs engine, lean passes (ICPMI_NN_LEAN, default on; single-GPU ungated
+                                                        loops over sources of 65,473 rows and more): passes queued without the row-list
+                                                        and coarse launches, because the two latest passes the host knew of had
+                                                        listed no row.  Counted on the host, profiling on or off */
 } icpmi_profile;
 
 void icpmi_options_default(icpmi_options *opt);     /* device 0, normal_k 20 (icp.hpp:170), search AUTO or the

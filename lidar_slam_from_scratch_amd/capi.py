@@ -128,7 +128,8 @@ class Profile(C.Structure):
                 ("nn_group_pairs_run", C.c_int64),
                 ("exchange_ms", C.c_double), ("exchange_launches", C.c_int64), ("coarse_minima_bytes", C.c_int64),
                 ("nn_rows_listed", C.c_int64), ("nn_coarse_skipped", C.c_int64),
-                ("knn_culled_launches", C.c_int64), ("nn_rows_certified", C.c_int64)]
+                ("knn_culled_launches", C.c_int64), ("nn_rows_certified", C.c_int64),
+                ("nn_lean_passes", C.c_int64)]
 
 
 MAX_RANKS_INFO = 64
@@ -958,7 +959,9 @@ class Context:
 
     def nn_reuse_passes(self, cap=1024):
         """Per bounded pass of the last registration (profiling on, all-pairs engine with list reuse): the rows its coarse
-        pass listed and the workgroup columns it ran (ceil(rows / rows per workgroup)), as two lists; empty without list reuse or profiling."""
+        pass listed and the workgroup columns it ran (ceil(rows / rows per workgroup)), as two lists; empty without list reuse or profiling.
+        A lean pass (ICPMI_NN_LEAN, get_profile()["nn_lean_passes"]) has no coarse launch: its rows are the rows that wanted a
+        list, its columns 0."""
         fn = self._lib.icpmi_debug_nn_reuse
         fn.restype = C.c_int64
         fn.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_int64]

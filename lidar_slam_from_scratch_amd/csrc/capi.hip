@@ -262,6 +262,9 @@ struct icpmi_ctx {
     size_t h_file_cap = 0;
     int32_t *h_flags = nullptr;    // host-mapped ring: (iteration + 1) * 2 + done, written by the device
     int32_t *d_flags = nullptr;    // the same words through the device's address space
+    unsigned long long *h_want = nullptr; // host-mapped ring beside it: (iteration + 1) << 32 | rows the pass wanted listed
+    unsigned long long *d_want = nullptr; // (lean passes: list_reuse.h; written by k_sum_groups)
+    unsigned *h_stat = nullptr;    // pinned: list reuse's per-pass statistics on their way back (profiling)
 
     // profiling
     std::vector<EventPair> ev_pool;
@@ -601,6 +604,22 @@ bool nn_margin_enabled()
     return !(e && e[0] == '0');
 }
 
+// Lean passes (list_reuse.h, "lean passes").  ICPMI_NN_LEAN=0: every pass launches k_row_list and the coarse
+// kernel, the launches of the form before lean passes -- the reference leg of tests and A/B runs.  ICPMI_NN_LEAN_FROM=k
+// (k >= 2) is a TEST HOOK: every pass from the k-th on is lean whatever the counts say, which is the only way to put many
+// rows through a lean pass's exhaustive search.  Both are read at every call like ICPMI_NN_MARGIN.
+bool nn_lean_enabled()
+{
+    const char *e = getenv("ICPMI_NN_LEAN");
+    return !(e && e[0] == '0');
+}
+int nn_lean_from()
+{
+    const char *e = getenv("ICPMI_NN_LEAN_FROM");
+    const int k = e ? atoi(e) : 0;
+    return k >= 2 ? k : 0;
+}
+
 // The per-row arrays of the bounded pass inside ctx->nn_lists (n rows), then list reuse's word per 64 rows, its packed
 // list of rows (kRowListHead words in front) and its per-pass statistics
 struct NnListRows {
@@ -611,18 +630,18 @@ struct NnListRows {
     RowList *xb;
     unsigned long long *mask;
     int *list;
-    unsigned *stat_rows, *stat_blocks; // [kReuseStatPasses] each (profiling)
+    unsigned *stat_rows;               // [kReuseStatPasses] rows listed per pass (profiling)
     unsigned *stat_cert;               // [kReuseStatPasses] the match margin: rows certified per pass (profiling)
     RowScan *scan;                     // the match margin's per-row records, covers and word per 64 rows (RowBounds)
     double *cover;
     unsigned long long *cert;
 };
 constexpr size_t kNnListRowBytes = sizeof(double) + 2 * sizeof(float) + sizeof(int) + sizeof(unsigned) * kNnEntCap + sizeof(RowList);
-constexpr int kReuseStatPasses = 1024; // (passes beyond are added to the last entry)
+constexpr int kReuseStatPasses = 1024; // (passes beyond overwrite the last entry)
 size_t nn_list_bytes(int n)
 {
     return kNnListRowBytes * (size_t)n + 64 + sizeof(unsigned long long) * (((size_t)n + 63) / 64) +
-           sizeof(int) * ((size_t)n + kRowListHead) + sizeof(unsigned) * 3 * kReuseStatPasses + 64 +
+           sizeof(int) * ((size_t)n + kRowListHead) + sizeof(unsigned) * 2 * kReuseStatPasses + 64 +
            (sizeof(RowScan) + sizeof(double)) * (size_t)n + sizeof(unsigned long long) * (((size_t)n + 63) / 64);
 }
 NnListRows nn_list_rows(const icpmi_ctx *ctx, int n)
@@ -637,8 +656,7 @@ NnListRows nn_list_rows(const icpmi_ctx *ctx, int n)
     r.mask = (unsigned long long *)(r.xb + n); // (RowList is 32 bytes: 8-byte aligned)
     r.list = (int *)(r.mask + ((size_t)n + 63) / 64);
     r.stat_rows = (unsigned *)(r.list + (size_t)n + kRowListHead);
-    r.stat_blocks = r.stat_rows + kReuseStatPasses;
-    r.stat_cert = r.stat_blocks + kReuseStatPasses;
+    r.stat_cert = r.stat_rows + kReuseStatPasses;
     r.scan = (RowScan *)(((uintptr_t)(r.stat_cert + kReuseStatPasses) + 63) & ~(uintptr_t)63);
     r.cover = (double *)(r.scan + n);
     r.cert = (unsigned long long *)(r.cover + n);
@@ -686,7 +704,7 @@ size_t coarse_groups_lds(int splits) { return sizeof(unsigned) * (2 * (size_t)sp
 int launch_nn_mfma(icpmi_ctx *ctx, const double *d_qry, int n, int m, int *d_idx, double *d_d2,
                    const IcpState *st, const double *d_tgt = nullptr, const double *d_nrm = nullptr,
                    double *d_partials = nullptr, int pruned_pass = -1, bool bounded = false, bool reuse_list = false,
-                   int stat_pass = 0, bool margin = false)
+                   bool lean = false, bool margin = false)
 {
     const int splits = ctx->nn_splits;
     int rc;
@@ -701,7 +719,9 @@ int launch_nn_mfma(icpmi_ctx *ctx, const double *d_qry, int n, int m, int *d_idx
         unsigned *ent_row = lr.ent;
         float *ubf_row = lr.ubf, *sqf_row = lr.sqf;
         int *cnt_row = lr.cnt;
-        {
+        // (a lean pass of the all-pairs engine -- list_reuse.h, "lean passes" -- has no coarse launch: the rows' kept lists and
+        // certificates stand, and a row that wanted a new list takes the resolve's exhaustive search)
+        if (!lean) {
             StageTimer tc(ctx, ST_COARSE);
             const KnnLists kl{ubf_row, sqf_row, cnt_row, ent_row, kNnEntCap};
             if (pruned_pass >= 0) {
@@ -718,15 +738,13 @@ int launch_nn_mfma(icpmi_ctx *ctx, const double *d_qry, int n, int m, int *d_idx
             } else {
                 // list reuse (`reuse_list`): the pass runs over the packed list of the rows listed again (k_row_list) and no others
                 const int *list = reuse_list ? lr.list : nullptr;
-                unsigned *blocks_run = reuse_list && ctx->opt.profile ? lr.stat_blocks + std::min(stat_pass, kReuseStatPasses - 1) : nullptr;
                 if (coarse_half_units(ctx, n, splits)) {
                     constexpr int per = kCoarseQueries / kCoarseQT; // queries per workgroup with one tile per wave
                     hipLaunchKernelGGL((k_nn_coarse_bounded<1, kCoarseWaves>), dim3((n + per - 1) / per, splits), dim3(kCoarseThreads), 0,
-                                       ctx->stream, d_qry, n, (const uint4 *)ctx->bpack.p, frames, kl, st, list, blocks_run);
+                                       ctx->stream, d_qry, n, (const uint4 *)ctx->bpack.p, frames, kl, st, list);
                 } else
                     hipLaunchKernelGGL((k_nn_coarse_bounded<kCoarseQT, kCoarseWaves>), dim3((n + kCoarseQueries - 1) / kCoarseQueries, splits),
-                                       dim3(kCoarseThreads), 0, ctx->stream, d_qry, n, (const uint4 *)ctx->bpack.p, frames, kl, st, list,
-                                       blocks_run);
+                                       dim3(kCoarseThreads), 0, ctx->stream, d_qry, n, (const uint4 *)ctx->bpack.p, frames, kl, st, list);
             }
             ctx->prof.nn_coarse_blocks += (int64_t)((n + kCoarseQueries - 1) / kCoarseQueries) * splits;
         }
@@ -746,7 +764,7 @@ int launch_nn_mfma(icpmi_ctx *ctx, const double *d_qry, int n, int m, int *d_idx
                                (const unsigned long long *)nullptr, (const double *)nullptr, (RowScan *)nullptr);
 #undef ICPMI_BOUNDED_ARGS
         if (!reuse_list) ctx->prof.nn_pairs += (double)n * (double)m; // (a pass with list reuse: its workgroup columns that ran,
-                                                                      // counted on the device -- profiling only -- and added after the call)
+                                                                      // from the rows listed -- profiling only -- and added after the call)
         ctx->prof.bounded_launches += 1;
         HIP_TRY(ctx, hipGetLastError());
         return ICPMI_OK;
@@ -1342,15 +1360,26 @@ int align_device(icpmi_ctx *ctx, const double *d_src, int64_t n_src64, const dou
             rb.skin = kNnSkin;
             rb.loose = kNnLoose;
             if (margin) rb.scan = lr.scan, rb.cover = lr.cover, rb.cert = lr.cert;
-            if (ctx->opt.profile) HIP_TRY(ctx, hipMemsetAsync(lr.stat_rows, 0, sizeof(unsigned) * 3 * kReuseStatPasses, s));
+            if (ctx->opt.profile) HIP_TRY(ctx, hipMemsetAsync(lr.stat_rows, 0, sizeof(unsigned) * 2 * kReuseStatPasses, s));
         }
     }
-    // before each kernel that moves the rows for pass `next`: where it counts the rows listed again (profiling)
-    unsigned *cert_count = nullptr; // (the match margin's: k_row_list counts the rows certified for the coming pass)
+    // before each k_row_list for pass `next`: where it stores the rows listed and, with the match margin, the rows certified
+    // for the coming pass (profiling)
+    unsigned *rows_count = nullptr, *cert_count = nullptr;
     auto next_pass_stats = [&](int next) {
-        if (reuse) rb.rebuilt = ctx->opt.profile ? lr.stat_rows + std::min(next, kReuseStatPasses - 1) : nullptr;
+        if (reuse) rows_count = ctx->opt.profile ? lr.stat_rows + std::min(next, kReuseStatPasses - 1) : nullptr;
         if (margin) cert_count = ctx->opt.profile ? lr.stat_cert + std::min(next, kReuseStatPasses - 1) : nullptr;
     };
+    // Lean passes (list_reuse.h, "lean passes"): once the passes list no row, k_row_list and the coarse kernel
+    // are no longer launched.  Single-GPU, ungated loops with list reuse, the fused finish kernel and a k_sum_groups launch,
+    // whose extra workgroup tells the host how many rows each pass wanted listed (WantPublish, kernels.h); everywhere else
+    // the launches are those of the form before.  The host learns the counts in the loop below, two passes late, where it
+    // waits for the progress word anyway: the launches are a function of the data, not of timing.
+    const bool lean_on = reuse && !sharded_run && !gate && fuse_finish_enabled() && sum_tree && nn_lean_enabled();
+    const int lean_from = lean_on ? nn_lean_from() : 0;
+    std::vector<unsigned> want_known;  // [p - 1]: the rows pass p wanted listed, as far as the host has read them
+    std::vector<char> lean_passes;     // [p - 1]: pass p was queued lean
+    bool lean_cur = false, lean_nxt = false; // the pass being queued, and the one after it
 
     // current_source = source * R0^T + t0^T (icp.hpp:174-176)
     if (n > 0 && !small) { // (an empty shard of a sharded run launches nothing over its rows; the small-cloud kernel moves them itself)
@@ -1394,10 +1423,23 @@ int align_device(icpmi_ctx *ctx, const double *d_src, int64_t n_src64, const dou
         }
         const bool fuse_step = sharded && n > 0 && !final_pass;
         const bool fuse_finish = !sharded && n > 0 && !final_pass && !gate && fuse_finish_enabled();
+        if (lean_on) {
+            // this pass (P, from 1) is what the tail of the pass before decided; the pass after it is decided now, from the
+            // two latest counts the loop below has read: want(P - 3) and want(P - 2) (list_reuse.h)
+            const int P = pass_no + 1;
+            lean_cur = lean_nxt;
+            lean_nxt = false;
+            if (!final_pass) {
+                if (lean_from) lean_nxt = P + 1 >= lean_from;
+                else if (P >= 6 && (int)want_known.size() >= P - 2) lean_nxt = lean_pass(P + 1, want_known[P - 4], want_known[P - 3]);
+            }
+            lean_passes.push_back(lean_cur ? 1 : 0);
+            if (lean_cur) ctx->prof.nn_lean_passes += 1;
+        }
         if (n > 0 && fused) {
             if ((r2 = launch_nn_mfma(ctx, cur, n, m, idx, nullptr, st, d_tgt, nrm, partials,
                                      pruned ? pass_no : -1, bounded_loop /* incumbents in idx, bounds in place: from k_nn_prebound1 or the kernel that moved the rows */,
-                                     pass_list, pass_no, margin))) return r2;
+                                     pass_list, lean_cur, margin))) return r2;
             ++pass_no;
             if (!final_pass) next_pass_stats(pass_no);
             pass_list = reuse && !final_pass;
@@ -1416,9 +1458,17 @@ int align_device(icpmi_ctx *ctx, const double *d_src, int64_t n_src64, const dou
             else if (!fused)
                 hipLaunchKernelGGL(k_reduce, dim3(rblocks), dim3(256), 0, s, cur, n, d_tgt, m, nrm, idx, partials,
                                    st);
-            if (sum_tree)
+            if (sum_tree && lean_on) { // (+ the workgroup that counts the rows this pass wanted listed; pass_no - 1: this pass, from 0)
+                const int here = pass_no - 1, at = std::min(here, kReuseStatPasses - 1);
+                const bool stats = lean_cur && ctx->opt.profile;
+                const WantPublish wp{ctx->d_want + here % kFlagRing, (unsigned)(here + 1), n, here == 0, (const unsigned long long *)lr.mask,
+                                     margin ? (const unsigned long long *)lr.cert : nullptr, stats ? lr.stat_rows + at : nullptr,
+                                     stats && margin ? lr.stat_cert + at : nullptr};
+                hipLaunchKernelGGL(k_sum_groups, dim3((rblocks2 + 7) / 8 + 1), dim3(256), 0, s, (const double *)partials, rblocks,
+                                   partials + kSumsStride * (size_t)rblocks, (const IcpState *)st, wp);
+            } else if (sum_tree)
                 hipLaunchKernelGGL(k_sum_groups, dim3((rblocks2 + 7) / 8), dim3(256), 0, s, (const double *)partials, rblocks,
-                                   partials + kSumsStride * (size_t)rblocks, (const IcpState *)st);
+                                   partials + kSumsStride * (size_t)rblocks, (const IcpState *)st, WantPublish{});
             if (sharded) {
                 hipLaunchKernelGGL(k_finish, dim3(1), dim3(kFinishThreads), 0, s, fin_rows, fin_blocks, n,
                                    st);
@@ -1473,17 +1523,17 @@ int align_device(icpmi_ctx *ctx, const double *d_src, int64_t n_src64, const dou
                 hipLaunchKernelGGL(k_transform, dim3(std::min(2048, (n + 255) / 256)), dim3(256), 0, s,
                                    cur, cur, n, st, 0, 1, (const unsigned *)nullptr, rb);
         }
-        if (pass_list) // the rows just moved left their "listed again" words: the coming pass's list of rows
+        if (pass_list && !lean_nxt) // the rows just moved left their "listed again" words: the coming pass's list of rows
             hipLaunchKernelGGL(k_row_list, dim3(((n + 63) / 64 + kRowListThreads - 1) / kRowListThreads), dim3(kRowListThreads), 0, s,
                                (const unsigned long long *)lr.mask, n, lr.list, (const IcpState *)st,
-                               (const unsigned long long *)(margin ? lr.cert : nullptr), cert_count);
+                               (const unsigned long long *)(margin ? lr.cert : nullptr), cert_count, rows_count);
         return ICPMI_OK;
     };
 
     Range range_loop("icpmi:icp_loop");
     StageTimer *t_loop = new StageTimer(ctx, ST_LOOP);
     struct Closer2 { StageTimer *&p; ~Closer2() { delete p; p = nullptr; } } close_loop{t_loop};
-    for (int i = 0; i < kFlagRing; ++i) ctx->h_flags[i] = 0;
+    for (int i = 0; i < kFlagRing; ++i) ctx->h_flags[i] = 0, ctx->h_want[i] = 0ull;
     bool ended_early = false; // the host has SEEN the device leave the loop on a convergence test
     // `after_first` (may be null): called once the first iterations are queued and before the host first waits for
     // the device -- what it queues (on another stream) costs the host its launch time while the device is busy
@@ -1511,6 +1561,23 @@ int align_device(icpmi_ctx *ctx, const double *d_src, int64_t n_src64, const dou
             if (v & 1) { // loop already left on the device
                 ended_early = true;
                 break;
+            }
+            if (lean_on) {
+                // the rows that iteration's pass wanted listed: its k_sum_groups ran in front of the kernel whose progress word
+                // has just been read, so the word is there or on its way (the same bounded spin)
+                volatile unsigned long long *word = &ctx->h_want[slot];
+                unsigned long long w = *word;
+                for (long spin = 0; (int)(w >> 32) != want; ++spin) {
+                    if (spin > 2000000) {
+                        HIP_TRY(ctx, hipStreamSynchronize(s));
+                        w = *word;
+                        if ((int)(w >> 32) != want) return fail(ctx, ICPMI_ERR_HIP, "device row count word never arrived");
+                        break;
+                    }
+                    if ((spin & 63) == 63) sched_yield();
+                    w = *word;
+                }
+                want_known.push_back((unsigned)(w & 0xFFFFFFFFull));
             }
         }
         if ((rc = iteration(0, ctx->d_flags + it % kFlagRing, it + 1))) return rc;
@@ -1548,6 +1615,13 @@ int align_device(icpmi_ctx *ctx, const double *d_src, int64_t n_src64, const dou
         if (pruned) // (row group, split) pairs run / of all passes: cleared with the counters at the head of the next call
             HIP_TRY(ctx, hipMemcpyAsync(ctx->h_cnt + 3, group_stats(ctx), 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     }
+    // ... and so do list reuse's per-pass statistics (the arrays lie one behind the other: one copy into pinned memory,
+    // where a blocking copy after the wait cost the caller some 15 us)
+    const bool stats_back = reuse && ctx->opt.profile && pass_no > 0;
+    const int stat_passes = std::min(pass_no, kReuseStatPasses);
+    if (stats_back)
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->h_stat, lr.stat_rows, sizeof(unsigned) * ((size_t)(margin ? 1 : 0) * kReuseStatPasses + stat_passes),
+                                    hipMemcpyDeviceToHost, s));
     if (before_wait && ctx->opt.profile == 0) {
         // the results are waited for through an event; what before_wait queues behind it keeps the device busy
         // while the caller digests them (with profiling on, the stage timers want the whole stream drained)
@@ -1578,21 +1652,22 @@ int align_device(icpmi_ctx *ctx, const double *d_src, int64_t n_src64, const dou
     ctx->reuse_rows.clear();
     ctx->reuse_blocks.clear();
     ctx->margin_rows.clear();
-    if (reuse && ctx->opt.profile && pass_no > 0) {
+    if (stats_back) {
         // list reuse, per pass: the rows listed (the first pass lists all) and the workgroup columns of the coarse pass that
-        // ran, ceil(rows / rows per workgroup); their pairs are the pairs searched, and a pass none of which ran is a skipped
-        // coarse launch
-        const int np = std::min(pass_no, kReuseStatPasses);
-        // (the three arrays lie one behind the other: ONE blocking copy -- each costs the caller some 15 us)
-        std::vector<unsigned> stat((size_t)(margin ? 2 : 1) * kReuseStatPasses + np);
-        HIP_TRY(ctx, hipMemcpy(stat.data(), lr.stat_rows, sizeof(unsigned) * stat.size(), hipMemcpyDeviceToHost));
-        ctx->reuse_rows.assign(stat.begin(), stat.begin() + np);
-        ctx->reuse_blocks.assign(stat.begin() + kReuseStatPasses, stat.begin() + kReuseStatPasses + np);
+        // ran, ceil(rows / rows per workgroup) -- none in a lean pass, which has no coarse launch; their pairs are the pairs
+        // searched, and a pass none of which ran is a skipped coarse launch
+        const int np = stat_passes;
+        const unsigned *stat = ctx->h_stat;
         const int per = coarse_half_units(ctx, n, ctx->nn_splits) ? kCoarseQueries / kCoarseQT : kCoarseQueries;
+        ctx->reuse_rows.assign(stat, stat + np);
         ctx->reuse_rows[0] = (unsigned)n;
-        ctx->reuse_blocks[0] = (unsigned)((n + per - 1) / per);
+        ctx->reuse_blocks.resize((size_t)np);
+        for (int p = 0; p < np; ++p) {
+            const bool lean = p < (int)lean_passes.size() && lean_passes[p];
+            ctx->reuse_blocks[p] = lean ? 0u : (unsigned)(((long)ctx->reuse_rows[p] + per - 1) / per);
+        }
         if (margin) { // the match margin, per pass: the rows certified (the first pass certifies none)
-            ctx->margin_rows.assign(stat.begin() + 2 * kReuseStatPasses, stat.begin() + 2 * kReuseStatPasses + np);
+            ctx->margin_rows.assign(stat + kReuseStatPasses, stat + kReuseStatPasses + np);
             for (int p = 0; p < np; ++p) ctx->prof.nn_rows_certified += ctx->margin_rows[p];
         }
         for (int p = 0; p < np; ++p) {
@@ -1899,8 +1974,12 @@ int icpmi_create(const icpmi_options *opt, icpmi_ctx **out)
     if (hipHostMalloc((void **)&ctx->h_flags, sizeof(int32_t) * kFlagRing, hipHostMallocMapped) != hipSuccess) return bail("hipHostMalloc");
     if (hipHostMalloc((void **)&ctx->h_grid, 4 * sizeof(unsigned), hipHostMallocDefault) != hipSuccess) return bail("hipHostMalloc");
     if (hipHostMalloc((void **)&ctx->h_cnt, 8 * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess) return bail("hipHostMalloc");
+    if (hipHostMalloc((void **)&ctx->h_want, sizeof(unsigned long long) * kFlagRing, hipHostMallocMapped) != hipSuccess) return bail("hipHostMalloc");
+    if (hipHostMalloc((void **)&ctx->h_stat, sizeof(unsigned) * 2 * kReuseStatPasses, hipHostMallocDefault) != hipSuccess) return bail("hipHostMalloc");
     memset(ctx->h_flags, 0, sizeof(int32_t) * kFlagRing);
+    memset(ctx->h_want, 0, sizeof(unsigned long long) * kFlagRing);
     if (hipHostGetDevicePointer((void **)&ctx->d_flags, ctx->h_flags, 0) != hipSuccess) return bail("hipHostGetDevicePointer");
+    if (hipHostGetDevicePointer((void **)&ctx->d_want, ctx->h_want, 0) != hipSuccess) return bail("hipHostGetDevicePointer");
     *out = ctx;
     return ICPMI_OK;
 }
@@ -1972,6 +2051,8 @@ void icpmi_destroy(icpmi_ctx *ctx)
     if (ctx->h_hist) (void)hipHostFree(ctx->h_hist);
     if (ctx->h_file) (void)hipHostFree(ctx->h_file);
     if (ctx->h_flags) (void)hipHostFree(ctx->h_flags);
+    if (ctx->h_want) (void)hipHostFree(ctx->h_want);
+    if (ctx->h_stat) (void)hipHostFree(ctx->h_stat);
     for (EventPair &p : ctx->ev_pool) {
         (void)hipEventDestroy(p.a);
         (void)hipEventDestroy(p.b);

@@ -263,10 +263,44 @@ __device__ inline void finish_sums(const double *__restrict__ partials, int nblo
 // tolerance of the tests).
 constexpr int kSumGroup = 16;
 constexpr int kSumTreeFrom = 1024;
+// Lean passes (list_reuse.h, "lean passes"; `slot` null: none of this): k_sum_groups of pass p sits behind the mover of
+// pass p - 1 and in front of the mover of pass p, so ONE MORE workgroup of it can count the rows pass p wanted listed from
+// the words that mover left (RowBounds::mask) without racing their writer, and tell the host: (ticket << 32) | count in a
+// host-mapped word, one relaxed system-scope store like publish_progress -- the host reads this one word only.  `first`: a
+// call's first pass, whose words no mover has written yet, reports every row.  In a lean pass with profiling on
+// (`stat_rows` non-null) the same workgroup leaves the pass's statistics, which k_row_list leaves in a full one.
+struct WantPublish {
+    unsigned long long *slot;       // host-mapped
+    unsigned ticket;
+    int n, first;
+    const unsigned long long *mask; // [(n + 63) / 64]
+    const unsigned long long *cert; // the match margin's words (or null)
+    unsigned *stat_rows, *stat_cert;
+};
+__device__ __forceinline__ void publish_want(const WantPublish &wp)
+{
+    __shared__ unsigned part[2][4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = (wp.n + 63) / 64;
+    const bool certs = wp.stat_cert && wp.cert;
+    const unsigned want = wp.first ? 0u : wave_scan_incl((unsigned)row_list_count(wp.mask, tid, nw, 256));
+    const unsigned sure = certs && !wp.first ? wave_scan_incl((unsigned)row_list_count(wp.cert, tid, nw, 256)) : 0u;
+    if (lane == 63) part[0][wave] = want, part[1][wave] = sure;
+    __syncthreads();
+    if (tid == 0) {
+        const unsigned w = wp.first ? (unsigned)wp.n : (part[0][0] + part[0][1]) + (part[0][2] + part[0][3]);
+        __hip_atomic_store(wp.slot, ((unsigned long long)wp.ticket << 32) | w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (wp.stat_rows) *wp.stat_rows = w;
+        if (certs) *wp.stat_cert = (part[1][0] + part[1][1]) + (part[1][2] + part[1][3]);
+    }
+}
 __global__ __launch_bounds__(256) void k_sum_groups(const double *__restrict__ rows, int nblocks, double *__restrict__ rows2,
-                                                    const IcpState *__restrict__ st)
+                                                    const IcpState *__restrict__ st, const WantPublish wp = WantPublish{})
 {
     if (st && st->done) return;
+    if (wp.slot && blockIdx.x == gridDim.x - 1) { // (the workgroup behind those of the sums)
+        publish_want(wp);
+        return;
+    }
     const int e = threadIdx.x & 31, grp = blockIdx.x * 8 + (threadIdx.x >> 5);
     const int r0 = grp * kSumGroup;
     if (r0 >= nblocks || e >= kNumSums) return;
@@ -497,7 +531,6 @@ struct RowBounds {
     unsigned long long *mask; // [(n + 63) / 64] list reuse: bit b of word g = row 64 g + b is listed again by the coming pass
     double skin;       // the skin as a fraction of the row's sqrt(ub)
     double loose;      // a list built for more than `loose` x the radius it would be built for now is not kept (0: no limit)
-    unsigned *rebuilt; // profiling (or null): the coming pass's count of rows listed again
     // The match margin (null: off; on only with list reuse -- list_reuse.h, "the match margin"): the resolve leaves, per row
     // it scans, where it scanned it and how far every target but the winner is from there (g); a row whose kept match is
     // nearer than g less the row's drift since needs no search at all in the coming pass.  Such a row keeps ub, is left
@@ -563,7 +596,6 @@ struct RowBatch {
     __device__ __forceinline__ void finish(double *out, const RowBounds &rb, int i0, int stride, int n, const double *T) const
     {
         const Rigid34 P = Rigid34::load(T);
-        unsigned listed = 0; // profiling: rows of this wave listed again (counted by the wave's first active lane)
 #pragma unroll
         for (int b = 0; b < B; ++b) {
             const int i = i0 + b * stride;
@@ -621,7 +653,6 @@ struct RowBatch {
                     // bits clear): lane 0 holds the first of them and stores the group's word
                     const unsigned long long again = __ballot(!keep && !cert && ubf == ubf);
                     if ((i & 63) == 0) rb.mask[i >> 6] = again;
-                    if (rb.rebuilt) listed += (unsigned)__popcll(again);
                     if (rb.cert) {
                         const unsigned long long sure = __ballot(cert);
                         if ((i & 63) == 0) rb.cert[i >> 6] = sure;
@@ -629,7 +660,6 @@ struct RowBatch {
                 }
             }
         }
-        if (rb.rebuilt && listed && (int)(threadIdx.x & 63) == __ffsll((long long)__ballot(1)) - 1) atomicAdd(rb.rebuilt, listed);
     }
 };
 // Rows per thread and batch.  The fused kernels' grids give a thread ONE row up to 131,072 rows (k_transform: 524,288), so a
@@ -652,12 +682,14 @@ constexpr int kRowBatch = 2;
 // alternating; profiles/row_list/).
 constexpr int kRowListThreads = 256;
 constexpr int kRowListHead = 16; // (the rows start on a 64-byte line)
-// Profiling of the match margin (`cert_count` non-null): the first workgroup also counts the set bits of the rows' "certified"
-// words (RowBounds::cert) and stores their number -- a plain store, no atomics.
+// Profiling (`rows_count` non-null): the first workgroup stores the number of rows listed, and with the match margin
+// (`cert_count` non-null) it also counts the set bits of the rows' "certified" words (RowBounds::cert) and stores their
+// number -- plain stores, no atomics (a count per wave in the kernel that moves the rows was 1,563 atomics on one word).
 __global__ __launch_bounds__(kRowListThreads) void k_row_list(const unsigned long long *__restrict__ mask, int n, int *__restrict__ list,
                                                               const IcpState *__restrict__ st,
                                                               const unsigned long long *__restrict__ cert = nullptr,
-                                                              unsigned *__restrict__ cert_count = nullptr)
+                                                              unsigned *__restrict__ cert_count = nullptr,
+                                                              unsigned *__restrict__ rows_count = nullptr)
 {
     if (st->done) return; // (the rows were not moved and the coarse pass will not run)
     __shared__ int part[4][kRowListThreads / 64];
@@ -685,7 +717,10 @@ __global__ __launch_bounds__(kRowListThreads) void k_row_list(const unsigned lon
         at += part[0][v] + (v < wave ? part[2][v] : 0);
         total += part[0][v] + part[1][v] + part[2][v];
     }
-    if (blockIdx.x == 0 && tid == 0) list[0] = total, list[1] = total == n;
+    if (blockIdx.x == 0 && tid == 0) {
+        list[0] = total, list[1] = total == n;
+        if (rows_count) *rows_count = (unsigned)total;
+    }
     if (total == n) return;
     row_list_expand(w, g, list + kRowListHead, at + (int)incl - mine);
 }

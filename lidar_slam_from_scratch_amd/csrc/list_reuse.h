@@ -97,4 +97,28 @@ ICPMI_HD inline int row_list_expand(const unsigned long long w, const int g, int
     return c;
 }
 
+// ---- lean passes (the loop of icpmi_align in capi.hip; k_sum_groups in kernels.h) ------------------------
+// want(p): the rows whose bit the mover of pass p - 1 left set in RowBounds::mask, the rows pass p lists.  A LEAN pass
+// launches neither k_row_list nor the coarse kernel: a row that wanted a list then has cnt == 0 and takes the resolve's
+// exhaustive search, exact with ties (nn_bounded.h, `over`) -- slower for that row, never another bit.  The host decides
+// pass p when it queues the tail of pass p - 1; it has then seen the progress word of pass p - 3, so want(p - 4) and
+// want(p - 3), published by kernels that completed, are the two latest counts it knows.  Pass p is lean when both are 0
+// and neither is a call's first or second pass (those list every row whatever the words say).  Passes are numbered from 1.
+ICPMI_HD inline bool lean_pass(const int pass, const unsigned want_older, const unsigned want_newer)
+{
+    return pass - 4 >= 3 && want_older == 0u && want_newer == 0u;
+}
+
+// lean[p - 1] for the passes p = 1 ... passes of a call whose counts are want[p - 1] = want(p): the rule applied the way
+// the host loop applies it, each pass decided from the two counts known by then.  Returns the number of lean passes.
+ICPMI_HD inline int lean_schedule(const unsigned *want, const int passes, bool *lean)
+{
+    int c = 0;
+    for (int p = 1; p <= passes; ++p) {
+        lean[p - 1] = p >= 5 && lean_pass(p, want[p - 5], want[p - 4]);
+        c += lean[p - 1] ? 1 : 0;
+    }
+    return c;
+}
+
 } // namespace icpmi

@@ -860,18 +860,18 @@ __global__ __launch_bounds__(64 * WAVES) void k_nn_coarse_rows(
 // normal estimation): the packed list of the rows listed again, as k_row_list left it.  The grid is sized for n rows, since
 // the host never learns the count: workgroup bx takes the list's positions from bx x (its rows) on and leaves at once
 // where the list ends before them.  Where the list says that it holds every row, the rows are indexed directly, as
-// without one.  `blocks_run` (profiling, or null): the workgroup columns that did run, counted by their split-0 workgroup.
+// without one.  (The workgroup columns that run are ceil(rows listed / rows per workgroup): the host works them out from
+// the count k_row_list leaves with profiling on, nothing is counted here.)
 template <int QT, int WAVES>
 __global__ __launch_bounds__(64 * WAVES) void k_nn_coarse_bounded(
     const double *__restrict__ qry, int n, const uint4 *__restrict__ Bpack,
     const SplitFrame *__restrict__ frames, KnnLists kl, const IcpState *__restrict__ st,
-    const int *__restrict__ list = nullptr, unsigned *__restrict__ blocks_run = nullptr)
+    const int *__restrict__ list = nullptr)
 {
     if (st && st->done) return;
     RowsListed map{nullptr, n};
     if (list && !list[1]) map = RowsListed{list + kRowListHead, list[0]};
     if (blockIdx.x * (kTile * QT * WAVES) >= map.count) return;
-    if (blocks_run && blockIdx.y == 0 && threadIdx.x == 0) atomicAdd(blocks_run, 1u);
     __shared__ uint4 lds[CoarseLds<WAVES>::SCRATCH16];
     coarse_unit<2, QT, WAVES, false, RowsListed>(lds, blockIdx.x, blockIdx.y, gridDim.y, qry, n, 0, Bpack, frames, nullptr, nullptr, kl, map);
 }
