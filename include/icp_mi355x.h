@@ -566,6 +566,39 @@ int icpmi_pose_graph_poses(icpmi_pose_graph *graph, double *poses, int64_t cap, 
 int icpmi_pose_graph_size(const icpmi_pose_graph *graph, int64_t *num_poses, int64_t *num_loop_closures,
                           icpmi_pose_graph_info *last);
 
+/* A robust loss on the loop-closure edges: GTSAM 4.1+ noiseModel::Robust over the loop factors' diagonal model,
+ * restated from the source as published (the reference itself uses the plain Gaussian model, pose_graph.cpp:118-141, and
+ * cannot refuse a false closure).  Off by default; with the loss off every call does what it did, bit for bit.
+ * The setting is the graph's, not a factor's: it applies to every factor added by add_loop_closure, past and future, at
+ * the next optimize().  Priors and odometry factors are never touched.  Per loop factor rw = r / sigma and
+ * d = sqrt(sum rw_a^2), `scale` k in whitened units (sigmas):
+ *     ICPMI_PG_LOSS_HUBER (1)          w = d <= k ? 1 : k / d              rho = d <= k ? 0.5 d^2 : k (d - 0.5 k)
+ *     ICPMI_PG_LOSS_CAUCHY (2)         s = k k,  w = s / (s + d^2)         rho = 0.5 s log1p(d^2 / s)
+ *     ICPMI_PG_LOSS_GEMAN_MCCLURE (3)  s = k k,  q = s / (s + d^2), w = q q   rho = 0.5 s d^2 / (s + d^2)
+ * No form divides by d except Huber's outer branch, where d > k > 0.
+ * Linearisation (Robust::WhitenSystem): A_i, A_j and rw of a loop factor are multiplied by sqrt(w) (q itself for
+ * Geman-McClure, sqrt() for the other two); H, g and the linearised error are formed from the scaled values.
+ * Error (NoiseModelFactor::error -> Robust::loss): a loop factor contributes rho(d), every other factor 0.5 d^2, for the
+ * initial error, every trial's candidate error, the history and final_error.  The LM policy is untouched, and
+ * optimize() still starts from the initial estimates: a redescending loss (Cauchy, Geman-McClure) whose scale is below
+ * the drift, measured in sigmas, rejects true closures too. */
+#define ICPMI_PG_LOSS_NONE 0
+#define ICPMI_PG_LOSS_HUBER 1
+#define ICPMI_PG_LOSS_CAUCHY 2
+#define ICPMI_PG_LOSS_GEMAN_MCCLURE 3
+/* A kind outside 0..3, or with a kind other than NONE a scale that is not finite or not > 0, is ICPMI_ERR_ARG with
+ * nothing changed.  NONE ignores the scale.  A call that changes the setting clears the optimised state, as adding a
+ * factor does; one that repeats it changes nothing. */
+int icpmi_pose_graph_set_loop_loss(icpmi_pose_graph *graph, int32_t kind, double scale);
+int icpmi_pose_graph_loop_loss(const icpmi_pose_graph *graph, int32_t *kind, double *scale);   /* either may be NULL */
+/* Weight w and whitened distance d of every loop closure at the optimised values, in add_loop_closure order: which
+ * closures the loss refused.  *n_out receives the number of loop closures; weights and distances may each be NULL;
+ * cap < *n_out with a non-NULL array is ICPMI_ERR_CAPACITY.  Only valid while the optimised state of the last
+ * optimize() holds, otherwise ICPMI_ERR_ARG.  With the loss off the weights are 1.0 and the distances each closure's
+ * residual in sigmas.  One launch and one wait. */
+int icpmi_pose_graph_loop_weights(icpmi_pose_graph *graph, double *weights, double *distances, int64_t cap,
+                                  int64_t *n_out);
+
 /* Global map: the node's kept filtered scans and what it builds from them with the optimised poses
  * (slam_viz/src/ros/slam_node.cpp):
  *     downsampled_clouds_.push_back(curr)                      :71, :123      icpmi_map_add_frame*

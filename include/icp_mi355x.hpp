@@ -1029,6 +1029,25 @@ public:
         }
         return out;
     }
+    // A robust loss on the loop-closure edges (icpmi_pose_graph_set_loop_loss): kind ICPMI_PG_LOSS_*, scale in sigmas.
+    // Not in the reference; off by default.
+    void setLoopLoss(int kind, double scale = 0.0) { check(icpmi_pose_graph_set_loop_loss(g_, kind, scale)); }
+    std::pair<int, double> loopLoss() const
+    {
+        int32_t kind = 0;
+        double scale = 0.0;
+        check(icpmi_pose_graph_loop_loss(g_, &kind, &scale));
+        return {static_cast<int>(kind), scale};
+    }
+    // (weights, distances) of the loop closures at the optimised values, in addLoopClosure order; throws unless the
+    // optimised state of the last optimize() holds
+    std::pair<std::vector<double>, std::vector<double>> loopWeights() const
+    {
+        int64_t n = counts().second;
+        std::vector<double> w(static_cast<std::size_t>(n)), d(static_cast<std::size_t>(n));
+        check(icpmi_pose_graph_loop_weights(g_, w.data(), d.data(), n, &n));
+        return {w, d};
+    }
     std::size_t size() const { return static_cast<std::size_t>(counts().first); }
     std::size_t loopClosureCount() const { return static_cast<std::size_t>(counts().second); }
     double getFinalError() const { return last().final_error; }

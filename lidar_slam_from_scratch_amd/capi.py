@@ -48,6 +48,7 @@ EXPORTS = [
     "icpmi_local_map_add", "icpmi_local_map_add_device", "icpmi_local_map_add_stream_frame", "icpmi_local_map_size",
     "icpmi_local_map_points", "icpmi_local_map_register", "icpmi_local_map_register_device",
     "icpmi_local_map_register_robust", "icpmi_local_map_register_robust_device",
+    "icpmi_pose_graph_set_loop_loss", "icpmi_pose_graph_loop_loss", "icpmi_pose_graph_loop_weights",
 ]
 
 
@@ -227,6 +228,8 @@ class PoseGraphInfo(C.Structure):
 
 PG_STOP_NONE, PG_STOP_ZERO_ERROR, PG_STOP_MAX_ITERATIONS, PG_STOP_RELATIVE, PG_STOP_ABSOLUTE, PG_STOP_LAMBDA_BOUND, \
     PG_STOP_SMALL_COST_CHANGE, PG_STOP_NOT_FINITE = range(8)
+# a robust loss on the pose graph's loop-closure edges (ICPMI_PG_LOSS_*)
+PG_LOSS_NONE, PG_LOSS_HUBER, PG_LOSS_CAUCHY, PG_LOSS_GEMAN_MCCLURE = range(4)
 
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int32)
@@ -379,6 +382,9 @@ def load_library(path=None):
     L.icpmi_pose_graph_pose.argtypes = [pg, C.c_int64, dp]
     L.icpmi_pose_graph_poses.argtypes = [pg, dp, C.c_int64, i64p, i64p]
     L.icpmi_pose_graph_size.argtypes = [pg, i64p, i64p, C.POINTER(PoseGraphInfo)]
+    L.icpmi_pose_graph_set_loop_loss.argtypes = [pg, C.c_int32, C.c_double]
+    L.icpmi_pose_graph_loop_loss.argtypes = [pg, C.POINTER(C.c_int32), C.POINTER(C.c_double)]
+    L.icpmi_pose_graph_loop_weights.argtypes = [pg, dp, dp, C.c_int64, i64p]
     L.icpmi_map_create.argtypes = [vp, C.POINTER(vp)]
     L.icpmi_map_destroy.argtypes = [vp]
     L.icpmi_map_destroy.restype = None

@@ -50,6 +50,7 @@
 #include "ground.h"
 #include "loop_store.h"
 #include "pose_graph.h"
+#include "pose_graph_loss.h"
 #include "local_map.h"
 
 using namespace icpmi;
@@ -3589,11 +3590,16 @@ struct icpmi_pose_graph {
     std::vector<double> opt;             // optimised values, 12 per pose index (valid where has_init, while optimized)
     int64_t num_poses = 0, num_loops = 0;
     bool optimized = false;
+    int32_t loss_kind = ICPMI_PG_LOSS_NONE;   // on the loop-closure factors (pose_graph_loss.h)
+    double loss_scale = 0.0;
+    bool values_on_device = false;       // d_X, d_fac, d_map and d_rank are those of the last optimize()
+    int opt_factors = 0;                 // factors and loop factors of that optimize()
+    int64_t opt_loops = 0;
     size_t uploaded_factors = 0;         // factors already in d_fac
     int64_t init_dirty_lo = INT64_MAX, init_dirty_hi = 0;   // pose range of estimates not yet in d_init
     DevBuf d_fac, d_init, d_map, d_keys, d_X, d_Xc, d_A, d_rw, d_err, d_H, d_g, d_D, d_gn, d_Cn, d_L, d_U, d_Y,
         d_schur, d_S, d_xb, d_delta, d_errc, d_errl, d_out, d_status, d_inc_ptr, d_inc, d_cn_ptr, d_cn, d_segs,
-        d_blocks, d_codes, d_sep_node, d_sep_segs, d_sep_pos, d_node_seg;
+        d_blocks, d_codes, d_sep_node, d_sep_segs, d_sep_pos, d_node_seg, d_rank, d_wd;
     double *h_out = nullptr;             // pinned: the two sums and the status of a trial
     icpmi_pose_graph_info last{};        // of the last optimize()
 };
@@ -3650,7 +3656,7 @@ void pg_factor(PgFactor &f, int kind, int64_t i, int64_t j, const double *T, dou
     f.kind = kind;
     f.i = (int32_t)i;
     f.j = (int32_t)j;
-    f.reserved = 0;
+    f.reserved = 0;                       // 1: a loop closure (pose_graph_loss.h)
     pg_to12(T, f.Z);
     for (int a = 0; a < 3; ++a) {
         f.inv_sigma[a] = 1.0 / rs;        // noiseModel::Diagonal::Sigmas keeps 1/sigma and whitens by multiplying
@@ -3670,7 +3676,8 @@ unsigned pg_grid(size_t n, unsigned b) { return (unsigned)((n + b - 1) / b); }
 
 // The graph's structure for the device solve (rebuilt by every optimize(): O(poses + factors) on the host).
 struct PgPlan {
-    int n = 0, F = 0, nb = 0, nseg = 0, nblocks = 0;
+    int n = 0, F = 0, nb = 0, nseg = 0, nblocks = 0, nloops = 0;
+    bool loss = false;                   // the loss is on and the graph has a loop factor: the kernels of pose_graph_loss.h
     std::vector<int32_t> keys, map;
 };
 
@@ -3788,6 +3795,10 @@ int pg_plan(icpmi_pose_graph *g, PgPlan &P)
             per[bidx].push_back(((pi > pj ? 3 : 2) << 28) | f);
         }
     }
+    std::vector<int32_t> rank(F, -1);                      // loop factors in add_loop_closure order
+    for (int f = 0; f < F; ++f)
+        if (g->factors[f].reserved == 1) rank[f] = P.nloops++;
+    P.loss = g->loss_kind != ICPMI_PG_LOSS_NONE && P.nloops > 0;
     std::vector<int32_t> codes;
     for (size_t b = 0; b < blocks.size(); ++b) {
         blocks[b].begin = (int32_t)codes.size();
@@ -3805,7 +3816,7 @@ int pg_plan(icpmi_pose_graph *g, PgPlan &P)
         (rc = pg_upload(ctx, g->d_segs, segs)) || (rc = pg_upload(ctx, g->d_blocks, blocks)) ||
         (rc = pg_upload(ctx, g->d_codes, codes)) || (rc = pg_upload(ctx, g->d_sep_node, sep_node)) ||
         (rc = pg_upload(ctx, g->d_sep_segs, sep_segs)) || (rc = pg_upload(ctx, g->d_sep_pos, sep_pos)) ||
-        (rc = pg_upload(ctx, g->d_node_seg, node_seg)))
+        (rc = pg_upload(ctx, g->d_node_seg, node_seg)) || (rc = pg_upload(ctx, g->d_rank, rank)))
         return rc;
     const size_t F1 = std::max(F, 1), n1 = std::max(n, 1), nr = 6 * (size_t)std::max(nb, 1);
     struct { DevBuf *b; size_t bytes; } need[] = {
@@ -3813,7 +3824,7 @@ int pg_plan(icpmi_pose_graph *g, PgPlan &P)
         {&g->d_H, 864 * F1}, {&g->d_g, 96 * F1}, {&g->d_D, 288 * n1}, {&g->d_gn, 48 * n1}, {&g->d_Cn, 288 * n1},
         {&g->d_L, 288 * n1}, {&g->d_U, 288 * n1}, {&g->d_Y, 624 * n1}, {&g->d_schur, 1248 * (size_t)std::max(P.nseg, 1)},
         {&g->d_S, 8 * nr * nr}, {&g->d_xb, 8 * nr}, {&g->d_delta, 48 * n1}, {&g->d_errc, 8 * F1}, {&g->d_errl, 8 * F1},
-        {&g->d_out, 64}, {&g->d_status, 64}};
+        {&g->d_out, 64}, {&g->d_status, 64}, {&g->d_wd, 16 * (size_t)std::max(P.nloops, 1)}};
     for (auto &q : need)
         if ((rc = reserve(ctx, *q.b, q.bytes))) return rc;
     return ICPMI_OK;
@@ -3873,16 +3884,37 @@ int pg_trial(icpmi_pose_graph *g, const PgPlan &P, const PgLin &lin, double lam,
                        (const double *)g->d_xb.p, n, (double *)g->d_delta.p);
     hipLaunchKernelGGL(k_pg_retract, dim3(pg_grid(n, 128)), dim3(128), 0, s, (const double *)g->d_X.p,
                        (const double *)g->d_delta.p, n, (double *)g->d_Xc.p);
-    hipLaunchKernelGGL(k_pg_trial, dim3(pg_grid(F, 128)), dim3(128), 0, s, (const PgFactor *)g->d_fac.p,
-                       (const int32_t *)g->d_map.p, F, (const double *)g->d_Xc.p, lin, (const double *)g->d_delta.p,
-                       (double *)g->d_errc.p, (double *)g->d_errl.p);
+    if (P.loss)
+        hipLaunchKernelGGL(k_pg_trial_loss, dim3(pg_grid(F, 128)), dim3(128), 0, s, (const PgFactor *)g->d_fac.p,
+                           (const int32_t *)g->d_map.p, F, (const double *)g->d_Xc.p, lin, (const double *)g->d_delta.p,
+                           (int)g->loss_kind, g->loss_scale, (double *)g->d_errc.p, (double *)g->d_errl.p);
+    else
+        hipLaunchKernelGGL(k_pg_trial, dim3(pg_grid(F, 128)), dim3(128), 0, s, (const PgFactor *)g->d_fac.p,
+                           (const int32_t *)g->d_map.p, F, (const double *)g->d_Xc.p, lin, (const double *)g->d_delta.p,
+                           (double *)g->d_errc.p, (double *)g->d_errl.p);
     return pg_sums(g, (const double *)g->d_errc.p, (const double *)g->d_errl.p, F, out);
 }
 
-int pg_linearize(icpmi_pose_graph *g, const PgPlan &P, const PgLin &lin, double *error)
+// error: the sum of lin.err, read back when asked for.  lin0: the linearised error at a zero step; without a loss it is
+// the error itself and costs nothing, under a loss it is a sum of its own (per factor in d_errl, which the next trial
+// overwrites) and always read back.
+int pg_linearize(icpmi_pose_graph *g, const PgPlan &P, const PgLin &lin, double *error, double *lin0)
 {
     icpmi_ctx *ctx = g->ctx;
     hipStream_t s = ctx->stream;
+    if (P.loss) {
+        hipLaunchKernelGGL(k_pg_linearize_loss, dim3(pg_grid(P.F, 128)), dim3(128), 0, s, (const PgFactor *)g->d_fac.p,
+                           (const int32_t *)g->d_map.p, P.F, (const double *)g->d_X.p, lin, (int)g->loss_kind,
+                           g->loss_scale, (double *)g->d_errl.p);
+        hipLaunchKernelGGL(k_pg_assemble, dim3(pg_grid(78 * (size_t)P.n, 256)), dim3(256), 0, s, lin,
+                           (const int32_t *)g->d_inc_ptr.p, (const int32_t *)g->d_inc.p, (const int32_t *)g->d_cn_ptr.p,
+                           (const int32_t *)g->d_cn.p, P.n, (double *)g->d_D.p, (double *)g->d_gn.p, (double *)g->d_Cn.p);
+        double out[3];
+        int rc = pg_sums(g, lin.err, (const double *)g->d_errl.p, P.F, out);
+        if (error) *error = out[0];
+        *lin0 = out[1];
+        return rc;
+    }
     hipLaunchKernelGGL(k_pg_linearize, dim3(pg_grid(P.F, 128)), dim3(128), 0, s, (const PgFactor *)g->d_fac.p,
                        (const int32_t *)g->d_map.p, P.F, (const double *)g->d_X.p, lin);
     hipLaunchKernelGGL(k_pg_assemble, dim3(pg_grid(78 * (size_t)P.n, 256)), dim3(256), 0, s, lin,
@@ -3949,7 +3981,7 @@ void icpmi_pose_graph_destroy(icpmi_pose_graph *g)
                       &g->d_H, &g->d_g, &g->d_D, &g->d_gn, &g->d_Cn, &g->d_L, &g->d_U, &g->d_Y, &g->d_schur, &g->d_S,
                       &g->d_xb, &g->d_delta, &g->d_errc, &g->d_errl, &g->d_out, &g->d_status, &g->d_inc_ptr, &g->d_inc,
                       &g->d_cn_ptr, &g->d_cn, &g->d_segs, &g->d_blocks, &g->d_codes, &g->d_sep_node, &g->d_sep_segs,
-                      &g->d_sep_pos, &g->d_node_seg};
+                      &g->d_sep_pos, &g->d_node_seg, &g->d_rank, &g->d_wd};
     for (DevBuf *b : bufs) release(*b);
     if (g->h_out) (void)hipHostFree(g->h_out);
     delete g;
@@ -4004,6 +4036,7 @@ int icpmi_pose_graph_add_loop_closure(icpmi_pose_graph *g, int64_t from, int64_t
         return fail(g->ctx, ICPMI_ERR_ARG, "bad loop closure");
     PgFactor f;
     pg_factor(f, 1, from, to, rel, g->cfg.loop_rotation_sigma, g->cfg.loop_translation_sigma);
+    f.reserved = 1;
     g->factors.push_back(f);                       // pose_graph.cpp:132-134
     g->num_loops++;                                // :136
     g->optimized = false;                          // :137
@@ -4041,6 +4074,7 @@ int icpmi_pose_graph_optimize(icpmi_pose_graph *g, icpmi_pose_graph_info *info, 
             return fail(ctx, ICPMI_ERR_ARG, "a factor names pose %lld, which has no estimate",
                         (long long)(pg_has(g, f.i) ? f.j : f.i));   // the reference's catch (:166-169)
     hipStream_t s = ctx->stream;
+    g->values_on_device = false;
     // only what was added since the last call goes up: the new factors and the new estimates
     const size_t F = g->factors.size();
     if ((rc = pg_reserve_keep(ctx, g->d_fac, sizeof(PgFactor) * g->uploaded_factors, sizeof(PgFactor) * F))) return rc;
@@ -4068,8 +4102,8 @@ int icpmi_pose_graph_optimize(icpmi_pose_graph *g, icpmi_pose_graph_info *info, 
     double lam = 1e-5;                                    // lambdaInitial
     const double lam_factor = 10.0, lam_lower = 0.0, lam_upper = 1e5, min_fidelity = 1e-3;
     const double rel_tol = c.relative_error_tol, abs_tol = c.absolute_error_tol, err_tol = 0.0;   // errorTol 0
-    double error;
-    if ((rc = pg_linearize(g, P, lin, &error))) return rc;
+    double error, lin0 = 0.0;
+    if ((rc = pg_linearize(g, P, lin, &error, &lin0))) return rc;
     st.initial_error = error;
     int nh = 0;
     if (history) history[nh] = error;
@@ -4081,8 +4115,9 @@ int icpmi_pose_graph_optimize(icpmi_pose_graph *g, icpmi_pose_graph_info *info, 
     while (st.stop_reason == ICPMI_PG_STOP_NONE) {
         const double current = error;
         // LevenbergMarquardtOptimizer::iterate: linearise once, then tryLambda until it returns true
-        if (!linearized && (rc = pg_linearize(g, P, lin, nullptr))) return rc;
-        const double old_lin = current;                   // linear.error(VectorValues::Zero) = 0.5 sum ||rw||^2
+        if (!linearized && (rc = pg_linearize(g, P, lin, nullptr, &lin0))) return rc;
+        // linear.error(VectorValues::Zero) = 0.5 sum ||rw||^2: the error itself, except under a loss (rho against w d^2)
+        const double old_lin = P.loss ? lin0 : current;
         bool stepped = false;
         int inner_stop = ICPMI_PG_STOP_NONE;
         double new_err = 0.0;
@@ -4147,12 +4182,67 @@ int icpmi_pose_graph_optimize(icpmi_pose_graph *g, icpmi_pose_graph_info *info, 
     g->opt.assign(12 * (size_t)g->num_poses, 0.0);
     for (int k = 0; k < P.n; ++k) std::copy(X.begin() + 12 * k, X.begin() + 12 * (k + 1), g->opt.begin() + 12 * (size_t)P.keys[k]);
     g->optimized = true;                                  // pose_graph.cpp:160-162
+    g->values_on_device = true;
+    g->opt_factors = P.F;
+    g->opt_loops = P.nloops;
     st.optimized = 1;
     st.final_error = error;
     st.final_lambda = lam;
     st.history_len = nh;
     g->last = st;
     if (info) *info = st;
+    return ICPMI_OK;
+}
+
+int icpmi_pose_graph_set_loop_loss(icpmi_pose_graph *g, int32_t kind, double scale)
+{
+    if (!g) return ICPMI_ERR_NULL;
+    if (kind < ICPMI_PG_LOSS_NONE || kind > ICPMI_PG_LOSS_GEMAN_MCCLURE)
+        return fail(g->ctx, ICPMI_ERR_ARG, "loss kind %d is not one of ICPMI_PG_LOSS_*", (int)kind);
+    if (kind == ICPMI_PG_LOSS_NONE) scale = 0.0;
+    else if (!std::isfinite(scale) || !(scale > 0.0))
+        return fail(g->ctx, ICPMI_ERR_ARG, "the loss scale must be finite and positive");
+    if (kind == g->loss_kind && scale == g->loss_scale) return ICPMI_OK;
+    g->loss_kind = kind;
+    g->loss_scale = scale;
+    g->optimized = false;                          // as adding a factor does
+    return ICPMI_OK;
+}
+
+int icpmi_pose_graph_loop_loss(const icpmi_pose_graph *g, int32_t *kind, double *scale)
+{
+    if (!g) return ICPMI_ERR_NULL;
+    if (kind) *kind = g->loss_kind;
+    if (scale) *scale = g->loss_scale;
+    return ICPMI_OK;
+}
+
+int icpmi_pose_graph_loop_weights(icpmi_pose_graph *g, double *weights, double *distances, int64_t cap, int64_t *n_out)
+{
+    if (!g) return ICPMI_ERR_NULL;
+    icpmi_ctx *ctx = g->ctx;
+    int rc;
+    if ((rc = check_common(ctx))) return rc;
+    if (n_out) *n_out = g->num_loops;
+    if (!g->optimized || !g->values_on_device || g->opt_loops != g->num_loops)
+        return fail(ctx, ICPMI_ERR_ARG, "loop weights need the optimised state of the last optimize()");
+    if (!weights && !distances) return ICPMI_OK;
+    const int64_t nl = g->num_loops;
+    if (cap < nl) return fail(ctx, ICPMI_ERR_CAPACITY, "%lld loop closures need room", (long long)nl);
+    if (nl == 0) return ICPMI_OK;
+    hipStream_t s = ctx->stream;
+    const int F = g->opt_factors;
+    hipLaunchKernelGGL(k_pg_loop_weights, dim3(pg_grid(F, 128)), dim3(128), 0, s, (const PgFactor *)g->d_fac.p,
+                       (const int32_t *)g->d_map.p, (const int32_t *)g->d_rank.p, F, (const double *)g->d_X.p,
+                       (int)g->loss_kind, g->loss_scale, (double *)g->d_wd.p);
+    std::vector<double> wd(2 * (size_t)nl);
+    HIP_TRY(ctx, hipMemcpyAsync(wd.data(), g->d_wd.p, sizeof(double) * wd.size(), hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    HIP_TRY(ctx, hipGetLastError());
+    for (int64_t k = 0; k < nl; ++k) {
+        if (weights) weights[k] = wd[2 * k];
+        if (distances) distances[k] = wd[2 * k + 1];
+    }
     return ICPMI_OK;
 }
 

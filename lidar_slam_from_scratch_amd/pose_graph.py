@@ -87,6 +87,28 @@ class PoseGraph:
         T = _T(relative_transform)
         self.ctx._check(self._lib.icpmi_pose_graph_add_loop_closure(self._h, int(from_idx), int(to_idx), capi._dp(T)))
 
+    def set_loop_loss(self, kind, scale=0.0):
+        """A robust loss on the loop-closure edges (icpmi_pose_graph_set_loop_loss; not in the reference): kind one of
+        capi.PG_LOSS_*, scale in sigmas.  The graph's setting: every loop closure, past and future, at the next
+        optimize().  A change clears the optimised state."""
+        self.ctx._check(self._lib.icpmi_pose_graph_set_loop_loss(self._h, int(kind), float(scale)))
+
+    def loop_loss(self):
+        kind, scale = C.c_int32(0), C.c_double(0.0)
+        self.ctx._check(self._lib.icpmi_pose_graph_loop_loss(self._h, C.byref(kind), C.byref(scale)))
+        return kind.value, scale.value
+
+    def loop_weights(self):
+        """-> (weights, distances) of the loop closures at the optimised values, in add_loop_closure order; raises
+        unless the optimised state of the last optimize() holds.  With the loss off the weights are 1."""
+        n = C.c_int64(0)
+        self.ctx._check(self._lib.icpmi_pose_graph_loop_weights(self._h, None, None, 0, C.byref(n)))
+        w, d = np.zeros(n.value), np.zeros(n.value)
+        if n.value:
+            self.ctx._check(self._lib.icpmi_pose_graph_loop_weights(self._h, capi._dp(w), capi._dp(d), n.value,
+                                                                    C.byref(n)))
+        return w, d
+
     def optimize(self):
         """pose_graph.cpp:147-171: False on an empty graph or where a factor names a pose with no estimate"""
         info = capi.PoseGraphInfo()

@@ -37,6 +37,8 @@ class SlamRun:
         self.counts = None            # ... and, with counts=True, the per-cell hit and miss counts
         self.live = None              # ... and, with live=True, the counts kept up to date frame by frame
         self.live_log = []            # ... with (frames_cast, rebuilt) per live_update, in call order
+        self.loop_weights = None      # with loop_edge_loss: each closure's weight after the final optimize, if it succeeded
+        self.loop_distances = None    # ... and its whitened distance (sigmas)
 
 
 def node_loop_config():
@@ -47,7 +49,7 @@ def node_loop_config():
 def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, pose_graph_config=None,
              align=None, loop_backend=None, pose_graph=None, global_map=None, grid=None, map_voxel=1.0,
              loop_on_device=False, raycast=False, counts=False, live=False, loop_yaw_guess=False, loop_gate=None,
-             ground=None, odom_robust=None, loop_robust=None, odom_local_map=None):
+             ground=None, odom_robust=None, loop_robust=None, odom_local_map=None, loop_edge_loss=None):
     """frames: sequence of N x 3 fp64 clouds (already downsampled).  Returns a SlamRun.  global_map: an object with
     add_frame, recent_clouds and finish (None: no map is built); grid: its occupancy grid config (None: defaults).
     loop_on_device: the detector is loop_closure.StoreLoopClosureDetector over global_map (a global_map.GlobalMap),
@@ -73,6 +75,10 @@ def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, po
     The local map lives in its own odometry frame and is never touched by optimize: the factor is pose_{k-1}^-1 . pose_k
     of that frame, and the track goes on as poses[-1] @ delta.  Combines with odom_robust; with an `align` of the
     caller's it is refused.
+    loop_edge_loss: (kind, scale), kind one of capi.PG_LOSS_* (None: none); pose_graph.set_loop_loss(kind, scale) on
+    whichever graph is in use, before the prior is added (not in the reference node): the back end prices every loop
+    closure under that robust loss and can refuse a false one.  The factor list does not depend on it.
+    SlamRun.loop_weights / loop_distances = pose_graph.loop_weights() after the final optimize when that succeeded.
     Under weights final_error is a weighted RMS and reads lower than the plain one: the gate `> 1.0` above, the
     detector's fitness threshold and the odometry factors' noise all read that number."""
     if loop_on_device and loop_backend is not None:
@@ -95,6 +101,8 @@ def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, po
     if pose_graph is None:
         from .pose_graph import PoseGraph
         pose_graph = PoseGraph(ctx, pose_graph_config)
+    if loop_edge_loss is not None:
+        pose_graph.set_loop_loss(int(loop_edge_loss[0]), float(loop_edge_loss[1]))
     if ground is not None and global_map is not None:
         global_map.set_ground(ground)
     store = None                                                     # (the store the device detector indexes)
@@ -181,6 +189,8 @@ def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, po
         if pending:                                                  # :112-115
             optimize(k)
     optimize("end")                                                  # :103-106
+    if loop_edge_loss is not None and run.optimizations[-1][1]:
+        run.loop_weights, run.loop_distances = pose_graph.loop_weights()
     if global_map is not None:                                       # build_final_global_map, :107,196-209
         run.cells, run.published_map = global_map.finish(run.poses, grid, map_voxel)
         if raycast:

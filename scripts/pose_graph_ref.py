@@ -331,16 +331,20 @@ def _margin(a, b):
     return abs(a - b) / max(abs(a), abs(b), 1e-300)
 
 
-def levenberg_marquardt(kind, fi, fj, Z, inv_sigma, X0, cfg, ordering="COLAMD"):
+def levenberg_marquardt(kind, fi, fj, Z, inv_sigma, X0, cfg, ordering="COLAMD", linearize=None, errors=None):
     """LevenbergMarquardtOptimizer::optimize() with LevenbergMarquardtParams' defaults and the caller's
-    max_iterations / relativeErrorTol / absoluteErrorTol (pose_graph.cpp:153-157).  Returns (X, LMStats)."""
+    max_iterations / relativeErrorTol / absoluteErrorTol (pose_graph.cpp:153-157).  Returns (X, LMStats).
+    `linearize` and `errors` replace `_linearize` and `factor_errors` (same arguments, same returns): a robust noise
+    model whitens the system and prices a factor differently (scripts/pose_graph_loss_ref.py); the policy is this one."""
+    linearize = linearize or _linearize
+    errors = errors or factor_errors
     lam, lam_factor, lam_lower, lam_upper = 1e-5, 10.0, 0.0, 1e5   # LevenbergMarquardtParams: lambdaInitial,
     min_fidelity = 1e-3                                             # lambdaFactor, lambdaLowerBound, lambdaUpperBound,
     rel_tol, abs_tol, err_tol = cfg.relative_error_tol, cfg.absolute_error_tol, 0.0   # minModelFidelity; errorTol 0
     n = X0.shape[0]
     X = X0.copy()
     st = LMStats()
-    error = total_error(kind, fi, fj, Z, inv_sigma, X)
+    error = float(np.sum(errors(kind, fi, fj, Z, inv_sigma, X)))
     st.initial_error = error
     st.history.append(error)
     # NonlinearOptimizer::defaultOptimize: nothing to do when the error is already <= errorTol or no iteration is allowed
@@ -351,7 +355,7 @@ def levenberg_marquardt(kind, fi, fj, Z, inv_sigma, X0, cfg, ordering="COLAMD"):
     while st.stop_reason == STOP_NONE:
         current = error
         # LevenbergMarquardtOptimizer::iterate: linearise once, then tryLambda until it returns true
-        rw, Ai, Aj = _linearize(kind, fi, fj, Z, inv_sigma, X)
+        rw, Ai, Aj = linearize(kind, fi, fj, Z, inv_sigma, X)
         H, g = _normal_equations(n, kind, fi, fj, rw, Ai, Aj)
         old_lin = _linear_error(kind, fi, fj, rw, Ai, Aj, np.zeros(6 * n))   # linear.error(VectorValues::Zero)
         stepped, inner_stop = False, STOP_NONE
@@ -365,7 +369,7 @@ def levenberg_marquardt(kind, fi, fj, Z, inv_sigma, X0, cfg, ordering="COLAMD"):
                 lin_change = old_lin - new_lin
                 if lin_change >= 0.0:                                           # tryLambda: the step is valid
                     Xn = retract(X, delta)
-                    new_err = total_error(kind, fi, fj, Z, inv_sigma, Xn)
+                    new_err = float(np.sum(errors(kind, fi, fj, Z, inv_sigma, Xn)))
                     cost_change = current - new_err
                     if lin_change > EPS * old_lin:
                         fidelity = cost_change / lin_change                     # tryLambda: modelFidelity
