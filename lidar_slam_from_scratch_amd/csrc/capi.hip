@@ -26,11 +26,13 @@
 #include <condition_variable>
 #include <functional>
 #include <mutex>
+#include <optional>
 #include <string>
 #include <thread>
 #include <vector>
 
 #include "../../include/icp_mi355x.h"
+#include "loop_plan.h"
 #include "kernels.h"
 #include "nn_mfma.h"
 #include "icp_small.h"
@@ -415,8 +417,7 @@ void harvest_profile(icpmi_ctx *ctx)
 // registration, 8k points 17.7 -> 0.44 ms).
 // The MFMA engine still wins at 300 points (1.5 vs 2.6 ms for 50 iterations, 0.2 vs 0.8 ms of
 // normals); below 256 targets a split is mostly padding and the exact kernels are kept.
-constexpr int kMfmaMinTargets = 256;
-constexpr int kMfmaMinQueries = 64;
+constexpr int kMfmaMinTargets = 256; // (and sources of at least kMfmaMinQueries rows: loop_plan.h)
 
 // Single-GPU loop: final sum, step and pose update in one launch (k_finish_step_transform).
 // ICPMI_FUSE_FINISH=0 keeps the two separate kernels (the A/B knob of scripts/ab_fuse_finish.sh).
@@ -437,11 +438,7 @@ int finish_transform_blocks(int n)
     return std::max(1, std::min(kFinishBlocksMax, (n + kFinishThreads - 1) / kFinishThreads));
 }
 
-// Small clouds (the reference's real callers: filtered scans of 5-20k points): search, residuals and
-// pose update of the rows in ONE kernel per iteration (icp_small.h) when the target is at most
-// kSmallMaxSplits splits and the source at most kSmallMaxQueries rows (beyond, the general path's 512-query
-// units amortise the operand reads better).  ICPMI_SMALL=0 switches the path off (A/B runs, parity
-// test).
+// ICPMI_SMALL=0 switches the small-cloud kernel off (loop_plan.h, kSmallMaxQueries)
 bool small_enabled()
 {
     static const bool v = [] {
@@ -450,13 +447,7 @@ bool small_enabled()
     }();
     return v;
 }
-constexpr int kSmallMaxQueries = 32768;
-// The small-cloud kernel's workgroup takes 32 rows through ALL splits, so its time grows with rows x splits where the
-// general path's grows with the units on the chip: measured (scripts/engine_threshold.py, profiles/r4_final/
-// engine_threshold.json: registrations of n -> n points by the three paths) it wins or ties up to 7 splits (14k points:
-// 0.385 against 0.416 ms on a LiDAR-like pair), ties at 10 and loses from 14 (uniform 28k: 1.03 against 0.93 ms).
-// ICPMI_SMALL_MAX_SPLITS moves the limit (at most kSmallMaxSplits, what the kernel's LDS records hold).
-constexpr int kSmallSplitsDefault = 8;
+// ICPMI_SMALL_MAX_SPLITS moves its limit of splits (loop_plan.h, kSmallSplitsDefault)
 int small_max_splits()
 {
     static const int v = [] {
@@ -468,10 +459,16 @@ int small_max_splits()
     }();
     return v;
 }
-// (by the target alone: whether its Morton-ordered normals are worth keeping)
-bool small_target(const icpmi_ctx *ctx)
+// what a call's form is decided from (loop_plan.h), first the part the prepared target alone gives
+LoopFacts target_facts(const icpmi_ctx *ctx)
 {
-    return small_enabled() && ctx->nn_engine == ICPMI_SEARCH_MFMA_BF16 && !ctx->nn_pruned && ctx->nn_splits <= small_max_splits();
+    LoopFacts f;
+    f.nn_engine = ctx->nn_engine;
+    f.nn_pruned = ctx->nn_pruned;
+    f.nn_splits = ctx->nn_splits;
+    f.sw_small = small_enabled();
+    f.sw_small_max_splits = small_max_splits();
+    return f;
 }
 
 // Choose and prepare the search engine for a target cloud (once per call: the target does
@@ -552,68 +549,32 @@ int prepare_nn(icpmi_ctx *ctx, const double *d_tgt, int m, int n_hint)
     return ICPMI_OK;
 }
 
-// when d_nrm/d_partials are given the resolve kernel also does k_reduce's work (one partial
-// row per resolve workgroup: resolve_blocks(n) rows)
-// Which resolve kernel: 0 = k_nn_resolve<16> (16 queries per wave, 64 per workgroup); 8 = k_nn_resolve4<8> (4 queries
-// per wave, 32 per workgroup).  Measured (resolve + finish_step per pass, 100k targets): 8.8k / 12.5k / 25k queries
-// 34 -> 25 / 37 -> 27 / 41 -> 36 us with the quarter-wave kernel, 50k / 100k queries 46 -> 52 / 63 -> 80 us (its 2-4x
-// more partial rows and waves cost more than the shorter chains save).  32 queries per wave (k_nn_resolve<32>: all the
-// waves of a C3 pass on the chip at once) lost too: 55.7 us against 48.7 at C3, the longer chain per wave costs more.
-int resolve_waves(int n)
+// an on / off switch of the environment: on unless its value starts with 0
+bool env_on(const char *name)
 {
-    return n <= 32768 ? 8 : 0;
-}
-// All-pairs coarse pass on few units (filtered scans: 14 query blocks x 4 splits): 256-query units -- one
-// 32-query tile per wave instead of two -- when even those fit the chip in one round (at most one unit per CU).
-// The units' time is their waves' time there, so half the work per wave is a shorter pass; once the chip is full
-// the 512-query unit amortises its staging and operand build over twice the results.
-bool coarse_half_units(const icpmi_ctx *ctx, int n, int splits)
-{
-    const long units = (long)((n + kCoarseQueries - 1) / kCoarseQueries) * splits;
-    return units <= (long)ctx->cu_count;
-}
-int resolve_blocks(int n)
-{
-    const int w = resolve_waves(n);
-    const int per = w > 0 ? 4 * w : kResolveWW * kResolveQ;
-    return (n + per - 1) / per;
+    const char *e = getenv(name);
+    return !(e && e[0] == '0');
 }
 
 // ICPMI_NN_BOUNDED=0: every pass of the ICP loop keeps its coarse minima and certifies afterwards (round 2's form)
 // (read at every call, so that one process can run both forms on the same input: scripts/fuzz_bounded.py)
-bool nn_bounded_enabled()
-{
-    const char *e = getenv("ICPMI_NN_BOUNDED");
-    return !(e && e[0] == '0');
-}
+bool nn_bounded_enabled() { return env_on("ICPMI_NN_BOUNDED"); }
 
 // ICPMI_NN_REUSE=0: every bounded pass of the all-pairs engine lists every row again (the form before list reuse; read at
 // every call like ICPMI_NN_BOUNDED).  The skin (a fraction of a row's sqrt(ub)) and the looseness limit: RowBounds.
-bool nn_reuse_enabled()
-{
-    const char *e = getenv("ICPMI_NN_REUSE");
-    return !(e && e[0] == '0');
-}
+bool nn_reuse_enabled() { return env_on("ICPMI_NN_REUSE"); }
 constexpr double kNnSkin = 0.5, kNnLoose = 8.0; // (the sweep: DESIGN.md, "List reuse")
 
 // ICPMI_NN_MARGIN=0: no row's match is certified by its margin (list_reuse.h, "the match margin"): the launches and bits of
 // the form before it.  Read at every call like ICPMI_NN_REUSE; on only where list reuse is and the loop's resolve is
 // k_nn_resolve_bounded (sources of more than 32,768 rows), ungated.
-bool nn_margin_enabled()
-{
-    const char *e = getenv("ICPMI_NN_MARGIN");
-    return !(e && e[0] == '0');
-}
+bool nn_margin_enabled() { return env_on("ICPMI_NN_MARGIN"); }
 
 // Lean passes (list_reuse.h, "lean passes").  ICPMI_NN_LEAN=0: every pass launches k_row_list and the coarse
 // kernel, the launches of the form before lean passes -- the reference leg of tests and A/B runs.  ICPMI_NN_LEAN_FROM=k
 // (k >= 2) is a TEST HOOK: every pass from the k-th on is lean whatever the counts say, which is the only way to put many
 // rows through a lean pass's exhaustive search.  Both are read at every call like ICPMI_NN_MARGIN.
-bool nn_lean_enabled()
-{
-    const char *e = getenv("ICPMI_NN_LEAN");
-    return !(e && e[0] == '0');
-}
+bool nn_lean_enabled() { return env_on("ICPMI_NN_LEAN"); }
 int nn_lean_from()
 {
     const char *e = getenv("ICPMI_NN_LEAN_FROM");
@@ -700,12 +661,18 @@ size_t group_cnt_bytes(const icpmi_ctx *ctx)
 int coarse_groups_grid(const icpmi_ctx *ctx) { return 2 * ctx->cu_count; }
 size_t coarse_groups_lds(int splits) { return sizeof(unsigned) * (2 * (size_t)splits + 1); }
 
-// `bounded`: d_idx holds the rows' matches of the previous pass and the kernel that moved the rows has left their bounds
-// in ctx->nn_lists (RowBounds, kernels.h; nn_bounded.h)
+// One search of the ICP loop, as the loop's plan describes it; default-constructed: a stand-alone search over all pairs.
+struct NnPass {
+    int pruned_pass = -1; // the culled engine: which pass of the call (selects the set of group lists); -1: all-pairs engine
+    bool bounded = false; // d_idx holds the rows' matches of the previous pass and the kernel that moved the rows has left
+                          // their bounds in ctx->nn_lists (RowBounds, kernels.h; nn_bounded.h)
+    bool list = false;    // list reuse: the coarse pass runs over the packed list of the rows listed again
+    bool lean = false;    // a lean pass: no coarse launch
+    bool margin = false;  // the match margin's resolve
+};
 int launch_nn_mfma(icpmi_ctx *ctx, const double *d_qry, int n, int m, int *d_idx, double *d_d2,
                    const IcpState *st, const double *d_tgt = nullptr, const double *d_nrm = nullptr,
-                   double *d_partials = nullptr, int pruned_pass = -1, bool bounded = false, bool reuse_list = false,
-                   bool lean = false, bool margin = false)
+                   double *d_partials = nullptr, const NnPass &pass = NnPass{})
 {
     const int splits = ctx->nn_splits;
     int rc;
@@ -714,32 +681,28 @@ int launch_nn_mfma(icpmi_ctx *ctx, const double *d_qry, int n, int m, int *d_idx
     unsigned long long *counters = (unsigned long long *)((char *)ctx->nn_misc.p + 128);
     Range range("icpmi:nn_search");
     StageTimer t(ctx, ST_NN);
-    if (bounded) {
+    if (pass.bounded) {
         const NnListRows lr = nn_list_rows(ctx, n);
-        double *ub_row = lr.ub;
-        unsigned *ent_row = lr.ent;
-        float *ubf_row = lr.ubf, *sqf_row = lr.sqf;
-        int *cnt_row = lr.cnt;
         // (a lean pass of the all-pairs engine -- list_reuse.h, "lean passes" -- has no coarse launch: the rows' kept lists and
         // certificates stand, and a row that wanted a new list takes the resolve's exhaustive search)
-        if (!lean) {
+        if (!pass.lean) {
             StageTimer tc(ctx, ST_COARSE);
-            const KnnLists kl{ubf_row, sqf_row, cnt_row, ent_row, kNnEntCap};
-            if (pruned_pass >= 0) {
+            const KnnLists kl{lr.ubf, lr.sqf, lr.cnt, lr.ent, kNnEntCap};
+            if (pass.pruned_pass >= 0) {
                 // the culled engine's surviving (row group, split) pairs, list epilogue: a row's list then holds slots of
                 // evaluated splits only, and every split that can hold a target within the row's bound IS evaluated (the
                 // group's bound is the largest of its rows'); pass p reads the lists counted in set p & 1 and clears the other
-                const GroupLists cur = group_lists(ctx, pruned_pass & 1), nxt = group_lists(ctx, (pruned_pass + 1) & 1);
+                const GroupLists cur = group_lists(ctx, pass.pruned_pass & 1), nxt = group_lists(ctx, (pass.pruned_pass + 1) & 1);
                 const long groups = (n + kGroupRows - 1) / kGroupRows;
                 hipLaunchKernelGGL((k_nn_coarse_groups<false, kCoarseWaves>), dim3(coarse_groups_grid(ctx)), dim3(kCoarseThreads),
                                    coarse_groups_lds(splits), ctx->stream, d_qry, n, (size_t)0, (const uint4 *)ctx->bpack.p, frames, splits,
                                    (const unsigned *)cur.items, cur.cap, (const unsigned *)cur.cnt, nxt.cnt,
                                    ctx->opt.profile ? group_stats(ctx) : (unsigned long long *)nullptr, (unsigned long long)(groups * splits),
-                                   st, kl, group_work(ctx, pruned_pass & 1), group_work(ctx, (pruned_pass + 1) & 1));
+                                   st, kl, group_work(ctx, pass.pruned_pass & 1), group_work(ctx, (pass.pruned_pass + 1) & 1));
             } else {
-                // list reuse (`reuse_list`): the pass runs over the packed list of the rows listed again (k_row_list) and no others
-                const int *list = reuse_list ? lr.list : nullptr;
-                if (coarse_half_units(ctx, n, splits)) {
+                // list reuse (`pass.list`): the pass runs over the packed list of the rows listed again (k_row_list) and no others
+                const int *list = pass.list ? lr.list : nullptr;
+                if (coarse_half_units(ctx->cu_count, n, splits)) {
                     constexpr int per = kCoarseQueries / kCoarseQT; // queries per workgroup with one tile per wave
                     hipLaunchKernelGGL((k_nn_coarse_bounded<1, kCoarseWaves>), dim3((n + per - 1) / per, splits), dim3(kCoarseThreads), 0,
                                        ctx->stream, d_qry, n, (const uint4 *)ctx->bpack.p, frames, kl, st, list);
@@ -753,28 +716,28 @@ int launch_nn_mfma(icpmi_ctx *ctx, const double *d_qry, int n, int m, int *d_idx
         // same two words, and per wave those atomics were 25 of the kernel's 55 us -- they leave per workgroup now, and
         // only when the stage profile (level 2) is asked for)
 #define ICPMI_BOUNDED_ARGS                                                                                                        \
-    d_qry, n, (const double *)ctx->tgt_sorted.p, perm, m, ctx->nn_ms, splits, frames, (const double *)ub_row, (const int *)cnt_row, \
-        (const unsigned *)ent_row, d_idx, ctx->opt.profile >= 2 ? counters : (unsigned long long *)nullptr, d_tgt, d_nrm, d_partials, st
+    d_qry, n, (const double *)ctx->tgt_sorted.p, perm, m, ctx->nn_ms, splits, frames, (const double *)lr.ub, (const int *)lr.cnt, \
+        (const unsigned *)lr.ent, d_idx, ctx->opt.profile >= 2 ? counters : (unsigned long long *)nullptr, d_tgt, d_nrm, d_partials, st
         if (resolve_waves(n) == 8)
             hipLaunchKernelGGL(k_nn_resolve4_bounded<8>, dim3(resolve_blocks(n)), dim3(512), 0, ctx->stream, ICPMI_BOUNDED_ARGS);
-        else if (margin) // (the match margin: certified rows are not scanned, scanned rows leave their new margin)
+        else if (pass.margin) // (the match margin: certified rows are not scanned, scanned rows leave their new margin)
             hipLaunchKernelGGL(k_nn_resolve_bounded<true>, dim3(resolve_blocks(n)), dim3(64 * kResolveWW), 0, ctx->stream, ICPMI_BOUNDED_ARGS,
                                (const unsigned long long *)lr.cert, (const double *)lr.cover, lr.scan);
         else
             hipLaunchKernelGGL(k_nn_resolve_bounded<false>, dim3(resolve_blocks(n)), dim3(64 * kResolveWW), 0, ctx->stream, ICPMI_BOUNDED_ARGS,
                                (const unsigned long long *)nullptr, (const double *)nullptr, (RowScan *)nullptr);
 #undef ICPMI_BOUNDED_ARGS
-        if (!reuse_list) ctx->prof.nn_pairs += (double)n * (double)m; // (a pass with list reuse: its workgroup columns that ran,
+        if (!pass.list) ctx->prof.nn_pairs += (double)n * (double)m; // (a pass with list reuse: its workgroup columns that ran,
                                                                       // from the rows listed -- profiling only -- and added after the call)
         ctx->prof.bounded_launches += 1;
         HIP_TRY(ctx, hipGetLastError());
         return ICPMI_OK;
     }
-    if (pruned_pass >= 0) return fail(ctx, ICPMI_ERR_ARG, "internal: the culled engine has bounded passes only");
+    if (pass.pruned_pass >= 0) return fail(ctx, ICPMI_ERR_ARG, "internal: the culled engine has bounded passes only");
     if ((rc = reserve(ctx, ctx->coarse, coarse_bytes(splits, n)))) return rc;
     {
         StageTimer tc(ctx, ST_COARSE); // the dominant kernel alone (matches rocprofv3's per-kernel average)
-        if (coarse_half_units(ctx, n, splits)) {
+        if (coarse_half_units(ctx->cu_count, n, splits)) {
             constexpr int per = kCoarseQueries / kCoarseQT; // queries per workgroup with one tile per wave
             hipLaunchKernelGGL((k_nn_coarse<0, 1, kCoarseWaves>), dim3((n + per - 1) / per, splits), dim3(kCoarseThreads), 0,
                                ctx->stream, d_qry, n, (const uint4 *)ctx->bpack.p, frames, (float2 *)ctx->coarse.p,
@@ -786,10 +749,10 @@ int launch_nn_mfma(icpmi_ctx *ctx, const double *d_qry, int n, int m, int *d_idx
         }
         ctx->prof.nn_coarse_blocks += (int64_t)((n + kCoarseQueries - 1) / kCoarseQueries) * splits;
     }
-    const int *blk_cnt = nullptr, *blk_list = nullptr; // (round 3's per-block split lists: the culled engine no longer has unbounded passes)
+    // (the two null lists: round 3's per-block split lists -- the culled engine no longer has unbounded passes)
 #define ICPMI_RESOLVE_ARGS                                                                                            \
     d_qry, n, (const double *)ctx->tgt_sorted.p, perm, m, ctx->nn_ms, (const float2 *)ctx->coarse.p, splits, frames,  \
-        (const NnFrame *)ctx->nn_misc.p, d_idx, d_d2, counters, d_tgt, d_nrm, d_partials, blk_cnt, blk_list, st
+        (const NnFrame *)ctx->nn_misc.p, d_idx, d_d2, counters, d_tgt, d_nrm, d_partials, (const int *)nullptr, (const int *)nullptr, st
     if (resolve_waves(n) == 8)
         hipLaunchKernelGGL(k_nn_resolve4<8>, dim3(resolve_blocks(n)), dim3(512), 0, ctx->stream, ICPMI_RESOLVE_ARGS);
     else
@@ -827,20 +790,12 @@ int launch_nn(icpmi_ctx *ctx, const double *d_qry, int n, const double *d_tgt, i
     return ICPMI_OK;
 }
 
-int reduce_blocks(const icpmi_ctx *ctx, int n)
-{
-    return std::max(1, std::min(ctx->cu_count, (n + 255) / 256));
-}
-
 // Normal estimation takes the target's rows in Morton order (a rank's slice is then a range of sorted positions) with
 // the pruned engine, whose blocks must be compact, and with the all-pairs engine's list form (knn_lists.h;
 // ICPMI_KNN_LISTS=0: round 2's slot-minimum form, rows in point order)
 bool knn_lists_enabled()
 {
-    static const bool on = [] {
-        const char *e = getenv("ICPMI_KNN_LISTS");
-        return !(e && e[0] == '0');
-    }();
+    static const bool on = env_on("ICPMI_KNN_LISTS");
     return on;
 }
 // The target's k-NN setup on the all-pairs engine culls its coarse pass like the culled engine's does (k_knn_group_cull +
@@ -852,10 +807,7 @@ bool knn_lists_enabled()
 constexpr int kKnnCullFromSplits = kAutoCulledFrom;
 bool knn_cull_enabled()
 {
-    static const bool on = [] {
-        const char *e = getenv("ICPMI_KNN_CULL");
-        return !(e && e[0] == '0');
-    }();
+    static const bool on = env_on("ICPMI_KNN_CULL");
     return on;
 }
 bool knn_culled(const icpmi_ctx *ctx)
@@ -936,7 +888,7 @@ int launch_knn(icpmi_ctx *ctx, const double *d_qry, int nq_total, const double *
                                        splits, (const unsigned *)gl.items, gl.cap, (const unsigned *)gl.cnt, (unsigned *)nullptr,
                                        (unsigned long long *)nullptr, 0ull, (const IcpState *)nullptr, kl, group_work(ctx, 0),
                                        (unsigned *)nullptr);
-                } else if (coarse_half_units(ctx, nq, splits)) {
+                } else if (coarse_half_units(ctx->cu_count, nq, splits)) {
                     constexpr int per = kCoarseQueries / kCoarseQT;
                     hipLaunchKernelGGL((k_nn_coarse_rows<1, kCoarseWaves>), dim3((nq + per - 1) / per, splits), dim3(kCoarseThreads), 0,
                                        s, sorted + c0, nq, (size_t)ctx->nn_ms, (const uint4 *)ctx->bpack.p, frames, kl);
@@ -956,7 +908,7 @@ int launch_knn(icpmi_ctx *ctx, const double *d_qry, int nq_total, const double *
                                    (const unsigned *)ctx->sort_keys.p + (size_t)m /* the sorted keys */, m, ctx->nn_ms, k,
                                    (const NnFrame *)ctx->nn_misc.p, t_row, tf_row, sqf_row, cnt_row,
                                    c0 == row0 ? fb_count : (int *)nullptr);
-                if (coarse_half_units(ctx, nq, splits)) {
+                if (coarse_half_units(ctx->cu_count, nq, splits)) {
                     constexpr int per = kCoarseQueries / kCoarseQT;
                     hipLaunchKernelGGL((k_nn_coarse_bounded<1, kCoarseWaves>), dim3((nq + per - 1) / per, splits), dim3(kCoarseThreads), 0,
                                        s, d_qry + 3 * c0, nq, (const uint4 *)ctx->bpack.p, frames, kl, (const IcpState *)nullptr);
@@ -967,7 +919,7 @@ int launch_knn(icpmi_ctx *ctx, const double *d_qry, int nq_total, const double *
                                    (int)c0, nq, (const double *)t_row, (const int *)cnt_row, (const unsigned *)ent_row, knn, fb_list,
                                    fb_count);
             } else {
-                if (coarse_half_units(ctx, nq, splits)) {
+                if (coarse_half_units(ctx->cu_count, nq, splits)) {
                     constexpr int per = kCoarseQueries / kCoarseQT;
                     hipLaunchKernelGGL((k_nn_coarse<1, 1, kCoarseWaves>), dim3((nq + per - 1) / per, splits),
                                        dim3(kCoarseThreads), 0, s, d_qry + 3 * c0, nq, (const uint4 *)ctx->bpack.p,
@@ -1114,7 +1066,7 @@ int exchange_allgather(icpmi_ctx *ctx, double *d_buf, size_t per)
 // kernel: its slot scans then read a candidate's normal next to its coordinates.
 int sort_normals(icpmi_ctx *ctx, int m)
 {
-    if (!small_target(ctx)) return ICPMI_OK;
+    if (!small_target(target_facts(ctx))) return ICPMI_OK;
     int rc;
     if ((rc = reserve(ctx, ctx->nrm_sorted, sizeof(double) * 3 * (size_t)ctx->nn_ms))) return rc;
     hipLaunchKernelGGL(k_gather_points, dim3((m + 255) / 256), dim3(256), 0, ctx->stream, (const double *)ctx->nrm.p,
@@ -1179,141 +1131,195 @@ struct GateRun {
 };
 static_assert(kRobustHuber == ICPMI_ROBUST_HUBER && kRobustGemanMcClure == ICPMI_ROBUST_GEMAN_MCCLURE, "the kernels' kinds are the header's");
 
-// `gate` (may be null): see GateRun.  A gated registration runs the small-cloud kernel's gated form in the small regime
-// and otherwise the unfused general path -- search (launch_nn), k_reduce_gated, k_finish_step_gated, k_transform -- on
-// whichever engine prepare_nn chose: no fused resolve, no culling, no bounds, no list reuse, no sorted rows.
-// `before_wait` (may be null): called once everything of the registration, the copies of its results
-// included, is queued and an event behind them recorded -- what it queues runs while the host waits
-// for that event only (icpmi_stream_push prepares the next frame's target there).
-int align_device(icpmi_ctx *ctx, const double *d_src, int64_t n_src64, const double *d_tgt,
-                 int64_t n_tgt64, const icpmi_config *cfg, icpmi_result *result,
-                 double *error_history, int32_t history_cap, int (*before_wait)(icpmi_ctx *) = nullptr,
-                 int (*after_first)(icpmi_ctx *) = nullptr, GateRun *gate = nullptr)
+LoopRule rule_of(const GateRun *gate) { return !gate ? kRuleNone : gate->kind ? kRuleRobust : kRuleGate; }
+
+// One launch of the kernel that the call's rule selects out of a plain / gated / robust triple whose arguments differ only in
+// the rule's own, which go behind the common ones (k_reduce*, k_icp_small*).
+template <class... PA, class... GA, class... RA, class... A>
+void launch_by_rule(const GateRun *gate, void (*plain)(PA...), void (*gated)(GA...), void (*robust)(RA...), dim3 grid, dim3 block,
+                    hipStream_t s, A... common)
 {
-    const int n = (int)n_src64, m = (int)n_tgt64;
-    const int max_it = cfg->max_iterations;
-    const int max_hist = max_it + 1;
-    hipStream_t s = ctx->stream;
-    int rc;
-
-    ctx->loop_rows = -1; // (set again once this call has completed)
-    if ((rc = reserve(ctx, ctx->cur, sizeof(double) * 3 * (size_t)n))) return rc;
-    if ((rc = reserve(ctx, ctx->nrm, sizeof(double) * 3 * (size_t)m))) return rc;
-    if ((rc = reserve(ctx, ctx->idx, sizeof(int) * (size_t)n))) return rc;
-    if ((rc = reserve(ctx, ctx->history, sizeof(double) * (size_t)(max_hist + 1)))) return rc;
-
-    double *cur = (double *)ctx->cur.p;
-    double *nrm = (double *)ctx->nrm.p;
-    int *idx = (int *)ctx->idx.p;
-    double *hist = (double *)ctx->history.p;
-
-    Range range_call("icpmi:align");
-    StageTimer *t_total = new StageTimer(ctx, ST_TOTAL);
-    struct Closer { StageTimer *&p; ~Closer() { delete p; p = nullptr; } } close_total{t_total};
-
-    // state: total = initial_transform (icp.hpp:163,178), prev_error = DBL_MAX (icp.hpp:179)
-    IcpState *hs = ctx->h_state;
-    memset(hs, 0, sizeof(*hs));
-    memcpy(hs->total, cfg->initial_transform, sizeof(double) * 16);
-    hs->prev_error = 1.7976931348623157e308;
-    hs->tolerance = cfg->tolerance;
-    hs->min_error = cfg->min_error;
-    hs->max_hist = max_hist;
-    // two state buffers: the sharded loop's fused step + transform kernel reads one and writes the
-    // other (k_step_transform); `st` is the one the coming kernels read
-    IcpState *st = ctx->d_state;
-    HIP_TRY(ctx, hipMemcpyAsync(st, hs, sizeof(IcpState), hipMemcpyHostToDevice, s));
-
-    const bool sharded_run = ctx->comm != nullptr || ctx->cb_allreduce != nullptr;
-    if (gate && sharded_run) return fail(ctx, ICPMI_ERR_ARG, "a context with a communicator does not run gated registrations");
-    const bool prepared = !sharded_run && ctx->prep_valid && ctx->prep_tgt == d_tgt && ctx->prep_m == m &&
-                          ctx->prep_engine == engine_for(ctx, m, n);
-    // (the ranks of a sharded run must agree on the engine -- it decides the order of the normal rows they gather -- so
-    // there AUTO looks at the target alone, whatever this rank's share of the source)
-    if (!prepared && (rc = prepare_nn(ctx, d_tgt, m, sharded_run ? std::max(n, kMfmaMinQueries) : n))) return rc;
-    // with the MFMA engine the resolve kernel also forms the normal-equation partial sums
-    // (not under a gate: its general path searches first and tests the rows in k_reduce_gated)
-    const bool fused = ctx->nn_engine == ICPMI_SEARCH_MFMA_BF16 && !gate;
-    // small clouds: one kernel per iteration for the rows' work (icp_small.h), then k_finish_step
-    const bool small = !sharded_run && n > 0 && n <= kSmallMaxQueries && small_target(ctx);
-    const int rblocks = small ? (n + kSmallQ - 1) / kSmallQ : (fused ? resolve_blocks(n) : reduce_blocks(ctx, n));
-    // very many partial rows (a resolve workgroup leaves one per 64 queries) are first added in groups of kSumGroup by a
-    // kernel of their own (k_sum_groups, kernels.h): the step kernels then sum rblocks2 rows
-    const bool sum_tree = rblocks >= kSumTreeFrom;
-    const int rblocks2 = sum_tree ? (rblocks + kSumGroup - 1) / kSumGroup : 0;
-    // (k_sum_groups adds kNumSums columns, one short of a robust row's; a robust general pass leaves reduce_blocks() rows)
-    if (gate && gate->kind && sum_tree && !small) return fail(ctx, ICPMI_ERR_ARG, "internal: a robust pass of %d partial rows", rblocks);
-    if ((rc = reserve(ctx, ctx->partials, sizeof(double) * kSumsStride * ((size_t)rblocks + (size_t)rblocks2)))) return rc;
-    double *partials = (double *)ctx->partials.p;
-    // what the step kernels sum
-    const double *fin_rows = sum_tree ? partials + kSumsStride * (size_t)rblocks : partials;
-    const int fin_blocks = sum_tree ? rblocks2 : rblocks;
-
-    // normals of the target (icp.hpp:169-171).  With several ranks each computes a slice of
-    // rows against the full target and the slices are all-gathered.
-    const bool sharded = ctx->comm != nullptr || ctx->cb_allreduce != nullptr; // exchanges on, even for 1 rank
-    // pruned engine: rows are taken in the target's Morton order, so that a block's neighbours
-    // lie in few splits (launch_normals); a rank's slice is then a range of sorted positions
-    const bool sorted_rows = sorted_normal_rows(ctx, ctx->opt.normal_k, m);
-    if (sharded) {
-        int per = (m + ctx->n_ranks - 1) / ctx->n_ranks;
-        if (sorted_rows) per = (per + kCoarseQueries - 1) / kCoarseQueries * kCoarseQueries; // whole blocks (and slots) per rank
-        if ((rc = reserve(ctx, ctx->stage_a, sizeof(double) * 3 * (size_t)per * ctx->n_ranks))) return rc;
-        double *gathered = (double *)ctx->stage_a.p;
-        const int row0 = (int)std::min<long>(m, (long)ctx->rank * per), row1 = (int)std::min<long>(m, (long)row0 + per);
-        // rows land at their global offset inside `gathered`, so the gather is in place
-        if ((rc = launch_normals(ctx, d_tgt, m, ctx->opt.normal_k, row0, row1, gathered, sorted_rows, false))) return rc;
-        if ((rc = exchange_allgather(ctx, gathered, 3 * (size_t)per))) return rc;
-        if (sorted_rows)
-            hipLaunchKernelGGL(k_scatter_rows, dim3((m + 255) / 256), dim3(256), 0, s, (const double *)gathered,
-                               (const unsigned *)ctx->sort_keys.p + 3 * (size_t)m, m, nrm);
-        else
-            HIP_TRY(ctx, hipMemcpyAsync(nrm, gathered, sizeof(double) * 3 * (size_t)m,
-                                        hipMemcpyDeviceToDevice, s));
-    } else if (!prepared) {
-        if ((rc = launch_normals(ctx, d_tgt, m, ctx->opt.normal_k, 0, m, nrm, sorted_rows, true))) return rc;
-        if ((rc = sort_normals(ctx, m))) return rc;
+    switch (rule_of(gate)) {
+    case kRuleRobust: hipLaunchKernelGGL(robust, grid, block, 0, s, common..., gate->g2, (int)gate->kind, gate->ks); break;
+    case kRuleGate: hipLaunchKernelGGL(gated, grid, block, 0, s, common..., gate->g2); break;
+    case kRuleNone: hipLaunchKernelGGL(plain, grid, block, 0, s, common...); break;
     }
-    ctx->prep_valid = false; // (the stream path prepares the next target below; nothing else relies on it)
+}
 
-    // Pruned engine: the source is put in Morton order once (a rigid motion keeps neighbours
-    // together), so that every block of kCoarseQueries consecutive rows of `cur` is a compact
-    // blob whose bounding box can rule whole target splits out.  The order of the rows of
-    // `cur` is internal: only sums over all rows leave this function.
-    const bool pruned = fused && ctx->nn_pruned && n > 0;
-    const SplitFrame *frames = (const SplitFrame *)ctx->frames.p;
-    const int splits = ctx->nn_splits;
-    int pass_no = 0; // coarse passes queued so far: selects the work counter (see k_nn_coarse_list)
+// Waits (bounded) until the device has stored `want` in a host-mapped word, as `value_of` reads it out of the word.
+template <class W, class F>
+int await_word(icpmi_ctx *ctx, const volatile W *word, int want, F value_of, const char *never, W *out)
+{
+    W v = *word;
+    for (long spin = 0; value_of(v) != want; ++spin) {
+        if (spin > 2000000) { // ~seconds: something is wrong with the stream, find out what
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            v = *word;
+            if (value_of(v) != want) return fail(ctx, ICPMI_ERR_HIP, "%s", never);
+            break;
+        }
+        if ((spin & 63) == 63) sched_yield();
+        v = *word;
+    }
+    *out = v;
+    return ICPMI_OK;
+}
+
+// One registration on its way through align_device: the call's arguments, its plan (loop_plan.h) and what the stages hand
+// each other.  The stages are the member functions below, in the order align_device calls them.
+struct LoopRun {
+    icpmi_ctx *ctx;
+    const double *d_src, *d_tgt;
+    const icpmi_config *cfg;
+    GateRun *gate; // (may be null): see GateRun
+    int n, m, max_hist;
+    hipStream_t s;
+    LoopPlan p;
+    bool prepared = false;
+    double *cur = nullptr, *nrm = nullptr, *hist = nullptr, *partials = nullptr;
+    int *idx = nullptr;
+    const double *fin_rows = nullptr; // what the step kernels sum
+    IcpState *hs = nullptr, *st = nullptr; // the pinned copy; of the two device buffers the one the coming kernels read
+    RowBounds rb{};
+    NnListRows lr{};
     const unsigned *src_perm = nullptr;
-    // All-pairs engine, general kernels: the rows are taken in Morton order too (the order is internal here as well).  A
-    // tile of 32 neighbouring rows has its matches in one or two splits, so the bounded pass's epilogue (nn_bounded.h)
-    // finds nothing to list in the other 47 and leaves by its short path: with rows in the caller's order half of all
-    // (tile, split) pairs listed something (k_nn_coarse_bounded 305 -> 295 us on C3, k_nn_resolve_bounded 29 -> 28).
-    // (from 4,096 rows: below, the Morton sort of the rows costs a call more than its passes gain)
-    // (not where ICPMI_SMALL=0 puts the general kernels in the small-cloud kernel's place: there they keep its order of rows,
-    // hence its bits)
-    const bool small_regime = !sharded_run && n <= kSmallMaxQueries && ctx->nn_splits <= small_max_splits();
-    // (and only against targets of more than a dozen splits: at 10 splits -- 18k x 20k points, six iterations -- the rows' sort is
-    // 55 us of a 0.45 ms registration whose coarse pass is 5 us; profiles/r4_final/c2_20k/timeline.txt)
-    constexpr int kSortRowsFromSplits = 12;
-    const bool sorted_rows_loop = fused && !pruned && !small && !small_regime && n >= 4096 && ctx->nn_splits > kSortRowsFromSplits;
-    size_t sort_bytes = 0;
-    if (pruned || sorted_rows_loop) {
-        HIP_TRY(ctx, sort_pairs_u32(nullptr, &sort_bytes, nullptr, nullptr, nullptr, nullptr, (unsigned)n, s));
+    int pass_no = 0;                  // coarse passes queued so far: selects the work counter (see k_nn_coarse_list)
+    bool pass_list = false;           // the coming bounded pass runs over the packed list (false: over every row -- a call's first pass)
+    bool small_first = true;          // the small-cloud kernel's first pass applies the initial transform to the caller's rows
+    std::vector<unsigned> want_known; // [p - 1]: the rows pass p wanted listed, as far as the host has read them
+    std::vector<char> lean_passes;    // [p - 1]: pass p was queued lean
+    bool lean_cur = false, lean_nxt = false; // the pass being queued, and the one after it
+    // before each k_row_list for pass `next`: where it stores the rows listed and, with the match margin, the rows certified
+    // for the coming pass (profiling)
+    unsigned *rows_count = nullptr, *cert_count = nullptr;
+    bool ended_early = false;         // the host has SEEN the device leave the loop on a convergence test
+    bool counters_back = false, stats_back = false;
+    int stat_passes = 0, hl = 0;
+    // the call's and the loop's brackets: closed by `queue_loop` behind the last pass, or with the run
+    std::optional<Range> range_call;
+    std::optional<StageTimer> t_total;
+    std::optional<Range> range_loop;
+    std::optional<StageTimer> t_loop;
+
+    // Stage 1: the buffers every form needs, and the start state
+    int begin()
+    {
+        int rc;
+        ctx->loop_rows = -1; // (set again once this call has completed)
+        if ((rc = reserve(ctx, ctx->cur, sizeof(double) * 3 * (size_t)n))) return rc;
+        if ((rc = reserve(ctx, ctx->nrm, sizeof(double) * 3 * (size_t)m))) return rc;
+        if ((rc = reserve(ctx, ctx->idx, sizeof(int) * (size_t)n))) return rc;
+        if ((rc = reserve(ctx, ctx->history, sizeof(double) * (size_t)(max_hist + 1)))) return rc;
+        cur = (double *)ctx->cur.p;
+        nrm = (double *)ctx->nrm.p;
+        idx = (int *)ctx->idx.p;
+        hist = (double *)ctx->history.p;
+        range_call.emplace("icpmi:align");
+        t_total.emplace(ctx, ST_TOTAL);
+        // state: total = initial_transform (icp.hpp:163,178), prev_error = DBL_MAX (icp.hpp:179)
+        hs = ctx->h_state;
+        memset(hs, 0, sizeof(*hs));
+        memcpy(hs->total, cfg->initial_transform, sizeof(double) * 16);
+        hs->prev_error = 1.7976931348623157e308;
+        hs->tolerance = cfg->tolerance;
+        hs->min_error = cfg->min_error;
+        hs->max_hist = max_hist;
+        // two state buffers: the sharded loop's fused step + transform kernel reads one and writes the
+        // other (k_step_transform); `st` is the one the coming kernels read
+        st = ctx->d_state;
+        HIP_TRY(ctx, hipMemcpyAsync(st, hs, sizeof(IcpState), hipMemcpyHostToDevice, s));
+        return ICPMI_OK;
+    }
+
+    // Stage 2a: the target's search structure, unless the context holds it (prepare_target)
+    int prepare_search()
+    {
+        const bool sharded = ctx->comm != nullptr || ctx->cb_allreduce != nullptr;
+        if (gate && sharded) return fail(ctx, ICPMI_ERR_ARG, "a context with a communicator does not run gated registrations");
+        prepared = !sharded && ctx->prep_valid && ctx->prep_tgt == d_tgt && ctx->prep_m == m && ctx->prep_engine == engine_for(ctx, m, n);
+        // (the ranks of a sharded run must agree on the engine -- it decides the order of the normal rows they gather -- so
+        // there AUTO looks at the target alone, whatever this rank's share of the source)
+        return prepared ? ICPMI_OK : prepare_nn(ctx, d_tgt, m, sharded ? std::max(n, kMfmaMinQueries) : n);
+    }
+
+    // Stage 2b: with the engine known, the call's form (loop_plan.h) and the partial rows it needs
+    int settle_plan()
+    {
+        LoopFacts f = target_facts(ctx);
+        f.n = n;
+        f.m = m;
+        f.cu_count = ctx->cu_count;
+        f.normal_k = ctx->opt.normal_k;
+        f.comm = ctx->comm != nullptr || ctx->cb_allreduce != nullptr;
+        f.rule = rule_of(gate);
+        f.profile = ctx->opt.profile;
+        f.sw_bounded = nn_bounded_enabled();
+        f.sw_reuse = nn_reuse_enabled();
+        f.sw_margin = nn_margin_enabled();
+        f.sw_lean = nn_lean_enabled();
+        f.sw_lean_from = nn_lean_from();
+        f.sw_fuse_finish = fuse_finish_enabled();
+        p = make_loop_plan(f);
+        if (p.error) return fail(ctx, ICPMI_ERR_ARG, p.error, p.rblocks);
+        int rc;
+        if ((rc = reserve(ctx, ctx->partials, sizeof(double) * kSumsStride * ((size_t)p.rblocks + (size_t)p.rblocks2)))) return rc;
+        partials = (double *)ctx->partials.p;
+        fin_rows = p.sum_tree ? partials + kSumsStride * (size_t)p.rblocks : partials;
+        return ICPMI_OK;
+    }
+
+    // Stage 2c: normals of the target (icp.hpp:169-171).  With several ranks each computes a slice of
+    // rows against the full target and the slices are all-gathered.
+    int target_normals()
+    {
+        int rc;
+        // pruned engine: rows are taken in the target's Morton order, so that a block's neighbours
+        // lie in few splits (launch_normals); a rank's slice is then a range of sorted positions
+        const bool sorted_rows = sorted_normal_rows(ctx, ctx->opt.normal_k, m);
+        if (p.sharded) {
+            int per = (m + ctx->n_ranks - 1) / ctx->n_ranks;
+            if (sorted_rows) per = (per + kCoarseQueries - 1) / kCoarseQueries * kCoarseQueries; // whole blocks (and slots) per rank
+            if ((rc = reserve(ctx, ctx->stage_a, sizeof(double) * 3 * (size_t)per * ctx->n_ranks))) return rc;
+            double *gathered = (double *)ctx->stage_a.p;
+            const int row0 = (int)std::min<long>(m, (long)ctx->rank * per), row1 = (int)std::min<long>(m, (long)row0 + per);
+            // rows land at their global offset inside `gathered`, so the gather is in place
+            if ((rc = launch_normals(ctx, d_tgt, m, ctx->opt.normal_k, row0, row1, gathered, sorted_rows, false))) return rc;
+            if ((rc = exchange_allgather(ctx, gathered, 3 * (size_t)per))) return rc;
+            if (sorted_rows)
+                hipLaunchKernelGGL(k_scatter_rows, dim3((m + 255) / 256), dim3(256), 0, s, (const double *)gathered,
+                                   (const unsigned *)ctx->sort_keys.p + 3 * (size_t)m, m, nrm);
+            else
+                HIP_TRY(ctx, hipMemcpyAsync(nrm, gathered, sizeof(double) * 3 * (size_t)m,
+                                            hipMemcpyDeviceToDevice, s));
+        } else if (!prepared) {
+            if ((rc = launch_normals(ctx, d_tgt, m, ctx->opt.normal_k, 0, m, nrm, sorted_rows, true))) return rc;
+            if ((rc = sort_normals(ctx, m))) return rc;
+        }
+        ctx->prep_valid = false; // (the stream path prepares the next target below; nothing else relies on it)
+        return ICPMI_OK;
+    }
+
+    // Stage 3: the Morton order of the source rows, where the plan sorts them (LoopPlan::sort_source), and the culled engine's
+    // group lists
+    int sort_source()
+    {
+        int rc;
+        size_t sort_bytes = 0;
         const int bblocks = std::max(1, std::min(256, (n + 255) / 256));
-        if ((rc = reserve(ctx, ctx->src_sort, sizeof(unsigned) * 4 * (size_t)n))) return rc;
-        if ((rc = reserve(ctx, ctx->sort_tmp, sort_bytes))) return rc; // the target's sort is done (stream order)
-        if ((rc = reserve(ctx, ctx->bbox_part, sizeof(double) * 6 * (size_t)bblocks))) return rc;
-    }
-    if (pruned) { // the group lists of the coming passes (nn_culled.h); both sets of counters start empty
-        if ((rc = reserve_group_lists(ctx, splits, (n + kGroupRows - 1) / kGroupRows))) return rc;
-        HIP_TRY(ctx, hipMemsetAsync(ctx->grp_cnt.p, 0, group_cnt_bytes(ctx), s));
-    }
-    if (pruned || sorted_rows_loop) {
+        if (p.sort_source) {
+            HIP_TRY(ctx, sort_pairs_u32(nullptr, &sort_bytes, nullptr, nullptr, nullptr, nullptr, (unsigned)n, s));
+            if ((rc = reserve(ctx, ctx->src_sort, sizeof(unsigned) * 4 * (size_t)n))) return rc;
+            if ((rc = reserve(ctx, ctx->sort_tmp, sort_bytes))) return rc; // the target's sort is done (stream order)
+            if ((rc = reserve(ctx, ctx->bbox_part, sizeof(double) * 6 * (size_t)bblocks))) return rc;
+        }
+        if (p.pruned) { // the group lists of the coming passes (nn_culled.h); both sets of counters start empty
+            if ((rc = reserve_group_lists(ctx, ctx->nn_splits, (n + kGroupRows - 1) / kGroupRows))) return rc;
+            HIP_TRY(ctx, hipMemsetAsync(ctx->grp_cnt.p, 0, group_cnt_bytes(ctx), s));
+        }
+        if (!p.sort_source) return ICPMI_OK;
         // (Measured and not kept: this dozen of small launches on a stream of its own beside the target's pre-pass and normals
         // -- 180 us off the call under rocprofv3, whose launch overhead starves the device at the head of a call, and nothing
         // without it: 8,567 against 8,595 iterations/s at C3.)
-        const int bblocks = std::max(1, std::min(256, (n + 255) / 256));
         NnFrame *sframe = (NnFrame *)((char *)ctx->nn_misc.p + 64);
         unsigned *keys_in = (unsigned *)ctx->src_sort.p, *keys_out = keys_in + n, *vals_in = keys_in + 2 * (size_t)n,
                  *perm = keys_in + 3 * (size_t)n;
@@ -1328,198 +1334,183 @@ int align_device(icpmi_ctx *ctx, const double *d_src, int64_t n_src64, const dou
                            keys_in, vals_in);
         HIP_TRY(ctx, sort_pairs_u32(ctx->sort_tmp.p, &sort_bytes, keys_in, keys_out, vals_in, perm, (unsigned)n, s));
         src_perm = perm;
+        return ICPMI_OK;
     }
 
-    // Bounded passes (nn_bounded.h): every kernel that moves the rows after a pass also leaves, per row, the exact distance
-    // to the target it was just matched with -- the bound the next pass searches behind.
-    // Round 4: the FIRST pass has a bound too -- the nearest of the sorted targets around each row's place in the target's
-    // Morton order (k_nn_prebound1) stands in for the previous match -- so no pass of a registration keeps coarse minima:
-    // the (row, split) buffer (6 B each: 2.9 GB at 1M x 1M) is not reserved by this function at all.  Every general-path
-    // loop of the MFMA engines is bounded now, whatever its row order (ICPMI_NN_BOUNDED=0: round 2's form for the
-    // all-pairs engine, the A/B and fuzz reference; the culled engine has no other form).
-    const bool bounded_loop = fused && !small && n > 0 && (pruned || nn_bounded_enabled());
-    if (pruned && !bounded_loop) return fail(ctx, ICPMI_ERR_ARG, "internal: the culled engine needs the bounded resolve kernels");
-    // List reuse (RowBounds, kernels.h), all-pairs engine: a row keeps its list of slots from pass to pass while its bound and
-    // its drift from where the list was built show that a new list could hold nothing the kept one lacks, and the coarse
-    // pass runs over the packed list of the rows that were listed again (k_row_list, queued behind the kernel that moves
-    // the rows).  A call's first pass lists every row (k_nn_prebound1 marks its lists as not to be kept).  The culled engine
-    // keeps its own form.
-    const bool reuse = bounded_loop && !pruned && nn_reuse_enabled();
-    // The match margin (list_reuse.h): rows whose kept match is certified as the unique nearest target are neither listed
-    // nor scanned.  k_nn_resolve_bounded's loops only; the gated and robust loops keep the form before it.
-    const bool margin = reuse && !gate && resolve_waves(n) == 0 && nn_margin_enabled();
-    bool pass_list = false; // the coming bounded pass runs over the packed list (false: over every row -- a call's first pass)
-    RowBounds rb{};
-    NnListRows lr{};
-    if (bounded_loop) {
-        if ((rc = reserve(ctx, ctx->nn_lists, nn_list_bytes(n)))) return rc;
-        lr = nn_list_rows(ctx, n);
-        rb = RowBounds{d_tgt, idx, m, lr.ub, lr.ubf, lr.sqf, lr.cnt};
-        if (reuse) {
-            rb.xb = lr.xb;
-            rb.mask = lr.mask;
-            rb.skin = kNnSkin;
-            rb.loose = kNnLoose;
-            if (margin) rb.scan = lr.scan, rb.cover = lr.cover, rb.cert = lr.cert;
-            if (ctx->opt.profile) HIP_TRY(ctx, hipMemsetAsync(lr.stat_rows, 0, sizeof(unsigned) * 2 * kReuseStatPasses, s));
+    // Stage 4: the rows' bounds and lists of a bounded loop, the first move and the first pass's bounds
+    int first_move()
+    {
+        int rc;
+        if (p.bounded) {
+            if ((rc = reserve(ctx, ctx->nn_lists, nn_list_bytes(n)))) return rc;
+            lr = nn_list_rows(ctx, n);
+            rb = RowBounds{d_tgt, idx, m, lr.ub, lr.ubf, lr.sqf, lr.cnt};
+            if (p.reuse) {
+                rb.xb = lr.xb;
+                rb.mask = lr.mask;
+                rb.skin = kNnSkin;
+                rb.loose = kNnLoose;
+                if (p.margin) rb.scan = lr.scan, rb.cover = lr.cover, rb.cert = lr.cert;
+                if (ctx->opt.profile) HIP_TRY(ctx, hipMemsetAsync(lr.stat_rows, 0, sizeof(unsigned) * 2 * kReuseStatPasses, s));
+            }
+        }
+        // current_source = source * R0^T + t0^T (icp.hpp:174-176)
+        if (n > 0 && !p.small) { // (an empty shard of a sharded run launches nothing over its rows; the small-cloud kernel moves them itself)
+            StageTimer t(ctx, ST_TRANSFORM);
+            hipLaunchKernelGGL(k_transform, dim3(std::min(2048, (n + 255) / 256)), dim3(256), 0, s, d_src, cur, n, st, 1, 0, src_perm);
+            if (p.bounded) // the first pass's incumbents and bounds (and, culled engine, its group lists: set 0)
+                hipLaunchKernelGGL(k_nn_prebound1, dim3((n + kPreThreads - 1) / kPreThreads), dim3(kPreThreads), 0, s, (const double *)cur, n, (const double *)ctx->tgt_sorted.p,
+                                   (const unsigned *)ctx->sort_keys.p + (size_t)m /* the sorted keys */,
+                                   (const unsigned *)ctx->sort_keys.p + 3 * (size_t)m, m, ctx->nn_ms, (const NnFrame *)ctx->nn_misc.p, idx, rb,
+                                   (const SplitFrame *)ctx->frames.p, ctx->nn_splits, p.pruned ? group_lists(ctx, 0) : GroupLists{nullptr, nullptr, 0});
+        }
+        return ICPMI_OK;
+    }
+
+    // k_finish_step by the call's rule: the gated and robust kernels take the count from the partial rows, not from n
+    void launch_finish_step(const double *rows, int blocks, int final_pass, int *progress, int ticket)
+    {
+        switch (p.rule) {
+        case kRuleRobust: hipLaunchKernelGGL(k_finish_step_robust, dim3(1), dim3(kFinishThreads), 0, s, rows, blocks, st, hist, final_pass, progress, ticket); break;
+        case kRuleGate: hipLaunchKernelGGL(k_finish_step_gated, dim3(1), dim3(kFinishThreads), 0, s, rows, blocks, st, hist, final_pass, progress, ticket); break;
+        case kRuleNone: hipLaunchKernelGGL(k_finish_step, dim3(1), dim3(kFinishThreads), 0, s, rows, blocks, n, st, hist, final_pass, progress, ticket); break;
         }
     }
-    // before each k_row_list for pass `next`: where it stores the rows listed and, with the match margin, the rows certified
-    // for the coming pass (profiling)
-    unsigned *rows_count = nullptr, *cert_count = nullptr;
-    auto next_pass_stats = [&](int next) {
-        if (reuse) rows_count = ctx->opt.profile ? lr.stat_rows + std::min(next, kReuseStatPasses - 1) : nullptr;
-        if (margin) cert_count = ctx->opt.profile ? lr.stat_cert + std::min(next, kReuseStatPasses - 1) : nullptr;
-    };
-    // Lean passes (list_reuse.h, "lean passes"): once the passes list no row, k_row_list and the coarse kernel
-    // are no longer launched.  Single-GPU, ungated loops with list reuse, the fused finish kernel and a k_sum_groups launch,
-    // whose extra workgroup tells the host how many rows each pass wanted listed (WantPublish, kernels.h); everywhere else
-    // the launches are those of the form before.  The host learns the counts in the loop below, two passes late, where it
-    // waits for the progress word anyway: the launches are a function of the data, not of timing.
-    const bool lean_on = reuse && !sharded_run && !gate && fuse_finish_enabled() && sum_tree && nn_lean_enabled();
-    const int lean_from = lean_on ? nn_lean_from() : 0;
-    std::vector<unsigned> want_known;  // [p - 1]: the rows pass p wanted listed, as far as the host has read them
-    std::vector<char> lean_passes;     // [p - 1]: pass p was queued lean
-    bool lean_cur = false, lean_nxt = false; // the pass being queued, and the one after it
 
-    // current_source = source * R0^T + t0^T (icp.hpp:174-176)
-    if (n > 0 && !small) { // (an empty shard of a sharded run launches nothing over its rows; the small-cloud kernel moves them itself)
-        StageTimer t(ctx, ST_TRANSFORM);
-        hipLaunchKernelGGL(k_transform, dim3(std::min(2048, (n + 255) / 256)), dim3(256), 0, s, d_src, cur, n, st, 1, 0, src_perm);
-        if (bounded_loop) // the first pass's incumbents and bounds (and, culled engine, its group lists: set 0)
-            hipLaunchKernelGGL(k_nn_prebound1, dim3((n + kPreThreads - 1) / kPreThreads), dim3(kPreThreads), 0, s, (const double *)cur, n, (const double *)ctx->tgt_sorted.p,
-                               (const unsigned *)ctx->sort_keys.p + (size_t)m /* the sorted keys */,
-                               (const unsigned *)ctx->sort_keys.p + 3 * (size_t)m, m, ctx->nn_ms, (const NnFrame *)ctx->nn_misc.p, idx, rb,
-                               frames, splits, pruned ? group_lists(ctx, 0) : GroupLists{nullptr, nullptr, 0});
+    // Stage 5, one pass of a small cloud: the rows' work in one kernel (icp_small.h), then the step
+    int queue_pass_small(int final_pass, int *progress, int ticket)
+    {
+        {
+            Range range("icpmi:nn_search");
+            StageTimer t(ctx, ST_NN);
+            launch_by_rule(gate, k_icp_small, k_icp_small_gated, k_icp_small_robust, dim3(p.rblocks), dim3(kSmallThreads), s,
+                           small_first ? d_src : (const double *)cur, cur, n, (const IcpState *)st, small_first ? 1 : 0, (const uint4 *)ctx->bpack.p,
+                           (const SplitFrame *)ctx->frames.p, ctx->nn_splits, (const double *)ctx->tgt_sorted.p, (const double *)ctx->nrm_sorted.p,
+                           (const unsigned *)ctx->sort_keys.p + 3 * (size_t)m, m, ctx->nn_ms, d_tgt, (const double *)nrm, partials,
+                           (unsigned long long *)((char *)ctx->nn_misc.p + 128));
+            small_first = false;
+            ctx->prof.nn_pairs += (double)n * (double)m;
+            ctx->prof.small_launches += 1;
+            ctx->prof.nn_coarse_blocks += (int64_t)((n + kCoarseQueries - 1) / kCoarseQueries) * ctx->nn_splits; // the units the general path would run
+        }
+        Range range("icpmi:reduce_solve");
+        StageTimer t(ctx, ST_REDUCE);
+        launch_finish_step(partials, p.rblocks, final_pass, progress, ticket);
+        HIP_TRY(ctx, hipGetLastError());
+        return ICPMI_OK;
     }
 
-    bool small_first = true; // the small-cloud kernel's first pass applies the initial transform to the caller's rows
-    auto iteration = [&](int final_pass, int *progress, int ticket) -> int {
-        int r2;
-        if (small) {
+    // Lean passes: this pass (P, from 1) is what the tail of the pass before decided; the pass after it is decided now, from
+    // the two latest counts the queue loop has read: want(P - 3) and want(P - 2) (lean_next, loop_plan.h)
+    void decide_lean(int final_pass)
+    {
+        lean_cur = lean_nxt;
+        lean_nxt = lean_next(pass_no + 1, final_pass, p.lean_from, want_known.data(), (int)want_known.size());
+        lean_passes.push_back(lean_cur ? 1 : 0);
+        if (lean_cur) ctx->prof.nn_lean_passes += 1;
+    }
+
+    // ... its search: the MFMA engines' resolve leaves the partial rows too (LoopPlan::fused)
+    int pass_search()
+    {
+        if (n <= 0) return ICPMI_OK;
+        if (!p.fused) return launch_nn(ctx, cur, n, d_tgt, m, idx, nullptr, st);
+        // (bounded: incumbents in idx, bounds in place -- from k_nn_prebound1 or the kernel that moved the rows)
+        const NnPass pass{p.pruned ? pass_no : -1, p.bounded, pass_list, lean_cur, p.margin};
+        return launch_nn_mfma(ctx, cur, n, m, idx, nullptr, st, d_tgt, nrm, partials, pass);
+    }
+
+    // ... the partial rows of an unfused pass (k_reduce*) and, of very many rows, their sums in groups
+    void pass_sums()
+    {
+        if (!p.fused)
+            launch_by_rule(gate, k_reduce_rule<RuleNone>, k_reduce_rule<RuleGate, double>, k_reduce_rule<RuleRobust, double, int, double>, dim3(p.rblocks), dim3(256), s, (const double *)cur, n, d_tgt, m,
+                           (const double *)nrm, (const int *)idx, partials, (const IcpState *)st);
+        if (p.sum_tree && p.lean_on) { // (+ the workgroup that counts the rows this pass wanted listed; pass_no - 1: this pass, from 0)
+            const int here = pass_no - 1, at = std::min(here, kReuseStatPasses - 1);
+            const bool stats = lean_cur && ctx->opt.profile;
+            const WantPublish wp{ctx->d_want + here % kFlagRing, (unsigned)(here + 1), n, here == 0, (const unsigned long long *)lr.mask,
+                                 p.margin ? (const unsigned long long *)lr.cert : nullptr, stats ? lr.stat_rows + at : nullptr,
+                                 stats && p.margin ? lr.stat_cert + at : nullptr};
+            hipLaunchKernelGGL(k_sum_groups, dim3((p.rblocks2 + 7) / 8 + 1), dim3(256), 0, s, (const double *)partials, p.rblocks,
+                               partials + kSumsStride * (size_t)p.rblocks, (const IcpState *)st, wp);
+        } else if (p.sum_tree)
+            hipLaunchKernelGGL(k_sum_groups, dim3((p.rblocks2 + 7) / 8), dim3(256), 0, s, (const double *)partials, p.rblocks,
+                               partials + kSumsStride * (size_t)p.rblocks, (const IcpState *)st, WantPublish{});
+    }
+
+    // ... the final sum, the exchange of a sharded run, the step and the rows' move (with their bounds, RowBounds, and the culled
+    // engine's group lists of the coming pass: set pass_no & 1); behind them the coming pass's list of rows
+    int pass_step_and_move(int final_pass, int *progress, int ticket)
+    {
+        const bool step_moves = fuse_step(p, n, final_pass), finish_moves = fuse_finish(p, n, final_pass);
+        const SplitFrame *frames = (const SplitFrame *)ctx->frames.p;
+        const int splits = ctx->nn_splits;
+        IcpState *other = st == ctx->d_state ? ctx->d_state + 1 : ctx->d_state; // (the fused kernels write the other state buffer)
+        if (p.sharded) {
+            int rc;
+            hipLaunchKernelGGL(k_finish, dim3(1), dim3(kFinishThreads), 0, s, fin_rows, p.fin_blocks, n, st);
             {
-                Range range("icpmi:nn_search");
-                StageTimer t(ctx, ST_NN);
-#define ICPMI_SMALL_ARGS                                                                                                        \
-    small_first ? d_src : (const double *)cur, cur, n, (const IcpState *)st, small_first ? 1 : 0, (const uint4 *)ctx->bpack.p,    \
-        frames, splits, (const double *)ctx->tgt_sorted.p, (const double *)ctx->nrm_sorted.p,                                       \
-        (const unsigned *)ctx->sort_keys.p + 3 * (size_t)m, m, ctx->nn_ms, d_tgt, (const double *)nrm, partials,                    \
-        (unsigned long long *)((char *)ctx->nn_misc.p + 128)
-                if (gate && gate->kind) hipLaunchKernelGGL(k_icp_small_robust, dim3(rblocks), dim3(kSmallThreads), 0, s, ICPMI_SMALL_ARGS, gate->g2, (int)gate->kind, gate->ks);
-                else if (gate) hipLaunchKernelGGL(k_icp_small_gated, dim3(rblocks), dim3(kSmallThreads), 0, s, ICPMI_SMALL_ARGS, gate->g2);
-                else hipLaunchKernelGGL(k_icp_small, dim3(rblocks), dim3(kSmallThreads), 0, s, ICPMI_SMALL_ARGS);
-#undef ICPMI_SMALL_ARGS
-                small_first = false;
-                ctx->prof.nn_pairs += (double)n * (double)m;
-                ctx->prof.small_launches += 1;
-                ctx->prof.nn_coarse_blocks += (int64_t)((n + kCoarseQueries - 1) / kCoarseQueries) * splits; // the units the general path would run
+                StageTimer tx(ctx, ST_EXCHANGE); // the per-pass all-reduce alone (30 doubles; RCCL on the library's stream)
+                if ((rc = exchange_allreduce(ctx, st->sums, kNumExchanged))) return rc;
             }
-            Range range("icpmi:reduce_solve");
-            StageTimer t(ctx, ST_REDUCE);
-            if (gate && gate->kind) hipLaunchKernelGGL(k_finish_step_robust, dim3(1), dim3(kFinishThreads), 0, s, partials, rblocks, st, hist, final_pass, progress, ticket);
-            else if (gate) hipLaunchKernelGGL(k_finish_step_gated, dim3(1), dim3(kFinishThreads), 0, s, partials, rblocks, st, hist, final_pass, progress, ticket);
-            else hipLaunchKernelGGL(k_finish_step, dim3(1), dim3(kFinishThreads), 0, s, partials, rblocks, n, st, hist, final_pass, progress, ticket);
-            HIP_TRY(ctx, hipGetLastError());
-            return ICPMI_OK;
-        }
-        const bool fuse_step = sharded && n > 0 && !final_pass;
-        const bool fuse_finish = !sharded && n > 0 && !final_pass && !gate && fuse_finish_enabled();
-        if (lean_on) {
-            // this pass (P, from 1) is what the tail of the pass before decided; the pass after it is decided now, from the
-            // two latest counts the loop below has read: want(P - 3) and want(P - 2) (list_reuse.h)
-            const int P = pass_no + 1;
-            lean_cur = lean_nxt;
-            lean_nxt = false;
-            if (!final_pass) {
-                if (lean_from) lean_nxt = P + 1 >= lean_from;
-                else if (P >= 6 && (int)want_known.size() >= P - 2) lean_nxt = lean_pass(P + 1, want_known[P - 4], want_known[P - 3]);
+            if (step_moves) { // step + pose update of this rank's rows in one launch, into the other state buffer
+                if (p.pruned)
+                    hipLaunchKernelGGL(k_step_transform_cull, dim3(std::min(2048, (n + 255) / 256)), dim3(256), 0, s,
+                                       (const double *)cur, cur, n, (const IcpState *)st, other, hist, progress, ticket,
+                                       ctx->n_ranks, rb, frames, splits, group_lists(ctx, pass_no & 1));
+                else
+                    hipLaunchKernelGGL(k_step_transform, dim3(std::min(2048, (n + 255) / 256)), dim3(256), 0, s,
+                                       (const double *)cur, cur, n, (const IcpState *)st, other, hist, progress, ticket,
+                                       ctx->n_ranks, rb);
+                st = other;
+            } else {
+                hipLaunchKernelGGL(k_step, dim3(1), dim3(64), 0, s, st, hist, final_pass, progress, ticket,
+                                   ctx->n_ranks);
             }
-            lean_passes.push_back(lean_cur ? 1 : 0);
-            if (lean_cur) ctx->prof.nn_lean_passes += 1;
+        } else if (finish_moves) { // final sum + step + pose update of the rows in one launch
+            if (p.pruned)
+                hipLaunchKernelGGL(k_finish_step_transform_cull, dim3(finish_transform_blocks(n)), dim3(kFinishThreads), 0, s,
+                                   fin_rows, p.fin_blocks, n, (const double *)cur, cur, n, (const IcpState *)st, other,
+                                   hist, progress, ticket, rb, frames, splits, group_lists(ctx, pass_no & 1));
+            else
+                hipLaunchKernelGGL(k_finish_step_transform, dim3(finish_transform_blocks(n)), dim3(kFinishThreads), 0, s,
+                                   fin_rows, p.fin_blocks, n, (const double *)cur, cur, n,
+                                   (const IcpState *)st, other, hist, progress, ticket, rb);
+            st = other;
+        } else {
+            launch_finish_step(fin_rows, p.fin_blocks, final_pass, progress, ticket);
         }
-        if (n > 0 && fused) {
-            if ((r2 = launch_nn_mfma(ctx, cur, n, m, idx, nullptr, st, d_tgt, nrm, partials,
-                                     pruned ? pass_no : -1, bounded_loop /* incumbents in idx, bounds in place: from k_nn_prebound1 or the kernel that moved the rows */,
-                                     pass_list, lean_cur, margin))) return r2;
+        return ICPMI_OK;
+    }
+
+    // Stage 5, one pass of the general kernels: search, sums, step and move
+    int queue_pass_general(int final_pass, int *progress, int ticket)
+    {
+        int rc;
+        if (p.lean_on) decide_lean(final_pass);
+        if ((rc = pass_search())) return rc;
+        if (n > 0 && p.fused) {
             ++pass_no;
-            if (!final_pass) next_pass_stats(pass_no);
-            pass_list = reuse && !final_pass;
-        } else if (n > 0) {
-            if ((r2 = launch_nn(ctx, cur, n, d_tgt, m, idx, nullptr, st))) return r2;
+            if (!final_pass) {
+                const int at = std::min(pass_no, kReuseStatPasses - 1);
+                if (p.reuse) rows_count = ctx->opt.profile ? lr.stat_rows + at : nullptr;
+                if (p.margin) cert_count = ctx->opt.profile ? lr.stat_cert + at : nullptr;
+            }
+            pass_list = p.reuse && !final_pass;
         }
         {
             Range range("icpmi:reduce_solve");
             StageTimer t(ctx, ST_REDUCE);
-            if (gate && gate->kind)
-                hipLaunchKernelGGL(k_reduce_robust, dim3(rblocks), dim3(256), 0, s, cur, n, d_tgt, m, nrm, idx, partials,
-                                   st, gate->g2, (int)gate->kind, gate->ks);
-            else if (gate)
-                hipLaunchKernelGGL(k_reduce_gated, dim3(rblocks), dim3(256), 0, s, cur, n, d_tgt, m, nrm, idx, partials,
-                                   st, gate->g2);
-            else if (!fused)
-                hipLaunchKernelGGL(k_reduce, dim3(rblocks), dim3(256), 0, s, cur, n, d_tgt, m, nrm, idx, partials,
-                                   st);
-            if (sum_tree && lean_on) { // (+ the workgroup that counts the rows this pass wanted listed; pass_no - 1: this pass, from 0)
-                const int here = pass_no - 1, at = std::min(here, kReuseStatPasses - 1);
-                const bool stats = lean_cur && ctx->opt.profile;
-                const WantPublish wp{ctx->d_want + here % kFlagRing, (unsigned)(here + 1), n, here == 0, (const unsigned long long *)lr.mask,
-                                     margin ? (const unsigned long long *)lr.cert : nullptr, stats ? lr.stat_rows + at : nullptr,
-                                     stats && margin ? lr.stat_cert + at : nullptr};
-                hipLaunchKernelGGL(k_sum_groups, dim3((rblocks2 + 7) / 8 + 1), dim3(256), 0, s, (const double *)partials, rblocks,
-                                   partials + kSumsStride * (size_t)rblocks, (const IcpState *)st, wp);
-            } else if (sum_tree)
-                hipLaunchKernelGGL(k_sum_groups, dim3((rblocks2 + 7) / 8), dim3(256), 0, s, (const double *)partials, rblocks,
-                                   partials + kSumsStride * (size_t)rblocks, (const IcpState *)st, WantPublish{});
-            if (sharded) {
-                hipLaunchKernelGGL(k_finish, dim3(1), dim3(kFinishThreads), 0, s, fin_rows, fin_blocks, n,
-                                   st);
-                {
-                    StageTimer tx(ctx, ST_EXCHANGE); // the per-pass all-reduce alone (30 doubles; RCCL on the library's stream)
-                    if ((r2 = exchange_allreduce(ctx, st->sums, kNumExchanged))) return r2;
-                }
-                if (fuse_step) { // step + pose update of this rank's rows in one launch, into the other state buffer
-                    IcpState *other = st == ctx->d_state ? ctx->d_state + 1 : ctx->d_state;
-                    if (pruned) // (+ the group lists of the coming pass: set pass_no & 1)
-                        hipLaunchKernelGGL(k_step_transform_cull, dim3(std::min(2048, (n + 255) / 256)), dim3(256), 0, s,
-                                           (const double *)cur, cur, n, (const IcpState *)st, other, hist, progress, ticket,
-                                           ctx->n_ranks, rb, frames, splits, group_lists(ctx, pass_no & 1));
-                    else
-                        hipLaunchKernelGGL(k_step_transform, dim3(std::min(2048, (n + 255) / 256)), dim3(256), 0, s,
-                                           (const double *)cur, cur, n, (const IcpState *)st, other, hist, progress, ticket,
-                                           ctx->n_ranks, rb);
-                    st = other;
-                } else {
-                    hipLaunchKernelGGL(k_step, dim3(1), dim3(64), 0, s, st, hist, final_pass, progress, ticket,
-                                       ctx->n_ranks);
-                }
-            } else if (fuse_finish) { // final sum + step + pose update of the rows in one launch
-                IcpState *other = st == ctx->d_state ? ctx->d_state + 1 : ctx->d_state;
-                if (pruned) // (+ the group lists of the coming pass: set pass_no & 1)
-                    hipLaunchKernelGGL(k_finish_step_transform_cull, dim3(finish_transform_blocks(n)), dim3(kFinishThreads), 0, s,
-                                       fin_rows, fin_blocks, n, (const double *)cur, cur, n, (const IcpState *)st, other,
-                                       hist, progress, ticket, rb, frames, splits, group_lists(ctx, pass_no & 1));
-                else
-                    hipLaunchKernelGGL(k_finish_step_transform, dim3(finish_transform_blocks(n)), dim3(kFinishThreads), 0, s,
-                                       fin_rows, fin_blocks, n, (const double *)cur, cur, n,
-                                       (const IcpState *)st, other, hist, progress, ticket, rb);
-                st = other;
-            } else if (gate && gate->kind) {
-                hipLaunchKernelGGL(k_finish_step_robust, dim3(1), dim3(kFinishThreads), 0, s, fin_rows, fin_blocks,
-                                   st, hist, final_pass, progress, ticket);
-            } else if (gate) {
-                hipLaunchKernelGGL(k_finish_step_gated, dim3(1), dim3(kFinishThreads), 0, s, fin_rows, fin_blocks,
-                                   st, hist, final_pass, progress, ticket);
-            } else {
-                hipLaunchKernelGGL(k_finish_step, dim3(1), dim3(kFinishThreads), 0, s, fin_rows, fin_blocks, n,
-                                   st, hist, final_pass, progress, ticket);
-            }
+            pass_sums();
+            if ((rc = pass_step_and_move(final_pass, progress, ticket))) return rc;
         }
-        if (!final_pass && n > 0 && !fuse_step && !fuse_finish) {
+        if (!final_pass && n > 0 && !fuse_step(p, n, final_pass) && !fuse_finish(p, n, final_pass)) {
             Range range("icpmi:transform");
             StageTimer t(ctx, ST_TRANSFORM);
-            if (pruned) // (ICPMI_FUSE_FINISH=0 only: + the rows' bounds and the group lists of the coming pass, set pass_no & 1)
+            if (p.pruned) // (ICPMI_FUSE_FINISH=0 only: + the rows' bounds and the group lists of the coming pass, set pass_no & 1)
                 hipLaunchKernelGGL(k_transform_cull, dim3((n + 255) / 256), dim3(256), 0, s, (const double *)cur, (const unsigned *)nullptr,
-                                   cur, n, (const IcpState *)st, 0, 1, rb, frames, splits, group_lists(ctx, pass_no & 1));
+                                   cur, n, (const IcpState *)st, 0, 1, rb, (const SplitFrame *)ctx->frames.p, ctx->nn_splits, group_lists(ctx, pass_no & 1));
             else
                 hipLaunchKernelGGL(k_transform, dim3(std::min(2048, (n + 255) / 256)), dim3(256), 0, s,
                                    cur, cur, n, st, 0, 1, (const unsigned *)nullptr, rb);
@@ -1527,179 +1518,210 @@ int align_device(icpmi_ctx *ctx, const double *d_src, int64_t n_src64, const dou
         if (pass_list && !lean_nxt) // the rows just moved left their "listed again" words: the coming pass's list of rows
             hipLaunchKernelGGL(k_row_list, dim3(((n + 63) / 64 + kRowListThreads - 1) / kRowListThreads), dim3(kRowListThreads), 0, s,
                                (const unsigned long long *)lr.mask, n, lr.list, (const IcpState *)st,
-                               (const unsigned long long *)(margin ? lr.cert : nullptr), cert_count, rows_count);
+                               (const unsigned long long *)(p.margin ? lr.cert : nullptr), cert_count, rows_count);
         return ICPMI_OK;
-    };
+    }
 
-    Range range_loop("icpmi:icp_loop");
-    StageTimer *t_loop = new StageTimer(ctx, ST_LOOP);
-    struct Closer2 { StageTimer *&p; ~Closer2() { delete p; p = nullptr; } } close_loop{t_loop};
-    for (int i = 0; i < kFlagRing; ++i) ctx->h_flags[i] = 0, ctx->h_want[i] = 0ull;
-    bool ended_early = false; // the host has SEEN the device leave the loop on a convergence test
+    int queue_pass(int final_pass, int *progress, int ticket) // Stage 5, one pass
+    {
+        return p.small ? queue_pass_small(final_pass, progress, ticket) : queue_pass_general(final_pass, progress, ticket);
+    }
+
+    // Stage 5: the queue loop.  The host runs kLag passes ahead of the device's progress words.
     // `after_first` (may be null): called once the first iterations are queued and before the host first waits for
     // the device -- what it queues (on another stream) costs the host its launch time while the device is busy
-    bool after_first_done = after_first == nullptr;
-    for (int it = 0; it < max_it; ++it) {
-        if (it >= kLag && !after_first_done) {
-            after_first_done = true;
-            (void)after_first(ctx); // (a failure there only means the next call prepares its target itself)
-        }
-        if (it >= kLag) {
-            // wait until iteration it - kLag has reported; stop queueing once the loop has ended
-            const int slot = (it - kLag) % kFlagRing, want = it - kLag + 1;
-            volatile int32_t *flag = &ctx->h_flags[slot];
-            int32_t v = *flag;
-            for (long spin = 0; (v >> 1) != want; ++spin) {
-                if (spin > 2000000) { // ~seconds: something is wrong with the stream, find out what
-                    HIP_TRY(ctx, hipStreamSynchronize(s));
-                    v = *flag;
-                    if ((v >> 1) != want) return fail(ctx, ICPMI_ERR_HIP, "device progress word never arrived");
+    int queue_loop(int (*after_first)(icpmi_ctx *))
+    {
+        int rc;
+        range_loop.emplace("icpmi:icp_loop");
+        t_loop.emplace(ctx, ST_LOOP);
+        for (int i = 0; i < kFlagRing; ++i) ctx->h_flags[i] = 0, ctx->h_want[i] = 0ull;
+        bool after_first_done = after_first == nullptr;
+        for (int it = 0; it < cfg->max_iterations; ++it) {
+            if (it >= kLag && !after_first_done) {
+                after_first_done = true;
+                (void)after_first(ctx); // (a failure there only means the next call prepares its target itself)
+            }
+            if (it >= kLag) {
+                // wait until iteration it - kLag has reported; stop queueing once the loop has ended
+                const int slot = (it - kLag) % kFlagRing, want = it - kLag + 1;
+                int32_t v;
+                if ((rc = await_word(ctx, &ctx->h_flags[slot], want, [](int32_t x) { return (int)(x >> 1); },
+                                     "device progress word never arrived", &v)))
+                    return rc;
+                if (v & 1) { // loop already left on the device
+                    ended_early = true;
                     break;
                 }
-                if ((spin & 63) == 63) sched_yield();
-                v = *flag;
-            }
-            if (v & 1) { // loop already left on the device
-                ended_early = true;
-                break;
-            }
-            if (lean_on) {
-                // the rows that iteration's pass wanted listed: its k_sum_groups ran in front of the kernel whose progress word
-                // has just been read, so the word is there or on its way (the same bounded spin)
-                volatile unsigned long long *word = &ctx->h_want[slot];
-                unsigned long long w = *word;
-                for (long spin = 0; (int)(w >> 32) != want; ++spin) {
-                    if (spin > 2000000) {
-                        HIP_TRY(ctx, hipStreamSynchronize(s));
-                        w = *word;
-                        if ((int)(w >> 32) != want) return fail(ctx, ICPMI_ERR_HIP, "device row count word never arrived");
-                        break;
-                    }
-                    if ((spin & 63) == 63) sched_yield();
-                    w = *word;
+                if (p.lean_on) {
+                    // the rows that iteration's pass wanted listed: its k_sum_groups ran in front of the kernel whose progress word
+                    // has just been read, so the word is there or on its way (the same bounded spin)
+                    unsigned long long w;
+                    if ((rc = await_word(ctx, &ctx->h_want[slot], want, [](unsigned long long x) { return (int)(x >> 32); },
+                                         "device row count word never arrived", &w)))
+                        return rc;
+                    want_known.push_back((unsigned)(w & 0xFFFFFFFFull));
                 }
-                want_known.push_back((unsigned)(w & 0xFFFFFFFFull));
+            }
+            if ((rc = queue_pass(0, ctx->d_flags + it % kFlagRing, it + 1))) return rc;
+        }
+        // post-loop evaluation (icp.hpp:235-252): a full pass after exhaustion; after a convergence break it restates
+        // the last error, which the step that broke the loop has already entered (step_update): nothing to queue then.
+        // (Single-GPU loops only: in a sharded run `done` is agreed one exchange later, k_step.)
+        if (!(ended_early && !p.sharded) && (rc = queue_pass(1, nullptr, 0))) return rc;
+        if (!after_first_done) (void)after_first(ctx);
+        t_loop.reset();
+        t_total.reset();
+        return ICPMI_OK;
+    }
+
+    // Stage 6: state and history come back behind ONE wait (the history through the pinned staging area: a
+    // second, blocking copy after the wait was one more host round trip per call)
+    // `before_wait` (may be null): called once everything of the registration, the copies of its results
+    // included, is queued and an event behind them recorded -- what it queues runs while the host waits
+    // for that event only (icpmi_stream_push prepares the next frame's target there).
+    int results_back(double *error_history, int32_t history_cap, int (*before_wait)(icpmi_ctx *))
+    {
+        const int hcopy = std::min(max_hist, history_cap);
+        if ((int)ctx->h_hist_cap < hcopy) {
+            if (ctx->h_hist) (void)hipHostFree(ctx->h_hist);
+            ctx->h_hist = nullptr;
+            ctx->h_hist_cap = 0;
+            HIP_TRY(ctx, hipHostMalloc((void **)&ctx->h_hist, sizeof(double) * (size_t)(hcopy + 64), hipHostMallocDefault));
+            ctx->h_hist_cap = (size_t)hcopy + 64;
+        }
+        HIP_TRY(ctx, hipMemcpyAsync(hs, st, sizeof(IcpState), hipMemcpyDeviceToHost, s));
+        if (hcopy > 0) HIP_TRY(ctx, hipMemcpyAsync(ctx->h_hist, hist, sizeof(double) * (size_t)hcopy, hipMemcpyDeviceToHost, s));
+        // profiling: the resolve's counters come back behind the same wait, and the events are read when somebody asks
+        // for the profile (icpmi_get_profile) -- a blocking copy and a dozen hipEventElapsedTime calls inside every
+        // call were ~0.1 ms of host time in a 9 ms C3 call, charged to the very thing they measure
+        counters_back = ctx->opt.profile && ctx->nn_engine == ICPMI_SEARCH_MFMA_BF16 && ctx->nn_misc.p;
+        if (counters_back) {
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->h_cnt, (char *)ctx->nn_misc.p + 128, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+            HIP_TRY(ctx, hipMemsetAsync((char *)ctx->nn_misc.p + 128, 0, 3 * sizeof(unsigned long long), s));
+            ctx->h_cnt[3] = ctx->h_cnt[4] = 0;
+            if (p.pruned) // (row group, split) pairs run / of all passes: cleared with the counters at the head of the next call
+                HIP_TRY(ctx, hipMemcpyAsync(ctx->h_cnt + 3, group_stats(ctx), 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+        }
+        // ... and so do list reuse's per-pass statistics (the arrays lie one behind the other: one copy into pinned memory,
+        // where a blocking copy after the wait cost the caller some 15 us)
+        stats_back = p.reuse && ctx->opt.profile && pass_no > 0;
+        stat_passes = std::min(pass_no, kReuseStatPasses);
+        if (stats_back)
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->h_stat, lr.stat_rows, sizeof(unsigned) * ((size_t)(p.margin ? 1 : 0) * kReuseStatPasses + stat_passes),
+                                        hipMemcpyDeviceToHost, s));
+        if (before_wait && ctx->opt.profile == 0) {
+            // the results are waited for through an event; what before_wait queues behind it keeps the device busy
+            // while the caller digests them (with profiling on, the stage timers want the whole stream drained)
+            if (!ctx->result_ready) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->result_ready, hipEventDisableTiming));
+            HIP_TRY(ctx, hipEventRecord(ctx->result_ready, s));
+            {   // (a failure there only means the next call prepares its target itself: it must not leave its text in
+                // the error string of a call that succeeded)
+                const std::string keep = ctx->err;
+                if (before_wait(ctx) != ICPMI_OK) ctx->err = keep;
+                ctx->trailing_work = true; // kernels of the NEXT call's target are queued behind this call's results
+            }
+            HIP_TRY(ctx, hipEventSynchronize(ctx->result_ready));
+        } else {
+            HIP_TRY(ctx, hipStreamSynchronize(s));
+        }
+        HIP_TRY(ctx, hipGetLastError());
+        hl = std::min(hs->hist_len, max_hist);
+        if (hl > 0) memcpy(error_history, ctx->h_hist, sizeof(double) * (size_t)std::min(hl, history_cap));
+        return ICPMI_OK;
+    }
+
+    // Stage 7: the counters and per-pass statistics that came back, into the profile
+    void account_profile()
+    {
+        if (counters_back) {
+            ctx->prof.nn_recheck_queries += (int64_t)ctx->h_cnt[0];
+            ctx->prof.nn_fallback_queries += (int64_t)ctx->h_cnt[1];
+            ctx->prof.nn_pruned_blocks += (int64_t)ctx->h_cnt[2];
+            ctx->prof.nn_group_pairs_run += (int64_t)ctx->h_cnt[3];
+            ctx->prof.nn_group_pairs += (int64_t)ctx->h_cnt[4];
+            // (the older pair of fields, in 512-row units like the all-pairs engine's)
+            ctx->prof.nn_pruned_blocks += (int64_t)(ctx->h_cnt[4] - ctx->h_cnt[3]) / (kCoarseQueries / kGroupRows); // (16 tiles to a 512-row block)
+        }
+        ctx->reuse_rows.clear();
+        ctx->reuse_blocks.clear();
+        ctx->margin_rows.clear();
+        if (stats_back) {
+            // list reuse, per pass: the rows listed (the first pass lists all) and the workgroup columns of the coarse pass that
+            // ran, ceil(rows / rows per workgroup) -- none in a lean pass, which has no coarse launch; their pairs are the pairs
+            // searched, and a pass none of which ran is a skipped coarse launch
+            const int np = stat_passes;
+            const unsigned *stat = ctx->h_stat;
+            const int per = coarse_half_units(ctx->cu_count, n, ctx->nn_splits) ? kCoarseQueries / kCoarseQT : kCoarseQueries;
+            ctx->reuse_rows.assign(stat, stat + np);
+            ctx->reuse_rows[0] = (unsigned)n;
+            ctx->reuse_blocks.resize((size_t)np);
+            for (int q = 0; q < np; ++q) {
+                const bool lean = q < (int)lean_passes.size() && lean_passes[q];
+                ctx->reuse_blocks[q] = lean ? 0u : (unsigned)(((long)ctx->reuse_rows[q] + per - 1) / per);
+            }
+            if (p.margin) { // the match margin, per pass: the rows certified (the first pass certifies none)
+                ctx->margin_rows.assign(stat + kReuseStatPasses, stat + kReuseStatPasses + np);
+                for (int q = 0; q < np; ++q) ctx->prof.nn_rows_certified += ctx->margin_rows[q];
+            }
+            for (int q = 0; q < np; ++q) {
+                ctx->prof.nn_rows_listed += ctx->reuse_rows[q];
+                if (q > 0) ctx->prof.nn_pairs += std::min((double)n, (double)ctx->reuse_blocks[q] * per) * (double)m;
+                if (q > 0 && ctx->reuse_blocks[q] == 0) ctx->prof.nn_coarse_skipped += 1;
             }
         }
-        if ((rc = iteration(0, ctx->d_flags + it % kFlagRing, it + 1))) return rc;
-    }
-    // post-loop evaluation (icp.hpp:235-252): a full pass after exhaustion; after a convergence break it restates
-    // the last error, which the step that broke the loop has already entered (step_update): nothing to queue then.
-    // (Single-GPU loops only: in a sharded run `done` is agreed one exchange later, k_step.)
-    if (!(ended_early && !sharded) && (rc = iteration(1, nullptr, 0))) return rc;
-    if (!after_first_done) (void)after_first(ctx);
-    delete t_loop;
-    t_loop = nullptr;
-    delete t_total;
-    t_total = nullptr;
-
-    // state and history come back behind ONE wait (the history through the pinned staging area: a
-    // second, blocking copy after the wait was one more host round trip per call)
-    const int hcopy = std::min(max_hist, history_cap);
-    if ((int)ctx->h_hist_cap < hcopy) {
-        if (ctx->h_hist) (void)hipHostFree(ctx->h_hist);
-        ctx->h_hist = nullptr;
-        ctx->h_hist_cap = 0;
-        HIP_TRY(ctx, hipHostMalloc((void **)&ctx->h_hist, sizeof(double) * (size_t)(hcopy + 64), hipHostMallocDefault));
-        ctx->h_hist_cap = (size_t)hcopy + 64;
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(hs, st, sizeof(IcpState), hipMemcpyDeviceToHost, s));
-    if (hcopy > 0) HIP_TRY(ctx, hipMemcpyAsync(ctx->h_hist, hist, sizeof(double) * (size_t)hcopy, hipMemcpyDeviceToHost, s));
-    // profiling: the resolve's counters come back behind the same wait, and the events are read when somebody asks
-    // for the profile (icpmi_get_profile) -- a blocking copy and a dozen hipEventElapsedTime calls inside every
-    // call were ~0.1 ms of host time in a 9 ms C3 call, charged to the very thing they measure
-    const bool counters_back = ctx->opt.profile && ctx->nn_engine == ICPMI_SEARCH_MFMA_BF16 && ctx->nn_misc.p;
-    if (counters_back) {
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->h_cnt, (char *)ctx->nn_misc.p + 128, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-        HIP_TRY(ctx, hipMemsetAsync((char *)ctx->nn_misc.p + 128, 0, 3 * sizeof(unsigned long long), s));
-        ctx->h_cnt[3] = ctx->h_cnt[4] = 0;
-        if (pruned) // (row group, split) pairs run / of all passes: cleared with the counters at the head of the next call
-            HIP_TRY(ctx, hipMemcpyAsync(ctx->h_cnt + 3, group_stats(ctx), 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    }
-    // ... and so do list reuse's per-pass statistics (the arrays lie one behind the other: one copy into pinned memory,
-    // where a blocking copy after the wait cost the caller some 15 us)
-    const bool stats_back = reuse && ctx->opt.profile && pass_no > 0;
-    const int stat_passes = std::min(pass_no, kReuseStatPasses);
-    if (stats_back)
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->h_stat, lr.stat_rows, sizeof(unsigned) * ((size_t)(margin ? 1 : 0) * kReuseStatPasses + stat_passes),
-                                    hipMemcpyDeviceToHost, s));
-    if (before_wait && ctx->opt.profile == 0) {
-        // the results are waited for through an event; what before_wait queues behind it keeps the device busy
-        // while the caller digests them (with profiling on, the stage timers want the whole stream drained)
-        if (!ctx->result_ready) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->result_ready, hipEventDisableTiming));
-        HIP_TRY(ctx, hipEventRecord(ctx->result_ready, s));
-        {   // (a failure there only means the next call prepares its target itself: it must not leave its text in
-            // the error string of a call that succeeded)
-            const std::string keep = ctx->err;
-            if (before_wait(ctx) != ICPMI_OK) ctx->err = keep;
-            ctx->trailing_work = true; // kernels of the NEXT call's target are queued behind this call's results
-        }
-        HIP_TRY(ctx, hipEventSynchronize(ctx->result_ready));
-    } else {
-        HIP_TRY(ctx, hipStreamSynchronize(s));
-    }
-    HIP_TRY(ctx, hipGetLastError());
-    const int hl = std::min(hs->hist_len, max_hist);
-    if (hl > 0) memcpy(error_history, ctx->h_hist, sizeof(double) * (size_t)std::min(hl, history_cap));
-    if (counters_back) {
-        ctx->prof.nn_recheck_queries += (int64_t)ctx->h_cnt[0];
-        ctx->prof.nn_fallback_queries += (int64_t)ctx->h_cnt[1];
-        ctx->prof.nn_pruned_blocks += (int64_t)ctx->h_cnt[2];
-        ctx->prof.nn_group_pairs_run += (int64_t)ctx->h_cnt[3];
-        ctx->prof.nn_group_pairs += (int64_t)ctx->h_cnt[4];
-        // (the older pair of fields, in 512-row units like the all-pairs engine's)
-        ctx->prof.nn_pruned_blocks += (int64_t)(ctx->h_cnt[4] - ctx->h_cnt[3]) / (kCoarseQueries / kGroupRows); // (16 tiles to a 512-row block)
-    }
-    ctx->reuse_rows.clear();
-    ctx->reuse_blocks.clear();
-    ctx->margin_rows.clear();
-    if (stats_back) {
-        // list reuse, per pass: the rows listed (the first pass lists all) and the workgroup columns of the coarse pass that
-        // ran, ceil(rows / rows per workgroup) -- none in a lean pass, which has no coarse launch; their pairs are the pairs
-        // searched, and a pass none of which ran is a skipped coarse launch
-        const int np = stat_passes;
-        const unsigned *stat = ctx->h_stat;
-        const int per = coarse_half_units(ctx, n, ctx->nn_splits) ? kCoarseQueries / kCoarseQT : kCoarseQueries;
-        ctx->reuse_rows.assign(stat, stat + np);
-        ctx->reuse_rows[0] = (unsigned)n;
-        ctx->reuse_blocks.resize((size_t)np);
-        for (int p = 0; p < np; ++p) {
-            const bool lean = p < (int)lean_passes.size() && lean_passes[p];
-            ctx->reuse_blocks[p] = lean ? 0u : (unsigned)(((long)ctx->reuse_rows[p] + per - 1) / per);
-        }
-        if (margin) { // the match margin, per pass: the rows certified (the first pass certifies none)
-            ctx->margin_rows.assign(stat + kReuseStatPasses, stat + kReuseStatPasses + np);
-            for (int p = 0; p < np; ++p) ctx->prof.nn_rows_certified += ctx->margin_rows[p];
-        }
-        for (int p = 0; p < np; ++p) {
-            ctx->prof.nn_rows_listed += ctx->reuse_rows[p];
-            if (p > 0) ctx->prof.nn_pairs += std::min((double)n, (double)ctx->reuse_blocks[p] * per) * (double)m;
-            if (p > 0 && ctx->reuse_blocks[p] == 0) ctx->prof.nn_coarse_skipped += 1;
-        }
-    }
-    if (ctx->ev_used > 4096) harvest_profile(ctx); // (otherwise when the profile is asked for)
-    if (hs->error)
-        return fail(ctx, ICPMI_ERR_RCCL, "the ranks of this sharded run disagreed on the end of the loop "
-                                         "(different icpmi_config per rank, or an exchange that is not bit-identical on every rank)");
-    ctx->loop_rows = n;
-    ctx->loop_idx_valid = n > 0 && !small;
-    ctx->loop_sorted = pruned || sorted_rows_loop;
-    if (gate) {
-        // A gated loop's idx holds matches of rows the gate dropped as well: loop_rows stays -1 ("no registration's rows
-        // are held"), so icpmi_debug_loop_rows refuses every row count and nothing reads them as an ungated loop's.
-        ctx->loop_rows = -1;
-        ctx->loop_idx_valid = false;
-        gate->pairs = (int64_t)hs->sums[gate->kind ? 29 : 28];
-        gate->weight_sum = gate->kind ? hs->sums[28] : 0.0;
+        if (ctx->ev_used > 4096) harvest_profile(ctx); // (otherwise when the profile is asked for)
     }
 
-    memcpy(result->transformation, hs->total, sizeof(double) * 16); // icp.hpp:254
-    result->converged = hs->converged;
-    result->num_iterations = hs->hist_len - 1;                      // icp.hpp:255
-    result->final_error = hs->final_error;
-    result->history_len = hl;
-    result->loop_iterations = hs->loops;
-    return ICPMI_OK;
+    // Stage 8: the caller's result, what the context remembers of the loop's rows, and the rule's own outputs
+    int fill_result(icpmi_result *result)
+    {
+        if (hs->error)
+            return fail(ctx, ICPMI_ERR_RCCL, "the ranks of this sharded run disagreed on the end of the loop "
+                                             "(different icpmi_config per rank, or an exchange that is not bit-identical on every rank)");
+        ctx->loop_rows = n;
+        ctx->loop_idx_valid = n > 0 && !p.small;
+        ctx->loop_sorted = p.sort_source;
+        if (gate) {
+            // A gated loop's idx holds matches of rows the gate dropped as well: loop_rows stays -1 ("no registration's rows
+            // are held"), so icpmi_debug_loop_rows refuses every row count and nothing reads them as an ungated loop's.
+            ctx->loop_rows = -1;
+            ctx->loop_idx_valid = false;
+            gate->pairs = (int64_t)hs->sums[gate->kind ? 29 : 28];
+            gate->weight_sum = gate->kind ? hs->sums[28] : 0.0;
+        }
+
+        memcpy(result->transformation, hs->total, sizeof(double) * 16); // icp.hpp:254
+        result->converged = hs->converged;
+        result->num_iterations = hs->hist_len - 1;                      // icp.hpp:255
+        result->final_error = hs->final_error;
+        result->history_len = hl;
+        result->loop_iterations = hs->loops;
+        return ICPMI_OK;
+    }
+};
+
+// `gate` (may be null): see GateRun.  A gated registration runs the small-cloud kernel's gated form in the small regime
+// and otherwise the unfused general path -- search (launch_nn), k_reduce_gated, k_finish_step_gated, k_transform -- on
+// whichever engine prepare_nn chose: no fused resolve, no culling, no bounds, no list reuse, no sorted rows.
+// `before_wait`, `after_first` (may be null): see LoopRun::results_back and LoopRun::queue_loop.
+int align_device(icpmi_ctx *ctx, const double *d_src, int64_t n_src64, const double *d_tgt,
+                 int64_t n_tgt64, const icpmi_config *cfg, icpmi_result *result,
+                 double *error_history, int32_t history_cap, int (*before_wait)(icpmi_ctx *) = nullptr,
+                 int (*after_first)(icpmi_ctx *) = nullptr, GateRun *gate = nullptr)
+{
+    LoopRun run{ctx, d_src, d_tgt, cfg, gate, (int)n_src64, (int)n_tgt64, cfg->max_iterations + 1, ctx->stream};
+    int rc;
+    if ((rc = run.begin())) return rc;
+    if ((rc = run.prepare_search())) return rc;
+    if ((rc = run.settle_plan())) return rc;
+    if ((rc = run.target_normals())) return rc;
+    if ((rc = run.sort_source())) return rc;
+    if ((rc = run.first_move())) return rc;
+    if ((rc = run.queue_loop(after_first))) return rc;
+    if ((rc = run.results_back(error_history, history_cap, before_wait))) return rc;
+    run.account_profile();
+    return run.fill_result(result);
 }
 
 // voxel filter on device memory -> d_out (n_out rows); see voxel.h
@@ -2067,18 +2089,6 @@ const char *icpmi_last_error(const icpmi_ctx *ctx)
     return ctx ? ctx->err.c_str() : g_create_error.c_str();
 }
 
-int icpmi_align_device(icpmi_ctx *ctx, const double *d_source_xyz, int64_t n_src,
-                       const double *d_target_xyz, int64_t n_tgt, const icpmi_config *cfg,
-                       icpmi_result *result, double *error_history, int32_t history_cap)
-{
-    int rc = validate_align(ctx, d_source_xyz, n_src, d_target_xyz, n_tgt, cfg, result,
-                            error_history, history_cap);
-    if (rc) return rc;
-    if ((rc = check_common(ctx))) return rc;
-    return align_device(ctx, d_source_xyz, n_src, d_target_xyz, n_tgt, cfg, result, error_history,
-                        history_cap);
-}
-
 namespace {
 
 // the gate of the gated entry points: finite and > 0, and not on a context with a communicator (out of scope)
@@ -2179,18 +2189,53 @@ int batch_run(icpmi_ctx *ctx, int32_t count, const std::function<int(icpmi_ctx *
     return ICPMI_OK;
 }
 
+// Every icpmi_align* entry point: the checks in their order -- the call's arguments, the context, then the entry's rule
+// (`entry`: which of icpmi_gate / icpmi_robust `rule` points to, and of icpmi_gate_info / icpmi_robust_info `info`, which
+// may be null; kRuleNone: neither) -- then the registration, on rows in device memory or on the caller's host arrays.
+int align_entry(icpmi_ctx *ctx, bool on_device, const double *source_xyz, int64_t n_src, const double *target_xyz, int64_t n_tgt,
+                const icpmi_config *cfg, LoopRule entry, const void *rule, void *info, icpmi_result *result, double *error_history,
+                int32_t history_cap)
+{
+    int rc = validate_align(ctx, source_xyz, n_src, target_xyz, n_tgt, cfg, result, error_history, history_cap);
+    if (rc) return rc;
+    if ((rc = check_common(ctx))) return rc;
+    GateRun run;
+    if (entry == kRuleGate && (rc = validate_gate(ctx, (const icpmi_gate *)rule, &run))) return rc;
+    if (entry == kRuleRobust && (rc = validate_robust(ctx, (const icpmi_robust *)rule, &run))) return rc;
+    GateRun *gate = entry == kRuleNone ? nullptr : &run;
+    rc = on_device ? align_device(ctx, source_xyz, n_src, target_xyz, n_tgt, cfg, result, error_history, history_cap, nullptr, nullptr, gate)
+                   : align_staged(ctx, source_xyz, n_src, target_xyz, n_tgt, hipMemcpyHostToDevice, cfg, result, error_history, history_cap, gate);
+    if (rc || !info) return rc;
+    if (entry == kRuleGate) *(icpmi_gate_info *)info = icpmi_gate_info{run.pairs, n_src};
+    if (entry == kRuleRobust) *(icpmi_robust_info *)info = icpmi_robust_info{run.weight_sum, run.pairs, n_src};
+    return ICPMI_OK;
+}
+
+// the three batch forms' own checks; `all_given`: none of the form's required arrays is null
+int batch_check(icpmi_ctx *ctx, int32_t count, bool all_given)
+{
+    int rc;
+    if ((rc = check_common(ctx))) return rc;
+    if (!all_given) return fail(ctx, ICPMI_ERR_NULL, "null argument");
+    if (count < 1 || count > ICPMI_MAX_BATCH) return fail(ctx, ICPMI_ERR_ARG, "count %d outside [1,%d]", count, ICPMI_MAX_BATCH);
+    if (ctx->comm || ctx->cb_allreduce) return fail(ctx, ICPMI_ERR_ARG, "a context with a communicator registers one (sharded) problem at a time");
+    return ICPMI_OK;
+}
+
 } // namespace
+
+int icpmi_align_device(icpmi_ctx *ctx, const double *d_source_xyz, int64_t n_src,
+                       const double *d_target_xyz, int64_t n_tgt, const icpmi_config *cfg,
+                       icpmi_result *result, double *error_history, int32_t history_cap)
+{
+    return align_entry(ctx, true, d_source_xyz, n_src, d_target_xyz, n_tgt, cfg, kRuleNone, nullptr, nullptr, result, error_history, history_cap);
+}
 
 int icpmi_align(icpmi_ctx *ctx, const double *source_xyz, int64_t n_src, const double *target_xyz,
                 int64_t n_tgt, const icpmi_config *cfg, icpmi_result *result,
                 double *error_history, int32_t history_cap)
 {
-    int rc = validate_align(ctx, source_xyz, n_src, target_xyz, n_tgt, cfg, result, error_history,
-                            history_cap);
-    if (rc) return rc;
-    if ((rc = check_common(ctx))) return rc;
-    return align_staged(ctx, source_xyz, n_src, target_xyz, n_tgt, hipMemcpyHostToDevice, cfg, result, error_history,
-                        history_cap);
+    return align_entry(ctx, false, source_xyz, n_src, target_xyz, n_tgt, cfg, kRuleNone, nullptr, nullptr, result, error_history, history_cap);
 }
 
 int icpmi_align_batch(icpmi_ctx *ctx, int32_t count, const double *const *sources_xyz, const int64_t *n_src,
@@ -2198,11 +2243,7 @@ int icpmi_align_batch(icpmi_ctx *ctx, int32_t count, const double *const *source
                       icpmi_result *results, double *error_history, int32_t history_stride, int32_t *status)
 {
     int rc;
-    if ((rc = check_common(ctx))) return rc;
-    if (!sources_xyz || !n_src || !targets_xyz || !n_tgt || !cfgs || !results || !error_history || !status)
-        return fail(ctx, ICPMI_ERR_NULL, "null argument");
-    if (count < 1 || count > ICPMI_MAX_BATCH) return fail(ctx, ICPMI_ERR_ARG, "count %d outside [1,%d]", count, ICPMI_MAX_BATCH);
-    if (ctx->comm || ctx->cb_allreduce) return fail(ctx, ICPMI_ERR_ARG, "a context with a communicator registers one (sharded) problem at a time");
+    if ((rc = batch_check(ctx, count, sources_xyz && n_src && targets_xyz && n_tgt && cfgs && results && error_history && status))) return rc;
     return batch_run(ctx, count, [&](icpmi_ctx *c, int k) {
         return icpmi_align(c, sources_xyz[k], n_src[k], targets_xyz[k], n_tgt[k], &cfgs[k], &results[k],
                            error_history + (size_t)k * (size_t)history_stride, history_stride);
@@ -2213,32 +2254,14 @@ int icpmi_align_gated_device(icpmi_ctx *ctx, const double *d_source_xyz, int64_t
                              int64_t n_tgt, const icpmi_config *cfg, const icpmi_gate *gate, icpmi_result *result,
                              icpmi_gate_info *info, double *error_history, int32_t history_cap)
 {
-    int rc = validate_align(ctx, d_source_xyz, n_src, d_target_xyz, n_tgt, cfg, result, error_history, history_cap);
-    if (rc) return rc;
-    if ((rc = check_common(ctx))) return rc;
-    GateRun run;
-    if ((rc = validate_gate(ctx, gate, &run))) return rc;
-    if ((rc = align_device(ctx, d_source_xyz, n_src, d_target_xyz, n_tgt, cfg, result, error_history, history_cap, nullptr,
-                           nullptr, &run)))
-        return rc;
-    if (info) info->pairs = run.pairs, info->rows = n_src;
-    return ICPMI_OK;
+    return align_entry(ctx, true, d_source_xyz, n_src, d_target_xyz, n_tgt, cfg, kRuleGate, gate, info, result, error_history, history_cap);
 }
 
 int icpmi_align_gated(icpmi_ctx *ctx, const double *source_xyz, int64_t n_src, const double *target_xyz, int64_t n_tgt,
                       const icpmi_config *cfg, const icpmi_gate *gate, icpmi_result *result, icpmi_gate_info *info,
                       double *error_history, int32_t history_cap)
 {
-    int rc = validate_align(ctx, source_xyz, n_src, target_xyz, n_tgt, cfg, result, error_history, history_cap);
-    if (rc) return rc;
-    if ((rc = check_common(ctx))) return rc;
-    GateRun run;
-    if ((rc = validate_gate(ctx, gate, &run))) return rc;
-    if ((rc = align_staged(ctx, source_xyz, n_src, target_xyz, n_tgt, hipMemcpyHostToDevice, cfg, result, error_history,
-                           history_cap, &run)))
-        return rc;
-    if (info) info->pairs = run.pairs, info->rows = n_src;
-    return ICPMI_OK;
+    return align_entry(ctx, false, source_xyz, n_src, target_xyz, n_tgt, cfg, kRuleGate, gate, info, result, error_history, history_cap);
 }
 
 int icpmi_align_gated_batch(icpmi_ctx *ctx, int32_t count, const double *const *sources_xyz, const int64_t *n_src,
@@ -2247,11 +2270,7 @@ int icpmi_align_gated_batch(icpmi_ctx *ctx, int32_t count, const double *const *
                             int32_t history_stride, int32_t *status)
 {
     int rc;
-    if ((rc = check_common(ctx))) return rc;
-    if (!sources_xyz || !n_src || !targets_xyz || !n_tgt || !cfgs || !gates || !results || !error_history || !status)
-        return fail(ctx, ICPMI_ERR_NULL, "null argument");
-    if (count < 1 || count > ICPMI_MAX_BATCH) return fail(ctx, ICPMI_ERR_ARG, "count %d outside [1,%d]", count, ICPMI_MAX_BATCH);
-    if (ctx->comm || ctx->cb_allreduce) return fail(ctx, ICPMI_ERR_ARG, "a context with a communicator registers one (sharded) problem at a time");
+    if ((rc = batch_check(ctx, count, sources_xyz && n_src && targets_xyz && n_tgt && cfgs && gates && results && error_history && status))) return rc;
     return batch_run(ctx, count, [&](icpmi_ctx *c, int k) {
         return icpmi_align_gated(c, sources_xyz[k], n_src[k], targets_xyz[k], n_tgt[k], &cfgs[k], &gates[k], &results[k],
                                  infos ? &infos[k] : nullptr, error_history + (size_t)k * (size_t)history_stride, history_stride);
@@ -2262,32 +2281,14 @@ int icpmi_align_robust_device(icpmi_ctx *ctx, const double *d_source_xyz, int64_
                               int64_t n_tgt, const icpmi_config *cfg, const icpmi_robust *rule, icpmi_result *result,
                               icpmi_robust_info *info, double *error_history, int32_t history_cap)
 {
-    int rc = validate_align(ctx, d_source_xyz, n_src, d_target_xyz, n_tgt, cfg, result, error_history, history_cap);
-    if (rc) return rc;
-    if ((rc = check_common(ctx))) return rc;
-    GateRun run;
-    if ((rc = validate_robust(ctx, rule, &run))) return rc;
-    if ((rc = align_device(ctx, d_source_xyz, n_src, d_target_xyz, n_tgt, cfg, result, error_history, history_cap, nullptr,
-                           nullptr, &run)))
-        return rc;
-    if (info) info->weight_sum = run.weight_sum, info->pairs = run.pairs, info->rows = n_src;
-    return ICPMI_OK;
+    return align_entry(ctx, true, d_source_xyz, n_src, d_target_xyz, n_tgt, cfg, kRuleRobust, rule, info, result, error_history, history_cap);
 }
 
 int icpmi_align_robust(icpmi_ctx *ctx, const double *source_xyz, int64_t n_src, const double *target_xyz, int64_t n_tgt,
                        const icpmi_config *cfg, const icpmi_robust *rule, icpmi_result *result, icpmi_robust_info *info,
                        double *error_history, int32_t history_cap)
 {
-    int rc = validate_align(ctx, source_xyz, n_src, target_xyz, n_tgt, cfg, result, error_history, history_cap);
-    if (rc) return rc;
-    if ((rc = check_common(ctx))) return rc;
-    GateRun run;
-    if ((rc = validate_robust(ctx, rule, &run))) return rc;
-    if ((rc = align_staged(ctx, source_xyz, n_src, target_xyz, n_tgt, hipMemcpyHostToDevice, cfg, result, error_history,
-                           history_cap, &run)))
-        return rc;
-    if (info) info->weight_sum = run.weight_sum, info->pairs = run.pairs, info->rows = n_src;
-    return ICPMI_OK;
+    return align_entry(ctx, false, source_xyz, n_src, target_xyz, n_tgt, cfg, kRuleRobust, rule, info, result, error_history, history_cap);
 }
 
 int icpmi_align_robust_batch(icpmi_ctx *ctx, int32_t count, const double *const *sources_xyz, const int64_t *n_src,
@@ -2296,11 +2297,7 @@ int icpmi_align_robust_batch(icpmi_ctx *ctx, int32_t count, const double *const 
                              double *error_history, int32_t history_stride, int32_t *status)
 {
     int rc;
-    if ((rc = check_common(ctx))) return rc;
-    if (!sources_xyz || !n_src || !targets_xyz || !n_tgt || !cfgs || !rules || !results || !error_history || !status)
-        return fail(ctx, ICPMI_ERR_NULL, "null argument");
-    if (count < 1 || count > ICPMI_MAX_BATCH) return fail(ctx, ICPMI_ERR_ARG, "count %d outside [1,%d]", count, ICPMI_MAX_BATCH);
-    if (ctx->comm || ctx->cb_allreduce) return fail(ctx, ICPMI_ERR_ARG, "a context with a communicator registers one (sharded) problem at a time");
+    if ((rc = batch_check(ctx, count, sources_xyz && n_src && targets_xyz && n_tgt && cfgs && rules && results && error_history && status))) return rc;
     return batch_run(ctx, count, [&](icpmi_ctx *c, int k) {
         return icpmi_align_robust(c, sources_xyz[k], n_src[k], targets_xyz[k], n_tgt[k], &cfgs[k], &rules[k], &results[k],
                                   infos ? &infos[k] : nullptr, error_history + (size_t)k * (size_t)history_stride, history_stride);
@@ -2413,7 +2410,7 @@ int icpmi_solve_point_to_plane(icpmi_ctx *ctx, const double *source_xyz, const d
     if ((rc = reserve(ctx, ctx->stage_a, bytes))) return rc;
     if ((rc = reserve(ctx, ctx->stage_b, bytes))) return rc;
     if ((rc = reserve(ctx, ctx->stage_c, bytes))) return rc;
-    const int rblocks = reduce_blocks(ctx, n);
+    const int rblocks = reduce_blocks(ctx->cu_count, n);
     if ((rc = reserve(ctx, ctx->partials, sizeof(double) * kSumsStride * (size_t)rblocks))) return rc;
     hipStream_t s = ctx->stream;
     HIP_TRY(ctx, hipMemcpyAsync(ctx->stage_a.p, source_xyz, bytes, hipMemcpyHostToDevice, s));
@@ -2422,7 +2419,7 @@ int icpmi_solve_point_to_plane(icpmi_ctx *ctx, const double *source_xyz, const d
     HIP_TRY(ctx, hipMemsetAsync(ctx->d_state, 0, sizeof(IcpState), s));
     {
         StageTimer t(ctx, ST_REDUCE);
-        hipLaunchKernelGGL(k_reduce, dim3(rblocks), dim3(256), 0, s, (const double *)ctx->stage_a.p, n,
+        hipLaunchKernelGGL(k_reduce_rule<RuleNone>, dim3(rblocks), dim3(256), 0, s, (const double *)ctx->stage_a.p, n,
                            (const double *)ctx->stage_b.p, n, (const double *)ctx->stage_c.p,
                            (const int *)nullptr, (double *)ctx->partials.p, (const IcpState *)nullptr);
         hipLaunchKernelGGL(k_finish_solve, dim3(1), dim3(kFinishThreads), 0, s, (const double *)ctx->partials.p,

@@ -44,7 +44,7 @@ namespace icpmi {
 
 constexpr int kSmallWaves = 8;
 constexpr int kSmallThreads = 64 * kSmallWaves;
-constexpr int kSmallQ = 32;                                  // rows (queries) per workgroup
+// (kSmallQ = 32 rows (queries) per workgroup: loop_plan.h)
 constexpr int kSmallUnitTiles = 32;                          // target tiles per unit of a wave's work
 constexpr int kSmallUnitsPerSplit = kSplitTiles / kSmallUnitTiles;
 constexpr int kSmallMaxSplits = 16;                          // one lane of a quarter-wave per split

@@ -21,6 +21,7 @@
 
 #include "device_math.h"
 #include "list_reuse.h"
+#include "loop_plan.h"
 
 namespace icpmi {
 
@@ -140,25 +141,43 @@ __device__ __forceinline__ double wave_sum(double v)
     return v;
 }
 
-__global__ __launch_bounds__(256) void k_reduce(const double *__restrict__ cur, int n,
-                                                const double *__restrict__ tgt, int m_tgt,
-                                                const double *__restrict__ nrm,
-                                                const int *__restrict__ idx,
-                                                double *__restrict__ partials,
-                                                const IcpState *__restrict__ st)
+// The rule of a pass's rows (LoopRule, loop_plan.h) as the kernels of the k_reduce and k_finish_step families see it: a type
+// with kCounted (the rows are tested and the kept ones counted in the partial row), kWeighted (each kept row has a weight)
+// and kCols, the columns of a partial row; a counted rule carries g2, a weighted one gives weight(b).  No rule here;
+// RuleGate: icp_gated.h, RuleRobust: icp_robust.h.
+struct RuleNone {
+    static constexpr bool kCounted = false, kWeighted = false;
+    static constexpr int kCols = 28;
+};
+
+// k_reduce and its gated and robust forms: one kernel template, k_reduce_rule<RuleNone>, <RuleGate, double> and
+// <RuleRobust, double, int, double> -- the rule's own arguments (g2; g2, kind, ks) follow the common ones.  Per instantiation
+// the fp64 operations and their order are those of the contracts at the heads of icp_gated.h and icp_robust.h; with no
+// rule every row is added (a row without a neighbour too: the sums are garbage then anyway, but the gather must stay in
+// bounds).  (The body sits in the kernel itself: inlined from a device function, the compiler commuted operands.)
+template <class Rule, class... RuleArgs>
+__global__ __launch_bounds__(256) void k_reduce_rule(const double *__restrict__ cur, int n, const double *__restrict__ tgt, int m_tgt,
+                                                     const double *__restrict__ nrm, const int *__restrict__ idx,
+                                                     double *__restrict__ partials, const IcpState *__restrict__ st,
+                                                     const RuleArgs... rule_args)
 {
+    [[maybe_unused]] const Rule rule{rule_args...};
     if (st && st->done) return;
     double acc[28];
 #pragma unroll
     for (int e = 0; e < 28; ++e) acc[e] = 0.0;
+    [[maybe_unused]] double wsum = 0.0;
+    [[maybe_unused]] double kept = 0.0; // (a small integer: exact in any order of additions)
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-        int j = idx ? idx[i] : i;
-        // a query with NaN/Inf coordinates has no nearest neighbour (index -1, like
-        // kdtree.hpp:53); the sums are garbage then anyway, but the gather must stay in bounds
-        j = (unsigned)j < (unsigned)m_tgt ? j : 0;
+        const int ji = idx ? idx[i] : i;
+        const bool found = (unsigned)ji < (unsigned)m_tgt; // (-1: a non-finite row has no neighbour, kdtree.hpp:53)
+        const int j = found ? ji : 0;                      // the gather stays in bounds
         const double p0 = cur[3 * i], p1 = cur[3 * i + 1], p2 = cur[3 * i + 2];
         const double q0 = tgt[3 * j], q1 = tgt[3 * j + 1], q2 = tgt[3 * j + 2];
         const double n0 = nrm[3 * j], n1 = nrm[3 * j + 1], n2 = nrm[3 * j + 2];
+        const double d0 = q0 - p0, d1 = q1 - p1, d2 = q2 - p2;
+        if constexpr (Rule::kCounted)
+            if (!(found && (d0 * d0 + d1 * d1) + d2 * d2 <= rule.g2)) continue; // dropped: nothing is added, not even a zero
         double J[6];
         J[0] = p1 * n2 - p2 * n1; // p x n, icp.hpp:105
         J[1] = p2 * n0 - p0 * n2;
@@ -166,26 +185,48 @@ __global__ __launch_bounds__(256) void k_reduce(const double *__restrict__ cur, 
         J[3] = n0;
         J[4] = n1;
         J[5] = n2;
-        const double d0 = q0 - p0, d1 = q1 - p1, d2 = q2 - p2;
         const double b = (d0 * n0 + d1 * n1) + d2 * n2; // icp.hpp:116
         int o = 0;
+        if constexpr (Rule::kWeighted) {
+            const double w = rule.weight(b);
+            double wJ[6];
 #pragma unroll
-        for (int r = 0; r < 6; ++r)
+            for (int r = 0; r < 6; ++r) wJ[r] = w * J[r];
 #pragma unroll
-            for (int c = r; c < 6; ++c) acc[o++] += J[r] * J[c];
+            for (int r = 0; r < 6; ++r)
 #pragma unroll
-        for (int r = 0; r < 6; ++r) acc[21 + r] += J[r] * b;
-        acc[27] += b * b;
+                for (int c = r; c < 6; ++c) acc[o++] += wJ[r] * J[c];
+#pragma unroll
+            for (int r = 0; r < 6; ++r) acc[21 + r] += wJ[r] * b;
+            acc[27] += (w * b) * b;
+            wsum += w;
+        } else {
+#pragma unroll
+            for (int r = 0; r < 6; ++r)
+#pragma unroll
+                for (int c = r; c < 6; ++c) acc[o++] += J[r] * J[c];
+#pragma unroll
+            for (int r = 0; r < 6; ++r) acc[21 + r] += J[r] * b;
+            acc[27] += b * b;
+        }
+        if constexpr (Rule::kCounted) kept += 1.0;
     }
-    __shared__ double red[4][28];
+    __shared__ double red[4][Rule::kCols];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int e = 0; e < 28; ++e) {
         const double s = wave_sum(acc[e]);
         if (lane == 0) red[wave][e] = s;
     }
+    if constexpr (Rule::kWeighted) {
+        const double s = wave_sum(wsum), c = wave_sum(kept);
+        if (lane == 0) red[wave][28] = s, red[wave][29] = c;
+    } else if constexpr (Rule::kCounted) {
+        const double s = wave_sum(kept);
+        if (lane == 0) red[wave][28] = s;
+    }
     __syncthreads();
-    if (threadIdx.x < 28) {
+    if (threadIdx.x < Rule::kCols) {
         const int e = threadIdx.x;
         partials[(size_t)blockIdx.x * kSumsStride + e] = ((red[0][e] + red[1][e]) + red[2][e]) + red[3][e];
     }
@@ -261,8 +302,7 @@ __device__ inline void finish_sums(const double *__restrict__ partials, int nblo
 // the step kernel's sum of C3's 1,563 rows 6.7: measured at C3, default engine, 30 iterations, same box: 9,614 -> 9,810
 // iterations/s with the threshold at 1,024 rows (the sums' order of additions differs on either side of it, inside every
 // tolerance of the tests).
-constexpr int kSumGroup = 16;
-constexpr int kSumTreeFrom = 1024;
+// (kSumGroup = 16 and kSumTreeFrom = 1024 are defined in loop_plan.h: the host plans its launches with them)
 // Lean passes (list_reuse.h, "lean passes"; `slot` null: none of this): k_sum_groups of pass p sits behind the mover of
 // pass p - 1 and in front of the mover of pass p, so ONE MORE workgroup of it can count the rows pass p wanted listed from
 // the words that mover left (RowBounds::mask) without racing their writer, and tell the host: (ticket << 32) | count in a
@@ -433,25 +473,47 @@ __device__ __forceinline__ void state_copy(void *dst, const void *src)
     for (unsigned w = threadIdx.x; w < sizeof(IcpState) / 8; w += blockDim.x) d[w] = s[w];
 }
 
-__global__ __launch_bounds__(kFinishThreads) void k_finish_step(const double *__restrict__ partials,
-                                                     int nblocks, int n_local, IcpState *st,
-                                                     double *history, int final_pass, int *progress,
-                                                     int ticket)
+__device__ inline void step_no_pairs(IcpState *st, double *history, int final_pass); // (icp_gated.h)
+
+// k_finish_step, k_finish_step_gated, k_finish_step_robust: one body.  A counted rule takes the count from the partial rows'
+// column 28 (n_local is not looked at) and has the no-pairs rule in front of the step (icp_gated.h).
+template <class Rule>
+__device__ __forceinline__ void finish_step_rows(const double *__restrict__ partials, int nblocks, int n_local, IcpState *st,
+                                                 double *history, int final_pass, int *progress, int ticket)
 {
     __shared__ IcpState ls, sums; // `sums`: only its sums[] are used
     // the state and the partial rows are requested together (one round trip instead of two); the
     // sums are taken over only if the loop has not ended
     state_copy(&ls, st);
-    finish_sums(partials, nblocks, n_local, &sums);
+    finish_sums<Rule::kCounted, Rule::kCols>(partials, nblocks, n_local, &sums);
     __syncthreads();
-    if (!ls.done && threadIdx.x < kNumSums) ls.sums[threadIdx.x] = sums.sums[threadIdx.x];
+    constexpr int taken = Rule::kCols > kNumSums ? Rule::kCols : kNumSums;
+    if (!ls.done && threadIdx.x < taken) ls.sums[threadIdx.x] = sums.sums[threadIdx.x];
     __syncthreads();
     if (threadIdx.x < 64) {
-        step_update_wave(&ls, history, final_pass, threadIdx.x);
+        if constexpr (Rule::kCounted) {
+            const bool none = !ls.done && !(ls.sums[28] > 0.0); // wave-uniform
+            __builtin_amdgcn_wave_barrier();
+            if (none) {
+                if (threadIdx.x == 0) step_no_pairs(&ls, history, final_pass);
+            } else {
+                step_update_wave(&ls, history, final_pass, threadIdx.x);
+            }
+        } else {
+            step_update_wave(&ls, history, final_pass, threadIdx.x);
+        }
         if (threadIdx.x == 0) publish_progress(progress, ticket, ls.done);
     }
     __syncthreads();
     state_copy(st, &ls);
+}
+
+__global__ __launch_bounds__(kFinishThreads) void k_finish_step(const double *__restrict__ partials,
+                                                     int nblocks, int n_local, IcpState *st,
+                                                     double *history, int final_pass, int *progress,
+                                                     int ticket)
+{
+    finish_step_rows<RuleNone>(partials, nblocks, n_local, st, history, final_pass, progress, ticket);
 }
 
 // multi GPU: k_finish -> ncclAllReduce(st->sums, kNumExchanged) -> k_step

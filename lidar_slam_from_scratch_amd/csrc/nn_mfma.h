@@ -69,16 +69,14 @@
 
 namespace icpmi {
 
-constexpr int kTile = 32;                         // queries / targets per MFMA tile
+// (kTile = 32, queries / targets per MFMA tile, and the coarse workgroup's kCoarseQT = 2 tiles per wave, kCoarseWaves = 8
+// and kCoarseQueries = 512: loop_plan.h, which the host plans its launches with)
 constexpr int kCols = 32;                         // columns (slots) per split
 constexpr int kSplitTiles = 64;                   // target tiles per split
 constexpr int kSplitTargets = kSplitTiles * kTile;// targets per split
 constexpr int kSlotTargets = kSplitTiles;         // targets per (split, column) slot
 constexpr int kChunkTiles = 32;                   // tiles staged in LDS at a time (32 KiB)
-constexpr int kCoarseQT = 2;                      // 32-query tiles per wave
-constexpr int kCoarseWaves = 8;                   // waves per workgroup
 constexpr int kCoarseThreads = 64 * kCoarseWaves;
-constexpr int kCoarseQueries = kTile * kCoarseQT * kCoarseWaves; // queries per workgroup
 constexpr float kBig = 3.0e38f;
 constexpr double kArithBound = 52.0;              // x u a^2, see above
 constexpr double kReprEps = 1.52587890625e-05 + 5.9604644775390625e-08; // 2^-16 + 2^-24
@@ -1138,7 +1136,7 @@ __device__ __forceinline__ void resolve_certify(const float (&pv)[KEEP], // phas
     }
 }
 
-constexpr int kResolveWW = 4; // waves per workgroup = Q * WW queries per partial row of normal-equation terms
+// (kResolveWW = 4 waves per workgroup = Q * WW queries per partial row of normal-equation terms: loop_plan.h)
 // The end of the Q-queries-per-wave resolve kernels (k_nn_resolve, k_nn_resolve_bounded): results out, counters, and the
 // fused residual + normal-equation terms.  (jspec, q*, n*): the matched target and normal gathered ahead for target
 // `jspec` (< 0: nothing was gathered).
@@ -1301,8 +1299,7 @@ __device__ __forceinline__ void resolve_finish(const int lane, const int wave, c
 // One wave resolves 16 queries.  Lane = (query ql, sub-lane): the sub-lanes share the
 // bookkeeping of a query (each looks at its share of the splits) and each quarter-wave scans one
 // winning slot at a time (lane l16 takes sorted positions l16, l16+16, ... of the slot: three
-// coalesced streams), so 4 slots are in flight per wave.
-constexpr int kResolveQ = 16;
+// coalesced streams), so 4 slots are in flight per wave.  (kResolveQ = 16: loop_plan.h)
 // Waves per SIMD the register allocation must allow: 5.  The kernel waits on memory three
 // quarters of the time (SQ_WAIT_ANY / SQ_WAVE_CYCLES = 0.77) and, at 64 queries per workgroup, C3
 // has 1,563 workgroups: at 5 per CU (82 VGPRs) 283 of them form a second round.  Forcing 6 / 7
