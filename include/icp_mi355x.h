@@ -258,6 +258,33 @@ int icpmi_align_robust_batch(icpmi_ctx *ctx, int32_t count, const double *const 
                              const icpmi_robust *rules, icpmi_result *results, icpmi_robust_info *infos,
                              double *error_history, int32_t history_stride, int32_t *status);
 
+/* The normal equations of the pass that produced final_error of the last registration this context ran: what the
+ * registration minimised, at its result.  Costs nothing: the sums come back with the result behind the call's one wait,
+ * and this getter only copies them on the host.
+ *   JtJ     row-major 6 x 6, symmetric: sum w J^T J over the pass's pairs, J = [(p x n)^T, n^T], p the source point moved by
+ *           T, n the normal of its nearest target point, in the order [rotation; translation] of the registration's step
+ *           (a left perturbation of T in the target frame).  Filled from the 21 sums of the upper triangle, bits copied.
+ *   Jtb     sum w J^T b, b = (q - p) . n with q the matched target point: the step solves JtJ x = Jtb
+ *   sum_sq  sum w b^2;  final_error = sqrt(sum_sq / weight), to the bit
+ *   weight  the divisor: the pairs of a plain or gated call, the weight sum of a robust one (w is 1 except there)
+ *   pairs   rows that entered the sums
+ *   T       the registration's result
+ * After a loop that broke on a convergence test these are the breaking pass's sums, after an exhausted loop the
+ * post-loop pass's; either way the pass ran at T.  k: the problem of the last icpmi_align*_batch call, 0 after a single
+ * call (host or device entry, plain, gated or robust, icpmi_stream_push*, icpmi_local_map_register*).
+ * ICPMI_ERR_ARG, with a text in icpmi_last_error: k out of range; no registration ran (a fresh context, a stream push
+ * that registered nothing, a call that failed); a gated or robust pass that kept no row; a context with a
+ * communicator (its sums are the ranks' shares). */
+typedef struct {
+    double JtJ[36];
+    double Jtb[6];
+    double sum_sq;
+    double weight;
+    int64_t pairs;
+    double T[16];
+} icpmi_normal_matrix;
+int icpmi_last_normal_matrix(icpmi_ctx *ctx, int32_t k, icpmi_normal_matrix *out);
+
 /* Replaces KDTree(points) + KDTree::nearest_batch (kdtree.hpp:20-26,43-59): for each
  * query the index of, and squared distance to, its nearest target.  Host pointers;
  * dist_sq may be NULL. */
@@ -599,6 +626,41 @@ int icpmi_pose_graph_loop_loss(const icpmi_pose_graph *graph, int32_t *kind, dou
 int icpmi_pose_graph_loop_weights(icpmi_pose_graph *graph, double *weights, double *distances, int64_t cap,
                                   int64_t *n_out);
 
+/* Between factors weighted by a full 6 x 6 information matrix (GTSAM's noiseModel::Gaussian::Information):
+ * an edge stiff where its measurement is well constrained and soft where it is not, instead of six fixed sigmas.  Off by
+ * default: a graph that holds no such factor runs the kernels it ran before, bit for bit.
+ * `info` is row-major, in the factor's tangent order (omega, v), the inverse covariance of the residual
+ * Log(rel^-1 X_from^-1 X_to).  It is checked when the factor is added, on the host: every entry finite, every diagonal
+ * entry > 0, |info_ab - info_ba| <= 1e-9 sqrt(info_aa info_bb) (beyond what rounding a 6 x 6 triple product leaves: see
+ * csrc/pose_graph_info_host.h), and the upper Cholesky info = R^T R, taken from the upper triangle, succeeds with every
+ * pivot finite and > 0.  A matrix that fails is ICPMI_ERR_ARG and the graph is untouched: a semi-definite one (one plane's
+ * JtJ) needs a floor first, see icpmi_information_from_icp.  The graph keeps R and whitens by it: rw = R r, A = R J.
+ * Estimates, the loop count and the loop edges' loss (icpmi_pose_graph_set_loop_loss, on d = ||R r||) are exactly those
+ * of icpmi_pose_graph_add_odometry (with fitness 0) and icpmi_pose_graph_add_loop_closure; icpmi_pose_graph_loop_weights
+ * reports d = ||R r|| for such a loop edge.  Diagonal and information factors mix freely in one graph. */
+int icpmi_pose_graph_add_odometry_information(icpmi_pose_graph *graph, int64_t from, int64_t to, const double rel[16],
+                                              const double info[36]);
+int icpmi_pose_graph_add_loop_closure_information(icpmi_pose_graph *graph, int64_t from, int64_t to,
+                                                  const double rel[16], const double info[36]);
+/* The information of an edge from the normal matrix of the point-to-plane registration that measured it.  Pure host
+ * function, fp64 in a fixed operation order (no context, no device):
+ *     info_out = Ad_T^T (JtJ / sigma^2) Ad_T + diag(1 / floor_rotation_sigma^2 x 3, 1 / floor_translation_sigma^2 x 3)
+ * with Ad_T = [[R, 0], [t^ R, R]], symmetric by construction.
+ * JtJ (row-major 6 x 6, the upper triangle is read) is sum J^T J over the registration's pairs at its result T, with
+ * J = [(p x n)^T, n^T] per pair, p the moved source point and n the target normal: the curvature of the cost in ICP's own
+ * step, a LEFT perturbation x = [r; t] of T in the target frame, p' = p + r x p + t.  The graph's factor perturbs on the
+ * RIGHT, and Exp(x) T = T Exp(Ad_{T^-1} x) to first order, hence the adjoint.  The result is the information of an edge
+ * entered as rel = T with from = the target's pose and to = the source's.  For a caller who enters the edge the other
+ * way round, rel = T^-1 with from = the source's pose: the same JtJ is already right-frame information, info = JtJ /
+ * sigma^2 (+ floors), no adjoint -- pass the identity for T.
+ * sigma: the residual noise of one pair in metres, finite and > 0; a caller who wants fewer effective points than rows
+ * (neighbouring returns are not independent) folds sqrt(rows / effective) into it.  The floors are 0 (none) or finite and
+ * > 0: sigmas of an isotropic prior information added to the diagonal, which keep a rank-deficient JtJ (a single plane,
+ * a corridor) positive definite.  Anything else, or a non-finite entry of JtJ or T, is ICPMI_ERR_ARG; a NULL pointer
+ * ICPMI_ERR_NULL. */
+int icpmi_information_from_icp(const double JtJ[36], const double T[16], double sigma, double floor_rotation_sigma,
+                               double floor_translation_sigma, double info_out[36]);
+
 /* Global map: the node's kept filtered scans and what it builds from them with the optimised poses
  * (slam_viz/src/ros/slam_node.cpp):
  *     downsampled_clouds_.push_back(curr)                      :71, :123      icpmi_map_add_frame*
@@ -877,6 +939,16 @@ int icpmi_map_ground_labels(icpmi_map *map, int64_t frame, uint8_t *labels, int6
  *                             Anything else: ICPMI_ERR_ARG.
  *   icpmi_loop_last_weights   the weight sum of each of the last detect's results' last pass, in result order, as
  *                             icpmi_loop_last_pairs returns the pairs; each is -1 when that detect ran without weights.
+ *   icpmi_loop_set_information   sigma finite and > 0 with floors 0 or finite and > 0 (sigma 0: off, as at creation, the
+ *                             floors ignored; not in the reference): detect keeps, per result, the information matrix
+ *                             icpmi_information_from_icp makes of that verification's own normal matrix
+ *                             (icpmi_last_normal_matrix) and transform with these three arguments -- the edge's weight
+ *                             for icpmi_pose_graph_add_loop_closure_information(match, query, transform, info).  Costs
+ *                             a detect nothing on the device.  Composes with gate, weights and yaw guess; takes effect
+ *                             at the next detect.  Anything else: ICPMI_ERR_ARG.
+ *   icpmi_loop_last_information   36 doubles (row-major 6 x 6) per result of the last detect, in result order, as
+ *                             icpmi_loop_last_pairs returns the pairs (cap counts matrices); none (*n_out 0) when that
+ *                             detect ran with the setting off.
  * A store frame or an entry out of range is ICPMI_ERR_ARG and changes nothing.  The handle uses its map's context and
  * stream: destroy it before its map, and the map before the context. */
 typedef struct icpmi_loop icpmi_loop;
@@ -906,6 +978,8 @@ int icpmi_loop_set_gate(icpmi_loop *loop, double max_distance);
 int icpmi_loop_last_pairs(const icpmi_loop *loop, int64_t *pairs, int64_t cap, int64_t *n_out);
 int icpmi_loop_set_robust(icpmi_loop *loop, int32_t kind, double scale);
 int icpmi_loop_last_weights(const icpmi_loop *loop, double *weights, int64_t cap, int64_t *n_out);
+int icpmi_loop_set_information(icpmi_loop *loop, double sigma, double floor_rotation_sigma, double floor_translation_sigma);
+int icpmi_loop_last_information(const icpmi_loop *loop, double *info, int64_t cap, int64_t *n_out);
 
 /* Scan-to-local-map odometry (not in the reference node, which registers each scan against the one before it,
  * slam_node.cpp:132-138): a sliding voxel map of the recent scans in one frame, kept on the device, as the

@@ -189,6 +189,52 @@ inline Context &default_context()
     return ctx;
 }
 
+// 6 x 6 row-major: the normal matrix of a registration, the information matrix of a pose-graph edge
+using Matrix6 = std::array<double, 36>;
+
+// icpmi_last_normal_matrix: the normal equations of the pass that produced final_error of the last registration `ctx`
+// ran (problem k of the last *_batch call, 0 after a single one): JtJ and Jtb in the order [rotation; translation] of
+// the registration's own step, sum_sq / weight = final_error^2, and the result T the pass ran at.  Throws IcpError
+// where no registration ran or its last pass kept no row.
+struct NormalMatrix {
+    Matrix6 JtJ{};
+    std::array<double, 6> Jtb{};
+    double sum_sq = 0.0, weight = 0.0;
+    long long pairs = 0;
+    Transformation T;
+};
+inline NormalMatrix last_normal_matrix(Context &ctx, int k = 0)
+{
+    icpmi_normal_matrix nm;
+    const int rc = icpmi_last_normal_matrix(ctx.get(), k, &nm);
+    if (rc != ICPMI_OK) throw IcpError(rc, icpmi_last_error(ctx.get()));
+    NormalMatrix out;
+    std::copy(nm.JtJ, nm.JtJ + 36, out.JtJ.begin());
+    std::copy(nm.Jtb, nm.Jtb + 6, out.Jtb.begin());
+    out.sum_sq = nm.sum_sq;
+    out.weight = nm.weight;
+    out.pairs = nm.pairs;
+    std::array<double, 16> m;
+    std::copy(nm.T, nm.T + 16, m.begin());
+    out.T = Transformation(m);
+    return out;
+}
+
+// icpmi_information_from_icp (host only, no device): the information of the pose-graph edge entered as rel = T, from the
+// target's pose to the source's, of a registration with normal matrix JtJ at result T.  sigma: the residual noise of
+// one pair in metres; the floors (0: none) are sigmas of an isotropic term that keeps a rank-deficient JtJ positive
+// definite.
+inline Matrix6 information_from_icp(const Matrix6 &JtJ, const Transformation &T, double sigma,
+                                    double floor_rotation_sigma = 0.0, double floor_translation_sigma = 0.0)
+{
+    Matrix6 out;
+    const int rc = icpmi_information_from_icp(JtJ.data(), T.matrix().data(), sigma, floor_rotation_sigma,
+                                              floor_translation_sigma, out.data());
+    if (rc != ICPMI_OK)
+        throw IcpError(rc, "information_from_icp: sigma must be finite and > 0, a floor 0 or finite and > 0, JtJ and T finite");
+    return out;
+}
+
 namespace detail {
 inline icpmi_config to_c(const ICPConfig &c)
 {
@@ -785,6 +831,10 @@ struct LoopClosureConfig { // loop_closure.hpp:14-19
     // against icp_fitness_threshold.  0: the reference's behaviour.
     int robust_kind = 0;
     double robust_scale = 0.0;
+    // Not in the reference: > 0 attaches to each result the information matrix of its edge, information_from_icp on that
+    // verification's own normal matrix with this sigma and these floors -- what PoseGraph::addLoopClosureInformation takes.
+    double information_sigma = 0.0;
+    double information_floor_rotation = 0.0, information_floor_translation = 0.0;
 };
 struct LoopClosureResult { // loop_closure.hpp:25-31
     int query_frame = 0, match_frame = 0;
@@ -793,6 +843,8 @@ struct LoopClosureResult { // loop_closure.hpp:25-31
     int sector_shift = -1; // the shift the verification started from (-1: yaw_guess off)
     long long pairs = -1;  // the rows the verification's last pass kept (-1: no correspondence-distance gate)
     double weight_sum = -1.0; // that pass's weight sum (-1: no robust weights)
+    bool has_information = false; // information_sigma was set: `information` is the edge's 6 x 6 information matrix
+    Matrix6 information{};
 };
 
 // icpmi_sc_shift_transform: the start of a verification whose candidate matched at column shift `shift` (0..59).
@@ -903,6 +955,13 @@ public:
                     if (config_.yaw_guess) out.sector_shift = shift[static_cast<std::size_t>(cand.second)];
                     out.pairs = kept[i];
                     out.weight_sum = weight[i];
+                    if (config_.information_sigma > 0.0) { // problem i of the batch just run
+                        const NormalMatrix nm = last_normal_matrix(*ctx_, static_cast<int>(i));
+                        out.information = information_from_icp(nm.JtJ, nm.T, config_.information_sigma,
+                                                               config_.information_floor_rotation,
+                                                               config_.information_floor_translation);
+                        out.has_information = true;
+                    }
                     results.push_back(out);
                     ++verified;
                 }
@@ -1028,6 +1087,21 @@ public:
             out.emplace_back(m);
         }
         return out;
+    }
+    // The same two factors weighted by a full 6 x 6 information matrix in the factor's tangent order (omega, v) instead
+    // of the config's sigmas (icpmi_pose_graph_add_*_information; not in the reference).  A matrix that is not finite,
+    // symmetric and positive definite throws IcpError(ICPMI_ERR_ARG) and changes nothing.
+    void addOdometryInformation(std::size_t from_idx, std::size_t to_idx, const Transformation &relative_transform,
+                                const Matrix6 &information)
+    {
+        check(icpmi_pose_graph_add_odometry_information(g_, static_cast<int64_t>(from_idx), static_cast<int64_t>(to_idx),
+                                                        relative_transform.matrix().data(), information.data()));
+    }
+    void addLoopClosureInformation(std::size_t from_idx, std::size_t to_idx, const Transformation &relative_transform,
+                                   const Matrix6 &information)
+    {
+        check(icpmi_pose_graph_add_loop_closure_information(g_, static_cast<int64_t>(from_idx), static_cast<int64_t>(to_idx),
+                                                            relative_transform.matrix().data(), information.data()));
     }
     // A robust loss on the loop-closure edges (icpmi_pose_graph_set_loop_loss): kind ICPMI_PG_LOSS_*, scale in sigmas.
     // Not in the reference; off by default.
@@ -1496,6 +1570,9 @@ public:
         if (config.yaw_guess) check(icpmi_loop_set_yaw_guess(l_, 1));
         if (config.max_correspondence_distance > 0.0) check(icpmi_loop_set_gate(l_, config.max_correspondence_distance));
         if (config.robust_kind != 0) check(icpmi_loop_set_robust(l_, config.robust_kind, config.robust_scale));
+        if (config.information_sigma > 0.0)
+            check(icpmi_loop_set_information(l_, config.information_sigma, config.information_floor_rotation,
+                                             config.information_floor_translation));
     }
     ~StoreLoopClosureDetector() { icpmi_loop_destroy(l_); }
     StoreLoopClosureDetector(const StoreLoopClosureDetector &) = delete;
@@ -1529,11 +1606,18 @@ public:
         check(icpmi_loop_last_pairs(l_, kept.data(), n, &ns)); // -1 each with the gate off
         std::vector<double> weight(static_cast<std::size_t>(std::max<int64_t>(n, 1)), -1.0);
         check(icpmi_loop_last_weights(l_, weight.data(), n, &ns)); // -1 each with the weights off
+        std::vector<double> infos(36 * static_cast<std::size_t>(std::max<int64_t>(n, 1)));
+        int64_t ni = 0;
+        check(icpmi_loop_last_information(l_, infos.data(), n, &ni)); // none with the setting off
         std::vector<LoopClosureResult> out;
         for (int64_t i = 0; i < n; ++i) {
             const icpmi_loop_result &r = buf[static_cast<std::size_t>(i)];
             LoopClosureResult o;
             o.weight_sum = weight[static_cast<std::size_t>(i)];
+            if (i < ni) {
+                std::copy(infos.begin() + 36 * i, infos.begin() + 36 * (i + 1), o.information.begin());
+                o.has_information = true;
+            }
             o.sector_shift = shifts[static_cast<std::size_t>(i)];
             o.pairs = kept[static_cast<std::size_t>(i)];
             o.query_frame = r.query_frame;

@@ -49,6 +49,8 @@ EXPORTS = [
     "icpmi_local_map_points", "icpmi_local_map_register", "icpmi_local_map_register_device",
     "icpmi_local_map_register_robust", "icpmi_local_map_register_robust_device",
     "icpmi_pose_graph_set_loop_loss", "icpmi_pose_graph_loop_loss", "icpmi_pose_graph_loop_weights",
+    "icpmi_pose_graph_add_odometry_information", "icpmi_pose_graph_add_loop_closure_information",
+    "icpmi_information_from_icp", "icpmi_last_normal_matrix", "icpmi_loop_set_information", "icpmi_loop_last_information",
 ]
 
 
@@ -101,6 +103,12 @@ def as_robust(rule):
     r.kind, r.scale = int(rule[0]), float(rule[1])
     r.max_distance = float(rule[2]) if len(rule) > 2 else 0.0
     return r
+
+
+class NormalMatrix(C.Structure):
+    """icpmi_normal_matrix: the normal equations of the pass that produced final_error"""
+    _fields_ = [("JtJ", C.c_double * 36), ("Jtb", C.c_double * 6), ("sum_sq", C.c_double), ("weight", C.c_double),
+                ("pairs", C.c_int64), ("T", C.c_double * 16)]
 
 
 class LoopConfig(C.Structure):
@@ -385,6 +393,10 @@ def load_library(path=None):
     L.icpmi_pose_graph_set_loop_loss.argtypes = [pg, C.c_int32, C.c_double]
     L.icpmi_pose_graph_loop_loss.argtypes = [pg, C.POINTER(C.c_int32), C.POINTER(C.c_double)]
     L.icpmi_pose_graph_loop_weights.argtypes = [pg, dp, dp, C.c_int64, i64p]
+    L.icpmi_pose_graph_add_odometry_information.argtypes = [pg, C.c_int64, C.c_int64, dp, dp]
+    L.icpmi_pose_graph_add_loop_closure_information.argtypes = [pg, C.c_int64, C.c_int64, dp, dp]
+    L.icpmi_information_from_icp.argtypes = [dp, dp, C.c_double, C.c_double, C.c_double, dp]
+    L.icpmi_last_normal_matrix.argtypes = [vp, C.c_int32, C.POINTER(NormalMatrix)]
     L.icpmi_map_create.argtypes = [vp, C.POINTER(vp)]
     L.icpmi_map_destroy.argtypes = [vp]
     L.icpmi_map_destroy.restype = None
@@ -426,6 +438,8 @@ def load_library(path=None):
     L.icpmi_loop_last_pairs.argtypes = [vp, i64p, C.c_int64, i64p]
     L.icpmi_loop_set_robust.argtypes = [vp, C.c_int32, C.c_double]
     L.icpmi_loop_last_weights.argtypes = [vp, dp, C.c_int64, i64p]
+    L.icpmi_loop_set_information.argtypes = [vp, C.c_double, C.c_double, C.c_double]
+    L.icpmi_loop_last_information.argtypes = [vp, dp, C.c_int64, i64p]
     L.icpmi_local_map_config_default.argtypes = [C.POINTER(LocalMapConfig)]
     L.icpmi_local_map_config_default.restype = None
     L.icpmi_local_map_create.argtypes = [vp, C.POINTER(LocalMapConfig), C.POINTER(vp)]
@@ -490,6 +504,24 @@ def _f64(a, cols=3):
 
 def _dp(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def information_from_icp(JtJ, T, sigma, floor_rotation_sigma=0.0, floor_translation_sigma=0.0):
+    """icpmi_information_from_icp: the 6 x 6 information of a pose-graph edge entered as rel = T (from the target's pose
+    to the source's) from the normal matrix JtJ of the registration that gave T.  sigma: the residual noise of one pair
+    in metres; the floors (0: none) are sigmas of an isotropic term that keeps a rank-deficient JtJ positive definite.
+    A pure host function: no context, no device."""
+    J = np.ascontiguousarray(JtJ, dtype=np.float64)
+    Tm = np.ascontiguousarray(T, dtype=np.float64)
+    if J.shape != (6, 6) or Tm.shape != (4, 4):
+        raise ValueError("expected a 6 x 6 normal matrix and a 4 x 4 transform")
+    out = np.zeros((6, 6))
+    rc = load_library().icpmi_information_from_icp(_dp(J), _dp(Tm), float(sigma), float(floor_rotation_sigma),
+                                                   float(floor_translation_sigma), _dp(out))
+    if rc != OK:
+        raise IcpError(rc, "information_from_icp: sigma must be finite and > 0, a floor 0 or finite and > 0, and "
+                           "JtJ and T finite")
+    return out
 
 
 class Context:
@@ -569,6 +601,23 @@ class Context:
             r = Result()
             C.memmove(C.byref(r), C.byref(res[i]), C.sizeof(Result))
             out.append((r, hist[i, :r.history_len].copy()))
+        return out
+
+    def last_normal_matrix(self, k=0):
+        """icpmi_last_normal_matrix: the normal equations of the pass that produced final_error of the last registration
+        this context ran (problem k of the last batch call) -> an object with JtJ (6 x 6), Jtb (6), sum_sq, weight, pairs
+        and T (4 x 4).  Raises IcpError(ERR_ARG) where no registration ran or its last pass kept no row."""
+        nm = NormalMatrix()
+        self._check(self._lib.icpmi_last_normal_matrix(self._h, int(k), C.byref(nm)))
+
+        class _N:
+            pass
+
+        out = _N()
+        out.JtJ = np.array(nm.JtJ[:]).reshape(6, 6)
+        out.Jtb = np.array(nm.Jtb[:])
+        out.sum_sq, out.weight, out.pairs = float(nm.sum_sq), float(nm.weight), int(nm.pairs)
+        out.T = np.array(nm.T[:]).reshape(4, 4)
         return out
 
     def align_device(self, src_ptr, n_src, tgt_ptr, n_tgt, cfg):

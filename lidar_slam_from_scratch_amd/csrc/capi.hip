@@ -53,6 +53,7 @@
 #include "loop_store.h"
 #include "pose_graph.h"
 #include "pose_graph_loss.h"
+#include "pose_graph_info.h"
 #include "local_map.h"
 
 using namespace icpmi;
@@ -268,6 +269,12 @@ struct icpmi_ctx {
     unsigned long long *h_want = nullptr; // host-mapped ring beside it: (iteration + 1) << 32 | rows the pass wanted listed
     unsigned long long *d_want = nullptr; // (lean passes: list_reuse.h; written by k_sum_groups)
     unsigned *h_stat = nullptr;    // pinned: list reuse's per-pass statistics on their way back (profiling)
+    // icpmi_last_normal_matrix: the sums of the pass that produced final_error of the last registration on this context,
+    // taken from the state that came back behind its one wait (LoopRun::fill_result); nm_count: the problems of the last
+    // batch this context led (problem k >= 1 ran on helper k - 1, which holds its record), 1 after a single call
+    icpmi_normal_matrix nm{};
+    bool nm_valid = false;
+    int nm_count = 1;
 
     // profiling
     std::vector<EventPair> ev_pool;
@@ -1206,6 +1213,8 @@ struct LoopRun {
     {
         int rc;
         ctx->loop_rows = -1; // (set again once this call has completed)
+        ctx->nm_valid = false;
+        ctx->nm_count = 1;
         if ((rc = reserve(ctx, ctx->cur, sizeof(double) * 3 * (size_t)n))) return rc;
         if ((rc = reserve(ctx, ctx->nrm, sizeof(double) * 3 * (size_t)m))) return rc;
         if ((rc = reserve(ctx, ctx->idx, sizeof(int) * (size_t)n))) return rc;
@@ -1691,6 +1700,21 @@ struct LoopRun {
             gate->weight_sum = gate->kind ? hs->sums[28] : 0.0;
         }
 
+        // The normal matrix of the pass that produced final_error.  Every finish kernel takes a pass's sums over only while
+        // the loop has not ended (`!ls.done`: finish_step_rows, k_finish_step_transform, k_finish_step_transform_cull), and
+        // the breaking and the post-loop step return in front of the solve: after a convergence break these are the
+        // breaking pass's sums, after exhaustion the post-loop pass's, both at `total`, whatever was queued behind.
+        {
+            icpmi_normal_matrix &nm = ctx->nm;
+            for (int a = 0, e = 0; a < 6; ++a)
+                for (int b = a; b < 6; ++b, ++e) nm.JtJ[6 * a + b] = nm.JtJ[6 * b + a] = hs->sums[e];
+            memcpy(nm.Jtb, hs->sums + 21, sizeof(double) * 6);
+            nm.sum_sq = hs->sums[27];
+            nm.weight = hs->sums[28];
+            nm.pairs = (int64_t)hs->sums[gate && gate->kind ? 29 : 28];
+            memcpy(nm.T, hs->total, sizeof(double) * 16);
+            ctx->nm_valid = nm.weight > 0.0; // (a gated or robust pass that kept no row leaves no matrix)
+        }
         memcpy(result->transformation, hs->total, sizeof(double) * 16); // icp.hpp:254
         result->converged = hs->converged;
         result->num_iterations = hs->hist_len - 1;                      // icp.hpp:255
@@ -2181,6 +2205,7 @@ int batch_run(icpmi_ctx *ctx, int32_t count, const std::function<int(icpmi_ctx *
         std::unique_lock<std::mutex> lk(w->mu);
         w->cv.wait(lk, [w] { return w->done; });
     }
+    ctx->nm_count = count; // (icpmi_last_normal_matrix: problem k's record is on the context that ran it)
     for (int k = 0; k < count; ++k)
         if (status[k] != ICPMI_OK) {
             if (k > 0) ctx->err = ctx->helpers[(size_t)k - 1]->helper->err;
@@ -2302,6 +2327,21 @@ int icpmi_align_robust_batch(icpmi_ctx *ctx, int32_t count, const double *const 
         return icpmi_align_robust(c, sources_xyz[k], n_src[k], targets_xyz[k], n_tgt[k], &cfgs[k], &rules[k], &results[k],
                                   infos ? &infos[k] : nullptr, error_history + (size_t)k * (size_t)history_stride, history_stride);
     }, status);
+}
+
+int icpmi_last_normal_matrix(icpmi_ctx *ctx, int32_t k, icpmi_normal_matrix *out)
+{
+    if (!ctx) return ICPMI_ERR_NULL;
+    if (!out) return fail(ctx, ICPMI_ERR_NULL, "out is NULL");
+    if (ctx->comm || ctx->cb_allreduce)
+        return fail(ctx, ICPMI_ERR_ARG, "a context with a communicator keeps no normal matrix (its sums are the ranks' shares)");
+    if (k < 0 || k >= ctx->nm_count)
+        return fail(ctx, ICPMI_ERR_ARG, "problem %d: the last registration call on this context ran %d", (int)k, ctx->nm_count);
+    const icpmi_ctx *c = k == 0 ? ctx : ctx->helpers[(size_t)k - 1]->helper;
+    if (!c->nm_valid)
+        return fail(ctx, ICPMI_ERR_ARG, "no normal matrix: no registration ran, it failed, or its last pass kept no row");
+    *out = c->nm;
+    return ICPMI_OK;
 }
 
 int icpmi_nearest_batch(icpmi_ctx *ctx, const double *targets_xyz, int64_t n_tgt,
@@ -2808,6 +2848,8 @@ int stream_register(icpmi_ctx *ctx, int64_t n_cur, int64_t min_points, const icp
     int rc;
     info->n_filtered = n_cur;
     info->n_target = ctx->stream_prev_n < 0 ? 0 : ctx->stream_prev_n;
+    ctx->nm_valid = false; // (a push that registers nothing leaves no normal matrix)
+    ctx->nm_count = 1;
     ctx->stream_robust_info = icpmi_robust_info{};
     GateRun rule{};
     if (ctx->stream_robust_on && (rc = validate_robust(ctx, &ctx->stream_robust, &rule))) return rc; // (a communicator set since)
@@ -3593,10 +3635,15 @@ struct icpmi_pose_graph {
     int opt_factors = 0;                 // factors and loop factors of that optimize()
     int64_t opt_loops = 0;
     size_t uploaded_factors = 0;         // factors already in d_fac
+    // full-information factors (pose_graph_info.h): info_slot[f] = position of factor f's R among info_R's blocks of 21
+    // doubles, -1 for a diagonal factor.  Both go up incrementally, and only once the graph holds an information factor.
+    std::vector<int32_t> info_slot;
+    std::vector<double> info_R;
+    size_t uploaded_slots = 0, uploaded_R = 0;   // entries of info_slot in d_slot, doubles of info_R in d_infoR
     int64_t init_dirty_lo = INT64_MAX, init_dirty_hi = 0;   // pose range of estimates not yet in d_init
     DevBuf d_fac, d_init, d_map, d_keys, d_X, d_Xc, d_A, d_rw, d_err, d_H, d_g, d_D, d_gn, d_Cn, d_L, d_U, d_Y,
         d_schur, d_S, d_xb, d_delta, d_errc, d_errl, d_out, d_status, d_inc_ptr, d_inc, d_cn_ptr, d_cn, d_segs,
-        d_blocks, d_codes, d_sep_node, d_sep_segs, d_sep_pos, d_node_seg, d_rank, d_wd;
+        d_blocks, d_codes, d_sep_node, d_sep_segs, d_sep_pos, d_node_seg, d_rank, d_wd, d_slot, d_infoR;
     double *h_out = nullptr;             // pinned: the two sums and the status of a trial
     icpmi_pose_graph_info last{};        // of the last optimize()
 };
@@ -3661,6 +3708,28 @@ void pg_factor(PgFactor &f, int kind, int64_t i, int64_t j, const double *T, dou
     }
 }
 
+// the information matrix of a new factor -> R's upper triangle, or ICPMI_ERR_ARG with the reason
+int pg_factor_information(icpmi_ctx *ctx, const double *info, double *R21)
+{
+    switch (pg_info_cholesky(info, R21)) {
+    case kPgInfoOk: return ICPMI_OK;
+    case kPgInfoNotFinite: return fail(ctx, ICPMI_ERR_ARG, "non-finite information matrix entry");
+    case kPgInfoAsymmetric: return fail(ctx, ICPMI_ERR_ARG, "the information matrix is not symmetric");
+    default: return fail(ctx, ICPMI_ERR_ARG, "the information matrix is not positive definite (a Cholesky pivot is not > 0)");
+    }
+}
+
+// the slot of the factor just pushed: R21 null for a diagonal factor
+void pg_push_slot(icpmi_pose_graph *g, const double *R21)
+{
+    if (!R21) {
+        g->info_slot.push_back(-1);
+        return;
+    }
+    g->info_slot.push_back((int32_t)(g->info_R.size() / 21));
+    g->info_R.insert(g->info_R.end(), R21, R21 + 21);
+}
+
 template <class T> int pg_upload(icpmi_ctx *ctx, DevBuf &b, const std::vector<T> &v)
 {
     int rc;
@@ -3675,6 +3744,7 @@ unsigned pg_grid(size_t n, unsigned b) { return (unsigned)((n + b - 1) / b); }
 struct PgPlan {
     int n = 0, F = 0, nb = 0, nseg = 0, nblocks = 0, nloops = 0;
     bool loss = false;                   // the loss is on and the graph has a loop factor: the kernels of pose_graph_loss.h
+    bool info = false;                   // the graph has an information factor: the kernels of pose_graph_info.h
     std::vector<int32_t> keys, map;
 };
 
@@ -3796,6 +3866,7 @@ int pg_plan(icpmi_pose_graph *g, PgPlan &P)
     for (int f = 0; f < F; ++f)
         if (g->factors[f].reserved == 1) rank[f] = P.nloops++;
     P.loss = g->loss_kind != ICPMI_PG_LOSS_NONE && P.nloops > 0;
+    P.info = !g->info_R.empty();
     std::vector<int32_t> codes;
     for (size_t b = 0; b < blocks.size(); ++b) {
         blocks[b].begin = (int32_t)codes.size();
@@ -3881,7 +3952,13 @@ int pg_trial(icpmi_pose_graph *g, const PgPlan &P, const PgLin &lin, double lam,
                        (const double *)g->d_xb.p, n, (double *)g->d_delta.p);
     hipLaunchKernelGGL(k_pg_retract, dim3(pg_grid(n, 128)), dim3(128), 0, s, (const double *)g->d_X.p,
                        (const double *)g->d_delta.p, n, (double *)g->d_Xc.p);
-    if (P.loss)
+    if (P.info)
+        hipLaunchKernelGGL(k_pg_trial_info, dim3(pg_grid(F, 128)), dim3(128), 0, s, (const PgFactor *)g->d_fac.p,
+                           (const int32_t *)g->d_slot.p, (const double *)g->d_infoR.p, (const int32_t *)g->d_map.p, F,
+                           (const double *)g->d_Xc.p, lin, (const double *)g->d_delta.p,
+                           P.loss ? (int)g->loss_kind : kPgLossNone, g->loss_scale, (double *)g->d_errc.p,
+                           (double *)g->d_errl.p);
+    else if (P.loss)
         hipLaunchKernelGGL(k_pg_trial_loss, dim3(pg_grid(F, 128)), dim3(128), 0, s, (const PgFactor *)g->d_fac.p,
                            (const int32_t *)g->d_map.p, F, (const double *)g->d_Xc.p, lin, (const double *)g->d_delta.p,
                            (int)g->loss_kind, g->loss_scale, (double *)g->d_errc.p, (double *)g->d_errl.p);
@@ -3899,24 +3976,28 @@ int pg_linearize(icpmi_pose_graph *g, const PgPlan &P, const PgLin &lin, double 
 {
     icpmi_ctx *ctx = g->ctx;
     hipStream_t s = ctx->stream;
-    if (P.loss) {
+    if (P.info)
+        hipLaunchKernelGGL(k_pg_linearize_info, dim3(pg_grid(P.F, kPgInfoThreads)), dim3(kPgInfoThreads), 0, s, (const PgFactor *)g->d_fac.p,
+                           (const int32_t *)g->d_slot.p, (const double *)g->d_infoR.p, (const int32_t *)g->d_map.p, P.F,
+                           (const double *)g->d_X.p, lin, P.loss ? (int)g->loss_kind : kPgLossNone, g->loss_scale,
+                           P.loss ? (double *)g->d_errl.p : nullptr);
+    else if (P.loss)
         hipLaunchKernelGGL(k_pg_linearize_loss, dim3(pg_grid(P.F, 128)), dim3(128), 0, s, (const PgFactor *)g->d_fac.p,
                            (const int32_t *)g->d_map.p, P.F, (const double *)g->d_X.p, lin, (int)g->loss_kind,
                            g->loss_scale, (double *)g->d_errl.p);
-        hipLaunchKernelGGL(k_pg_assemble, dim3(pg_grid(78 * (size_t)P.n, 256)), dim3(256), 0, s, lin,
-                           (const int32_t *)g->d_inc_ptr.p, (const int32_t *)g->d_inc.p, (const int32_t *)g->d_cn_ptr.p,
-                           (const int32_t *)g->d_cn.p, P.n, (double *)g->d_D.p, (double *)g->d_gn.p, (double *)g->d_Cn.p);
+    else
+        hipLaunchKernelGGL(k_pg_linearize, dim3(pg_grid(P.F, 128)), dim3(128), 0, s, (const PgFactor *)g->d_fac.p,
+                           (const int32_t *)g->d_map.p, P.F, (const double *)g->d_X.p, lin);
+    hipLaunchKernelGGL(k_pg_assemble, dim3(pg_grid(78 * (size_t)P.n, 256)), dim3(256), 0, s, lin,
+                       (const int32_t *)g->d_inc_ptr.p, (const int32_t *)g->d_inc.p, (const int32_t *)g->d_cn_ptr.p,
+                       (const int32_t *)g->d_cn.p, P.n, (double *)g->d_D.p, (double *)g->d_gn.p, (double *)g->d_Cn.p);
+    if (P.loss) {
         double out[3];
         int rc = pg_sums(g, lin.err, (const double *)g->d_errl.p, P.F, out);
         if (error) *error = out[0];
         *lin0 = out[1];
         return rc;
     }
-    hipLaunchKernelGGL(k_pg_linearize, dim3(pg_grid(P.F, 128)), dim3(128), 0, s, (const PgFactor *)g->d_fac.p,
-                       (const int32_t *)g->d_map.p, P.F, (const double *)g->d_X.p, lin);
-    hipLaunchKernelGGL(k_pg_assemble, dim3(pg_grid(78 * (size_t)P.n, 256)), dim3(256), 0, s, lin,
-                       (const int32_t *)g->d_inc_ptr.p, (const int32_t *)g->d_inc.p, (const int32_t *)g->d_cn_ptr.p,
-                       (const int32_t *)g->d_cn.p, P.n, (double *)g->d_D.p, (double *)g->d_gn.p, (double *)g->d_Cn.p);
     if (!error) return ICPMI_OK;
     double out[3];
     int rc = pg_sums(g, lin.err, nullptr, P.F, out);
@@ -3978,7 +4059,7 @@ void icpmi_pose_graph_destroy(icpmi_pose_graph *g)
                       &g->d_H, &g->d_g, &g->d_D, &g->d_gn, &g->d_Cn, &g->d_L, &g->d_U, &g->d_Y, &g->d_schur, &g->d_S,
                       &g->d_xb, &g->d_delta, &g->d_errc, &g->d_errl, &g->d_out, &g->d_status, &g->d_inc_ptr, &g->d_inc,
                       &g->d_cn_ptr, &g->d_cn, &g->d_segs, &g->d_blocks, &g->d_codes, &g->d_sep_node, &g->d_sep_segs,
-                      &g->d_sep_pos, &g->d_node_seg, &g->d_rank, &g->d_wd};
+                      &g->d_sep_pos, &g->d_node_seg, &g->d_rank, &g->d_wd, &g->d_slot, &g->d_infoR};
     for (DevBuf *b : bufs) release(*b);
     if (g->h_out) (void)hipHostFree(g->h_out);
     delete g;
@@ -3994,13 +4075,16 @@ int icpmi_pose_graph_add_prior(icpmi_pose_graph *g, int64_t index, const double 
     PgFactor f;
     pg_factor(f, 0, index, -1, pose, c, t);
     g->factors.push_back(f);                       // graph_->addPrior (pose_graph.cpp:72)
+    g->info_slot.push_back(-1);
     if (!pg_has(g, index)) pg_set_init(g, index, f.Z);   // :75-78; optimized_ is left as it is
     return ICPMI_OK;
 }
 
-int icpmi_pose_graph_add_odometry(icpmi_pose_graph *g, int64_t from, int64_t to, const double rel[16], double fitness)
+// addOdometryFactor with either noise model: `info` null, the reference's diagonal sigmas scaled by 1 + 10 fitness; else
+// the 6 x 6 information matrix, factored here and refused before anything changes
+static int pg_add_odometry(icpmi_pose_graph *g, int64_t from, int64_t to, const double rel[16], double fitness,
+                           const double *info)
 {
-    if (!g) return ICPMI_ERR_NULL;
     int rc;
     if ((rc = pg_check_T(g->ctx, rel))) return rc;
     if (from < 0 || to < 0 || from >= INT32_MAX - 1 || to >= INT32_MAX - 1 || from == to || !std::isfinite(fitness))
@@ -4008,10 +4092,13 @@ int icpmi_pose_graph_add_odometry(icpmi_pose_graph *g, int64_t from, int64_t to,
     const bool need = !pg_has(g, to);
     if (need && !pg_has(g, from))                  // Values::at throws in the reference (pose_graph.cpp:104)
         return fail(g->ctx, ICPMI_ERR_ARG, "pose %lld has no estimate", (long long)from);
+    double R21[21];
+    if (info && (rc = pg_factor_information(g->ctx, info, R21))) return rc;
     const double scale = 1.0 + fitness * 10.0;     // :88
     PgFactor f;
     pg_factor(f, 1, from, to, rel, g->cfg.odom_rotation_sigma * scale, g->cfg.odom_translation_sigma * scale);
     g->factors.push_back(f);                       // :99-101
+    pg_push_slot(g, info ? R21 : nullptr);
     if (need) {                                    // :103-110: X_to = X_from * Z (Pose3::compose)
         const double *a = g->init.data() + 12 * from, *b = f.Z;
         double o[12];
@@ -4024,19 +4111,59 @@ int icpmi_pose_graph_add_odometry(icpmi_pose_graph *g, int64_t from, int64_t to,
     return ICPMI_OK;
 }
 
-int icpmi_pose_graph_add_loop_closure(icpmi_pose_graph *g, int64_t from, int64_t to, const double rel[16])
+static int pg_add_loop_closure(icpmi_pose_graph *g, int64_t from, int64_t to, const double rel[16], const double *info)
 {
-    if (!g) return ICPMI_ERR_NULL;
     int rc;
     if ((rc = pg_check_T(g->ctx, rel))) return rc;
     if (from < 0 || to < 0 || from >= INT32_MAX - 1 || to >= INT32_MAX - 1 || from == to)
         return fail(g->ctx, ICPMI_ERR_ARG, "bad loop closure");
+    double R21[21];
+    if (info && (rc = pg_factor_information(g->ctx, info, R21))) return rc;
     PgFactor f;
     pg_factor(f, 1, from, to, rel, g->cfg.loop_rotation_sigma, g->cfg.loop_translation_sigma);
     f.reserved = 1;
     g->factors.push_back(f);                       // pose_graph.cpp:132-134
+    pg_push_slot(g, info ? R21 : nullptr);
     g->num_loops++;                                // :136
     g->optimized = false;                          // :137
+    return ICPMI_OK;
+}
+
+int icpmi_pose_graph_add_odometry(icpmi_pose_graph *g, int64_t from, int64_t to, const double rel[16], double fitness)
+{
+    if (!g) return ICPMI_ERR_NULL;
+    return pg_add_odometry(g, from, to, rel, fitness, nullptr);
+}
+
+int icpmi_pose_graph_add_loop_closure(icpmi_pose_graph *g, int64_t from, int64_t to, const double rel[16])
+{
+    if (!g) return ICPMI_ERR_NULL;
+    return pg_add_loop_closure(g, from, to, rel, nullptr);
+}
+
+int icpmi_pose_graph_add_odometry_information(icpmi_pose_graph *g, int64_t from, int64_t to, const double rel[16],
+                                              const double info[36])
+{
+    if (!g) return ICPMI_ERR_NULL;
+    if (!info) return fail(g->ctx, ICPMI_ERR_NULL, "info is NULL");
+    return pg_add_odometry(g, from, to, rel, 0.0, info);
+}
+
+int icpmi_pose_graph_add_loop_closure_information(icpmi_pose_graph *g, int64_t from, int64_t to, const double rel[16],
+                                                  const double info[36])
+{
+    if (!g) return ICPMI_ERR_NULL;
+    if (!info) return fail(g->ctx, ICPMI_ERR_NULL, "info is NULL");
+    return pg_add_loop_closure(g, from, to, rel, info);
+}
+
+int icpmi_information_from_icp(const double JtJ[36], const double T[16], double sigma, double floor_rotation_sigma,
+                               double floor_translation_sigma, double info_out[36])
+{
+    if (!JtJ || !T || !info_out) return ICPMI_ERR_NULL;
+    double out[36];
+    if (!pg_information_from_icp(JtJ, T, sigma, floor_rotation_sigma, floor_translation_sigma, out)) return ICPMI_ERR_ARG;
+    memcpy(info_out, out, sizeof(out));
     return ICPMI_OK;
 }
 
@@ -4079,6 +4206,20 @@ int icpmi_pose_graph_optimize(icpmi_pose_graph *g, icpmi_pose_graph_info *info, 
         HIP_TRY(ctx, hipMemcpyAsync((PgFactor *)g->d_fac.p + g->uploaded_factors, g->factors.data() + g->uploaded_factors,
                                     sizeof(PgFactor) * (F - g->uploaded_factors), hipMemcpyHostToDevice, s));
     g->uploaded_factors = F;
+    if (!g->info_R.empty()) {   // the slots of all factors and the new R go up from the first information factor on
+        const size_t nR = g->info_R.size();
+        if ((rc = pg_reserve_keep(ctx, g->d_slot, sizeof(int32_t) * g->uploaded_slots, sizeof(int32_t) * F)) ||
+            (rc = pg_reserve_keep(ctx, g->d_infoR, sizeof(double) * g->uploaded_R, sizeof(double) * nR)))
+            return rc;
+        if (F > g->uploaded_slots)
+            HIP_TRY(ctx, hipMemcpyAsync((int32_t *)g->d_slot.p + g->uploaded_slots, g->info_slot.data() + g->uploaded_slots,
+                                        sizeof(int32_t) * (F - g->uploaded_slots), hipMemcpyHostToDevice, s));
+        if (nR > g->uploaded_R)
+            HIP_TRY(ctx, hipMemcpyAsync((double *)g->d_infoR.p + g->uploaded_R, g->info_R.data() + g->uploaded_R,
+                                        sizeof(double) * (nR - g->uploaded_R), hipMemcpyHostToDevice, s));
+        g->uploaded_slots = F;
+        g->uploaded_R = nR;
+    }
     const size_t init_used = g->d_init.cap / 96 * 96;
     if ((rc = pg_reserve_keep(ctx, g->d_init, init_used, 96 * (size_t)g->num_poses))) return rc;
     if (g->init_dirty_hi > g->init_dirty_lo) {
@@ -4229,9 +4370,15 @@ int icpmi_pose_graph_loop_weights(icpmi_pose_graph *g, double *weights, double *
     if (nl == 0) return ICPMI_OK;
     hipStream_t s = ctx->stream;
     const int F = g->opt_factors;
-    hipLaunchKernelGGL(k_pg_loop_weights, dim3(pg_grid(F, 128)), dim3(128), 0, s, (const PgFactor *)g->d_fac.p,
-                       (const int32_t *)g->d_map.p, (const int32_t *)g->d_rank.p, F, (const double *)g->d_X.p,
-                       (int)g->loss_kind, g->loss_scale, (double *)g->d_wd.p);
+    if (!g->info_R.empty())   // (the optimised state holds: every factor's slot went up with that optimize())
+        hipLaunchKernelGGL(k_pg_loop_weights_info, dim3(pg_grid(F, 128)), dim3(128), 0, s, (const PgFactor *)g->d_fac.p,
+                           (const int32_t *)g->d_slot.p, (const double *)g->d_infoR.p, (const int32_t *)g->d_map.p,
+                           (const int32_t *)g->d_rank.p, F, (const double *)g->d_X.p, (int)g->loss_kind, g->loss_scale,
+                           (double *)g->d_wd.p);
+    else
+        hipLaunchKernelGGL(k_pg_loop_weights, dim3(pg_grid(F, 128)), dim3(128), 0, s, (const PgFactor *)g->d_fac.p,
+                           (const int32_t *)g->d_map.p, (const int32_t *)g->d_rank.p, F, (const double *)g->d_X.p,
+                           (int)g->loss_kind, g->loss_scale, (double *)g->d_wd.p);
     std::vector<double> wd(2 * (size_t)nl);
     HIP_TRY(ctx, hipMemcpyAsync(wd.data(), g->d_wd.p, sizeof(double) * wd.size(), hipMemcpyDeviceToHost, s));
     HIP_TRY(ctx, hipStreamSynchronize(s));
@@ -5303,6 +5450,8 @@ struct icpmi_loop {
     int32_t robust_kind = 0;             // icpmi_loop_set_robust (0: off)
     double robust_scale = 0.0;
     std::vector<double> last_weights;    // per result of the last detect its weight sum (-1: the weights were off)
+    double info_sigma = 0.0, info_floor_r = 0.0, info_floor_t = 0.0;   // icpmi_loop_set_information (sigma 0: off)
+    std::vector<double> last_info;       // 36 per result of the last detect (empty: the setting was off)
 };
 
 namespace {
@@ -5484,6 +5633,7 @@ int icpmi_loop_detect(icpmi_loop *L, icpmi_loop_result *out, int64_t cap, int64_
     L->last_shifts.clear();
     L->last_pairs.clear();
     L->last_weights.clear();
+    L->last_info.clear();
     const bool guess = L->yaw_guess;
     const bool gated = L->gate > 0.0;
     const int32_t robust = L->robust_kind;
@@ -5601,6 +5751,14 @@ int icpmi_loop_detect(icpmi_loop *L, icpmi_loop_result *out, int64_t cap, int64_
                 L->last_shifts.push_back(guess ? shift_of[(size_t)cand.second] : -1);
                 L->last_pairs.push_back(gated ? gates[k].pairs : -1);
                 L->last_weights.push_back(robust ? gates[k].weight_sum : -1.0);
+                if (L->info_sigma > 0.0) { // the verification's own normal matrix, on the context that ran it
+                    icpmi_normal_matrix nm;
+                    double info[36];
+                    if ((rc = icpmi_last_normal_matrix(ctx, k, &nm))) return rc;
+                    if ((rc = icpmi_information_from_icp(nm.JtJ, nm.T, L->info_sigma, L->info_floor_r, L->info_floor_t, info)))
+                        return fail(ctx, rc, "loop store: the information of an accepted closure is not finite");
+                    L->last_info.insert(L->last_info.end(), info, info + 36);
+                }
                 ++verified;
             }
         }
@@ -5642,6 +5800,35 @@ int icpmi_loop_set_robust(icpmi_loop *L, int32_t kind, double scale)
     if (!(scale > 0.0) || !std::isfinite(scale)) return fail(L->map->ctx, ICPMI_ERR_ARG, "scale must be finite and > 0");
     L->robust_kind = kind;
     L->robust_scale = scale;
+    return ICPMI_OK;
+}
+
+int icpmi_loop_set_information(icpmi_loop *L, double sigma, double floor_rotation_sigma, double floor_translation_sigma)
+{
+    if (!L) return ICPMI_ERR_NULL;
+    if (sigma == 0.0) {
+        L->info_sigma = L->info_floor_r = L->info_floor_t = 0.0;
+        return ICPMI_OK;
+    }
+    const double eye[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    double zero[36] = {0.0}, out[36];
+    if (icpmi_information_from_icp(zero, eye, sigma, floor_rotation_sigma, floor_translation_sigma, out) != ICPMI_OK)
+        return fail(L->map->ctx, ICPMI_ERR_ARG, "sigma must be 0 (off) or finite and > 0, a floor 0 or finite and > 0");
+    L->info_sigma = sigma;
+    L->info_floor_r = floor_rotation_sigma;
+    L->info_floor_t = floor_translation_sigma;
+    return ICPMI_OK;
+}
+
+int icpmi_loop_last_information(const icpmi_loop *L, double *info, int64_t cap, int64_t *n_out)
+{
+    if (!L) return ICPMI_ERR_NULL;
+    icpmi_ctx *ctx = L->map->ctx;
+    if (!n_out || (!info && cap > 0)) return fail(ctx, ICPMI_ERR_NULL, "null argument");
+    const int64_t n = (int64_t)L->last_info.size() / 36;
+    *n_out = n;
+    if (n > cap) return fail(ctx, ICPMI_ERR_CAPACITY, "output holds %lld matrices, needs %lld", (long long)cap, (long long)n);
+    if (n) memcpy(info, L->last_info.data(), sizeof(double) * 36 * (size_t)n);
     return ICPMI_OK;
 }
 

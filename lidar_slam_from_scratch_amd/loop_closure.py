@@ -26,6 +26,12 @@ LoopClosureConfig(robust_kind=k, robust_scale=s) with k one of capi.ROBUST_* (no
 verifications under robust row weights (icpmi_align_robust), with the gate above if that is set too.  align / align_many
 are then passed keyword-only robust=(kind, scale), and their results carry `weight_sum`.  icp_fitness is then the WEIGHTED
 RMS, which reads lower than the plain one against icp_fitness_threshold.  0 (the default) passes nothing.
+
+LoopClosureConfig(information_sigma=s, information_floor=(sigma_R, sigma_t)) with s > 0 (not in the reference)
+attaches to each result the 6 x 6 information matrix of its edge, icpmi_information_from_icp on that verification's own
+normal matrix (icpmi_last_normal_matrix) and transform: what PoseGraph.add_loop_closure_information(match, query,
+transform, information) takes.  align / align_many are then passed keyword-only information=(s, sigma_R, sigma_t), and their
+results carry `information`.  0 (the default) passes nothing.
 """
 import ctypes as C
 import weakref
@@ -39,7 +45,10 @@ class LoopClosureConfig:
     """loop_closure.hpp:14-19"""
 
     def __init__(self, frame_gap=50, sc_distance_threshold=0.25, icp_fitness_threshold=0.3, max_candidates=3,
-                 yaw_guess=False, max_correspondence_distance=0.0, robust_kind=0, robust_scale=0.0):
+                 yaw_guess=False, max_correspondence_distance=0.0, robust_kind=0, robust_scale=0.0,
+                 information_sigma=0.0, information_floor=(0.0, 0.0)):
+        self.information_sigma = information_sigma
+        self.information_floor = information_floor
         self.yaw_guess = yaw_guess
         self.robust_kind = robust_kind
         self.robust_scale = robust_scale
@@ -53,10 +62,11 @@ class LoopClosureConfig:
 class LoopClosureResult:
     """loop_closure.hpp:25-31; sector_shift: the column shift the verification started from (None: yaw_guess off);
     pairs: the rows the verification's last pass kept (None: no correspondence-distance gate); weight_sum: that pass's
-    weight sum (None: no robust weights)"""
+    weight sum (None: no robust weights); information: the edge's 6 x 6 information matrix (None: information_sigma off)"""
 
     def __init__(self, query_frame, match_frame, transform, scan_context_distance, icp_fitness, sector_shift=None,
-                 pairs=None, weight_sum=None):
+                 pairs=None, weight_sum=None, information=None):
+        self.information = information
         self.sector_shift = sector_shift
         self.weight_sum = weight_sum
         self.pairs = pairs
@@ -81,21 +91,24 @@ class GpuBackend:
         """-> (distances, the smallest column shift attaining each), icpmi_scan_context_distances_shift"""
         return self.ctx.scan_context_distances_shift(query_desc, hist_descs)
 
-    def align(self, source, target, max_iterations, tolerance, *, initial_transform=None, max_distance=None, robust=None):
-        if initial_transform is None and max_distance is None and robust is None:
+    def align(self, source, target, max_iterations, tolerance, *, initial_transform=None, max_distance=None, robust=None,
+              information=None):
+        if initial_transform is None and max_distance is None and robust is None and information is None:
             from .odometry import gpu_align
             return gpu_align(self.ctx)(source, target, max_iterations, tolerance)
         return self.align_many(source, [target], max_iterations, tolerance,
                                initial_transforms=None if initial_transform is None else [initial_transform],
-                               max_distance=max_distance, robust=robust)[0]
+                               max_distance=max_distance, robust=robust, information=information)[0]
 
     def align_many(self, source, targets, max_iterations, tolerance, *, initial_transforms=None, max_distance=None,
-                   robust=None):
+                   robust=None, information=None):
         """The verifications of one detect() side by side on the GPU (icpmi_align_batch): same results as
         align() one after the other.  initial_transforms: one 4 x 4 per target (None: the identity for all).
         max_distance: the correspondence-distance gate (icpmi_align_gated_batch; None: none); the results then carry
         `pairs`.  robust: (kind, scale), the row weights (icpmi_align_robust_batch, behind max_distance if that is given
-        too; None: none); the results then carry `weight_sum` as well."""
+        too; None: none); the results then carry `weight_sum` as well.  information: (sigma, floor sigma_R, floor sigma_t);
+        the results then carry `information`, capi.information_from_icp of problem k's normal matrix (None where its
+        last pass kept no row: such a result has an infinite final_error and is never accepted)."""
         from . import capi
 
         class _R:
@@ -115,8 +128,14 @@ class GpuBackend:
         else:
             runs = [(res, pairs, None) for res, _hist, pairs in
                     self.ctx.align_gated_batch([source] * len(targets), targets, cfg, float(max_distance))]
-        for res, pairs, weight_sum in runs:
+        for k, (res, pairs, weight_sum) in enumerate(runs):
             r = _R()
+            if information is not None:
+                try:
+                    nm = self.ctx.last_normal_matrix(k)
+                    r.information = capi.information_from_icp(nm.JtJ, nm.T, *information)
+                except capi.IcpError:
+                    r.information = None
             r.transformation = np.array(res.transformation[:]).reshape(4, 4)
             r.converged, r.final_error, r.num_iterations = bool(res.converged), res.final_error, res.num_iterations
             r.pairs = pairs
@@ -172,6 +191,10 @@ class LoopClosureDetector:
         gated = gate > 0.0
         if robust:
             gkw["robust"] = (kind, float(self.config.robust_scale))
+        info_sigma = float(getattr(self.config, "information_sigma", 0.0) or 0.0)
+        if info_sigma > 0.0:
+            floor = getattr(self.config, "information_floor", (0.0, 0.0))
+            gkw["information"] = (info_sigma, float(floor[0]), float(floor[1]))
         if guess:
             dist, shift = self.backend.distances_shift(self._descriptors[q], hist)
         else:
@@ -208,7 +231,8 @@ class LoopClosureDetector:
                                                      np.asarray(r.transformation), sc_dist, r.final_error,
                                                      int(shift[cand]) if guess else None,
                                                      getattr(r, "pairs", None) if gated else None,
-                                                     getattr(r, "weight_sum", None) if robust else None))
+                                                     getattr(r, "weight_sum", None) if robust else None,
+                                                     getattr(r, "information", None) if info_sigma > 0.0 else None))
                     verified += 1
         return results
 
@@ -239,6 +263,11 @@ class StoreLoopClosureDetector:
         self._robust = int(getattr(self.config, "robust_kind", 0) or 0) != 0
         if self._robust:
             ctx._check(self._lib.icpmi_loop_set_robust(h, int(self.config.robust_kind), float(self.config.robust_scale)))
+        self._information = float(getattr(self.config, "information_sigma", 0.0) or 0.0) > 0.0
+        if self._information:
+            floor = getattr(self.config, "information_floor", (0.0, 0.0))
+            ctx._check(self._lib.icpmi_loop_set_information(h, float(self.config.information_sigma), float(floor[0]),
+                                                            float(floor[1])))
         for owner in (ctx, store):     # Context.close() and store.close() destroy it before the map
             if not hasattr(owner, "_loops"):
                 owner._loops = weakref.WeakSet()
@@ -260,6 +289,12 @@ class StoreLoopClosureDetector:
         """icpmi_loop_set_robust: the verifications' row weights from the next detect on (kind 0: off)"""
         self.ctx._check(self._lib.icpmi_loop_set_robust(self._h, int(kind), float(scale)))
         self._robust = int(kind) != 0
+
+    def set_information(self, sigma, floor_rotation_sigma=0.0, floor_translation_sigma=0.0):
+        """icpmi_loop_set_information: each result's edge information from the next detect on (sigma 0: off)"""
+        self.ctx._check(self._lib.icpmi_loop_set_information(self._h, float(sigma), float(floor_rotation_sigma),
+                                                             float(floor_translation_sigma)))
+        self._information = float(sigma) > 0.0
 
     def add_frame(self, store_frame, frame_idx):
         """loop_closure.hpp:54-60 for the cloud the store holds as frame `store_frame`"""
@@ -306,6 +341,12 @@ class StoreLoopClosureDetector:
             m = C.c_int64(0)
             self.ctx._check(self._lib.icpmi_loop_last_weights(self._h, wt, n.value, C.byref(m)))
             weights = [float(v) for v in wt[:m.value]]
+        infos = [None] * n.value
+        if self._information:
+            mats = np.zeros((max(n.value, 1), 6, 6))
+            m = C.c_int64(0)
+            self.ctx._check(self._lib.icpmi_loop_last_information(self._h, capi._dp(mats), n.value, C.byref(m)))
+            infos = [mats[i].copy() for i in range(m.value)]
         return [LoopClosureResult(r.query_frame, r.match_frame, np.array(r.transform[:]).reshape(4, 4),
-                                  r.scan_context_distance, r.icp_fitness, s, p, w)
-                for r, s, p, w in zip(buf[:n.value], shifts, pairs, weights)]
+                                  r.scan_context_distance, r.icp_fitness, s, p, w, a)
+                for r, s, p, w, a in zip(buf[:n.value], shifts, pairs, weights, infos)]

@@ -87,6 +87,28 @@ class PoseGraph:
         T = _T(relative_transform)
         self.ctx._check(self._lib.icpmi_pose_graph_add_loop_closure(self._h, int(from_idx), int(to_idx), capi._dp(T)))
 
+    @staticmethod
+    def _info(information):
+        A = np.ascontiguousarray(information, dtype=np.float64)
+        if A.shape != (6, 6):
+            raise ValueError("expected a 6 x 6 information matrix")
+        return A
+
+    def add_odometry_information(self, from_idx, to_idx, relative_transform, information):
+        """add_odometry_factor weighted by a full 6 x 6 information matrix in the factor's tangent order (omega, v)
+        instead of the config's sigmas (icpmi_pose_graph_add_odometry_information; not in the reference).  A matrix
+        that is not finite, symmetric and positive definite raises IcpError(ERR_ARG) and changes nothing."""
+        T, A = _T(relative_transform), self._info(information)
+        self.ctx._check(self._lib.icpmi_pose_graph_add_odometry_information(self._h, int(from_idx), int(to_idx),
+                                                                            capi._dp(T), capi._dp(A)))
+
+    def add_loop_closure_information(self, from_idx, to_idx, relative_transform, information):
+        """add_loop_closure weighted by a full 6 x 6 information matrix (icpmi_pose_graph_add_loop_closure_information);
+        the loop loss and loop_weights() see it as any loop closure, with d = ||R r||."""
+        T, A = _T(relative_transform), self._info(information)
+        self.ctx._check(self._lib.icpmi_pose_graph_add_loop_closure_information(self._h, int(from_idx), int(to_idx),
+                                                                                capi._dp(T), capi._dp(A)))
+
     def set_loop_loss(self, kind, scale=0.0):
         """A robust loss on the loop-closure edges (icpmi_pose_graph_set_loop_loss; not in the reference): kind one of
         capi.PG_LOSS_*, scale in sigmas.  The graph's setting: every loop closure, past and future, at the next

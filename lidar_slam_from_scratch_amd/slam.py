@@ -27,7 +27,8 @@ from . import loop_closure as lc
 class SlamRun:
     def __init__(self):
         self.poses = [np.eye(4)]      # slam_node.cpp:64
-        self.factors = []             # ("prior", i, T) / ("odom", i, j, T, fitness) / ("loop", i, j, T), in call order
+        self.factors = []             # ("prior", i, T) / ("odom", i, j, T, fitness) / ("loop", i, j, T), in call order;
+        #                               with edge_information also ("odom_info", i, j, T, info) / ("loop_info", i, j, T, info)
         self.closures = []            # LoopClosureResult, in the order found
         self.optimizations = []       # (frame index or "end", ok, stats) per optimize()
         self.recent_world = []        # with a global map: recent_clouds_world_ after each successful optimize
@@ -49,7 +50,8 @@ def node_loop_config():
 def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, pose_graph_config=None,
              align=None, loop_backend=None, pose_graph=None, global_map=None, grid=None, map_voxel=1.0,
              loop_on_device=False, raycast=False, counts=False, live=False, loop_yaw_guess=False, loop_gate=None,
-             ground=None, odom_robust=None, loop_robust=None, odom_local_map=None, loop_edge_loss=None):
+             ground=None, odom_robust=None, loop_robust=None, odom_local_map=None, loop_edge_loss=None,
+             edge_information=None, information_floor=(1.0, 10.0)):
     """frames: sequence of N x 3 fp64 clouds (already downsampled).  Returns a SlamRun.  global_map: an object with
     add_frame, recent_clouds and finish (None: no map is built); grid: its occupancy grid config (None: defaults).
     loop_on_device: the detector is loop_closure.StoreLoopClosureDetector over global_map (a global_map.GlobalMap),
@@ -79,12 +81,29 @@ def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, po
     whichever graph is in use, before the prior is added (not in the reference node): the back end prices every loop
     closure under that robust loss and can refuse a false one.  The factor list does not depend on it.
     SlamRun.loop_weights / loop_distances = pose_graph.loop_weights() after the final optimize when that succeeded.
+    edge_information: sigma in metres (None: off), the residual noise of one point-to-plane pair (not in the reference
+    node).  The edge of every good registration -- odometry and loop closure alike -- is then weighted by the
+    6 x 6 information capi.information_from_icp makes of that registration's own normal matrix
+    (Context.last_normal_matrix) with this sigma and information_floor = (sigma_R, sigma_t), and enters through
+    pose_graph.add_odometry_information / add_loop_closure_information: stiff where the scans constrain the pose, soft
+    along a corridor.  SlamRun.factors records it as ("odom_info", i, j, T, info) / ("loop_info", i, j, T, info).  A
+    registration the node's gate rejects enters as before, the identity under the diagonal model.  The default floor, one
+    radian and ten metres, is far looser than any registration and only keeps a degenerate one positive definite.  The
+    closures found and their transforms do not depend on it.  Works with odom_robust, loop_gate, loop_robust,
+    loop_edge_loss and odom_local_map (whose registration's T is the pose in the odometry frame: the adjoint is taken at
+    that T); with an `align` or a `loop_backend` of the caller's it is refused, their normal matrices are not the library's.
     Under weights final_error is a weighted RMS and reads lower than the plain one: the gate `> 1.0` above, the
     detector's fitness threshold and the odometry factors' noise all read that number."""
     if loop_on_device and loop_backend is not None:
         raise ValueError("loop_backend and loop_on_device=True both choose the detector")
     if align is not None and odom_robust is not None:
         raise ValueError("odom_robust configures the default align; pass a robust align of your own instead")
+    if edge_information is not None and (align is not None or loop_backend is not None):
+        raise ValueError("edge_information reads the library's own normal matrices; it does not combine with an align or "
+                         "a loop_backend of the caller's")
+    info_args = None
+    if edge_information is not None:
+        info_args = (float(edge_information), float(information_floor[0]), float(information_floor[1]))
     run = SlamRun()
     if align is not None and odom_local_map is not None:
         raise ValueError("odom_local_map replaces the default align; it does not combine with an align of your own")
@@ -112,6 +131,8 @@ def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, po
         loop_config.max_correspondence_distance = float(loop_gate)
     if loop_robust is not None:
         loop_config.robust_kind, loop_config.robust_scale = int(loop_robust[0]), float(loop_robust[1])
+    if info_args is not None:
+        loop_config.information_sigma, loop_config.information_floor = info_args[0], info_args[1:]
     if loop_on_device:
         from .global_map import GlobalMap
         store = global_map if global_map is not None else GlobalMap(ctx)
@@ -133,6 +154,10 @@ def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, po
             pose_graph.add_prior(*args)
         elif kind == "odom":
             pose_graph.add_odometry_factor(*args)
+        elif kind == "odom_info":
+            pose_graph.add_odometry_information(*args)
+        elif kind == "loop_info":
+            pose_graph.add_loop_closure_information(*args)
         else:
             pose_graph.add_loop_closure(*args)
 
@@ -177,13 +202,22 @@ def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, po
             bad = (not r.converged) or r.final_error > 1.0           # :139-140
             delta = np.eye(4) if bad else np.asarray(r.transformation, dtype=np.float64)
         run.poses.append(run.poses[-1] @ delta)                      # :142-143
-        add("odom", len(run.poses) - 2, len(run.poses) - 1, delta, float(r.final_error))   # :145
+        if info_args is not None and not bad:                        # the registration just run, at its own T
+            from . import capi
+            nm = ctx.last_normal_matrix()
+            add("odom_info", len(run.poses) - 2, len(run.poses) - 1, delta,
+                capi.information_from_icp(nm.JtJ, nm.T, *info_args))
+        else:
+            add("odom", len(run.poses) - 2, len(run.poses) - 1, delta, float(r.final_error))   # :145
         prev = curr                                                  # :151
         live_update()
         detector.add_frame(kept if loop_on_device else curr, k)      # :159
         if k % 10 == 0 and k > 50:                                   # :160
             for c in detector.detect():                              # :161-166
-                add("loop", c.match_frame, c.query_frame, np.asarray(c.transform, dtype=np.float64))
+                if info_args is not None:
+                    add("loop_info", c.match_frame, c.query_frame, np.asarray(c.transform, dtype=np.float64), c.information)
+                else:
+                    add("loop", c.match_frame, c.query_frame, np.asarray(c.transform, dtype=np.float64))
                 run.closures.append(c)
                 pending = True
         if pending:                                                  # :112-115
