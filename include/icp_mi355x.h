@@ -626,6 +626,27 @@ int icpmi_pose_graph_loop_loss(const icpmi_pose_graph *graph, int32_t *kind, dou
 int icpmi_pose_graph_loop_weights(icpmi_pose_graph *graph, double *weights, double *distances, int64_t cap,
                                   int64_t *n_out);
 
+/* Covariances of the optimised poses (GTSAM's Marginals::marginalCovariance / jointMarginalCovariance; not
+ * in the reference, which never asks).  H is the Gauss-Newton matrix of the whole graph at the optimised values, with the
+ * loop loss' weights and the information edges' R as the optimiser applies them.  For q distinct pose indices, cov
+ * receives the 6q x 6q joint marginal covariance, row-major: block (a, b) = (H^-1)[indices[a], indices[b]], in the
+ * tangent order (omega, v) of a right perturbation X Exp(xi).  A block does not depend, bit for bit, on the order of the
+ * query or on what else is queried.
+ * Only valid while the optimised state of the last optimize() holds (nothing added, no loss change since), otherwise
+ * ICPMI_ERR_ARG.  Also ICPMI_ERR_ARG: q <= 0, an index without an estimate, an index named twice, and a graph whose H
+ * meets a non-positive pivot (no prior: gauge freedom has no covariance).  NULL indices or cov: ICPMI_ERR_NULL.
+ * The first call after an optimize() factors H once more at lam = 0 and keeps the factor; later calls only solve. */
+int icpmi_pose_graph_marginals(icpmi_pose_graph *graph, const int64_t *indices, int32_t q, double *cov);
+/* First-order covariance of the tangent of X_from^-1 X_to: J Sigma J^T with Sigma the joint covariance of (from, to) and
+ * J = [-Ad(X_to^-1 X_from), I].  from == to is ICPMI_ERR_ARG; the rest as icpmi_pose_graph_marginals. */
+int icpmi_pose_graph_relative_covariance(icpmi_pose_graph *graph, int64_t from, int64_t to, double cov[36]);
+/* Squared Mahalanobis distance of a proposed edge `rel` (from -> to, as icpmi_pose_graph_add_loop_closure takes it)
+ * against the graph: e = Log(rel^-1 X_from^-1 X_to), *d2 = e^T (Sigma_rel + edge_cov)^-1 e, chi-squared with 6 degrees of
+ * freedom for a true closure.  edge_cov is the edge's own 6 x 6 noise covariance; a sum that is not positive definite
+ * is ICPMI_ERR_ARG. */
+int icpmi_pose_graph_closure_distance(icpmi_pose_graph *graph, int64_t from, int64_t to, const double rel[16],
+                                      const double edge_cov[36], double *d2);
+
 /* Between factors weighted by a full 6 x 6 information matrix (GTSAM's noiseModel::Gaussian::Information):
  * an edge stiff where its measurement is well constrained and soft where it is not, instead of six fixed sigmas.  Off by
  * default: a graph that holds no such factor runs the kernels it ran before, bit for bit.

@@ -1122,6 +1122,41 @@ public:
         check(icpmi_pose_graph_loop_weights(g_, w.data(), d.data(), n, &n));
         return {w, d};
     }
+    // Covariances of the optimised poses (icpmi_pose_graph_marginals and its two companions; GTSAM's
+    // Marginals::marginalCovariance / jointMarginalCovariance, not in the reference): blocks of H^-1 in the tangent order
+    // (omega, v).  All four throw unless the optimised state of the last optimize() holds.
+    Matrix6 marginalCovariance(std::size_t index) const
+    {
+        const int64_t idx = static_cast<int64_t>(index);
+        Matrix6 out;
+        check(icpmi_pose_graph_marginals(g_, &idx, 1, out.data()));
+        return out;
+    }
+    // 6q x 6q, row-major: block (a, b) belongs to indices[a] and indices[b]; the indices must be distinct
+    std::vector<double> jointMarginalCovariance(const std::vector<std::size_t> &indices) const
+    {
+        std::vector<int64_t> idx(indices.begin(), indices.end());
+        std::vector<double> out(36 * idx.size() * idx.size());
+        check(icpmi_pose_graph_marginals(g_, idx.data(), static_cast<int32_t>(idx.size()), out.data()));
+        return out;
+    }
+    // first-order covariance of the tangent of X_i^-1 X_j
+    Matrix6 relativeCovariance(std::size_t i, std::size_t j) const
+    {
+        Matrix6 out;
+        check(icpmi_pose_graph_relative_covariance(g_, static_cast<int64_t>(i), static_cast<int64_t>(j), out.data()));
+        return out;
+    }
+    // d^2 of a proposed edge i -> j against the graph, chi-squared with 6 degrees of freedom for a true closure;
+    // edge_covariance is the edge's own noise
+    double closureDistance(std::size_t i, std::size_t j, const Transformation &relative_transform,
+                           const Matrix6 &edge_covariance) const
+    {
+        double d2 = 0.0;
+        check(icpmi_pose_graph_closure_distance(g_, static_cast<int64_t>(i), static_cast<int64_t>(j),
+                                                relative_transform.matrix().data(), edge_covariance.data(), &d2));
+        return d2;
+    }
     std::size_t size() const { return static_cast<std::size_t>(counts().first); }
     std::size_t loopClosureCount() const { return static_cast<std::size_t>(counts().second); }
     double getFinalError() const { return last().final_error; }

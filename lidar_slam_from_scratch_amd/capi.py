@@ -50,6 +50,7 @@ EXPORTS = [
     "icpmi_local_map_register_robust", "icpmi_local_map_register_robust_device",
     "icpmi_pose_graph_set_loop_loss", "icpmi_pose_graph_loop_loss", "icpmi_pose_graph_loop_weights",
     "icpmi_pose_graph_add_odometry_information", "icpmi_pose_graph_add_loop_closure_information",
+    "icpmi_pose_graph_marginals", "icpmi_pose_graph_relative_covariance", "icpmi_pose_graph_closure_distance",
     "icpmi_information_from_icp", "icpmi_last_normal_matrix", "icpmi_loop_set_information", "icpmi_loop_last_information",
 ]
 
@@ -395,6 +396,9 @@ def load_library(path=None):
     L.icpmi_pose_graph_loop_weights.argtypes = [pg, dp, dp, C.c_int64, i64p]
     L.icpmi_pose_graph_add_odometry_information.argtypes = [pg, C.c_int64, C.c_int64, dp, dp]
     L.icpmi_pose_graph_add_loop_closure_information.argtypes = [pg, C.c_int64, C.c_int64, dp, dp]
+    L.icpmi_pose_graph_marginals.argtypes = [pg, i64p, C.c_int32, dp]
+    L.icpmi_pose_graph_relative_covariance.argtypes = [pg, C.c_int64, C.c_int64, dp]
+    L.icpmi_pose_graph_closure_distance.argtypes = [pg, C.c_int64, C.c_int64, dp, dp, dp]
     L.icpmi_information_from_icp.argtypes = [dp, dp, C.c_double, C.c_double, C.c_double, dp]
     L.icpmi_last_normal_matrix.argtypes = [vp, C.c_int32, C.POINTER(NormalMatrix)]
     L.icpmi_map_create.argtypes = [vp, C.POINTER(vp)]

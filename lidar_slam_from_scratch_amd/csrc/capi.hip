@@ -54,6 +54,8 @@
 #include "pose_graph.h"
 #include "pose_graph_loss.h"
 #include "pose_graph_info.h"
+#include "pose_graph_marginals.h"
+#include "pose_graph_marginals_host.h"
 #include "local_map.h"
 
 using namespace icpmi;
@@ -3620,6 +3622,15 @@ extern "C" int64_t icpmi_debug_nn_margin(const icpmi_ctx *ctx, uint32_t *rows_ou
 // The LM policy below restates LevenbergMarquardtOptimizer::tryLambda / iterate and NonlinearOptimizer::defaultOptimize
 // exactly as scripts/pose_graph_ref.py levenberg_marquardt does, rule for rule.
 
+// The graph's structure for the device solve (rebuilt by every optimize(): O(poses + factors) on the host).
+struct PgPlan {
+    int n = 0, F = 0, nb = 0, nseg = 0, nblocks = 0, nloops = 0;
+    int max_seg = 0;                     // nodes of the longest segment
+    bool loss = false;                   // the loss is on and the graph has a loop factor: the kernels of pose_graph_loss.h
+    bool info = false;                   // the graph has an information factor: the kernels of pose_graph_info.h
+    std::vector<int32_t> keys, map;
+};
+
 struct icpmi_pose_graph {
     icpmi_ctx *ctx = nullptr;
     icpmi_pose_graph_config cfg;
@@ -3645,6 +3656,11 @@ struct icpmi_pose_graph {
         d_schur, d_S, d_xb, d_delta, d_errc, d_errl, d_out, d_status, d_inc_ptr, d_inc, d_cn_ptr, d_cn, d_segs,
         d_blocks, d_codes, d_sep_node, d_sep_segs, d_sep_pos, d_node_seg, d_rank, d_wd, d_slot, d_infoR;
     double *h_out = nullptr;             // pinned: the two sums and the status of a trial
+    // marginal covariances (pose_graph_marginals.h): the plan of the last optimize(), and whether d_L / d_U / d_Y / d_S
+    // hold the lam = 0 factorisation at d_X (cleared by every add, optimize() and set_loop_loss)
+    PgPlan plan;
+    bool marg_factored = false;
+    DevBuf d_mq, d_mW, d_mblk, d_mX, d_mout;
     icpmi_pose_graph_info last{};        // of the last optimize()
 };
 
@@ -3739,14 +3755,6 @@ template <class T> int pg_upload(icpmi_ctx *ctx, DevBuf &b, const std::vector<T>
 }
 
 unsigned pg_grid(size_t n, unsigned b) { return (unsigned)((n + b - 1) / b); }
-
-// The graph's structure for the device solve (rebuilt by every optimize(): O(poses + factors) on the host).
-struct PgPlan {
-    int n = 0, F = 0, nb = 0, nseg = 0, nblocks = 0, nloops = 0;
-    bool loss = false;                   // the loss is on and the graph has a loop factor: the kernels of pose_graph_loss.h
-    bool info = false;                   // the graph has an information factor: the kernels of pose_graph_info.h
-    std::vector<int32_t> keys, map;
-};
 
 int pg_plan(icpmi_pose_graph *g, PgPlan &P)
 {
@@ -3876,6 +3884,7 @@ int pg_plan(icpmi_pose_graph *g, PgPlan &P)
     if (F >= (1 << 28) || n >= (1 << 26)) return fail(ctx, ICPMI_ERR_ARG, "pose graph too large for the block codes");
     P.nb = nb;
     P.nseg = (int)segs.size();
+    for (const PgSeg &sg : segs) P.max_seg = std::max(P.max_seg, (int)sg.len);
     P.nblocks = (int)blocks.size();
     int rc;
     if ((rc = pg_upload(ctx, g->d_map, P.map)) || (rc = pg_upload(ctx, g->d_keys, P.keys)) ||
@@ -4005,6 +4014,126 @@ int pg_linearize(icpmi_pose_graph *g, const PgPlan &P, const PgLin &lin, double 
     return rc;
 }
 
+// The lam = 0 factorisation of H at d_X for the marginal covariances (pose_graph_marginals.h): linearise, then the
+// segment, reduced and Cholesky launches exactly as pg_trial makes them.  A non-positive pivot is the caller's graph.
+int pg_marg_factorize(icpmi_pose_graph *g)
+{
+    icpmi_ctx *ctx = g->ctx;
+    hipStream_t s = ctx->stream;
+    const PgPlan &P = g->plan;
+    PgLin lin{(double *)g->d_A.p, (double *)g->d_rw.p, (double *)g->d_err.p, (double *)g->d_H.p, (double *)g->d_g.p};
+    const int nr = 6 * P.nb;
+    const double lam = 0.0;
+    double lin0 = 0.0;
+    int rc;
+    if ((rc = pg_linearize(g, P, lin, nullptr, &lin0))) return rc;
+    HIP_TRY(ctx, hipMemsetAsync(g->d_status.p, 0, sizeof(int), s));
+    int *status = (int *)g->d_status.p;
+    if (P.nseg > 0)
+        hipLaunchKernelGGL(k_pg_segment, dim3(P.nseg), dim3(kPgSegThreads), 0, s, (const PgSeg *)g->d_segs.p, lam,
+                           (const double *)g->d_D.p, (const double *)g->d_gn.p, (const double *)g->d_Cn.p,
+                           (double *)g->d_L.p, (double *)g->d_U.p, (double *)g->d_Y.p, (double *)g->d_schur.p, status);
+    if (P.nb > 0) {
+        double *S = (double *)g->d_S.p;
+        HIP_TRY(ctx, hipMemsetAsync(S, 0, sizeof(double) * (size_t)nr * nr, s));
+        hipLaunchKernelGGL(k_pg_reduced, dim3(P.nblocks), dim3(64), 0, s, (const PgBlock *)g->d_blocks.p,
+                           (const int32_t *)g->d_codes.p, nr, lam, (const double *)g->d_D.p, (const double *)g->d_Cn.p,
+                           (const double *)lin.H, (const double *)g->d_schur.p, S);
+        for (int k0 = 0; k0 < nr; k0 += kCholNb) {
+            hipLaunchKernelGGL(k_chol_diag, dim3(1), dim3(256), 0, s, S, nr, k0, status);
+            const int rest = nr - k0 - kCholNb;
+            if (rest <= 0) break;
+            hipLaunchKernelGGL(k_chol_panel, dim3(pg_grid(rest, 64)), dim3(64), 0, s, S, nr, k0);
+            const unsigned T = pg_grid(rest, 32);
+            hipLaunchKernelGGL(k_chol_update, dim3(T, T), dim3(256), 0, s, S, nr, k0);
+        }
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(g->h_out + 2, g->d_status.p, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    HIP_TRY(ctx, hipGetLastError());
+    int st;
+    memcpy(&st, g->h_out + 2, sizeof(int));
+    if (st != 0)
+        return fail(ctx, ICPMI_ERR_ARG, "the Gauss-Newton matrix met a non-positive pivot: the graph has no covariance "
+                                        "(is a prior missing?)");
+    g->marg_factored = true;
+    return ICPMI_OK;
+}
+
+// the state rule of the covariance calls, as icpmi_pose_graph_loop_weights states it
+int pg_marg_state(icpmi_pose_graph *g)
+{
+    if (!g->optimized || !g->values_on_device || (int64_t)g->factors.size() != g->opt_factors ||
+        (int64_t)g->plan.map.size() != g->num_poses)
+        return fail(g->ctx, ICPMI_ERR_ARG, "covariances need the optimised state of the last optimize()");
+    return ICPMI_OK;
+}
+
+// the joint marginal covariance of q distinct poses into cov (6q x 6q, row-major)
+int pg_marginals(icpmi_pose_graph *g, const int64_t *indices, int32_t q, double *cov)
+{
+    icpmi_ctx *ctx = g->ctx;
+    int rc;
+    if ((rc = pg_marg_state(g))) return rc;
+    if (q <= 0) return fail(ctx, ICPMI_ERR_ARG, "a covariance query names at least one pose");
+    if (q >= 46341) return fail(ctx, ICPMI_ERR_ARG, "a covariance query of %d poses is too large", (int)q);   // q^2 blocks
+    const PgPlan &P = g->plan;
+    std::vector<int32_t> qnode(q);
+    for (int32_t a = 0; a < q; ++a) {
+        if (!pg_has(g, indices[a]) || P.map[indices[a]] < 0)
+            return fail(ctx, ICPMI_ERR_ARG, "Pose index %lld not found", (long long)indices[a]);
+        qnode[a] = P.map[indices[a]];
+    }
+    {
+        std::vector<int32_t> sorted(qnode);
+        std::sort(sorted.begin(), sorted.end());
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
+            return fail(ctx, ICPMI_ERR_ARG, "a covariance query names a pose twice");
+    }
+    if (!g->marg_factored && (rc = pg_marg_factorize(g))) return rc;
+    hipStream_t s = ctx->stream;
+    const size_t nr = 6 * (size_t)P.nb, Q = (size_t)q;
+    const size_t wstride = 36 * (size_t)std::max(P.max_seg, 1);   // doubles of one queried node's W
+    if ((rc = pg_upload(ctx, g->d_mq, qnode)) || (rc = reserve(ctx, g->d_mW, 8 * wstride * Q)) ||
+        (rc = reserve(ctx, g->d_mblk, 8 * 72 * Q)) || (rc = reserve(ctx, g->d_mX, 8 * std::max<size_t>(nr * 6 * Q, 1))) ||
+        (rc = reserve(ctx, g->d_mout, 8 * 36 * Q * Q)))
+        return rc;
+    const int32_t *dq = (const int32_t *)g->d_mq.p, *node_seg = (const int32_t *)g->d_node_seg.p,
+                  *sep_pos = (const int32_t *)g->d_sep_pos.p;
+    const PgSeg *segs = (const PgSeg *)g->d_segs.p;
+    if (P.nseg > 0)
+        hipLaunchKernelGGL(k_pg_marg_segment, dim3(q), dim3(64), 0, s, dq, node_seg, segs, (const double *)g->d_Cn.p,
+                           (const double *)g->d_L.p, (const double *)g->d_U.p, (int)wstride,
+                           (double *)g->d_mW.p, (double *)g->d_mblk.p);
+    if (P.nb > 0) {
+        hipLaunchKernelGGL(k_pg_marg_rhs, dim3(pg_grid(nr * 6 * Q, 256)), dim3(256), 0, s, dq, node_seg, segs, sep_pos,
+                           (const double *)g->d_mblk.p, (int)q, (int)nr, (double *)g->d_mX.p);
+        hipLaunchKernelGGL(k_pg_trsm_pair, dim3(q), dim3(kPgTrsmThreads), 0, s, (const double *)g->d_S.p, (int)nr,
+                           (double *)g->d_mX.p);
+    }
+    hipLaunchKernelGGL(k_pg_marg_gather, dim3((unsigned)(Q * Q)), dim3(64), 0, s, dq, node_seg, segs, sep_pos,
+                       (const double *)g->d_Y.p, (const double *)g->d_mW.p, (int)wstride, (const double *)g->d_mX.p, (int)q,
+                       (int)nr,
+                       (double *)g->d_mout.p);
+    HIP_TRY(ctx, hipMemcpyAsync(cov, g->d_mout.p, 8 * 36 * Q * Q, hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    HIP_TRY(ctx, hipGetLastError());
+    return ICPMI_OK;
+}
+
+// Sigma_rel of (from, to) and the two optimised poses
+int pg_relative(icpmi_pose_graph *g, int64_t from, int64_t to, double *cov)
+{
+    int rc;
+    if ((rc = pg_marg_state(g))) return rc;
+    if (from == to) return fail(g->ctx, ICPMI_ERR_ARG, "a relative covariance needs two different poses");
+    const int64_t idx[2] = {from, to};
+    double joint[144];
+    if ((rc = pg_marginals(g, idx, 2, joint))) return rc;
+    pg_relative_covariance(g->opt.data() + 12 * from, g->opt.data() + 12 * to, joint, cov);
+    return ICPMI_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -4059,7 +4188,8 @@ void icpmi_pose_graph_destroy(icpmi_pose_graph *g)
                       &g->d_H, &g->d_g, &g->d_D, &g->d_gn, &g->d_Cn, &g->d_L, &g->d_U, &g->d_Y, &g->d_schur, &g->d_S,
                       &g->d_xb, &g->d_delta, &g->d_errc, &g->d_errl, &g->d_out, &g->d_status, &g->d_inc_ptr, &g->d_inc,
                       &g->d_cn_ptr, &g->d_cn, &g->d_segs, &g->d_blocks, &g->d_codes, &g->d_sep_node, &g->d_sep_segs,
-                      &g->d_sep_pos, &g->d_node_seg, &g->d_rank, &g->d_wd, &g->d_slot, &g->d_infoR};
+                      &g->d_sep_pos, &g->d_node_seg, &g->d_rank, &g->d_wd, &g->d_slot, &g->d_infoR, &g->d_mq,
+                      &g->d_mW, &g->d_mblk, &g->d_mX, &g->d_mout};
     for (DevBuf *b : bufs) release(*b);
     if (g->h_out) (void)hipHostFree(g->h_out);
     delete g;
@@ -4076,6 +4206,7 @@ int icpmi_pose_graph_add_prior(icpmi_pose_graph *g, int64_t index, const double 
     pg_factor(f, 0, index, -1, pose, c, t);
     g->factors.push_back(f);                       // graph_->addPrior (pose_graph.cpp:72)
     g->info_slot.push_back(-1);
+    g->marg_factored = false;
     if (!pg_has(g, index)) pg_set_init(g, index, f.Z);   // :75-78; optimized_ is left as it is
     return ICPMI_OK;
 }
@@ -4108,6 +4239,7 @@ static int pg_add_odometry(icpmi_pose_graph *g, int64_t from, int64_t to, const 
         pg_set_init(g, to, o);
     }
     g->optimized = false;                          // :112
+    g->marg_factored = false;
     return ICPMI_OK;
 }
 
@@ -4126,6 +4258,7 @@ static int pg_add_loop_closure(icpmi_pose_graph *g, int64_t from, int64_t to, co
     pg_push_slot(g, info ? R21 : nullptr);
     g->num_loops++;                                // :136
     g->optimized = false;                          // :137
+    g->marg_factored = false;
     return ICPMI_OK;
 }
 
@@ -4199,6 +4332,7 @@ int icpmi_pose_graph_optimize(icpmi_pose_graph *g, icpmi_pose_graph_info *info, 
                         (long long)(pg_has(g, f.i) ? f.j : f.i));   // the reference's catch (:166-169)
     hipStream_t s = ctx->stream;
     g->values_on_device = false;
+    g->marg_factored = false;
     // only what was added since the last call goes up: the new factors and the new estimates
     const size_t F = g->factors.size();
     if ((rc = pg_reserve_keep(ctx, g->d_fac, sizeof(PgFactor) * g->uploaded_factors, sizeof(PgFactor) * F))) return rc;
@@ -4323,6 +4457,7 @@ int icpmi_pose_graph_optimize(icpmi_pose_graph *g, icpmi_pose_graph_info *info, 
     g->values_on_device = true;
     g->opt_factors = P.F;
     g->opt_loops = P.nloops;
+    g->plan = std::move(P);
     st.optimized = 1;
     st.final_error = error;
     st.final_lambda = lam;
@@ -4340,6 +4475,7 @@ int icpmi_pose_graph_set_loop_loss(icpmi_pose_graph *g, int32_t kind, double sca
     if (kind == ICPMI_PG_LOSS_NONE) scale = 0.0;
     else if (!std::isfinite(scale) || !(scale > 0.0))
         return fail(g->ctx, ICPMI_ERR_ARG, "the loss scale must be finite and positive");
+    g->marg_factored = false;
     if (kind == g->loss_kind && scale == g->loss_scale) return ICPMI_OK;
     g->loss_kind = kind;
     g->loss_scale = scale;
@@ -4387,6 +4523,40 @@ int icpmi_pose_graph_loop_weights(icpmi_pose_graph *g, double *weights, double *
         if (weights) weights[k] = wd[2 * k];
         if (distances) distances[k] = wd[2 * k + 1];
     }
+    return ICPMI_OK;
+}
+
+int icpmi_pose_graph_marginals(icpmi_pose_graph *g, const int64_t *indices, int32_t q, double *cov)
+{
+    if (!g) return ICPMI_ERR_NULL;
+    int rc;
+    if ((rc = check_common(g->ctx))) return rc;
+    if (!indices || !cov) return fail(g->ctx, ICPMI_ERR_NULL, "indices or cov is NULL");
+    return pg_marginals(g, indices, q, cov);
+}
+
+int icpmi_pose_graph_relative_covariance(icpmi_pose_graph *g, int64_t from, int64_t to, double cov[36])
+{
+    if (!g) return ICPMI_ERR_NULL;
+    int rc;
+    if ((rc = check_common(g->ctx))) return rc;
+    if (!cov) return fail(g->ctx, ICPMI_ERR_NULL, "cov is NULL");
+    return pg_relative(g, from, to, cov);
+}
+
+int icpmi_pose_graph_closure_distance(icpmi_pose_graph *g, int64_t from, int64_t to, const double rel[16],
+                                      const double edge_cov[36], double *d2)
+{
+    if (!g) return ICPMI_ERR_NULL;
+    int rc;
+    if ((rc = check_common(g->ctx))) return rc;
+    if (!edge_cov || !d2) return fail(g->ctx, ICPMI_ERR_NULL, "edge_cov or d2 is NULL");
+    if ((rc = pg_check_T(g->ctx, rel))) return rc;
+    double cov[36], Z[12];
+    if ((rc = pg_relative(g, from, to, cov))) return rc;
+    pg_to12(rel, Z);
+    if (!pg_closure_distance(g->opt.data() + 12 * from, g->opt.data() + 12 * to, Z, cov, edge_cov, d2))
+        return fail(g->ctx, ICPMI_ERR_ARG, "the relative covariance plus the edge covariance is not positive definite");
     return ICPMI_OK;
 }
 

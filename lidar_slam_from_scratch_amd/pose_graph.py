@@ -131,6 +131,41 @@ class PoseGraph:
                                                                     C.byref(n)))
         return w, d
 
+    def joint_marginal_covariance(self, indices):
+        """-> the (6q, 6q) joint marginal covariance of the q distinct poses `indices` at the optimised values
+        (icpmi_pose_graph_marginals; GTSAM's Marginals::jointMarginalCovariance, not in the reference): block (a, b) is
+        (H^-1)[indices[a], indices[b]] in the tangent order (omega, v).  Raises unless the optimised state of the last
+        optimize() holds.  The first call after an optimize() factors H; later ones only solve."""
+        idx = np.ascontiguousarray(indices, dtype=np.int64).reshape(-1)
+        q = idx.shape[0]
+        out = np.zeros((6 * q, 6 * q))
+        self.ctx._check(self._lib.icpmi_pose_graph_marginals(self._h, idx.ctypes.data_as(C.POINTER(C.c_int64)), q,
+                                                             capi._dp(out)))
+        return out
+
+    def marginal_covariance(self, index):
+        """-> the 6 x 6 marginal covariance of one pose (Marginals::marginalCovariance)"""
+        return self.joint_marginal_covariance([int(index)])
+
+    def relative_covariance(self, i, j):
+        """-> the 6 x 6 first-order covariance of the tangent of X_i^-1 X_j (icpmi_pose_graph_relative_covariance)"""
+        out = np.zeros((6, 6))
+        self.ctx._check(self._lib.icpmi_pose_graph_relative_covariance(self._h, int(i), int(j), capi._dp(out)))
+        return out
+
+    def closure_distance(self, i, j, relative_transform, edge_covariance):
+        """-> d^2 = e^T (Sigma_rel + edge_covariance)^-1 e with e = Log(rel^-1 X_i^-1 X_j): the squared Mahalanobis
+        distance of a proposed edge i -> j against the graph (icpmi_pose_graph_closure_distance), chi-squared with 6
+        degrees of freedom for a true closure."""
+        T = _T(relative_transform)
+        E = np.ascontiguousarray(edge_covariance, dtype=np.float64)
+        if E.shape != (6, 6):
+            raise ValueError("expected a 6 x 6 covariance matrix")
+        d2 = C.c_double(0.0)
+        self.ctx._check(self._lib.icpmi_pose_graph_closure_distance(self._h, int(i), int(j), capi._dp(T), capi._dp(E),
+                                                                    C.byref(d2)))
+        return d2.value
+
     def optimize(self):
         """pose_graph.cpp:147-171: False on an empty graph or where a factor names a pose with no estimate"""
         info = capi.PoseGraphInfo()

@@ -40,6 +40,7 @@ class SlamRun:
         self.live_log = []            # ... with (frames_cast, rebuilt) per live_update, in call order
         self.loop_weights = None      # with loop_edge_loss: each closure's weight after the final optimize, if it succeeded
         self.loop_distances = None    # ... and its whitened distance (sigmas)
+        self.rejected_closures = []   # with closure_gate: (LoopClosureResult, d2) of every closure the gate kept out
 
 
 def node_loop_config():
@@ -51,7 +52,7 @@ def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, po
              align=None, loop_backend=None, pose_graph=None, global_map=None, grid=None, map_voxel=1.0,
              loop_on_device=False, raycast=False, counts=False, live=False, loop_yaw_guess=False, loop_gate=None,
              ground=None, odom_robust=None, loop_robust=None, odom_local_map=None, loop_edge_loss=None,
-             edge_information=None, information_floor=(1.0, 10.0)):
+             edge_information=None, information_floor=(1.0, 10.0), closure_gate=None):
     """frames: sequence of N x 3 fp64 clouds (already downsampled).  Returns a SlamRun.  global_map: an object with
     add_frame, recent_clouds and finish (None: no map is built); grid: its occupancy grid config (None: defaults).
     loop_on_device: the detector is loop_closure.StoreLoopClosureDetector over global_map (a global_map.GlobalMap),
@@ -93,7 +94,14 @@ def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, po
     loop_edge_loss and odom_local_map (whose registration's T is the pose in the odometry frame: the adjoint is taken at
     that T); with an `align` or a `loop_backend` of the caller's it is refused, their normal matrices are not the library's.
     Under weights final_error is a weighted RMS and reads lower than the plain one: the gate `> 1.0` above, the
-    detector's fitness threshold and the odometry factors' noise all read that number."""
+    detector's fitness threshold and the odometry factors' noise all read that number.
+    closure_gate: a bound on d^2, chi-squared with 6 degrees of freedom, the caller's number (None: no gate, the run is
+    call for call what it was; not in the reference node).  When detect() yields closures at frame k the
+    graph is optimised once, logged in SlamRun.optimizations under the tag ("gate", k), and every closure of that
+    detect() is judged against that one state: d^2 = pose_graph.closure_distance(match, query, transform, Sigma_edge),
+    Sigma_edge the loop factor's own noise (the configured loop sigmas squared, or the inverse of the edge's
+    information matrix under edge_information).  Closures with d^2 <= closure_gate are added as without a gate; the
+    others go to SlamRun.rejected_closures as (closure, d^2) and never enter the graph."""
     if loop_on_device and loop_backend is not None:
         raise ValueError("loop_backend and loop_on_device=True both choose the detector")
     if align is not None and odom_robust is not None:
@@ -175,6 +183,23 @@ def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, po
                 run.recent_world.append(global_map.recent_clouds(run.poses))
         live_update()
 
+    def gate(found, k):
+        """-> the closures of one detect() that pass closure_gate, all judged against one optimised state"""
+        optimize(("gate", k))
+        if not run.optimizations[-1][1]:
+            raise RuntimeError("closure_gate: the graph could not be optimised at frame %d" % k)
+        cfg = pose_graph.config
+        sigma_loop = np.diag([cfg.loop_rotation_sigma ** 2] * 3 + [cfg.loop_translation_sigma ** 2] * 3)
+        passed = []
+        for c in found:
+            edge = np.linalg.inv(np.asarray(c.information, dtype=np.float64)) if info_args is not None else sigma_loop
+            d2 = pose_graph.closure_distance(c.match_frame, c.query_frame, np.asarray(c.transform, dtype=np.float64), edge)
+            if d2 <= closure_gate:
+                passed.append(c)
+            else:
+                run.rejected_closures.append((c, d2))
+        return passed
+
     add("prior", 0, np.eye(4))                                       # :66
     frames = list(frames)
     prev = np.ascontiguousarray(frames[0], dtype=np.float64)         # :69-72
@@ -213,7 +238,10 @@ def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, po
         live_update()
         detector.add_frame(kept if loop_on_device else curr, k)      # :159
         if k % 10 == 0 and k > 50:                                   # :160
-            for c in detector.detect():                              # :161-166
+            found = list(detector.detect())                          # :161-166
+            if closure_gate is not None and found:
+                found = gate(found, k)
+            for c in found:
                 if info_args is not None:
                     add("loop_info", c.match_frame, c.query_frame, np.asarray(c.transform, dtype=np.float64), c.information)
                 else:
