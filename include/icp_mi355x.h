@@ -896,6 +896,57 @@ int icpmi_ground_segment(icpmi_ctx *ctx, const double *xyz, int64_t n, const icp
 int icpmi_ground_segment_device(icpmi_ctx *ctx, const double *d_xyz, int64_t n, const icpmi_ground_config *cfg,
                                 uint8_t *labels, double *height, double *ground_z, icpmi_ground_info *info);
 
+/* Motion compensation (deskew) of a scan in its sensor frame (csrc/deskew.h; not in the reference, which
+ * takes every scan as a snapshot from one pose).  A spinning sensor measures row i at tau_i in [0, 1] of its sweep while
+ * it moves; with the motion over one whole sweep given as a twist xi = (omega, v) in the sensor frame (the tangent
+ * order of the pose graph), pose(tau) = pose(t_ref) Exp((tau - t_ref) xi), and row i becomes
+ *     p'_i = Exp(s_i xi) p_i = R(s_i) p_i + t(s_i),   s_i = tau_i - t_ref:
+ * the scan as a sensor standing at pose(t_ref) would have seen it.  With theta = |omega|, a = omega / theta, K = hat(a):
+ *     R(s) = I + sin(s theta) K + (1 - cos(s theta)) K^2
+ *     t(s) = s v + ((1 - cos(s theta)) / theta) (a x v) + ((s theta - sin(s theta)) / theta) (a x (a x v))
+ * and for theta < 1e-10 R = I, t = s v.  fp64, unfused, in the order csrc/deskew.h states (scripts/deskew_ref.py restates
+ * it byte for byte while |s| theta < pi/4; from there on the device library's sincos is used, a few ulp from libm's).
+ * A row with a non-finite coordinate or time, a row with tau_i == t_ref, and every row under a twist of six zeros pass
+ * through unchanged in every bit.
+ *   time_source  ICPMI_DESKEW_TIMES: `times` holds n doubles, tau_i as given.
+ *                ICPMI_DESKEW_AZIMUTH: tau_i = frac(direction * (atan2(y, x) - azimuth_start) / 2 pi); `times` is not
+ *                read.  What a KITTI .bin, which carries no times, gets.
+ *   t_ref        the moment of the sweep whose pose the deskewed scan is registered as: 0.5, mid-sweep, by default.
+ * icpmi_deskew works on host memory (one wait); icpmi_deskew_device on device memory, queued on the context's stream
+ * with no wait of its own.  out_xyz may be xyz.  n == 0 is ICPMI_OK.  Decided before any device work, with nothing
+ * written and a text in icpmi_last_error -- ICPMI_ERR_ARG: a twist entry, t_ref or azimuth_start that is not finite;
+ * t_ref outside [0, 1]; direction not +1 or -1; an unknown time_source; n < 0 -- ICPMI_ERR_NULL: cfg, xyz or out_xyz
+ * NULL with n > 0, or ICPMI_DESKEW_TIMES with times NULL and n > 0.  reserved[] is ignored.
+ * icpmi_deskew_twist: twist = Log(delta), the SE(3) log of a relative pose (row-major 4 x 4), with the pose graph's
+ * formulas and small-angle forms: the twist of a sweep under constant velocity, from the previous frame's delta.  Host
+ * only: no context, no device.  A non-finite entry is ICPMI_ERR_ARG. */
+#define ICPMI_DESKEW_TIMES 0
+#define ICPMI_DESKEW_AZIMUTH 1
+typedef struct {
+    double twist[6];        /* (omega, v) over one whole sweep, in the sensor frame */
+    double t_ref;           /* in [0, 1] */
+    int32_t time_source;    /* ICPMI_DESKEW_* */
+    int32_t direction;      /* +1: the azimuth grows with time (counter-clockwise); -1: clockwise */
+    double azimuth_start;   /* the azimuth at tau = 0 [rad] */
+    double reserved[4];
+} icpmi_deskew_config;
+void icpmi_deskew_config_default(icpmi_deskew_config *cfg); /* zero twist, 0.5, ICPMI_DESKEW_TIMES, +1, -pi */
+int icpmi_deskew(icpmi_ctx *ctx, const double *xyz, const double *times, int64_t n, const icpmi_deskew_config *cfg,
+                 double *out_xyz);
+int icpmi_deskew_device(icpmi_ctx *ctx, const double *d_xyz, const double *d_times, int64_t n,
+                        const icpmi_deskew_config *cfg, double *d_out_xyz);
+int icpmi_deskew_twist(const double delta[16], double twist[6]);
+/* Deskew in the odometry stream: while a config is set (NULL turns it off; off after icpmi_create), icpmi_stream_push
+ * and icpmi_stream_push_host first deskew the raw scan under it into a buffer of the context, on the context's stream
+ * and with no additional wait, and filter and register that: bit for bit icpmi_deskew followed by the same push with
+ * deskew off.  The caller sets the twist before each push (it owns the gate and the pose: icpmi_deskew_twist of its last
+ * delta is the constant-velocity choice).  The stream has no times: the config's time_source must be
+ * ICPMI_DESKEW_AZIMUTH (anything else is ICPMI_ERR_ARG, as are the cases of icpmi_deskew).  The setting survives
+ * icpmi_stream_reset.  While it is set icpmi_stream_push_file and icpmi_stream_prefetch_file return ICPMI_ERR_ARG: the
+ * prefetch worker filters the next file before this frame's delta exists.  With deskew off every stream call is bit for
+ * bit what it is without this function. */
+int icpmi_stream_set_deskew(icpmi_ctx *ctx, const icpmi_deskew_config *cfg);
+
 /* icpmi_map_set_ground(map, cfg): while a config is set (NULL turns it off; off after icpmi_map_create),
  * icpmi_map_finish's cell set, icpmi_map_raycast, icpmi_map_raycast_counts and icpmi_map_live_update take as a frame's
  * hits exactly its ICPMI_GROUND_OBSTACLE rows.  The grid's world-z band is not applied; every other test stays (0.5 <=

@@ -676,6 +676,60 @@ private:
     Context *ctx_;
 };
 
+// Motion compensation (deskew) of a scan in its sensor frame (icpmi_deskew; not in the reference, which takes every scan
+// as a snapshot from one pose).  twist = (omega, v): the sensor's motion over one whole sweep, in the sensor frame; row i,
+// measured at tau_i in [0, 1], becomes Exp((tau_i - t_ref) twist) p_i.  The defaults are icpmi_deskew_config_default's,
+// except time_source: deskew() sets it from whether times are given, OdometryStream::set_deskew to Azimuth.
+enum class DeskewTimeSource : int32_t { Times = ICPMI_DESKEW_TIMES, Azimuth = ICPMI_DESKEW_AZIMUTH };
+struct DeskewConfig {
+    std::array<double, 6> twist{{0.0, 0.0, 0.0, 0.0, 0.0, 0.0}};
+    double t_ref = 0.5;                        // the moment of the sweep the deskewed scan is registered as
+    int direction = 1;                         // +1: the azimuth grows with time; -1: clockwise
+    double azimuth_start = -3.14159265358979323846; // the azimuth at tau = 0
+};
+
+namespace detail {
+inline icpmi_deskew_config to_c(const DeskewConfig &c, DeskewTimeSource source)
+{
+    icpmi_deskew_config k;
+    icpmi_deskew_config_default(&k);
+    for (std::size_t e = 0; e < 6; ++e) k.twist[e] = c.twist[e];
+    k.t_ref = c.t_ref, k.direction = c.direction, k.azimuth_start = c.azimuth_start;
+    k.time_source = static_cast<int32_t>(source);
+    return k;
+}
+} // namespace detail
+
+// icpmi_deskew_twist (host only, no device): the SE(3) log (omega, v) of a relative pose -- the twist of the next sweep
+// under constant velocity, from this frame's delta.
+inline std::array<double, 6> deskew_twist(const Transformation &delta)
+{
+    std::array<double, 6> twist{};
+    const int rc = icpmi_deskew_twist(delta.matrix().data(), twist.data());
+    if (rc != ICPMI_OK) throw IcpError(rc, "deskew_twist: a pose entry is not finite");
+    return twist;
+}
+
+// the rows of `scan` at the times `times` (one per row, in [0, 1]) ...
+inline PointCloud deskew(Context &ctx, const PointCloud &scan, const std::vector<double> &times, const DeskewConfig &config)
+{
+    if (times.size() != scan.size()) throw IcpError(ICPMI_ERR_ARG, "deskew: one time per row");
+    const icpmi_deskew_config k = detail::to_c(config, DeskewTimeSource::Times);
+    std::vector<double> out(3 * scan.size());
+    const int rc = icpmi_deskew(ctx.get(), scan.data(), times.data(), static_cast<int64_t>(scan.size()), &k, out.data());
+    if (rc != ICPMI_OK) throw IcpError(rc, icpmi_last_error(ctx.get()));
+    return PointCloud(std::move(out));
+}
+// ... or at times taken from the rows' azimuths (what a KITTI .bin, which carries none, gets)
+inline PointCloud deskew(Context &ctx, const PointCloud &scan, const DeskewConfig &config)
+{
+    const icpmi_deskew_config k = detail::to_c(config, DeskewTimeSource::Azimuth);
+    std::vector<double> out(3 * scan.size());
+    const int rc = icpmi_deskew(ctx.get(), scan.data(), nullptr, static_cast<int64_t>(scan.size()), &k, out.data());
+    if (rc != ICPMI_OK) throw IcpError(rc, icpmi_last_error(ctx.get()));
+    return PointCloud(std::move(out));
+}
+
 // process_frame as two calls per frame with the scans resident in device memory: push() is
 // lines 122-138 (voxel filter, guards, registration against the previous filtered scan), the caller
 // applies its gate and pose update (139-145), map_update() is lines 147-153 (world points of the
@@ -758,6 +812,21 @@ public:
         const int rc = icpmi_stream_last_robust(ctx_->get(), &info);
         if (rc != ICPMI_OK) throw IcpError(rc, icpmi_last_error(ctx_->get()));
         return info;
+    }
+    // Not in the reference: every later push() first deskews the raw scan under `config`, its times taken from the rows'
+    // azimuths (icpmi_stream_set_deskew; the setting survives reset()); clear_deskew() turns that off.  Set the twist
+    // before each push -- deskew_twist(the last delta) is the constant-velocity choice.  push_file and prefetch_file
+    // are refused while it is set.
+    void set_deskew(const DeskewConfig &config)
+    {
+        const icpmi_deskew_config k = detail::to_c(config, DeskewTimeSource::Azimuth);
+        const int rc = icpmi_stream_set_deskew(ctx_->get(), &k);
+        if (rc != ICPMI_OK) throw IcpError(rc, icpmi_last_error(ctx_->get()));
+    }
+    void clear_deskew()
+    {
+        const int rc = icpmi_stream_set_deskew(ctx_->get(), nullptr);
+        if (rc != ICPMI_OK) throw IcpError(rc, icpmi_last_error(ctx_->get()));
     }
 
 private:

@@ -52,6 +52,7 @@ EXPORTS = [
     "icpmi_pose_graph_add_odometry_information", "icpmi_pose_graph_add_loop_closure_information",
     "icpmi_pose_graph_marginals", "icpmi_pose_graph_relative_covariance", "icpmi_pose_graph_closure_distance",
     "icpmi_information_from_icp", "icpmi_last_normal_matrix", "icpmi_loop_set_information", "icpmi_loop_last_information",
+    "icpmi_deskew_config_default", "icpmi_deskew", "icpmi_deskew_device", "icpmi_deskew_twist", "icpmi_stream_set_deskew",
 ]
 
 
@@ -207,6 +208,15 @@ class GroundInfo(C.Structure):
     """icpmi_ground_info"""
     _fields_ = [("n_ground", C.c_int64), ("n_obstacle", C.c_int64), ("n_ignored", C.c_int64),
                 ("bins_accepted", C.c_int64)]
+
+
+DESKEW_TIMES, DESKEW_AZIMUTH = 0, 1                       # ICPMI_DESKEW_*
+
+
+class DeskewConfig(C.Structure):
+    """icpmi_deskew_config"""
+    _fields_ = [("twist", C.c_double * 6), ("t_ref", C.c_double), ("time_source", C.c_int32), ("direction", C.c_int32),
+                ("azimuth_start", C.c_double), ("reserved", C.c_double * 4)]
 
 
 class LocalMapConfig(C.Structure):
@@ -426,6 +436,12 @@ def load_library(path=None):
     L.icpmi_ground_segment_device.argtypes = [vp, vp, C.c_int64, C.POINTER(GroundConfig), u8p, dp, dp, C.POINTER(GroundInfo)]
     L.icpmi_map_set_ground.argtypes = [vp, C.POINTER(GroundConfig)]
     L.icpmi_map_ground_labels.argtypes = [vp, C.c_int64, u8p, C.c_int64, i64p]
+    L.icpmi_deskew_config_default.argtypes = [C.POINTER(DeskewConfig)]
+    L.icpmi_deskew_config_default.restype = None
+    L.icpmi_deskew.argtypes = [vp, dp, dp, C.c_int64, C.POINTER(DeskewConfig), dp]
+    L.icpmi_deskew_device.argtypes = [vp, vp, vp, C.c_int64, C.POINTER(DeskewConfig), vp]
+    L.icpmi_deskew_twist.argtypes = [dp, dp]
+    L.icpmi_stream_set_deskew.argtypes = [vp, C.POINTER(DeskewConfig)]
     L.icpmi_loop_config_default.argtypes = [C.POINTER(LoopConfig)]
     L.icpmi_loop_config_default.restype = None
     L.icpmi_loop_create.argtypes = [vp, C.POINTER(LoopConfig), C.POINTER(vp)]
@@ -864,6 +880,28 @@ class Context:
             self._check(self._lib.icpmi_stream_set_robust(self._h, None))
         else:
             self._check(self._lib.icpmi_stream_set_robust(self._h, C.byref(as_robust(rule))))
+
+    def deskew(self, xyz, times, cfg):
+        """icpmi_deskew: the n rows of xyz (N x 3 fp64, host) moved into the sensor frame at cfg.t_ref under cfg (a
+        DeskewConfig structure); times: N doubles or None (ICPMI_DESKEW_AZIMUTH) -> N x 3"""
+        pts = _f64(xyz) if len(xyz) else np.zeros((0, 3))
+        t = None if times is None else np.ascontiguousarray(times, dtype=np.float64).reshape(-1)
+        if t is not None and t.shape[0] != pts.shape[0]:
+            raise ValueError("one time per row")
+        out = np.empty_like(pts)
+        self._check(self._lib.icpmi_deskew(self._h, _dp(pts), None if t is None else _dp(t), pts.shape[0], C.byref(cfg), _dp(out)))
+        return out
+
+    def deskew_device(self, xyz_ptr, times_ptr, n, cfg, out_ptr):
+        """icpmi_deskew_device: the same on device memory, queued on the context's stream without a wait; out_ptr may be
+        xyz_ptr; times_ptr None or 0 without times"""
+        self._check(self._lib.icpmi_deskew_device(self._h, C.c_void_p(xyz_ptr), C.c_void_p(times_ptr or None), int(n),
+                                                  C.byref(cfg), C.c_void_p(out_ptr)))
+
+    def stream_set_deskew(self, cfg):
+        """icpmi_stream_set_deskew: every later stream_push / stream_push_host deskews the raw scan under cfg (a
+        DeskewConfig structure with time_source DESKEW_AZIMUTH; None: off) before it filters it"""
+        self._check(self._lib.icpmi_stream_set_deskew(self._h, None if cfg is None else C.byref(cfg)))
 
     def stream_last_robust(self):
         """icpmi_stream_last_robust -> RobustInfo of the last push's registration (zeros without one, or without a rule)"""

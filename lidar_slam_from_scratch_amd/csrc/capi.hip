@@ -50,6 +50,7 @@
 #include "live_plane.h"
 #include "live_counts.h"
 #include "ground.h"
+#include "deskew.h"
 #include "loop_store.h"
 #include "pose_graph.h"
 #include "pose_graph_loss.h"
@@ -222,6 +223,9 @@ struct icpmi_ctx {
     bool stream_robust_on = false;                  // icpmi_stream_set_robust: the pushes register under stream_robust
     icpmi_robust stream_robust{};
     icpmi_robust_info stream_robust_info{};         // icpmi_stream_last_robust: of the last push
+    bool stream_deskew_on = false;                  // icpmi_stream_set_deskew: the pushes deskew the raw scan under stream_deskew first
+    icpmi_deskew_config stream_deskew{};
+    DevBuf deskew_raw, deskew_times;                // the deskewed raw scan of a push; icpmi_deskew's times on the device
     DevBuf grid_set, grid_in, grid_out, grid_cnt, world; // occupancy grid: the set (sorted unique keys), {set, new keys}, sorted, run data; world points
     int64_t grid_n = 0;                             // cells in grid_set
     unsigned *h_grid = nullptr;                     // pinned: the set's size on its way back
@@ -2089,7 +2093,7 @@ void icpmi_destroy(icpmi_ctx *ctx)
                       &ctx->history, &ctx->stage_a, &ctx->stage_b, &ctx->stage_c, &ctx->d2out, &ctx->src_sort, &ctx->grp_cnt, &ctx->grp_items,
                       &ctx->bpack, &ctx->coarse, &ctx->bbox_part, &ctx->nn_misc, &ctx->knn_idx, &ctx->slotmin, &ctx->nn_lists, &ctx->nrm_sorted,
                       &ctx->fb_list, &ctx->sort_keys, &ctx->sort_tmp, &ctx->tgt_sorted, &ctx->frames, &ctx->vox_keys,
-                      &ctx->vox_vals, &ctx->vox_out, &ctx->stream_prev, &ctx->stream_cur, &ctx->f32_stage, &ctx->grid_set,
+                      &ctx->vox_vals, &ctx->vox_out, &ctx->stream_prev, &ctx->stream_cur, &ctx->f32_stage, &ctx->deskew_raw, &ctx->deskew_times, &ctx->grid_set,
                       &ctx->grid_in, &ctx->grid_out, &ctx->grid_cnt, &ctx->world})
         release(*b);
     if (ctx->h_grid) (void)hipHostFree(ctx->h_grid);
@@ -2820,6 +2824,8 @@ int stream_check_args(icpmi_ctx *ctx, const icpmi_config *cfg, icpmi_result *res
 }
 int stream_register(icpmi_ctx *ctx, int64_t n_cur, int64_t min_points, const icpmi_config *cfg, icpmi_result *result,
                     double *error_history, int32_t history_cap, icpmi_stream_info *info);
+int deskew_check_config(icpmi_ctx *ctx, const icpmi_deskew_config *cfg);
+int deskew_queue(icpmi_ctx *ctx, const icpmi_deskew_config *cfg, const double *d_xyz, const double *d_times, int64_t n, double *d_out);
 } // namespace
 
 int icpmi_stream_push(icpmi_ctx *ctx, const double *d_raw_xyz, int64_t n_raw, double voxel_size, int64_t min_points,
@@ -2834,6 +2840,13 @@ int icpmi_stream_push(icpmi_ctx *ctx, const double *d_raw_xyz, int64_t n_raw, do
     if (ctx->prefetch) { // what the worker filters the next file with
         std::lock_guard<std::mutex> lk(ctx->prefetch->mu);
         ctx->prefetch->voxel_hint = voxel_size;
+    }
+    if (ctx->stream_deskew_on) {
+        // the raw scan into the frame of the sweep's t_ref first (deskew.h), queued in front of the filter: no wait
+        if ((rc = deskew_check_config(ctx, &ctx->stream_deskew))) return rc;
+        if ((rc = reserve(ctx, ctx->deskew_raw, sizeof(double) * 3 * (size_t)n_raw))) return rc;
+        if ((rc = deskew_queue(ctx, &ctx->stream_deskew, d_raw_xyz, nullptr, n_raw, (double *)ctx->deskew_raw.p))) return rc;
+        d_raw_xyz = (const double *)ctx->deskew_raw.p;
     }
     // curr = voxel_downsample(raw)  (slam_node.cpp:122), into the buffer that is not the previous frame
     if ((rc = reserve(ctx, ctx->stream_cur, sizeof(double) * 3 * (size_t)n_raw))) return rc;
@@ -3089,6 +3102,8 @@ int icpmi_stream_prefetch_file(icpmi_ctx *ctx, const char *path)
     int rc;
     if ((rc = check_common(ctx))) return rc;
     if (!path) return fail(ctx, ICPMI_ERR_NULL, "null argument");
+    if (ctx->stream_deskew_on)
+        return fail(ctx, ICPMI_ERR_ARG, "icpmi_stream_prefetch_file with deskew set: the worker filters a file before its twist is known");
     if (!is_bin(path)) return ICPMI_OK; // a PLY goes through the host parser when it is pushed: nothing to do ahead
     if (!ctx->prefetch) {
         ctx->prefetch = new FilePrefetch();
@@ -3113,6 +3128,8 @@ int icpmi_stream_push_file(icpmi_ctx *ctx, const char *path, double voxel_size, 
     int rc;
     if ((rc = check_common(ctx))) return rc;
     if (!path) return fail(ctx, ICPMI_ERR_NULL, "null argument");
+    if (ctx->stream_deskew_on)
+        return fail(ctx, ICPMI_ERR_ARG, "icpmi_stream_push_file with deskew set: push the scan with icpmi_stream_push or icpmi_stream_push_host");
     struct PushClock { icpmi_ctx *c; std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
                        ~PushClock() { c->t_push += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); c->pushes += 1; } } push_clock{ctx};
     if (!is_bin(path)) {
@@ -4698,6 +4715,114 @@ int icpmi_ground_segment_device(icpmi_ctx *ctx, const double *d_xyz, int64_t n, 
                                 double *height, double *ground_z, icpmi_ground_info *info)
 {
     return ground_segment(ctx, d_xyz, true, n, cfg, labels, height, ground_z, info);
+}
+
+} // extern "C"
+
+// ======================================================================================================================
+// Motion compensation of a scan in its sensor frame (deskew.h, deskew_host.h).
+
+static_assert(kDeskewTimes == ICPMI_DESKEW_TIMES && kDeskewAzimuth == ICPMI_DESKEW_AZIMUTH, "the header states these");
+
+namespace {
+
+int deskew_check_config(icpmi_ctx *ctx, const icpmi_deskew_config *c)
+{
+    if (!c) return fail(ctx, ICPMI_ERR_NULL, "the deskew config is NULL");
+    const DeskewRefusal r = deskew_check(c->twist, c->t_ref, c->time_source, c->direction, c->azimuth_start);
+    if (r != kDeskewOk) return fail(ctx, ICPMI_ERR_ARG, "%s", deskew_refusal_text(r));
+    return ICPMI_OK;
+}
+
+// Queue k_deskew for n > 0 rows on the context's stream (checked config; d_out may be d_xyz).
+int deskew_queue(icpmi_ctx *ctx, const icpmi_deskew_config *c, const double *d_xyz, const double *d_times, int64_t n, double *d_out)
+{
+    const DeskewConstants k = deskew_constants(c->twist, c->t_ref, c->time_source, c->direction, c->azimuth_start);
+    const unsigned blocks = (unsigned)std::min<int64_t>(kDeskewMaxBlocks, (n + kDeskewThreads - 1) / kDeskewThreads);
+    hipLaunchKernelGGL(k_deskew, dim3(blocks), dim3(kDeskewThreads), 0, ctx->stream, d_xyz, d_times, d_out, (size_t)n, k);
+    HIP_TRY(ctx, hipGetLastError());
+    return ICPMI_OK;
+}
+
+int deskew_args(icpmi_ctx *ctx, const double *xyz, const double *times, int64_t n, const icpmi_deskew_config *cfg, double *out)
+{
+    int rc;
+    if ((rc = check_common(ctx))) return rc;
+    if ((rc = deskew_check_config(ctx, cfg))) return rc;
+    if (n < 0 || n > 700000000) return fail(ctx, ICPMI_ERR_ARG, "n out of range");
+    if (n > 0 && (!xyz || !out)) return fail(ctx, ICPMI_ERR_NULL, "null argument");
+    if (n > 0 && cfg->time_source == ICPMI_DESKEW_TIMES && !times)
+        return fail(ctx, ICPMI_ERR_NULL, "ICPMI_DESKEW_TIMES without times");
+    return ICPMI_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+void icpmi_deskew_config_default(icpmi_deskew_config *cfg)
+{
+    if (!cfg) return;
+    *cfg = icpmi_deskew_config{};
+    cfg->t_ref = 0.5;
+    cfg->time_source = ICPMI_DESKEW_TIMES;
+    cfg->direction = 1;
+    cfg->azimuth_start = -3.14159265358979323846;
+}
+
+int icpmi_deskew_twist(const double delta[16], double twist[6])
+{
+    if (!delta || !twist) return fail(nullptr, ICPMI_ERR_NULL, "null argument");
+    if (!deskew_twist(delta, twist)) return fail(nullptr, ICPMI_ERR_ARG, "a pose entry is not finite");
+    return ICPMI_OK;
+}
+
+int icpmi_deskew_device(icpmi_ctx *ctx, const double *d_xyz, const double *d_times, int64_t n, const icpmi_deskew_config *cfg,
+                        double *d_out_xyz)
+{
+    int rc;
+    if ((rc = deskew_args(ctx, d_xyz, d_times, n, cfg, d_out_xyz))) return rc;
+    if (n == 0) return ICPMI_OK;
+    Range range("icpmi:deskew");
+    return deskew_queue(ctx, cfg, d_xyz, d_times, n, d_out_xyz);
+}
+
+int icpmi_deskew(icpmi_ctx *ctx, const double *xyz, const double *times, int64_t n, const icpmi_deskew_config *cfg, double *out_xyz)
+{
+    int rc;
+    if ((rc = deskew_args(ctx, xyz, times, n, cfg, out_xyz))) return rc;
+    if (n == 0) return ICPMI_OK;
+    Range range("icpmi:deskew");
+    hipStream_t s = ctx->stream;
+    const size_t un = (size_t)n;
+    const bool with_times = cfg->time_source == ICPMI_DESKEW_TIMES;
+    if ((rc = reserve(ctx, ctx->stage_a, sizeof(double) * 3 * un))) return rc;
+    if (with_times && (rc = reserve(ctx, ctx->deskew_times, sizeof(double) * un))) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->stage_a.p, xyz, sizeof(double) * 3 * un, hipMemcpyHostToDevice, s));
+    if (with_times) HIP_TRY(ctx, hipMemcpyAsync(ctx->deskew_times.p, times, sizeof(double) * un, hipMemcpyHostToDevice, s));
+    if ((rc = deskew_queue(ctx, cfg, (const double *)ctx->stage_a.p, with_times ? (const double *)ctx->deskew_times.p : nullptr, n,
+                           (double *)ctx->stage_a.p)))
+        return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(out_xyz, ctx->stage_a.p, sizeof(double) * 3 * un, hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s)); // the call's one wait
+    HIP_TRY(ctx, hipGetLastError());
+    return ICPMI_OK;
+}
+
+int icpmi_stream_set_deskew(icpmi_ctx *ctx, const icpmi_deskew_config *cfg)
+{
+    int rc;
+    if ((rc = check_common(ctx))) return rc;
+    if (!cfg) {
+        ctx->stream_deskew_on = false;
+        return ICPMI_OK;
+    }
+    if ((rc = deskew_check_config(ctx, cfg))) return rc;
+    if (cfg->time_source != ICPMI_DESKEW_AZIMUTH)
+        return fail(ctx, ICPMI_ERR_ARG, "the stream has no times: its deskew takes ICPMI_DESKEW_AZIMUTH");
+    ctx->stream_deskew = *cfg;
+    ctx->stream_deskew_on = true;
+    return ICPMI_OK;
 }
 
 } // extern "C"

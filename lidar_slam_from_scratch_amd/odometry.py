@@ -92,24 +92,48 @@ def gpu_align(ctx, *, robust=None):
     return align
 
 
-def run_odometry_device(raw_frames, ctx, voxel=0.5, max_iterations=50, tolerance=1e-6, min_points=1000):
+def run_odometry_device(raw_frames, ctx, voxel=0.5, max_iterations=50, tolerance=1e-6, min_points=1000, deskew=None,
+                        on_frame=None):
     """The same loop with the clouds resident in HBM: each RAW scan is
     uploaded once, voxel-filtered on the device (slam_node.cpp:122 -> icpmi_voxel_downsample_device)
     and registered against the previous filtered scan, which never left the device
     (slam_node.cpp:132-133,152: the target of frame t+1 is the source of frame t).
-    torch is used for device memory only."""
+    torch is used for device memory only.
+    deskew: a deskew.DeskewConfig (None: none) -- a frame is then `points` or `(points, times)`, and before it is
+    filtered it is deskewed in place on the device (icpmi_deskew_device) with the twist of the previous frame's delta
+    (deskew.twist_from_delta; a zero twist while there is none); track.twists holds the twists used.
+    on_frame(k, twist or None, raw rows as filtered (host copy), filtered scan (host copy), result or None): called when
+    frame k is done -- for tests; it costs two copies per frame."""
     import torch
     from . import capi
+    from . import deskew as dk
     track = OdometryTrack()
+    track.twists = []
     prev = None       # (tensor, rows)
     cfg = capi.Context.make_config(max_iterations=max_iterations, tolerance=tolerance)
+
+    def report(k, twist, d_raw, d_cur, n, res):
+        if on_frame:
+            on_frame(k, twist, d_raw.cpu().numpy(), d_cur[:n].cpu().numpy(), res)
+
     for k, raw in enumerate(raw_frames):
         t0 = time.perf_counter()
+        twist = None
+        if deskew is not None:
+            raw, times = dk.split_frame(raw)
         d_raw = torch.from_numpy(np.ascontiguousarray(raw, dtype=np.float64)).cuda()
+        if deskew is not None:
+            twist = dk.frame_twist(track.deltas[-1] if track.deltas else None)
+            track.twists.append(twist)
+            d_times = None if times is None else torch.from_numpy(np.ascontiguousarray(times, dtype=np.float64)).cuda()
+            if d_raw.shape[0]:
+                ctx.deskew_device(d_raw.data_ptr(), None if d_times is None else d_times.data_ptr(), d_raw.shape[0],
+                                  deskew.with_twist(twist).to_c(times is not None), d_raw.data_ptr())
         d_cur = torch.empty_like(d_raw)
         n = ctx.voxel_downsample_device(d_raw.data_ptr(), d_raw.shape[0], voxel, d_cur.data_ptr(), d_raw.shape[0])
         if k == 0:
             prev = (d_cur, n)              # slam_node.cpp:69-72
+            report(k, twist, d_raw, d_cur, n, None)
             continue
         if n < min_points:                 # slam_node.cpp:125-130
             track.poses.append(track.poses[-1].copy())
@@ -120,8 +144,10 @@ def run_odometry_device(raw_frames, ctx, voxel=0.5, max_iterations=50, tolerance
             track.gated.append(True)
             prev = (d_cur, n)
             track.frame_ms.append(1e3 * (time.perf_counter() - t0))
+            report(k, twist, d_raw, d_cur, n, None)
             continue
         res, _hist = ctx.align_device(d_cur.data_ptr(), n, prev[0].data_ptr(), prev[1], cfg)
+        res.error_history = _hist
         bad = (not res.converged) or res.final_error > 1.0   # slam_node.cpp:139-140
         delta = np.eye(4) if bad else np.array(res.transformation[:]).reshape(4, 4)
         track.poses.append(track.poses[-1] @ delta)           # slam_node.cpp:142
@@ -132,6 +158,7 @@ def run_odometry_device(raw_frames, ctx, voxel=0.5, max_iterations=50, tolerance
         track.gated.append(bool(bad))
         prev = (d_cur, n)                                     # slam_node.cpp:152
         track.frame_ms.append(1e3 * (time.perf_counter() - t0))
+        report(k, twist, d_raw, d_cur, n, res)
     return track
 
 
@@ -220,12 +247,18 @@ class LocalMapOdometry:
     result has the fields of run_odometry's `align` results, .guess, .error_history, and .weight_sum / .pairs under a
     robust rule."""
 
-    def __init__(self, ctx, config=None, max_iterations=50, tolerance=1e-6, min_points=1000, motion_model=True, robust=None):
+    def __init__(self, ctx, config=None, max_iterations=50, tolerance=1e-6, min_points=1000, motion_model=True, robust=None,
+                 deskew=None, voxel=0.5):
+        """deskew: a deskew.DeskewConfig (None: none, and frames are taken as they come, already downsampled) -- a frame
+        is then a RAW sweep, `points` or `(points, times)`: it is deskewed (icpmi_deskew) with the twist of the previous
+        frame's delta (deskew.twist_from_delta; a zero twist for frames 0 and 1), filtered with `voxel`
+        (icpmi_voxel_downsample) and only then registered and added.  self.twist: the one last used."""
         from .local_map import LocalMap
         self.ctx, self.map = ctx, LocalMap(ctx, config)
         self.max_iterations, self.tolerance, self.min_points = max_iterations, tolerance, min_points
         self.motion_model, self.robust = motion_model, robust
         self.pose, self.delta, self.frames = np.eye(4), np.eye(4), 0
+        self.deskew, self.voxel, self.twist = deskew, voxel, None
 
     def close(self):
         self.map.close()
@@ -236,6 +269,10 @@ class LocalMapOdometry:
         class _R:
             pass
 
+        if self.deskew is not None:
+            from . import deskew as dk
+            rows, self.twist = dk.deskew_frame(self.ctx, frame, self.deskew, self.delta if self.frames >= 2 else None)
+            frame = self.ctx.voxel_downsample(rows, self.voxel)
         curr = np.ascontiguousarray(frame, dtype=np.float64)
         self.frames += 1
         if self.frames == 1:
@@ -264,19 +301,24 @@ class LocalMapOdometry:
 
 
 def run_odometry_local_map(frames, ctx, config=None, max_iterations=50, tolerance=1e-6, min_points=1000, motion_model=True,
-                           robust=None, on_frame=None):
+                           robust=None, on_frame=None, deskew=None, voxel=0.5):
     """Scan-to-local-map odometry over already-downsampled frames (LocalMapOdometry) -> OdometryTrack; track.deltas are
     pose_{k-1}^-1 . pose_k, track.map_rows the table's size after each frame, and under a robust rule (a capi.Robust, or
     (kind, scale[, max_distance])) track.weight_sums each registration's weight sum.  config: a local_map.LocalMapConfig;
-    its max_range must cover the sensor's range.  on_frame(k, local map, result or None): called after frame k is done."""
-    odo = LocalMapOdometry(ctx, config, max_iterations, tolerance, min_points, motion_model, robust)
+    its max_range must cover the sensor's range.  on_frame(k, local map, result or None): called after frame k is done.
+    deskew: a deskew.DeskewConfig -- the frames are then RAW sweeps, deskewed and filtered with `voxel` first (see
+    LocalMapOdometry); track.twists holds the twists used."""
+    odo = LocalMapOdometry(ctx, config, max_iterations, tolerance, min_points, motion_model, robust, deskew, voxel)
     track = OdometryTrack()
     track.map_rows = []
     track.weight_sums = []
+    track.twists = []
     try:
         for k, curr in enumerate(frames):
             t0 = time.perf_counter()
             out = odo.push(curr)
+            if deskew is not None:
+                track.twists.append(odo.twist)
             track.map_rows.append(odo.map.size())
             if out is not None:
                 delta, r, bad = out

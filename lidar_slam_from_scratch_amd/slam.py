@@ -41,6 +41,7 @@ class SlamRun:
         self.loop_weights = None      # with loop_edge_loss: each closure's weight after the final optimize, if it succeeded
         self.loop_distances = None    # ... and its whitened distance (sigmas)
         self.rejected_closures = []   # with closure_gate: (LoopClosureResult, d2) of every closure the gate kept out
+        self.odom_twists = []         # with deskew: the twist each frame was deskewed with
 
 
 def node_loop_config():
@@ -52,7 +53,7 @@ def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, po
              align=None, loop_backend=None, pose_graph=None, global_map=None, grid=None, map_voxel=1.0,
              loop_on_device=False, raycast=False, counts=False, live=False, loop_yaw_guess=False, loop_gate=None,
              ground=None, odom_robust=None, loop_robust=None, odom_local_map=None, loop_edge_loss=None,
-             edge_information=None, information_floor=(1.0, 10.0), closure_gate=None):
+             edge_information=None, information_floor=(1.0, 10.0), closure_gate=None, deskew=None, deskew_voxel=0.5):
     """frames: sequence of N x 3 fp64 clouds (already downsampled).  Returns a SlamRun.  global_map: an object with
     add_frame, recent_clouds and finish (None: no map is built); grid: its occupancy grid config (None: defaults).
     loop_on_device: the detector is loop_closure.StoreLoopClosureDetector over global_map (a global_map.GlobalMap),
@@ -101,7 +102,12 @@ def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, po
     detect() is judged against that one state: d^2 = pose_graph.closure_distance(match, query, transform, Sigma_edge),
     Sigma_edge the loop factor's own noise (the configured loop sigmas squared, or the inverse of the edge's
     information matrix under edge_information).  Closures with d^2 <= closure_gate are added as without a gate; the
-    others go to SlamRun.rejected_closures as (closure, d^2) and never enter the graph."""
+    others go to SlamRun.rejected_closures as (closure, d^2) and never enter the graph.
+    deskew: a deskew.DeskewConfig (None: none; not in the reference node).  The frames are then RAW sweeps,
+    each `points` or `(points, times)`: before anything else sees it, a frame is deskewed (icpmi_deskew) with the twist of
+    the previous odometry delta (deskew.twist_from_delta; a zero twist for frames 0 and 1, and after a frame of too few
+    points) and filtered with deskew_voxel (icpmi_voxel_downsample).  What is kept, registered, mapped and searched for
+    closures is that scan; SlamRun.odom_twists holds the twists used."""
     if loop_on_device and loop_backend is not None:
         raise ValueError("loop_backend and loop_on_device=True both choose the detector")
     if align is not None and odom_robust is not None:
@@ -200,20 +206,31 @@ def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, po
                 run.rejected_closures.append((c, d2))
         return passed
 
+    last_delta = [None]                                              # the odometry delta the next frame is deskewed with
+
+    def scan(frame):
+        if deskew is None:
+            return np.ascontiguousarray(frame, dtype=np.float64)
+        from . import deskew as dk
+        rows, twist = dk.deskew_frame(ctx, frame, deskew, last_delta[0])
+        run.odom_twists.append(twist)
+        return np.ascontiguousarray(ctx.voxel_downsample(rows, deskew_voxel), dtype=np.float64)
+
     add("prior", 0, np.eye(4))                                       # :66
     frames = list(frames)
-    prev = np.ascontiguousarray(frames[0], dtype=np.float64)         # :69-72
+    prev = scan(frames[0])                                           # :69-72
     keep(prev)                                                       # :71
     if local_odo is not None:
         local_odo.push(prev)
     live_update()
     for k in range(1, len(frames)):
-        curr = np.ascontiguousarray(frames[k], dtype=np.float64)
+        curr = scan(frames[k])
         pending = False
         kept = keep(curr)                                            # :123
         if curr.shape[0] < min_points:                               # :125-130
             run.poses.append(run.poses[-1].copy())
             prev = curr
+            last_delta[0] = np.eye(4)
             if local_odo is not None:
                 local_odo.push(curr)
             live_update()
@@ -227,6 +244,7 @@ def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, po
             bad = (not r.converged) or r.final_error > 1.0           # :139-140
             delta = np.eye(4) if bad else np.asarray(r.transformation, dtype=np.float64)
         run.poses.append(run.poses[-1] @ delta)                      # :142-143
+        last_delta[0] = delta
         if info_args is not None and not bad:                        # the registration just run, at its own T
             from . import capi
             nm = ctx.last_normal_matrix()

@@ -300,3 +300,66 @@ def pose_delta(Ta, Tb):
     c = (np.trace(Rd) - 1.0) / 2.0
     s = np.linalg.norm([Rd[2, 1] - Rd[1, 2], Rd[0, 2] - Rd[2, 0], Rd[1, 0] - Rd[0, 1]]) / 2.0
     return dt, float(np.arctan2(s, c))
+
+
+# --------------------------------------------------------------------------- #
+# Sweeps: a scan whose columns are cast from the pose at their own time         #
+# (csrc/deskew.h).  Nothing above is touched.                      #
+# --------------------------------------------------------------------------- #
+
+def _raycast_sweep(origins, rotations, scene, beams=64, max_range=80.0):
+    """_raycast with one pose per azimuth column: column j is cast from origins[j] with rotations[j] (sensor -> world).
+    The azimuths lie half a step off -pi (no beam on the seam where an azimuth-derived time jumps) and are swept counter-
+    clockwise.  -> (returns in the sensor frame OF THEIR COLUMN'S POSE, beam-major like _raycast; the column of each)"""
+    origins, rotations = np.asarray(origins, dtype=np.float64), np.asarray(rotations, dtype=np.float64)
+    azimuths = origins.shape[0]
+    el = np.deg2rad(np.linspace(-24.8, 2.0, beams))
+    az = np.linspace(-np.pi, np.pi, azimuths, endpoint=False) + np.pi / azimuths
+    ce, se = np.cos(el)[:, None], np.sin(el)[:, None]
+    d_local = np.stack([ce * np.cos(az)[None, :], ce * np.sin(az)[None, :], np.broadcast_to(se, (beams, azimuths))], axis=-1)
+    d = np.einsum("jab,ijb->ija", rotations, d_local).reshape(-1, 3)          # R_j d_local[i, j]
+    col = np.broadcast_to(np.arange(azimuths)[None, :], (beams, azimuths)).reshape(-1)
+    o = origins[col]
+    t_hit = np.full(d.shape[0], np.inf)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        tg = (-1.73 - o[:, 2]) / d[:, 2]
+    ok = (tg > 0) & np.isfinite(tg)
+    t_hit[ok] = tg[ok]
+    for lo, hi in scene:
+        with np.errstate(divide="ignore", invalid="ignore"):
+            t1 = (lo - o) / d
+            t2 = (hi - o) / d
+        tmin = np.nanmax(np.minimum(t1, t2), axis=1)
+        tmax = np.nanmin(np.maximum(t1, t2), axis=1)
+        hit = (tmax >= tmin) & (tmax > 0) & (tmin > 0)
+        t_hit = np.where(hit & (tmin < t_hit), tmin, t_hit)
+    keep = np.isfinite(t_hit) & (t_hit <= max_range) & (t_hit > 0.5)
+    rel = d[keep] * t_hit[keep, None]                                          # world - origin
+    return np.einsum("nba,nb->na", rotations[col[keep]], rel), col[keep]       # R_j^T (world - origin)
+
+
+def accel_pose(frame, x0=-50.0, speed0=0.3, accel=0.16, yaw_deg=0.12):
+    """Pose of the sensor at `frame` (a real number: a sweep asks for the pose between two frames) of a drive whose speed
+    and yaw rate change from frame to frame: speed0 + accel * frame metres per frame along world x, yaw = yaw_deg *
+    frame^2 degrees.  Frames -0.5 .. 11.5 cover x in [-50.2, -36.0]: inside the scene's walls (x in [-85, 85]) and clear
+    of its boxes.  It starts 10 m behind lidar_pose's drive: from -40, at 16 x 600, single registrations of the skewed
+    and of the causally deskewed runs fail to converge and are gated, and one gated frame moves a 12-frame ATE by more
+    than the effect the drive is there to show."""
+    f = float(frame)
+    T = np.eye(4)
+    T[:3, :3] = rotvec_to_matrix((0.0, 0.0, np.deg2rad(yaw_deg) * f * f))
+    T[:3, 3] = (x0 + speed0 * f + 0.5 * accel * f * f, 0.0, 0.0)
+    return T
+
+
+def lidar_sweep(frame, pose_fn=accel_pose, t_ref=0.5, beams=64, azimuths=1800, range_noise=0.01, seed=3):
+    """One raw (unfiltered) scan of the synthetic street taken over a whole sweep: column j, at tau_j = (j + 0.5) /
+    azimuths of the sweep, is cast from pose_fn(frame + tau_j - t_ref), so the pose at tau = t_ref is pose_fn(frame).
+    -> (rows in the INSTANTANEOUS sensor frame of their column, tau per row)"""
+    tau = (np.arange(azimuths) + 0.5) / azimuths
+    poses = np.stack([pose_fn(frame + t - t_ref) for t in tau])
+    pts, col = _raycast_sweep(poses[:, :3, 3], poses[:, :3, :3], _scene(seed), beams=beams)
+    rng = np.random.Generator(np.random.PCG64(1000 + int(frame)))
+    r = np.linalg.norm(pts, axis=1, keepdims=True)
+    pts = pts * (1.0 + rng.normal(0.0, range_noise, size=r.shape) / np.maximum(r, 1e-9))
+    return pts, tau[col]
