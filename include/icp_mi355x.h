@@ -135,6 +135,11 @@ typedef struct {
                                                         loops over sources of 65,473 rows and more): passes queued without the row-list
                                                         and coarse launches, because the two latest passes the host knew of had
                                                         listed no row.  Counted on the host, profiling on or off */
+    int64_t nn_full_culled_passes;                   /* all-pairs engine, culled full passes (ICPMI_NN_CULL_FULL, default on; single-GPU
+                                                        ungated loops with list reuse and sorted rows -- sources of 4,096 rows and more -- over targets of 13 to 3,072 splits): the passes
+                                                        that list every row -- a call's first two -- whose coarse launch ran over the
+                                                        (32-row tile, split) pairs that survive the box test instead of all pairs.
+                                                        Counted on the host, profiling on or off */
 } icpmi_profile;
 
 void icpmi_options_default(icpmi_options *opt);     /* device 0, normal_k 20 (icp.hpp:170), search AUTO or the

@@ -588,6 +588,9 @@ bool nn_margin_enabled() { return env_on("ICPMI_NN_MARGIN"); }
 // (k >= 2) is a TEST HOOK: every pass from the k-th on is lean whatever the counts say, which is the only way to put many
 // rows through a lean pass's exhaustive search.  Both are read at every call like ICPMI_NN_MARGIN.
 bool nn_lean_enabled() { return env_on("ICPMI_NN_LEAN"); }
+// Culled full passes (LoopPlan::cull_full, loop_plan.h).  ICPMI_NN_CULL_FULL=0: a call's first two passes
+// evaluate all pairs, the launches of the form before -- the reference leg of tests and A/B runs.  Read at every call.
+bool nn_cull_full_enabled() { return env_on("ICPMI_NN_CULL_FULL"); }
 int nn_lean_from()
 {
     const char *e = getenv("ICPMI_NN_LEAN_FROM");
@@ -682,6 +685,8 @@ struct NnPass {
     bool list = false;    // list reuse: the coarse pass runs over the packed list of the rows listed again
     bool lean = false;    // a lean pass: no coarse launch
     bool margin = false;  // the match margin's resolve
+    int culled_full = -1; // all-pairs engine, a culled full pass (LoopPlan::cull_full): which pass of the call, 0 or 1 (selects
+                          // the set of group lists like pruned_pass); -1: not one
 };
 int launch_nn_mfma(icpmi_ctx *ctx, const double *d_qry, int n, int m, int *d_idx, double *d_d2,
                    const IcpState *st, const double *d_tgt = nullptr, const double *d_nrm = nullptr,
@@ -701,17 +706,22 @@ int launch_nn_mfma(icpmi_ctx *ctx, const double *d_qry, int n, int m, int *d_idx
         if (!pass.lean) {
             StageTimer tc(ctx, ST_COARSE);
             const KnnLists kl{lr.ubf, lr.sqf, lr.cnt, lr.ent, kNnEntCap};
-            if (pass.pruned_pass >= 0) {
+            if (pass.pruned_pass >= 0 || pass.culled_full >= 0) {
                 // the culled engine's surviving (row group, split) pairs, list epilogue: a row's list then holds slots of
                 // evaluated splits only, and every split that can hold a target within the row's bound IS evaluated (the
                 // group's bound is the largest of its rows'); pass p reads the lists counted in set p & 1 and clears the other
-                const GroupLists cur = group_lists(ctx, pass.pruned_pass & 1), nxt = group_lists(ctx, (pass.pruned_pass + 1) & 1);
+                // (the all-pairs engine's culled full passes: the same launch on the same sets, nothing counted -- the pair
+                // counters are the culled engine's)
+                const bool full = pass.pruned_pass < 0;
+                const int parity = (full ? pass.culled_full : pass.pruned_pass) & 1;
+                const GroupLists cur = group_lists(ctx, parity), nxt = group_lists(ctx, parity ^ 1);
                 const long groups = (n + kGroupRows - 1) / kGroupRows;
+                if (full) ctx->prof.nn_full_culled_passes += 1;
                 hipLaunchKernelGGL((k_nn_coarse_groups<false, kCoarseWaves>), dim3(coarse_groups_grid(ctx)), dim3(kCoarseThreads),
                                    coarse_groups_lds(splits), ctx->stream, d_qry, n, (size_t)0, (const uint4 *)ctx->bpack.p, frames, splits,
                                    (const unsigned *)cur.items, cur.cap, (const unsigned *)cur.cnt, nxt.cnt,
-                                   ctx->opt.profile ? group_stats(ctx) : (unsigned long long *)nullptr, (unsigned long long)(groups * splits),
-                                   st, kl, group_work(ctx, pass.pruned_pass & 1), group_work(ctx, (pass.pruned_pass + 1) & 1));
+                                   ctx->opt.profile && !full ? group_stats(ctx) : (unsigned long long *)nullptr, (unsigned long long)(groups * splits),
+                                   st, kl, group_work(ctx, parity), group_work(ctx, parity ^ 1));
             } else {
                 // list reuse (`pass.list`): the pass runs over the packed list of the rows listed again (k_row_list) and no others
                 const int *list = pass.list ? lr.list : nullptr;
@@ -816,8 +826,9 @@ bool knn_lists_enabled()
 // prepare_nn builds for both engines) once the target has more than kKnnCullFromSplits splits -- the size from which AUTO
 // takes the culled engine (kAutoCulledFrom, profiles/r4_final/engine_threshold.json); at a dozen splits or fewer the
 // all-pairs form stays, launch for launch.  ICPMI_KNN_CULL=0: the all-pairs coarse pass at every size (the reference leg of
-// tests/test_gpu_knn_cull_allpairs.py).  The ICP loop of the engine is all pairs either way.
-constexpr int kKnnCullFromSplits = kAutoCulledFrom;
+// tests/test_gpu_knn_cull_allpairs.py).  The engine's ICP loop culls its first two passes over the same window of sizes
+// (LoopPlan::cull_full, loop_plan.h, where the two limits live) and is all pairs from the third pass on.
+static_assert(kKnnCullFromSplits == kAutoCulledFrom, "the all-pairs engine culls from the size AUTO takes the culled engine from");
 bool knn_cull_enabled()
 {
     static const bool on = env_on("ICPMI_KNN_CULL");
@@ -1274,6 +1285,7 @@ struct LoopRun {
         f.sw_lean = nn_lean_enabled();
         f.sw_lean_from = nn_lean_from();
         f.sw_fuse_finish = fuse_finish_enabled();
+        f.sw_cull_full = nn_cull_full_enabled();
         p = make_loop_plan(f);
         if (p.error) return fail(ctx, ICPMI_ERR_ARG, p.error, p.rblocks);
         int rc;
@@ -1327,7 +1339,7 @@ struct LoopRun {
             if ((rc = reserve(ctx, ctx->sort_tmp, sort_bytes))) return rc; // the target's sort is done (stream order)
             if ((rc = reserve(ctx, ctx->bbox_part, sizeof(double) * 6 * (size_t)bblocks))) return rc;
         }
-        if (p.pruned) { // the group lists of the coming passes (nn_culled.h); both sets of counters start empty
+        if (p.pruned || p.cull_full) { // the group lists of the coming passes (nn_culled.h); both sets of counters start empty
             if ((rc = reserve_group_lists(ctx, ctx->nn_splits, (n + kGroupRows - 1) / kGroupRows))) return rc;
             HIP_TRY(ctx, hipMemsetAsync(ctx->grp_cnt.p, 0, group_cnt_bytes(ctx), s));
         }
@@ -1373,11 +1385,12 @@ struct LoopRun {
         if (n > 0 && !p.small) { // (an empty shard of a sharded run launches nothing over its rows; the small-cloud kernel moves them itself)
             StageTimer t(ctx, ST_TRANSFORM);
             hipLaunchKernelGGL(k_transform, dim3(std::min(2048, (n + 255) / 256)), dim3(256), 0, s, d_src, cur, n, st, 1, 0, src_perm);
-            if (p.bounded) // the first pass's incumbents and bounds (and, culled engine, its group lists: set 0)
+            if (p.bounded) // the first pass's incumbents and bounds (and, culled engine and culled full passes, its group lists: set 0)
                 hipLaunchKernelGGL(k_nn_prebound1, dim3((n + kPreThreads - 1) / kPreThreads), dim3(kPreThreads), 0, s, (const double *)cur, n, (const double *)ctx->tgt_sorted.p,
                                    (const unsigned *)ctx->sort_keys.p + (size_t)m /* the sorted keys */,
                                    (const unsigned *)ctx->sort_keys.p + 3 * (size_t)m, m, ctx->nn_ms, (const NnFrame *)ctx->nn_misc.p, idx, rb,
-                                   (const SplitFrame *)ctx->frames.p, ctx->nn_splits, p.pruned ? group_lists(ctx, 0) : GroupLists{nullptr, nullptr, 0});
+                                   (const SplitFrame *)ctx->frames.p, ctx->nn_splits,
+                                   p.pruned || p.cull_full ? group_lists(ctx, 0) : GroupLists{nullptr, nullptr, 0});
         }
         return ICPMI_OK;
     }
@@ -1431,7 +1444,8 @@ struct LoopRun {
         if (n <= 0) return ICPMI_OK;
         if (!p.fused) return launch_nn(ctx, cur, n, d_tgt, m, idx, nullptr, st);
         // (bounded: incumbents in idx, bounds in place -- from k_nn_prebound1 or the kernel that moved the rows)
-        const NnPass pass{p.pruned ? pass_no : -1, p.bounded, pass_list, lean_cur, p.margin};
+        // (culled full passes: a call's first two, whichever of them is the post-loop pass)
+        const NnPass pass{p.pruned ? pass_no : -1, p.bounded, pass_list, lean_cur, p.margin, p.cull_full && pass_no < 2 ? pass_no : -1};
         return launch_nn_mfma(ctx, cur, n, m, idx, nullptr, st, d_tgt, nrm, partials, pass);
     }
 
@@ -1530,6 +1544,11 @@ struct LoopRun {
                 hipLaunchKernelGGL(k_transform, dim3(std::min(2048, (n + 255) / 256)), dim3(256), 0, s,
                                    cur, cur, n, st, 0, 1, (const unsigned *)nullptr, rb);
         }
+        // culled full passes: the box test of the rows the first pass's mover has just left, into set 1 -- the second pass's
+        // group lists (the first pass's coarse kernel has cleared that set's counters)
+        if (p.cull_full && pass_no == 1 && !final_pass && !lean_nxt)
+            hipLaunchKernelGGL(k_row_group_cull, dim3(((n + 63) / 64 + 15) / 16), dim3(1024), 0, s, (const double *)cur, n, (const float *)lr.ubf,
+                               (const SplitFrame *)ctx->frames.p, ctx->nn_splits, group_lists(ctx, 1), (const IcpState *)st);
         if (pass_list && !lean_nxt) // the rows just moved left their "listed again" words: the coming pass's list of rows
             hipLaunchKernelGGL(k_row_list, dim3(((n + 63) / 64 + kRowListThreads - 1) / kRowListThreads), dim3(kRowListThreads), 0, s,
                                (const unsigned long long *)lr.mask, n, lr.list, (const IcpState *)st,

@@ -26,6 +26,16 @@ constexpr int kSumTreeFrom = 1024;
 // (AUTO takes the exact fp64 kernels for sources of fewer rows: engine_for in capi.hip)
 constexpr int kMfmaMinQueries = 64;
 
+// The box test of nn_culled.h (32-row tile against 2,048-target split) on the all-pairs engine: the target's 20-NN pass and
+// the two passes of a registration that list every row (LoopPlan::cull_full) run over the surviving pairs once the target
+// has more than kKnnCullFromSplits splits -- the size from which AUTO takes the culled engine (kAutoCulledFrom, capi.hip) --
+// and at most kCullMaxSplits: the splits whose running sums fit k_nn_coarse_groups' LDS beside its 36 KiB of staging
+// (2 x 3072 + 1 words of the 64 KiB a workgroup may have: 6.3M targets; nn_culled.h holds the assertion).  That kernel
+// keeps a list's length in 20 bits (tiles of 32 rows): sources of fewer than kCullMaxRows rows.
+constexpr int kKnnCullFromSplits = 12;
+constexpr int kCullMaxSplits = 3072;
+constexpr int kCullMaxRows = 1 << 25;
+
 // Small clouds (the reference's real callers: filtered scans of 5-20k points): search, residuals and
 // pose update of the rows in ONE kernel per iteration (icp_small.h) when the target is at most
 // kSmallMaxSplits splits and the source at most kSmallMaxQueries rows (beyond, the general path's 512-query
@@ -92,6 +102,7 @@ struct LoopFacts {
     bool sw_bounded = true, sw_reuse = true, sw_margin = true, sw_lean = true;
     int sw_lean_from = 0;   // ICPMI_NN_LEAN_FROM: 0 or k >= 2
     bool sw_fuse_finish = true;
+    bool sw_cull_full = true; // ICPMI_NN_CULL_FULL, read at every call
 };
 
 // (by the target alone: whether its Morton-ordered normals are worth keeping)
@@ -121,6 +132,7 @@ struct LoopPlan {
     int rblocks2 = 0;              // ... into this many rows behind them
     int fin_blocks = 0;            // rows the step kernels sum
     const char *error = nullptr;   // a refusal ("internal: ..."; a format that takes rblocks), or null
+    bool cull_full = false;        // all-pairs engine: the two passes that list every row run over the box test's survivors
 };
 
 inline LoopPlan make_loop_plan(const LoopFacts &f)
@@ -189,6 +201,16 @@ inline LoopPlan make_loop_plan(const LoopFacts &f)
     p.fused_tail = !p.sharded && f.rule == kRuleNone && f.sw_fuse_finish;
     p.lean_on = p.reuse && p.fused_tail && p.sum_tree && f.sw_lean;
     p.lean_from = p.lean_on ? f.sw_lean_from : 0;
+    // Culled full passes: a call's first two passes list every row -- the first has only k_nn_prebound1's
+    // bound, the second follows lists that are not kept -- and evaluate all n x m pairs for it.  Over targets of the sizes
+    // at which the 20-NN pass is culled (knn_culled, capi.hip) they run k_nn_coarse_groups on the (32-row tile, split) pairs
+    // whose boxes are within the tile's largest listing radius instead: single GPU, no rule, list reuse on.  Every later
+    // pass and every other kernel of the loop stays as it is.  ICPMI_NN_CULL_FULL=0: all pairs, the form before.
+    // (Only where the rows are in Morton order: a tile of 32 rows in the caller's order spans the cloud, every pair survives
+    // the box test and the lists are pure cost -- measured, sources of 1,000 to 4,000 unsorted rows against 30,000 and
+    // 100,000 points: 0.525 -> 0.543, 0.789 -> 0.812 and 0.917 -> 0.935 ms a call of 9 iterations with the passes culled.)
+    p.cull_full = p.reuse && p.sorted_rows_loop && !p.sharded && f.rule == kRuleNone && f.nn_splits > kKnnCullFromSplits &&
+                  f.nn_splits <= kCullMaxSplits && n < kCullMaxRows && f.sw_cull_full;
     return p;
 }
 

@@ -30,7 +30,7 @@
 namespace icpmi {
 
 constexpr int kGroupRows = 32;          // rows per group: one 32-row MFMA tile (a wave of the coarse pass takes two, any two of a split's list)
-constexpr int kCullMaxSplits = 3072;    // splits whose running sums fit the coarse kernel's LDS beside its 36 KiB of staging (2 x 3072 + 1 words of the 64 KiB a workgroup may have): 6.3M targets; beyond: all pairs
+// (kCullMaxSplits = 3072, loop_plan.h: the splits whose running sums fit the coarse kernel's LDS beside its staging; beyond: all pairs)
 static_assert(kGroupRows == kTile && kCoarseQT == 2, "a group is one tile; a wave of the coarse unit takes two");
 static_assert(sizeof(uint4) * CoarseLds<kCoarseWaves>::SCRATCH16 + sizeof(unsigned) * (2 * kCullMaxSplits + 1) + 64 <= 65536,
               "k_nn_coarse_groups: staging + the running sums of kCullMaxSplits splits must fit a workgroup's 64 KiB of LDS");
@@ -52,7 +52,7 @@ struct GroupLists {
 // ~7,400 pairs of a C3 pass queued up on 49 addresses: 150 returning atomics per address, one after the other in the L2 --
 // the kernel took 29.6 us against the 16.9 of the form without lists.)  Must be called by every wave of the workgroup
 // (four barriers); a wave without rows passes lo = +big, hi = -big.
-constexpr int kCullMaxRows = 1 << 25;                      // rows of a source (k_nn_coarse_groups keeps a list's length in 20 bits: tiles of 32 rows)
+// (kCullMaxRows = 2^25 rows of a source, loop_plan.h: k_nn_coarse_groups keeps a list's length in 20 bits, tiles of 32 rows)
 constexpr int kCullLdsBoxes = 128; // targets of up to this many splits (262k points): the splits' boxes are staged in LDS
 struct CullLds {
     unsigned cnt[kCullMaxSplits];   // survivors of this workgroup per split, then the cursor inside its run
@@ -462,6 +462,36 @@ __global__ __launch_bounds__(1024) void k_knn_group_cull(const double *__restric
             lo[0] = hi[0] = x, lo[1] = hi[1] = y, lo[2] = hi[2] = z;
             const double t = t_row[local];
             ub = t == t ? t : __builtin_inf();
+        }
+    }
+    block_cull(cl, 2 * w, lo, hi, ub, frames, nsplits, gl, lane); // (a wave past the last group brings empty boxes)
+}
+
+// ---- all-pairs engine, a call's second pass (LoopPlan::cull_full): the groups are runs of 32 moved source rows --------
+// Queued once per call behind the kernel that moved the rows after the first pass (the reuse mover, RowBatch::finish: it
+// knows nothing of groups, and sits at its register limit).  A row takes part iff the coming coarse pass lists it: ubf[i]
+// is its listing radius^2 rounded up to fp32 -- what coarse_epilogue derives the row's per-split thresholds from -- and NaN
+// for a row with a non-finite coordinate, one that keeps its list and one the match margin certified.  The group's bound
+// is the largest ubf of its rows, NOT the largest ub: with list reuse a row is listed for R_b = sqrt(ub) + 2 skin
+// (list_radius), and its kept list must hold every target within R_b.  +Inf (a row without a match) stays +Inf:
+// block_cull gives such a tile the bound that needs no match.  One wave per pair of groups like k_knn_group_cull; nothing
+// where the loop has ended (the rows were not moved and no pass follows), like k_row_list.
+__global__ __launch_bounds__(1024) void k_row_group_cull(const double *__restrict__ cur, int n, const float *__restrict__ ubf,
+                                                        const SplitFrame *__restrict__ frames, int nsplits, const GroupLists gl,
+                                                        const IcpState *__restrict__ st)
+{
+    __shared__ CullLds cl;
+    if (st->done) return; // (the whole grid alike)
+    cull_stage_boxes(cl, frames, nsplits);
+    const int lane = threadIdx.x & 63;
+    const int w = blockIdx.x * 16 + (threadIdx.x >> 6); // the wave's 64 rows: groups 2 w and 2 w + 1
+    const int i = w * 64 + lane;
+    double lo[3] = {1.7e308, 1.7e308, 1.7e308}, hi[3] = {-1.7e308, -1.7e308, -1.7e308}, ub = 0.0;
+    if (i < n) {
+        const float u = ubf[i];
+        if (u == u) {
+            lo[0] = hi[0] = cur[3 * (size_t)i], lo[1] = hi[1] = cur[3 * (size_t)i + 1], lo[2] = hi[2] = cur[3 * (size_t)i + 2];
+            ub = (double)u;
         }
     }
     block_cull(cl, 2 * w, lo, hi, ub, frames, nsplits, gl, lane); // (a wave past the last group brings empty boxes)
