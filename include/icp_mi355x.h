@@ -263,6 +263,71 @@ int icpmi_align_robust_batch(icpmi_ctx *ctx, int32_t count, const double *const 
                              const icpmi_robust *rules, icpmi_result *results, icpmi_robust_info *infos,
                              double *error_history, int32_t history_stride, int32_t *status);
 
+/* Plane-to-plane (generalized) ICP: the same registrations with a local surface model on BOTH clouds (Segal's
+ * Generalized-ICP; not in the reference, whose cost is point-to-plane: icp.hpp:89-144), optionally behind the
+ * correspondence-distance gate above.  The plane-regularised covariance U diag(1, 1, epsilon) U^T of a row with unit
+ * normal n is I - (1 - epsilon) n n^T, so the normals are all either side needs and no eigendecomposition is run.
+ *
+ * Per pass, for row i of the moved source `cur` with nearest target j (`found`: the row has a neighbour), in unfused
+ * fp64 and in this order:
+ *     R    = rotation block of IcpState::total as the pass finds it (total[0..2], [4..6], [8..10])
+ *     s    = normal of source row i, estimated ONCE per call on the source as the caller gave it
+ *            (before initial_transform; k = options.normal_k; the normals launch_normals gives)
+ *     m_a  = (R[a][0]*s0 + R[a][1]*s1) + R[a][2]*s2
+ *     n    = normal of target j;  p = cur_i;  e = q_j - p;  d2 = (e0*e0 + e1*e1) + e2*e2
+ *     kept iff found && d2 <= g2      (g2 = max_distance^2, or DBL_MAX when max_distance == 0)
+ *     c = 1 - epsilon, kappa = 2*epsilon            (formed once on the host)
+ *     S_ab = (a==b ? 2.0 : 0.0) - c*(n_a*n_b + m_a*m_b)          for a <= b
+ *     C00 = S11*S22 - S12*S12;  C01 = S02*S12 - S01*S22;  C02 = S01*S12 - S02*S11
+ *     C11 = S00*S22 - S02*S02;  C12 = S01*S02 - S00*S12;  C22 = S00*S11 - S01*S01
+ *     det = (S00*C00 + S01*C01) + S02*C02;  r = 1.0/det;  M_ab = C_ab*r      (one division per kept row)
+ *     u_a = (M_a0*e0 + M_a1*e1) + M_a2*e2
+ *     A   = [ -[p]x | I ]:  A0 = (0, p2, -p1, 1,0,0), A1 = (-p2, 0, p0, 0,1,0), A2 = (p1, -p0, 0, 0,0,1)
+ *     B   = [p]x M (rows 0..2 against columns 3..5 of A^T M A; M_ab = M_ba):
+ *           B0c = p1*M2c - p2*M1c;  B1c = p2*M0c - p0*M2c;  B2c = p0*M1c - p1*M0c
+ *     G   = B (-[p]x) (rows and columns 0..2), for r <= c only:
+ *           Gr0 = Br2*p1 - Br1*p2;  Gr1 = Br0*p2 - Br2*p0;  Gr2 = Br1*p0 - Br0*p1
+ *     v   = p x u:  v0 = p1*u2 - p2*u1;  v1 = p2*u0 - p0*u2;  v2 = p0*u1 - p1*u0
+ * Columns of a kept row (the gated call's layout; a dropped row adds nothing):
+ *     0..20   the upper triangle of A^T M A, row by row:
+ *             G00 G01 G02 B00 B01 B02 | G11 G12 B10 B11 B12 | G22 B20 B21 B22 | M00 M01 M02 | M11 M12 | M22
+ *     21..26  A^T u = v0 v1 v2 u0 u1 u2
+ *     27      kappa * ((e0*u0 + e1*u1) + e2*u2)
+ *     28      1.0
+ * The step solves H x = g with H = sum A^T M A and g = sum A^T M e, as icpmi_align's solves JtJ x = Jtb (in the
+ * point-to-plane limit M = n n^T they are the same sums); icpmi_last_normal_matrix hands them over as JtJ, Jtb, sum_sq
+ * and weight = pairs.
+ * Error: final_error, the history and what both stopping tests read is sqrt(sum kappa e^T M e / pairs).  The factor
+ * kappa = 2 epsilon makes it read in METRES: with parallel normals kappa e^T M e = (e.n)^2 + epsilon * (tangential)^2, the
+ * point-to-plane residual plus a small tangential term.  Without it the Mahalanobis RMS would be 1/sqrt(2 epsilon) times
+ * larger and a caller's thresholds on final_error (the reference node's `> 1.0`, a loop detector's fitness `< 0.3`,
+ * `tolerance`, `min_error`) would all mean something else.
+ * epsilon = 1 gives S = 2 I and M = I / 2 exactly: point-to-point ICP.
+ * A pass that keeps no row ends the call as icpmi_align_gated's does; the step, total = delta * total, the post-loop
+ * entry and the history invariants are icpmi_align's.  A non-finite source row is dropped by the d2 test.
+ * Validation: epsilon finite with 0 < epsilon <= 1; max_distance 0 or finite and > 0 -- anything else is ICPMI_ERR_ARG; a
+ * NULL rule is ICPMI_ERR_NULL; a context with a communicator is refused (ICPMI_ERR_ARG).
+ * Path: at every size a stand-alone search on the context's engine, then the plane-to-plane sums, the gated step and the
+ * rows' move; the source's normals cost one 20-NN pass over the source per call, in front of the target's preparation,
+ * and a target the context had remembered is forgotten by such a call.
+ * info (may be NULL): pairs = rows kept by the pass that produced final_error, rows = n_src. */
+#define ICPMI_GICP_EPSILON_DEFAULT 1e-3
+typedef struct {
+    double epsilon;                /* the covariance along the normal, relative to 1 in the plane; finite, 0 < epsilon <= 1 */
+    double max_distance;           /* the gate, metres; 0: none */
+    int64_t reserved;
+} icpmi_gicp;
+typedef struct {
+    int64_t pairs;
+    int64_t rows;
+} icpmi_gicp_info;
+int icpmi_align_gicp(icpmi_ctx *ctx, const double *source_xyz, int64_t n_src, const double *target_xyz, int64_t n_tgt,
+                     const icpmi_config *cfg, const icpmi_gicp *rule, icpmi_result *result, icpmi_gicp_info *info,
+                     double *error_history, int32_t history_cap);
+int icpmi_align_gicp_device(icpmi_ctx *ctx, const double *d_source_xyz, int64_t n_src, const double *d_target_xyz,
+                            int64_t n_tgt, const icpmi_config *cfg, const icpmi_gicp *rule, icpmi_result *result,
+                            icpmi_gicp_info *info, double *error_history, int32_t history_cap);
+
 /* The normal equations of the pass that produced final_error of the last registration this context ran: what the
  * registration minimised, at its result.  Costs nothing: the sums come back with the result behind the call's one wait,
  * and this getter only copies them on the host.
@@ -276,7 +341,7 @@ int icpmi_align_robust_batch(icpmi_ctx *ctx, int32_t count, const double *const 
  *   T       the registration's result
  * After a loop that broke on a convergence test these are the breaking pass's sums, after an exhausted loop the
  * post-loop pass's; either way the pass ran at T.  k: the problem of the last icpmi_align*_batch call, 0 after a single
- * call (host or device entry, plain, gated or robust, icpmi_stream_push*, icpmi_local_map_register*).
+ * call (host or device entry, plain, gated, robust or plane-to-plane, icpmi_stream_push*, icpmi_local_map_register*).
  * ICPMI_ERR_ARG, with a text in icpmi_last_error: k out of range; no registration ran (a fresh context, a stream push
  * that registered nothing, a call that failed); a gated or robust pass that kept no row; a context with a
  * communicator (its sums are the ranks' shares). */

@@ -492,6 +492,46 @@ inline std::vector<RobustICPResult> align_robust_batch(Context &ctx, const Point
     return out;
 }
 
+// ---- plane-to-plane (generalized) ICP (icpmi_align_gicp*; not in the reference) ---------------------
+// Both clouds carry a local surface model, I - (1 - epsilon) n n^T of each row's normal, and every correspondence is
+// weighted by the inverse of the two summed; optionally behind the gate above (max_distance; 0: none).  epsilon = 1 is
+// point-to-point ICP.  icpmi_align_gicp in icp_mi355x.h has the contract; final_error and the history read in metres.
+// pairs: the rows kept by the pass that produced final_error, of `rows`.  (No overload in the Eigen adapter, as for
+// the gate: the adapter mirrors the reference's call shapes only.)
+struct GicpRule {
+    double epsilon = ICPMI_GICP_EPSILON_DEFAULT;
+    double max_distance = 0.0;
+};
+struct GicpICPResult : ICPResult {
+    long long pairs = 0;
+    long long rows = 0;
+};
+
+inline GicpICPResult align_gicp(Context &ctx, const double *source_xyz, std::size_t n_src, const double *target_xyz,
+                                std::size_t n_tgt, const GicpRule &rule, const ICPConfig &config = ICPConfig())
+{
+    icpmi_config k = detail::to_c(config);
+    icpmi_gicp g{};
+    g.epsilon = rule.epsilon;
+    g.max_distance = rule.max_distance;
+    icpmi_gicp_info info{};
+    std::vector<double> hist(static_cast<std::size_t>(config.max_iterations > 0 ? config.max_iterations : 0) + 1);
+    icpmi_result r;
+    const int rc = icpmi_align_gicp(ctx.get(), source_xyz, static_cast<int64_t>(n_src), target_xyz, static_cast<int64_t>(n_tgt),
+                                    &k, &g, &r, &info, hist.data(), static_cast<int32_t>(hist.size()));
+    if (rc != ICPMI_OK) throw IcpError(rc, icpmi_last_error(ctx.get()));
+    GicpICPResult out;
+    detail::fill(out, r, hist.data());
+    out.pairs = info.pairs;
+    out.rows = info.rows;
+    return out;
+}
+inline GicpICPResult align_gicp(const PointCloud &source, const PointCloud &target, const GicpRule &rule = GicpRule(),
+                                const ICPConfig &config = ICPConfig())
+{
+    return align_gicp(default_context(), source.data(), source.size(), target.data(), target.size(), rule, config);
+}
+
 // Same call shape as slam::icp_point_to_plane (icp.hpp:157-161).
 inline ICPResult icp_point_to_plane(const PointCloud &source, const PointCloud &target,
                                     const ICPConfig &config = ICPConfig())

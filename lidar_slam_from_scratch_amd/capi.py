@@ -53,6 +53,7 @@ EXPORTS = [
     "icpmi_pose_graph_marginals", "icpmi_pose_graph_relative_covariance", "icpmi_pose_graph_closure_distance",
     "icpmi_information_from_icp", "icpmi_last_normal_matrix", "icpmi_loop_set_information", "icpmi_loop_last_information",
     "icpmi_deskew_config_default", "icpmi_deskew", "icpmi_deskew_device", "icpmi_deskew_twist", "icpmi_stream_set_deskew",
+    "icpmi_align_gicp", "icpmi_align_gicp_device",
 ]
 
 
@@ -105,6 +106,30 @@ def as_robust(rule):
     r.kind, r.scale = int(rule[0]), float(rule[1])
     r.max_distance = float(rule[2]) if len(rule) > 2 else 0.0
     return r
+
+
+GICP_EPSILON_DEFAULT = 1e-3                 # ICPMI_GICP_EPSILON_DEFAULT
+
+
+class Gicp(C.Structure):
+    """icpmi_gicp: the rule of align_gicp* (plane-to-plane ICP): epsilon, the covariance along a row's normal relative to
+    1 in its plane (1: point-to-point), and the optional correspondence-distance gate (max_distance; 0: none)"""
+    _fields_ = [("epsilon", C.c_double), ("max_distance", C.c_double), ("reserved", C.c_int64)]
+
+
+class GicpInfo(C.Structure):
+    """icpmi_gicp_info: rows kept by the pass that produced final_error, of `rows`"""
+    _fields_ = [("pairs", C.c_int64), ("rows", C.c_int64)]
+
+
+def as_gicp(rule):
+    """a Gicp, or (epsilon,) or (epsilon, max_distance) -> Gicp"""
+    if isinstance(rule, Gicp):
+        return rule
+    g = Gicp()
+    g.epsilon = float(rule[0])
+    g.max_distance = float(rule[1]) if len(rule) > 1 else 0.0
+    return g
 
 
 class NormalMatrix(C.Structure):
@@ -346,6 +371,10 @@ def load_library(path=None):
     L.icpmi_align_robust_batch.argtypes = [vp, C.c_int32, C.POINTER(dp), C.POINTER(C.c_int64), C.POINTER(dp), C.POINTER(C.c_int64),
                                            C.POINTER(Config), C.POINTER(Robust), C.POINTER(Result), C.POINTER(RobustInfo), dp,
                                            C.c_int32, C.POINTER(C.c_int32)]
+    L.icpmi_align_gicp.argtypes = [vp, dp, C.c_int64, dp, C.c_int64, C.POINTER(Config), C.POINTER(Gicp),
+                                   C.POINTER(Result), C.POINTER(GicpInfo), dp, C.c_int32]
+    L.icpmi_align_gicp_device.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, C.POINTER(Config), C.POINTER(Gicp),
+                                          C.POINTER(Result), C.POINTER(GicpInfo), dp, C.c_int32]
     L.icpmi_stream_set_robust.argtypes = [vp, C.POINTER(Robust)]
     L.icpmi_stream_last_robust.argtypes = [vp, C.POINTER(RobustInfo)]
     L.icpmi_nearest_batch.argtypes = [vp, dp, C.c_int64, dp, C.c_int64, C.POINTER(C.c_int32), dp]
@@ -725,6 +754,27 @@ class Context:
         self._check(self._lib.icpmi_align_robust_device(self._h, C.c_void_p(src_ptr), n_src, C.c_void_p(tgt_ptr), n_tgt,
                                                         C.byref(cfg), C.byref(r), C.byref(res), C.byref(info),
                                                         _dp(hist), cap))
+        return res, hist[:res.history_len].copy(), info
+
+    def align_gicp(self, source, target, cfg, rule):
+        """align() with the plane-to-plane cost (icpmi_align_gicp; rule: see as_gicp) -> (Result, error history,
+        GicpInfo).  final_error and the history read in metres (the header has the scaling)."""
+        src, tgt = _f64(source), _f64(target)
+        cap = cfg.max_iterations + 1
+        hist = np.zeros(max(cap, 1))
+        res, info, g = Result(), GicpInfo(), as_gicp(rule)
+        self._check(self._lib.icpmi_align_gicp(self._h, _dp(src), src.shape[0], _dp(tgt), tgt.shape[0], C.byref(cfg),
+                                               C.byref(g), C.byref(res), C.byref(info), _dp(hist), cap))
+        return res, hist[:res.history_len].copy(), info
+
+    def align_gicp_device(self, src_ptr, n_src, tgt_ptr, n_tgt, cfg, rule):
+        """align_gicp with both clouds in device memory (addresses of row-major N x 3 fp64)"""
+        cap = cfg.max_iterations + 1
+        hist = np.zeros(max(cap, 1))
+        res, info, g = Result(), GicpInfo(), as_gicp(rule)
+        self._check(self._lib.icpmi_align_gicp_device(self._h, C.c_void_p(src_ptr), n_src, C.c_void_p(tgt_ptr), n_tgt,
+                                                      C.byref(cfg), C.byref(g), C.byref(res), C.byref(info),
+                                                      _dp(hist), cap))
         return res, hist[:res.history_len].copy(), info
 
     def align_robust_batch(self, sources, targets, cfgs, rules):

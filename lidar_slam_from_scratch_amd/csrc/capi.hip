@@ -38,6 +38,7 @@
 #include "icp_small.h"
 #include "icp_gated.h"
 #include "icp_robust.h"
+#include "icp_gicp.h"
 #include "knn_lists.h"
 #include "nn_bounded.h"
 #include "nn_culled.h"
@@ -216,6 +217,7 @@ struct icpmi_ctx {
     DevBuf knn_idx, slotmin, fb_list;         // k-NN lists, slot minima, rows for the exact fallback
     DevBuf nn_lists;                          // bounded 1-NN pass: per row bound, threshold, count, listed columns (nn_bounded.h)
     DevBuf nrm_sorted;                        // small-cloud kernel: the target normals in Morton order (SoA, stride nn_ms)
+    DevBuf src_nrm;                           // plane-to-plane ICP: the source's normals, in the caller's row order (icp_gicp.h)
     DevBuf vox_keys, vox_vals, vox_out;             // voxel filter: 64-bit keys (in/out/unique), values + run data, result
     DevBuf stream_prev, stream_cur, f32_stage;      // odometry stream: previous / current filtered scan; float32 upload staging
     int64_t stream_prev_n = -1;                     // rows of stream_prev (-1: no frame yet)
@@ -1152,10 +1154,14 @@ struct GateRun {
     int32_t kind = 0;        // ICPMI_ROBUST_* (0: the gate alone)
     double ks = 0.0;         // the kernels' scale: k for Huber, k * k for Geman-McClure
     double weight_sum = 0.0; // out: the weight sum of that same pass
+    // Plane-to-plane rows (icp_gicp.h): k_reduce_gicp runs in k_reduce_gated's place at every size, behind g2 (DBL_MAX: no
+    // gate), over the source's normals that align_device estimates first; the step kernel and the outputs are the gate's.
+    bool gicp = false;
+    double c = 0.0, kappa = 0.0; // 1 - epsilon, 2 * epsilon
 };
 static_assert(kRobustHuber == ICPMI_ROBUST_HUBER && kRobustGemanMcClure == ICPMI_ROBUST_GEMAN_MCCLURE, "the kernels' kinds are the header's");
 
-LoopRule rule_of(const GateRun *gate) { return !gate ? kRuleNone : gate->kind ? kRuleRobust : kRuleGate; }
+LoopRule rule_of(const GateRun *gate) { return !gate ? kRuleNone : gate->gicp ? kRuleGicp : gate->kind ? kRuleRobust : kRuleGate; }
 
 // One launch of the kernel that the call's rule selects out of a plain / gated / robust triple whose arguments differ only in
 // the rule's own, which go behind the common ones (k_reduce*, k_icp_small*).
@@ -1167,6 +1173,9 @@ void launch_by_rule(const GateRun *gate, void (*plain)(PA...), void (*gated)(GA.
     case kRuleRobust: hipLaunchKernelGGL(robust, grid, block, 0, s, common..., gate->g2, (int)gate->kind, gate->ks); break;
     case kRuleGate: hipLaunchKernelGGL(gated, grid, block, 0, s, common..., gate->g2); break;
     case kRuleNone: hipLaunchKernelGGL(plain, grid, block, 0, s, common...); break;
+    // (no member of these triples: LoopRun::pass_sums launches k_reduce_gicp itself, and make_loop_plan refuses -- LoopPlan::error,
+    // the call fails in settle_plan -- every plane-to-plane plan that would come here)
+    case kRuleGicp: break;
     }
 }
 
@@ -1255,6 +1264,20 @@ struct LoopRun {
         st = ctx->d_state;
         HIP_TRY(ctx, hipMemcpyAsync(st, hs, sizeof(IcpState), hipMemcpyHostToDevice, s));
         return ICPMI_OK;
+    }
+
+    // Stage 1b, plane-to-plane rows only (icp_gicp.h): the source's normals, once per call, on the rows as the caller gave
+    // them -- its search structure (prepare_nn) and launch_normals, as icpmi_estimate_normals runs them -- into src_nrm in
+    // the caller's row order, on the call's stream and in front of the target's preparation, whose buffers it uses.  A
+    // target the context remembered (prep_valid) is forgotten by it: prepare_search then builds this call's target anew.
+    int source_normals()
+    {
+        if (!gate || !gate->gicp || n <= 0) return ICPMI_OK; // (never on a context with a communicator: validate_gicp)
+        int rc;
+        if ((rc = reserve(ctx, ctx->src_nrm, sizeof(double) * 3 * (size_t)n))) return rc;
+        if ((rc = prepare_nn(ctx, d_src, n, n))) return rc;
+        const int k = ctx->opt.normal_k;
+        return launch_normals(ctx, d_src, n, k, 0, n, (double *)ctx->src_nrm.p, sorted_normal_rows(ctx, k, n), true);
     }
 
     // Stage 2a: the target's search structure, unless the context holds it (prepare_target)
@@ -1400,6 +1423,7 @@ struct LoopRun {
     {
         switch (p.rule) {
         case kRuleRobust: hipLaunchKernelGGL(k_finish_step_robust, dim3(1), dim3(kFinishThreads), 0, s, rows, blocks, st, hist, final_pass, progress, ticket); break;
+        case kRuleGicp: // (the gate's partial row: 28 sums and the kept rows)
         case kRuleGate: hipLaunchKernelGGL(k_finish_step_gated, dim3(1), dim3(kFinishThreads), 0, s, rows, blocks, st, hist, final_pass, progress, ticket); break;
         case kRuleNone: hipLaunchKernelGGL(k_finish_step, dim3(1), dim3(kFinishThreads), 0, s, rows, blocks, n, st, hist, final_pass, progress, ticket); break;
         }
@@ -1452,7 +1476,11 @@ struct LoopRun {
     // ... the partial rows of an unfused pass (k_reduce*) and, of very many rows, their sums in groups
     void pass_sums()
     {
-        if (!p.fused)
+        if (p.rule == kRuleGicp)
+            hipLaunchKernelGGL(k_reduce_gicp, dim3(p.rblocks), dim3(256), 0, s, (const double *)cur, n, d_tgt, m, (const double *)nrm,
+                               (const int *)idx, (const double *)ctx->src_nrm.p, partials, (const IcpState *)st, gate->g2, gate->c,
+                               gate->kappa);
+        else if (!p.fused)
             launch_by_rule(gate, k_reduce_rule<RuleNone>, k_reduce_rule<RuleGate, double>, k_reduce_rule<RuleRobust, double, int, double>, dim3(p.rblocks), dim3(256), s, (const double *)cur, n, d_tgt, m,
                            (const double *)nrm, (const int *)idx, partials, (const IcpState *)st);
         if (p.sum_tree && p.lean_on) { // (+ the workgroup that counts the rows this pass wanted listed; pass_no - 1: this pass, from 0)
@@ -1753,6 +1781,8 @@ struct LoopRun {
 // `gate` (may be null): see GateRun.  A gated registration runs the small-cloud kernel's gated form in the small regime
 // and otherwise the unfused general path -- search (launch_nn), k_reduce_gated, k_finish_step_gated, k_transform -- on
 // whichever engine prepare_nn chose: no fused resolve, no culling, no bounds, no list reuse, no sorted rows.
+// A plane-to-plane registration (GateRun::gicp) runs that general path at every size, with k_reduce_gicp for the sums,
+// behind the source's normals (LoopRun::source_normals).
 // `before_wait`, `after_first` (may be null): see LoopRun::results_back and LoopRun::queue_loop.
 int align_device(icpmi_ctx *ctx, const double *d_src, int64_t n_src64, const double *d_tgt,
                  int64_t n_tgt64, const icpmi_config *cfg, icpmi_result *result,
@@ -1762,6 +1792,7 @@ int align_device(icpmi_ctx *ctx, const double *d_src, int64_t n_src64, const dou
     LoopRun run{ctx, d_src, d_tgt, cfg, gate, (int)n_src64, (int)n_tgt64, cfg->max_iterations + 1, ctx->stream};
     int rc;
     if ((rc = run.begin())) return rc;
+    if ((rc = run.source_normals())) return rc;
     if ((rc = run.prepare_search())) return rc;
     if ((rc = run.settle_plan())) return rc;
     if ((rc = run.target_normals())) return rc;
@@ -2111,7 +2142,7 @@ void icpmi_destroy(icpmi_ctx *ctx)
     for (DevBuf *b : {&ctx->cur, &ctx->nrm, &ctx->idx, &ctx->part_d2, &ctx->part_idx, &ctx->partials,
                       &ctx->history, &ctx->stage_a, &ctx->stage_b, &ctx->stage_c, &ctx->d2out, &ctx->src_sort, &ctx->grp_cnt, &ctx->grp_items,
                       &ctx->bpack, &ctx->coarse, &ctx->bbox_part, &ctx->nn_misc, &ctx->knn_idx, &ctx->slotmin, &ctx->nn_lists, &ctx->nrm_sorted,
-                      &ctx->fb_list, &ctx->sort_keys, &ctx->sort_tmp, &ctx->tgt_sorted, &ctx->frames, &ctx->vox_keys,
+                      &ctx->src_nrm, &ctx->fb_list, &ctx->sort_keys, &ctx->sort_tmp, &ctx->tgt_sorted, &ctx->frames, &ctx->vox_keys,
                       &ctx->vox_vals, &ctx->vox_out, &ctx->stream_prev, &ctx->stream_cur, &ctx->f32_stage, &ctx->deskew_raw, &ctx->deskew_times, &ctx->grid_set,
                       &ctx->grid_in, &ctx->grid_out, &ctx->grid_cnt, &ctx->world})
         release(*b);
@@ -2167,6 +2198,23 @@ int validate_robust(icpmi_ctx *ctx, const icpmi_robust *rule, GateRun *run)
     run->kind = rule->kind;
     run->ks = rule->kind == ICPMI_ROBUST_GEMAN_MCCLURE ? rule->scale * rule->scale : rule->scale;
     run->weight_sum = 0.0;
+    return ICPMI_OK;
+}
+
+// the rule of the plane-to-plane entry points (icp_gicp.h) -> the run
+int validate_gicp(icpmi_ctx *ctx, const icpmi_gicp *rule, GateRun *run)
+{
+    if (!rule) return fail(ctx, ICPMI_ERR_NULL, "rule is NULL (point-to-plane: icpmi_align*)");
+    if (!(rule->epsilon > 0.0 && rule->epsilon <= 1.0)) return fail(ctx, ICPMI_ERR_ARG, "epsilon must be finite with 0 < epsilon <= 1");
+    if (rule->max_distance != 0.0 && (!(rule->max_distance > 0.0) || !std::isfinite(rule->max_distance)))
+        return fail(ctx, ICPMI_ERR_ARG, "max_distance must be 0 (no gate) or finite and > 0");
+    if (ctx->comm || ctx->cb_allreduce) return fail(ctx, ICPMI_ERR_ARG, "a context with a communicator does not run plane-to-plane registrations");
+    *run = GateRun{};
+    run->g2 = rule->max_distance != 0.0 ? rule->max_distance * rule->max_distance : 1.7976931348623157e308;
+    run->pairs = 0;
+    run->gicp = true;
+    run->c = 1.0 - rule->epsilon;
+    run->kappa = 2.0 * rule->epsilon;
     return ICPMI_OK;
 }
 
@@ -2240,8 +2288,8 @@ int batch_run(icpmi_ctx *ctx, int32_t count, const std::function<int(icpmi_ctx *
 }
 
 // Every icpmi_align* entry point: the checks in their order -- the call's arguments, the context, then the entry's rule
-// (`entry`: which of icpmi_gate / icpmi_robust `rule` points to, and of icpmi_gate_info / icpmi_robust_info `info`, which
-// may be null; kRuleNone: neither) -- then the registration, on rows in device memory or on the caller's host arrays.
+// (`entry`: which of icpmi_gate / icpmi_robust / icpmi_gicp `rule` points to, and of icpmi_gate_info / icpmi_robust_info /
+// icpmi_gicp_info `info`, which may be null; kRuleNone: neither) -- then the registration, on rows in device memory or on the caller's host arrays.
 int align_entry(icpmi_ctx *ctx, bool on_device, const double *source_xyz, int64_t n_src, const double *target_xyz, int64_t n_tgt,
                 const icpmi_config *cfg, LoopRule entry, const void *rule, void *info, icpmi_result *result, double *error_history,
                 int32_t history_cap)
@@ -2252,12 +2300,14 @@ int align_entry(icpmi_ctx *ctx, bool on_device, const double *source_xyz, int64_
     GateRun run;
     if (entry == kRuleGate && (rc = validate_gate(ctx, (const icpmi_gate *)rule, &run))) return rc;
     if (entry == kRuleRobust && (rc = validate_robust(ctx, (const icpmi_robust *)rule, &run))) return rc;
+    if (entry == kRuleGicp && (rc = validate_gicp(ctx, (const icpmi_gicp *)rule, &run))) return rc;
     GateRun *gate = entry == kRuleNone ? nullptr : &run;
     rc = on_device ? align_device(ctx, source_xyz, n_src, target_xyz, n_tgt, cfg, result, error_history, history_cap, nullptr, nullptr, gate)
                    : align_staged(ctx, source_xyz, n_src, target_xyz, n_tgt, hipMemcpyHostToDevice, cfg, result, error_history, history_cap, gate);
     if (rc || !info) return rc;
     if (entry == kRuleGate) *(icpmi_gate_info *)info = icpmi_gate_info{run.pairs, n_src};
     if (entry == kRuleRobust) *(icpmi_robust_info *)info = icpmi_robust_info{run.weight_sum, run.pairs, n_src};
+    if (entry == kRuleGicp) *(icpmi_gicp_info *)info = icpmi_gicp_info{run.pairs, n_src};
     return ICPMI_OK;
 }
 
@@ -2339,6 +2389,20 @@ int icpmi_align_robust(icpmi_ctx *ctx, const double *source_xyz, int64_t n_src, 
                        double *error_history, int32_t history_cap)
 {
     return align_entry(ctx, false, source_xyz, n_src, target_xyz, n_tgt, cfg, kRuleRobust, rule, info, result, error_history, history_cap);
+}
+
+int icpmi_align_gicp_device(icpmi_ctx *ctx, const double *d_source_xyz, int64_t n_src, const double *d_target_xyz,
+                            int64_t n_tgt, const icpmi_config *cfg, const icpmi_gicp *rule, icpmi_result *result,
+                            icpmi_gicp_info *info, double *error_history, int32_t history_cap)
+{
+    return align_entry(ctx, true, d_source_xyz, n_src, d_target_xyz, n_tgt, cfg, kRuleGicp, rule, info, result, error_history, history_cap);
+}
+
+int icpmi_align_gicp(icpmi_ctx *ctx, const double *source_xyz, int64_t n_src, const double *target_xyz, int64_t n_tgt,
+                     const icpmi_config *cfg, const icpmi_gicp *rule, icpmi_result *result, icpmi_gicp_info *info,
+                     double *error_history, int32_t history_cap)
+{
+    return align_entry(ctx, false, source_xyz, n_src, target_xyz, n_tgt, cfg, kRuleGicp, rule, info, result, error_history, history_cap);
 }
 
 int icpmi_align_robust_batch(icpmi_ctx *ctx, int32_t count, const double *const *sources_xyz, const int64_t *n_src,

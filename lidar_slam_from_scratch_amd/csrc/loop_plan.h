@@ -84,7 +84,7 @@ inline bool coarse_half_units(int cu_count, int n, int splits)
 // ---- the facts a call's form is decided from ---------------------------------------------------------------------------
 // (Everything the loop's conditions read.  m, normal_k and profile select no kernel today: the stages read them for sizes,
 // the normals and the statistics, and a form that comes to depend on them finds them here.)
-enum LoopRule { kRuleNone = 0, kRuleGate = 1, kRuleRobust = 2 }; // plain / icp_gated.h / icp_robust.h kernels
+enum LoopRule { kRuleNone = 0, kRuleGate = 1, kRuleRobust = 2, kRuleGicp = 3 }; // plain / icp_gated.h / icp_robust.h / icp_gicp.h kernels
 
 struct LoopFacts {
     int n = 0, m = 0;       // rows of the source (this rank's) and of the target
@@ -146,7 +146,8 @@ inline LoopPlan make_loop_plan(const LoopFacts &f)
     p.fused = f.nn_engine == ICPMI_SEARCH_MFMA_BF16 && f.rule == kRuleNone;
     // the sizes of the small-cloud kernel, whatever runs at them
     const bool small_sizes = !p.sharded && n <= kSmallMaxQueries && f.nn_splits <= f.sw_small_max_splits;
-    p.small = small_sizes && n > 0 && small_target(f);
+    // (plane-to-plane rows have no small-cloud form: the gated general path at every size, icp_gicp.h)
+    p.small = small_sizes && n > 0 && small_target(f) && f.rule != kRuleGicp;
     p.resolve_waves = resolve_waves(n);
     p.rblocks = p.small ? (n + kSmallQ - 1) / kSmallQ : (p.fused ? resolve_blocks(n) : reduce_blocks(f.cu_count, n));
     // very many partial rows (a resolve workgroup leaves one per 64 queries) are first added in groups of kSumGroup by a
@@ -156,6 +157,9 @@ inline LoopPlan make_loop_plan(const LoopFacts &f)
     p.fin_blocks = p.sum_tree ? p.rblocks2 : p.rblocks;
     // (k_sum_groups adds kNumSums columns, one short of a robust row's; a robust general pass leaves reduce_blocks() rows)
     if (f.rule == kRuleRobust && p.sum_tree && !p.small) p.error = "internal: a robust pass of %d partial rows";
+    // (k_reduce_gicp is the only kernel that forms plane-to-plane sums: a plan that would hand such a pass to the small-cloud
+    // kernel, to a fused resolve or to k_sum_groups is refused here, not launched with another rule's kernel or with none)
+    if (f.rule == kRuleGicp && (p.small || p.fused || p.sum_tree)) p.error = "internal: a plane-to-plane pass of %d partial rows has only the general form";
 
     // Pruned engine: the source is put in Morton order once (a rigid motion keeps neighbours
     // together), so that every block of kCoarseQueries consecutive rows of `cur` is a compact

@@ -65,12 +65,15 @@ def run_odometry(frames, align, max_iterations=50, tolerance=1e-6, min_points=10
     return track
 
 
-def gpu_align(ctx, *, robust=None):
+def gpu_align(ctx, *, robust=None, gicp=None):
     """Adapter: capi.Context -> the `align` callable above.  robust: a capi.Robust, or (kind, scale[, max_distance]) --
     the registrations run under those row weights (icpmi_align_robust; None: none) and their results carry `weight_sum`
     and `pairs`.  final_error is then the WEIGHTED RMS, which reads lower than the plain one against the caller's
-    `> 1.0`."""
+    `> 1.0`.  gicp: a capi.Gicp, or (epsilon[, max_distance]) -- the registrations minimise the plane-to-plane cost
+    (icpmi_align_gicp; None: point-to-plane) and their results carry `pairs`; not together with `robust` (ValueError)."""
     from . import capi
+    if robust is not None and gicp is not None:
+        raise ValueError("robust= and gicp= exclude each other: the plane-to-plane rows carry no robust weights")
 
     class _R:
         pass
@@ -78,7 +81,10 @@ def gpu_align(ctx, *, robust=None):
     def align(source, target, max_iterations, tolerance):
         cfg = capi.Context.make_config(max_iterations=max_iterations, tolerance=tolerance)
         r = _R()
-        if robust is None:
+        if gicp is not None:
+            res, _hist, info = ctx.align_gicp(source, target, cfg, gicp)
+            r.pairs = int(info.pairs)
+        elif robust is None:
             res, _hist = ctx.align(source, target, cfg)
         else:
             res, _hist, info = ctx.align_robust(source, target, cfg, robust)

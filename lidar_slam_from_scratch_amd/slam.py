@@ -53,7 +53,7 @@ def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, po
              align=None, loop_backend=None, pose_graph=None, global_map=None, grid=None, map_voxel=1.0,
              loop_on_device=False, raycast=False, counts=False, live=False, loop_yaw_guess=False, loop_gate=None,
              ground=None, odom_robust=None, loop_robust=None, odom_local_map=None, loop_edge_loss=None,
-             edge_information=None, information_floor=(1.0, 10.0), closure_gate=None, deskew=None, deskew_voxel=0.5):
+             edge_information=None, information_floor=(1.0, 10.0), closure_gate=None, deskew=None, deskew_voxel=0.5, odom_gicp=None):
     """frames: sequence of N x 3 fp64 clouds (already downsampled).  Returns a SlamRun.  global_map: an object with
     add_frame, recent_clouds and finish (None: no map is built); grid: its occupancy grid config (None: defaults).
     loop_on_device: the detector is loop_closure.StoreLoopClosureDetector over global_map (a global_map.GlobalMap),
@@ -72,6 +72,9 @@ def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, po
     odom_robust: (kind, scale) or (kind, scale, max_distance), kind one of capi.ROBUST_* (None: none); the default
     `align` registers under those row weights (odometry.gpu_align(ctx, robust=...); not in the reference node).  With an
     `align` of the caller's it is refused.
+    odom_gicp: (epsilon,) or (epsilon, max_distance) (None: none); the default `align` minimises the plane-to-plane cost
+    (odometry.gpu_align(ctx, gicp=...), icpmi_align_gicp; not in the reference node).  Refused with an `align` of the
+    caller's, with odom_robust and with odom_local_map (whose registrations have no plane-to-plane form).
     loop_robust: (kind, scale) (None: none); the detector's verifications run under those row weights
     (LoopClosureConfig.robust_kind / robust_scale), behind loop_gate if that is given too.
     odom_local_map: a local_map.LocalMapConfig (None: frame-to-frame, as the reference node); each odometry factor's
@@ -112,6 +115,9 @@ def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, po
         raise ValueError("loop_backend and loop_on_device=True both choose the detector")
     if align is not None and odom_robust is not None:
         raise ValueError("odom_robust configures the default align; pass a robust align of your own instead")
+    if odom_gicp is not None and (align is not None or odom_robust is not None or odom_local_map is not None):
+        raise ValueError("odom_gicp configures the default align; it does not combine with an align of the caller's, "
+                         "odom_robust or odom_local_map")
     if edge_information is not None and (align is not None or loop_backend is not None):
         raise ValueError("edge_information reads the library's own normal matrices; it does not combine with an align or "
                          "a loop_backend of the caller's")
@@ -128,7 +134,7 @@ def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, po
         run.odom_weight_sums = []                                    # under odom_robust: per registration
     elif align is None:
         from .odometry import gpu_align
-        align = gpu_align(ctx, robust=odom_robust)
+        align = gpu_align(ctx, robust=odom_robust, gicp=odom_gicp)
     if loop_backend is None and not loop_on_device:
         loop_backend = lc.GpuBackend(ctx)
     if pose_graph is None:

@@ -399,6 +399,39 @@ def _robust_batch(ctx, env):
     return _batch_out(ctx, ctx.align_robust_batch([env.I[s] for s, _ in BATCH[:2]], [env.I[t] for _, t in BATCH[:2]], cfg, rule))
 
 
+# Plane-to-plane registrations (icp_gicp.h): the source's search structure and normals are built in front of the target's,
+# in the buffers every other call's target uses -- what a used context could leak into, and out of.  (No `reg`: their
+# plan is one form at every size, kRuleGicp, which tests/test_gicp_header.py holds; the paths' table above is the three
+# older rules'.)
+GICP_RULE = (1e-3, GATE_RC)
+
+
+def _make_gicp(name, form, src, tgt, iters):
+    @op(name, max(inputs()[src].shape[0], inputs()[tgt].shape[0]), "registration", (form, "last_normal_matrix"))
+    def run(ctx, env):
+        s, t = env.I[src], env.I[tgt]
+        cfg = _capi().Context.make_config(**_cfg_kw(iters))
+        if form == "align_gicp":
+            res, hist, info = ctx.align_gicp(s, t, cfg, GICP_RULE)
+        else:
+            ds, dt = env.dev(src), env.dev(tgt)
+            res, hist, info = ctx.align_gicp_device(ds.data_ptr(), ds.shape[0], dt.data_ptr(), dt.shape[0], cfg, GICP_RULE)
+        return _reg_out(ctx, s.shape[0], res, hist, [info], ruled=True)
+
+    @check(name)
+    def _check(env, out, orc):
+        import gicp_ref
+        kw = _cfg_kw(iters)
+        ref = gicp_ref.gicp_icp(env.I[src], env.I[tgt], GICP_RULE[0], GICP_RULE[1], kw["max_iterations"], kw.get("tolerance", 1e-6),
+                                kw.get("min_error", 1e-9), orc=orc)
+        assert out.raw["extra"][0].pairs == ref.pairs, (name, out.raw["extra"][0].pairs, ref.pairs)
+        check_against(out.raw["res"], out.raw["hist"], ref.transformation, ref.converged, ref.num_iterations, ref.error_history)
+
+
+_make_gicp("gicp_1001", "align_gicp", "rc_s1001", "rc_t1500", 3)
+_make_gicp("gicp_5000", "align_gicp_device", "u_s5000a", "u_t16385", 3)
+
+
 # ---- primitives
 def _nearest(name, tgt, qry):
     @op(name, max(inputs()[tgt].shape[0], inputs()[qry].shape[0]), "primitive", ("nearest_batch",))
