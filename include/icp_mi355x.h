@@ -907,7 +907,8 @@ int icpmi_map_counts(icpmi_map *map, uint16_t *hits, uint16_t *misses, int8_t *p
  *                       icpmi_map_counts, info->counts.width * height cells each.  One wait.
  *   icpmi_map_live_clear   forgets the cast frames: the next update casts every used frame again.
  * Neither call touches icpmi_map_counts' arrays, icpmi_map_raster's raster or the context's cell set, and neither
- * icpmi_map_raycast_counts nor icpmi_map_raycast touches the live counts.
+ * icpmi_map_raycast_counts nor icpmi_map_raycast touches the live counts.  icpmi_map_world_static and
+ * icpmi_map_finish_static (below) do: each begins with exactly this update.
  * info: counts is exactly what icpmi_map_raycast_counts would report; frames_cast the frames this call cast (0 when
  * nothing was new); rebuilt 1 when remembered frames were discarded and cast again; moved 1 when the plane was
  * reallocated and its words copied in this call; plane_* the plane's box in cells (0 x 0: no plane). */
@@ -1035,6 +1036,67 @@ int icpmi_stream_set_deskew(icpmi_ctx *ctx, const icpmi_deskew_config *cfg);
  * frame out of range, ICPMI_ERR_ARG. */
 int icpmi_map_set_ground(icpmi_map *map, const icpmi_ground_config *cfg);
 int icpmi_map_ground_labels(icpmi_map *map, int64_t frame, uint8_t *labels, int64_t cap, int64_t *n_out);
+
+/* The static map: icpmi_map_world and the published map of icpmi_map_finish without the rows whose cells the counts
+ * outvote (csrc/static_map.h; not in the reference, whose map keeps every return of everything that moved
+ * while the node drove).  For the used frames i < used = min(frames, n_poses) and the caller's grid, let hits[c],
+ * misses[c] and probability[c] be exactly what icpmi_map_raycast_counts(map, poses, n_poses, grid) defines.
+ *   A row of used frame i VOTES iff it marks a cell c under the rules the counts use: grid_cell_key of its world
+ *   point with frame i's translation as the sensor and, while icpmi_map_set_ground is on, additionally its label is
+ *   OBSTACLE and the band is open.  With n = hits[c] + misses[c] a row's label is
+ *     0  kept, does not vote: ground rows, rows out of band or ring, non-finite rows, an unrepresentable quotient
+ *     1  kept, votes
+ *     2  dropped: the row votes, n >= rule.min_observations and probability[c] < rule.min_probability
+ *   probability[c] = (200 hits[c] + n) / (2 n) in integer division.  A lookup that finds n == 0, or a cell outside
+ *   the plane's box, keeps the row with label 1 (it cannot happen for a voting row).  min_probability == 0 drops
+ *   nothing.  All integer: no dependence on the order of frames, rows or threads.
+ * The vote is two-dimensional: which rows vote is decided by the grid's band on world z, or by the ground labels.  With
+ * the default band (0.3 .. 2.0) and the sensor as the origin of z, a car whose roof lies below z = 0.3 never votes and is
+ * never dropped: give a band that holds what may move, or set a ground config, under which every OBSTACLE row votes.
+ * rule: 0 <= min_probability <= 100, min_observations >= 1, reserved == 0; anything else is ICPMI_ERR_ARG, a NULL rule
+ * ICPMI_ERR_NULL.
+ * Where the counts come from: both calls first bring the handle's live counts up to date, by the host decision and the
+ * kernels of icpmi_map_live_update(map, poses, n_poses, grid) and with its effect on the live state (incremental,
+ * rebuild or nothing new; info->live reports which), and label against the live plane: a node that publishes a static
+ * cloud every few frames casts only the new frames.  Every ICPMI_ERR_NULL and ICPMI_ERR_ARG case of
+ * icpmi_map_live_update applies unchanged, the ICPMI_RAYCOUNT_MAX_FRAMES cap included; those and the rule's are decided
+ * before any device work and leave *info unwritten and the labels and the live state as they were.  icpmi_map_counts'
+ * arrays, icpmi_map_raster's raster and the context's cell set are never touched.
+ *   icpmi_map_world_static   icpmi_map_world restricted to the kept rows: the world points of the rows of frames
+ *                       [first, used) whose label is not 2, frame then row order (a stable compaction), each bit for bit
+ *                       the point icpmi_map_world writes for that row.  *n_out their number; out_xyz may be NULL: only
+ *                       *n_out is set, which still needs the labels and so the device.  cap < *n_out with out_xyz given
+ *                       is ICPMI_ERR_CAPACITY.  The labels are formed for all used frames [0, used) whatever first is.
+ *                       Waits for the device for the counts (icpmi_map_live_update's wait), for the labels' totals, and
+ *                       for the points.
+ *   icpmi_map_finish_static  icpmi_map_finish's published-map half over the kept rows of all used frames:
+ *                       voxel_downsample(kept world rows, voxel_size) into map_out (map_cap rows), *n_map its rows, under
+ *                       the rules and errors of icpmi_map_finish; voxel_size <= 0 or map_out NULL skips the filter (the
+ *                       labels and *info are formed all the same).  The context's cell set is not touched.
+ *   icpmi_map_static_labels  one frame's label bytes as the last call of either of the two that got as far as the
+ *                       labels left them (a call that then fails with ICPMI_ERR_CAPACITY has), in a buffer the handle
+ *                       owns: *n_out = the frame's rows; labels may be NULL (the size alone); a cap below the rows is
+ *                       ICPMI_ERR_CAPACITY; before any such call, or for a frame that call did not use, ICPMI_ERR_ARG.
+ * info (may be NULL): rows = the used frames' rows; voting those with label 1 or 2; dropped those with label 2; kept =
+ * rows - dropped, all over the used frames [0, used) whatever first is; live = what icpmi_map_live_update reports. */
+#define ICPMI_STATIC_MIN_PROBABILITY_DEFAULT 50
+#define ICPMI_STATIC_MIN_OBSERVATIONS_DEFAULT 3
+typedef struct {
+    int32_t min_probability;    /* a voting row is dropped if its cell's probability is below this */
+    int32_t min_observations;   /* ... and the cell was observed (hit or seen through) by at least this many frames */
+    int64_t reserved;           /* 0 */
+} icpmi_static_rule;
+typedef struct {
+    int64_t rows, voting, dropped, kept;
+    icpmi_live_info live;
+} icpmi_static_info;
+int icpmi_map_world_static(icpmi_map *map, const double *poses, int64_t n_poses, const icpmi_grid_config *grid,
+                           const icpmi_static_rule *rule, int64_t first, double *out_xyz, int64_t cap, int64_t *n_out,
+                           icpmi_static_info *info);
+int icpmi_map_finish_static(icpmi_map *map, const double *poses, int64_t n_poses, const icpmi_grid_config *grid,
+                            const icpmi_static_rule *rule, double voxel_size, double *map_out, int64_t map_cap,
+                            int64_t *n_map, icpmi_static_info *info);
+int icpmi_map_static_labels(icpmi_map *map, int64_t frame, uint8_t *labels, int64_t cap, int64_t *n_out);
 
 /* Loop-closure detection over a global map's kept scans (slam::LoopClosureDetector, core/loop_closure.hpp:41-148),
  * with its database on the device: an entry is a store frame with a label (the node's frame_idx).  Each entry's

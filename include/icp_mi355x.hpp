@@ -1375,6 +1375,20 @@ inline GroundSegmentation ground_segment(const PointCloud &scan, const GroundCon
     return ground_segment(default_context(), scan, config);
 }
 
+// The rule of the static map (icpmi_static_rule; not in the reference): a voting row is dropped if its cell was
+// observed by at least min_observations frames and its occupancy probability is below min_probability (0: nothing).
+struct StaticRule {
+    int32_t min_probability = ICPMI_STATIC_MIN_PROBABILITY_DEFAULT;
+    int32_t min_observations = ICPMI_STATIC_MIN_OBSERVATIONS_DEFAULT;
+};
+
+// What GlobalMap::world_static and finish_static report (icpmi_static_info): over the used frames, their rows, those
+// that vote, those dropped and rows - dropped; and the live update at the head of the call.
+struct StaticInfo {
+    int64_t rows = 0, voting = 0, dropped = 0, kept = 0;
+    LiveUpdate live;
+};
+
 // The node's kept scans (downsampled_clouds_, slam_node.cpp:71,123) in device memory, and what it builds from them
 // with the optimised poses: rebuild_recent_clouds (:187-194), build_final_global_map (:196-209) with
 // rebuild_occupancy_grid (:223-229), and the map publish_global_map sends once complete (:235-238).  finish() rebuilds
@@ -1536,6 +1550,56 @@ public:
         if (n) check(icpmi_map_ground_labels(m_, static_cast<int64_t>(frame), out.data(), n, &n));
         return out;
     }
+    // The static map (icpmi_map_world_static): global_map() / recent_clouds()'s points without the rows whose cells the
+    // counts outvote, frames [first, used), frame then row order, each bit for bit the point global_map() holds for that
+    // row.  The live counts are brought up to date first, as by live_update(poses, grid).  The default grid's band holds
+    // no car roof when the sensor is the origin of z: see icp_mi355x.h.
+    PointCloud world_static(const std::vector<Transformation> &poses, const OccupancyGridConfig &grid, const StaticRule &rule = StaticRule(),
+                            std::size_t first = 0, StaticInfo *info = nullptr)
+    {
+        const std::vector<double> P = flatten(poses);
+        const icpmi_grid_config g = detail::to_c(grid);
+        const icpmi_static_rule r{rule.min_probability, rule.min_observations, 0};
+        icpmi_static_info si{};
+        int64_t n = 0;
+        std::size_t cap = 0; // one call, so that info->live is that call's update
+        for (std::size_t i = first; i < rows_.size() && i < poses.size(); ++i) cap += rows_[i];
+        std::vector<double> out(3 * std::max<std::size_t>(cap, 1));
+        check(icpmi_map_world_static(m_, P.data(), static_cast<int64_t>(poses.size()), &g, &r, static_cast<int64_t>(first), out.data(),
+                                     static_cast<int64_t>(cap), &n, &si));
+        out.resize(3 * static_cast<std::size_t>(n));
+        if (info) *info = from_c(si);
+        return PointCloud(std::move(out));
+    }
+    // finish()'s published map over the kept rows of all used frames (icpmi_map_finish_static).  The context's cell set
+    // is not touched.
+    PointCloud finish_static(const std::vector<Transformation> &poses, const OccupancyGridConfig &grid, const StaticRule &rule,
+                             double voxel_size, StaticInfo *info = nullptr)
+    {
+        const std::vector<double> P = flatten(poses);
+        const icpmi_grid_config g = detail::to_c(grid);
+        const icpmi_static_rule r{rule.min_probability, rule.min_observations, 0};
+        std::size_t rows = 0;
+        for (std::size_t i = 0; i < rows_.size() && i < poses.size(); ++i) rows += rows_[i];
+        std::vector<double> out(3 * std::max<std::size_t>(rows, 1));
+        icpmi_static_info si{};
+        int64_t n = 0;
+        check(icpmi_map_finish_static(m_, P.data(), static_cast<int64_t>(poses.size()), &g, &r, voxel_size, out.data(),
+                                      static_cast<int64_t>(rows), &n, &si));
+        out.resize(3 * static_cast<std::size_t>(n));
+        if (info) *info = from_c(si);
+        return PointCloud(std::move(out));
+    }
+    // one frame's labels (0 kept and does not vote, 1 kept and votes, 2 dropped) as the last world_static or
+    // finish_static left them
+    std::vector<uint8_t> static_labels(std::size_t frame)
+    {
+        int64_t n = 0;
+        check(icpmi_map_static_labels(m_, static_cast<int64_t>(frame), nullptr, 0, &n));
+        std::vector<uint8_t> out(static_cast<std::size_t>(n));
+        if (n) check(icpmi_map_static_labels(m_, static_cast<int64_t>(frame), out.data(), n, &n));
+        return out;
+    }
     icpmi_map *get() const { return m_; }
     Context *context() const { return ctx_; }
 
@@ -1549,6 +1613,16 @@ private:
         int64_t n = 0;
         check(icpmi_map_size(m_, nullptr, &n));
         return n;
+    }
+    static StaticInfo from_c(const icpmi_static_info &si)
+    {
+        StaticInfo out;
+        out.rows = si.rows, out.voting = si.voting, out.dropped = si.dropped, out.kept = si.kept;
+        out.live.frames_cast = si.live.frames_cast;
+        out.live.rebuilt = si.live.rebuilt != 0, out.live.moved = si.live.moved != 0;
+        out.live.plane_x0 = si.live.plane_x0, out.live.plane_y0 = si.live.plane_y0;
+        out.live.plane_w = si.live.plane_w, out.live.plane_h = si.live.plane_h;
+        return out;
     }
     static std::vector<double> flatten(const std::vector<Transformation> &poses)
     {

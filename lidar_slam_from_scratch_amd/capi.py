@@ -54,6 +54,7 @@ EXPORTS = [
     "icpmi_information_from_icp", "icpmi_last_normal_matrix", "icpmi_loop_set_information", "icpmi_loop_last_information",
     "icpmi_deskew_config_default", "icpmi_deskew", "icpmi_deskew_device", "icpmi_deskew_twist", "icpmi_stream_set_deskew",
     "icpmi_align_gicp", "icpmi_align_gicp_device",
+    "icpmi_map_world_static", "icpmi_map_finish_static", "icpmi_map_static_labels",
 ]
 
 
@@ -216,6 +217,32 @@ class LiveInfo(C.Structure):
     """icpmi_live_info"""
     _fields_ = [("counts", CountsInfo), ("frames_cast", C.c_int64), ("rebuilt", C.c_int32), ("moved", C.c_int32),
                 ("plane_x0", C.c_int32), ("plane_y0", C.c_int32), ("plane_w", C.c_int32), ("plane_h", C.c_int32)]
+
+
+STATIC_MIN_PROBABILITY_DEFAULT, STATIC_MIN_OBSERVATIONS_DEFAULT = 50, 3   # ICPMI_STATIC_*_DEFAULT
+STATIC_QUIET, STATIC_VOTES, STATIC_DROPPED = 0, 1, 2      # a row's label: kept and does not vote, kept and votes, dropped
+
+
+class StaticRule(C.Structure):
+    """icpmi_static_rule: a voting row is dropped if its cell was observed by at least min_observations frames and its
+    probability is below min_probability (0 drops nothing)"""
+    _fields_ = [("min_probability", C.c_int32), ("min_observations", C.c_int32), ("reserved", C.c_int64)]
+
+    def __init__(self, min_probability=STATIC_MIN_PROBABILITY_DEFAULT, min_observations=STATIC_MIN_OBSERVATIONS_DEFAULT, reserved=0):
+        super().__init__(int(min_probability), int(min_observations), int(reserved))
+
+
+class StaticInfo(C.Structure):
+    """icpmi_static_info: over the used frames, their rows, those that vote, those dropped and rows - dropped; and what
+    the live update at the head of the call reports"""
+    _fields_ = [("rows", C.c_int64), ("voting", C.c_int64), ("dropped", C.c_int64), ("kept", C.c_int64), ("live", LiveInfo)]
+
+
+def as_static_rule(rule):
+    """a StaticRule, or (min_probability, min_observations) -> StaticRule"""
+    if isinstance(rule, StaticRule):
+        return rule
+    return StaticRule(int(rule[0]), int(rule[1]))
 
 
 GROUND_OBSTACLE, GROUND_GROUND, GROUND_IGNORED = 0, 1, 2   # ICPMI_GROUND_*
@@ -465,6 +492,11 @@ def load_library(path=None):
     L.icpmi_ground_segment_device.argtypes = [vp, vp, C.c_int64, C.POINTER(GroundConfig), u8p, dp, dp, C.POINTER(GroundInfo)]
     L.icpmi_map_set_ground.argtypes = [vp, C.POINTER(GroundConfig)]
     L.icpmi_map_ground_labels.argtypes = [vp, C.c_int64, u8p, C.c_int64, i64p]
+    L.icpmi_map_world_static.argtypes = [vp, dp, C.c_int64, C.POINTER(GridConfig), C.POINTER(StaticRule), C.c_int64, dp, C.c_int64,
+                                         i64p, C.POINTER(StaticInfo)]
+    L.icpmi_map_finish_static.argtypes = [vp, dp, C.c_int64, C.POINTER(GridConfig), C.POINTER(StaticRule), C.c_double, dp, C.c_int64,
+                                          i64p, C.POINTER(StaticInfo)]
+    L.icpmi_map_static_labels.argtypes = [vp, C.c_int64, u8p, C.c_int64, i64p]
     L.icpmi_deskew_config_default.argtypes = [C.POINTER(DeskewConfig)]
     L.icpmi_deskew_config_default.restype = None
     L.icpmi_deskew.argtypes = [vp, dp, dp, C.c_int64, C.POINTER(DeskewConfig), dp]

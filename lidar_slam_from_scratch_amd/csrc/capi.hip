@@ -51,6 +51,7 @@
 #include "live_plane.h"
 #include "live_counts.h"
 #include "ground.h"
+#include "static_map.h"
 #include "deskew.h"
 #include "loop_store.h"
 #include "pose_graph.h"
@@ -4953,6 +4954,9 @@ struct icpmi_map {
     int64_t ground_frames = 0;           // frames [0, ground_frames) are labelled
     std::vector<int32_t> ground_hits;    // per labelled frame its OBSTACLE rows
     DevBuf d_labels, d_ground_tab;       // one byte per store row; a labelling launch's frame table and counts
+    // icpmi_map_world_static / icpmi_map_finish_static (static_map.h): the labels against the live counts
+    DevBuf d_static_labels, d_static_tab; // one byte per store row; per tile its kept rows, their exclusive sums, StaticTotals
+    int64_t static_frames = -1;          // frames [0, static_frames) hold the labels of the last call that formed them (-1: none)
 };
 
 namespace {
@@ -5024,10 +5028,9 @@ int map_check_poses(icpmi_map *m, const double *poses, int64_t n_poses, int64_t 
     return map_check_finite(m, poses, 0, *last);
 }
 
-// Queue, for frames [first, last) (first < last): the tile table's new entries, the frames' poses, and k_map_world
-// into world (rows x 3) and / or keys (rows), row 0 being frame first's first row.
-int map_queue_world(icpmi_map *m, const double *poses, int64_t first, int64_t last, double *world, unsigned long long *keys,
-                    const icpmi_grid_config *grid)
+// Queue, for frames [first, last) (first < last): the tile table's new entries and the frames' poses (into d_poses,
+// frame first's at its start).
+int map_queue_tables(icpmi_map *m, const double *poses, int64_t first, int64_t last)
 {
     icpmi_ctx *ctx = m->ctx;
     hipStream_t s = ctx->stream;
@@ -5045,6 +5048,18 @@ int map_queue_world(icpmi_map *m, const double *poses, int64_t first, int64_t la
     const size_t pose_bytes = sizeof(double) * 16 * (size_t)(last - first);
     if ((rc = reserve(ctx, m->d_poses, pose_bytes))) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(m->d_poses.p, poses + 16 * first, pose_bytes, hipMemcpyHostToDevice, s));
+    return ICPMI_OK;
+}
+
+// Queue, for frames [first, last) (first < last): map_queue_tables, and k_map_world into world (rows x 3) and / or keys
+// (rows), row 0 being frame first's first row.
+int map_queue_world(icpmi_map *m, const double *poses, int64_t first, int64_t last, double *world, unsigned long long *keys,
+                    const icpmi_grid_config *grid)
+{
+    icpmi_ctx *ctx = m->ctx;
+    hipStream_t s = ctx->stream;
+    int rc;
+    if ((rc = map_queue_tables(m, poses, first, last))) return rc;
     const int64_t t0 = m->tile0[first], nt = m->tile0[last] - t0;
     GridParams g{0.0, 0.0, 1.0, 0.0, 0.0, 0.0};
     if (grid) g = GridParams{0.0, 0.0, grid->resolution, grid->height_min, grid->height_max, grid->max_range};
@@ -5206,7 +5221,8 @@ void icpmi_map_destroy(icpmi_map *m)
     (void)hipStreamSynchronize(m->ctx->stream);
     for (DevBuf *b : {&m->d_rows, &m->d_tiles, &m->d_poses, &m->d_world, &m->d_ray_frames, &m->d_ray_planes, &m->d_raster,
                       &m->d_raster_next, &m->d_count_plane, &m->d_count_scratch, &m->d_counts, &m->d_counts_next, &m->live.d_plane,
-                      &m->live.d_bounds, &m->live.d_windows, &m->live.d_out, &m->d_labels, &m->d_ground_tab})
+                      &m->live.d_bounds, &m->live.d_windows, &m->live.d_out, &m->d_labels, &m->d_ground_tab, &m->d_static_labels,
+                      &m->d_static_tab})
         release(*b);
     delete m;
 }
@@ -5794,6 +5810,189 @@ int icpmi_map_ground_labels(icpmi_map *m, int64_t frame, uint8_t *labels, int64_
     if ((rc = map_ground_ready(m))) return rc;
     if (rows == 0) return ICPMI_OK;
     HIP_TRY(ctx, hipMemcpyAsync(labels, (const uint8_t *)m->d_labels.p + m->row0[frame], (size_t)rows, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return ICPMI_OK;
+}
+
+} // extern "C"
+
+// ---- the static map: the point products without the rows the counts outvote (static_map.h) ----
+
+namespace {
+
+static_assert(sizeof(icpmi_static_rule) == 16 && sizeof(icpmi_static_info) == 32 + sizeof(icpmi_live_info), "the header's layout");
+
+struct StaticRun {
+    int64_t t_first = 0, t_end = 0; // the tiles of frames [first, used)
+    unsigned base = 0;              // the kept rows before frame first
+    int64_t n = 0;                  // the kept rows of frames [first, used)
+    icpmi_static_info info{};
+};
+
+int static_check_rule(icpmi_ctx *ctx, const icpmi_static_rule *rule)
+{
+    if (!rule) return fail(ctx, ICPMI_ERR_NULL, "rule is NULL");
+    if (rule->min_probability < 0 || rule->min_probability > 100)
+        return fail(ctx, ICPMI_ERR_ARG, "rule: min_probability must lie in [0, 100]");
+    if (rule->min_observations < 1) return fail(ctx, ICPMI_ERR_ARG, "rule: min_observations must be at least 1");
+    if (rule->reserved != 0) return fail(ctx, ICPMI_ERR_ARG, "rule: reserved must be 0");
+    return ICPMI_OK;
+}
+
+// The live counts brought up to date (icpmi_map_live_update itself), then the labels of every used row against the
+// live plane, the tiles' kept rows and their exclusive sums, and one wait for the totals.  d_poses then holds the used
+// frames' poses from frame 0 on, for static_queue_world.
+int static_labels_run(icpmi_map *m, const double *poses, int64_t n_poses, const icpmi_grid_config *grid, const icpmi_static_rule *rule,
+                      int64_t first, StaticRun *run)
+{
+    icpmi_ctx *ctx = m->ctx;
+    hipStream_t s = ctx->stream;
+    int rc;
+    icpmi_live_info live{};
+    if ((rc = icpmi_map_live_update(m, poses, n_poses, grid, &live))) return rc;
+    const LiveCounts &L = m->live;
+    const int64_t used = L.n_cast, rows = m->row0[used];
+    first = std::min(first, used);
+    run->t_first = m->tile0[first], run->t_end = m->tile0[used];
+    run->info = icpmi_static_info{rows, 0, 0, rows, live};
+    m->static_frames = -1;          // until this call's labels stand
+    if (rows == 0) {
+        m->static_frames = used;
+        return ICPMI_OK;
+    }
+    Range range("icpmi:map_static_labels");
+    const size_t T = (size_t)run->t_end;
+    // kept (T + 1 words, the last one 0) | their exclusive sums (T + 1 words: the last one is the total) | StaticTotals
+    const size_t words = 2 * (T + 1);
+    if ((rc = reserve(ctx, m->d_static_labels, (size_t)rows))) return rc;
+    if ((rc = reserve(ctx, m->d_static_tab, sizeof(unsigned) * words + sizeof(StaticTotals)))) return rc;
+    unsigned *kept = (unsigned *)m->d_static_tab.p, *offs = kept + (T + 1);
+    StaticTotals *totals_d = (StaticTotals *)(kept + words);
+    size_t scan_bytes = 0;
+    HIP_TRY(ctx, exclusive_sum_u32(nullptr, &scan_bytes, kept, offs, (unsigned)(T + 1), s));
+    if ((rc = reserve(ctx, ctx->sort_tmp, scan_bytes))) return rc;
+    HIP_TRY(ctx, hipMemsetAsync(kept + T, 0, sizeof(unsigned), s));
+    HIP_TRY(ctx, hipMemsetAsync(totals_d, 0, sizeof(StaticTotals), s));
+    if ((rc = map_queue_tables(m, poses, 0, used))) return rc;
+    GridParams g{0.0, 0.0, grid->resolution, grid->height_min, grid->height_max, grid->max_range};
+    if (m->ground_on) // as map_queue_world: the band is open, the rows that are not OBSTACLE mark nothing
+        g.height_min = -std::numeric_limits<double>::max(), g.height_max = std::numeric_limits<double>::max();
+    const StaticPlane pl{L.box.w > 0 ? (const unsigned *)L.d_plane.p : nullptr, (long long)L.box.x0, (long long)L.box.y0,
+                         (long long)L.box.w, (long long)L.box.h};
+    hipLaunchKernelGGL(k_static_label, dim3((unsigned)T), dim3(256), 0, s, (const double *)m->d_rows.p, (const MapTile *)m->d_tiles.p,
+                       (const double *)m->d_poses.p, m->ground_on ? (const uint8_t *)m->d_labels.p : (const uint8_t *)nullptr, pl, g,
+                       StaticRuleK{rule->min_probability, rule->min_observations}, (uint8_t *)m->d_static_labels.p, kept, totals_d);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, exclusive_sum_u32(ctx->sort_tmp.p, &scan_bytes, kept, offs, (unsigned)(T + 1), s));
+    unsigned ends[2] = {0, 0};
+    StaticTotals totals{0, 0};
+    HIP_TRY(ctx, hipMemcpyAsync(&ends[0], offs + run->t_first, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipMemcpyAsync(&ends[1], offs + T, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipMemcpyAsync(&totals, totals_d, sizeof(StaticTotals), hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s)); // the labels' wait: how many rows are kept
+    HIP_TRY(ctx, hipGetLastError());
+    if ((int64_t)ends[1] != rows - (int64_t)totals.dropped || ends[0] > ends[1])
+        return fail(ctx, ICPMI_ERR_HIP, "static map: the tiles' kept rows (%u) and the dropped rows (%llu) do not add up to %lld",
+                    ends[1], totals.dropped, (long long)rows);
+    m->static_frames = used;
+    run->base = ends[0], run->n = (int64_t)(ends[1] - ends[0]);
+    run->info.voting = (int64_t)totals.voting, run->info.dropped = (int64_t)totals.dropped;
+    run->info.kept = rows - run->info.dropped;
+    return ICPMI_OK;
+}
+
+// Queue k_static_world for the tiles of frames [first, used) into world (run.n rows, run.n > 0), behind static_labels_run.
+int static_queue_world(icpmi_map *m, const StaticRun &run, double *world)
+{
+    icpmi_ctx *ctx = m->ctx;
+    const size_t T = (size_t)run.t_end;
+    const unsigned *offs = (const unsigned *)m->d_static_tab.p + (T + 1);
+    hipLaunchKernelGGL(k_static_world, dim3((unsigned)(run.t_end - run.t_first)), dim3(256), 0, ctx->stream, (const double *)m->d_rows.p,
+                       (const MapTile *)m->d_tiles.p + run.t_first, (const double *)m->d_poses.p,
+                       (const uint8_t *)m->d_static_labels.p, offs + run.t_first, run.base, world);
+    HIP_TRY(ctx, hipGetLastError());
+    return ICPMI_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int icpmi_map_world_static(icpmi_map *m, const double *poses, int64_t n_poses, const icpmi_grid_config *grid,
+                           const icpmi_static_rule *rule, int64_t first, double *out_xyz, int64_t cap, int64_t *n_out,
+                           icpmi_static_info *info)
+{
+    if (!m) return ICPMI_ERR_NULL;
+    icpmi_ctx *ctx = m->ctx;
+    int rc;
+    if ((rc = check_common(ctx))) return rc;
+    if ((rc = static_check_rule(ctx, rule))) return rc;
+    if (!n_out) return fail(ctx, ICPMI_ERR_NULL, "null argument");
+    if (first < 0) return fail(ctx, ICPMI_ERR_ARG, "first < 0");
+    StaticRun run;
+    if ((rc = static_labels_run(m, poses, n_poses, grid, rule, first, &run))) return rc;
+    *n_out = run.n;
+    if (info) *info = run.info;
+    if (!out_xyz || run.n == 0) return ICPMI_OK;
+    if (cap < run.n) return fail(ctx, ICPMI_ERR_CAPACITY, "output holds %lld rows, needs %lld", (long long)cap, (long long)run.n);
+    Range range("icpmi:map_world_static");
+    const size_t bytes = sizeof(double) * 3 * (size_t)run.n;
+    if ((rc = reserve(ctx, m->d_world, bytes))) return rc;
+    if ((rc = static_queue_world(m, run, (double *)m->d_world.p))) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(out_xyz, m->d_world.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); // the points' wait
+    HIP_TRY(ctx, hipGetLastError());
+    return ICPMI_OK;
+}
+
+int icpmi_map_finish_static(icpmi_map *m, const double *poses, int64_t n_poses, const icpmi_grid_config *grid,
+                            const icpmi_static_rule *rule, double voxel_size, double *map_out, int64_t map_cap, int64_t *n_map,
+                            icpmi_static_info *info)
+{
+    if (!m) return ICPMI_ERR_NULL;
+    icpmi_ctx *ctx = m->ctx;
+    int rc;
+    if ((rc = check_common(ctx))) return rc;
+    if ((rc = static_check_rule(ctx, rule))) return rc;
+    StaticRun run;
+    if ((rc = static_labels_run(m, poses, n_poses, grid, rule, 0, &run))) return rc;
+    if (n_map) *n_map = 0;
+    if (info) *info = run.info;
+    if (!(map_out && voxel_size > 0.0) || run.n == 0) return ICPMI_OK;
+    Range range("icpmi:map_finish_static");
+    hipStream_t s = ctx->stream;
+    if ((rc = reserve(ctx, m->d_world, sizeof(double) * 3 * (size_t)run.n))) return rc;
+    if ((rc = static_queue_world(m, run, (double *)m->d_world.p))) return rc;
+    // publish_global_map (slam_node.cpp:235-238) over the kept rows, in frame then row order: icpmi_map_finish's tail
+    int64_t rows = 0;
+    const int64_t cap = std::max<int64_t>(0, std::min<int64_t>(run.n, map_cap));
+    if ((rc = reserve(ctx, ctx->vox_out, sizeof(double) * 3 * (size_t)std::max<int64_t>(cap, 1)))) return rc;
+    if ((rc = voxel_downsample_device(ctx, (const double *)m->d_world.p, (int)run.n, voxel_size, (double *)ctx->vox_out.p, cap, &rows, false)))
+        return rc;
+    if (rows > 0) HIP_TRY(ctx, hipMemcpyAsync(map_out, ctx->vox_out.p, sizeof(double) * 3 * (size_t)rows, hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    HIP_TRY(ctx, hipGetLastError());
+    if (n_map) *n_map = rows;
+    return ICPMI_OK;
+}
+
+int icpmi_map_static_labels(icpmi_map *m, int64_t frame, uint8_t *labels, int64_t cap, int64_t *n_out)
+{
+    if (!m) return ICPMI_ERR_NULL;
+    icpmi_ctx *ctx = m->ctx;
+    int rc;
+    if ((rc = check_common(ctx))) return rc;
+    if (!n_out) return fail(ctx, ICPMI_ERR_NULL, "null argument");
+    if (m->static_frames < 0) return fail(ctx, ICPMI_ERR_ARG, "no labels yet: call icpmi_map_world_static or icpmi_map_finish_static first");
+    if (frame < 0 || frame >= m->static_frames)
+        return fail(ctx, ICPMI_ERR_ARG, "frame %lld was not used by the call that formed the labels (%lld frames)", (long long)frame,
+                    (long long)m->static_frames);
+    const int64_t rows = m->row0[frame + 1] - m->row0[frame];
+    *n_out = rows;
+    if (!labels) return ICPMI_OK;
+    if (cap < rows) return fail(ctx, ICPMI_ERR_CAPACITY, "labels holds %lld rows, needs %lld", (long long)cap, (long long)rows);
+    if (rows == 0) return ICPMI_OK;
+    HIP_TRY(ctx, hipMemcpyAsync(labels, (const uint8_t *)m->d_static_labels.p + m->row0[frame], (size_t)rows, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return ICPMI_OK;
 }

@@ -203,3 +203,56 @@ class GlobalMap:
         self.ctx._check(self._lib.icpmi_map_ground_labels(self._h, int(frame), out.ctypes.data_as(C.POINTER(C.c_uint8)),
                                                           n.value, C.byref(n)))
         return out
+
+    # ---- the static map (icpmi_map_world_static / icpmi_map_finish_static; csrc/static_map.h) ----
+
+    def world_static(self, poses, grid=None, rule=None, first=0):
+        """world() without the rows the counts outvote: the world points of the rows of frames [first, min(frames,
+        len(poses))) that the rule keeps, frame then row order, each bit for bit world()'s.  The live counts are brought
+        up to date first, as by live_update(poses, grid), and every used row is labelled against them (static_labels).
+        grid None: the default OccupancyGridConfig -- whose band holds no car roof with the sensor at z = 0: see
+        include/icp_mi355x.h.  rule: a capi.StaticRule or (min_probability, min_observations); None: the defaults.
+        Returns (N x 3, capi.StaticInfo)."""
+        P, pp = _poses(poses)
+        g = grid if grid is not None else self.ctx.make_grid_config()
+        r = capi.as_static_rule(rule) if rule is not None else capi.StaticRule()
+        n, info = C.c_int64(0), capi.StaticInfo()
+        last = min(len(self._rows), P.shape[0])
+        cap = int(sum(self._rows[min(max(int(first), 0), last):last]))      # one call: info.live is that call's update
+        out = np.empty((max(cap, 1), 3))
+        self.ctx._check(self._lib.icpmi_map_world_static(self._h, pp, P.shape[0], C.byref(g), C.byref(r), int(first),
+                                                         capi._dp(out), cap, C.byref(n), C.byref(info)))
+        return out[:n.value].copy(), info
+
+    def recent_clouds_static(self, poses, grid=None, rule=None, max_recent=MAX_RECENT_CLOUDS):
+        """recent_clouds() without the dropped rows: one world cloud per frame, for the last max_recent frames"""
+        frames = len(self._rows)
+        first = frames - max_recent if frames > max_recent else 0
+        last = min(frames, len(poses))
+        w, _ = self.world_static(poses, grid, rule, first)
+        kept = [int(np.count_nonzero(self.static_labels(i) != capi.STATIC_DROPPED)) for i in range(first, last)]
+        bounds = np.cumsum([0] + kept)
+        return [w[bounds[i]:bounds[i + 1]] for i in range(max(0, last - first))]
+
+    def finish_static(self, poses, grid=None, rule=None, voxel=1.0):
+        """finish()'s published map over the kept rows of all used frames: voxel_downsample(kept world rows, voxel).
+        The context's cell set is not touched.  Returns (published map: M x 3, capi.StaticInfo)."""
+        P, pp = _poses(poses)
+        g = grid if grid is not None else self.ctx.make_grid_config()
+        r = capi.as_static_rule(rule) if rule is not None else capi.StaticRule()
+        rows = int(sum(self._rows[:min(len(self._rows), P.shape[0])]))
+        out = np.empty((max(rows, 1), 3))
+        nm, info = C.c_int64(0), capi.StaticInfo()
+        self.ctx._check(self._lib.icpmi_map_finish_static(self._h, pp, P.shape[0], C.byref(g), C.byref(r), float(voxel),
+                                                          capi._dp(out), rows, C.byref(nm), C.byref(info)))
+        return out[:nm.value].copy(), info
+
+    def static_labels(self, frame):
+        """one frame's labels (uint8 per row: capi.STATIC_QUIET, STATIC_VOTES, STATIC_DROPPED) as the last world_static or
+        finish_static left them; an error before any, or for a frame that call did not use"""
+        n = C.c_int64(0)
+        self.ctx._check(self._lib.icpmi_map_static_labels(self._h, int(frame), None, 0, C.byref(n)))
+        out = np.empty(n.value, dtype=np.uint8)
+        self.ctx._check(self._lib.icpmi_map_static_labels(self._h, int(frame), out.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                          n.value, C.byref(n)))
+        return out

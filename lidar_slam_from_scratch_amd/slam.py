@@ -42,6 +42,8 @@ class SlamRun:
         self.loop_distances = None    # ... and its whitened distance (sigmas)
         self.rejected_closures = []   # with closure_gate: (LoopClosureResult, d2) of every closure the gate kept out
         self.odom_twists = []         # with deskew: the twist each frame was deskewed with
+        self.published_map_static = None   # with static_map and a global map: the published map without the dropped rows
+        self.static_info = None       # ... and the capi.StaticInfo of that call
 
 
 def node_loop_config():
@@ -53,7 +55,8 @@ def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, po
              align=None, loop_backend=None, pose_graph=None, global_map=None, grid=None, map_voxel=1.0,
              loop_on_device=False, raycast=False, counts=False, live=False, loop_yaw_guess=False, loop_gate=None,
              ground=None, odom_robust=None, loop_robust=None, odom_local_map=None, loop_edge_loss=None,
-             edge_information=None, information_floor=(1.0, 10.0), closure_gate=None, deskew=None, deskew_voxel=0.5, odom_gicp=None):
+             edge_information=None, information_floor=(1.0, 10.0), closure_gate=None, deskew=None, deskew_voxel=0.5, odom_gicp=None,
+             static_map=None):
     """frames: sequence of N x 3 fp64 clouds (already downsampled).  Returns a SlamRun.  global_map: an object with
     add_frame, recent_clouds and finish (None: no map is built); grid: its occupancy grid config (None: defaults).
     loop_on_device: the detector is loop_closure.StoreLoopClosureDetector over global_map (a global_map.GlobalMap),
@@ -69,6 +72,10 @@ def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, po
     ground: a ground.GroundConfig (None: none); with a global_map, global_map.set_ground(ground) before the first
     frame, so the cell set, raster, counts and live counts take each frame's OBSTACLE rows as its hits (not in the
     reference node).  Ignored without a global_map.
+    static_map: a capi.StaticRule or (min_probability, min_observations) (None: none); with a global_map, after its finish,
+    SlamRun.published_map_static, SlamRun.static_info = global_map.finish_static(poses, grid, rule, map_voxel): the
+    published map without the rows whose cells the counts outvote (not in the reference node).  The
+    recent_world clouds after an optimize stay as they are.  Ignored without a global_map.
     odom_robust: (kind, scale) or (kind, scale, max_distance), kind one of capi.ROBUST_* (None: none); the default
     `align` registers under those row weights (odometry.gpu_align(ctx, robust=...); not in the reference node).  With an
     `align` of the caller's it is refused.
@@ -286,6 +293,8 @@ def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, po
         if live:
             live_update()
             run.live = global_map.live_counts()[0]
+        if static_map is not None:
+            run.published_map_static, run.static_info = global_map.finish_static(run.poses, grid, static_map, map_voxel)
     if local_odo is not None:
         local_odo.close()
     if loop_on_device:                                               # the detector (and a private store) go now

@@ -860,7 +860,8 @@ def _counts_parts(c):
 
 @thread("global_map", ("add_frame", "add_frame_device", "size", "world", "recent_clouds", "finish", "raycast", "raster",
                        "raycast_counts", "counts", "live_update", "live_counts", "live_clear", "set_ground", "ground_labels",
-                       "close", "occupancy_cells"), claims=("cells",))
+                       "close", "occupancy_cells", "world_static", "recent_clouds_static", "finish_static", "static_labels"),
+        claims=("cells",))
 def _global_map(ctx, env):
     from lidar_slam_from_scratch_amd import ground
     from lidar_slam_from_scratch_amd.global_map import GlobalMap
@@ -893,6 +894,12 @@ def _global_map(ctx, env):
         gm.set_ground(None)
         info = gm.live_update(poses, grid)
         yield dig(info, _counts_parts(gm.live_counts()[0]))
+        # the static map (appended: the digests above stay as they were)
+        world, info = gm.world_static(poses, grid, (50, 2), 1)
+        yield dig(world, info, gm.static_labels(0), gm.static_labels(4))
+        yield dig(gm.recent_clouds_static(poses, grid, (50, 2), 2))
+        published, info = gm.finish_static(poses[:4], grid, (50, 2), 1.0)         # (fewer poses: a rebuild of the live counts)
+        yield dig(published, info, gm.static_labels(3))
     finally:
         gm.close()
 
