@@ -140,6 +140,13 @@ typedef struct {
                                                         that list every row -- a call's first two -- whose coarse launch ran over the
                                                         (32-row tile, split) pairs that survive the box test instead of all pairs.
                                                         Counted on the host, profiling on or off */
+    int64_t nn_solo_passes;                          /* all-pairs engine, solo passes (ICPMI_NN_SOLO, default on; where lean passes and
+                                                        the match margin are on, sources of 65,473 to 131,072 rows, profile < 2):
+                                                        passes whose closing kernel also formed the next pass's terms and group sums,
+                                                        because the two latest passes the host knew of had found every row certified;
+                                                        that next pass launches its closing kernel only.  Counted on the host,
+                                                        profiling on or off */
+    int64_t nn_solo_fallback_rows;                   /* ... rows those kernels had to search themselves (exhaustively; profiling on) */
 } icpmi_profile;
 
 void icpmi_options_default(icpmi_options *opt);     /* device 0, normal_k 20 (icp.hpp:170), search AUTO or the

@@ -166,7 +166,8 @@ class Profile(C.Structure):
                 ("exchange_ms", C.c_double), ("exchange_launches", C.c_int64), ("coarse_minima_bytes", C.c_int64),
                 ("nn_rows_listed", C.c_int64), ("nn_coarse_skipped", C.c_int64),
                 ("knn_culled_launches", C.c_int64), ("nn_rows_certified", C.c_int64),
-                ("nn_lean_passes", C.c_int64), ("nn_full_culled_passes", C.c_int64)]
+                ("nn_lean_passes", C.c_int64), ("nn_full_culled_passes", C.c_int64),
+                ("nn_solo_passes", C.c_int64), ("nn_solo_fallback_rows", C.c_int64)]
 
 
 MAX_RANKS_INFO = 64

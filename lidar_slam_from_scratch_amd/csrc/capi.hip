@@ -41,6 +41,7 @@
 #include "icp_gicp.h"
 #include "knn_lists.h"
 #include "nn_bounded.h"
+#include "solo_pass.h"
 #include "nn_culled.h"
 #include "voxel.h"
 #include "scan_context.h"
@@ -277,6 +278,7 @@ struct icpmi_ctx {
     int32_t *d_flags = nullptr;    // the same words through the device's address space
     unsigned long long *h_want = nullptr; // host-mapped ring beside it: (iteration + 1) << 32 | rows the pass wanted listed
     unsigned long long *d_want = nullptr; // (lean passes: list_reuse.h; written by k_sum_groups)
+                                          // (solo passes: a second ring behind it, the rows the pass did not find certified)
     unsigned *h_stat = nullptr;    // pinned: list reuse's per-pass statistics on their way back (profiling)
     // icpmi_last_normal_matrix: the sums of the pass that produced final_error of the last registration on this context,
     // taken from the state that came back behind its one wait (LoopRun::fill_result); nm_count: the problems of the last
@@ -445,14 +447,7 @@ bool fuse_finish_enabled()
     }();
     return v;
 }
-// Workgroups of the fused kernel, each of which repeats the final sum.  (Round 3: 128.  With the rows' bounds formed here
-// too (RowBounds) the row part is worth spreading over more CUs than the repeated sums cost: 32 / 64 / 128 / 256
-// workgroups 22.1 / 18.2 / 16.5 / 16.5 us at 100k rows.)
-constexpr int kFinishBlocksMax = 128;
-int finish_transform_blocks(int n)
-{
-    return std::max(1, std::min(kFinishBlocksMax, (n + kFinishThreads - 1) / kFinishThreads));
-}
+// (workgroups of the fused kernel, each of which repeats the final sum: finish_transform_blocks, loop_plan.h)
 
 // ICPMI_SMALL=0 switches the small-cloud kernel off (loop_plan.h, kSmallMaxQueries)
 bool small_enabled()
@@ -600,6 +595,17 @@ int nn_lean_from()
     const int k = e ? atoi(e) : 0;
     return k >= 2 ? k : 0;
 }
+// Solo passes (solo_pass.h).  ICPMI_NN_SOLO=0: a settled pass is the three launches of the form before -- the
+// reference leg of tests and A/B runs.  ICPMI_NN_SOLO_FROM=k (k >= 2) is a TEST HOOK: the tail of every pass from the k-th on
+// is the solo kernel whatever the counts say, the only way to put many rows through its exhaustive search.  Both are read
+// at every call like ICPMI_NN_LEAN.
+bool nn_solo_enabled() { return env_on("ICPMI_NN_SOLO"); }
+int nn_solo_from()
+{
+    const char *e = getenv("ICPMI_NN_SOLO_FROM");
+    const int k = e ? atoi(e) : 0;
+    return k >= 2 ? k : 0;
+}
 
 // The per-row arrays of the bounded pass inside ctx->nn_lists (n rows), then list reuse's word per 64 rows, its packed
 // list of rows (kRowListHead words in front) and its per-pass statistics
@@ -613,6 +619,7 @@ struct NnListRows {
     int *list;
     unsigned *stat_rows;               // [kReuseStatPasses] rows listed per pass (profiling)
     unsigned *stat_cert;               // [kReuseStatPasses] the match margin: rows certified per pass (profiling)
+    unsigned *stat_searched;           // [kReuseStatPasses] solo passes: rows the solo kernel searched for the pass (profiling)
     RowScan *scan;                     // the match margin's per-row records, covers and word per 64 rows (RowBounds)
     double *cover;
     unsigned long long *cert;
@@ -622,7 +629,7 @@ constexpr int kReuseStatPasses = 1024; // (passes beyond overwrite the last entr
 size_t nn_list_bytes(int n)
 {
     return kNnListRowBytes * (size_t)n + 64 + sizeof(unsigned long long) * (((size_t)n + 63) / 64) +
-           sizeof(int) * ((size_t)n + kRowListHead) + sizeof(unsigned) * 2 * kReuseStatPasses + 64 +
+           sizeof(int) * ((size_t)n + kRowListHead) + sizeof(unsigned) * 3 * kReuseStatPasses + 64 +
            (sizeof(RowScan) + sizeof(double)) * (size_t)n + sizeof(unsigned long long) * (((size_t)n + 63) / 64);
 }
 NnListRows nn_list_rows(const icpmi_ctx *ctx, int n)
@@ -638,7 +645,8 @@ NnListRows nn_list_rows(const icpmi_ctx *ctx, int n)
     r.list = (int *)(r.mask + ((size_t)n + 63) / 64);
     r.stat_rows = (unsigned *)(r.list + (size_t)n + kRowListHead);
     r.stat_cert = r.stat_rows + kReuseStatPasses;
-    r.scan = (RowScan *)(((uintptr_t)(r.stat_cert + kReuseStatPasses) + 63) & ~(uintptr_t)63);
+    r.stat_searched = r.stat_cert + kReuseStatPasses;
+    r.scan = (RowScan *)(((uintptr_t)(r.stat_searched + kReuseStatPasses) + 63) & ~(uintptr_t)63);
     r.cover = (double *)(r.scan + n);
     r.cert = (unsigned long long *)(r.cover + n);
     return r;
@@ -1223,6 +1231,12 @@ struct LoopRun {
     std::vector<unsigned> want_known; // [p - 1]: the rows pass p wanted listed, as far as the host has read them
     std::vector<char> lean_passes;    // [p - 1]: pass p was queued lean
     bool lean_cur = false, lean_nxt = false; // the pass being queued, and the one after it
+    // solo passes (solo_pass.h): the rows pass p did not find certified, as far as the host has read them; whether the tail of
+    // the pass being queued is the solo kernel; whether the tail of the pass before was (this pass then launches its tail
+    // only); and which of the two areas of group rows this pass's tail sums
+    std::vector<unsigned> uncert_known;
+    bool solo_cur = false, solo_fed = false;
+    int solo_area = 0;
     // before each k_row_list for pass `next`: where it stores the rows listed and, with the match margin, the rows certified
     // for the coming pass (profiling)
     unsigned *rows_count = nullptr, *cert_count = nullptr;
@@ -1310,10 +1324,14 @@ struct LoopRun {
         f.sw_lean_from = nn_lean_from();
         f.sw_fuse_finish = fuse_finish_enabled();
         f.sw_cull_full = nn_cull_full_enabled();
+        f.sw_solo = nn_solo_enabled();
+        f.sw_solo_from = nn_solo_from();
         p = make_loop_plan(f);
         if (p.error) return fail(ctx, ICPMI_ERR_ARG, p.error, p.rblocks);
         int rc;
-        if ((rc = reserve(ctx, ctx->partials, sizeof(double) * kSumsStride * ((size_t)p.rblocks + (size_t)p.rblocks2)))) return rc;
+        // (solo passes: a second area of group rows behind the first, then two sets of per-workgroup counts; solo_pass.h)
+        const size_t solo_bytes = p.solo_on ? sizeof(double) * kSumsStride * (size_t)p.rblocks2 + 2 * sizeof(SoloCounts) * kFinishBlocksMax : 0;
+        if ((rc = reserve(ctx, ctx->partials, sizeof(double) * kSumsStride * ((size_t)p.rblocks + (size_t)p.rblocks2) + solo_bytes))) return rc;
         partials = (double *)ctx->partials.p;
         fin_rows = p.sum_tree ? partials + kSumsStride * (size_t)p.rblocks : partials;
         return ICPMI_OK;
@@ -1402,7 +1420,7 @@ struct LoopRun {
                 rb.skin = kNnSkin;
                 rb.loose = kNnLoose;
                 if (p.margin) rb.scan = lr.scan, rb.cover = lr.cover, rb.cert = lr.cert;
-                if (ctx->opt.profile) HIP_TRY(ctx, hipMemsetAsync(lr.stat_rows, 0, sizeof(unsigned) * 2 * kReuseStatPasses, s));
+                if (ctx->opt.profile) HIP_TRY(ctx, hipMemsetAsync(lr.stat_rows, 0, sizeof(unsigned) * 3 * kReuseStatPasses, s));
             }
         }
         // current_source = source * R0^T + t0^T (icp.hpp:174-176)
@@ -1463,10 +1481,49 @@ struct LoopRun {
         if (lean_cur) ctx->prof.nn_lean_passes += 1;
     }
 
+    // Solo passes: whether this pass (P, from 1) is fed by the solo kernel that ended the pass before, and whether its own
+    // tail is one, from the two latest counts the queue loop has read (solo_next, loop_plan.h).  The pass behind a solo
+    // kernel is lean (by the rule it is anyway; the test hook).
+    void decide_solo(int final_pass)
+    {
+        solo_fed = solo_cur;
+        solo_cur = solo_next(pass_no + 1, final_pass, p.solo_from, uncert_known.data(), (int)uncert_known.size());
+        if (solo_cur) ctx->prof.nn_solo_passes += 1;
+    }
+    // the group rows this pass's tail sums, and the solo kernel's own arguments: what it writes for the coming pass and, in a
+    // pass that is itself fed by one, the counts it publishes in k_sum_groups' stead (also k_publish_counts' arguments)
+    const double *pass_fin_rows() const { return solo_fed ? solo_groups(solo_area) : fin_rows; }
+    double *solo_groups(int area) const { return partials + kSumsStride * ((size_t)p.rblocks + (size_t)area * p.rblocks2); }
+    SoloCounts *solo_counts(int parity) const
+    {
+        return (SoloCounts *)(partials + kSumsStride * ((size_t)p.rblocks + 2 * (size_t)p.rblocks2)) + (size_t)(parity & 1) * kFinishBlocksMax;
+    }
+    SoloPass solo_args() const
+    {
+        const int here = pass_no - 1, at = std::min(here, kReuseStatPasses - 1); // (this pass, from 0)
+        const int out_area = solo_fed ? 1 - solo_area : 1;
+        SoloPass sp{(const double *)ctx->tgt_sorted.p, (const unsigned *)ctx->sort_keys.p + 3 * (size_t)m, ctx->nn_ms, ctx->nn_splits,
+                    (const SplitFrame *)ctx->frames.p, (const double *)nrm, idx, solo_groups(out_area), solo_counts(here + 1),
+                    nullptr, 0, nullptr, nullptr, 0u, n, nullptr, nullptr, nullptr};
+        if (solo_fed) {
+            sp.counts_in = solo_counts(here);
+            sp.blocks_in = p.fin_blocks;
+            sp.want = ctx->d_want + here % kFlagRing;
+            sp.uncert = ctx->d_want + kFlagRing + here % kFlagRing;
+            sp.ticket = (unsigned)(here + 1);
+            if (ctx->opt.profile) sp.stat_rows = lr.stat_rows + at, sp.stat_cert = lr.stat_cert + at, sp.stat_searched = lr.stat_searched + at;
+        }
+        return sp;
+    }
+
     // ... its search: the MFMA engines' resolve leaves the partial rows too (LoopPlan::fused)
     int pass_search()
     {
         if (n <= 0) return ICPMI_OK;
+        if (solo_fed) { // (the solo kernel that ended the pass before has left this pass's matches and group sums: a lean bounded pass)
+            ctx->prof.bounded_launches += 1;
+            return ICPMI_OK;
+        }
         if (!p.fused) return launch_nn(ctx, cur, n, d_tgt, m, idx, nullptr, st);
         // (bounded: incumbents in idx, bounds in place -- from k_nn_prebound1 or the kernel that moved the rows)
         // (culled full passes: a call's first two, whichever of them is the post-loop pass)
@@ -1484,12 +1541,15 @@ struct LoopRun {
         else if (!p.fused)
             launch_by_rule(gate, k_reduce_rule<RuleNone>, k_reduce_rule<RuleGate, double>, k_reduce_rule<RuleRobust, double, int, double>, dim3(p.rblocks), dim3(256), s, (const double *)cur, n, d_tgt, m,
                            (const double *)nrm, (const int *)idx, partials, (const IcpState *)st);
-        if (p.sum_tree && p.lean_on) { // (+ the workgroup that counts the rows this pass wanted listed; pass_no - 1: this pass, from 0)
+        if (solo_fed) { // no partial rows to add; the pass's counts are the solo tail's to publish, or a wave's in front of any other
+            if (!solo_cur) hipLaunchKernelGGL(k_publish_counts, dim3(1), dim3(64), 0, s, (const IcpState *)st, solo_args());
+        } else if (p.sum_tree && p.lean_on) { // (+ the workgroup that counts the rows this pass wanted listed; pass_no - 1: this pass, from 0)
             const int here = pass_no - 1, at = std::min(here, kReuseStatPasses - 1);
             const bool stats = lean_cur && ctx->opt.profile;
             const WantPublish wp{ctx->d_want + here % kFlagRing, (unsigned)(here + 1), n, here == 0, (const unsigned long long *)lr.mask,
                                  p.margin ? (const unsigned long long *)lr.cert : nullptr, stats ? lr.stat_rows + at : nullptr,
-                                 stats && p.margin ? lr.stat_cert + at : nullptr};
+                                 stats && p.margin ? lr.stat_cert + at : nullptr,
+                                 p.solo_on ? ctx->d_want + kFlagRing + here % kFlagRing : nullptr};
             hipLaunchKernelGGL(k_sum_groups, dim3((p.rblocks2 + 7) / 8 + 1), dim3(256), 0, s, (const double *)partials, p.rblocks,
                                partials + kSumsStride * (size_t)p.rblocks, (const IcpState *)st, wp);
         } else if (p.sum_tree)
@@ -1507,7 +1567,7 @@ struct LoopRun {
         IcpState *other = st == ctx->d_state ? ctx->d_state + 1 : ctx->d_state; // (the fused kernels write the other state buffer)
         if (p.sharded) {
             int rc;
-            hipLaunchKernelGGL(k_finish, dim3(1), dim3(kFinishThreads), 0, s, fin_rows, p.fin_blocks, n, st);
+            hipLaunchKernelGGL(k_finish, dim3(1), dim3(kFinishThreads), 0, s, pass_fin_rows(), p.fin_blocks, n, st);
             {
                 StageTimer tx(ctx, ST_EXCHANGE); // the per-pass all-reduce alone (30 doubles; RCCL on the library's stream)
                 if ((rc = exchange_allreduce(ctx, st->sums, kNumExchanged))) return rc;
@@ -1527,17 +1587,22 @@ struct LoopRun {
                                    ctx->n_ranks);
             }
         } else if (finish_moves) { // final sum + step + pose update of the rows in one launch
-            if (p.pruned)
+            if (solo_cur) { // (... and the coming pass's terms and group sums: solo_pass.h)
+                hipLaunchKernelGGL(k_finish_step_transform_solo, dim3(finish_transform_blocks(n)), dim3(kFinishThreads), 0, s,
+                                   pass_fin_rows(), p.fin_blocks, n, (const double *)cur, cur, n, (const IcpState *)st, other, hist,
+                                   progress, ticket, rb, solo_args());
+                solo_area = solo_fed ? 1 - solo_area : 1;
+            } else if (p.pruned)
                 hipLaunchKernelGGL(k_finish_step_transform_cull, dim3(finish_transform_blocks(n)), dim3(kFinishThreads), 0, s,
                                    fin_rows, p.fin_blocks, n, (const double *)cur, cur, n, (const IcpState *)st, other,
                                    hist, progress, ticket, rb, frames, splits, group_lists(ctx, pass_no & 1));
             else
                 hipLaunchKernelGGL(k_finish_step_transform, dim3(finish_transform_blocks(n)), dim3(kFinishThreads), 0, s,
-                                   fin_rows, p.fin_blocks, n, (const double *)cur, cur, n,
+                                   pass_fin_rows(), p.fin_blocks, n, (const double *)cur, cur, n,
                                    (const IcpState *)st, other, hist, progress, ticket, rb);
             st = other;
         } else {
-            launch_finish_step(fin_rows, p.fin_blocks, final_pass, progress, ticket);
+            launch_finish_step(pass_fin_rows(), p.fin_blocks, final_pass, progress, ticket);
         }
         return ICPMI_OK;
     }
@@ -1547,6 +1612,7 @@ struct LoopRun {
     {
         int rc;
         if (p.lean_on) decide_lean(final_pass);
+        if (p.solo_on) decide_solo(final_pass);
         if ((rc = pass_search())) return rc;
         if (n > 0 && p.fused) {
             ++pass_no;
@@ -1575,6 +1641,7 @@ struct LoopRun {
         }
         // culled full passes: the box test of the rows the first pass's mover has just left, into set 1 -- the second pass's
         // group lists (the first pass's coarse kernel has cleared that set's counters)
+        if (solo_cur) lean_nxt = true; // (nothing of the coming pass but its tail is launched)
         if (p.cull_full && pass_no == 1 && !final_pass && !lean_nxt)
             hipLaunchKernelGGL(k_row_group_cull, dim3(((n + 63) / 64 + 15) / 16), dim3(1024), 0, s, (const double *)cur, n, (const float *)lr.ubf,
                                (const SplitFrame *)ctx->frames.p, ctx->nn_splits, group_lists(ctx, 1), (const IcpState *)st);
@@ -1598,7 +1665,7 @@ struct LoopRun {
         int rc;
         range_loop.emplace("icpmi:icp_loop");
         t_loop.emplace(ctx, ST_LOOP);
-        for (int i = 0; i < kFlagRing; ++i) ctx->h_flags[i] = 0, ctx->h_want[i] = 0ull;
+        for (int i = 0; i < kFlagRing; ++i) ctx->h_flags[i] = 0, ctx->h_want[i] = 0ull, ctx->h_want[kFlagRing + i] = 0ull;
         bool after_first_done = after_first == nullptr;
         for (int it = 0; it < cfg->max_iterations; ++it) {
             if (it >= kLag && !after_first_done) {
@@ -1624,6 +1691,12 @@ struct LoopRun {
                                          "device row count word never arrived", &w)))
                         return rc;
                     want_known.push_back((unsigned)(w & 0xFFFFFFFFull));
+                    if (p.solo_on) { // ... and the rows it did not find certified, published with it
+                        if ((rc = await_word(ctx, &ctx->h_want[kFlagRing + slot], want, [](unsigned long long x) { return (int)(x >> 32); },
+                                             "device row count word never arrived", &w)))
+                            return rc;
+                        uncert_known.push_back((unsigned)(w & 0xFFFFFFFFull));
+                    }
                 }
             }
             if ((rc = queue_pass(0, ctx->d_flags + it % kFlagRing, it + 1))) return rc;
@@ -1671,7 +1744,7 @@ struct LoopRun {
         stats_back = p.reuse && ctx->opt.profile && pass_no > 0;
         stat_passes = std::min(pass_no, kReuseStatPasses);
         if (stats_back)
-            HIP_TRY(ctx, hipMemcpyAsync(ctx->h_stat, lr.stat_rows, sizeof(unsigned) * ((size_t)(p.margin ? 1 : 0) * kReuseStatPasses + stat_passes),
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->h_stat, lr.stat_rows, sizeof(unsigned) * ((size_t)(p.solo_on ? 2 : p.margin ? 1 : 0) * kReuseStatPasses + stat_passes),
                                         hipMemcpyDeviceToHost, s));
         if (before_wait && ctx->opt.profile == 0) {
             // the results are waited for through an event; what before_wait queues behind it keeps the device busy
@@ -1726,6 +1799,8 @@ struct LoopRun {
             if (p.margin) { // the match margin, per pass: the rows certified (the first pass certifies none)
                 ctx->margin_rows.assign(stat + kReuseStatPasses, stat + kReuseStatPasses + np);
                 for (int q = 0; q < np; ++q) ctx->prof.nn_rows_certified += ctx->margin_rows[q];
+                if (p.solo_on)
+                    for (int q = 0; q < np; ++q) ctx->prof.nn_solo_fallback_rows += stat[2 * kReuseStatPasses + q];
             }
             for (int q = 0; q < np; ++q) {
                 ctx->prof.nn_rows_listed += ctx->reuse_rows[q];
@@ -2078,10 +2153,10 @@ int icpmi_create(const icpmi_options *opt, icpmi_ctx **out)
     if (hipHostMalloc((void **)&ctx->h_flags, sizeof(int32_t) * kFlagRing, hipHostMallocMapped) != hipSuccess) return bail("hipHostMalloc");
     if (hipHostMalloc((void **)&ctx->h_grid, 4 * sizeof(unsigned), hipHostMallocDefault) != hipSuccess) return bail("hipHostMalloc");
     if (hipHostMalloc((void **)&ctx->h_cnt, 8 * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess) return bail("hipHostMalloc");
-    if (hipHostMalloc((void **)&ctx->h_want, sizeof(unsigned long long) * kFlagRing, hipHostMallocMapped) != hipSuccess) return bail("hipHostMalloc");
-    if (hipHostMalloc((void **)&ctx->h_stat, sizeof(unsigned) * 2 * kReuseStatPasses, hipHostMallocDefault) != hipSuccess) return bail("hipHostMalloc");
+    if (hipHostMalloc((void **)&ctx->h_want, sizeof(unsigned long long) * 2 * kFlagRing, hipHostMallocMapped) != hipSuccess) return bail("hipHostMalloc");
+    if (hipHostMalloc((void **)&ctx->h_stat, sizeof(unsigned) * 3 * kReuseStatPasses, hipHostMallocDefault) != hipSuccess) return bail("hipHostMalloc");
     memset(ctx->h_flags, 0, sizeof(int32_t) * kFlagRing);
-    memset(ctx->h_want, 0, sizeof(unsigned long long) * kFlagRing);
+    memset(ctx->h_want, 0, sizeof(unsigned long long) * 2 * kFlagRing);
     if (hipHostGetDevicePointer((void **)&ctx->d_flags, ctx->h_flags, 0) != hipSuccess) return bail("hipHostGetDevicePointer");
     if (hipHostGetDevicePointer((void **)&ctx->d_want, ctx->h_want, 0) != hipSuccess) return bail("hipHostGetDevicePointer");
     *out = ctx;

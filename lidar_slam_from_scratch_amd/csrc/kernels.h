@@ -236,7 +236,7 @@ __global__ __launch_bounds__(256) void k_reduce_rule(const double *__restrict__ 
 // kFinishThreads threads = G row groups x 32 columns: every load instruction reads whole
 // 256-byte rows, thread (g, e) adds rows g, g+G, ... of column e with sixteen loads in flight,
 // then the G groups are added in order.  Must be called by the whole workgroup.
-constexpr int kFinishThreads = 1024;
+// (kFinishThreads = 1024 is defined in loop_plan.h: the host plans its launches with it)
 constexpr int kFinishGroups = kFinishThreads / 32;
 
 // Counted (icp_gated.h): column 28 of the partial rows holds each block's number of kept rows; their fixed-order sum
@@ -316,12 +316,15 @@ struct WantPublish {
     const unsigned long long *mask; // [(n + 63) / 64]
     const unsigned long long *cert; // the match margin's words (or null)
     unsigned *stat_rows, *stat_cert;
+    // solo passes (solo_pass.h; null: none of this): a second host-mapped word, (ticket << 32) | the rows of pass p that are
+    // NOT in `cert` -- every row in a call's first pass
+    unsigned long long *uncert = nullptr;
 };
 __device__ __forceinline__ void publish_want(const WantPublish &wp)
 {
     __shared__ unsigned part[2][4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = (wp.n + 63) / 64;
-    const bool certs = wp.stat_cert && wp.cert;
+    const bool certs = (wp.stat_cert || wp.uncert) && wp.cert;
     const unsigned want = wp.first ? 0u : wave_scan_incl((unsigned)row_list_count(wp.mask, tid, nw, 256));
     const unsigned sure = certs && !wp.first ? wave_scan_incl((unsigned)row_list_count(wp.cert, tid, nw, 256)) : 0u;
     if (lane == 63) part[0][wave] = want, part[1][wave] = sure;
@@ -330,7 +333,11 @@ __device__ __forceinline__ void publish_want(const WantPublish &wp)
         const unsigned w = wp.first ? (unsigned)wp.n : (part[0][0] + part[0][1]) + (part[0][2] + part[0][3]);
         __hip_atomic_store(wp.slot, ((unsigned long long)wp.ticket << 32) | w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         if (wp.stat_rows) *wp.stat_rows = w;
-        if (certs) *wp.stat_cert = (part[1][0] + part[1][1]) + (part[1][2] + part[1][3]);
+        const unsigned c = (part[1][0] + part[1][1]) + (part[1][2] + part[1][3]);
+        if (certs && wp.stat_cert) *wp.stat_cert = c;
+        if (wp.uncert)
+            __hip_atomic_store(wp.uncert, ((unsigned long long)wp.ticket << 32) | ((unsigned)wp.n - (certs ? c : 0u)), __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
 __global__ __launch_bounds__(256) void k_sum_groups(const double *__restrict__ rows, int nblocks, double *__restrict__ rows2,
@@ -655,6 +662,80 @@ struct RowBatch {
         load_rows(in, rb, i0, stride, n, perm);
         load_matches(rb);
     }
+    // one row of the batch: moved, stored, its bounds and words left for the coming pass; what the caller may go on with
+    struct Moved {
+        double px, py, pz, ub;             // the moved row and its exact squared distance to its kept match (+Inf: none)
+        bool cert;                         // the match margin certified it
+        unsigned long long again, sure;    // the wave's words (RowBounds::mask, RowBounds::cert), as stored
+    };
+    __device__ __forceinline__ Moved finish_row(const int b, const int i, double *out, const RowBounds &rb, const Rigid34 &P) const
+    {
+        Moved mv{0.0, 0.0, 0.0, __builtin_inf(), false, 0ull, 0ull};
+        double px, py, pz;
+        P.apply(x[b], y[b], z[b], px, py, pz);
+        mv.px = px, mv.py = py, mv.pz = pz;
+        out[3 * i] = px;
+        out[3 * i + 1] = py;
+        out[3 * i + 2] = pz;
+        if (rb.tgt) {
+            // A row with a NaN or infinite coordinate has no neighbour (kdtree.hpp:125): NaN, under which the coarse pass
+            // lists nothing.  No previous match (every target non-finite ...): +Inf, everything is listed.
+            double ub = __builtin_inf();
+            float ubf = __builtin_nanf(""), sqf = 0.f;
+            bool keep = false, cert = false;
+            if (__builtin_isfinite(px) && __builtin_isfinite(py) && __builtin_isfinite(pz)) {
+                if (have[b]) ub = sqdist(tx[b], ty[b], tz[b], px, py, pz);
+                double r2 = ub; // the radius^2 the coarse pass lists for
+                if (rb.xb) {
+                    // the certificate (see RowBounds; list_reuse.h).  A list is not kept if it overflowed (cnt > kNnEntCap: the resolve's exhaustive path) or is empty (cnt == 0: a row beyond fp32's
+                    // range), nor if R_b is more than `loose` times the radius it would be built for now (a loose list:
+                    // slots the resolve would scan for nothing).  R_b NaN (first pass) fails every comparison.
+                    const double sq = __builtin_sqrt(ub);
+                    if (rb.scan) { // the match margin first: a certified row has nothing to do with its list
+                        const double sx = px - sc[b].x, sy = py - sc[b].y, sz = pz - sc[b].z;
+                        cert = match_certified(sq, __builtin_sqrt((sx * sx + sy * sy) + sz * sz), sc[b].g);
+                    }
+                    if (!cert) {
+                        const double ex = px - lb[b].x, ey = py - lb[b].y, ez = pz - lb[b].z;
+                        const double d = __builtin_sqrt((ex * ex + ey * ey) + ez * ez);
+                        const double mx = px - x[b], my = py - y[b], mz = pz - z[b];
+                        const double rn = list_radius(sq, __builtin_sqrt((mx * mx + my * my) + mz * mz), rb.skin);
+                        keep = c[b] > 0 && c[b] <= kNnEntCap && list_certified(sq, d, lb[b].r) &&
+                               (rb.loose <= 0.0 || lb[b].r <= rb.loose * rn);
+                        if (!keep) {
+                            r2 = rn * rn;
+                            rb.xb[i] = RowList{px, py, pz, rn};
+                        }
+                        if (rb.cover) rb.cover[i] = keep ? list_cover(lb[b].r, d) : list_cover(rn, 0.0);
+                    }
+                }
+                if (!keep && !cert) {
+                    ubf = (float)r2;
+                    ubf = (double)ubf < r2 ? __uint_as_float(__float_as_uint(ubf) + 1u) : ubf; // (r2 >= 0; Inf stays Inf)
+                    sqf = __builtin_amdgcn_sqrtf(ubf);
+                    sqf = sqf < 3.0e38f ? __uint_as_float(__float_as_uint(sqf) + 2u) : sqf;   // (1 ulp of v_sqrt_f32 and one more)
+                }
+            }
+            mv.ub = ub, mv.cert = cert;
+            rb.ub[i] = ub;
+            rb.ubf[i] = ubf;
+            rb.sqf[i] = sqf;
+            if (!keep && !cert) rb.cnt[i] = 0;
+            if (rb.mask) {
+                // the wave's rows are 64 consecutive ones from a multiple of 64 (rows past n are not here and leave their
+                // bits clear): lane 0 holds the first of them and stores the group's word
+                const unsigned long long again = __ballot(!keep && !cert && ubf == ubf);
+                if ((i & 63) == 0) rb.mask[i >> 6] = again;
+                mv.again = again;
+                if (rb.cert) {
+                    const unsigned long long sure = __ballot(cert);
+                    if ((i & 63) == 0) rb.cert[i >> 6] = sure;
+                    mv.sure = sure;
+                }
+            }
+        }
+        return mv;
+    }
     __device__ __forceinline__ void finish(double *out, const RowBounds &rb, int i0, int stride, int n, const double *T) const
     {
         const Rigid34 P = Rigid34::load(T);
@@ -662,65 +743,7 @@ struct RowBatch {
         for (int b = 0; b < B; ++b) {
             const int i = i0 + b * stride;
             if (i >= n) continue;
-            double px, py, pz;
-            P.apply(x[b], y[b], z[b], px, py, pz);
-            out[3 * i] = px;
-            out[3 * i + 1] = py;
-            out[3 * i + 2] = pz;
-            if (rb.tgt) {
-                // A row with a NaN or infinite coordinate has no neighbour (kdtree.hpp:125): NaN, under which the coarse pass
-                // lists nothing.  No previous match (every target non-finite ...): +Inf, everything is listed.
-                double ub = __builtin_inf();
-                float ubf = __builtin_nanf(""), sqf = 0.f;
-                bool keep = false, cert = false;
-                if (__builtin_isfinite(px) && __builtin_isfinite(py) && __builtin_isfinite(pz)) {
-                    if (have[b]) ub = sqdist(tx[b], ty[b], tz[b], px, py, pz);
-                    double r2 = ub; // the radius^2 the coarse pass lists for
-                    if (rb.xb) {
-                        // the certificate (see RowBounds; list_reuse.h).  A list is not kept if it overflowed (cnt > kNnEntCap: the resolve's exhaustive path) or is empty (cnt == 0: a row beyond fp32's
-                        // range), nor if R_b is more than `loose` times the radius it would be built for now (a loose list:
-                        // slots the resolve would scan for nothing).  R_b NaN (first pass) fails every comparison.
-                        const double sq = __builtin_sqrt(ub);
-                        if (rb.scan) { // the match margin first: a certified row has nothing to do with its list
-                            const double sx = px - sc[b].x, sy = py - sc[b].y, sz = pz - sc[b].z;
-                            cert = match_certified(sq, __builtin_sqrt((sx * sx + sy * sy) + sz * sz), sc[b].g);
-                        }
-                        if (!cert) {
-                            const double ex = px - lb[b].x, ey = py - lb[b].y, ez = pz - lb[b].z;
-                            const double d = __builtin_sqrt((ex * ex + ey * ey) + ez * ez);
-                            const double mx = px - x[b], my = py - y[b], mz = pz - z[b];
-                            const double rn = list_radius(sq, __builtin_sqrt((mx * mx + my * my) + mz * mz), rb.skin);
-                            keep = c[b] > 0 && c[b] <= kNnEntCap && list_certified(sq, d, lb[b].r) &&
-                                   (rb.loose <= 0.0 || lb[b].r <= rb.loose * rn);
-                            if (!keep) {
-                                r2 = rn * rn;
-                                rb.xb[i] = RowList{px, py, pz, rn};
-                            }
-                            if (rb.cover) rb.cover[i] = keep ? list_cover(lb[b].r, d) : list_cover(rn, 0.0);
-                        }
-                    }
-                    if (!keep && !cert) {
-                        ubf = (float)r2;
-                        ubf = (double)ubf < r2 ? __uint_as_float(__float_as_uint(ubf) + 1u) : ubf; // (r2 >= 0; Inf stays Inf)
-                        sqf = __builtin_amdgcn_sqrtf(ubf);
-                        sqf = sqf < 3.0e38f ? __uint_as_float(__float_as_uint(sqf) + 2u) : sqf;   // (1 ulp of v_sqrt_f32 and one more)
-                    }
-                }
-                rb.ub[i] = ub;
-                rb.ubf[i] = ubf;
-                rb.sqf[i] = sqf;
-                if (!keep && !cert) rb.cnt[i] = 0;
-                if (rb.mask) {
-                    // the wave's rows are 64 consecutive ones from a multiple of 64 (rows past n are not here and leave their
-                    // bits clear): lane 0 holds the first of them and stores the group's word
-                    const unsigned long long again = __ballot(!keep && !cert && ubf == ubf);
-                    if ((i & 63) == 0) rb.mask[i >> 6] = again;
-                    if (rb.cert) {
-                        const unsigned long long sure = __ballot(cert);
-                        if ((i & 63) == 0) rb.cert[i >> 6] = sure;
-                    }
-                }
-            }
+            (void)finish_row(b, i, out, rb, P);
         }
     }
 };

@@ -22,6 +22,16 @@ constexpr int kSmallQ = 32;   // rows (queries) per workgroup of the small-cloud
 // (k_sum_groups, kernels.h: from kSumTreeFrom partial rows on they are first added in groups of kSumGroup)
 constexpr int kSumGroup = 16;
 constexpr int kSumTreeFrom = 1024;
+// the kernels that sum, step and move the rows in one launch (k_finish_step_transform*, kernels.h): threads per workgroup,
+// and the most workgroups of a launch -- each repeats the final sum.  (Round 3: 128.  With the rows' bounds formed there
+// too (RowBounds) the row part is worth spreading over more CUs than the repeated sums cost: 32 / 64 / 128 / 256
+// workgroups 22.1 / 18.2 / 16.5 / 16.5 us at 100k rows.)
+constexpr int kFinishThreads = 1024;
+constexpr int kFinishBlocksMax = 128;
+inline int finish_transform_blocks(int n)
+{
+    return std::max(1, std::min(kFinishBlocksMax, (n + kFinishThreads - 1) / kFinishThreads));
+}
 
 // (AUTO takes the exact fp64 kernels for sources of fewer rows: engine_for in capi.hip)
 constexpr int kMfmaMinQueries = 64;
@@ -103,6 +113,8 @@ struct LoopFacts {
     int sw_lean_from = 0;   // ICPMI_NN_LEAN_FROM: 0 or k >= 2
     bool sw_fuse_finish = true;
     bool sw_cull_full = true; // ICPMI_NN_CULL_FULL, read at every call
+    bool sw_solo = true;      // ICPMI_NN_SOLO, read at every call
+    int sw_solo_from = 0;     // ICPMI_NN_SOLO_FROM: 0 or k >= 2
 };
 
 // (by the target alone: whether its Morton-ordered normals are worth keeping)
@@ -133,6 +145,8 @@ struct LoopPlan {
     int fin_blocks = 0;            // rows the step kernels sum
     const char *error = nullptr;   // a refusal ("internal: ..."; a format that takes rblocks), or null
     bool cull_full = false;        // all-pairs engine: the two passes that list every row run over the box test's survivors
+    bool solo_on = false;          // solo passes: a settled pass is one launch (k_finish_step_transform_solo, solo_pass.h)
+    int solo_from = 0;             // the test hook's first solo tail (0: by the counts)
 };
 
 inline LoopPlan make_loop_plan(const LoopFacts &f)
@@ -215,6 +229,14 @@ inline LoopPlan make_loop_plan(const LoopFacts &f)
     // 100,000 points: 0.525 -> 0.543, 0.789 -> 0.812 and 0.917 -> 0.935 ms a call of 9 iterations with the passes culled.)
     p.cull_full = p.reuse && p.sorted_rows_loop && !p.sharded && f.rule == kRuleNone && f.nn_splits > kKnnCullFromSplits &&
                   f.nn_splits <= kCullMaxSplits && n < kCullMaxRows && f.sw_cull_full;
+    // Solo passes (solo_pass.h): once every row's match is certified, the kernel that ends a pass also forms
+    // the next pass's terms and group sums for its own rows, and that pass launches nothing else.  Where lean passes and the
+    // match margin are on, a workgroup of the moving kernel holds exactly the rows of one group sum (one row per thread, one
+    // group row per workgroup: at most kFinishBlocksMax x kFinishThreads rows), and the stage brackets of profile level 2,
+    // which want the three launches, are off.  ICPMI_NN_SOLO=0: the launches of the form before.
+    p.solo_on = p.lean_on && p.margin && p.fin_blocks == finish_transform_blocks(n) && n <= kFinishBlocksMax * kFinishThreads &&
+                f.profile < 2 && f.sw_solo;
+    p.solo_from = p.solo_on ? f.sw_solo_from : 0;
     return p;
 }
 
@@ -233,6 +255,19 @@ inline bool lean_next(int P, int final_pass, int lean_from, const unsigned *want
     if (final_pass) return false;
     if (lean_from) return P + 1 >= lean_from;
     return P >= 6 && known >= P - 2 && lean_pass(P + 1, want[P - 4], want[P - 3]);
+}
+
+// Solo passes, the host's bookkeeping: whether the tail of pass P (from 1, never the post-loop pass) is the solo kernel,
+// decided when pass P is queued from uncert[p - 1] = the rows pass p did not find certified, `known` of which the host has
+// read (P - 2 by then, like the counts of lean_next).  It is when the two latest, uncert(P - 3) and uncert(P - 2), are 0:
+// uncert(1) = uncert(2) = n, so never before pass 6, and a row that is not certified is not listed either, so the pass
+// behind such a tail is lean by lean_next's own rule.  `solo_from` (the test hook): every tail from that pass on, whatever
+// the counts; the queue loop then takes the passes behind them as lean.
+inline bool solo_next(int P, int final_pass, int solo_from, const unsigned *uncert, int known)
+{
+    if (final_pass) return false;
+    if (solo_from) return P >= solo_from;
+    return P >= 6 && known >= P - 2 && uncert[P - 4] == 0u && uncert[P - 3] == 0u;
 }
 
 } // namespace icpmi
