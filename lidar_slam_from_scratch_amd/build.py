@@ -5,7 +5,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(_HERE, "libicp_mi355x.so")
-_SOURCES = ["capi.hip", "sort.hip", "kernels.h", "device_math.h", "list_reuse.h", "loop_plan.h", "nn_mfma.h", "icp_small.h", "icp_small_kernel.inc", "icp_gated.h", "icp_robust.h", "icp_gicp.h", "icp_gicp_row.inc", "knn_lists.h", "nn_bounded.h", "solo_pass.h", "nn_culled.h", "voxel.h", "scan_context.h", "occupancy.h", "global_map.h", "raycast.h", "raycount.h", "live_plane.h", "live_counts.h", "ground.h", "static_map.h", "deskew.h", "deskew_host.h", "loop_store.h", "se3.h", "pose_graph.h", "pose_graph_loss.h", "pose_graph_info.h", "pose_graph_info_host.h", "pose_graph_marginals.h", "pose_graph_marginals_host.h", "local_map.h", "Makefile"]
+_SOURCES = ["capi.hip", "sort.hip", "kernels.h", "device_math.h", "list_reuse.h", "loop_plan.h", "workspace_layout.h", "nn_mfma.h", "icp_small.h", "icp_small_kernel.inc", "icp_gated.h", "icp_robust.h", "icp_gicp.h", "icp_gicp_row.inc", "knn_lists.h", "nn_bounded.h", "solo_pass.h", "nn_culled.h", "voxel.h", "scan_context.h", "occupancy.h", "global_map.h", "raycast.h", "raycount.h", "live_plane.h", "live_counts.h", "ground.h", "static_map.h", "deskew.h", "deskew_host.h", "loop_store.h", "se3.h", "pose_graph.h", "pose_graph_loss.h", "pose_graph_info.h", "pose_graph_info_host.h", "pose_graph_marginals.h", "pose_graph_marginals_host.h", "local_map.h", "Makefile"]
 
 
 def _stale():

@@ -33,6 +33,7 @@
 
 #include "../../include/icp_mi355x.h"
 #include "loop_plan.h"
+#include "workspace_layout.h"
 #include "kernels.h"
 #include "nn_mfma.h"
 #include "icp_small.h"
@@ -209,16 +210,44 @@ struct BatchWorker {
     bool has_job = false, done = false, quit = false;
 };
 
+// What defines a prepared target (prepare_nn, prepare_target): its search structure, its normals, what the engine chose for
+// it and whose preparation it is.  A context holds one; adopt_target hands a helper context's over whole.
+struct PreparedTarget {
+    DevBuf bpack, nn_misc;                    // MFMA engine: operands; frames + counters (MiscBlock, workspace_layout.h)
+    DevBuf sort_keys, tgt_sorted, frames;     // Morton pre-pass: the sort's planes (SortPlanes), sorted copy, split frames
+    DevBuf nrm, nrm_sorted;                   // the normals by point; small-cloud kernel: in Morton order (SoA, stride nn_ms)
+    int nn_engine = ICPMI_SEARCH_EXACT_F64;   // engine prepared for the current target
+    bool nn_pruned = false;                   // the culled engine (ICPMI_SEARCH_MFMA_PRUNED; AUTO on large targets)
+    int nn_splits = 0;
+    int nn_ms = 0;                            // component stride of the SoA sorted target
+    int m = 0;                                // its rows (MFMA engines)
+    // the target whose search structure and normals the buffers currently hold (prepare_target):
+    // icpmi_stream_push prepares the NEXT frame's target while the caller is still busy with this frame's result
+    const double *prep_tgt = nullptr;
+    int prep_m = 0, prep_engine = 0;
+    bool prep_valid = false;
+
+    const unsigned *perm() const { return SortPlanes(sort_keys.p, (size_t)m).perm; }
+    const unsigned *sorted_keys() const { return SortPlanes(sort_keys.p, (size_t)m).keys_out; }
+    NnFrame *frame() const { return MiscBlock::at<NnFrame>(nn_misc.p, MiscBlock::kTargetFrame); }
+    NnFrame *source_frame() const { return MiscBlock::at<NnFrame>(nn_misc.p, MiscBlock::kSourceFrame); }
+    unsigned long long *counters() const { return MiscBlock::at<unsigned long long>(nn_misc.p, MiscBlock::kCounters); }
+    const SplitFrame *split_frames() const { return (const SplitFrame *)frames.p; }
+    const double *sorted() const { return (const double *)tgt_sorted.p; }
+    const uint4 *operands() const { return (const uint4 *)bpack.p; }
+};
+static_assert(sizeof(VoxelBox) == sizeof(NnFrame), "the voxel filter's box takes an NnFrame's place in the misc block");
+
 struct icpmi_ctx {
     icpmi_options opt;
     hipStream_t stream = nullptr;
     std::string err;
     int cu_count = 256;
 
-    DevBuf cur, nrm, idx, part_d2, part_idx, partials, history, stage_a, stage_b, stage_c, d2out;
+    PreparedTarget tgt;
+    DevBuf cur, idx, part_d2, part_idx, partials, history, stage_a, stage_b, stage_c, d2out;
     DevBuf knn_idx, slotmin, fb_list;         // k-NN lists, slot minima, rows for the exact fallback
     DevBuf nn_lists;                          // bounded 1-NN pass: per row bound, threshold, count, listed columns (nn_bounded.h)
-    DevBuf nrm_sorted;                        // small-cloud kernel: the target normals in Morton order (SoA, stride nn_ms)
     DevBuf src_nrm;                           // plane-to-plane ICP: the source's normals, in the caller's row order (icp_gicp.h)
     DevBuf vox_keys, vox_vals, vox_out;             // voxel filter: 64-bit keys (in/out/unique), values + run data, result
     DevBuf stream_prev, stream_cur, f32_stage;      // odometry stream: previous / current filtered scan; float32 upload staging
@@ -237,11 +266,6 @@ struct icpmi_ctx {
     std::vector<unsigned> reuse_rows, reuse_blocks; // profiling: per pass of the last registration, rows listed and workgroup columns run
     std::vector<unsigned> margin_rows;              // ... and rows certified by the match margin (empty where it was off)
     FilePrefetch *prefetch = nullptr;               // worker reading the next frame file (icpmi_stream_prefetch_file)
-    // the target whose search structure and normals the context's buffers currently hold (prepare_target):
-    // icpmi_stream_push prepares the NEXT frame's target while the caller is still busy with this frame's result
-    const double *prep_tgt = nullptr;
-    int prep_m = 0, prep_engine = 0;
-    bool prep_valid = false;
     hipEvent_t result_ready = nullptr;              // recorded behind a call's result copies (stream path)
     bool trailing_work = false;                     // a push returned with the next target's preparation still queued
     // odometry stream: the NEXT target's search structure and normals are built on a stream and workspace of their
@@ -253,9 +277,8 @@ struct icpmi_ctx {
     // where the calling thread's time goes in the frame stream (ICPMI_STREAM_STATS=1: printed when the context is destroyed)
     double t_push = 0, t_wait_file = 0, t_prep_queue = 0, t_align = 0, t_gpu_span = 0;
     long pushes = 0;
-    DevBuf sort_keys, sort_tmp, tgt_sorted, frames; // Morton pre-pass: keys/values, sorted copy, split frames
-    DevBuf bpack, coarse, bbox_part, nn_misc; // MFMA engine: operands, coarse minima, frame + counters
-    DevBuf src_sort;                          // Morton order of the source rows (the loop's internal order)
+    DevBuf sort_tmp, coarse, bbox_part;       // the sorts' working memory; MFMA engine: coarse minima; bounding-box partials
+    DevBuf src_sort;                          // Morton order of the source rows (the loop's internal order; SortPlanes)
     // the rows the last registration left in cur / idx (icpmi_debug_loop_rows): their count (-1: no registration has
     // completed since), whether idx holds the last pass's matches (not after the small-cloud kernel, which keeps them in
     // registers, nor after a nearest_batch call, which reuses the buffer), whether the rows were Morton-sorted (src_sort)
@@ -263,10 +286,6 @@ struct icpmi_ctx {
     bool loop_idx_valid = false, loop_sorted = false;
 
     DevBuf grp_cnt, grp_items;                // culled engine: per target split the list of 64-row groups within reach (nn_culled.h)
-    bool nn_pruned = false;                   // the culled engine (ICPMI_SEARCH_MFMA_PRUNED; AUTO on large targets)
-    int nn_engine = ICPMI_SEARCH_EXACT_F64;   // engine prepared for the current target
-    int nn_splits = 0;
-    int nn_ms = 0;                            // component stride of the SoA sorted target
     int grp_cap = 0;                          // groups a split's list in grp_items can hold
     IcpState *d_state = nullptr;   // two of them (align_device alternates in the sharded loop)
     IcpState *h_state = nullptr;   // pinned
@@ -307,8 +326,7 @@ struct icpmi_ctx {
 
 namespace {
 
-constexpr int kFlagRing = 8;
-constexpr int kLag = 2;
+constexpr int kLag = 2; // (the rings of kFlagRing slots: ProgressRings, workspace_layout.h)
 
 int fail(icpmi_ctx *ctx, int code, const char *fmt, ...)
 {
@@ -397,13 +415,13 @@ struct StageTimer {
 // call after the stream has been synchronised
 void harvest_profile(icpmi_ctx *ctx)
 {
-    if (ctx->opt.profile && ctx->nn_engine == ICPMI_SEARCH_MFMA_BF16 && ctx->nn_misc.p) {
-        unsigned long long cnt[3] = {0, 0, 0};
-        if (hipMemcpy(cnt, (char *)ctx->nn_misc.p + 128, sizeof(cnt), hipMemcpyDeviceToHost) == hipSuccess) {
+    if (ctx->opt.profile && ctx->tgt.nn_engine == ICPMI_SEARCH_MFMA_BF16 && ctx->tgt.nn_misc.p) {
+        unsigned long long cnt[MiscBlock::kCounterBytes / sizeof(unsigned long long)] = {0, 0, 0};
+        if (hipMemcpy(cnt, ctx->tgt.counters(), sizeof(cnt), hipMemcpyDeviceToHost) == hipSuccess) {
             ctx->prof.nn_recheck_queries += (int64_t)cnt[0];
             ctx->prof.nn_fallback_queries += (int64_t)cnt[1];
             ctx->prof.nn_pruned_blocks += (int64_t)cnt[2];
-            (void)hipMemset((char *)ctx->nn_misc.p + 128, 0, sizeof(cnt));
+            (void)hipMemset(ctx->tgt.counters(), 0, sizeof(cnt));
         }
     }
     for (size_t i = 0; i < ctx->ev_used; ++i) {
@@ -474,9 +492,9 @@ int small_max_splits()
 LoopFacts target_facts(const icpmi_ctx *ctx)
 {
     LoopFacts f;
-    f.nn_engine = ctx->nn_engine;
-    f.nn_pruned = ctx->nn_pruned;
-    f.nn_splits = ctx->nn_splits;
+    f.nn_engine = ctx->tgt.nn_engine;
+    f.nn_pruned = ctx->tgt.nn_pruned;
+    f.nn_splits = ctx->tgt.nn_splits;
     f.sw_small = small_enabled();
     f.sw_small_max_splits = small_max_splits();
     return f;
@@ -508,54 +526,54 @@ int engine_for(const icpmi_ctx *ctx, int m, int n_hint)
 
 int prepare_nn(icpmi_ctx *ctx, const double *d_tgt, int m, int n_hint)
 {
-    ctx->prep_valid = false; // whatever target the buffers held: it is being replaced
+    ctx->tgt.prep_valid = false; // whatever target the buffers held: it is being replaced
     int engine = engine_for(ctx, m, n_hint);
     // the culled engine is the MFMA engine plus the box test of (row group, split) pairs in the ICP loop and in normal
     // estimation; the stand-alone 1-NN search (nearest_batch) runs over all pairs
-    ctx->nn_pruned = engine == ICPMI_SEARCH_MFMA_PRUNED;
-    if (ctx->nn_pruned) engine = ICPMI_SEARCH_MFMA_BF16;
-    ctx->nn_engine = engine;
+    ctx->tgt.nn_pruned = engine == ICPMI_SEARCH_MFMA_PRUNED;
+    if (ctx->tgt.nn_pruned) engine = ICPMI_SEARCH_MFMA_BF16;
+    ctx->tgt.nn_engine = engine;
     if (engine != ICPMI_SEARCH_MFMA_BF16) return ICPMI_OK;
     if (m >= (1 << 27)) return fail(ctx, ICPMI_ERR_ARG, "the MFMA engines take targets of fewer than 2^27 points (32-bit byte offsets into the sorted records)");
     const int splits = (m + kSplitTargets - 1) / kSplitTargets;
-    ctx->nn_splits = splits;
+    ctx->tgt.nn_splits = splits;
+    ctx->tgt.m = m;
     int rc;
     const int bblocks = std::max(1, std::min(256, (m + 255) / 256));
     size_t sort_bytes = 0;
     HIP_TRY(ctx, sort_pairs_u32(nullptr, &sort_bytes, nullptr, nullptr, nullptr, nullptr, (unsigned)m, ctx->stream));
-    if ((rc = reserve(ctx, ctx->bpack, sizeof(uint4) * kSplitTiles * 64 * (size_t)splits))) return rc;
+    if ((rc = reserve(ctx, ctx->tgt.bpack, sizeof(uint4) * kSplitTiles * 64 * (size_t)splits))) return rc;
     if ((rc = reserve(ctx, ctx->bbox_part, sizeof(double) * 6 * (size_t)bblocks))) return rc;
-    if ((rc = reserve(ctx, ctx->nn_misc, 256))) return rc;
-    if ((rc = reserve(ctx, ctx->sort_keys, sizeof(unsigned) * 4 * (size_t)m))) return rc;
+    if ((rc = reserve(ctx, ctx->tgt.nn_misc, MiscBlock::kBytes))) return rc;
+    if ((rc = reserve(ctx, ctx->tgt.sort_keys, SortPlanes(nullptr, (size_t)m).bytes))) return rc;
     if ((rc = reserve(ctx, ctx->sort_tmp, sort_bytes))) return rc;
     const int ms = (m + 63) / 64 * 64; // component stride of the SoA sorted copy
-    ctx->nn_ms = ms;
-    if ((rc = reserve(ctx, ctx->tgt_sorted, sizeof(double) * sorted_doubles(ms)))) return rc; // three planes + the records (nn_mfma.h)
-    if ((rc = reserve(ctx, ctx->frames, frames_bytes(splits)))) return rc; // split frames, then the slots' boxes
-    NnFrame *frame = (NnFrame *)ctx->nn_misc.p;
-    unsigned *keys_in = (unsigned *)ctx->sort_keys.p, *keys_out = keys_in + m, *vals_in = keys_in + 2 * (size_t)m,
-             *perm = keys_in + 3 * (size_t)m;
+    ctx->tgt.nn_ms = ms;
+    if ((rc = reserve(ctx, ctx->tgt.tgt_sorted, sizeof(double) * sorted_doubles(ms)))) return rc; // three planes + the records (nn_mfma.h)
+    if ((rc = reserve(ctx, ctx->tgt.frames, frames_bytes(splits)))) return rc; // split frames, then the slots' boxes
+    NnFrame *frame = ctx->tgt.frame();
+    const SortPlanes sp(ctx->tgt.sort_keys.p, (size_t)m);
     hipStream_t s = ctx->stream;
     Range range("icpmi:target_prepass");
     StageTimer t(ctx, ST_SETUP);
-    unsigned long long *stat3 = (unsigned long long *)((char *)ctx->nn_misc.p + 128); // the resolve's statistics words of the coming call
+    unsigned long long *stat3 = ctx->tgt.counters(); // the resolve's statistics words of the coming call
     if (m <= kBboxSingleMax)
         hipLaunchKernelGGL(k_bbox_single, dim3(1), dim3(1024), 0, s, d_tgt, m, frame, 1, stat3);
     else {
         hipLaunchKernelGGL(k_bbox_partial, dim3(bblocks), dim3(256), 0, s, d_tgt, m, (double *)ctx->bbox_part.p, 1);
         hipLaunchKernelGGL(k_bbox_final, dim3(1), dim3(64), 0, s, (const double *)ctx->bbox_part.p, bblocks, frame);
-        HIP_TRY(ctx, hipMemsetAsync(stat3, 0, 24, s));
+        HIP_TRY(ctx, hipMemsetAsync(stat3, 0, MiscBlock::kCounterBytes, s));
     }
     hipLaunchKernelGGL(k_morton_keys, dim3((m + 255) / 256), dim3(256), 0, s, d_tgt, m, (const NnFrame *)frame,
-                       keys_in, vals_in);
-    HIP_TRY(ctx, sort_pairs_u32(ctx->sort_tmp.p, &sort_bytes, keys_in, keys_out, vals_in, perm, (unsigned)m, s));
-    hipLaunchKernelGGL(k_gather_points_rec, dim3((m + 255) / 256), dim3(256), 0, s, d_tgt, (const unsigned *)perm, m, ms,
-                       (double *)ctx->tgt_sorted.p);
-    hipLaunchKernelGGL(k_split_frames, dim3(splits), dim3(256), 0, s, (const double *)ctx->tgt_sorted.p, m, ms,
-                       (SplitFrame *)ctx->frames.p);
+                       sp.keys_in, sp.vals_in);
+    HIP_TRY(ctx, sort_pairs_u32(ctx->sort_tmp.p, &sort_bytes, sp.keys_in, sp.keys_out, sp.vals_in, sp.perm, (unsigned)m, s));
+    hipLaunchKernelGGL(k_gather_points_rec, dim3((m + 255) / 256), dim3(256), 0, s, d_tgt, (const unsigned *)sp.perm, m, ms,
+                       (double *)ctx->tgt.tgt_sorted.p);
+    hipLaunchKernelGGL(k_split_frames, dim3(splits), dim3(256), 0, s, ctx->tgt.sorted(), m, ms,
+                       (SplitFrame *)ctx->tgt.frames.p);
     hipLaunchKernelGGL(k_pack_targets, dim3((splits * kSplitTiles * 64 + 255) / 256), dim3(256), 0, s,
-                       (const double *)ctx->tgt_sorted.p, m, ms, (const SplitFrame *)ctx->frames.p,
-                       (uint4 *)ctx->bpack.p, splits);
+                       ctx->tgt.sorted(), m, ms, ctx->tgt.split_frames(),
+                       (uint4 *)ctx->tgt.bpack.p, splits);
     HIP_TRY(ctx, hipGetLastError());
     return ICPMI_OK;
 }
@@ -607,82 +625,22 @@ int nn_solo_from()
     return k >= 2 ? k : 0;
 }
 
-// The per-row arrays of the bounded pass inside ctx->nn_lists (n rows), then list reuse's word per 64 rows, its packed
-// list of rows (kRowListHead words in front) and its per-pass statistics
-struct NnListRows {
-    double *ub;
-    unsigned *ent;
-    float *ubf, *sqf;
-    int *cnt;
-    RowList *xb;
-    unsigned long long *mask;
-    int *list;
-    unsigned *stat_rows;               // [kReuseStatPasses] rows listed per pass (profiling)
-    unsigned *stat_cert;               // [kReuseStatPasses] the match margin: rows certified per pass (profiling)
-    unsigned *stat_searched;           // [kReuseStatPasses] solo passes: rows the solo kernel searched for the pass (profiling)
-    RowScan *scan;                     // the match margin's per-row records, covers and word per 64 rows (RowBounds)
-    double *cover;
-    unsigned long long *cert;
-};
-constexpr size_t kNnListRowBytes = sizeof(double) + 2 * sizeof(float) + sizeof(int) + sizeof(unsigned) * kNnEntCap + sizeof(RowList);
-constexpr int kReuseStatPasses = 1024; // (passes beyond overwrite the last entry)
-size_t nn_list_bytes(int n)
-{
-    return kNnListRowBytes * (size_t)n + 64 + sizeof(unsigned long long) * (((size_t)n + 63) / 64) +
-           sizeof(int) * ((size_t)n + kRowListHead) + sizeof(unsigned) * 3 * kReuseStatPasses + 64 +
-           (sizeof(RowScan) + sizeof(double)) * (size_t)n + sizeof(unsigned long long) * (((size_t)n + 63) / 64);
-}
-NnListRows nn_list_rows(const icpmi_ctx *ctx, int n)
-{
-    NnListRows r;
-    r.ub = (double *)ctx->nn_lists.p;
-    r.ent = (unsigned *)(r.ub + n); // (8-byte aligned: read two words at a time)
-    r.ubf = (float *)(r.ent + (size_t)kNnEntCap * n);
-    r.sqf = r.ubf + n;
-    r.cnt = (int *)(r.sqf + n);
-    r.xb = (RowList *)(((uintptr_t)(r.cnt + n) + 63) & ~(uintptr_t)63);
-    r.mask = (unsigned long long *)(r.xb + n); // (RowList is 32 bytes: 8-byte aligned)
-    r.list = (int *)(r.mask + ((size_t)n + 63) / 64);
-    r.stat_rows = (unsigned *)(r.list + (size_t)n + kRowListHead);
-    r.stat_cert = r.stat_rows + kReuseStatPasses;
-    r.stat_searched = r.stat_cert + kReuseStatPasses;
-    r.scan = (RowScan *)(((uintptr_t)(r.stat_searched + kReuseStatPasses) + 63) & ~(uintptr_t)63);
-    r.cover = (double *)(r.scan + n);
-    r.cert = (unsigned long long *)(r.cover + n);
-    return r;
-}
+// (The per-row arrays of the bounded pass inside ctx->nn_lists, list reuse's words, packed list and statistics, the match
+// margin's records: BoundedRows, workspace_layout.h.)
 
-// The culled engine's group lists (nn_culled.h) inside ctx->grp_cnt / grp_items: two alternating sets of per-split counters
-// (a pass reads one and clears the other), one array of lists, and two statistics words behind the counters.
-constexpr int kGrpCntPad = 64;
+// The culled engine's group lists (nn_culled.h) inside ctx->grp_cnt / grp_items: the counters, statistics and chunk counters
+// of GroupCounters (workspace_layout.h) and one array of lists.
+GroupCounters group_counters(const icpmi_ctx *ctx) { return GroupCounters(ctx->grp_cnt.p, (size_t)ctx->tgt.nn_splits); }
 int reserve_group_lists(icpmi_ctx *ctx, int splits, long groups)
 {
     int rc;
-    const size_t per = ((size_t)splits + kGrpCntPad - 1) / kGrpCntPad * kGrpCntPad;
-    if ((rc = reserve(ctx, ctx->grp_cnt, sizeof(unsigned) * 2 * per + 2 * sizeof(unsigned long long) + 4 * sizeof(unsigned)))) return rc;
-    const long cap = (std::max<long>(groups, 1) + 1) / 2 * 2; // (even: the coarse kernel reads a wave's two entries as one 8-byte word)
-    if ((rc = reserve(ctx, ctx->grp_items, sizeof(unsigned) * (size_t)splits * (size_t)cap + 16))) return rc;
+    if ((rc = reserve(ctx, ctx->grp_cnt, GroupCounters(nullptr, (size_t)splits).bytes))) return rc;
+    const long cap = GroupCounters::items_cap(groups);
+    if ((rc = reserve(ctx, ctx->grp_items, GroupCounters::items_bytes((size_t)splits, cap)))) return rc;
     ctx->grp_cap = (int)cap;
     return ICPMI_OK;
 }
-GroupLists group_lists(const icpmi_ctx *ctx, int set)
-{
-    const size_t per = ((size_t)ctx->nn_splits + kGrpCntPad - 1) / kGrpCntPad * kGrpCntPad;
-    return GroupLists{(unsigned *)ctx->grp_cnt.p + (size_t)set * per, (unsigned *)ctx->grp_items.p, ctx->grp_cap};
-}
-unsigned long long *group_stats(const icpmi_ctx *ctx)
-{
-    const size_t per = ((size_t)ctx->nn_splits + kGrpCntPad - 1) / kGrpCntPad * kGrpCntPad;
-    return (unsigned long long *)((unsigned *)ctx->grp_cnt.p + 2 * per);
-}
-// the coarse kernel's chunk counters (nn_culled.h), one per parity of the pass: a pass hands its chunks out through its own
-// and clears the other; behind the statistics
-unsigned *group_work(const icpmi_ctx *ctx, int parity) { return (unsigned *)(group_stats(ctx) + 2) + (parity & 1); }
-size_t group_cnt_bytes(const icpmi_ctx *ctx)
-{
-    const size_t per = ((size_t)ctx->nn_splits + kGrpCntPad - 1) / kGrpCntPad * kGrpCntPad;
-    return sizeof(unsigned) * 2 * per + 2 * sizeof(unsigned long long) + 4 * sizeof(unsigned);
-}
+GroupLists group_lists(const icpmi_ctx *ctx, int set) { return GroupLists{group_counters(ctx).set[set], (unsigned *)ctx->grp_items.p, ctx->grp_cap}; }
 // workgroups of k_nn_coarse_groups (kCoarseWaves pairs each): the chip's resident set, two per CU at 4 waves per SIMD; a
 // workgroup starts on chunk blockIdx and takes its next ones from a counter (nn_culled.h)
 int coarse_groups_grid(const icpmi_ctx *ctx) { return 2 * ctx->cu_count; }
@@ -703,15 +661,15 @@ int launch_nn_mfma(icpmi_ctx *ctx, const double *d_qry, int n, int m, int *d_idx
                    const IcpState *st, const double *d_tgt = nullptr, const double *d_nrm = nullptr,
                    double *d_partials = nullptr, const NnPass &pass = NnPass{})
 {
-    const int splits = ctx->nn_splits;
+    const int splits = ctx->tgt.nn_splits;
     int rc;
-    const SplitFrame *frames = (const SplitFrame *)ctx->frames.p;
-    const unsigned *perm = (const unsigned *)ctx->sort_keys.p + 3 * (size_t)m;
-    unsigned long long *counters = (unsigned long long *)((char *)ctx->nn_misc.p + 128);
+    const SplitFrame *frames = ctx->tgt.split_frames();
+    const unsigned *perm = ctx->tgt.perm();
+    unsigned long long *counters = ctx->tgt.counters();
     Range range("icpmi:nn_search");
     StageTimer t(ctx, ST_NN);
     if (pass.bounded) {
-        const NnListRows lr = nn_list_rows(ctx, n);
+        const BoundedRows lr(ctx->nn_lists.p, (size_t)n);
         // (a lean pass of the all-pairs engine -- list_reuse.h, "lean passes" -- has no coarse launch: the rows' kept lists and
         // certificates stand, and a row that wanted a new list takes the resolve's exhaustive search)
         if (!pass.lean) {
@@ -726,23 +684,24 @@ int launch_nn_mfma(icpmi_ctx *ctx, const double *d_qry, int n, int m, int *d_idx
                 const bool full = pass.pruned_pass < 0;
                 const int parity = (full ? pass.culled_full : pass.pruned_pass) & 1;
                 const GroupLists cur = group_lists(ctx, parity), nxt = group_lists(ctx, parity ^ 1);
+                const GroupCounters gc = group_counters(ctx);
                 const long groups = (n + kGroupRows - 1) / kGroupRows;
                 if (full) ctx->prof.nn_full_culled_passes += 1;
                 hipLaunchKernelGGL((k_nn_coarse_groups<false, kCoarseWaves>), dim3(coarse_groups_grid(ctx)), dim3(kCoarseThreads),
-                                   coarse_groups_lds(splits), ctx->stream, d_qry, n, (size_t)0, (const uint4 *)ctx->bpack.p, frames, splits,
+                                   coarse_groups_lds(splits), ctx->stream, d_qry, n, (size_t)0, ctx->tgt.operands(), frames, splits,
                                    (const unsigned *)cur.items, cur.cap, (const unsigned *)cur.cnt, nxt.cnt,
-                                   ctx->opt.profile && !full ? group_stats(ctx) : (unsigned long long *)nullptr, (unsigned long long)(groups * splits),
-                                   st, kl, group_work(ctx, parity), group_work(ctx, parity ^ 1));
+                                   ctx->opt.profile && !full ? gc.stats : (unsigned long long *)nullptr, (unsigned long long)(groups * splits),
+                                   st, kl, gc.work[parity], gc.work[parity ^ 1]);
             } else {
                 // list reuse (`pass.list`): the pass runs over the packed list of the rows listed again (k_row_list) and no others
                 const int *list = pass.list ? lr.list : nullptr;
                 if (coarse_half_units(ctx->cu_count, n, splits)) {
                     constexpr int per = kCoarseQueries / kCoarseQT; // queries per workgroup with one tile per wave
                     hipLaunchKernelGGL((k_nn_coarse_bounded<1, kCoarseWaves>), dim3((n + per - 1) / per, splits), dim3(kCoarseThreads), 0,
-                                       ctx->stream, d_qry, n, (const uint4 *)ctx->bpack.p, frames, kl, st, list);
+                                       ctx->stream, d_qry, n, ctx->tgt.operands(), frames, kl, st, list);
                 } else
                     hipLaunchKernelGGL((k_nn_coarse_bounded<kCoarseQT, kCoarseWaves>), dim3((n + kCoarseQueries - 1) / kCoarseQueries, splits),
-                                       dim3(kCoarseThreads), 0, ctx->stream, d_qry, n, (const uint4 *)ctx->bpack.p, frames, kl, st, list);
+                                       dim3(kCoarseThreads), 0, ctx->stream, d_qry, n, ctx->tgt.operands(), frames, kl, st, list);
             }
             ctx->prof.nn_coarse_blocks += (int64_t)((n + kCoarseQueries - 1) / kCoarseQueries) * splits;
         }
@@ -750,7 +709,7 @@ int launch_nn_mfma(icpmi_ctx *ctx, const double *d_qry, int n, int m, int *d_idx
         // same two words, and per wave those atomics were 25 of the kernel's 55 us -- they leave per workgroup now, and
         // only when the stage profile (level 2) is asked for)
 #define ICPMI_BOUNDED_ARGS                                                                                                        \
-    d_qry, n, (const double *)ctx->tgt_sorted.p, perm, m, ctx->nn_ms, splits, frames, (const double *)lr.ub, (const int *)lr.cnt, \
+    d_qry, n, ctx->tgt.sorted(), perm, m, ctx->tgt.nn_ms, splits, frames, (const double *)lr.ub, (const int *)lr.cnt, \
         (const unsigned *)lr.ent, d_idx, ctx->opt.profile >= 2 ? counters : (unsigned long long *)nullptr, d_tgt, d_nrm, d_partials, st
         if (resolve_waves(n) == 8)
             hipLaunchKernelGGL(k_nn_resolve4_bounded<8>, dim3(resolve_blocks(n)), dim3(512), 0, ctx->stream, ICPMI_BOUNDED_ARGS);
@@ -774,19 +733,19 @@ int launch_nn_mfma(icpmi_ctx *ctx, const double *d_qry, int n, int m, int *d_idx
         if (coarse_half_units(ctx->cu_count, n, splits)) {
             constexpr int per = kCoarseQueries / kCoarseQT; // queries per workgroup with one tile per wave
             hipLaunchKernelGGL((k_nn_coarse<0, 1, kCoarseWaves>), dim3((n + per - 1) / per, splits), dim3(kCoarseThreads), 0,
-                               ctx->stream, d_qry, n, (const uint4 *)ctx->bpack.p, frames, (float2 *)ctx->coarse.p,
+                               ctx->stream, d_qry, n, ctx->tgt.operands(), frames, (float2 *)ctx->coarse.p,
                                (float *)nullptr, st);
         } else {
             hipLaunchKernelGGL((k_nn_coarse<0, kCoarseQT, kCoarseWaves>), dim3((n + kCoarseQueries - 1) / kCoarseQueries, splits),
-                               dim3(kCoarseThreads), 0, ctx->stream, d_qry, n, (const uint4 *)ctx->bpack.p, frames,
+                               dim3(kCoarseThreads), 0, ctx->stream, d_qry, n, ctx->tgt.operands(), frames,
                                (float2 *)ctx->coarse.p, (float *)nullptr, st);
         }
         ctx->prof.nn_coarse_blocks += (int64_t)((n + kCoarseQueries - 1) / kCoarseQueries) * splits;
     }
     // (the two null lists: round 3's per-block split lists -- the culled engine no longer has unbounded passes)
 #define ICPMI_RESOLVE_ARGS                                                                                            \
-    d_qry, n, (const double *)ctx->tgt_sorted.p, perm, m, ctx->nn_ms, (const float2 *)ctx->coarse.p, splits, frames,  \
-        (const NnFrame *)ctx->nn_misc.p, d_idx, d_d2, counters, d_tgt, d_nrm, d_partials, (const int *)nullptr, (const int *)nullptr, st
+    d_qry, n, ctx->tgt.sorted(), perm, m, ctx->tgt.nn_ms, (const float2 *)ctx->coarse.p, splits, frames,  \
+        ctx->tgt.frame(), d_idx, d_d2, counters, d_tgt, d_nrm, d_partials, (const int *)nullptr, (const int *)nullptr, st
     if (resolve_waves(n) == 8)
         hipLaunchKernelGGL(k_nn_resolve4<8>, dim3(resolve_blocks(n)), dim3(512), 0, ctx->stream, ICPMI_RESOLVE_ARGS);
     else
@@ -801,7 +760,7 @@ int launch_nn_mfma(icpmi_ctx *ctx, const double *d_qry, int n, int m, int *d_idx
 int launch_nn(icpmi_ctx *ctx, const double *d_qry, int n, const double *d_tgt, int m, int *d_idx,
               double *d_d2, const IcpState *st)
 {
-    if (ctx->nn_engine == ICPMI_SEARCH_MFMA_BF16) return launch_nn_mfma(ctx, d_qry, n, m, d_idx, d_d2, st);
+    if (ctx->tgt.nn_engine == ICPMI_SEARCH_MFMA_BF16) return launch_nn_mfma(ctx, d_qry, n, m, d_idx, d_d2, st);
     constexpr int QPT = 2;
     const int qblocks = (n + 256 * QPT - 1) / (256 * QPT);
     // enough workgroups to fill 256 CUs several times over; every split keeps >= 256 targets
@@ -847,11 +806,11 @@ bool knn_cull_enabled()
 }
 bool knn_culled(const icpmi_ctx *ctx)
 {
-    return ctx->nn_pruned || (knn_cull_enabled() && ctx->nn_splits > kKnnCullFromSplits && ctx->nn_splits <= kCullMaxSplits);
+    return ctx->tgt.nn_pruned || (knn_cull_enabled() && ctx->tgt.nn_splits > kKnnCullFromSplits && ctx->tgt.nn_splits <= kCullMaxSplits);
 }
 bool sorted_normal_rows(const icpmi_ctx *ctx, int k, int m)
 {
-    return ctx->nn_engine == ICPMI_SEARCH_MFMA_BF16 && (ctx->nn_pruned || knn_lists_enabled()) && k <= 32 && m >= kMfmaMinTargets;
+    return ctx->tgt.nn_engine == ICPMI_SEARCH_MFMA_BF16 && (ctx->tgt.nn_pruned || knn_lists_enabled()) && k <= 32 && m >= kMfmaMinTargets;
 }
 
 // k-NN lists of rows [row0,row1) of d_qry among the m points d_pts (kdtree.hpp:65-78): MFMA
@@ -870,12 +829,12 @@ int launch_knn(icpmi_ctx *ctx, const double *d_qry, int nq_total, const double *
     hipStream_t s = ctx->stream;
     constexpr int BLOCK = 128;
     const size_t smem = (size_t)k * BLOCK * (sizeof(double) + sizeof(int));
-    const bool mfma = ctx->nn_engine == ICPMI_SEARCH_MFMA_BF16 && k <= 32 && m >= kMfmaMinTargets;
-    const unsigned *perm = mfma ? (const unsigned *)ctx->sort_keys.p + 3 * (size_t)m : nullptr;
+    const bool mfma = ctx->tgt.nn_engine == ICPMI_SEARCH_MFMA_BF16 && k <= 32 && m >= kMfmaMinTargets;
+    const unsigned *perm = mfma ? ctx->tgt.perm() : nullptr;
     const double *qsep = d_qry == d_pts ? nullptr : d_qry; // the exact kernels read rows from d_pts unless told otherwise
     if (by_sorted_row && (!mfma || qsep)) return fail(ctx, ICPMI_ERR_ARG, "sorted-row lists need the MFMA engine's sorted target");
     if (mfma) {
-        const int splits = ctx->nn_splits, nslots = splits * kCols;
+        const int splits = ctx->tgt.nn_splits, nslots = splits * kCols;
         // bound the per-row buffer (the lists, or 2 B x nslots of slot minima) by chunking the rows: ~1 GiB
         // all-pairs engine, rows in the target's Morton order: bound first, lists instead of minima (knn_lists.h)
         // (culled -- the pruned engine, and the all-pairs engine on targets of more than a dozen splits, knn_culled(): the same
@@ -885,86 +844,79 @@ int launch_knn(icpmi_ctx *ctx, const double *d_qry, int nq_total, const double *
         // rows that are not a range of sorted positions (arbitrary queries: icpmi_k_nearest; rows by point index:
         // icpmi_estimate_normals_rows) get their place in the sorted order from their Morton key (k_knn_prebound_q)
         const bool lists_q = !by_sorted_row && knn_lists_enabled();
-        constexpr long kListRowBytes = sizeof(double) + 2 * sizeof(float) + sizeof(int) + sizeof(unsigned) * kKnnEntCap;
         constexpr long budget = 1l << 30;
-        long chunk = (budget / ((lists || lists_q) ? kListRowBytes : (long)nslots * 2)) / kCoarseQueries * kCoarseQueries; // 2 bytes per slot minimum (bf16)
+        long chunk = (budget / ((lists || lists_q) ? (long)KnnRows::kRowBytes : (long)nslots * 2)) / kCoarseQueries * kCoarseQueries; // 2 bytes per slot minimum (bf16)
         chunk = std::max<long>(kCoarseQueries, std::min<long>(chunk, ((long)rows + kCoarseQueries - 1) / kCoarseQueries * kCoarseQueries));
-        if ((rc = reserve(ctx, ctx->slotmin, (lists || lists_q) ? (size_t)kListRowBytes * chunk : sizeof(unsigned short) * (size_t)chunk * nslots))) return rc;
+        if ((rc = reserve(ctx, ctx->slotmin, (lists || lists_q) ? KnnRows(nullptr, (size_t)chunk).bytes : sizeof(unsigned short) * (size_t)chunk * nslots))) return rc;
         if ((rc = reserve(ctx, ctx->fb_list, sizeof(int) * ((size_t)rows + 16)))) return rc;
         int *fb_count = (int *)ctx->fb_list.p, *fb_list = fb_count + 16;
         // (the list forms: a chunk's first kernel, k_knn_prebound / k_knn_prebound_q, clears fb_count before the first chunk
         // and the group counters before every chunk -- knn_lists.h)
         if (!lists && !lists_q) HIP_TRY(ctx, hipMemsetAsync(fb_count, 0, sizeof(int), s));
-        const SplitFrame *frames = (const SplitFrame *)ctx->frames.p;
-        const double *sorted = (const double *)ctx->tgt_sorted.p;
+        const SplitFrame *frames = ctx->tgt.split_frames();
+        const double *sorted = ctx->tgt.sorted();
         if (lists_culled && (rc = reserve_group_lists(ctx, splits, chunk / kGroupRows))) return rc;
+        // (the list forms' rows of a chunk, and the group counters the culled one clears and counts in)
+        const KnnRows kr(ctx->slotmin.p, (size_t)chunk);
+        const KnnLists kl{kr.tf_row, kr.sqf_row, kr.cnt_row, kr.ent_row, kKnnEntCap};
+        const GroupCounters gc = group_counters(ctx);
         for (long c0 = row0; c0 < row1; c0 += chunk) {
             const int nq = (int)std::min<long>(chunk, row1 - c0);
             const int nblk = (nq + kCoarseQueries - 1) / kCoarseQueries;
             if (lists) {
-                double *t_row = (double *)ctx->slotmin.p;
-                float *tf_row = (float *)(t_row + chunk), *sqf_row = tf_row + chunk;
-                int *cnt_row = (int *)(sqf_row + chunk);
-                unsigned *ent_row = (unsigned *)(cnt_row + chunk);
-                const KnnLists kl{tf_row, sqf_row, cnt_row, ent_row, kKnnEntCap};
-                hipLaunchKernelGGL(k_knn_prebound, dim3((nq + kPreRows - 1) / kPreRows), dim3(256), 0, s, sorted, m, ctx->nn_ms, k, (int)c0, nq,
-                                   t_row, tf_row, sqf_row, cnt_row, c0 == row0 ? fb_count : (int *)nullptr,
+                hipLaunchKernelGGL(k_knn_prebound, dim3((nq + kPreRows - 1) / kPreRows), dim3(256), 0, s, sorted, m, ctx->tgt.nn_ms, k, (int)c0, nq,
+                                   kr.t_row, kr.tf_row, kr.sqf_row, kr.cnt_row, c0 == row0 ? fb_count : (int *)nullptr,
                                    lists_culled ? (unsigned *)ctx->grp_cnt.p : (unsigned *)nullptr,
-                                   lists_culled ? (int)(group_cnt_bytes(ctx) / sizeof(unsigned)) : 0);
+                                   lists_culled ? (int)(gc.bytes / sizeof(unsigned)) : 0);
                 if (lists_culled) {
                     // the groups are runs of 32 sorted rows, their bound the largest of their rows' (nn_culled.h); a wave takes two
                     const GroupLists gl = group_lists(ctx, 0);
                     const int waves = (nq + 63) / 64;
                     ctx->prof.knn_culled_launches += 1;
-                    hipLaunchKernelGGL(k_knn_group_cull, dim3((waves + 15) / 16), dim3(1024), 0, s, sorted, m, ctx->nn_ms, (int)c0, nq,
-                                       (const double *)t_row, frames, splits, gl);
+                    hipLaunchKernelGGL(k_knn_group_cull, dim3((waves + 15) / 16), dim3(1024), 0, s, sorted, m, ctx->tgt.nn_ms, (int)c0, nq,
+                                       (const double *)kr.t_row, frames, splits, gl);
                     hipLaunchKernelGGL((k_nn_coarse_groups<true, kCoarseWaves>), dim3(coarse_groups_grid(ctx)), dim3(kCoarseThreads),
-                                       coarse_groups_lds(splits), s, sorted + c0, nq, (size_t)ctx->nn_ms, (const uint4 *)ctx->bpack.p, frames,
+                                       coarse_groups_lds(splits), s, sorted + c0, nq, (size_t)ctx->tgt.nn_ms, ctx->tgt.operands(), frames,
                                        splits, (const unsigned *)gl.items, gl.cap, (const unsigned *)gl.cnt, (unsigned *)nullptr,
-                                       (unsigned long long *)nullptr, 0ull, (const IcpState *)nullptr, kl, group_work(ctx, 0),
+                                       (unsigned long long *)nullptr, 0ull, (const IcpState *)nullptr, kl, gc.work[0],
                                        (unsigned *)nullptr);
                 } else if (coarse_half_units(ctx->cu_count, nq, splits)) {
                     constexpr int per = kCoarseQueries / kCoarseQT;
                     hipLaunchKernelGGL((k_nn_coarse_rows<1, kCoarseWaves>), dim3((nq + per - 1) / per, splits), dim3(kCoarseThreads), 0,
-                                       s, sorted + c0, nq, (size_t)ctx->nn_ms, (const uint4 *)ctx->bpack.p, frames, kl);
+                                       s, sorted + c0, nq, (size_t)ctx->tgt.nn_ms, ctx->tgt.operands(), frames, kl);
                 } else
                     hipLaunchKernelGGL((k_nn_coarse_rows<kCoarseQT, kCoarseWaves>), dim3(nblk, splits), dim3(kCoarseThreads), 0, s,
-                                       sorted + c0, nq, (size_t)ctx->nn_ms, (const uint4 *)ctx->bpack.p, frames, kl);
+                                       sorted + c0, nq, (size_t)ctx->tgt.nn_ms, ctx->tgt.operands(), frames, kl);
                 hipLaunchKernelGGL(k_knn_resolve_lists<false>, dim3((nq + 3) / 4), dim3(256), 0, s, (const double *)nullptr, sorted, perm, m,
-                                   ctx->nn_ms, k, (int)c0, nq, (const double *)t_row, (const int *)cnt_row, (const unsigned *)ent_row, knn,
+                                   ctx->tgt.nn_ms, k, (int)c0, nq, (const double *)kr.t_row, (const int *)kr.cnt_row, (const unsigned *)kr.ent_row, knn,
                                    fb_list, fb_count);
             } else if (lists_q) {
-                double *t_row = (double *)ctx->slotmin.p;
-                float *tf_row = (float *)(t_row + chunk), *sqf_row = tf_row + chunk;
-                int *cnt_row = (int *)(sqf_row + chunk);
-                unsigned *ent_row = (unsigned *)(cnt_row + chunk);
-                const KnnLists kl{tf_row, sqf_row, cnt_row, ent_row, kKnnEntCap};
                 hipLaunchKernelGGL(k_knn_prebound_q, dim3((nq + 7) / 8), dim3(256), 0, s, d_qry, (int)c0, nq, sorted,
-                                   (const unsigned *)ctx->sort_keys.p + (size_t)m /* the sorted keys */, m, ctx->nn_ms, k,
-                                   (const NnFrame *)ctx->nn_misc.p, t_row, tf_row, sqf_row, cnt_row,
+                                   ctx->tgt.sorted_keys(), m, ctx->tgt.nn_ms, k,
+                                   ctx->tgt.frame(), kr.t_row, kr.tf_row, kr.sqf_row, kr.cnt_row,
                                    c0 == row0 ? fb_count : (int *)nullptr);
                 if (coarse_half_units(ctx->cu_count, nq, splits)) {
                     constexpr int per = kCoarseQueries / kCoarseQT;
                     hipLaunchKernelGGL((k_nn_coarse_bounded<1, kCoarseWaves>), dim3((nq + per - 1) / per, splits), dim3(kCoarseThreads), 0,
-                                       s, d_qry + 3 * c0, nq, (const uint4 *)ctx->bpack.p, frames, kl, (const IcpState *)nullptr);
+                                       s, d_qry + 3 * c0, nq, ctx->tgt.operands(), frames, kl, (const IcpState *)nullptr);
                 } else
                     hipLaunchKernelGGL((k_nn_coarse_bounded<kCoarseQT, kCoarseWaves>), dim3(nblk, splits), dim3(kCoarseThreads), 0, s,
-                                       d_qry + 3 * c0, nq, (const uint4 *)ctx->bpack.p, frames, kl, (const IcpState *)nullptr);
-                hipLaunchKernelGGL(k_knn_resolve_lists<true>, dim3((nq + 3) / 4), dim3(256), 0, s, d_qry, sorted, perm, m, ctx->nn_ms, k,
-                                   (int)c0, nq, (const double *)t_row, (const int *)cnt_row, (const unsigned *)ent_row, knn, fb_list,
+                                       d_qry + 3 * c0, nq, ctx->tgt.operands(), frames, kl, (const IcpState *)nullptr);
+                hipLaunchKernelGGL(k_knn_resolve_lists<true>, dim3((nq + 3) / 4), dim3(256), 0, s, d_qry, sorted, perm, m, ctx->tgt.nn_ms, k,
+                                   (int)c0, nq, (const double *)kr.t_row, (const int *)kr.cnt_row, (const unsigned *)kr.ent_row, knn, fb_list,
                                    fb_count);
             } else {
                 if (coarse_half_units(ctx->cu_count, nq, splits)) {
                     constexpr int per = kCoarseQueries / kCoarseQT;
                     hipLaunchKernelGGL((k_nn_coarse<1, 1, kCoarseWaves>), dim3((nq + per - 1) / per, splits),
-                                       dim3(kCoarseThreads), 0, s, d_qry + 3 * c0, nq, (const uint4 *)ctx->bpack.p,
+                                       dim3(kCoarseThreads), 0, s, d_qry + 3 * c0, nq, ctx->tgt.operands(),
                                        frames, (float2 *)nullptr, (float *)ctx->slotmin.p, (const IcpState *)nullptr);
                 } else
                 hipLaunchKernelGGL((k_nn_coarse<1, kCoarseQT, kCoarseWaves>), dim3(nblk, splits),
-                                   dim3(kCoarseThreads), 0, s, d_qry + 3 * c0, nq, (const uint4 *)ctx->bpack.p,
+                                   dim3(kCoarseThreads), 0, s, d_qry + 3 * c0, nq, ctx->tgt.operands(),
                                    frames, (float2 *)nullptr, (float *)ctx->slotmin.p, (const IcpState *)nullptr);
                 hipLaunchKernelGGL(k_knn_resolve<false>, dim3((nq + 3) / 4), dim3(256), 0, s, d_qry, (int)c0, nq, sorted, perm, m,
-                                   ctx->nn_ms, k, (const float *)ctx->slotmin.p, nslots, frames, (const NnFrame *)ctx->nn_misc.p, knn,
+                                   ctx->tgt.nn_ms, k, (const float *)ctx->slotmin.p, nslots, frames, ctx->tgt.frame(), knn,
                                    fb_list, fb_count, (const int *)nullptr, (const int *)nullptr);
             }
         }
@@ -998,8 +950,8 @@ int launch_normals(icpmi_ctx *ctx, const double *d_pts, int m, int k, int row0, 
     Range range("icpmi:normals");
     StageTimer t(ctx, ST_NORMALS);
     if ((rc = launch_knn(ctx, d_pts, m, d_pts, m, k, row0, row1, by_sorted_row))) return rc;
-    const bool mfma = ctx->nn_engine == ICPMI_SEARCH_MFMA_BF16 && k <= 32 && m >= kMfmaMinTargets;
-    const unsigned *perm = mfma ? (const unsigned *)ctx->sort_keys.p + 3 * (size_t)m : nullptr;
+    const bool mfma = ctx->tgt.nn_engine == ICPMI_SEARCH_MFMA_BF16 && k <= 32 && m >= kMfmaMinTargets;
+    const unsigned *perm = mfma ? ctx->tgt.perm() : nullptr;
     hipLaunchKernelGGL(k_normals_from_knn, dim3((rows + 255) / 256), dim3(256), 0, ctx->stream, d_pts, m, k, row0, row1,
                        (const int *)ctx->knn_idx.p, d_normals, by_sorted_row ? perm : (const unsigned *)nullptr,
                        (int)(by_sorted_row && scatter));
@@ -1019,7 +971,7 @@ int check_common(icpmi_ctx *ctx)
         const hipError_t e = hipStreamQuery(ctx->stream);
         if (e != hipSuccess && e != hipErrorNotReady) {
             (void)hipGetLastError();
-            ctx->prep_valid = false;
+            ctx->tgt.prep_valid = false;
             return fail(ctx, ICPMI_ERR_HIP, "the target preparation queued behind the previous icpmi_stream_push failed: %s",
                         hipGetErrorString(e));
         }
@@ -1097,40 +1049,27 @@ int exchange_allgather(icpmi_ctx *ctx, double *d_buf, size_t per)
     return ICPMI_OK;
 }
 
-// The target normals (ctx->nrm, by point) once more in the target's Morton order, for the small-cloud
+// The target normals (ctx->tgt.nrm, by point) once more in the target's Morton order, for the small-cloud
 // kernel: its slot scans then read a candidate's normal next to its coordinates.
 int sort_normals(icpmi_ctx *ctx, int m)
 {
     if (!small_target(target_facts(ctx))) return ICPMI_OK;
     int rc;
-    if ((rc = reserve(ctx, ctx->nrm_sorted, sizeof(double) * 3 * (size_t)ctx->nn_ms))) return rc;
-    hipLaunchKernelGGL(k_gather_points, dim3((m + 255) / 256), dim3(256), 0, ctx->stream, (const double *)ctx->nrm.p,
-                       (const unsigned *)ctx->sort_keys.p + 3 * (size_t)m, m, ctx->nn_ms, (double *)ctx->nrm_sorted.p);
+    if ((rc = reserve(ctx, ctx->tgt.nrm_sorted, sizeof(double) * 3 * (size_t)ctx->tgt.nn_ms))) return rc;
+    hipLaunchKernelGGL(k_gather_points, dim3((m + 255) / 256), dim3(256), 0, ctx->stream, (const double *)ctx->tgt.nrm.p,
+                       ctx->tgt.perm(), m, ctx->tgt.nn_ms, (double *)ctx->tgt.nrm_sorted.p);
     HIP_TRY(ctx, hipGetLastError());
     return ICPMI_OK;
 }
 
 // A target prepared on a helper context (prepare_target on its stream and workspace) becomes this context's:
-// the buffers that DEFINE a prepared target change hands (the helper gets this context's old ones to build the
+// what DEFINES a prepared target (PreparedTarget) changes hands (the helper gets this context's old one to build the
 // next target in), scratch stays where it is.  The caller orders this context's stream behind the helper's work.
 void adopt_target(icpmi_ctx *ctx, icpmi_ctx *h)
 {
-    std::swap(ctx->bpack, h->bpack);
-    std::swap(ctx->nn_misc, h->nn_misc);       // the target's frame (+ counters, + the voxel filter's box: scratch)
-    std::swap(ctx->sort_keys, h->sort_keys);   // holds the Morton permutation
-    std::swap(ctx->tgt_sorted, h->tgt_sorted);
-    std::swap(ctx->frames, h->frames);
-    std::swap(ctx->nrm, h->nrm);
-    std::swap(ctx->nrm_sorted, h->nrm_sorted);
-    ctx->nn_splits = h->nn_splits;
-    ctx->nn_ms = h->nn_ms;
-    ctx->nn_engine = h->nn_engine;
-    ctx->nn_pruned = h->nn_pruned;
-    ctx->prep_tgt = h->prep_tgt;
-    ctx->prep_m = h->prep_m;
-    ctx->prep_engine = h->prep_engine;
-    ctx->prep_valid = true;
-    h->prep_valid = false;
+    std::swap(ctx->tgt, h->tgt); // (the helper reads none of the scalars it is handed before its next prepare_nn rewrites them)
+    ctx->tgt.prep_valid = true;
+    h->tgt.prep_valid = false;
 }
 
 // ---- the ICP call, device pointers -----------------------------------------------------
@@ -1140,15 +1079,15 @@ void adopt_target(icpmi_ctx *ctx, icpmi_ctx *h)
 int prepare_target(icpmi_ctx *ctx, const double *d_tgt, int m, int n_hint)
 {
     int rc;
-    if ((rc = reserve(ctx, ctx->nrm, sizeof(double) * 3 * (size_t)m))) return rc;
+    if ((rc = reserve(ctx, ctx->tgt.nrm, sizeof(double) * 3 * (size_t)m))) return rc;
     if ((rc = prepare_nn(ctx, d_tgt, m, n_hint))) return rc;
     const bool sorted_rows = sorted_normal_rows(ctx, ctx->opt.normal_k, m);
-    if ((rc = launch_normals(ctx, d_tgt, m, ctx->opt.normal_k, 0, m, (double *)ctx->nrm.p, sorted_rows, true))) return rc;
+    if ((rc = launch_normals(ctx, d_tgt, m, ctx->opt.normal_k, 0, m, (double *)ctx->tgt.nrm.p, sorted_rows, true))) return rc;
     if ((rc = sort_normals(ctx, m))) return rc;
-    ctx->prep_tgt = d_tgt;
-    ctx->prep_m = m;
-    ctx->prep_engine = engine_for(ctx, m, n_hint);
-    ctx->prep_valid = true;
+    ctx->tgt.prep_tgt = d_tgt;
+    ctx->tgt.prep_m = m;
+    ctx->tgt.prep_engine = engine_for(ctx, m, n_hint);
+    ctx->tgt.prep_valid = true;
     return ICPMI_OK;
 }
 
@@ -1223,7 +1162,8 @@ struct LoopRun {
     const double *fin_rows = nullptr; // what the step kernels sum
     IcpState *hs = nullptr, *st = nullptr; // the pinned copy; of the two device buffers the one the coming kernels read
     RowBounds rb{};
-    NnListRows lr{};
+    BoundedRows lr{};
+    PartialRows pr{};
     const unsigned *src_perm = nullptr;
     int pass_no = 0;                  // coarse passes queued so far: selects the work counter (see k_nn_coarse_list)
     bool pass_list = false;           // the coming bounded pass runs over the packed list (false: over every row -- a call's first pass)
@@ -1257,11 +1197,11 @@ struct LoopRun {
         ctx->nm_valid = false;
         ctx->nm_count = 1;
         if ((rc = reserve(ctx, ctx->cur, sizeof(double) * 3 * (size_t)n))) return rc;
-        if ((rc = reserve(ctx, ctx->nrm, sizeof(double) * 3 * (size_t)m))) return rc;
+        if ((rc = reserve(ctx, ctx->tgt.nrm, sizeof(double) * 3 * (size_t)m))) return rc;
         if ((rc = reserve(ctx, ctx->idx, sizeof(int) * (size_t)n))) return rc;
         if ((rc = reserve(ctx, ctx->history, sizeof(double) * (size_t)(max_hist + 1)))) return rc;
         cur = (double *)ctx->cur.p;
-        nrm = (double *)ctx->nrm.p;
+        nrm = (double *)ctx->tgt.nrm.p;
         idx = (int *)ctx->idx.p;
         hist = (double *)ctx->history.p;
         range_call.emplace("icpmi:align");
@@ -1300,7 +1240,7 @@ struct LoopRun {
     {
         const bool sharded = ctx->comm != nullptr || ctx->cb_allreduce != nullptr;
         if (gate && sharded) return fail(ctx, ICPMI_ERR_ARG, "a context with a communicator does not run gated registrations");
-        prepared = !sharded && ctx->prep_valid && ctx->prep_tgt == d_tgt && ctx->prep_m == m && ctx->prep_engine == engine_for(ctx, m, n);
+        prepared = !sharded && ctx->tgt.prep_valid && ctx->tgt.prep_tgt == d_tgt && ctx->tgt.prep_m == m && ctx->tgt.prep_engine == engine_for(ctx, m, n);
         // (the ranks of a sharded run must agree on the engine -- it decides the order of the normal rows they gather -- so
         // there AUTO looks at the target alone, whatever this rank's share of the source)
         return prepared ? ICPMI_OK : prepare_nn(ctx, d_tgt, m, sharded ? std::max(n, kMfmaMinQueries) : n);
@@ -1329,11 +1269,10 @@ struct LoopRun {
         p = make_loop_plan(f);
         if (p.error) return fail(ctx, ICPMI_ERR_ARG, p.error, p.rblocks);
         int rc;
-        // (solo passes: a second area of group rows behind the first, then two sets of per-workgroup counts; solo_pass.h)
-        const size_t solo_bytes = p.solo_on ? sizeof(double) * kSumsStride * (size_t)p.rblocks2 + 2 * sizeof(SoloCounts) * kFinishBlocksMax : 0;
-        if ((rc = reserve(ctx, ctx->partials, sizeof(double) * kSumsStride * ((size_t)p.rblocks + (size_t)p.rblocks2) + solo_bytes))) return rc;
-        partials = (double *)ctx->partials.p;
-        fin_rows = p.sum_tree ? partials + kSumsStride * (size_t)p.rblocks : partials;
+        if ((rc = reserve(ctx, ctx->partials, PartialRows(nullptr, p.rblocks, p.rblocks2, p.solo_on).bytes))) return rc;
+        pr = PartialRows(ctx->partials.p, p.rblocks, p.rblocks2, p.solo_on);
+        partials = pr.rows;
+        fin_rows = p.sum_tree ? pr.groups[0] : partials;
         return ICPMI_OK;
     }
 
@@ -1356,7 +1295,7 @@ struct LoopRun {
             if ((rc = exchange_allgather(ctx, gathered, 3 * (size_t)per))) return rc;
             if (sorted_rows)
                 hipLaunchKernelGGL(k_scatter_rows, dim3((m + 255) / 256), dim3(256), 0, s, (const double *)gathered,
-                                   (const unsigned *)ctx->sort_keys.p + 3 * (size_t)m, m, nrm);
+                                   ctx->tgt.perm(), m, nrm);
             else
                 HIP_TRY(ctx, hipMemcpyAsync(nrm, gathered, sizeof(double) * 3 * (size_t)m,
                                             hipMemcpyDeviceToDevice, s));
@@ -1364,7 +1303,7 @@ struct LoopRun {
             if ((rc = launch_normals(ctx, d_tgt, m, ctx->opt.normal_k, 0, m, nrm, sorted_rows, true))) return rc;
             if ((rc = sort_normals(ctx, m))) return rc;
         }
-        ctx->prep_valid = false; // (the stream path prepares the next target below; nothing else relies on it)
+        ctx->tgt.prep_valid = false; // (the stream path prepares the next target below; nothing else relies on it)
         return ICPMI_OK;
     }
 
@@ -1377,21 +1316,20 @@ struct LoopRun {
         const int bblocks = std::max(1, std::min(256, (n + 255) / 256));
         if (p.sort_source) {
             HIP_TRY(ctx, sort_pairs_u32(nullptr, &sort_bytes, nullptr, nullptr, nullptr, nullptr, (unsigned)n, s));
-            if ((rc = reserve(ctx, ctx->src_sort, sizeof(unsigned) * 4 * (size_t)n))) return rc;
+            if ((rc = reserve(ctx, ctx->src_sort, SortPlanes(nullptr, (size_t)n).bytes))) return rc;
             if ((rc = reserve(ctx, ctx->sort_tmp, sort_bytes))) return rc; // the target's sort is done (stream order)
             if ((rc = reserve(ctx, ctx->bbox_part, sizeof(double) * 6 * (size_t)bblocks))) return rc;
         }
         if (p.pruned || p.cull_full) { // the group lists of the coming passes (nn_culled.h); both sets of counters start empty
-            if ((rc = reserve_group_lists(ctx, ctx->nn_splits, (n + kGroupRows - 1) / kGroupRows))) return rc;
-            HIP_TRY(ctx, hipMemsetAsync(ctx->grp_cnt.p, 0, group_cnt_bytes(ctx), s));
+            if ((rc = reserve_group_lists(ctx, ctx->tgt.nn_splits, (n + kGroupRows - 1) / kGroupRows))) return rc;
+            HIP_TRY(ctx, hipMemsetAsync(ctx->grp_cnt.p, 0, group_counters(ctx).bytes, s));
         }
         if (!p.sort_source) return ICPMI_OK;
         // (Measured and not kept: this dozen of small launches on a stream of its own beside the target's pre-pass and normals
         // -- 180 us off the call under rocprofv3, whose launch overhead starves the device at the head of a call, and nothing
         // without it: 8,567 against 8,595 iterations/s at C3.)
-        NnFrame *sframe = (NnFrame *)((char *)ctx->nn_misc.p + 64);
-        unsigned *keys_in = (unsigned *)ctx->src_sort.p, *keys_out = keys_in + n, *vals_in = keys_in + 2 * (size_t)n,
-                 *perm = keys_in + 3 * (size_t)n;
+        NnFrame *sframe = ctx->tgt.source_frame();
+        const SortPlanes sp(ctx->src_sort.p, (size_t)n);
         StageTimer t(ctx, ST_SETUP);
         if (n <= kBboxSingleMax)
             hipLaunchKernelGGL(k_bbox_single, dim3(1), dim3(1024), 0, s, d_src, n, sframe, 1, (unsigned long long *)nullptr);
@@ -1400,9 +1338,9 @@ struct LoopRun {
             hipLaunchKernelGGL(k_bbox_final, dim3(1), dim3(64), 0, s, (const double *)ctx->bbox_part.p, bblocks, sframe);
         }
         hipLaunchKernelGGL(k_morton_keys, dim3((n + 255) / 256), dim3(256), 0, s, d_src, n, (const NnFrame *)sframe,
-                           keys_in, vals_in);
-        HIP_TRY(ctx, sort_pairs_u32(ctx->sort_tmp.p, &sort_bytes, keys_in, keys_out, vals_in, perm, (unsigned)n, s));
-        src_perm = perm;
+                           sp.keys_in, sp.vals_in);
+        HIP_TRY(ctx, sort_pairs_u32(ctx->sort_tmp.p, &sort_bytes, sp.keys_in, sp.keys_out, sp.vals_in, sp.perm, (unsigned)n, s));
+        src_perm = sp.perm;
         return ICPMI_OK;
     }
 
@@ -1411,8 +1349,8 @@ struct LoopRun {
     {
         int rc;
         if (p.bounded) {
-            if ((rc = reserve(ctx, ctx->nn_lists, nn_list_bytes(n)))) return rc;
-            lr = nn_list_rows(ctx, n);
+            if ((rc = reserve(ctx, ctx->nn_lists, BoundedRows(nullptr, (size_t)n).bytes))) return rc;
+            lr = BoundedRows(ctx->nn_lists.p, (size_t)n);
             rb = RowBounds{d_tgt, idx, m, lr.ub, lr.ubf, lr.sqf, lr.cnt};
             if (p.reuse) {
                 rb.xb = lr.xb;
@@ -1428,10 +1366,10 @@ struct LoopRun {
             StageTimer t(ctx, ST_TRANSFORM);
             hipLaunchKernelGGL(k_transform, dim3(std::min(2048, (n + 255) / 256)), dim3(256), 0, s, d_src, cur, n, st, 1, 0, src_perm);
             if (p.bounded) // the first pass's incumbents and bounds (and, culled engine and culled full passes, its group lists: set 0)
-                hipLaunchKernelGGL(k_nn_prebound1, dim3((n + kPreThreads - 1) / kPreThreads), dim3(kPreThreads), 0, s, (const double *)cur, n, (const double *)ctx->tgt_sorted.p,
-                                   (const unsigned *)ctx->sort_keys.p + (size_t)m /* the sorted keys */,
-                                   (const unsigned *)ctx->sort_keys.p + 3 * (size_t)m, m, ctx->nn_ms, (const NnFrame *)ctx->nn_misc.p, idx, rb,
-                                   (const SplitFrame *)ctx->frames.p, ctx->nn_splits,
+                hipLaunchKernelGGL(k_nn_prebound1, dim3((n + kPreThreads - 1) / kPreThreads), dim3(kPreThreads), 0, s, (const double *)cur, n, ctx->tgt.sorted(),
+                                   ctx->tgt.sorted_keys(),
+                                   ctx->tgt.perm(), m, ctx->tgt.nn_ms, ctx->tgt.frame(), idx, rb,
+                                   ctx->tgt.split_frames(), ctx->tgt.nn_splits,
                                    p.pruned || p.cull_full ? group_lists(ctx, 0) : GroupLists{nullptr, nullptr, 0});
         }
         return ICPMI_OK;
@@ -1455,14 +1393,14 @@ struct LoopRun {
             Range range("icpmi:nn_search");
             StageTimer t(ctx, ST_NN);
             launch_by_rule(gate, k_icp_small, k_icp_small_gated, k_icp_small_robust, dim3(p.rblocks), dim3(kSmallThreads), s,
-                           small_first ? d_src : (const double *)cur, cur, n, (const IcpState *)st, small_first ? 1 : 0, (const uint4 *)ctx->bpack.p,
-                           (const SplitFrame *)ctx->frames.p, ctx->nn_splits, (const double *)ctx->tgt_sorted.p, (const double *)ctx->nrm_sorted.p,
-                           (const unsigned *)ctx->sort_keys.p + 3 * (size_t)m, m, ctx->nn_ms, d_tgt, (const double *)nrm, partials,
-                           (unsigned long long *)((char *)ctx->nn_misc.p + 128));
+                           small_first ? d_src : (const double *)cur, cur, n, (const IcpState *)st, small_first ? 1 : 0, ctx->tgt.operands(),
+                           ctx->tgt.split_frames(), ctx->tgt.nn_splits, ctx->tgt.sorted(), (const double *)ctx->tgt.nrm_sorted.p,
+                           ctx->tgt.perm(), m, ctx->tgt.nn_ms, d_tgt, (const double *)nrm, partials,
+                           ctx->tgt.counters());
             small_first = false;
             ctx->prof.nn_pairs += (double)n * (double)m;
             ctx->prof.small_launches += 1;
-            ctx->prof.nn_coarse_blocks += (int64_t)((n + kCoarseQueries - 1) / kCoarseQueries) * ctx->nn_splits; // the units the general path would run
+            ctx->prof.nn_coarse_blocks += (int64_t)((n + kCoarseQueries - 1) / kCoarseQueries) * ctx->tgt.nn_splits; // the units the general path would run
         }
         Range range("icpmi:reduce_solve");
         StageTimer t(ctx, ST_REDUCE);
@@ -1492,24 +1430,19 @@ struct LoopRun {
     }
     // the group rows this pass's tail sums, and the solo kernel's own arguments: what it writes for the coming pass and, in a
     // pass that is itself fed by one, the counts it publishes in k_sum_groups' stead (also k_publish_counts' arguments)
-    const double *pass_fin_rows() const { return solo_fed ? solo_groups(solo_area) : fin_rows; }
-    double *solo_groups(int area) const { return partials + kSumsStride * ((size_t)p.rblocks + (size_t)area * p.rblocks2); }
-    SoloCounts *solo_counts(int parity) const
-    {
-        return (SoloCounts *)(partials + kSumsStride * ((size_t)p.rblocks + 2 * (size_t)p.rblocks2)) + (size_t)(parity & 1) * kFinishBlocksMax;
-    }
+    const double *pass_fin_rows() const { return solo_fed ? pr.groups[solo_area] : fin_rows; }
     SoloPass solo_args() const
     {
         const int here = pass_no - 1, at = std::min(here, kReuseStatPasses - 1); // (this pass, from 0)
         const int out_area = solo_fed ? 1 - solo_area : 1;
-        SoloPass sp{(const double *)ctx->tgt_sorted.p, (const unsigned *)ctx->sort_keys.p + 3 * (size_t)m, ctx->nn_ms, ctx->nn_splits,
-                    (const SplitFrame *)ctx->frames.p, (const double *)nrm, idx, solo_groups(out_area), solo_counts(here + 1),
+        SoloPass sp{ctx->tgt.sorted(), ctx->tgt.perm(), ctx->tgt.nn_ms, ctx->tgt.nn_splits,
+                    ctx->tgt.split_frames(), (const double *)nrm, idx, pr.groups[out_area], pr.counts[(here + 1) & 1],
                     nullptr, 0, nullptr, nullptr, 0u, n, nullptr, nullptr, nullptr};
         if (solo_fed) {
-            sp.counts_in = solo_counts(here);
+            sp.counts_in = pr.counts[here & 1];
             sp.blocks_in = p.fin_blocks;
-            sp.want = ctx->d_want + here % kFlagRing;
-            sp.uncert = ctx->d_want + kFlagRing + here % kFlagRing;
+            sp.want = ctx->d_want + ProgressRings::wanted(here % kFlagRing);
+            sp.uncert = ctx->d_want + ProgressRings::uncertified(here % kFlagRing);
             sp.ticket = (unsigned)(here + 1);
             if (ctx->opt.profile) sp.stat_rows = lr.stat_rows + at, sp.stat_cert = lr.stat_cert + at, sp.stat_searched = lr.stat_searched + at;
         }
@@ -1546,15 +1479,15 @@ struct LoopRun {
         } else if (p.sum_tree && p.lean_on) { // (+ the workgroup that counts the rows this pass wanted listed; pass_no - 1: this pass, from 0)
             const int here = pass_no - 1, at = std::min(here, kReuseStatPasses - 1);
             const bool stats = lean_cur && ctx->opt.profile;
-            const WantPublish wp{ctx->d_want + here % kFlagRing, (unsigned)(here + 1), n, here == 0, (const unsigned long long *)lr.mask,
+            const WantPublish wp{ctx->d_want + ProgressRings::wanted(here % kFlagRing), (unsigned)(here + 1), n, here == 0, (const unsigned long long *)lr.mask,
                                  p.margin ? (const unsigned long long *)lr.cert : nullptr, stats ? lr.stat_rows + at : nullptr,
                                  stats && p.margin ? lr.stat_cert + at : nullptr,
-                                 p.solo_on ? ctx->d_want + kFlagRing + here % kFlagRing : nullptr};
+                                 p.solo_on ? ctx->d_want + ProgressRings::uncertified(here % kFlagRing) : nullptr};
             hipLaunchKernelGGL(k_sum_groups, dim3((p.rblocks2 + 7) / 8 + 1), dim3(256), 0, s, (const double *)partials, p.rblocks,
-                               partials + kSumsStride * (size_t)p.rblocks, (const IcpState *)st, wp);
+                               pr.groups[0], (const IcpState *)st, wp);
         } else if (p.sum_tree)
             hipLaunchKernelGGL(k_sum_groups, dim3((p.rblocks2 + 7) / 8), dim3(256), 0, s, (const double *)partials, p.rblocks,
-                               partials + kSumsStride * (size_t)p.rblocks, (const IcpState *)st, WantPublish{});
+                               pr.groups[0], (const IcpState *)st, WantPublish{});
     }
 
     // ... the final sum, the exchange of a sharded run, the step and the rows' move (with their bounds, RowBounds, and the culled
@@ -1562,8 +1495,8 @@ struct LoopRun {
     int pass_step_and_move(int final_pass, int *progress, int ticket)
     {
         const bool step_moves = fuse_step(p, n, final_pass), finish_moves = fuse_finish(p, n, final_pass);
-        const SplitFrame *frames = (const SplitFrame *)ctx->frames.p;
-        const int splits = ctx->nn_splits;
+        const SplitFrame *frames = ctx->tgt.split_frames();
+        const int splits = ctx->tgt.nn_splits;
         IcpState *other = st == ctx->d_state ? ctx->d_state + 1 : ctx->d_state; // (the fused kernels write the other state buffer)
         if (p.sharded) {
             int rc;
@@ -1634,7 +1567,7 @@ struct LoopRun {
             StageTimer t(ctx, ST_TRANSFORM);
             if (p.pruned) // (ICPMI_FUSE_FINISH=0 only: + the rows' bounds and the group lists of the coming pass, set pass_no & 1)
                 hipLaunchKernelGGL(k_transform_cull, dim3((n + 255) / 256), dim3(256), 0, s, (const double *)cur, (const unsigned *)nullptr,
-                                   cur, n, (const IcpState *)st, 0, 1, rb, (const SplitFrame *)ctx->frames.p, ctx->nn_splits, group_lists(ctx, pass_no & 1));
+                                   cur, n, (const IcpState *)st, 0, 1, rb, ctx->tgt.split_frames(), ctx->tgt.nn_splits, group_lists(ctx, pass_no & 1));
             else
                 hipLaunchKernelGGL(k_transform, dim3(std::min(2048, (n + 255) / 256)), dim3(256), 0, s,
                                    cur, cur, n, st, 0, 1, (const unsigned *)nullptr, rb);
@@ -1644,7 +1577,7 @@ struct LoopRun {
         if (solo_cur) lean_nxt = true; // (nothing of the coming pass but its tail is launched)
         if (p.cull_full && pass_no == 1 && !final_pass && !lean_nxt)
             hipLaunchKernelGGL(k_row_group_cull, dim3(((n + 63) / 64 + 15) / 16), dim3(1024), 0, s, (const double *)cur, n, (const float *)lr.ubf,
-                               (const SplitFrame *)ctx->frames.p, ctx->nn_splits, group_lists(ctx, 1), (const IcpState *)st);
+                               ctx->tgt.split_frames(), ctx->tgt.nn_splits, group_lists(ctx, 1), (const IcpState *)st);
         if (pass_list && !lean_nxt) // the rows just moved left their "listed again" words: the coming pass's list of rows
             hipLaunchKernelGGL(k_row_list, dim3(((n + 63) / 64 + kRowListThreads - 1) / kRowListThreads), dim3(kRowListThreads), 0, s,
                                (const unsigned long long *)lr.mask, n, lr.list, (const IcpState *)st,
@@ -1665,7 +1598,8 @@ struct LoopRun {
         int rc;
         range_loop.emplace("icpmi:icp_loop");
         t_loop.emplace(ctx, ST_LOOP);
-        for (int i = 0; i < kFlagRing; ++i) ctx->h_flags[i] = 0, ctx->h_want[i] = 0ull, ctx->h_want[kFlagRing + i] = 0ull;
+        for (int i = 0; i < ProgressRings::kProgressWords; ++i) ctx->h_flags[i] = 0;
+        for (int i = 0; i < ProgressRings::kCountWords; ++i) ctx->h_want[i] = 0ull;
         bool after_first_done = after_first == nullptr;
         for (int it = 0; it < cfg->max_iterations; ++it) {
             if (it >= kLag && !after_first_done) {
@@ -1687,12 +1621,12 @@ struct LoopRun {
                     // the rows that iteration's pass wanted listed: its k_sum_groups ran in front of the kernel whose progress word
                     // has just been read, so the word is there or on its way (the same bounded spin)
                     unsigned long long w;
-                    if ((rc = await_word(ctx, &ctx->h_want[slot], want, [](unsigned long long x) { return (int)(x >> 32); },
+                    if ((rc = await_word(ctx, &ctx->h_want[ProgressRings::wanted(slot)], want, [](unsigned long long x) { return (int)(x >> 32); },
                                          "device row count word never arrived", &w)))
                         return rc;
                     want_known.push_back((unsigned)(w & 0xFFFFFFFFull));
                     if (p.solo_on) { // ... and the rows it did not find certified, published with it
-                        if ((rc = await_word(ctx, &ctx->h_want[kFlagRing + slot], want, [](unsigned long long x) { return (int)(x >> 32); },
+                        if ((rc = await_word(ctx, &ctx->h_want[ProgressRings::uncertified(slot)], want, [](unsigned long long x) { return (int)(x >> 32); },
                                              "device row count word never arrived", &w)))
                             return rc;
                         uncert_known.push_back((unsigned)(w & 0xFFFFFFFFull));
@@ -1731,13 +1665,13 @@ struct LoopRun {
         // profiling: the resolve's counters come back behind the same wait, and the events are read when somebody asks
         // for the profile (icpmi_get_profile) -- a blocking copy and a dozen hipEventElapsedTime calls inside every
         // call were ~0.1 ms of host time in a 9 ms C3 call, charged to the very thing they measure
-        counters_back = ctx->opt.profile && ctx->nn_engine == ICPMI_SEARCH_MFMA_BF16 && ctx->nn_misc.p;
+        counters_back = ctx->opt.profile && ctx->tgt.nn_engine == ICPMI_SEARCH_MFMA_BF16 && ctx->tgt.nn_misc.p;
         if (counters_back) {
-            HIP_TRY(ctx, hipMemcpyAsync(ctx->h_cnt, (char *)ctx->nn_misc.p + 128, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-            HIP_TRY(ctx, hipMemsetAsync((char *)ctx->nn_misc.p + 128, 0, 3 * sizeof(unsigned long long), s));
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->h_cnt, ctx->tgt.counters(), MiscBlock::kCounterBytes, hipMemcpyDeviceToHost, s));
+            HIP_TRY(ctx, hipMemsetAsync(ctx->tgt.counters(), 0, MiscBlock::kCounterBytes, s));
             ctx->h_cnt[3] = ctx->h_cnt[4] = 0;
             if (p.pruned) // (row group, split) pairs run / of all passes: cleared with the counters at the head of the next call
-                HIP_TRY(ctx, hipMemcpyAsync(ctx->h_cnt + 3, group_stats(ctx), 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+                HIP_TRY(ctx, hipMemcpyAsync(ctx->h_cnt + 3, group_counters(ctx).stats, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
         }
         // ... and so do list reuse's per-pass statistics (the arrays lie one behind the other: one copy into pinned memory,
         // where a blocking copy after the wait cost the caller some 15 us)
@@ -1788,7 +1722,7 @@ struct LoopRun {
             // searched, and a pass none of which ran is a skipped coarse launch
             const int np = stat_passes;
             const unsigned *stat = ctx->h_stat;
-            const int per = coarse_half_units(ctx->cu_count, n, ctx->nn_splits) ? kCoarseQueries / kCoarseQT : kCoarseQueries;
+            const int per = coarse_half_units(ctx->cu_count, n, ctx->tgt.nn_splits) ? kCoarseQueries / kCoarseQT : kCoarseQueries;
             ctx->reuse_rows.assign(stat, stat + np);
             ctx->reuse_rows[0] = (unsigned)n;
             ctx->reuse_blocks.resize((size_t)np);
@@ -1979,8 +1913,8 @@ int voxel_downsample_device(icpmi_ctx *ctx, const double *d_pts, int n, double v
         *n_out = n;
         return ICPMI_OK;
     }
-    // (the box sits at offset 192 of nn_misc: offset 0 is the search's own frame of the target)
-    const VoxelScratch vs{&ctx->bbox_part, &ctx->nn_misc, &ctx->vox_keys, &ctx->vox_vals, &ctx->sort_tmp, 192};
+    // (the box has a place of its own in nn_misc: offset 0 is the search's own frame of the target)
+    const VoxelScratch vs{&ctx->bbox_part, &ctx->tgt.nn_misc, &ctx->vox_keys, &ctx->vox_vals, &ctx->sort_tmp, MiscBlock::kVoxelBox};
     const char *msg = "";
     const int rc = voxel_filter_core(s, vs, d_pts, n, voxel, d_out, out_cap, n_out, finish, &msg);
     return rc == ICPMI_OK ? rc : fail(ctx, rc, "%s", msg);
@@ -2150,13 +2084,13 @@ int icpmi_create(const icpmi_options *opt, icpmi_ctx **out)
     if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) return bail("hipStreamCreate");
     if (hipMalloc((void **)&ctx->d_state, 2 * sizeof(IcpState)) != hipSuccess) return bail("hipMalloc state");
     if (hipHostMalloc((void **)&ctx->h_state, sizeof(IcpState), hipHostMallocDefault) != hipSuccess) return bail("hipHostMalloc");
-    if (hipHostMalloc((void **)&ctx->h_flags, sizeof(int32_t) * kFlagRing, hipHostMallocMapped) != hipSuccess) return bail("hipHostMalloc");
+    if (hipHostMalloc((void **)&ctx->h_flags, sizeof(int32_t) * ProgressRings::kProgressWords, hipHostMallocMapped) != hipSuccess) return bail("hipHostMalloc");
     if (hipHostMalloc((void **)&ctx->h_grid, 4 * sizeof(unsigned), hipHostMallocDefault) != hipSuccess) return bail("hipHostMalloc");
     if (hipHostMalloc((void **)&ctx->h_cnt, 8 * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess) return bail("hipHostMalloc");
-    if (hipHostMalloc((void **)&ctx->h_want, sizeof(unsigned long long) * 2 * kFlagRing, hipHostMallocMapped) != hipSuccess) return bail("hipHostMalloc");
+    if (hipHostMalloc((void **)&ctx->h_want, sizeof(unsigned long long) * ProgressRings::kCountWords, hipHostMallocMapped) != hipSuccess) return bail("hipHostMalloc");
     if (hipHostMalloc((void **)&ctx->h_stat, sizeof(unsigned) * 3 * kReuseStatPasses, hipHostMallocDefault) != hipSuccess) return bail("hipHostMalloc");
-    memset(ctx->h_flags, 0, sizeof(int32_t) * kFlagRing);
-    memset(ctx->h_want, 0, sizeof(unsigned long long) * 2 * kFlagRing);
+    memset(ctx->h_flags, 0, sizeof(int32_t) * ProgressRings::kProgressWords);
+    memset(ctx->h_want, 0, sizeof(unsigned long long) * ProgressRings::kCountWords);
     if (hipHostGetDevicePointer((void **)&ctx->d_flags, ctx->h_flags, 0) != hipSuccess) return bail("hipHostGetDevicePointer");
     if (hipHostGetDevicePointer((void **)&ctx->d_want, ctx->h_want, 0) != hipSuccess) return bail("hipHostGetDevicePointer");
     *out = ctx;
@@ -2215,10 +2149,10 @@ void icpmi_destroy(icpmi_ctx *ctx)
     }
     ctx->helpers.clear();
     if (ctx->comm && ctx->rccl.CommDestroy) ctx->rccl.CommDestroy(ctx->comm);
-    for (DevBuf *b : {&ctx->cur, &ctx->nrm, &ctx->idx, &ctx->part_d2, &ctx->part_idx, &ctx->partials,
+    for (DevBuf *b : {&ctx->cur, &ctx->tgt.nrm, &ctx->idx, &ctx->part_d2, &ctx->part_idx, &ctx->partials,
                       &ctx->history, &ctx->stage_a, &ctx->stage_b, &ctx->stage_c, &ctx->d2out, &ctx->src_sort, &ctx->grp_cnt, &ctx->grp_items,
-                      &ctx->bpack, &ctx->coarse, &ctx->bbox_part, &ctx->nn_misc, &ctx->knn_idx, &ctx->slotmin, &ctx->nn_lists, &ctx->nrm_sorted,
-                      &ctx->src_nrm, &ctx->fb_list, &ctx->sort_keys, &ctx->sort_tmp, &ctx->tgt_sorted, &ctx->frames, &ctx->vox_keys,
+                      &ctx->tgt.bpack, &ctx->coarse, &ctx->bbox_part, &ctx->tgt.nn_misc, &ctx->knn_idx, &ctx->slotmin, &ctx->nn_lists, &ctx->tgt.nrm_sorted,
+                      &ctx->src_nrm, &ctx->fb_list, &ctx->tgt.sort_keys, &ctx->sort_tmp, &ctx->tgt.tgt_sorted, &ctx->tgt.frames, &ctx->vox_keys,
                       &ctx->vox_vals, &ctx->vox_out, &ctx->stream_prev, &ctx->stream_cur, &ctx->f32_stage, &ctx->deskew_raw, &ctx->deskew_times, &ctx->grid_set,
                       &ctx->grid_in, &ctx->grid_out, &ctx->grid_cnt, &ctx->world})
         release(*b);
@@ -2551,13 +2485,13 @@ int icpmi_estimate_normals(icpmi_ctx *ctx, const double *points_xyz, int64_t n, 
     if (k < 1 || k > 64) return fail(ctx, ICPMI_ERR_ARG, "k %d outside [1,64]", k);
     const int m = (int)n;
     if ((rc = reserve(ctx, ctx->stage_c, sizeof(double) * 3 * (size_t)m))) return rc;
-    if ((rc = reserve(ctx, ctx->nrm, sizeof(double) * 3 * (size_t)m))) return rc;
+    if ((rc = reserve(ctx, ctx->tgt.nrm, sizeof(double) * 3 * (size_t)m))) return rc;
     hipStream_t s = ctx->stream;
     HIP_TRY(ctx, hipMemcpyAsync(ctx->stage_c.p, points_xyz, sizeof(double) * 3 * (size_t)m, hipMemcpyHostToDevice, s));
     if ((rc = prepare_nn(ctx, (const double *)ctx->stage_c.p, m, m))) return rc;
     const bool sorted_rows = sorted_normal_rows(ctx, k, m);
-    if ((rc = launch_normals(ctx, (const double *)ctx->stage_c.p, m, k, 0, m, (double *)ctx->nrm.p, sorted_rows, true))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(normals_xyz, ctx->nrm.p, sizeof(double) * 3 * (size_t)m, hipMemcpyDeviceToHost, s));
+    if ((rc = launch_normals(ctx, (const double *)ctx->stage_c.p, m, k, 0, m, (double *)ctx->tgt.nrm.p, sorted_rows, true))) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(normals_xyz, ctx->tgt.nrm.p, sizeof(double) * 3 * (size_t)m, hipMemcpyDeviceToHost, s));
     HIP_TRY(ctx, hipStreamSynchronize(s));
     harvest_profile(ctx);
     return ICPMI_OK;
@@ -2941,17 +2875,17 @@ int icpmi_estimate_normals_rows(icpmi_ctx *ctx, const double *points_xyz, int64_
     if (row1 == row0) return ICPMI_OK;
     const int m = (int)n, rows = (int)(row1 - row0);
     if ((rc = reserve(ctx, ctx->stage_c, sizeof(double) * 3 * (size_t)m))) return rc;
-    if ((rc = reserve(ctx, ctx->nrm, sizeof(double) * 3 * (size_t)m))) return rc;
+    if ((rc = reserve(ctx, ctx->tgt.nrm, sizeof(double) * 3 * (size_t)m))) return rc;
     hipStream_t s = ctx->stream;
     HIP_TRY(ctx, hipMemcpyAsync(ctx->stage_c.p, points_xyz, sizeof(double) * 3 * (size_t)m, hipMemcpyHostToDevice, s));
     // a slice is always taken in point order (what a rank of a caller-sharded job wants back)
-    const bool keep_pruned = ctx->nn_pruned;
+    const bool keep_pruned = ctx->tgt.nn_pruned;
     if ((rc = prepare_nn(ctx, (const double *)ctx->stage_c.p, m, m))) return rc;
-    ctx->nn_pruned = false;
-    rc = launch_normals(ctx, (const double *)ctx->stage_c.p, m, k, (int)row0, (int)row1, (double *)ctx->nrm.p, false, true);
-    ctx->nn_pruned = keep_pruned;
+    ctx->tgt.nn_pruned = false;
+    rc = launch_normals(ctx, (const double *)ctx->stage_c.p, m, k, (int)row0, (int)row1, (double *)ctx->tgt.nrm.p, false, true);
+    ctx->tgt.nn_pruned = keep_pruned;
     if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(normals_xyz, (const double *)ctx->nrm.p + 3 * (size_t)row0, sizeof(double) * 3 * (size_t)rows,
+    HIP_TRY(ctx, hipMemcpyAsync(normals_xyz, (const double *)ctx->tgt.nrm.p + 3 * (size_t)row0, sizeof(double) * 3 * (size_t)rows,
                                 hipMemcpyDeviceToHost, s));
     HIP_TRY(ctx, hipStreamSynchronize(s));
     harvest_profile(ctx);
@@ -2963,8 +2897,8 @@ int icpmi_stream_reset(icpmi_ctx *ctx)
 {
     if (!ctx) return ICPMI_ERR_NULL;
     ctx->stream_prev_n = -1;
-    ctx->prep_valid = false;
-    if (ctx->prep_helper) ctx->prep_helper->prep_valid = false; // (a preparation still in flight is waited for by the next push)
+    ctx->tgt.prep_valid = false;
+    if (ctx->prep_helper) ctx->prep_helper->tgt.prep_valid = false; // (a preparation still in flight is waited for by the next push)
     return ICPMI_OK;
 }
 
@@ -3055,7 +2989,7 @@ int stream_register(icpmi_ctx *ctx, int64_t n_cur, int64_t min_points, const icp
         const int r = prepare_target(h, (const double *)c->stream_cur.p, (int)c->stream_cur_n, (int)c->stream_cur_n);
         c->helper_busy = true; // (whatever was queued reads the scan: somebody has to wait for it before the scan's buffer is reused)
         if (r != ICPMI_OK || hipEventRecord(c->prep_done, h->stream) != hipSuccess) {
-            h->prep_valid = false;
+            h->tgt.prep_valid = false;
             (void)hipStreamSynchronize(h->stream);
             c->helper_busy = false;
             return ICPMI_ERR_HIP;
@@ -3063,8 +2997,8 @@ int stream_register(icpmi_ctx *ctx, int64_t n_cur, int64_t min_points, const icp
         return ICPMI_OK;
     };
     // the target of THIS registration: prepared by the helper during the previous push?  Adopt it.
-    if (helper && helper->prep_valid && ctx->stream_prev_n > 0 && helper->prep_tgt == (const double *)ctx->stream_prev.p &&
-        helper->prep_m == (int)ctx->stream_prev_n) {
+    if (helper && helper->tgt.prep_valid && ctx->stream_prev_n > 0 && helper->tgt.prep_tgt == (const double *)ctx->stream_prev.p &&
+        helper->tgt.prep_m == (int)ctx->stream_prev_n) {
         HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->prep_done, 0));
         adopt_target(ctx, helper);
         ctx->helper_busy = false; // (this push's registration runs behind it, and the push waits for the registration)
@@ -3073,7 +3007,7 @@ int stream_register(icpmi_ctx *ctx, int64_t n_cur, int64_t min_points, const icp
         // scan buffer of this stream -- wait for it before anything is queued that could write there
         HIP_TRY(ctx, hipEventSynchronize(ctx->prep_done));
         ctx->helper_busy = false;
-        if (helper) helper->prep_valid = false;
+        if (helper) helper->tgt.prep_valid = false;
     }
     bool queued_next = false;
     if (ctx->stream_prev_n < 0) {
@@ -3107,7 +3041,7 @@ int stream_register(icpmi_ctx *ctx, int64_t n_cur, int64_t min_points, const icp
             if (ctx->helper_busy) {
                 (void)hipEventSynchronize(ctx->prep_done);
                 ctx->helper_busy = false;
-                if (helper) helper->prep_valid = false;
+                if (helper) helper->tgt.prep_valid = false;
             }
             return rc;
         }
@@ -3757,8 +3691,9 @@ extern "C" int icpmi_debug_loop_rows(icpmi_ctx *ctx, int32_t *idx_out, double *c
     else if (hipMemcpy(idx_out, ctx->idx.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
         return ICPMI_ERR_HIP;
     if (hipMemcpy(cur_out, ctx->cur.p, (size_t)n * 24, hipMemcpyDeviceToHost) != hipSuccess) return ICPMI_ERR_HIP;
-    if (ctx->loop_sorted && ctx->src_sort.p && ctx->src_sort.cap >= (size_t)n * 16) {
-        if (hipMemcpy(perm_out, (const unsigned *)ctx->src_sort.p + 3 * (size_t)n, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess) return ICPMI_ERR_HIP;
+    const SortPlanes sp(ctx->src_sort.p, (size_t)n);
+    if (ctx->loop_sorted && ctx->src_sort.p && ctx->src_sort.cap >= sp.bytes) {
+        if (hipMemcpy(perm_out, sp.perm, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess) return ICPMI_ERR_HIP;
     } else {
         for (int64_t i = 0; i < n; ++i) perm_out[i] = (uint32_t)i;
     }
@@ -6549,7 +6484,7 @@ const double *lmap_points(const icpmi_local_map *m) { return (const double *)m->
 void lmap_forget_target(icpmi_local_map *m)
 {
     icpmi_ctx *ctx = m->ctx;
-    if (ctx->prep_tgt == (const double *)m->d_pts[0].p || ctx->prep_tgt == (const double *)m->d_pts[1].p) ctx->prep_valid = false;
+    if (ctx->tgt.prep_tgt == (const double *)m->d_pts[0].p || ctx->tgt.prep_tgt == (const double *)m->d_pts[1].p) ctx->tgt.prep_valid = false;
 }
 
 // d_scan: n rows in device memory (null with n == 0)
@@ -6616,7 +6551,7 @@ int lmap_add(icpmi_local_map *m, const double *d_scan, int64_t n64, const double
         const std::string keep = ctx->err;
         if (prepare_target(ctx, lmap_points(m), (int)total, (int)n) != ICPMI_OK) {
             ctx->err = keep;
-            ctx->prep_valid = false;
+            ctx->tgt.prep_valid = false;
         }
         ctx->trailing_work = true;
     }

@@ -22,12 +22,13 @@
 #include "device_math.h"
 #include "list_reuse.h"
 #include "loop_plan.h"
+#include "workspace_layout.h"
 
 namespace icpmi {
 
 constexpr int kWave = 64;
 constexpr int kNumSums = 29;       // 21 JtJ (upper, row by row) + 6 Jtb + sum b^2 + count
-constexpr int kSumsStride = 32;
+// (kSumsStride = 32, the doubles a partial row is stored in: workspace_layout.h)
 // Sharded runs all-reduce one more word: sums[kDoneSlot] = 1 on a rank whose loop has ended.
 // Small integers add exactly in any order, so every rank reads the same count whatever the
 // collective's algorithm: the hosts stop queueing iterations on that agreed count alone.
@@ -578,15 +579,7 @@ __global__ __launch_bounds__(64) void k_step(IcpState *st, double *history, int 
 // zeros too, so nothing is ever cleared); k_row_list below packs the set bits' rows, in ascending order, into the list
 // k_nn_coarse_bounded takes its rows from (nn_mfma.h, RowsListed).  A row that keeps its list is not in it, and costs the
 // coarse pass nothing.
-constexpr int kNnEntCap = 8;   // list words per row of the bounded 1-NN pass (nn_mfma.h, nn_bounded.h)
-struct RowList {
-    double x, y, z; // where the row's list was built
-    double r;       // its listing radius R_b (NaN: the list is not to be kept, e.g. a call's first pass)
-};
-struct RowScan {
-    double x, y, z; // where the resolve last scanned the row's listed slots
-    double g;       // every target but that scan's winner is at least g away from there (NaN: nothing is known)
-};
+// (kNnEntCap = 8 list words per row, and the records RowList and RowScan: workspace_layout.h)
 struct RowBounds {
     const double *tgt; // the target, caller's order
     const int *idx;    // the rows' matches of the pass just finished
@@ -766,7 +759,7 @@ constexpr int kRowBatch = 2;
 // C3 at 30 steps 1.11x the parent's rate against 1.43x in this form, and 0.82x against 1.22x at 100 steps (same box,
 // alternating; profiles/row_list/).
 constexpr int kRowListThreads = 256;
-constexpr int kRowListHead = 16; // (the rows start on a 64-byte line)
+// (kRowListHead = 16 words in front of the list, so that the rows start on a 64-byte line: workspace_layout.h)
 // Profiling (`rows_count` non-null): the first workgroup stores the number of rows listed, and with the match margin
 // (`cert_count` non-null) it also counts the set bits of the rows' "certified" words (RowBounds::cert) and stores their
 // number -- plain stores, no atomics (a count per wave in the kernel that moves the rows was 1,563 atomics on one word).

@@ -85,9 +85,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-struct NnFrame {     // bounding box of the whole target (Morton quantisation)
-    double lo[3], hi[3];
-};
+// (NnFrame, the bounding box of the whole target for the Morton quantisation: workspace_layout.h)
 // The Morton-sorted copy of the target is stored SoA -- x[0..m), y[0..m), z[0..m) with the
 // component stride `ms` (m rounded up to 64) -- so that a run of consecutive sorted positions
 // is read as three fully coalesced streams.
@@ -505,7 +503,7 @@ __device__ __forceinline__ float tag_low5(float x, unsigned tag)
 
 // MODE 2's output: per row a count and up to `cap` words (split << 17 | half << 16 | mask of the 16 columns
 // split*32 + half*16 + bit whose minimum is under the threshold); rows are numbered from the launch's first row.
-constexpr int kKnnEntCap = 32;
+// (kKnnEntCap = 32 words per row of normal estimation's lists: workspace_layout.h)
 struct KnnLists {
     const float *thr; // [rows] the row's distance bound, fp32 rounded up
     const float *sq;  // [rows] its square root, rounded up

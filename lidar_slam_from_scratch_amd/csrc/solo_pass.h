@@ -33,9 +33,7 @@ constexpr int kSoloStride = kSoloCols + 1;      // doubles per staged row (5: th
 static_assert(kSoloPhases * kSoloCols == 28, "whole phases");
 static_assert(kResolveWW * kResolveQ == 64 && kSumGroup == kSoloWaves, "a wave's rows are a partial row's, a workgroup's a group row's");
 
-struct SoloCounts {
-    unsigned want, uncert, searched, pad; // of one workgroup's rows: listed again, not certified, searched by the solo kernel
-};
+// (SoloCounts, one workgroup's counts: workspace_layout.h)
 
 struct SoloPass {
     // the target's search structure, for rows this kernel has to search itself (k_nn_resolve_bounded's arguments)
