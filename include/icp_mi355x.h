@@ -317,12 +317,18 @@ int icpmi_align_robust_batch(icpmi_ctx *ctx, int32_t count, const double *const 
  * Path: at every size a stand-alone search on the context's engine, then the plane-to-plane sums, the gated step and the
  * rows' move; the source's normals cost one 20-NN pass over the source per call, in front of the target's preparation,
  * and a target the context had remembered is forgotten by such a call.
+ * Form (bit 0 of `reserved`, ICPMI_GICP_FORM_SMALL; the other bits are ignored): with it, a call whose sizes the small-cloud
+ * kernel takes -- a source of at most 32,768 rows, a target within its 8 splits of 2,048 points on the bf16 MFMA engine, no
+ * communicator -- runs each pass's search, rows and sums in ONE kernel, as icpmi_align_gated does at those sizes; at other
+ * sizes the bit has no effect.  The rows are the ones above, word for word; they are ADDED in the small-cloud kernel's
+ * order, not the general path's, so the two forms agree to rounding, not to bits.  0 is the general path at every size.
  * info (may be NULL): pairs = rows kept by the pass that produced final_error, rows = n_src. */
 #define ICPMI_GICP_EPSILON_DEFAULT 1e-3
+#define ICPMI_GICP_FORM_SMALL 1
 typedef struct {
     double epsilon;                /* the covariance along the normal, relative to 1 in the plane; finite, 0 < epsilon <= 1 */
     double max_distance;           /* the gate, metres; 0: none */
-    int64_t reserved;
+    int64_t reserved;              /* bit 0: ICPMI_GICP_FORM_SMALL; 0: the general path */
 } icpmi_gicp;
 typedef struct {
     int64_t pairs;
@@ -334,6 +340,12 @@ int icpmi_align_gicp(icpmi_ctx *ctx, const double *source_xyz, int64_t n_src, co
 int icpmi_align_gicp_device(icpmi_ctx *ctx, const double *d_source_xyz, int64_t n_src, const double *d_target_xyz,
                             int64_t n_tgt, const icpmi_config *cfg, const icpmi_gicp *rule, icpmi_result *result,
                             icpmi_gicp_info *info, double *error_history, int32_t history_cap);
+/* icpmi_align_batch with a rule per problem (rules: `count` entries, each with its own form; infos: `count` entries or
+ * NULL): every result is bit-identical to the same icpmi_align_gicp call made alone. */
+int icpmi_align_gicp_batch(icpmi_ctx *ctx, int32_t count, const double *const *sources_xyz, const int64_t *n_src,
+                           const double *const *targets_xyz, const int64_t *n_tgt, const icpmi_config *cfgs,
+                           const icpmi_gicp *rules, icpmi_result *results, icpmi_gicp_info *infos,
+                           double *error_history, int32_t history_stride, int32_t *status);
 
 /* The normal equations of the pass that produced final_error of the last registration this context ran: what the
  * registration minimised, at its result.  Costs nothing: the sums come back with the result behind the call's one wait,
@@ -1150,6 +1162,14 @@ int icpmi_map_static_labels(icpmi_map *map, int64_t frame, uint8_t *labels, int6
  *                             Anything else: ICPMI_ERR_ARG.
  *   icpmi_loop_last_weights   the weight sum of each of the last detect's results' last pass, in result order, as
  *                             icpmi_loop_last_pairs returns the pairs; each is -1 when that detect ran without weights.
+ *   icpmi_loop_set_gicp       epsilon with 0 < epsilon <= 1 (0: off, as at creation; not in the reference): detect's
+ *                             verifications are plane-to-plane registrations (icpmi_align_gicp with
+ *                             ICPMI_GICP_FORM_SMALL and max_distance = the loop's gate, 0 for none); icp_fitness is then
+ *                             that call's error, in metres.  Composes with icpmi_loop_set_gate and the yaw guess;
+ *                             exclusive with icpmi_loop_set_robust: whichever setter would turn both on returns
+ *                             ICPMI_ERR_ARG and leaves the state as it was.  While it is on icpmi_loop_last_pairs
+ *                             reports the kept rows, gate or not, and icpmi_loop_set_information keeps working with
+ *                             weight = pairs.  Takes effect at the next detect.  Anything else: ICPMI_ERR_ARG.
  *   icpmi_loop_set_information   sigma finite and > 0 with floors 0 or finite and > 0 (sigma 0: off, as at creation, the
  *                             floors ignored; not in the reference): detect keeps, per result, the information matrix
  *                             icpmi_information_from_icp makes of that verification's own normal matrix
@@ -1189,6 +1209,7 @@ int icpmi_loop_set_gate(icpmi_loop *loop, double max_distance);
 int icpmi_loop_last_pairs(const icpmi_loop *loop, int64_t *pairs, int64_t cap, int64_t *n_out);
 int icpmi_loop_set_robust(icpmi_loop *loop, int32_t kind, double scale);
 int icpmi_loop_last_weights(const icpmi_loop *loop, double *weights, int64_t cap, int64_t *n_out);
+int icpmi_loop_set_gicp(icpmi_loop *loop, double epsilon);
 int icpmi_loop_set_information(icpmi_loop *loop, double sigma, double floor_rotation_sigma, double floor_translation_sigma);
 int icpmi_loop_last_information(const icpmi_loop *loop, double *info, int64_t cap, int64_t *n_out);
 

@@ -498,9 +498,12 @@ inline std::vector<RobustICPResult> align_robust_batch(Context &ctx, const Point
 // point-to-point ICP.  icpmi_align_gicp in icp_mi355x.h has the contract; final_error and the history read in metres.
 // pairs: the rows kept by the pass that produced final_error, of `rows`.  (No overload in the Eigen adapter, as for
 // the gate: the adapter mirrors the reference's call shapes only.)
+// small_form (ICPMI_GICP_FORM_SMALL): at the sizes the small-cloud kernel takes, a pass is one kernel; the result agrees
+// with the general path's to rounding, not to bits.  Off: the general path at every size.
 struct GicpRule {
     double epsilon = ICPMI_GICP_EPSILON_DEFAULT;
     double max_distance = 0.0;
+    bool small_form = false;
 };
 struct GicpICPResult : ICPResult {
     long long pairs = 0;
@@ -514,6 +517,7 @@ inline GicpICPResult align_gicp(Context &ctx, const double *source_xyz, std::siz
     icpmi_gicp g{};
     g.epsilon = rule.epsilon;
     g.max_distance = rule.max_distance;
+    g.reserved = rule.small_form ? ICPMI_GICP_FORM_SMALL : 0;
     icpmi_gicp_info info{};
     std::vector<double> hist(static_cast<std::size_t>(config.max_iterations > 0 ? config.max_iterations : 0) + 1);
     icpmi_result r;
@@ -530,6 +534,49 @@ inline GicpICPResult align_gicp(const PointCloud &source, const PointCloud &targ
                                 const ICPConfig &config = ICPConfig())
 {
     return align_gicp(default_context(), source.data(), source.size(), target.data(), target.size(), rule, config);
+}
+
+// icp_point_to_plane_batch under one rule for every problem (icpmi_align_gicp_batch): each result is that of align_gicp
+// alone.
+inline std::vector<GicpICPResult> align_gicp_batch(Context &ctx, const PointCloud &source,
+                                                   const std::vector<const PointCloud *> &targets, const GicpRule &rule,
+                                                   const ICPConfig &config,
+                                                   const std::vector<Transformation> &initial_transforms = {})
+{
+    const std::size_t k = targets.size();
+    std::vector<GicpICPResult> out(k);
+    if (k == 0) return out;
+    if (!initial_transforms.empty() && initial_transforms.size() != k)
+        throw IcpError(ICPMI_ERR_ARG, "as many initial transforms as targets, or none");
+    std::vector<const double *> sp(k, source.data()), tp(k);
+    std::vector<int64_t> ns(k, static_cast<int64_t>(source.size())), nt(k);
+    for (std::size_t i = 0; i < k; ++i) {
+        tp[i] = targets[i]->data();
+        nt[i] = static_cast<int64_t>(targets[i]->size());
+    }
+    std::vector<icpmi_config> cfgs(k, detail::to_c(config));
+    for (std::size_t i = 0; i < initial_transforms.size(); ++i)
+        for (int e = 0; e < 16; ++e) cfgs[i].initial_transform[e] = initial_transforms[i].matrix()[static_cast<std::size_t>(e)];
+    icpmi_gicp g{};
+    g.epsilon = rule.epsilon;
+    g.max_distance = rule.max_distance;
+    g.reserved = rule.small_form ? ICPMI_GICP_FORM_SMALL : 0;
+    std::vector<icpmi_gicp> rules(k, g);
+    std::vector<icpmi_gicp_info> infos(k);
+    const std::size_t stride = static_cast<std::size_t>(config.max_iterations > 0 ? config.max_iterations : 0) + 1;
+    std::vector<double> hist(k * stride);
+    std::vector<icpmi_result> res(k);
+    std::vector<int32_t> status(k);
+    const int rc = icpmi_align_gicp_batch(ctx.get(), static_cast<int32_t>(k), sp.data(), ns.data(), tp.data(), nt.data(),
+                                          cfgs.data(), rules.data(), res.data(), infos.data(), hist.data(),
+                                          static_cast<int32_t>(stride), status.data());
+    if (rc != ICPMI_OK) throw IcpError(rc, icpmi_last_error(ctx.get()));
+    for (std::size_t i = 0; i < k; ++i) {
+        detail::fill(out[i], res[i], hist.data() + i * stride);
+        out[i].pairs = infos[i].pairs;
+        out[i].rows = infos[i].rows;
+    }
+    return out;
 }
 
 // Same call shape as slam::icp_point_to_plane (icp.hpp:157-161).
@@ -940,6 +987,10 @@ struct LoopClosureConfig { // loop_closure.hpp:14-19
     // against icp_fitness_threshold.  0: the reference's behaviour.
     int robust_kind = 0;
     double robust_scale = 0.0;
+    // Not in the reference: 0 < epsilon <= 1 runs the verifications as plane-to-plane registrations in their small form
+    // (align_gicp with GicpRule::small_form), behind the gate above if that is set too; `pairs` is then reported, gate or
+    // not.  Not together with robust_kind (ICPMI_ERR_ARG).  0: the reference's behaviour.
+    double gicp_epsilon = 0.0;
     // Not in the reference: > 0 attaches to each result the information matrix of its edge, information_from_icp on that
     // verification's own normal matrix with this sigma and these floors -- what PoseGraph::addLoopClosureInformation takes.
     double information_sigma = 0.0;
@@ -950,7 +1001,7 @@ struct LoopClosureResult { // loop_closure.hpp:25-31
     Transformation transform;
     double scan_context_distance = 0.0, icp_fitness = 0.0;
     int sector_shift = -1; // the shift the verification started from (-1: yaw_guess off)
-    long long pairs = -1;  // the rows the verification's last pass kept (-1: no correspondence-distance gate)
+    long long pairs = -1;  // the rows the verification's last pass kept (-1: neither a correspondence-distance gate nor gicp_epsilon)
     double weight_sum = -1.0; // that pass's weight sum (-1: no robust weights)
     bool has_information = false; // information_sigma was set: `information` is the edge's 6 x 6 information matrix
     Matrix6 information{};
@@ -1031,7 +1082,18 @@ public:
             std::vector<ICPResult> rs; // :109
             std::vector<long long> kept(take, -1);
             std::vector<double> weight(take, -1.0);
-            if (config_.robust_kind != 0) {
+            if (config_.gicp_epsilon != 0.0) {
+                if (config_.robust_kind != 0) throw IcpError(ICPMI_ERR_ARG, "gicp_epsilon and robust_kind exclude each other");
+                GicpRule rule;
+                rule.epsilon = config_.gicp_epsilon;
+                rule.max_distance = gated ? config_.max_correspondence_distance : 0.0;
+                rule.small_form = true;
+                const std::vector<GicpICPResult> gs = align_gicp_batch(*ctx_, clouds_[q], tg, rule, icp, starts);
+                for (std::size_t i = 0; i < take; ++i) {
+                    rs.push_back(gs[i]);
+                    kept[i] = gs[i].pairs;
+                }
+            } else if (config_.robust_kind != 0) {
                 RobustRule rule;
                 rule.kind = config_.robust_kind;
                 rule.scale = config_.robust_scale;
@@ -1785,12 +1847,18 @@ public:
         c.sc_distance_threshold = config.sc_distance_threshold;
         c.icp_fitness_threshold = config.icp_fitness_threshold;
         check(icpmi_loop_create(map.get(), &c, &l_));
-        if (config.yaw_guess) check(icpmi_loop_set_yaw_guess(l_, 1));
-        if (config.max_correspondence_distance > 0.0) check(icpmi_loop_set_gate(l_, config.max_correspondence_distance));
-        if (config.robust_kind != 0) check(icpmi_loop_set_robust(l_, config.robust_kind, config.robust_scale));
-        if (config.information_sigma > 0.0)
-            check(icpmi_loop_set_information(l_, config.information_sigma, config.information_floor_rotation,
-                                             config.information_floor_translation));
+        try {
+            if (config.yaw_guess) check(icpmi_loop_set_yaw_guess(l_, 1));
+            if (config.max_correspondence_distance > 0.0) check(icpmi_loop_set_gate(l_, config.max_correspondence_distance));
+            if (config.robust_kind != 0) check(icpmi_loop_set_robust(l_, config.robust_kind, config.robust_scale));
+            if (config.gicp_epsilon != 0.0) check(icpmi_loop_set_gicp(l_, config.gicp_epsilon));
+            if (config.information_sigma > 0.0)
+                check(icpmi_loop_set_information(l_, config.information_sigma, config.information_floor_rotation,
+                                                 config.information_floor_translation));
+        } catch (...) { // (a setter refused: no destructor will run for this object)
+            icpmi_loop_destroy(l_);
+            throw;
+        }
     }
     ~StoreLoopClosureDetector() { icpmi_loop_destroy(l_); }
     StoreLoopClosureDetector(const StoreLoopClosureDetector &) = delete;
@@ -1821,7 +1889,7 @@ public:
         int64_t ns = 0;
         check(icpmi_loop_last_shifts(l_, shifts.data(), n, &ns)); // -1 each with the guess off
         std::vector<int64_t> kept(static_cast<std::size_t>(std::max<int64_t>(n, 1)), -1);
-        check(icpmi_loop_last_pairs(l_, kept.data(), n, &ns)); // -1 each with the gate off
+        check(icpmi_loop_last_pairs(l_, kept.data(), n, &ns)); // -1 each with the gate and plane-to-plane off
         std::vector<double> weight(static_cast<std::size_t>(std::max<int64_t>(n, 1)), -1.0);
         check(icpmi_loop_last_weights(l_, weight.data(), n, &ns)); // -1 each with the weights off
         std::vector<double> infos(36 * static_cast<std::size_t>(std::max<int64_t>(n, 1)));

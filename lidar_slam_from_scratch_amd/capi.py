@@ -53,7 +53,7 @@ EXPORTS = [
     "icpmi_pose_graph_marginals", "icpmi_pose_graph_relative_covariance", "icpmi_pose_graph_closure_distance",
     "icpmi_information_from_icp", "icpmi_last_normal_matrix", "icpmi_loop_set_information", "icpmi_loop_last_information",
     "icpmi_deskew_config_default", "icpmi_deskew", "icpmi_deskew_device", "icpmi_deskew_twist", "icpmi_stream_set_deskew",
-    "icpmi_align_gicp", "icpmi_align_gicp_device",
+    "icpmi_align_gicp", "icpmi_align_gicp_device", "icpmi_align_gicp_batch", "icpmi_loop_set_gicp",
     "icpmi_map_world_static", "icpmi_map_finish_static", "icpmi_map_static_labels",
 ]
 
@@ -110,11 +110,13 @@ def as_robust(rule):
 
 
 GICP_EPSILON_DEFAULT = 1e-3                 # ICPMI_GICP_EPSILON_DEFAULT
+GICP_FORM_SMALL = 1                         # ICPMI_GICP_FORM_SMALL, bit 0 of Gicp.reserved
 
 
 class Gicp(C.Structure):
     """icpmi_gicp: the rule of align_gicp* (plane-to-plane ICP): epsilon, the covariance along a row's normal relative to
-    1 in its plane (1: point-to-point), and the optional correspondence-distance gate (max_distance; 0: none)"""
+    1 in its plane (1: point-to-point), the optional correspondence-distance gate (max_distance; 0: none) and the form
+    (reserved: GICP_FORM_SMALL -- one kernel per pass at the small-cloud kernel's sizes -- or 0, the general path)"""
     _fields_ = [("epsilon", C.c_double), ("max_distance", C.c_double), ("reserved", C.c_int64)]
 
 
@@ -124,12 +126,14 @@ class GicpInfo(C.Structure):
 
 
 def as_gicp(rule):
-    """a Gicp, or (epsilon,) or (epsilon, max_distance) -> Gicp"""
+    """a Gicp, or (epsilon[, max_distance[, small]]) -> Gicp (small: the small form where the sizes allow it,
+    GICP_FORM_SMALL; default: the general path)"""
     if isinstance(rule, Gicp):
         return rule
     g = Gicp()
     g.epsilon = float(rule[0])
     g.max_distance = float(rule[1]) if len(rule) > 1 else 0.0
+    g.reserved = GICP_FORM_SMALL if len(rule) > 2 and rule[2] else 0
     return g
 
 
@@ -403,6 +407,10 @@ def load_library(path=None):
                                    C.POINTER(Result), C.POINTER(GicpInfo), dp, C.c_int32]
     L.icpmi_align_gicp_device.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, C.POINTER(Config), C.POINTER(Gicp),
                                           C.POINTER(Result), C.POINTER(GicpInfo), dp, C.c_int32]
+    L.icpmi_align_gicp_batch.argtypes = [vp, C.c_int32, C.POINTER(dp), C.POINTER(C.c_int64), C.POINTER(dp), C.POINTER(C.c_int64),
+                                         C.POINTER(Config), C.POINTER(Gicp), C.POINTER(Result), C.POINTER(GicpInfo), dp,
+                                         C.c_int32, C.POINTER(C.c_int32)]
+    L.icpmi_loop_set_gicp.argtypes = [vp, C.c_double]
     L.icpmi_stream_set_robust.argtypes = [vp, C.POINTER(Robust)]
     L.icpmi_stream_last_robust.argtypes = [vp, C.POINTER(RobustInfo)]
     L.icpmi_nearest_batch.argtypes = [vp, dp, C.c_int64, dp, C.c_int64, C.POINTER(C.c_int32), dp]
@@ -814,6 +822,15 @@ class Context:
         """align_batch under row weights (icpmi_align_robust_batch) -> [(Result, error history, RobustInfo), ...], each
         bit-identical to align_robust() of the same pair.  rules: one for all (a Robust or a tuple), or a list, one per
         pair."""
+        return self._align_rule_batch(self._lib.icpmi_align_robust_batch, Robust, RobustInfo, as_robust, sources, targets, cfgs, rules)
+
+    def align_gicp_batch(self, sources, targets, cfgs, rules):
+        """align_batch with the plane-to-plane cost (icpmi_align_gicp_batch) -> [(Result, error history, GicpInfo), ...],
+        each bit-identical to align_gicp() of the same pair.  rules: one for all (a Gicp or a tuple, see as_gicp), or a
+        list, one per pair, each with its own form."""
+        return self._align_rule_batch(self._lib.icpmi_align_gicp_batch, Gicp, GicpInfo, as_gicp, sources, targets, cfgs, rules)
+
+    def _align_rule_batch(self, entry, Rule, Info, as_rule, sources, targets, cfgs, rules):
         srcs, tgts = [_f64(a) for a in sources], [_f64(a) for a in targets]
         k = len(srcs)
         if k != len(tgts) or k < 1:
@@ -821,25 +838,24 @@ class Context:
         cfg_list = list(cfgs) if isinstance(cfgs, (list, tuple)) else [cfgs] * k
         rule_list = list(rules) if isinstance(rules, list) else [rules] * k
         cfg_arr = (Config * k)(*cfg_list)
-        rule_arr = (Robust * k)()
+        rule_arr = (Rule * k)()
         for i, rule in enumerate(rule_list):
-            C.memmove(C.byref(rule_arr[i]), C.byref(as_robust(rule)), C.sizeof(Robust))
+            C.memmove(C.byref(rule_arr[i]), C.byref(as_rule(rule)), C.sizeof(Rule))
         stride = max(c.max_iterations for c in cfg_list) + 1
         hist = np.zeros((k, stride))
-        res, infos = (Result * k)(), (RobustInfo * k)()
+        res, infos = (Result * k)(), (Info * k)()
         status = (C.c_int32 * k)()
         dpp = C.POINTER(C.c_double)
         sp = (dpp * k)(*[_dp(a) for a in srcs])
         tp = (dpp * k)(*[_dp(a) for a in tgts])
         ns = (C.c_int64 * k)(*[a.shape[0] for a in srcs])
         nt = (C.c_int64 * k)(*[a.shape[0] for a in tgts])
-        self._check(self._lib.icpmi_align_robust_batch(self._h, k, sp, ns, tp, nt, cfg_arr, rule_arr, res, infos, _dp(hist),
-                                                       stride, status))
+        self._check(entry(self._h, k, sp, ns, tp, nt, cfg_arr, rule_arr, res, infos, _dp(hist), stride, status))
         out = []
         for i in range(k):
-            r, inf = Result(), RobustInfo()
+            r, inf = Result(), Info()
             C.memmove(C.byref(r), C.byref(res[i]), C.sizeof(Result))
-            C.memmove(C.byref(inf), C.byref(infos[i]), C.sizeof(RobustInfo))
+            C.memmove(C.byref(inf), C.byref(infos[i]), C.sizeof(Info))
             out.append((r, hist[i, :r.history_len].copy(), inf))
         return out
 

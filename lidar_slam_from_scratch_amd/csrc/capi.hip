@@ -1106,6 +1106,8 @@ struct GateRun {
     // gate), over the source's normals that align_device estimates first; the step kernel and the outputs are the gate's.
     bool gicp = false;
     double c = 0.0, kappa = 0.0; // 1 - epsilon, 2 * epsilon
+    // ICPMI_GICP_FORM_SMALL: at the small-cloud kernel's sizes (LoopFacts::gicp_small) the passes run k_icp_small_gicp
+    bool gicp_small = false;
 };
 static_assert(kRobustHuber == ICPMI_ROBUST_HUBER && kRobustGemanMcClure == ICPMI_ROBUST_GEMAN_MCCLURE, "the kernels' kinds are the header's");
 
@@ -1121,8 +1123,9 @@ void launch_by_rule(const GateRun *gate, void (*plain)(PA...), void (*gated)(GA.
     case kRuleRobust: hipLaunchKernelGGL(robust, grid, block, 0, s, common..., gate->g2, (int)gate->kind, gate->ks); break;
     case kRuleGate: hipLaunchKernelGGL(gated, grid, block, 0, s, common..., gate->g2); break;
     case kRuleNone: hipLaunchKernelGGL(plain, grid, block, 0, s, common...); break;
-    // (no member of these triples: LoopRun::pass_sums launches k_reduce_gicp itself, and make_loop_plan refuses -- LoopPlan::error,
-    // the call fails in settle_plan -- every plane-to-plane plan that would come here)
+    // (no member of these triples: LoopRun::pass_sums launches k_reduce_gicp and LoopRun::queue_pass_small k_icp_small_gicp
+    // themselves, and make_loop_plan refuses -- LoopPlan::error, the call fails in settle_plan -- every other plane-to-plane
+    // plan that would come here)
     case kRuleGicp: break;
     }
 }
@@ -1256,6 +1259,7 @@ struct LoopRun {
         f.normal_k = ctx->opt.normal_k;
         f.comm = ctx->comm != nullptr || ctx->cb_allreduce != nullptr;
         f.rule = rule_of(gate);
+        f.gicp_small = gate && gate->gicp && gate->gicp_small;
         f.profile = ctx->opt.profile;
         f.sw_bounded = nn_bounded_enabled();
         f.sw_reuse = nn_reuse_enabled();
@@ -1392,11 +1396,18 @@ struct LoopRun {
         {
             Range range("icpmi:nn_search");
             StageTimer t(ctx, ST_NN);
-            launch_by_rule(gate, k_icp_small, k_icp_small_gated, k_icp_small_robust, dim3(p.rblocks), dim3(kSmallThreads), s,
-                           small_first ? d_src : (const double *)cur, cur, n, (const IcpState *)st, small_first ? 1 : 0, ctx->tgt.operands(),
-                           ctx->tgt.split_frames(), ctx->tgt.nn_splits, ctx->tgt.sorted(), (const double *)ctx->tgt.nrm_sorted.p,
-                           ctx->tgt.perm(), m, ctx->tgt.nn_ms, d_tgt, (const double *)nrm, partials,
-                           ctx->tgt.counters());
+            if (p.rule == kRuleGicp) // (the gated kernel's arguments, then the source's normals and the rule's two words)
+                hipLaunchKernelGGL(k_icp_small_gicp, dim3(p.rblocks), dim3(kSmallThreads), 0, s,
+                                   small_first ? d_src : (const double *)cur, cur, n, (const IcpState *)st, small_first ? 1 : 0, ctx->tgt.operands(),
+                                   ctx->tgt.split_frames(), ctx->tgt.nn_splits, ctx->tgt.sorted(), (const double *)ctx->tgt.nrm_sorted.p,
+                                   ctx->tgt.perm(), m, ctx->tgt.nn_ms, d_tgt, (const double *)nrm, partials,
+                                   ctx->tgt.counters(), gate->g2, (const double *)ctx->src_nrm.p, gate->c, gate->kappa);
+            else
+                launch_by_rule(gate, k_icp_small, k_icp_small_gated, k_icp_small_robust, dim3(p.rblocks), dim3(kSmallThreads), s,
+                               small_first ? d_src : (const double *)cur, cur, n, (const IcpState *)st, small_first ? 1 : 0, ctx->tgt.operands(),
+                               ctx->tgt.split_frames(), ctx->tgt.nn_splits, ctx->tgt.sorted(), (const double *)ctx->tgt.nrm_sorted.p,
+                               ctx->tgt.perm(), m, ctx->tgt.nn_ms, d_tgt, (const double *)nrm, partials,
+                               ctx->tgt.counters());
             small_first = false;
             ctx->prof.nn_pairs += (double)n * (double)m;
             ctx->prof.small_launches += 1;
@@ -1792,7 +1803,7 @@ struct LoopRun {
 // and otherwise the unfused general path -- search (launch_nn), k_reduce_gated, k_finish_step_gated, k_transform -- on
 // whichever engine prepare_nn chose: no fused resolve, no culling, no bounds, no list reuse, no sorted rows.
 // A plane-to-plane registration (GateRun::gicp) runs that general path at every size, with k_reduce_gicp for the sums,
-// behind the source's normals (LoopRun::source_normals).
+// behind the source's normals (LoopRun::source_normals); with GateRun::gicp_small it runs k_icp_small_gicp in the small regime.
 // `before_wait`, `after_first` (may be null): see LoopRun::results_back and LoopRun::queue_loop.
 int align_device(icpmi_ctx *ctx, const double *d_src, int64_t n_src64, const double *d_tgt,
                  int64_t n_tgt64, const icpmi_config *cfg, icpmi_result *result,
@@ -2225,6 +2236,7 @@ int validate_gicp(icpmi_ctx *ctx, const icpmi_gicp *rule, GateRun *run)
     run->gicp = true;
     run->c = 1.0 - rule->epsilon;
     run->kappa = 2.0 * rule->epsilon;
+    run->gicp_small = (rule->reserved & ICPMI_GICP_FORM_SMALL) != 0;
     return ICPMI_OK;
 }
 
@@ -2413,6 +2425,19 @@ int icpmi_align_gicp(icpmi_ctx *ctx, const double *source_xyz, int64_t n_src, co
                      double *error_history, int32_t history_cap)
 {
     return align_entry(ctx, false, source_xyz, n_src, target_xyz, n_tgt, cfg, kRuleGicp, rule, info, result, error_history, history_cap);
+}
+
+int icpmi_align_gicp_batch(icpmi_ctx *ctx, int32_t count, const double *const *sources_xyz, const int64_t *n_src,
+                           const double *const *targets_xyz, const int64_t *n_tgt, const icpmi_config *cfgs,
+                           const icpmi_gicp *rules, icpmi_result *results, icpmi_gicp_info *infos,
+                           double *error_history, int32_t history_stride, int32_t *status)
+{
+    int rc;
+    if ((rc = batch_check(ctx, count, sources_xyz && n_src && targets_xyz && n_tgt && cfgs && rules && results && error_history && status))) return rc;
+    return batch_run(ctx, count, [&](icpmi_ctx *c, int k) {
+        return icpmi_align_gicp(c, sources_xyz[k], n_src[k], targets_xyz[k], n_tgt[k], &cfgs[k], &rules[k], &results[k],
+                                infos ? &infos[k] : nullptr, error_history + (size_t)k * (size_t)history_stride, history_stride);
+    }, status);
 }
 
 int icpmi_align_robust_batch(icpmi_ctx *ctx, int32_t count, const double *const *sources_xyz, const int64_t *n_src,
@@ -6035,6 +6060,7 @@ struct icpmi_loop {
     double gate = 0.0;                   // icpmi_loop_set_gate (0: off)
     std::vector<int64_t> last_pairs;     // per result of the last detect its kept rows (-1: the gate was off)
     int32_t robust_kind = 0;             // icpmi_loop_set_robust (0: off)
+    double gicp_epsilon = 0.0;           // icpmi_loop_set_gicp (0: off; never on together with robust_kind)
     double robust_scale = 0.0;
     std::vector<double> last_weights;    // per result of the last detect its weight sum (-1: the weights were off)
     double info_sigma = 0.0, info_floor_r = 0.0, info_floor_t = 0.0;   // icpmi_loop_set_information (sigma 0: off)
@@ -6225,6 +6251,8 @@ int icpmi_loop_detect(icpmi_loop *L, icpmi_loop_result *out, int64_t cap, int64_
     const bool gated = L->gate > 0.0;
     const int32_t robust = L->robust_kind;
     const double robust_ks = robust == ICPMI_ROBUST_GEMAN_MCCLURE ? L->robust_scale * L->robust_scale : L->robust_scale;
+    const bool gicp = L->gicp_epsilon > 0.0; // (plane-to-plane verifications: the small form, behind the loop's gate)
+    const icpmi_gicp gicp_rule{L->gicp_epsilon, gated ? L->gate : 0.0, ICPMI_GICP_FORM_SMALL};
     const int64_t E = (int64_t)L->frames.size();
     if (E < 2) return ICPMI_OK; // :69
     Range range("icpmi:loop_detect");
@@ -6318,9 +6346,10 @@ int icpmi_loop_detect(icpmi_loop *L, icpmi_loop_result *out, int64_t cap, int64_
             if (r == ICPMI_OK) r = check_common(c);
             gates[k] = GateRun{L->gate * L->gate, 0};
             if (robust) gates[k] = GateRun{gated ? L->gate * L->gate : 1.7976931348623157e308, 0, robust, robust_ks, 0.0};
+            if (gicp && r == ICPMI_OK) r = validate_gicp(c, &gicp_rule, &gates[k]);
             if (r == ICPMI_OK)
                 r = align_staged(c, rows + 3 * (size_t)q0, nq, rows + 3 * (size_t)t0, nt, hipMemcpyDeviceToDevice, &icps[k],
-                                 &res[k], hist.data() + (size_t)k * hcap, hcap, gated || robust ? &gates[k] : nullptr);
+                                 &res[k], hist.data() + (size_t)k * hcap, hcap, gated || robust || gicp ? &gates[k] : nullptr);
             return r;
         }, status);
         if (rc) return rc;
@@ -6336,7 +6365,7 @@ int icpmi_loop_detect(icpmi_loop *L, icpmi_loop_result *out, int64_t cap, int64_
                 o.icp_fitness = r.final_error;
                 results.push_back(o);
                 L->last_shifts.push_back(guess ? shift_of[(size_t)cand.second] : -1);
-                L->last_pairs.push_back(gated ? gates[k].pairs : -1);
+                L->last_pairs.push_back(gated || gicp ? gates[k].pairs : -1);
                 L->last_weights.push_back(robust ? gates[k].weight_sum : -1.0);
                 if (L->info_sigma > 0.0) { // the verification's own normal matrix, on the context that ran it
                     icpmi_normal_matrix nm;
@@ -6385,8 +6414,22 @@ int icpmi_loop_set_robust(icpmi_loop *L, int32_t kind, double scale)
     if (kind != ICPMI_ROBUST_HUBER && kind != ICPMI_ROBUST_GEMAN_MCCLURE)
         return fail(L->map->ctx, ICPMI_ERR_ARG, "kind %d is neither 0 (off), ICPMI_ROBUST_HUBER nor ICPMI_ROBUST_GEMAN_MCCLURE", (int)kind);
     if (!(scale > 0.0) || !std::isfinite(scale)) return fail(L->map->ctx, ICPMI_ERR_ARG, "scale must be finite and > 0");
+    if (L->gicp_epsilon > 0.0) return fail(L->map->ctx, ICPMI_ERR_ARG, "plane-to-plane verifications take no robust weights (icpmi_loop_set_gicp(0) first)");
     L->robust_kind = kind;
     L->robust_scale = scale;
+    return ICPMI_OK;
+}
+
+int icpmi_loop_set_gicp(icpmi_loop *L, double epsilon)
+{
+    if (!L) return ICPMI_ERR_NULL;
+    if (epsilon == 0.0) {
+        L->gicp_epsilon = 0.0;
+        return ICPMI_OK;
+    }
+    if (!(epsilon > 0.0 && epsilon <= 1.0)) return fail(L->map->ctx, ICPMI_ERR_ARG, "epsilon must be 0 (off) or finite with 0 < epsilon <= 1");
+    if (L->robust_kind != 0) return fail(L->map->ctx, ICPMI_ERR_ARG, "plane-to-plane verifications take no robust weights (icpmi_loop_set_robust(0, 0) first)");
+    L->gicp_epsilon = epsilon;
     return ICPMI_OK;
 }
 

@@ -40,7 +40,13 @@
 //
 //   k_reduce_gicp         k_reduce_gated's grid, block, grid-stride loop, wave / LDS reduction and partial-row store around
 //                         a body of its own (icp_gicp_row.inc, included as text: the arithmetic sits in the kernel)
-//   k_finish_step_gated   reused as it is (icp_gated.h);  k_transform likewise.  No small-cloud form.
+//   k_finish_step_gated   reused as it is (icp_gated.h);  k_transform likewise.
+//   k_icp_small_gicp      icp_small_kernel.inc's fourth expansion (ICPMI_SMALL_GATED 1, ICPMI_SMALL_GICP 1): the gated
+//                         small-cloud kernel with step 4's row formed by the same text from the winner it holds.  R is loaded
+//                         with the state at the top of the kernel and m formed per row beside step 1's move; a dropped row
+//                         leaves 28 zeros and count 0.  Its rows are added in the small-cloud kernel's order (a wave's four
+//                         rows, the waves, then k_finish_step_gated's), not k_reduce_gicp's: the two forms agree to rounding,
+//                         not to bits, so the form is the caller's choice (ICPMI_GICP_FORM_SMALL) and off by default.
 #pragma once
 #include "icp_gated.h"
 #include "kernels.h"
@@ -96,5 +102,13 @@ __global__ __launch_bounds__(256) void k_reduce_gicp(const double *__restrict__ 
         partials[(size_t)blockIdx.x * kSumsStride + k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
     }
 }
+
+#define ICPMI_SMALL_ROBUST 0
+#define ICPMI_SMALL_GATED 1
+#define ICPMI_SMALL_GICP 1
+#include "icp_small_kernel.inc"
+#undef ICPMI_SMALL_GICP
+#undef ICPMI_SMALL_GATED
+#undef ICPMI_SMALL_ROBUST
 
 } // namespace icpmi

@@ -3,8 +3,13 @@
 // with ICPMI_SMALL_GATED 1 it is k_icp_small_gated (icp_gated.h): the same kernel with the gate's test on the winner that
 // step 4 already holds, and the kept count in column 28 of the partial row.  With ICPMI_SMALL_ROBUST 1 as well (icp_robust.h)
 // it is k_icp_small_robust: the gated kernel with the row's weight on its terms, the weight in column 28 and the kept
-// count in column 29.  The first two expansions stay token for token what they were.
-#if ICPMI_SMALL_ROBUST
+// count in column 29.  With ICPMI_SMALL_GATED 1 and ICPMI_SMALL_GICP 1 (icp_gicp.h) it is k_icp_small_gicp: the gated
+// kernel with step 4's row formed by icp_gicp_row.inc from the winner it holds and the row's source normal.  The other
+// expansions stay token for token what they were.
+#if ICPMI_SMALL_GICP
+#define ICPMI_SMALL_COLS 29 // the gate's partial row: the 28 plane-to-plane sums and the kept count
+__global__ __launch_bounds__(kSmallThreads) void k_icp_small_gicp(
+#elif ICPMI_SMALL_ROBUST
 #define ICPMI_SMALL_COLS 30 // the 28 weighted sums, the weight sum and the kept count
 __global__ __launch_bounds__(kSmallThreads) void k_icp_small_robust(
 #elif ICPMI_SMALL_GATED
@@ -24,6 +29,9 @@ __global__ __launch_bounds__(kSmallThreads) void k_icp_small(
 #endif
 #if ICPMI_SMALL_ROBUST
     , const int kind, const double ks // the weight and its scale (icp_robust.h: k for Huber, k * k for Geman-McClure)
+#endif
+#if ICPMI_SMALL_GICP
+    , const double *__restrict__ src_nrm, const double c, const double kappa // the source's normals in the caller's row order, 1 - epsilon, 2 * epsilon (icp_gicp.h)
 #endif
     )
 {
@@ -50,6 +58,15 @@ __global__ __launch_bounds__(kSmallThreads) void k_icp_small(
     const int iq = q0 + (lane & 31) < n ? q0 + (lane & 31) : n - 1;
     double x = in[3 * iq], y = in[3 * iq + 1], z = in[3 * iq + 2];
     asm volatile("" : "+v"(x), "+v"(y), "+v"(z)); // (the row loads stay in front of the operand loads and of the test below)
+#if ICPMI_SMALL_GICP
+    // the rotation of IcpState::total as the pass finds it -- the pose the rows have once step 1 has moved them, in the first
+    // pass (T is total itself) and in the later ones (k_finish_step_gated has composed the step into it) -- and the row's
+    // source normal, with the state and the rows: wave-uniform words and one more row load of the same trip
+    const double R00 = st->total[0], R01 = st->total[1], R02 = st->total[2];
+    const double R10 = st->total[4], R11 = st->total[5], R12 = st->total[6];
+    const double R20 = st->total[8], R21 = st->total[9], R22 = st->total[10];
+    const double s0 = src_nrm[3 * iq], s1 = src_nrm[3 * iq + 1], s2 = src_nrm[3 * iq + 2];
+#endif
     int u = wave;
     uint4 b[kSmallUnitTiles];
     if (u < nunits) {
@@ -63,6 +80,12 @@ __global__ __launch_bounds__(kSmallThreads) void k_icp_small(
     const double px = ((x * r00 + y * r01) + z * r02) + t0;
     const double py = ((x * r10 + y * r11) + z * r12) + t1;
     const double pz = ((x * r20 + y * r21) + z * r22) + t2;
+#if ICPMI_SMALL_GICP
+    // (the source normal in the target frame, per row like px: three words live through the coarse pass, R and s are dead)
+#define ICPMI_GICP_PART 1
+#include "icp_gicp_row.inc"
+#undef ICPMI_GICP_PART
+#endif
 
     // 2. coarse records of this wave's units
     f32x16 zero;
@@ -156,6 +179,9 @@ __global__ __launch_bounds__(kSmallThreads) void k_icp_small(
     const int qi = wave * 4 + quarter;
     const bool valid = q0 + qi < n;
     const double qx = __shfl(px, qi, 64), qy = __shfl(py, qi, 64), qz = __shfl(pz, qi, 64);
+#if ICPMI_SMALL_GICP
+    const double qm0 = __shfl(m0, qi, 64), qm1 = __shfl(m1, qi, 64), qm2 = __shfl(m2, qi, 64);
+#endif
     float v1 = kBig, v2 = kBig;
     if (ql < splits) {
         const float2 a = rec[ql * kSmallUnitsPerSplit][qi];
@@ -261,6 +287,24 @@ __global__ __launch_bounds__(kSmallThreads) void k_icp_small(
             have = true;
         }
         if (have) {
+#if ICPMI_SMALL_GICP
+            // the gate's test as below, then the kept row's 29 columns by icp_gicp_row.inc, the text k_reduce_gicp includes: a
+            // dropped row leaves 28 zeros and count 0, a kept row count 1 (column 28)
+            const double e0 = lq0 - qx, e1 = lq1 - qy, e2 = lq2 - qz;
+            double *row = jrow[qi];
+            const bool keep = (e0 * e0 + e1 * e1) + e2 * e2 <= g2;
+            if (!keep) {
+#pragma unroll
+                for (int e = 0; e < 29; ++e) row[e] = 0.0;
+            } else {
+                const double p0 = qx, p1 = qy, p2 = qz, n0 = ln0, n1 = ln1, n2 = ln2, m0 = qm0, m1 = qm1, m2 = qm2;
+#define ICPMI_GICP_PART 2
+#define ICPMI_GICP_COL(k, value) row[k] = (value);
+#include "icp_gicp_row.inc"
+#undef ICPMI_GICP_COL
+#undef ICPMI_GICP_PART
+            }
+#else
             double J[6];
             J[0] = qy * ln2 - qz * ln1; // p x n, icp.hpp:105
             J[1] = qz * ln0 - qx * ln2;
@@ -317,6 +361,7 @@ __global__ __launch_bounds__(kSmallThreads) void k_icp_small(
             row[27] = bb * bb;
 #if ICPMI_SMALL_GATED
             }
+#endif
 #endif
 #endif
         } else if (!valid && ql == 0) {

@@ -104,6 +104,9 @@ struct LoopFacts {
     int cu_count = 256, normal_k = 20;
     bool comm = false;      // the context has a communicator or exchange callbacks
     LoopRule rule = kRuleNone;
+    // plane-to-plane, small form allowed (ICPMI_GICP_FORM_SMALL; kRuleGicp only): at the small-cloud kernel's sizes the pass
+    // runs k_icp_small_gicp.  Off, a plane-to-plane call has the general form at every size.
+    bool gicp_small = false;
     int profile = 0;        // icpmi_options::profile
     // the environment switches, as capi.hip read them (ICPMI_SMALL, ICPMI_SMALL_MAX_SPLITS and ICPMI_FUSE_FINISH once per
     // process, the others at every call)
@@ -160,8 +163,9 @@ inline LoopPlan make_loop_plan(const LoopFacts &f)
     p.fused = f.nn_engine == ICPMI_SEARCH_MFMA_BF16 && f.rule == kRuleNone;
     // the sizes of the small-cloud kernel, whatever runs at them
     const bool small_sizes = !p.sharded && n <= kSmallMaxQueries && f.nn_splits <= f.sw_small_max_splits;
-    // (plane-to-plane rows have no small-cloud form: the gated general path at every size, icp_gicp.h)
-    p.small = small_sizes && n > 0 && small_target(f) && f.rule != kRuleGicp;
+    // (plane-to-plane rows take the small-cloud form only where the caller allows it -- its sums are another order's,
+    // icp_gicp.h -- and otherwise the gated general path at every size)
+    p.small = small_sizes && n > 0 && small_target(f) && (f.rule != kRuleGicp || f.gicp_small);
     p.resolve_waves = resolve_waves(n);
     p.rblocks = p.small ? (n + kSmallQ - 1) / kSmallQ : (p.fused ? resolve_blocks(n) : reduce_blocks(f.cu_count, n));
     // very many partial rows (a resolve workgroup leaves one per 64 queries) are first added in groups of kSumGroup by a
@@ -171,9 +175,11 @@ inline LoopPlan make_loop_plan(const LoopFacts &f)
     p.fin_blocks = p.sum_tree ? p.rblocks2 : p.rblocks;
     // (k_sum_groups adds kNumSums columns, one short of a robust row's; a robust general pass leaves reduce_blocks() rows)
     if (f.rule == kRuleRobust && p.sum_tree && !p.small) p.error = "internal: a robust pass of %d partial rows";
-    // (k_reduce_gicp is the only kernel that forms plane-to-plane sums: a plan that would hand such a pass to the small-cloud
-    // kernel, to a fused resolve or to k_sum_groups is refused here, not launched with another rule's kernel or with none)
-    if (f.rule == kRuleGicp && (p.small || p.fused || p.sum_tree)) p.error = "internal: a plane-to-plane pass of %d partial rows has only the general form";
+    // (k_reduce_gicp and, where allowed, k_icp_small_gicp are the only kernels that form plane-to-plane sums: a plan that would
+    // hand such a pass to the small-cloud kernel unasked, to a fused resolve or to k_sum_groups -- which a small pass never
+    // launches, whatever sum_tree says -- is refused here, not launched with another rule's kernel or with none)
+    if (f.rule == kRuleGicp && (p.small ? !f.gicp_small : (p.fused || p.sum_tree)))
+        p.error = "internal: a plane-to-plane pass of %d partial rows has only the general form";
 
     // Pruned engine: the source is put in Morton order once (a rigid motion keeps neighbours
     // together), so that every block of kCoarseQueries consecutive rows of `cur` is a compact

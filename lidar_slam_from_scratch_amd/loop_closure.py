@@ -32,6 +32,11 @@ attaches to each result the 6 x 6 information matrix of its edge, icpmi_informat
 normal matrix (icpmi_last_normal_matrix) and transform: what PoseGraph.add_loop_closure_information(match, query,
 transform, information) takes.  align / align_many are then passed keyword-only information=(s, sigma_R, sigma_t), and their
 results carry `information`.  0 (the default) passes nothing.
+
+LoopClosureConfig(gicp_epsilon=e) with 0 < e <= 1 (not in the reference) runs the verifications as
+plane-to-plane registrations (icpmi_align_gicp in its small form, capi.GICP_FORM_SMALL), behind the gate above if that is
+set too.  align / align_many are then passed keyword-only gicp=(e,), and their results carry `pairs`, gate or not.  Not
+together with robust_kind (ValueError; the store detector's setter refuses).  0 (the default) passes nothing.
 """
 import ctypes as C
 import weakref
@@ -46,7 +51,8 @@ class LoopClosureConfig:
 
     def __init__(self, frame_gap=50, sc_distance_threshold=0.25, icp_fitness_threshold=0.3, max_candidates=3,
                  yaw_guess=False, max_correspondence_distance=0.0, robust_kind=0, robust_scale=0.0,
-                 information_sigma=0.0, information_floor=(0.0, 0.0)):
+                 information_sigma=0.0, information_floor=(0.0, 0.0), gicp_epsilon=0.0):
+        self.gicp_epsilon = gicp_epsilon
         self.information_sigma = information_sigma
         self.information_floor = information_floor
         self.yaw_guess = yaw_guess
@@ -61,7 +67,7 @@ class LoopClosureConfig:
 
 class LoopClosureResult:
     """loop_closure.hpp:25-31; sector_shift: the column shift the verification started from (None: yaw_guess off);
-    pairs: the rows the verification's last pass kept (None: no correspondence-distance gate); weight_sum: that pass's
+    pairs: the rows the verification's last pass kept (None: neither a correspondence-distance gate nor gicp_epsilon); weight_sum: that pass's
     weight sum (None: no robust weights); information: the edge's 6 x 6 information matrix (None: information_sigma off)"""
 
     def __init__(self, query_frame, match_frame, transform, scan_context_distance, icp_fitness, sector_shift=None,
@@ -92,24 +98,28 @@ class GpuBackend:
         return self.ctx.scan_context_distances_shift(query_desc, hist_descs)
 
     def align(self, source, target, max_iterations, tolerance, *, initial_transform=None, max_distance=None, robust=None,
-              information=None):
-        if initial_transform is None and max_distance is None and robust is None and information is None:
+              information=None, gicp=None):
+        if initial_transform is None and max_distance is None and robust is None and information is None and gicp is None:
             from .odometry import gpu_align
             return gpu_align(self.ctx)(source, target, max_iterations, tolerance)
         return self.align_many(source, [target], max_iterations, tolerance,
                                initial_transforms=None if initial_transform is None else [initial_transform],
-                               max_distance=max_distance, robust=robust, information=information)[0]
+                               max_distance=max_distance, robust=robust, information=information, gicp=gicp)[0]
 
     def align_many(self, source, targets, max_iterations, tolerance, *, initial_transforms=None, max_distance=None,
-                   robust=None, information=None):
+                   robust=None, information=None, gicp=None):
         """The verifications of one detect() side by side on the GPU (icpmi_align_batch): same results as
         align() one after the other.  initial_transforms: one 4 x 4 per target (None: the identity for all).
         max_distance: the correspondence-distance gate (icpmi_align_gated_batch; None: none); the results then carry
         `pairs`.  robust: (kind, scale), the row weights (icpmi_align_robust_batch, behind max_distance if that is given
         too; None: none); the results then carry `weight_sum` as well.  information: (sigma, floor sigma_R, floor sigma_t);
         the results then carry `information`, capi.information_from_icp of problem k's normal matrix (None where its
-        last pass kept no row: such a result has an infinite final_error and is never accepted)."""
+        last pass kept no row: such a result has an infinite final_error and is never accepted).  gicp: (epsilon,), the
+        plane-to-plane cost in its small form (icpmi_align_gicp_batch with capi.GICP_FORM_SMALL, behind max_distance if
+        that is given too; None: point-to-plane; not with robust); the results then carry `pairs`, gate or not."""
         from . import capi
+        if gicp is not None and robust is not None:
+            raise ValueError("gicp= and robust= exclude each other: the plane-to-plane rows carry no robust weights")
 
         class _R:
             pass
@@ -119,7 +129,11 @@ class GpuBackend:
             cfg = [capi.Context.make_config(max_iterations=max_iterations, tolerance=tolerance, initial_transform=T)
                    for T in initial_transforms]
         out = []
-        if robust is not None:
+        if gicp is not None:
+            rule = capi.as_gicp((float(gicp[0]), 0.0 if max_distance is None else float(max_distance), True))
+            runs = [(res, int(info.pairs), None) for res, _hist, info in
+                    self.ctx.align_gicp_batch([source] * len(targets), targets, cfg, rule)]
+        elif robust is not None:
             rule = capi.as_robust((robust[0], robust[1], 0.0 if max_distance is None else float(max_distance)))
             runs = [(res, int(info.pairs) if max_distance is not None else None, float(info.weight_sum)) for res, _hist, info in
                     self.ctx.align_robust_batch([source] * len(targets), targets, cfg, rule)]
@@ -191,6 +205,12 @@ class LoopClosureDetector:
         gated = gate > 0.0
         if robust:
             gkw["robust"] = (kind, float(self.config.robust_scale))
+        gicp = float(getattr(self.config, "gicp_epsilon", 0.0) or 0.0)
+        if gicp != 0.0:
+            if robust:
+                raise ValueError("gicp_epsilon and robust_kind exclude each other")
+            gkw["gicp"] = (gicp,)
+            gated = True   # (the results carry the kept rows, gate or not)
         info_sigma = float(getattr(self.config, "information_sigma", 0.0) or 0.0)
         if info_sigma > 0.0:
             floor = getattr(self.config, "information_floor", (0.0, 0.0))
@@ -255,6 +275,17 @@ class StoreLoopClosureDetector:
         h = C.c_void_p()
         ctx._check(self._lib.icpmi_loop_create(store._h, C.byref(c), C.byref(h)))
         self._h = h
+        try:
+            self._configure(ctx, h)
+        except Exception:
+            self.close()               # (a setter refused: the handle goes now, not when the object is collected -- after its map)
+            raise
+        for owner in (ctx, store):     # Context.close() and store.close() destroy it before the map
+            if not hasattr(owner, "_loops"):
+                owner._loops = weakref.WeakSet()
+            owner._loops.add(self)
+
+    def _configure(self, ctx, h):
         if getattr(self.config, "yaw_guess", False):
             ctx._check(self._lib.icpmi_loop_set_yaw_guess(h, 1))
         self._gated = float(getattr(self.config, "max_correspondence_distance", 0.0) or 0.0) > 0.0
@@ -263,15 +294,14 @@ class StoreLoopClosureDetector:
         self._robust = int(getattr(self.config, "robust_kind", 0) or 0) != 0
         if self._robust:
             ctx._check(self._lib.icpmi_loop_set_robust(h, int(self.config.robust_kind), float(self.config.robust_scale)))
+        self._gicp = float(getattr(self.config, "gicp_epsilon", 0.0) or 0.0) != 0.0
+        if self._gicp:
+            ctx._check(self._lib.icpmi_loop_set_gicp(h, float(self.config.gicp_epsilon)))
         self._information = float(getattr(self.config, "information_sigma", 0.0) or 0.0) > 0.0
         if self._information:
             floor = getattr(self.config, "information_floor", (0.0, 0.0))
             ctx._check(self._lib.icpmi_loop_set_information(h, float(self.config.information_sigma), float(floor[0]),
                                                             float(floor[1])))
-        for owner in (ctx, store):     # Context.close() and store.close() destroy it before the map
-            if not hasattr(owner, "_loops"):
-                owner._loops = weakref.WeakSet()
-            owner._loops.add(self)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -289,6 +319,11 @@ class StoreLoopClosureDetector:
         """icpmi_loop_set_robust: the verifications' row weights from the next detect on (kind 0: off)"""
         self.ctx._check(self._lib.icpmi_loop_set_robust(self._h, int(kind), float(scale)))
         self._robust = int(kind) != 0
+
+    def set_gicp(self, epsilon):
+        """icpmi_loop_set_gicp: plane-to-plane verifications (the small form) from the next detect on (0: off)"""
+        self.ctx._check(self._lib.icpmi_loop_set_gicp(self._h, float(epsilon)))
+        self._gicp = float(epsilon) != 0.0
 
     def set_information(self, sigma, floor_rotation_sigma=0.0, floor_translation_sigma=0.0):
         """icpmi_loop_set_information: each result's edge information from the next detect on (sigma 0: off)"""
@@ -330,7 +365,7 @@ class StoreLoopClosureDetector:
             self.ctx._check(self._lib.icpmi_loop_last_shifts(self._h, sh, n.value, C.byref(m)))
             shifts = [int(v) for v in sh[:m.value]]
         pairs = [None] * n.value
-        if self._gated:
+        if self._gated or self._gicp:
             pr = (C.c_int64 * max(n.value, 1))()
             m = C.c_int64(0)
             self.ctx._check(self._lib.icpmi_loop_last_pairs(self._h, pr, n.value, C.byref(m)))

@@ -69,8 +69,10 @@ def gpu_align(ctx, *, robust=None, gicp=None):
     """Adapter: capi.Context -> the `align` callable above.  robust: a capi.Robust, or (kind, scale[, max_distance]) --
     the registrations run under those row weights (icpmi_align_robust; None: none) and their results carry `weight_sum`
     and `pairs`.  final_error is then the WEIGHTED RMS, which reads lower than the plain one against the caller's
-    `> 1.0`.  gicp: a capi.Gicp, or (epsilon[, max_distance]) -- the registrations minimise the plane-to-plane cost
-    (icpmi_align_gicp; None: point-to-plane) and their results carry `pairs`; not together with `robust` (ValueError)."""
+    `> 1.0`.  gicp: a capi.Gicp, or (epsilon[, max_distance[, small]]) -- the registrations minimise the plane-to-plane cost
+    (icpmi_align_gicp; None: point-to-plane) and their results carry `pairs`; with `small` (capi.GICP_FORM_SMALL) a pass
+    is one kernel at the small-cloud kernel's sizes, to rounding the general path's result; not together with `robust`
+    (ValueError)."""
     from . import capi
     if robust is not None and gicp is not None:
         raise ValueError("robust= and gicp= exclude each other: the plane-to-plane rows carry no robust weights")

@@ -56,7 +56,7 @@ def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, po
              loop_on_device=False, raycast=False, counts=False, live=False, loop_yaw_guess=False, loop_gate=None,
              ground=None, odom_robust=None, loop_robust=None, odom_local_map=None, loop_edge_loss=None,
              edge_information=None, information_floor=(1.0, 10.0), closure_gate=None, deskew=None, deskew_voxel=0.5, odom_gicp=None,
-             static_map=None):
+             static_map=None, loop_gicp=None):
     """frames: sequence of N x 3 fp64 clouds (already downsampled).  Returns a SlamRun.  global_map: an object with
     add_frame, recent_clouds and finish (None: no map is built); grid: its occupancy grid config (None: defaults).
     loop_on_device: the detector is loop_closure.StoreLoopClosureDetector over global_map (a global_map.GlobalMap),
@@ -84,6 +84,9 @@ def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, po
     caller's, with odom_robust and with odom_local_map (whose registrations have no plane-to-plane form).
     loop_robust: (kind, scale) (None: none); the detector's verifications run under those row weights
     (LoopClosureConfig.robust_kind / robust_scale), behind loop_gate if that is given too.
+    loop_gicp: epsilon (None: none); the detector's verifications are plane-to-plane registrations in their small form
+    (LoopClosureConfig.gicp_epsilon; not in the reference node), behind loop_gate if that is given too.  Together with
+    loop_robust it raises ValueError.
     odom_local_map: a local_map.LocalMapConfig (None: frame-to-frame, as the reference node); each odometry factor's
     delta and final_error come from scan-to-local-map odometry (odometry.LocalMapOdometry; not in the reference node).
     The local map lives in its own odometry frame and is never touched by optimize: the factor is pose_{k-1}^-1 . pose_k
@@ -122,6 +125,8 @@ def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, po
         raise ValueError("loop_backend and loop_on_device=True both choose the detector")
     if align is not None and odom_robust is not None:
         raise ValueError("odom_robust configures the default align; pass a robust align of your own instead")
+    if loop_gicp is not None and loop_robust is not None:
+        raise ValueError("loop_gicp and loop_robust exclude each other: the plane-to-plane rows carry no robust weights")
     if odom_gicp is not None and (align is not None or odom_robust is not None or odom_local_map is not None):
         raise ValueError("odom_gicp configures the default align; it does not combine with an align of the caller's, "
                          "odom_robust or odom_local_map")
@@ -158,6 +163,8 @@ def run_slam(frames, ctx, max_iterations=50, tolerance=1e-6, min_points=1000, po
         loop_config.max_correspondence_distance = float(loop_gate)
     if loop_robust is not None:
         loop_config.robust_kind, loop_config.robust_scale = int(loop_robust[0]), float(loop_robust[1])
+    if loop_gicp is not None:
+        loop_config.gicp_epsilon = float(loop_gicp)
     if info_args is not None:
         loop_config.information_sigma, loop_config.information_floor = info_args[0], info_args[1:]
     if loop_on_device:

@@ -402,20 +402,22 @@ def _robust_batch(ctx, env):
 # Plane-to-plane registrations (icp_gicp.h): the source's search structure and normals are built in front of the target's,
 # in the buffers every other call's target uses -- what a used context could leak into, and out of.  (No `reg`: their
 # plan is one form at every size, kRuleGicp, which tests/test_gicp_header.py holds; the paths' table above is the three
-# older rules'.)
+# older rules'.  The small form, ICPMI_GICP_FORM_SMALL, runs the small-cloud kernel's plane-to-plane expansion on the
+# sorted normals and partial rows the gated small calls use: gicp_small_1001 and one problem of gicp_batch_2.)
 GICP_RULE = (1e-3, GATE_RC)
+GICP_RULE_SMALL = (1e-3, GATE_RC, True)
 
 
-def _make_gicp(name, form, src, tgt, iters):
+def _make_gicp(name, form, src, tgt, iters, rule=GICP_RULE):
     @op(name, max(inputs()[src].shape[0], inputs()[tgt].shape[0]), "registration", (form, "last_normal_matrix"))
     def run(ctx, env):
         s, t = env.I[src], env.I[tgt]
         cfg = _capi().Context.make_config(**_cfg_kw(iters))
         if form == "align_gicp":
-            res, hist, info = ctx.align_gicp(s, t, cfg, GICP_RULE)
+            res, hist, info = ctx.align_gicp(s, t, cfg, rule)
         else:
             ds, dt = env.dev(src), env.dev(tgt)
-            res, hist, info = ctx.align_gicp_device(ds.data_ptr(), ds.shape[0], dt.data_ptr(), dt.shape[0], cfg, GICP_RULE)
+            res, hist, info = ctx.align_gicp_device(ds.data_ptr(), ds.shape[0], dt.data_ptr(), dt.shape[0], cfg, rule)
         return _reg_out(ctx, s.shape[0], res, hist, [info], ruled=True)
 
     @check(name)
@@ -430,6 +432,25 @@ def _make_gicp(name, form, src, tgt, iters):
 
 _make_gicp("gicp_1001", "align_gicp", "rc_s1001", "rc_t1500", 3)
 _make_gicp("gicp_5000", "align_gicp_device", "u_s5000a", "u_t16385", 3)
+_make_gicp("gicp_small_1001", "align_gicp", "rc_s1001", "rc_t1500", 3, GICP_RULE_SMALL)
+
+
+@op("gicp_batch_2", 4500, "registration", ("align_gicp_batch", "last_normal_matrix"))
+def _gicp_batch(ctx, env):
+    cfg = _capi().Context.make_config(**_cfg_kw(3))
+    rules = [GICP_RULE_SMALL, GICP_RULE]                 # (one problem in each form)
+    return _batch_out(ctx, ctx.align_gicp_batch([env.I[s] for s, _ in BATCH[1:]], [env.I[t] for _, t in BATCH[1:]], cfg, rules))
+
+
+@check("gicp_batch_2")
+def _gicp_batch_check(env, out, orc):
+    import gicp_ref
+    kw = _cfg_kw(3)
+    for (s, t), (res, hist, info) in zip(BATCH[1:], out.raw["runs"]):
+        ref = gicp_ref.gicp_icp(env.I[s], env.I[t], GICP_RULE[0], GICP_RULE[1], kw["max_iterations"], kw.get("tolerance", 1e-6),
+                                kw.get("min_error", 1e-9), orc=orc)
+        assert info.pairs == ref.pairs, (s, info.pairs, ref.pairs)
+        check_against(res, hist, ref.transformation, ref.converged, ref.num_iterations, ref.error_history)
 
 
 # ---- primitives
@@ -921,11 +942,11 @@ def loop_store_setup(ctx, env):
     return gm, det, [env.I["f16_%d" % f] for f in range(5)] + [env.I["f16_revisit"]]
 
 
-@thread("loop_store", ("add_frame", "detect", "descriptor", "size", "set_gate", "set_robust", "set_information", "clear",
-                       "close"))
+@thread("loop_store", ("add_frame", "detect", "descriptor", "size", "set_gate", "set_robust", "set_gicp", "set_information",
+                       "clear", "close"))
 def _loop_store(ctx, env):
-    """a detector over a map of its own, under a gate, a robust rule, the yaw guess and edge information; the last frame
-    revisits the first one's place with another heading"""
+    """a detector over a map of its own, under a gate, a robust rule, the yaw guess and edge information, then with
+    plane-to-plane verifications behind the gate; the last frame revisits the first one's place with another heading"""
     gm, det, clouds = loop_store_setup(ctx, env)
     try:
         for k, cloud in enumerate(clouds):
@@ -933,8 +954,12 @@ def _loop_store(ctx, env):
             det.add_frame(k, k)
             found = det.detect()
             yield dig(len(found), [_closure_parts(r) for r in found], det.descriptor(k), det.size())
-        det.set_gate(0.0)
         det.set_robust(0)
+        det.set_gicp(1e-3)
+        found = det.detect()
+        yield dig(len(found), [_closure_parts(r) for r in found])
+        det.set_gicp(0.0)
+        det.set_gate(0.0)
         det.set_information(0.0)
         found = det.detect()
         yield dig(len(found), [_closure_parts(r) for r in found])

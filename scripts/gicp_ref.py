@@ -47,9 +47,14 @@ The sums are formed in numpy, row after row in index order (a cumulative sum, no
     gicp_sums(p, q, n, m, c, kappa)          their sums, row after row
     gicp_icp(source, target, epsilon, max_distance=0.0, ...)
     gicp_align(epsilon, max_distance)        gicp_icp as run_odometry's `align` (robust_icp_ref.odometry_ate)
+    GicpOracleBackend(epsilon, max_distance) gicp_icp behind loop_yaw_ref.YawLoopClosureDetector's backend interface
+
+The library's small form (ICPMI_GICP_FORM_SMALL: k_icp_small_gicp) forms these rows word for word and adds them in another
+order; it is held to this restatement within the same bounds as the general path.
 
 Run as a script it prints DESIGN 7.16's accuracy table: point-to-plane, Huber 0.1 m and plane-to-plane on the C2 pair, on
-the cars pair behind 2 m and over frames 0..11 of the default drive."""
+the cars pair behind 2 m and over frames 0..11 of the default drive, then the L12 loop-verification row: Huber 0.1 m and
+plane-to-plane behind the 2 m gate."""
 import math
 import os
 import sys
@@ -62,6 +67,7 @@ for _p in (_ROOT, os.path.join(_ROOT, "scripts")):
         sys.path.insert(0, _p)
 
 import gated_icp_ref as gr  # noqa: E402
+import loop_yaw_ref as yr  # noqa: E402
 
 DBL_MAX = sys.float_info.max
 EPSILON_DEFAULT = 1e-3        # ICPMI_GICP_EPSILON_DEFAULT
@@ -235,6 +241,55 @@ def gicp_align(epsilon=EPSILON_DEFAULT, max_distance=0.0, orc=None):
     return lambda s, t, it, tol: gicp_icp(s, t, epsilon, max_distance, it, tol, orc=orc)
 
 
+class GicpOracleBackend(yr.OracleBackend):
+    """gicp_icp behind YawLoopClosureDetector's backend interface (robust_icp_ref.RobustOracleBackend's shape).  Every
+    verification is kept in `runs`, in call order; run_of(closure) is the one a closure came from (the detector hands its
+    transform array on as it is).  A cloud's tree and normals are formed once and kept by identity: as a target's, and
+    -- the same normals -- as a source's."""
+
+    def __init__(self, epsilon=EPSILON_DEFAULT, max_distance=0.0, orc=None):
+        super().__init__(orc)
+        check_rule(float(epsilon), float(max_distance))
+        self.epsilon, self.max_distance = float(epsilon), float(max_distance)
+        self.runs = []
+        self._normals = {}                                            # per cloud (by identity): (cloud, tree, normals)
+
+    def _cloud(self, c):
+        key = id(c)
+        if key not in self._normals:
+            tree = self.orc.KDTree(c)
+            self._normals[key] = (c, tree, self.orc.estimate_normals(c, tree, NORMAL_K))
+        return self._normals[key]
+
+    def align(self, s, t, max_iterations, tolerance, *, initial_transform=None):
+        _, _stree, snrm = self._cloud(s)
+        _, tree, nrm = self._cloud(t)
+        r = gicp_icp(s, t, self.epsilon, self.max_distance, max_iterations, tolerance, 1e-9, initial_transform, orc=self.orc,
+                     normals=nrm, tree=tree, source_normals=snrm)
+        self.iterations.append(r.num_iterations)
+        self.runs.append(r)
+        return r
+
+    def run_of(self, closure):
+        for r in self.runs:
+            if r.transformation is closure.transform:
+                return r
+        raise KeyError("not a closure of this backend")
+
+    def min_margins(self):
+        """-> (stopping margin, gate margin) over every verification"""
+        return (min((r.stop_margin for r in self.runs), default=math.inf),
+                min((r.gate_margin for r in self.runs), default=math.inf))
+
+
+def l12_run(backend):
+    """the L12 drive (gated_icp_ref.l12_scans, l12_config) through `backend` -> (closures, worst error from truth, m)"""
+    import robust_icp_ref as rr
+    poses, labels, clouds = gr.l12_scans()
+    found = gr.run_detector(yr.YawLoopClosureDetector(backend, gr.l12_config()), clouds, labels)
+    return found, rr.l12_worst(found, poses, labels)
+
+
 def subsample_pair(n_src=1001, n_tgt=1500, seed=7):
     """-> (source, target, truth): a seeded subsample of synth.c2_lidar_pair(), rows in index order"""
     from lidar_slam_from_scratch_amd import synth
@@ -303,3 +358,11 @@ if __name__ == "__main__":
     for label, align in (("point-to-plane", rr.oracle_align(orc)), ("Huber 0.1", rr.robust_align(rr.HUBER, rr.HUBER_SCALE, orc=orc)),
                          ("plane-to-plane", gicp_align(orc=orc))):
         print("drive 0..%d %-15s ATE rms %.3f m, end %.3f m, %d passes" % ((n - 1, label) + rr.odometry_ate(frames, poses, align)))
+    for label, backend in (("Huber 0.1 m, 2 m gate", rr.RobustOracleBackend(rr.HUBER, rr.HUBER_SCALE, gr.L12_GATE, orc)),
+                           ("plane-to-plane eps = 1e-3, 2 m gate", GicpOracleBackend(EPSILON_DEFAULT, gr.L12_GATE, orc))):
+        found, worst = l12_run(backend)
+        stop, gate = backend.min_margins()
+        print("L12 %-36s verifications %d, closures %d, worst %.4f m, passes %d, largest final_error %.4f, kept %s, "
+              "margins %.2e / %.2e m^2"
+              % (label, len(backend.runs), len(found), worst, sum(r.num_iterations for r in backend.runs),
+                 max(r.final_error for r in backend.runs), [backend.run_of(c).pairs for c in found], stop, gate))
